@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- frames/sec of the CubemapSLAM hot path (remap + ORB extract + matching + pose optimisation + local BA) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps (the headline pass below), writes the last step's outputs if --dump-outputs is given and
+prints the JSON line.  --full adds everything else this file measures or checks, after the headline pass: the extra timed passes
+(--xxx-steps), the Python step loop's figure, the local-BA check against the CPU oracle (--verify-windows), the CPU baseline (--cpu-frames),
+one local-BA call and the closed loop (--closed-loop-frames), and the runs confined to 2 / 4 host cores (--confined-steps, before the GPU is
+touched).  Without --full those options are ignored.
+
+--dump-outputs DIR: after the timed steps, what the headline pass's last step computed, as its caller holds it, as DIR/<name>.npy (float32,
+poses float64, under 64 MB): the pose optimisation of every frame, key points / descriptors / matches of a fixed sample of the frames, and the
+mapping side's CreateNewMapPoints and Fuse results.  The local-BA windows' estimates stay inside the C++ step driver (its read-back arrays);
+--full's --verify-windows holds them to the oracle.  The inputs are seeded: the same arguments give the same inputs in every run.
 
 N > 1: bench.py starts its N ranks itself (one process per GPU through torch.distributed.run, rendezvous on 127.0.0.1) unless it
 already runs under a launcher (RANK / WORLD_SIZE in the environment, e.g. the driver's own torch.distributed.run line); it fails if
@@ -29,13 +40,13 @@ One step = one batch of frames through, all on the device:
         windows of step s + 1 while step s runs and reads back / destroys the windows of step s -- all of it inside the timed region.
 Two frame batches (different streams) alternate from step to step, so no step replays the previous step's inputs.
 
-`value` is measured with both batches resident in HBM (a device-to-device copy into the staging buffer opens the step).  A second
-timed pass streams the same batches from pinned host memory (cms_frames_upload_async: the copy of step s + 1 overlaps step s) and
+`value` is measured with both batches resident in HBM (a device-to-device copy into the staging buffer opens the step).  With --full a
+second timed pass streams the same batches from pinned host memory (cms_frames_upload_async: the copy of step s + 1 overlaps step s) and
 is reported as `config.with_input_streaming`.
 
-After the timed passes, outside any timed region: the local-BA results of a sample of windows are compared with the CPU oracle
-(iterations of both stages, outlier flags, updates), the CPU baseline is taken (rank 0, N = 1 only) and ONE JSON line is printed
-(rank 0) with `roofline` (dominant kernel of the step, HIP-event timing inside the timed region) and `cpu_baseline`.
+After the timed passes, outside any timed region, with --full: the local-BA results of a sample of windows are compared with the CPU
+oracle (iterations of both stages, outlier flags, updates) and the CPU baseline is taken (rank 0, N = 1 only).  ONE JSON line is printed
+(rank 0) with `roofline` (dominant kernel of the step, HIP-event timing inside the timed region) and `cpu_baseline` (null without --full).
 """
 import argparse
 import collections
@@ -116,26 +127,38 @@ def parse_args(argv=None):
     ap.add_argument("--pose-edges", type=int, default=600, help="matched map points per frame for the pose-only optimisation")
     ap.add_argument("--save-trajectory", default="", help="rank 0 writes the gathered trajectory of the last step here (TUM format)")
     ap.add_argument("--force-gather", action="store_true", help="run the trajectory gather code path even with one rank (self-test)")
-    ap.add_argument("--cpu-frames", type=int, default=24, help="frames of the CPU-oracle baseline sample (0 = skip)")
-    ap.add_argument("--no-streaming-pass", action="store_true", help="skip the second timed pass with inputs streamed from pinned host memory")
-    ap.add_argument("--verify-windows", type=int, default=8, help="local-BA windows whose estimates are checked against the CPU oracle after the timed region (rank 0); "
+    ap.add_argument("--cpu-frames", type=int, default=24, help="--full: frames of the CPU-oracle baseline sample (0 = skip)")
+    ap.add_argument("--no-streaming-pass", action="store_true", help="--full: skip the second timed pass with inputs streamed from pinned host memory")
+    ap.add_argument("--verify-windows", type=int, default=8, help="--full: local-BA windows whose estimates are checked against the CPU oracle after the timed region (rank 0); "
                     "the iteration counts and outlier counts of ALL windows of that step are checked as well (0 = no check)")
     ap.add_argument("--ba-views", choices=("track", "random"), default="track", help="how the synthetic windows' observations are drawn (synth.ba_problem)")
     ap.add_argument("--window-threads", type=int, default=0, help="host threads that build / read back / destroy local-BA windows (0 = this rank's share of the "
                     "node's usable cores minus two, between 4 and 32: host_budget())")
-    ap.add_argument("--extract-only-steps", type=int, default=10, help="steps of the extra pass that runs the frame path alone (config.extract_only; 0 = skip)")
-    ap.add_argument("--random-views-steps", type=int, default=8, help="steps of the extra pass on windows with RANDOM views (no signature runs: round 2's windows), "
+    ap.add_argument("--extract-only-steps", type=int, default=10, help="--full: steps of the extra pass that runs the frame path alone (config.extract_only; 0 = skip)")
+    ap.add_argument("--random-views-steps", type=int, default=8, help="--full: steps of the extra pass on windows with RANDOM views (no signature runs: round 2's windows), "
                     "reported as config.ba_views_random next to the headline (0 = skip)")
-    ap.add_argument("--optimise-only-steps", type=int, default=10, help="steps of the extra pass that keeps the windows and only resets them between steps "
+    ap.add_argument("--optimise-only-steps", type=int, default=10, help="--full: steps of the extra pass that keeps the windows and only resets them between steps "
                     "(round 2's headline, reported as config.optimise_only; 0 = skip)")
-    ap.add_argument("--unpipelined-steps", type=int, default=10, help="steps of the loop that waits for every step's own mapping side (config.unpipelined; 0 = skip)")
-    ap.add_argument("--deterministic-steps", type=int, default=6, help="steps of the extra pass with cms_ba_set_deterministic(1) (config.deterministic; 0 = skip)")
-    ap.add_argument("--mapping-only-steps", type=int, default=6, help="steps of the mapping side alone (CreateNewMapPoints + local BA, no frame path): config.mapping_only, and the Schur kernel's launch time without the frame path next to it in roofline (0 = skip)")
-    ap.add_argument("--closed-loop-frames", type=int, default=24, help="frames of the single-stream closed-loop run reported next to the batch figure (rank 0, N = 1; 0 = skip)")
-    ap.add_argument("--confined-steps", type=int, default=40, help="steps of the two child runs of the same step with the process confined to 2 and to 4 host cores "
+    ap.add_argument("--unpipelined-steps", type=int, default=10, help="--full: steps of the loop that waits for every step's own mapping side (config.unpipelined; 0 = skip)")
+    ap.add_argument("--deterministic-steps", type=int, default=6, help="--full: steps of the extra pass with cms_ba_set_deterministic(1) (config.deterministic; 0 = skip)")
+    ap.add_argument("--mapping-only-steps", type=int, default=6, help="--full: steps of the mapping side alone (CreateNewMapPoints + local BA, no frame path): config.mapping_only, and the Schur kernel's launch time without the frame path next to it in roofline (0 = skip)")
+    ap.add_argument("--closed-loop-frames", type=int, default=24, help="--full: frames of the single-stream closed-loop run reported next to the batch figure (rank 0, N = 1; 0 = skip)")
+    ap.add_argument("--confined-steps", type=int, default=40, help="--full: steps of the two child runs of the same step with the process confined to 2 and to 4 host cores "
                     "(config.host.confined_2_cores / _4_cores: what a rank gets when eight of them share a 16-core box; rank 0, N = 1; 0 = skip)")
     ap.add_argument("--launcher-selftest", action="store_true", help="no GPU work: every rank reports its rendezvous (gloo) and exits")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also run the extra passes, checks and baselines (the options marked --full); a plain run times the headline pass only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
+    args = ap.parse_args(argv)
+    if not args.full:
+        for k in FULL_ONLY:
+            setattr(args, k, 0)
+        args.no_streaming_pass = True
+    return args
+
+
+# what a plain run skips: the extra passes, checks and baselines (their options apply with --full)
+FULL_ONLY = ("cpu_frames", "verify_windows", "extract_only_steps", "random_views_steps", "optimise_only_steps", "unpipelined_steps", "deterministic_steps",
+             "mapping_only_steps", "closed_loop_frames", "confined_steps")
 
 
 def _free_port():
@@ -752,7 +775,7 @@ def main():
         pskip, skip = pin(np.concatenate([j[2] for j in jobs_g2]).astype(np.uint8))
         n_mp = len(skip)
         pbi, bi = pin(np.zeros(n_mp, np.int32)); pbd, bd = pin(np.zeros(n_mp, np.int32))
-        fuse_prep.append(dict(keep=(cols, slots, jset, set_off, pskip, pbi, pbd), njobs=len(jobs_g2), n_mp=n_mp, n_set_points=int(set_off[-1]), best_idx=bi,
+        fuse_prep.append(dict(keep=(cols, slots, jset, set_off, pskip, pbi, pbd), njobs=len(jobs_g2), n_mp=n_mp, n_set_points=int(set_off[-1]), best_idx=bi, best_dist=bd,
                               args=(len(sets_g), api._p(set_off)) + tuple(api._p(v) for _, v in cols) + (len(jobs_g2), api._p(slots), api._p(jset), api._p(skip),
                                                                                                           C_.c_float(3.0), api._p(bi), api._p(bd))))
     store_lock = [threading.Lock() for _ in range(n_grp)]         # a store's calls one at a time (its mapping thread; the optimise-only pass's worker)
@@ -1256,6 +1279,42 @@ def main():
     else:
         dt, stage_ms, ba_ms_per_step, schur_prof = timed(False)
     host["host_cores_used"] = round((time.process_time() - cpu_t0) / max(dt, 1e-9), 2)      # CPU seconds of this process per second of the timed pass (warm-up included in both)
+
+    def dump_outputs(out_dir):
+        """the headline pass's last step, where its caller finds the results: the pose optimisation of every frame (cms_pose_fetch), key points,
+        descriptors and both searches' matches of a fixed sample of the step's frames (the frame context and the step's frame set on the device), and
+        the last CreateNewMapPoints / Fuse results of every window group (the host arrays those calls write).  Must run before any other pass."""
+        S = sets[(args.warmup + args.steps - 1) % 2]
+        ninl, poses, outl, _ = po.fetch()
+        frames = [ctx.fetch(b) for b in range(B)]
+        pick = np.sort(np.random.default_rng(0).choice(B, min(B, 32), replace=False))
+        kpmp = S.d_kpmp.cpu().numpy().reshape(B, -1)
+        mm_off, mm_match = S.d_mm_mpoff.cpu().numpy(), S.d_mm_match.cpu().numpy()
+        lm_off, lm_match = S.d_lm_mpoff.cpu().numpy(), S.d_lm_i[4].cpu().numpy()
+        kp = np.concatenate([frames[b][0] for b in pick])
+        n_new, pairs, x3d = [], [], []
+        for gi, st_ in enumerate(tri_store):
+            _, (_, _, _, nn_, on_, o1_, o2_, ox_), _ = st_._cnmp
+            for j in range(len(tri_jobs[gi])):
+                n_new.append(nn_[j]); pairs.append(np.stack([on_[j, :nn_[j]], o1_[j, :nn_[j]], o2_[j, :nn_[j]]], 1)); x3d.append(ox_[j, :nn_[j]])
+        out = {"frame_poses": poses, "frame_inliers": ninl, "pose_outlier_flags": np.concatenate(outl), "keypoints_per_frame": [len(f[0]) for f in frames],
+               "sample_frames": pick, "keypoints": np.stack([kp[f] for f in kp.dtype.names], 1),         # x, y, size, angle, response, octave
+               "descriptors": np.concatenate([frames[b][1] for b in pick]),
+               "keypoint_map_points": np.concatenate([kpmp[b, :len(frames[b][0])] for b in pick]),
+               "motion_model_matches": np.concatenate([mm_match[mm_off[b]:mm_off[b + 1]] for b in pick]), "motion_model_matches_per_frame": S.d_mm_n.cpu().numpy(),
+               "local_map_matches": np.concatenate([lm_match[lm_off[b]:lm_off[b + 1]] for b in pick]),
+               "new_map_points_per_key_frame": n_new, "new_map_point_pairs": np.concatenate(pairs), "new_map_points": np.concatenate(x3d),
+               "fuse_best_idx": np.concatenate([fq["best_idx"] for fq in fuse_prep]), "fuse_best_dist": np.concatenate([fq["best_dist"] for fq in fuse_prep])}
+        # (every integer here is far below 2^24: exact in float32)
+        out = {k: np.asarray(v, np.float64 if k == "frame_poses" else np.float32) for k, v in out.items()}
+        total = sum(a.nbytes for a in out.values())
+        if total > 64 << 20:
+            raise SystemExit("bench.py: --dump-outputs would write %.1f MB, more than 64" % (total / 2.0 ** 20))
+        os.makedirs(out_dir, exist_ok=True)
+        for k, a in out.items():
+            np.save(os.path.join(out_dir, k + ".npy"), a)
+    if args.dump_outputs and rank == 0 and not part:
+        dump_outputs(args.dump_outputs)
     host["step_driver"] = ("c++ (cubemapslam_amd/host/batch_driver.cpp: the step's C-ABI calls from C++ threads, no interpreter in the loop)" if cpp is not None
                            else "python (bench.py's own loop; ~25 threads)")
     host_all = [host]
@@ -1295,7 +1354,7 @@ def main():
                             "the step, CreateNewMapPoints' geometry stays consistent.  `minimal` = the same steps with CreateNewMapPoints + local BA only (round 4's step)"}
     create_ms_in_step = acc["create_ms"] / max(acc["create_n"], 1)
     worker_break = {k_: round(v_ / max(worker_ms.get("n", 1), 1), 3) for k_, v_ in worker_ms.items() if k_ != "n"}      # per window group and step
-    if cpp is not None and rank == 0 and world == 1 and os.environ.get("CMS_BENCH_NO_PY_LOOP", "") == "":
+    if args.full and cpp is not None and rank == 0 and world == 1 and os.environ.get("CMS_BENCH_NO_PY_LOOP", "") == "":
         n_py = min(args.steps, 10)
         c0_ = time.process_time()
         dt_p, _, ba_ms_p, _ = timed(False, steps=n_py)

@@ -1,21 +1,27 @@
-"""Reference-held INPUT DATA as test fixtures (build container only: /root/reference does not exist on the GPU box).
+"""Reference-held INPUT DATA as test fixtures, made from a checkout of the reference (the tests read only the committed files).
 
-    python tests/golden/make_reference_fixtures.py
+    python tests/golden/make_reference_fixtures.py REFERENCE_CHECKOUT            write the fixtures
+    python tests/golden/make_reference_fixtures.py REFERENCE_CHECKOUT --check    compare the committed fixtures with the checkout, write nothing
 
 Reads, from the reference checkout,
   * Masks/gray_lafida_cubemap_mask_{450,550,650}.png, Masks/gray_cubemap_{front,left}_mask_650.png -- the cubemap masks ORBextractor culls
-    key points with (ORBExtractor.cpp:887-904; loaded by Examples/cubemap_lafida.cpp / cubemap_fangshan.cpp) -- with Pillow, and
+    key points with (ORBExtractor.cpp:887-904; loaded by Examples/cubemap_lafida.cpp / cubemap_fangshan.cpp) -- with Pillow,
   * Config/{lafida_cam0,front_cam,left_cam}_params.yaml with the product's own reader of the reference's settings format
-    (cubemapslam_amd/host/io_formats.cpp, through libcubemapslam_host.so),
+    (cubemapslam_amd/host/io_formats.cpp, through libcubemapslam_host.so), and
+  * the numbers the product and the oracle take from the reference's text: the rBRIEF test pattern `bit_pattern_31_` (ORBExtractor.cpp:121-379),
+    TH_HIGH / TH_LOW / HISTO_LENGTH (ORBMatcher.cpp:42-44), PATCH_SIZE / HALF_PATCH_SIZE / EDGE_THRESHOLD (ORBExtractor.cpp:43-45), and the
+    chi2 values of the Huber widths and outlier gates of PoseOptimization / LocalBundleAdjustment (Optimizer.cpp:77,300,384,411),
 checks the parsed intrinsics against the constants the synthetic harness carries (cubemapslam_amd/synth.py LAFIDA / FRONT) and writes
 
     tests/golden/reference_masks.npz      the masks, bit-packed rows (1 = non-zero pixel) + their shapes + the set of distinct pixel values
     tests/golden/reference_configs.npz    the parsed values: cms_camera / cms_orb_params bytes, fps, withFisheyeMask, RGB per file
+    tests/golden/reference_constants.npz  the pattern (1024 x int8) and the named constants as numbers
 
 DATA only: pixels and numbers.  No reference source text is stored.
 """
 import ctypes as C
 import os
+import re
 import sys
 
 import numpy as np
@@ -23,7 +29,6 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-REF = "/root/reference"
 
 MASKS = {
     "lafida_450": "Masks/gray_lafida_cubemap_mask_450.png",
@@ -48,12 +53,34 @@ def load_settings(path):
     return cam, orb, float(fps.value), int(wm.value), int(rgb.value)
 
 
-def main():
+def constants(ref):
+    """the numbers the product and the oracle take from the reference's source text"""
+    src = lambda f: open(os.path.join(ref, "src", f)).read()
+    orb = src("ORBExtractor.cpp")
+    i = orb.index("bit_pattern_31_")
+    body = re.sub(r"/\*.*?\*/", "", orb[orb.index("=", i):orb.index("};", i)], flags=re.S)
+    out = {"orb_bit_pattern_31": np.array([int(x) for x in re.findall(r"-?\d+", body)], np.int8)}
+    assert out["orb_bit_pattern_31"].size == 1024
+    for name, f in (("TH_HIGH", "ORBMatcher.cpp"), ("TH_LOW", "ORBMatcher.cpp"), ("HISTO_LENGTH", "ORBMatcher.cpp"), ("PATCH_SIZE", "ORBExtractor.cpp"),
+                    ("HALF_PATCH_SIZE", "ORBExtractor.cpp"), ("EDGE_THRESHOLD", "ORBExtractor.cpp")):
+        m = re.search(r"\b%s\s*=\s*(-?[0-9.]+)" % name, src(f))
+        assert m, (f, name)
+        out[name] = np.float64(m.group(1))
+    opt = src("Optimizer.cpp")
+    # PoseOptimization's Huber width (deltaMono), LocalBundleAdjustment's (thHuberMono) and its outlier gates (e->chi2() > x, both stages)
+    for key, pat in (("deltaMono_sqrt_of", r"deltaMono\s*=\s*sqrt\(([0-9.]+)\)"), ("thHuberMono_sqrt_of", r"thHuberMono\s*=\s*sqrt\(([0-9.]+)\)"),
+                     ("local_ba_chi2_gates", r"\be->chi2\(\)\s*>\s*([0-9.]+)")):
+        out[key] = np.array([float(x) for x in re.findall(pat, opt)], np.float64)
+        assert out[key].size, key
+    return out
+
+
+def extract(ref):
     from PIL import Image
     from cubemapslam_amd import synth
     out_m, out_c = {}, {}
     for key, rel in MASKS.items():
-        im = Image.open(os.path.join(REF, rel))
+        im = Image.open(os.path.join(ref, rel))
         a = np.asarray(im)
         assert a.ndim == 2 and a.dtype == np.uint8 and a.shape[0] == a.shape[1] and a.shape[0] % 3 == 0, (key, a.shape, a.dtype)
         out_m[key + "_bits"] = np.packbits(a != 0, axis=1)
@@ -61,7 +88,7 @@ def main():
         out_m[key + "_values"] = np.unique(a)             # (the cull tests "== 0": only zero / non-zero matters; kept for the record)
         print("%-12s %4d x %4d, %5.1f %% non-zero, values %s" % (key, a.shape[1], a.shape[0], 100.0 * (a != 0).mean(), np.unique(a)[:8]))
     for key, rel in CONFIGS.items():
-        cam, orb, fps, wm, rgb = load_settings(os.path.join(REF, rel))
+        cam, orb, fps, wm, rgb = load_settings(os.path.join(ref, rel))
         out_c[key + "_camera"] = np.frombuffer(bytes(cam), np.uint8).copy()
         out_c[key + "_orb"] = np.frombuffer(bytes(orb), np.uint8).copy()
         out_c[key + "_misc"] = np.array([fps, wm, rgb], np.float64)
@@ -73,11 +100,23 @@ def main():
             assert list(cam.pol)[:len(want["pol"])] == list(want["pol"]), key
             assert (cam.Iw, cam.Ih, cam.fov_deg, orb.nfeatures) == (want["Iw"], want["Ih"], want["fov_deg"], want["nfeatures"]), key
         print("%-12s %d x %d, face %d, nFeatures %d, fov %.0f, fps %.0f, withFisheyeMask %d" % (key, cam.Iw, cam.Ih, cam.face, orb.nfeatures, cam.fov_deg, fps, wm))
-    np.savez_compressed(os.path.join(HERE, "reference_masks.npz"), **out_m)
-    np.savez_compressed(os.path.join(HERE, "reference_configs.npz"), **out_c)
-    for f in ("reference_masks.npz", "reference_configs.npz"):
+    return {"reference_masks.npz": out_m, "reference_configs.npz": out_c, "reference_constants.npz": constants(ref)}
+
+
+def main(argv):
+    if len(argv) not in (1, 2) or (len(argv) == 2 and argv[1] != "--check"):
+        raise SystemExit("usage: make_reference_fixtures.py REFERENCE_CHECKOUT [--check]")
+    fixtures = extract(argv[0])
+    if len(argv) == 2:
+        stale = [f for f, arrs in fixtures.items()
+                 if not os.path.exists(os.path.join(HERE, f)) or sorted(np.load(os.path.join(HERE, f)).files) != sorted(arrs)
+                 or any(not np.array_equal(np.load(os.path.join(HERE, f))[k], v) for k, v in arrs.items())]
+        print("stale: %s" % stale if stale else "the committed fixtures are current")
+        raise SystemExit(1 if stale else 0)
+    for f, arrs in fixtures.items():
+        np.savez_compressed(os.path.join(HERE, f), **arrs)
         print("wrote tests/golden/%s (%d bytes)" % (f, os.path.getsize(os.path.join(HERE, f))))
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

@@ -1,5 +1,5 @@
-"""Reference-held input data committed as fixtures (tests/golden/make_reference_fixtures.py made them in the build container):
-the cubemap masks of /root/reference/Masks and the parsed values of /root/reference/Config/*.yaml.  Data only."""
+"""Reference-held input data committed as fixtures (tests/golden/make_reference_fixtures.py made them from a checkout of the reference):
+the cubemap masks of its Masks/, the parsed values of its Config/*.yaml and the numbers the product takes from its source text.  Data only."""
 import os
 import numpy as np
 
@@ -21,3 +21,9 @@ def reference_config(key):
     """parsed values of Config/<key>_params.yaml: (camera struct bytes, orb params bytes, [fps, withFisheyeMask, RGB])"""
     z = np.load(os.path.join(_G, "reference_configs.npz"))
     return bytes(z[key + "_camera"]), bytes(z[key + "_orb"]), z[key + "_misc"]
+
+
+def reference_constants():
+    """the rBRIEF test pattern (1024 x int8) and the named constants of the reference's source text, as numbers: {name: array}"""
+    z = np.load(os.path.join(_G, "reference_constants.npz"))
+    return {k: z[k] for k in z.files}

@@ -63,3 +63,20 @@ def test_step_waits_for_the_frame_path_and_fetches_the_poses_unconditionally():
     # the gather of the trajectory uses what the fetch returned
     src = ast.unparse(steps[0])
     assert "frame_poses" in src and src.index("po.fetch") < src.index("cdist.gather_trajectory")
+
+
+def test_a_plain_run_times_the_headline_pass_only():
+    """`bench.py --gpus 1 --steps N --warmup W` runs set-up, warm-up and the N timed steps and nothing else: every extra pass, check and baseline
+    is off unless --full is given, and --full keeps their defaults."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2", "--verify-windows", "4"])
+    assert (plain.steps, plain.warmup, plain.full, plain.dump_outputs) == (7, 2, False, "")
+    assert all(getattr(plain, k) == 0 for k in bench.FULL_ONLY) and plain.no_streaming_pass
+    full = bench.parse_args(["--full", "--dump-outputs", "out"])
+    defaults = bench.parse_args(["--full"])
+    assert full.full and full.dump_outputs == "out" and not full.no_streaming_pass
+    assert all(getattr(full, k) == getattr(defaults, k) > 0 for k in bench.FULL_ONLY)
+    assert bench.parse_args(["--full", "--cpu-frames", "0"]).cpu_frames == 0

@@ -2,14 +2,11 @@
 the synthetic harness assumes, and they agree with the oracle's camera model.  The last point is one of the few places where the oracle meets
 reference-held data: the masks were drawn by the reference's authors around the part of the cubemap their camera model fills."""
 import ctypes as C
-import os
 import numpy as np
 import pytest
 import orc
 import refdata
 from cubemapslam_amd import api, synth
-
-REF = "/root/reference"
 
 
 @pytest.mark.parametrize("name,F", [("lafida", 450), ("lafida", 550), ("lafida", 650), ("front", 650)])
@@ -44,22 +41,6 @@ def test_reference_configs_are_what_the_harness_assumes():
         assert (orb.nfeatures, orb.nlevels, orb.ini_th_fast, orb.min_th_fast) == (want["nfeatures"], 8, 20, 7) and abs(orb.scale_factor - 1.2) < 1e-7
         assert list(misc) == [30.0, 1.0, 1.0]                       # fps, withFisheyeMask, RGB
     assert refdata.reference_config("left_cam")[0] != refdata.reference_config("front_cam")[0]
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout only exists in the build container")
-def test_fixtures_are_current_with_the_reference_checkout():
-    """the committed fixtures against the files they were made from (build container only)"""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-    import make_reference_fixtures as mk
-    from PIL import Image
-    for (name, F), key in refdata.MASK_KEYS.items():
-        a = np.asarray(Image.open(os.path.join(REF, mk.MASKS[key])))
-        assert np.array_equal(refdata.reference_mask(name, F) != 0, a != 0), key
-    for key, rel in mk.CONFIGS.items():
-        cam, orb, fps, wm, rgb = mk.load_settings(os.path.join(REF, rel))
-        cam_b, orb_b, misc = refdata.reference_config(key)
-        assert bytes(cam) == cam_b and bytes(orb) == orb_b and list(misc) == [fps, wm, rgb], key
 
 
 def test_oracle_extraction_culls_with_the_reference_mask():

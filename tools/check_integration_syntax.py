@@ -1,0 +1,61 @@
+"""integration/CubemapHipBridge.cpp + OrbExtractorHip.h are written against the reference's REAL headers (Frame.h, KeyFrame.h, MapPoint.h, Map.h,
+Converter.h, CamModelGeneral.h, ORBMatcher.h) and cannot be built without OpenCV / Eigen.  This check stops typos from shipping: `g++ -fsyntax-only`
+over the bridge, with the reference's include/ directory as a maintainer would have it after the integration step (ORBExtractor.h replaced by
+OrbExtractorHip.h) and DECLARATIONS-ONLY stand-ins for OpenCV / Eigen / g2o / DBoW2 under tests/stubs/.  It pins nothing about parity -- no body
+is compiled into anything, nothing is linked or run.  A second pass breaks one C-ABI call in each file and must fail: both files are really parsed.
+
+    python tools/check_integration_syntax.py REFERENCE_CHECKOUT/include
+
+The reference's headers are not part of this repository, so the check is a maintainer's tool rather than a test."""
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def syntax_check(ref_inc, work, integration_dir):
+    inc = os.path.join(work, "refinc")
+    os.mkdir(inc)
+    for f in os.listdir(ref_inc):
+        if f != "ORBExtractor.h":
+            os.symlink(os.path.join(ref_inc, f), os.path.join(inc, f))
+    shutil.copy(os.path.join(integration_dir, "OrbExtractorHip.h"), os.path.join(inc, "ORBExtractor.h"))      # integration/README.md: the header the extractor's users include
+    cmd = ["g++", "-std=c++11", "-fsyntax-only", "-Wall", "-I", os.path.join(ROOT, "tests", "stubs"), "-I", integration_dir, "-I", os.path.join(ROOT, "include"),
+           "-I", inc, os.path.join(integration_dir, "CubemapHipBridge.cpp")]
+    return subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+
+
+def main(ref_inc):
+    with tempfile.TemporaryDirectory() as td:
+        os.mkdir(os.path.join(td, "ok"))
+        r = syntax_check(ref_inc, os.path.join(td, "ok"), os.path.join(ROOT, "integration"))
+        if r.returncode != 0 or "error" in r.stderr:
+            print(r.stderr[-4000:])
+            return 1
+        # a misspelt C-ABI call in either file must fail the check
+        for i, (fname, old, new) in enumerate((("OrbExtractorHip.h", "cms_extract(ctx,", "cms_extrakt(ctx,"), ("CubemapHipBridge.cpp", "cms_area_grid(ctx, 1)", "cms_area_grid(ctx)"),
+                                               ("CubemapHipBridge.cpp", "cms_kfstore_fuse_search_sets(store, 2, set_off,", "cms_kfstore_fuse_search_sets(store, set_off,"))):
+            d = os.path.join(td, "broken_%d" % i)
+            shutil.copytree(os.path.join(ROOT, "integration"), d)
+            src = open(os.path.join(d, fname)).read()
+            if old not in src:
+                print("%s no longer contains %r: update this check" % (fname, old))
+                return 1
+            open(os.path.join(d, fname), "w").write(src.replace(old, new, 1))
+            sub = os.path.join(td, "t_%d" % i)
+            os.mkdir(sub)
+            r = syntax_check(ref_inc, sub, d)
+            if r.returncode == 0 or "error" not in r.stderr:
+                print("a broken %s passed the check: it is not parsed" % fname)
+                return 1
+    print("integration/ parses against %s" % ref_inc)
+    return 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) != 2 or not os.path.isdir(sys.argv[1]):
+        raise SystemExit("usage: check_integration_syntax.py REFERENCE_CHECKOUT/include")
+    sys.exit(main(sys.argv[1]))

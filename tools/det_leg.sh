@@ -3,7 +3,7 @@
 #   tools/det_leg.sh [tag] [ENV=VALUE ...]
 R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-det}; shift
-env "$@" python $R/bench.py --extract-only-steps 0 --random-views-steps 0 --optimise-only-steps 0 --unpipelined-steps 0 --mapping-only-steps 0 --deterministic-steps 10 \
+env "$@" python $R/bench.py --full --extract-only-steps 0 --random-views-steps 0 --optimise-only-steps 0 --unpipelined-steps 0 --mapping-only-steps 0 --deterministic-steps 10 \
   > $R/gpurun_out/$TAG.json 2> $R/gpurun_out/$TAG.err
 python - <<PY
 import json

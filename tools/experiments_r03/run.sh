@@ -27,7 +27,7 @@ CMS_BENCH_PART=ba bash tools/gb.sh baonly
 echo "== probe"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/probe/lds_atomics.hip -o /tmp/lds_atomics 2>/dev/null && /tmp/lds_atomics > $O/probe_lds_atomics.txt 2>&1; tail -5 $O/probe_lds_atomics.txt
 echo "== full bench line"
-timeout 900 python bench.py > $O/bench_full.json 2> $O/bench_full.err; tail -c 1500 $O/bench_full.json; tail -5 $O/bench_full.err
+timeout 900 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err; tail -c 1500 $O/bench_full.json; tail -5 $O/bench_full.err
 ;;
 2)
 O=gpurun_out/r2; mkdir -p $O

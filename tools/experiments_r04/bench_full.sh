@@ -1,6 +1,7 @@
 #!/bin/bash
-# the default bench line (what the driver runs) with its key numbers printed: bash tools/experiments_r04/bench_full.sh [tag] [bench args...]
+# the full bench line (bench.py --full) with its key numbers printed: bash tools/experiments_r04/bench_full.sh [tag] [bench args...]
 TAG=${1:-default}; shift
+set -- --full "$@"
 mkdir -p gpurun_out/r04
 ( time python bench.py "$@" ) > gpurun_out/r04/bench_$TAG.json 2> gpurun_out/r04/bench_$TAG.err; tail -4 gpurun_out/r04/bench_$TAG.err
 python - gpurun_out/r04/bench_$TAG.json <<'PY'

@@ -2,7 +2,7 @@
 O=gpurun_out/r05; mkdir -p $O
 bash tools/experiments_r05/exp.sh tests
 for i in 1 2 3; do
-  timeout 900 python bench.py > $O/bench_default_$i.json 2> $O/bench_default_$i.err
+  timeout 900 python bench.py --full > $O/bench_default_$i.json 2> $O/bench_default_$i.err
   python - $O/bench_default_$i.json <<'PY'
 import json, sys
 l=[x for x in open(sys.argv[1]) if x.startswith('{')]
