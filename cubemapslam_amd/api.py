@@ -543,6 +543,38 @@ def create_new_map_points(ctx, jobs, check_orientation=False, cap=None):
     return [(on[j, :n_new[j]].copy(), o1[j, :n_new[j]].copy(), o2[j, :n_new[j]].copy(), ox[j, :n_new[j]].copy()) for j in range(nj)]
 
 
+class BowJob(C.Structure):
+    """cms_bow_job (include/cubemapslam_hip.h)"""
+    _fields_ = [("slot", C.c_int), ("b", C.c_int), ("n", C.c_int), ("nnodes", C.c_int), ("node_id", C.c_void_p), ("node_off", C.c_void_p),
+                ("node_feat", C.c_void_p), ("kf_skip", C.c_void_p)]
+
+
+def _bow_fv(fv):
+    """a FeatureVector as CSR int32 arrays: fv = dict(node_id, node_off, node_feat) or the tuple (node_id, node_off, node_feat)"""
+    if isinstance(fv, dict):
+        fv = (fv["node_id"], fv["node_off"], fv["node_feat"])
+    nid, noff, nfeat = (np.ascontiguousarray(a, np.int32) for a in fv)
+    if len(noff) == 0:
+        noff = np.zeros(1, np.int32)
+    return nid, noff, (nfeat if len(nfeat) else np.zeros(1, np.int32))
+
+
+def search_by_bow(ctx, b, n, fv, K, skip=None, nnratio=0.7, check_orientation=True):
+    """cms_search_by_bow: ORBMatcher::SearchByBoW(pKF, F, vpMapPointMatches) with the key frame K (a Keyframe struct, make_keyframe) from the host and
+    the frame = row b of ctx's last batch (n key points) with FeatureVector fv (see _bow_fv).  skip: None or one byte per key-frame feature (!= 0:
+    the map point is bad).  Returns (kf_idx int32[n]: key-frame feature whose map point frame key point i receives, or -1; n_matches)."""
+    nid, noff, nfeat = _bow_fv(fv)
+    sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+    kf_idx = np.full(max(n, 1), -1, np.int32)
+    nm = C.c_int()
+    L = lib()
+    L.cms_search_by_bow.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
+                                    C.c_void_p, C.c_void_p]
+    _chk(L.cms_search_by_bow(ctx.h, b, n, len(nid), _p(nid), _p(noff), _p(nfeat), C.byref(K), _p(sk), float(nnratio), int(check_orientation), _p(kf_idx),
+                             C.byref(nm)), "cms_search_by_bow")
+    return kf_idx[:n].copy(), nm.value
+
+
 class KeyframeStore:
     """cms_kfstore: key frames resident on the device in slots"""
 
@@ -674,6 +706,25 @@ class KeyframeStore:
         if not copy:
             return [(on[j, :n_new[j]], o1[j, :n_new[j]], o2[j, :n_new[j]], ox[j, :n_new[j]]) for j in range(nj)]
         return [(on[j, :n_new[j]].copy(), o1[j, :n_new[j]].copy(), o2[j, :n_new[j]].copy(), ox[j, :n_new[j]].copy()) for j in range(nj)]
+
+    def search_by_bow(self, src_ctx, jobs, nnratio=0.7, check_orientation=True):
+        """cms_kfstore_search_by_bow: ORBMatcher::SearchByBoW(pKF, F, ...) for many (resident key frame, frame) pairs in ONE launch on src_ctx's stream.
+        jobs: list of (slot, b, n, fv, skip): frame b of src_ctx's last batch with n key points, fv its FeatureVector (see _bow_fv), skip None or one
+        byte per feature of the slot's key frame (!= 0: the map point is bad).  Returns per job (kf_idx int32[n], n_matches)."""
+        arr = (BowJob * max(len(jobs), 1))()
+        keep = []
+        for q, (slot, b, n, fv, skip) in zip(arr, jobs):
+            nid, noff, nfeat = _bow_fv(fv)
+            sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+            keep.append((nid, noff, nfeat, sk))
+            q.slot = slot; q.b = b; q.n = n; q.nnodes = len(nid)
+            q.node_id = nid.ctypes.data; q.node_off = noff.ctypes.data; q.node_feat = nfeat.ctypes.data; q.kf_skip = None if sk is None else sk.ctypes.data
+        off = np.concatenate([[0], np.cumsum([int(j[2]) for j in jobs])]).astype(np.int64)
+        kf_idx = np.full(max(int(off[-1]), 1), -1, np.int32); nm = np.zeros(max(len(jobs), 1), np.int32)
+        L = lib()
+        L.cms_kfstore_search_by_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+        _chk(L.cms_kfstore_search_by_bow(self.h, src_ctx.h, len(jobs), arr, float(nnratio), int(check_orientation), _p(kf_idx), _p(nm)), "cms_kfstore_search_by_bow")
+        return [(kf_idx[off[j]:off[j + 1]].copy(), int(nm[j])) for j in range(len(jobs))]
 
 
 def distinctive_descriptors(ctx, obs_off, desc):

@@ -1,0 +1,169 @@
+// cms_api_bow.hip -- host side of ORBMatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (src/ORBMatcher.cpp:409-539), included by
+// cms_lib.hip after cms_api_tri.hip (cms_kfstore).  Both entries stage what comes from the host (FeatureVectors, skip flags, job records; for the
+// stand-alone entry the key frame too) in the context's pinned block, make ONE copy to the device, ONE launch of k_search_by_bow and ONE copy back.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+namespace {
+inline size_t bow_al(size_t v) { return (v + 15) & ~(size_t)15; }
+// a FeatureVector in CSR: node ids strictly ascending, offsets ascending from >= 0, indices in [0, n); unique_of (n bytes of scratch, or NULL) also
+// rejects an index listed twice -- the frame side, where DBoW2 puts every feature into exactly one node
+int bow_check_fv(int n, int nnodes, const int* node_id, const int* node_off, const int* node_feat, std::vector<uint8_t>* unique_of, const char* who) {
+  if (nnodes < 0 || (nnodes > 0 && (!node_id || !node_off || !node_feat)) || (nnodes > 0 && node_off[0] < 0)) return cms_fail(CMS_ERR_ARG, who);
+  if (unique_of) unique_of->assign((size_t)std::max(n, 1), 0);
+  for (int e = 0; e < nnodes; ++e) {
+    if (e > 0 && node_id[e] <= node_id[e - 1]) return cms_fail(CMS_ERR_ARG, "SearchByBoW: FeatureVector node ids must ascend");
+    if (node_off[e + 1] < node_off[e]) return cms_fail(CMS_ERR_ARG, "SearchByBoW: FeatureVector offsets must ascend");
+    for (int q = node_off[e]; q < node_off[e + 1]; ++q) {
+      const int f = node_feat[q];
+      if (f < 0 || f >= n) return cms_fail(CMS_ERR_ARG, "SearchByBoW: FeatureVector index out of range");
+      if (unique_of) {
+        if ((*unique_of)[(size_t)f]) return cms_fail(CMS_ERR_ARG, "SearchByBoW: the frame's FeatureVector lists a feature twice");
+        (*unique_of)[(size_t)f] = 1;
+      }
+    }
+  }
+  return CMS_OK;
+}
+int bow_check_frame(cms_ctx* c, int b, int n, const char* who) {
+  if (b < 0 || b >= c->max_batch || n < 0) return cms_fail(CMS_ERR_ARG, who);
+  if (n > CMS_AREA_MAXKP) return cms_fail(CMS_ERR_UNSUPPORTED, "SearchByBoW: more than 16383 key points in the frame");
+  if (n > c->g.kp_cap) return cms_fail(CMS_ERR_ARG, "SearchByBoW: more key points than a frame row of the context holds");
+  return CMS_OK;
+}
+
+// A job as the host lays it out: where each host array goes in the staged input block (offsets), and what is already on the device.
+struct BowStage {
+  const void* src; size_t bytes; size_t at;
+};
+// stage -> device -> launch -> back.  jobs[j] has every device pointer filled except the ones given as offsets in rel[j] (pointer fields that
+// hold an offset into the input block, marked by the caller), which are rebased here once the block's device address is known.
+int bow_run(cms_ctx* c, std::vector<CmsBowJob>& jobs, const std::vector<std::vector<const void**>>& rel, std::vector<BowStage>& pieces, size_t in_bytes,
+            float nnratio, int check_orientation, int* kf_idx, int* n_matches) {
+  const int njobs = (int)jobs.size();
+  size_t total_n = 0;
+  for (const CmsBowJob& q : jobs) total_n += (size_t)q.n;
+  const size_t o_jobs = bow_al(in_bytes), o_idx = o_jobs + bow_al((size_t)njobs * sizeof(CmsBowJob)), o_nm = o_idx + bow_al(total_n * 4 + 4);
+  const size_t bytes = o_nm + bow_al((size_t)njobs * 4);
+  int rc = cms_scratch(c, bytes);
+  if (rc) return rc;
+  rc = cms_hstage(c, bytes);
+  if (rc) return rc;
+  uint8_t* p = (uint8_t*)c->d_match;
+  uint8_t* h = c->h_stage;
+  for (const BowStage& s : pieces) if (s.bytes) std::memcpy(h + s.at, s.src, s.bytes);
+  size_t cursor = 0;
+  for (int j = 0; j < njobs; ++j) {
+    CmsBowJob& q = jobs[(size_t)j];
+    for (const void** f : rel[(size_t)j]) *f = p + (size_t)(uintptr_t)(*f);
+    q.kf_idx = (int*)(p + o_idx) + cursor; q.n_matches = (int*)(p + o_nm) + j;
+    cursor += (size_t)q.n;
+  }
+  std::memcpy(h + o_jobs, jobs.data(), (size_t)njobs * sizeof(CmsBowJob));
+  hipStream_t s = c->stream;
+  HIPCHK(hipMemcpyAsync(p, h, o_idx, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_search_by_bow, dim3(njobs), dim3(CMS_BOW_THREADS), 0, s, (const CmsBowJob*)(p + o_jobs), nnratio, check_orientation);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h + o_idx, p + o_idx, bytes - o_idx, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (total_n) std::memcpy(kf_idx, h + o_idx, total_n * 4);
+  std::memcpy(n_matches, h + o_nm, (size_t)njobs * 4);
+  return CMS_OK;
+}
+// host array -> staged piece; the job field receives its offset in the block (rebased by bow_run)
+template <class T>
+void bow_put(std::vector<BowStage>& pieces, size_t& o, std::vector<const void**>& rel, const T*& field, const void* src, size_t bytes) {
+  pieces.push_back(BowStage{src, bytes, o});
+  field = reinterpret_cast<const T*>((uintptr_t)o);
+  rel.push_back(reinterpret_cast<const void**>(&field));
+  o += bow_al(bytes + 4);
+}
+}  // namespace
+
+// Tracking::TrackReferenceKeyFrame's matcher (Tracking.cpp:567-618) with the key frame from the host: frame b of ctx's last batch against kf
+extern "C" int cms_search_by_bow(cms_ctx* c, int b, int n, int nnodes, const int* node_id, const int* node_off, const int* node_feat, const cms_keyframe* kf,
+                                 const uint8_t* kf_skip, float nnratio, int check_orientation, int* kf_idx, int* n_matches) {
+  if (!c || !kf || !n_matches || (n > 0 && !kf_idx)) return cms_fail(CMS_ERR_ARG, "cms_search_by_bow: bad argument");
+  int rc = bow_check_frame(c, b, n, "cms_search_by_bow: bad frame");
+  if (rc) return rc;
+  if (kf->n > CMS_TRI_MAXF) return cms_fail(CMS_ERR_UNSUPPORTED, "cms_search_by_bow: more than 4096 features in the key frame");
+  if (kf->n < 0 || (kf->n > 0 && (!kf->kps || !kf->desc || !kf->mp))) return cms_fail(CMS_ERR_ARG, "cms_search_by_bow: bad key frame");
+  std::vector<uint8_t> seen;
+  rc = bow_check_fv(kf->n, kf->nnodes, kf->node_id, kf->node_off, kf->node_feat, nullptr, "cms_search_by_bow: bad key-frame FeatureVector");
+  if (rc) return rc;
+  rc = bow_check_fv(n, nnodes, node_id, node_off, node_feat, &seen, "cms_search_by_bow: bad frame FeatureVector");
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<CmsBowJob> jobs(1);
+  std::vector<std::vector<const void**>> rel(1);
+  std::vector<BowStage> pieces;
+  CmsBowJob& q = jobs[0];
+  std::memset(&q, 0, sizeof(q));
+  size_t o = 0;
+  const size_t kn = (size_t)kf->n;
+  const int kfeat = kf->nnodes > 0 ? kf->node_off[kf->nnodes] : 0, ffeat = nnodes > 0 ? node_off[nnodes] : 0;
+  bow_put(pieces, o, rel[0], q.kf_kp, kf->kps, kn * sizeof(CmsKeyPoint));
+  bow_put(pieces, o, rel[0], q.kf_desc, kf->desc, kn * 32);
+  bow_put(pieces, o, rel[0], q.kf_mp, kf->mp, kn * 4);
+  if (kf_skip) bow_put(pieces, o, rel[0], q.kf_skip, kf_skip, kn);
+  bow_put(pieces, o, rel[0], q.kf_nid, kf->node_id, 4 * (size_t)kf->nnodes);
+  bow_put(pieces, o, rel[0], q.kf_noff, kf->node_off, kf->nnodes > 0 ? 4 * ((size_t)kf->nnodes + 1) : 0);
+  bow_put(pieces, o, rel[0], q.kf_nfeat, kf->node_feat, 4 * (size_t)kfeat);
+  bow_put(pieces, o, rel[0], q.f_nid, node_id, 4 * (size_t)nnodes);
+  bow_put(pieces, o, rel[0], q.f_noff, node_off, nnodes > 0 ? 4 * ((size_t)nnodes + 1) : 0);
+  bow_put(pieces, o, rel[0], q.f_nfeat, node_feat, 4 * (size_t)ffeat);
+  q.kf_nnodes = kf->nnodes; q.f_nnodes = nnodes; q.n = n;
+  const size_t sb = (size_t)b * c->g.kp_cap;
+  q.f_kp = (const CmsKeyPoint*)c->d_kps + sb; q.f_desc = (const uint4*)(c->d_desc + 32 * sb);
+  return bow_run(c, jobs, rel, pieces, o, nnratio, check_orientation, kf_idx, n_matches);
+}
+
+// Relocalization's candidate loop (Tracking.cpp:1019-1040) or one TrackReferenceKeyFrame per camera stream on resident key frames: ONE launch on
+// src's stream.  Nothing is enqueued on the store's stream; the copies of cms_kfstore_put_from_frame(s) that filled a named slot are waited for on
+// the device (their events: the copy may still be in flight when it ran on another context's stream).
+extern "C" int cms_kfstore_search_by_bow(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_job* jobs, float nnratio, int check_orientation,
+                                         int* kf_idx, int* n_matches) {
+  if (!st || !src || njobs < 0 || (njobs > 0 && (!jobs || !n_matches))) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow: bad argument");
+  if (njobs == 0) return CMS_OK;
+  if (src->device != st->c->device) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow: the frame context and the store must share the device");
+  std::vector<uint8_t> seen;
+  size_t total_n = 0;
+  for (int j = 0; j < njobs; ++j) {
+    const cms_bow_job& q = jobs[j];
+    if (q.slot < 0 || q.slot >= st->maxkf || !st->used[(size_t)q.slot]) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow: empty slot");
+    int rc = bow_check_frame(src, q.b, q.n, "cms_kfstore_search_by_bow: bad frame");
+    if (rc) return rc;
+    rc = bow_check_fv(q.n, q.nnodes, q.node_id, q.node_off, q.node_feat, &seen, "cms_kfstore_search_by_bow: bad frame FeatureVector");
+    if (rc) return rc;
+    total_n += (size_t)q.n;
+  }
+  if (total_n > 0 && !kf_idx) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow: bad argument");
+  HIPCHK(hipSetDevice(src->device));
+  hipStream_t s = src->stream;
+  for (int j = 0; j < njobs; ++j) {
+    const auto& call = st->ff_call[(size_t)jobs[j].slot];
+    if (call) HIPCHK(hipStreamWaitEvent(s, call->ev, 0));
+  }
+  std::vector<CmsBowJob> dj((size_t)njobs);
+  std::vector<std::vector<const void**>> rel((size_t)njobs);
+  std::vector<BowStage> pieces;
+  size_t o = 0;
+  for (int j = 0; j < njobs; ++j) {
+    const cms_bow_job& q = jobs[j];
+    const CmsTriKF& k = st->h_kf[(size_t)q.slot];
+    CmsBowJob& d = dj[(size_t)j];
+    std::memset(&d, 0, sizeof(d));
+    d.kf_kp = st->d_kp + k.f0; d.kf_desc = (const uint4*)(st->d_desc + 32 * (size_t)k.f0); d.kf_mp = st->d_mp + k.f0;
+    d.kf_nid = st->d_nid + k.node0; d.kf_noff = st->d_noff + k.noff0; d.kf_nfeat = st->d_nfeat + k.nfeat0; d.kf_nnodes = k.nnodes;
+    if (q.kf_skip) bow_put(pieces, o, rel[(size_t)j], d.kf_skip, q.kf_skip, (size_t)k.n);
+    const int ffeat = q.nnodes > 0 ? q.node_off[q.nnodes] : 0;
+    bow_put(pieces, o, rel[(size_t)j], d.f_nid, q.node_id, 4 * (size_t)q.nnodes);
+    bow_put(pieces, o, rel[(size_t)j], d.f_noff, q.node_off, q.nnodes > 0 ? 4 * ((size_t)q.nnodes + 1) : 0);
+    bow_put(pieces, o, rel[(size_t)j], d.f_nfeat, q.node_feat, 4 * (size_t)ffeat);
+    d.f_nnodes = q.nnodes; d.n = q.n;
+    const size_t sb = (size_t)q.b * src->g.kp_cap;
+    d.f_kp = (const CmsKeyPoint*)src->d_kps + sb; d.f_desc = (const uint4*)(src->d_desc + 32 * sb);
+  }
+  return bow_run(src, dj, rel, pieces, o, nnratio, check_orientation, kf_idx, n_matches);
+}

@@ -384,6 +384,7 @@ extern "C" int cms_kfstore_create(cms_kfstore** out, cms_ctx* c, int max_keyfram
   KF_ALLOC(st->d_kp_cnt, K * sizeof(int));
 #undef KF_ALLOC
   st->h_kf.assign(K, CmsTriKF{}); st->h_median.assign(K, 1.0f); st->used.assign(K, 0); st->busy.assign(K, 0);
+  st->ff_call.assign(K, nullptr);      // (here, not at the first put from a frame: cms_kfstore_search_by_bow reads it from the frame thread)
   *out = st;
   return CMS_OK;
 }
@@ -477,7 +478,6 @@ static int kfstore_ff_reserve(cms_kfstore* st) {
   st->ff_stride = ((size_t)3 * st->maxf + 2 * (size_t)st->maxn + 1 + 63) & ~(size_t)63;      // ints per slot: mp | feat_node | node_feat | node_id | node_off
   HIPCHK(hipHostMalloc((void**)&st->h_ff, (size_t)st->maxkf * st->ff_stride * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
   HIPCHK(hipHostMalloc((void**)&st->h_items, 2 * (size_t)st->maxkf * sizeof(CmsKfFromFrame), hipHostMallocMapped | hipHostMallocCoherent));
-  st->ff_call.assign((size_t)st->maxkf, nullptr);
   return CMS_OK;
 }
 // validation of one key frame of a cms_kfstore_put_from_frames call: touches nothing

@@ -239,6 +239,27 @@ extern "C" __global__ void __launch_bounds__(256) k_project_last(CmsProjectLastA
   a.qx[i] = u; a.qy[i] = v; a.qr[i] = r; a.qmin[i] = o - 1; a.qmax[i] = o + 1;
 }
 
+// the rotation histogram of the matchers (ORBMatcher.cpp, HISTO_LENGTH = 12): the bin of one match, rot = angle of the reference side's key
+// point - angle of the current one, +360 when negative, round(rot * 1/12), 30 -> 0 ...
+__device__ __forceinline__ int track_rot_bin(float angle_ref, float angle_cur) {
+  float rot = __fsub_rn(angle_ref, angle_cur);
+  if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
+  int bin = (int)roundf(__fmul_rn(rot, 1.0f / 12));
+  return bin == 30 ? 0 : bin;
+}
+// ... and ComputeThreeMaxima (:905-946) over bins 0..29: keep[0..2] = the three fullest bins, -1 where the 0.1 * max1 rule drops one
+__device__ __forceinline__ void track_three_maxima(const int* hist, int* keep) {
+  int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
+  for (int b = 0; b < 30; ++b) {
+    const int s = hist[b];
+    if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = b; }
+    else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = b; }
+    else if (s > max3) { max3 = s; i3 = b; }
+  }
+  if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { i2 = -1; i3 = -1; } else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) i3 = -1;
+  keep[0] = i1; keep[1] = i2; keep[2] = i3;
+}
+
 struct CmsRotFilterArgs {
   const int* mp_off; const float* last_angle; const CmsKeyPoint* kp; int* kp_mp; int* mp_match; int* n_matches; int check_orientation;
   const int* total; int cap;  // as in CmsSearchLocalArgs
@@ -253,28 +274,13 @@ extern "C" __global__ void __launch_bounds__(1024) k_rot_filter(CmsRotFilterArgs
   if (tid < 32) hist[tid] = 0;
   if (tid == 0) s_n = 0;
   __syncthreads();
-  auto bin_of = [&](int i, int row) {
-    float rot = __fsub_rn(a.last_angle[i], a.kp[row].angle);
-    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-    int bin = (int)roundf(__fmul_rn(rot, 1.0f / 12));
-    return bin == 30 ? 0 : bin;
-  };
+  auto bin_of = [&](int i, int row) { return track_rot_bin(a.last_angle[i], a.kp[row].angle); };
   for (int i = m0 + tid; i < m1; i += nt) {
     const int row = a.mp_match[i];
     if (row >= 0 && a.check_orientation) atomicAdd(&hist[bin_of(i, row)], 1);
   }
   __syncthreads();
-  if (tid == 0) {
-    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-    for (int b = 0; b < 30; ++b) {
-      const int s = hist[b];
-      if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = b; }
-      else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = b; }
-      else if (s > max3) { max3 = s; i3 = b; }
-    }
-    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { i2 = -1; i3 = -1; } else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) i3 = -1;
-    keep[0] = i1; keep[1] = i2; keep[2] = i3;
-  }
+  if (tid == 0) track_three_maxima(hist, keep);
   __syncthreads();
   int mine = 0;
   for (int i = m0 + tid; i < m1; i += nt) {

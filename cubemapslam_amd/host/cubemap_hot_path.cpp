@@ -372,6 +372,58 @@ int ORBMatcher::SearchForTriangulation(const KeyFrameView& pKF1, const KeyFrameV
   return nm;
 }
 
+int ORBMatcher::SearchByBoW(const KeyFrameView& pKF, FrameView& F, std::vector<long>& vpMapPointMatches) {
+  const int N = (int)F.mvKeys.size(), NK = (int)pKF.mvKeys.size();
+  vpMapPointMatches.assign(N, -1);
+  if (N == 0) return 0;
+  cms_ctx* ctx = SharedContext(g_ctx_orb.nfeatures, g_ctx_orb.scale_factor, g_ctx_orb.nlevels, g_ctx_orb.ini_th_fast, g_ctx_orb.min_th_fast);
+  // the key frame as cms_keyframe (key points, descriptors, map-point slots, mFeatVec; rays and pose are not read) and the skip flags
+  std::vector<cms_keypoint> kk(NK + 1);
+  std::vector<uint8_t> kd(32 * (size_t)NK + 32), skip(NK + 1, 0);
+  std::vector<int> kmp(NK + 1), nid, noff(1, 0), nfeat;
+  for (int i = 0; i < NK; ++i) {
+    const cv::KeyPoint& k = pKF.mvKeys[i];
+    kk[i].x = k.pt.x; kk[i].y = k.pt.y; kk[i].size = k.size; kk[i].angle = k.angle; kk[i].response = k.response; kk[i].octave = k.octave;
+    std::memcpy(&kd[32 * (size_t)i], pKF.mDescriptors.ptr<uint8_t>(i), 32);
+    kmp[i] = pKF.mvpMapPoints[i] >= 0 ? 1 : -1;
+    skip[i] = i < (int)pKF.mvbMapPointBad.size() ? pKF.mvbMapPointBad[i] : 0;
+  }
+  for (const auto& e : pKF.mFeatVec) {
+    nid.push_back((int)e.first);
+    for (unsigned f : e.second) nfeat.push_back((int)f);
+    noff.push_back((int)nfeat.size());
+  }
+  cms_keyframe k{};
+  k.n = NK; k.kps = kk.data(); k.desc = kd.data(); k.mp = kmp.data();
+  k.nnodes = (int)nid.size(); k.node_id = nid.data(); k.node_off = noff.data(); k.node_feat = nfeat.data();
+  // the frame: key points and descriptors into row 0 of the shared context, FeatureVector from the host
+  std::vector<cms_keypoint> fk(N);
+  std::vector<uint8_t> fd(32 * (size_t)N);
+  for (int i = 0; i < N; ++i) {
+    const cv::KeyPoint& q = F.mvKeys[i];
+    fk[i].x = q.pt.x; fk[i].y = q.pt.y; fk[i].size = q.size; fk[i].angle = q.angle; fk[i].response = q.response; fk[i].octave = q.octave;
+    std::memcpy(&fd[32 * (size_t)i], F.mDescriptors.ptr<uint8_t>(i), 32);
+  }
+  std::vector<int> fid, foff(1, 0), ffeat;
+  for (const auto& e : F.mFeatVec) {
+    fid.push_back((int)e.first);
+    for (unsigned f : e.second) ffeat.push_back((int)f);
+    foff.push_back((int)ffeat.size());
+  }
+  std::vector<int> kf_idx(N, -1);
+  int nm = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    int rc = cms_area_set_keypoints(ctx, 0, N, fk.data());
+    if (rc == CMS_OK) rc = cms_area_set_descriptors(ctx, 0, N, fd.data());
+    if (rc == CMS_OK) rc = cms_search_by_bow(ctx, 0, N, (int)fid.size(), fid.data(), foff.data(), ffeat.data(), &k, skip.data(), mfNNratio,
+                                             mbCheckOrientation ? 1 : 0, kf_idx.data(), &nm);
+    if (rc != CMS_OK) throw std::runtime_error(std::string("cms_search_by_bow: ") + cms_last_error());
+  }
+  for (int i = 0; i < N; ++i) if (kf_idx[i] >= 0) vpMapPointMatches[i] = pKF.mvpMapPoints[kf_idx[i]];
+  return nm;
+}
+
 int ORBMatcher::SearchByProjection(FrameView& Cur, const FrameView& Last, float th, bool) {
   const int N2 = (int)Cur.mvKeys.size();
   if (!Last.mvMapPointPos.empty() && Cur.mTcw.rows == 4 && Cur.mTcw.cols == 4 && N2 > 0) {

@@ -108,6 +108,7 @@ struct FrameView {
   // When given (and CurrentFrame.mTcw is set) SearchByProjection projects on the device instead of reading projInCurrent.
   std::vector<cv::Vec3f> mvMapPointPos;
   cv::Mat mMapPointDescriptors;         // N x 32 CV_8U
+  std::vector<std::pair<unsigned, std::vector<unsigned>>> mFeatVec;   // Frame::ComputeBoW: ascending node id (SearchByBoW)
 };
 
 struct KeyFrameView;
@@ -138,6 +139,10 @@ class ORBMatcher {
   // ORBMatcher.cpp:1127-1226: search on the device (cms_fuse_search), then the reference's Replace / AddObservation decisions in list
   // order: fused[i] = key point map point i is fused with (or -1); returns nFused.  mvpMapPoints of pKF is updated for additions.
   int Fuse(KeyFrameView& pKF, const std::vector<MapPointView>& vpMapPoints, const std::vector<uint8_t>& skip, float th, std::vector<int>& fused);
+  // ORBMatcher.cpp:409-539, Tracking.cpp:578 / 1030: features of pKF with a map point that is not bad against F's features of the same vocabulary
+  // node, best / second best with mfNNratio, a frame feature taken once, rotation histogram.  vpMapPointMatches[i] = id of the map point frame key
+  // point i receives, or -1; returns nmatches.  (cms_search_by_bow: F's key points and descriptors go to the device first)
+  int SearchByBoW(const KeyFrameView& pKF, FrameView& F, std::vector<long>& vpMapPointMatches);
   static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 12;
 
  protected:
@@ -199,6 +204,7 @@ struct KeyFrameView {
   cv::Mat mDescriptors;                                  // N x 32 CV_8U
   std::vector<cv::Vec3f> mvKeyRays;
   std::vector<long> mvpMapPoints;                        // -1 = none
+  std::vector<uint8_t> mvbMapPointBad;                   // per key point: the map point isBad() (SearchByBoW); empty = none is bad
   cv::Mat Tcw;                                           // 4x4 CV_32F
   std::vector<std::pair<unsigned, std::vector<unsigned>>> mFeatVec;   // ascending node id
   float medianDepth = 1.0f;                              // ComputeSceneMedianDepth(2)

@@ -227,6 +227,37 @@ extern "C" int hm_search_for_triangulation(const int* feat_off, const cms_keypoi
     for (int i = 0; i < (int)pairs.size() && i < cap; ++i) { out_idx1[i] = (int)pairs[i].first; out_idx2[i] = (int)pairs[i].second; }
     return n;)
 }
+// ORBMatcher::SearchByBoW(pKF, F, vpMapPointMatches) through the mirror: the key frame (nk features, map-point ids mp (-1 = none), bad flags or NULL,
+// FeatureVector as CSR) and the frame (n features, FeatureVector as CSR); out_mp[n] = the matched map point's id or -1
+extern "C" int hm_search_by_bow(int nk, const cms_keypoint* kk, const uint8_t* kd, const long* mp, const uint8_t* bad, int kn_nodes, const int* k_nid,
+                                const int* k_noff, const int* k_nfeat, int n, const cms_keypoint* fk, const uint8_t* fd, int f_nodes, const int* f_nid,
+                                const int* f_noff, const int* f_nfeat, float nnratio, int check_ori, long* out_mp) {
+  HM_TRY(
+    KeyFrameView kf;
+    FrameView f;
+    auto keys = [](std::vector<cv::KeyPoint>& v, cv::Mat& d, int m, const cms_keypoint* k, const uint8_t* desc) {
+      v.resize(m);
+      d.create(m > 0 ? m : 1, 32, cv::CV_8U);
+      for (int i = 0; i < m; ++i) {
+        v[i].pt = cv::Point2f(k[i].x, k[i].y); v[i].angle = k[i].angle; v[i].octave = k[i].octave; v[i].size = k[i].size; v[i].response = k[i].response;
+        std::memcpy(d.ptr<uint8_t>(i), desc + (size_t)i * 32, 32);
+      }
+    };
+    auto featvec = [](std::vector<std::pair<unsigned, std::vector<unsigned>>>& fv, int nn, const int* nid, const int* noff, const int* nfeat) {
+      for (int e = 0; e < nn; ++e) fv.emplace_back((unsigned)nid[e], std::vector<unsigned>(nfeat + noff[e], nfeat + noff[e + 1]));
+    };
+    keys(kf.mvKeys, kf.mDescriptors, nk, kk, kd);
+    kf.mvpMapPoints.assign(mp, mp + nk);
+    if (bad) kf.mvbMapPointBad.assign(bad, bad + nk);
+    featvec(kf.mFeatVec, kn_nodes, k_nid, k_noff, k_nfeat);
+    keys(f.mvKeys, f.mDescriptors, n, fk, fd);
+    featvec(f.mFeatVec, f_nodes, f_nid, f_noff, f_nfeat);
+    std::vector<long> m;
+    ORBMatcher matcher(nnratio, check_ori != 0);
+    const int nm = matcher.SearchByBoW(kf, f, m);
+    for (int i = 0; i < n; ++i) out_mp[i] = m[i];
+    return nm;)
+}
 // LocalMapping::CreateNewMapPoints through the mirror: key frame 0 is the current one, 1..nkf-1 its neighbours.  Flat inputs:
 // feat_off[nkf+1]; per feature kps/desc/rays/mp; Tcw nkf x 16; FeatureVector per key frame as node_off2[nkf+1] into (node_id, node_cnt)
 // and the features of the nodes concatenated in node_feat; median_depth[nkf].  Outputs up to cap records.

@@ -464,6 +464,36 @@ int cms_update_normal_and_depth(cms_ctx* ctx, int npts, const int* obs_off, cons
 int cms_fuse_search(cms_ctx* ctx, int b, const float* pose15, int nmp, const uint8_t* skip, const float* pos, const float* normal,
                     const float* min_dist, const float* max_dist, const uint8_t* mp_desc, float th, int* best_idx, int* best_dist);
 
+/* ---- ORBMatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches) (include/ORBMatcher.h:67, src/ORBMatcher.cpp:409-539),
+ * the matcher of Tracking::TrackReferenceKeyFrame (Tracking.cpp:567-618, ORBMatcher(0.7, true)) and of Tracking::Relocalization's candidate loop
+ * (:995-1040, ORBMatcher(0.75, true)).  Only vocabulary nodes present in both FeatureVectors take part, in ascending id order; per common node the
+ * key frame's features with a map point (mp >= 0) that is not bad (kf_skip == NULL or kf_skip[i] == 0: pMP->isBad()) are taken in list order, each
+ * against the node's frame features not matched yet (best < second best, both from 256; best <= TH_LOW and (float)best < nnratio * (float)second);
+ * then the rotation histogram when check_orientation (HISTO_LENGTH 12, ComputeThreeMaxima).  kf_idx[i] (one per frame key point) = the key-frame
+ * feature whose map point frame key point i receives, or -1: the caller maps it to its MapPoint*.  *n_matches = nmatches after the histogram.
+ * The frame's FeatureVector (Frame::ComputeBoW, DBoW2 on the host) comes as CSR like cms_keyframe's; a feature listed twice in it, node ids that
+ * do not ascend or an index >= n are CMS_ERR_ARG.  The frame is row b of the context's last batch: the key points and descriptors cms_frames_process
+ * left on the device, or cms_area_set_keypoints + cms_area_set_descriptors put there.  Limits: n <= 16383 (the frame grid's CMS_AREA_MAXKP), key
+ * frames up to 4096 features (stand-alone) or the store's max_features (resident); more is CMS_ERR_UNSUPPORTED.  Synchronous: Tracking decides on
+ * nmatches at once.
+ * cms_search_by_bow: the key frame from the host (cms_keyframe as for cms_search_for_triangulation; rays and pose are not read), on ctx's stream. */
+int cms_search_by_bow(cms_ctx* ctx, int b, int n, int nnodes, const int* node_id, const int* node_off, const int* node_feat,
+                      const cms_keyframe* kf, const uint8_t* kf_skip, float nnratio, int check_orientation,
+                      int* kf_idx /* n */, int* n_matches);
+/* cms_kfstore_search_by_bow: resident key frames, many jobs, ONE launch (Relocalization's candidate loop, or one TrackReferenceKeyFrame per camera
+ * stream).  A key-frame feature has a map point where the slot's mp (as put / updated) is >= 0.  Runs on src's stream -- the frame thread's -- and
+ * enqueues nothing on the store's: src's stream waits on the device for the copies of cms_kfstore_put_from_frame(s) that filled the named slots.
+ * Threading: the call may run on the frame thread while the mapping thread uses the store, provided no concurrent call refills, updates or
+ * releases a slot that the search names. */
+typedef struct {
+  int slot;                 /* key frame: store slot */
+  int b, n;                 /* frame: row b of src's last batch, n key points */
+  int nnodes; const int* node_id; const int* node_off; const int* node_feat;   /* Frame::ComputeBoW output, CSR */
+  const uint8_t* kf_skip;   /* NULL, or one byte per key-frame feature: != 0 <=> pMP->isBad() */
+} cms_bow_job;
+int cms_kfstore_search_by_bow(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_job* jobs, float nnratio,
+                              int check_orientation, int* kf_idx /* sum of jobs[j].n, job after job */, int* n_matches /* njobs */);
+
 /* ---- pose-only optimisation: Optimizer::PoseOptimization(Frame*) (src/Optimizer.cpp:48-190), the per-frame solver Tracking calls
  * 1-3 times per frame (Tracking.cpp:585,647,688).  Edge = EdgeSE3ProjectXYZMultiPinholeOnlyPose
  * (include/g2o_cubemap_vertices_edges.h:42-88, src/g2o_cubemap_vertices_edges.cpp:61-134).  One workgroup per frame runs all four

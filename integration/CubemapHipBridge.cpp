@@ -259,11 +259,15 @@ void LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap) {
 
 // ------------------------------------------------------------------------------------------------ LocalMapping on resident key frames
 namespace {
-struct StoreBook { std::map<KeyFrame*, int> slot; std::vector<int> free_slots; int max_features = 0; };
-std::map<cms_kfstore*, StoreBook> g_books;
+// The book is read by the tracking thread (SearchByBoW) and written by the mapping thread.  `mu` guards the two containers, and it is also held
+// across every host call that refills or updates a slot (cms_kfstore_put_from_frame, cms_kfstore_update) and across a whole search, so a slot a
+// search names is never released, refilled or updated while the search runs (the threading contract of cms_kfstore_search_by_bow).
+struct StoreBook { std::map<KeyFrame*, int> slot; std::vector<int> free_slots; int max_features = 0; std::mutex mu; };
+std::map<cms_kfstore*, StoreBook> g_books;      // (std::map: a StoreBook never moves once created)
 std::mutex g_books_mutex;
 StoreBook& book(cms_kfstore* st) { std::lock_guard<std::mutex> lk(g_books_mutex); return g_books[st]; }
-int slot_of(StoreBook& b, KeyFrame* k) { const auto it = b.slot.find(k); return it == b.slot.end() ? -1 : it->second; }
+int slot_locked(StoreBook& b, KeyFrame* k) { const auto it = b.slot.find(k); return it == b.slot.end() ? -1 : it->second; }      // b.mu held
+int slot_of(StoreBook& b, KeyFrame* k) { std::lock_guard<std::mutex> lk(b.mu); return slot_locked(b, k); }
 void pose_floats(KeyFrame* k, float* R9, float* t3, float* O3) {
   const cv::Mat R = k->GetRotation(), t = k->GetTranslation(), O = k->GetCameraCenter();
   for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) R9[3 * r + c] = R.at<float>(r, c); t3[r] = t.at<float>(r); O3[r] = O.at<float>(r); }
@@ -287,6 +291,7 @@ cms_kfstore* CreateKeyFrameStore(cms_ctx* mappingCtx, int maxKeyFrames, int maxF
   cms_kfstore* st = nullptr;
   check(cms_kfstore_create(&st, mappingCtx, maxKeyFrames, maxFeatures, 4096), "cms_kfstore_create");
   StoreBook& b = book(st);
+  std::lock_guard<std::mutex> lk(b.mu);
   b.max_features = maxFeatures;
   for (int s = maxKeyFrames - 1; s >= 0; --s) b.free_slots.push_back(s);
   return st;
@@ -294,7 +299,8 @@ cms_kfstore* CreateKeyFrameStore(cms_ctx* mappingCtx, int maxKeyFrames, int maxF
 
 int ProcessNewKeyFrame(cms_kfstore* store, cms_ctx* frameCtx, KeyFrame* pKF) {
   StoreBook& b = book(store);
-  int slot = slot_of(b, pKF);
+  std::lock_guard<std::mutex> lk(b.mu);      // (to the end: the book entry appears together with the put, and no search runs on a slot being refilled)
+  int slot = slot_locked(b, pKF);
   if (slot < 0) {
     if (b.free_slots.empty()) throw std::runtime_error("Hip::ProcessNewKeyFrame: the key-frame store is full");
     slot = b.free_slots.back(); b.free_slots.pop_back(); b.slot[pKF] = slot;
@@ -316,6 +322,7 @@ int ProcessNewKeyFrame(cms_kfstore* store, cms_ctx* frameCtx, KeyFrame* pKF) {
 
 void ReleaseKeyFrame(cms_kfstore* store, KeyFrame* pKF) {
   StoreBook& b = book(store);
+  std::lock_guard<std::mutex> lk(b.mu);
   const auto it = b.slot.find(pKF);
   if (it == b.slot.end()) return;
   b.free_slots.push_back(it->second);
@@ -335,12 +342,16 @@ int CreateNewMapPoints(cms_kfstore* store, KeyFrame* pCurrentKF, Map* pMap, std:
     float R[9], t[3], O[3]; std::vector<int> mp;
     pose_floats(k, R, t, O); mp_slots(k, mp);
     const float md = k->ComputeSceneMedianDepth(2);
-    check(cms_kfstore_update(store, s, R, t, O, &md, mp.data()), "cms_kfstore_update");
+    {
+      std::lock_guard<std::mutex> lk(b.mu);
+      check(cms_kfstore_update(store, s, R, t, O, &md, mp.data()), "cms_kfstore_update");
+    }
     neigh.push_back(k); neigh_slot.push_back(s);
   }
   {
     float R[9], t[3], O[3]; std::vector<int> mp;
     pose_floats(pCurrentKF, R, t, O); mp_slots(pCurrentKF, mp);
+    std::lock_guard<std::mutex> lk(b.mu);
     check(cms_kfstore_update(store, cur, R, t, O, nullptr, mp.data()), "cms_kfstore_update");
   }
   if (neigh.empty()) return 0;
@@ -452,5 +463,88 @@ void UpdateKeyFramePoses(cms_kfstore* store, const std::vector<KeyFrame*>& vpKFs
     slots.push_back(s); R.insert(R.end(), r9, r9 + 9); t.insert(t.end(), t3, t3 + 3); O.insert(O.end(), o3, o3 + 3);
   }
   if (!slots.empty()) check(cms_kfstore_update_poses(store, (int)slots.size(), slots.data(), R.data(), t.data(), O.data()), "cms_kfstore_update_poses");
+}
+
+// ------------------------------------------------------------------------------------------------ Tracking: SearchByBoW on resident key frames
+namespace {
+// the frame's FeatureVector (Frame::ComputeBoW) as CSR
+void feat_vec_csr(const DBoW2::FeatureVector& fv, std::vector<int>& node_id, std::vector<int>& node_off, std::vector<int>& node_feat) {
+  node_id.clear(); node_off.assign(1, 0); node_feat.clear();
+  for (DBoW2::FeatureVector::const_iterator it = fv.begin(); it != fv.end(); ++it) {
+    node_id.push_back((int)it->first);
+    for (size_t q = 0; q < it->second.size(); ++q) node_feat.push_back((int)it->second[q]);
+    node_off.push_back((int)node_feat.size());
+  }
+}
+// skip flags of a key frame's features: no map point any more, or a bad one (ORBMatcher.cpp:444-450)
+void bad_flags(const std::vector<MapPoint*>& v, std::vector<uint8_t>& skip) {
+  skip.assign(v.size() + 1, 0);
+  for (size_t i = 0; i < v.size(); ++i) skip[i] = (!v[i] || v[i]->isBad()) ? 1 : 0;
+}
+}  // namespace
+
+void SearchByBoWCandidates(cms_kfstore* store, cms_ctx* frameCtx, const std::vector<KeyFrame*>& vpCandidateKFs, Frame& F,
+                           std::vector<std::vector<MapPoint*> >& vvpMapPointMatches, std::vector<bool>& vbDiscarded, std::vector<int>& nmatches,
+                           float nnratio, bool checkOri) {
+  StoreBook& b = book(store);
+  const size_t nKFs = vpCandidateKFs.size();
+  vvpMapPointMatches.assign(nKFs, std::vector<MapPoint*>());
+  vbDiscarded.assign(nKFs, false);
+  nmatches.assign(nKFs, 0);
+  std::vector<int> node_id, node_off, node_feat;
+  feat_vec_csr(F.mFeatVec, node_id, node_off, node_feat);
+  std::vector<cms_bow_job> jobs;
+  std::vector<size_t> job_kf;
+  std::vector<int> job_slot;
+  std::vector<std::vector<MapPoint*> > kf_points;
+  std::vector<std::vector<uint8_t> > skips;
+  std::vector<int> kf_idx, nm;
+  {
+    // the book stays locked from the look-up to the end of the device call: the mapping thread can neither release nor refill nor update a slot
+    // this search names meanwhile (ProcessNewKeyFrame, ReleaseKeyFrame and the updates of CreateNewMapPoints take the same lock)
+    std::lock_guard<std::mutex> lk(b.mu);
+    for (size_t i = 0; i < nKFs; ++i) {
+      KeyFrame* pKF = vpCandidateKFs[i];
+      const int slot = slot_locked(b, pKF);
+      if (pKF->isBad() || slot < 0) { vbDiscarded[i] = true; continue; }      // Tracking.cpp:1022-1023 (and a key frame that never entered the store)
+      kf_points.push_back(pKF->GetMapPointMatches());
+      skips.push_back(std::vector<uint8_t>());
+      bad_flags(kf_points.back(), skips.back());
+      job_kf.push_back(i); job_slot.push_back(slot);
+    }
+    for (size_t j = 0; j < job_kf.size(); ++j) {
+      cms_bow_job q;
+      q.slot = job_slot[j]; q.b = 0; q.n = F.N;
+      q.nnodes = (int)node_id.size(); q.node_id = node_id.data(); q.node_off = node_off.data(); q.node_feat = node_feat.data();
+      q.kf_skip = skips[j].data();
+      jobs.push_back(q);
+    }
+    kf_idx.assign(jobs.size() * (size_t)F.N + 1, -1); nm.assign(jobs.size() + 1, 0);
+    if (!jobs.empty())
+      check(cms_kfstore_search_by_bow(store, frameCtx, (int)jobs.size(), jobs.data(), nnratio, checkOri ? 1 : 0, kf_idx.data(), nm.data()),
+            "cms_kfstore_search_by_bow");
+  }
+  for (size_t j = 0; j < job_kf.size(); ++j) {
+    const size_t i = job_kf[j];
+    std::vector<MapPoint*>& out = vvpMapPointMatches[i];
+    out.assign(F.N, static_cast<MapPoint*>(NULL));
+    for (int f = 0; f < F.N; ++f) {
+      const int k = kf_idx[j * (size_t)F.N + f];
+      if (k >= 0) out[f] = kf_points[j][k];
+    }
+    nmatches[i] = nm[j];
+    if (nm[j] < 15) vbDiscarded[i] = true;                                 // Tracking.cpp:1027-1031
+  }
+}
+
+int SearchByBoW(cms_kfstore* store, cms_ctx* frameCtx, KeyFrame* pKF, Frame& F, std::vector<MapPoint*>& vpMapPointMatches, float nnratio, bool checkOri) {
+  std::vector<KeyFrame*> one(1, pKF);
+  std::vector<std::vector<MapPoint*> > m;
+  std::vector<bool> discarded;
+  std::vector<int> n;
+  if (slot_of(book(store), pKF) < 0) throw std::runtime_error("Hip::SearchByBoW: the reference key frame is not in the store");
+  SearchByBoWCandidates(store, frameCtx, one, F, m, discarded, n, nnratio, checkOri);
+  vpMapPointMatches = m[0].empty() ? std::vector<MapPoint*>(F.N, static_cast<MapPoint*>(NULL)) : m[0];
+  return n[0];
 }
 }  // namespace Hip

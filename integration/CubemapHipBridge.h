@@ -61,5 +61,17 @@ int CreateNewMapPoints(cms_kfstore* store, KeyFrame* pCurrentKF, Map* pMap, std:
 void SearchInNeighbors(cms_kfstore* store, KeyFrame* pCurrentKF);
 // after Optimizer::LocalBundleAdjustment's write-back (Optimizer.cpp:419-431): the resident copies of the local key frames get their new poses
 void UpdateKeyFramePoses(cms_kfstore* store, const std::vector<KeyFrame*>& vpKFs);
+// ---- Tracking's SearchByBoW(KeyFrame*, Frame&, ...) (ORBMatcher.cpp:409-539) against key frames resident in `store`, on the FRAME thread: F is the frame
+// `frameCtx` extracted last (slot 0 of its batch) after F.ComputeBoW().  The slot comes from the store's KeyFrame* -> slot book; a key-frame feature takes
+// part where the slot's map-point entry (as ProcessNewKeyFrame / CreateNewMapPoints last wrote it) is set and GetMapPointMatches() still holds a point
+// that is not bad.  Nothing runs on the store's stream (cms_kfstore_search_by_bow).  The store's book is locked from the look-up to the end of the call;
+// ProcessNewKeyFrame, ReleaseKeyFrame and CreateNewMapPoints' slot updates take the same lock, so no searched slot is refilled, updated or released meanwhile.
+// The body of ORBMatcher(nnratio, checkOri).SearchByBoW(pKF, F, vpMapPointMatches) in Tracking::TrackReferenceKeyFrame (Tracking.cpp:567-618).
+int SearchByBoW(cms_kfstore* store, cms_ctx* frameCtx, KeyFrame* pKF, Frame& F, std::vector<MapPoint*>& vpMapPointMatches, float nnratio, bool checkOri);
+// Tracking::Relocalization's candidate loop (Tracking.cpp:1019-1040) as ONE device call: vbDiscarded[i] for candidates that are bad (as the reference),
+// not resident, or below 15 matches; vvpMapPointMatches[i] and nmatches[i] as SearchByBoW gives them.  The PnPsolver set-up stays with the caller.
+void SearchByBoWCandidates(cms_kfstore* store, cms_ctx* frameCtx, const std::vector<KeyFrame*>& vpCandidateKFs, Frame& F,
+                           std::vector<std::vector<MapPoint*> >& vvpMapPointMatches, std::vector<bool>& vbDiscarded, std::vector<int>& nmatches,
+                           float nnratio, bool checkOri);
 }  // namespace Hip
 #endif

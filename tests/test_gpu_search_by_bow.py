@@ -1,0 +1,302 @@
+"""ORBMatcher::SearchByBoW(KeyFrame*, Frame&, ...) (src/ORBMatcher.cpp:409-539) on the device: cms_search_by_bow (key frame from the host) and
+cms_kfstore_search_by_bow (resident key frames, many jobs in one launch) against the CPU restatement tests/npref_bow.py, bit for bit."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import npref_bow
+from cubemapslam_amd import api, build, synth
+from test_search_by_bow_cpu import desc_at, fv
+
+pytestmark = pytest.mark.gpu
+KP = api.KP_DTYPE
+
+
+def _fv_of(desc, kind, keep=None):
+    """FeatureVector stand-in (DBoW2 is the host's): features binned by descriptor bits; coarse ~32 nodes, fine 1024 nodes (as in
+    test_gpu_mapping_sequence.py); keep: features to list (None = all)"""
+    n = len(desc)
+    node = (desc[:, 0].astype(np.int32) >> 3) if kind == "coarse" else (desc[:, 0].astype(np.int32) * 4 + (desc[:, 1] >> 6)) % 1024
+    order = np.lexsort((np.arange(n), node))
+    if keep is not None:
+        order = order[keep[order]]
+    ids, starts = np.unique(node[order], return_index=True)
+    return dict(node_id=ids.astype(np.int32), node_off=np.concatenate([starts, [len(order)]]).astype(np.int32), node_feat=order.astype(np.int32))
+
+
+def _keyframe(kps, desc, mp, kfv):
+    kf = dict(x=kps["x"], y=kps["y"], octave=kps["octave"], angle=kps["angle"], desc=desc, rays=np.zeros((len(desc), 3), np.float32), mp=mp,
+              R=np.eye(3, dtype=np.float32), t=np.zeros(3, np.float32), Ow=np.zeros(3, np.float32), median_depth=1.0, **kfv)
+    return kf
+
+
+def _ref(kf, skip, f_angle, f_desc, ffv, n, nnratio, ori):
+    return npref_bow.search_by_bow(kf["angle"], np.asarray(kf["desc"], np.uint8), np.asarray(kf["mp"]) >= 0, skip, kf, f_angle, f_desc, ffv, n, nnratio, ori)
+
+
+def _kps(x, y, octave, angle):
+    k = np.zeros(len(x), KP); k["x"] = x; k["y"] = y; k["octave"] = octave; k["angle"] = angle
+    return k
+
+
+@pytest.fixture(scope="module")
+def big_ctx():
+    camd = synth.camera("lafida", 550)
+    ctx = api.Context(camd, nfeatures=5000, max_batch=2)      # kp_cap > 4096: the frame side up to the frame grid's limit
+    assert ctx.geom.kp_cap > 4096
+    yield ctx
+    ctx.close()
+
+
+def _place(ctx, b, kps, desc):
+    ctx.area_set_keypoints(b, kps)
+    ctx.area_set_descriptors(b, desc)
+
+
+def _check(ctx, b, kf, skip, kps, desc, ffv, nnratio, ori):
+    K, keep = api.make_keyframe(kf)
+    got = api.search_by_bow(ctx, b, len(kps), ffv, K, skip=skip, nnratio=nnratio, check_orientation=ori)
+    want = _ref(kf, skip, kps["angle"], desc, ffv, len(kps), nnratio, ori)
+    assert np.array_equal(got[0], want[0]) and got[1] == want[1], (got[1], want[1], np.flatnonzero(got[0] != want[0])[:10])
+    return got
+
+
+@pytest.mark.parametrize("kind", ["coarse", "fine"])
+def test_synthetic_keyframes_equal_restatement(big_ctx, kind):
+    ks = synth.keyframe_set(550, n_kf=2, n_pts=2600, seed=31)
+    a, f = ks["kfs"][0], ks["kfs"][1]
+    kfv = _fv_of(a["desc"], kind)
+    kf = _keyframe(_kps(a["x"], a["y"], a["octave"], a["angle"]), a["desc"], a["mp"], kfv)
+    fk = _kps(f["x"], f["y"], f["octave"], f["angle"])
+    ffv = _fv_of(f["desc"], kind)
+    _place(big_ctx, 0, fk, f["desc"])
+    rng = np.random.default_rng(3)
+    skips = [None, (rng.random(len(a["x"])) < 0.1).astype(np.uint8)]
+    total = 0
+    for nnratio in (0.7, 0.75):
+        for ori in (True, False):
+            for skip in skips:
+                total += _check(big_ctx, 0, kf, skip, fk, f["desc"], ffv, nnratio, ori)[1]
+    assert total > 100
+
+
+@pytest.fixture(scope="module")
+def rendered():
+    F = 550
+    camd = synth.camera("lafida", F)
+    scene = synth.room_scene(0xC0FFEE)
+    poses = [synth.room_pose(i, 300) for i in (0, 3)]
+    frames = np.stack([synth.render_fisheye(camd, scene, R, t) for R, t in poses])
+    ctx = api.Context(camd, nfeatures=2000, max_batch=2)
+    ctx.set_mask(synth.cubemap_valid_mask(camd))
+    ctx.upload(frames); ctx.process(2, True); ctx.area_grid(2); ctx.sync()
+    out = [ctx.fetch(b) for b in range(2)]
+    yield camd, ctx, out
+    ctx.close()
+
+
+def test_rendered_frames_standalone_and_resident_agree(rendered):
+    camd, ctx, fr = rendered
+    (k0, d0), (k1, d1) = fr
+    assert len(k0) > 800 and len(k1) > 800
+    rng = np.random.default_rng(11)
+    mp = np.where(rng.random(len(k0)) < 0.6, np.arange(len(k0)), -1).astype(np.int32)
+    kf = _keyframe(k0, d0, mp, _fv_of(d0, "fine"))
+    ffv = _fv_of(d1, "fine")
+    skip = (rng.random(len(k0)) < 0.1).astype(np.uint8)
+    K, keep = api.make_keyframe(kf)
+    want = _ref(kf, skip, k1["angle"], d1, ffv, len(k1), 0.7, True)
+    assert want[1] > 50, want[1]
+    alone = api.search_by_bow(ctx, 1, len(k1), ffv, K, skip=skip, nnratio=0.7, check_orientation=True)
+    cg = api.Context(camd, nfeatures=2000, max_batch=1)             # the mapping side's context: the store's stream is not the frame's
+    st = api.KeyframeStore(cg, max_keyframes=4, max_features=4096, max_nodes=1024)
+    st.put(0, K)
+    res_put = st.search_by_bow(ctx, [(0, 1, len(k1), ffv, skip)], nnratio=0.7, check_orientation=True)[0]
+    st.put_from_frame(2, ctx, 0, len(k0), kf)                      # asynchronous on the frame context's stream; the search follows at once
+    res_ff = st.search_by_bow(ctx, [(2, 1, len(k1), ffv, skip)], nnratio=0.7, check_orientation=True)[0]
+    for got in (alone, res_put, res_ff):
+        assert np.array_equal(got[0], want[0]) and got[1] == want[1]
+    # the store's copy was put from the frame context of ANOTHER thread's stream: a search from a third context waits for that copy on the device
+    ctx2 = api.Context(camd, nfeatures=2000, max_batch=2)
+    ctx2.area_set_keypoints(1, k1); ctx2.area_set_descriptors(1, d1)
+    st.put_from_frame(3, ctx, 0, len(k0), kf)
+    res_x = st.search_by_bow(ctx2, [(3, 1, len(k1), ffv, skip)], nnratio=0.7, check_orientation=True)[0]
+    assert np.array_equal(res_x[0], want[0]) and res_x[1] == want[1]
+    st.close(); cg.close(); ctx2.close()
+
+
+def test_batched_jobs_equal_single_calls():
+    F = 550
+    camd = synth.camera("lafida", F)
+    B = 8
+    ctx = api.Context(camd, nfeatures=2000, max_batch=B)
+    ctx.set_mask(synth.cubemap_valid_mask(camd))
+    base = synth.texture(camd["Ih"], camd["Iw"], 5)
+    frames = np.stack([np.roll(base, 3 * b, axis=1) for b in range(B)])      # overlapping views: real matches between neighbours
+    ctx.upload(frames); ctx.process(B, True); ctx.area_grid(B); ctx.sync()
+    fr = [ctx.fetch(b) for b in range(B)]
+    cg = api.Context(camd, nfeatures=2000, max_batch=1)
+    st = api.KeyframeStore(cg, max_keyframes=B + 1, max_features=4096, max_nodes=1024)
+    rng = np.random.default_rng(5)
+    kfs = []
+    for b in range(B):
+        k, d = fr[b]
+        mp = np.where(rng.random(len(k)) < 0.5, np.arange(len(k)), -1).astype(np.int32)
+        kfs.append(_keyframe(k, d, mp, _fv_of(d, "fine")))
+    nomp = dict(kfs[0]); nomp["mp"] = np.full(len(fr[0][0]), -1, np.int32)
+    st.put_from_frames(ctx, [(b, b, len(fr[b][0]), kfs[b]) for b in range(B)] + [(B, 0, len(fr[0][0]), nomp)])
+    kfs.append(nomp)
+    jobs = []
+    for b in range(B):
+        k, d = fr[b]
+        ffv = _fv_of(d, "fine")
+        for s in ((b + 1) % B, (b + 2) % B, (b + 5) % B, b if b % 2 else B):
+            skip = (rng.random(len(kfs[s]["mp"])) < 0.1).astype(np.uint8) if (b + s) % 3 == 0 else None
+            jobs.append((s, b, len(k), ffv, skip))
+    jobs.append((1, 2, len(fr[2][0]), dict(node_id=[], node_off=[0], node_feat=[]), None))      # empty FeatureVector
+    jobs.append((3, 4, 0, dict(node_id=[], node_off=[0], node_feat=[]), None))                   # a frame with 0 key points
+    got = st.search_by_bow(ctx, jobs, nnratio=0.75, check_orientation=True)
+    assert len(got) == len(jobs) >= 32
+    total = 0
+    for job, g in zip(jobs, got):
+        s, b, n, ffv, skip = job
+        single = st.search_by_bow(ctx, [job], nnratio=0.75, check_orientation=True)[0]
+        want = _ref(kfs[s], skip, fr[b][0]["angle"][:n], fr[b][1][:n], ffv, n, 0.75, True)
+        assert np.array_equal(g[0], single[0]) and g[1] == single[1], job[:3]
+        assert np.array_equal(g[0], want[0]) and g[1] == want[1], job[:3]
+        total += g[1]
+    assert total > 100, total
+    assert got[-2][1] == 0 and got[-1][1] == 0 and len(got[-1][0]) == 0
+    assert all(g[1] == 0 for j, g in zip(jobs, got) if j[0] == B)
+    st.close(); cg.close(); ctx.close()
+
+
+CASES = [  # the hand-built cases of test_search_by_bow_cpu.py: (kf rows, frame rows, kf fv, frame fv, kf angle, f angle, has_mp, bad, nnratio, ori)
+    ([0], [20, 20], {5: [0]}, {5: [0, 1]}, None, None, None, None, 0.7, False),
+    ([0, 0, 0], [10, 30, 10], {5: [0, 1], 9: [2]}, {5: [0, 1], 9: [2]}, None, None, None, None, 0.7, False),
+    ([0], [50], {1: [0]}, {1: [0]}, None, None, None, None, 0.7, False),
+    ([0], [51], {1: [0]}, {1: [0]}, None, None, None, None, 0.7, False),
+    ([0], [35, 50], {1: [0]}, {1: [0, 1]}, None, None, None, None, 0.7, False),
+    ([0], [34, 50], {1: [0]}, {1: [0, 1]}, None, None, None, None, 0.7, False),
+    ([0, 0, 0], [10, 10, 10], {1: [0], 2: [1], 3: [2]}, {1: [0], 2: [1], 3: [2]}, [359.9, 0.0, 100.0], [0.0] * 3, None, None, 0.7, True),
+    ([0] * 12, [10] * 12, {i: [i] for i in range(12)}, {i: [i] for i in range(12)}, [0.0] * 11 + [120.0], [0.0] * 12, None, None, 0.7, True),
+    ([0] * 12, [10] * 12, {i: [i] for i in range(12)}, {i: [i] for i in range(12)}, [0.0] * 9 + [120.0, 240.0, 300.0], [0.0] * 12, None, None, 0.7, True),
+    ([0] * 12, [10] * 12, {i: [i] for i in range(12)}, {i: [i] for i in range(12)}, [0.0] * 11 + [120.0], [0.0] * 12, None, None, 0.7, False),
+    ([0, 0], [10, 10], {1: [0], 4: [1]}, {2: [0], 4: [1]}, None, None, None, None, 0.7, False),
+    ([0, 0], [10, 30], {5: [0, 1]}, {5: [0, 1]}, None, None, [False, True], None, 0.7, False),
+    ([0, 0], [10, 30], {5: [0, 1]}, {5: [0, 1]}, None, None, None, [1, 0], 0.7, False),
+]
+EXPECT_N = [0, 3, 1, 0, 0, 1, 3, 11, 11, 12, 1, 1, 1]
+
+
+def test_hand_built_cases_through_the_device(big_ctx):
+    for c_, en in zip(CASES, EXPECT_N):
+        kr, fr_, kfv, ffv, ka, fa, hm, bad, nnr, ori = c_
+        nk, n = len(kr), len(fr_)
+        kd = np.zeros((nk, 32), np.uint8)
+        fd = np.stack([desc_at(d, 7 * i) for i, d in enumerate(fr_)])
+        kk = _kps(np.full(nk, 100.0), np.full(nk, 100.0), np.zeros(nk), np.zeros(nk) if ka is None else ka)
+        fk = _kps(np.full(n, 100.0), np.full(n, 100.0), np.zeros(n), np.zeros(n) if fa is None else fa)
+        mp = np.where(np.ones(nk, bool) if hm is None else np.asarray(hm, bool), np.arange(nk), -1).astype(np.int32)
+        ki, ko, kf_ = fv(kfv)
+        fi, fo, ff = fv(ffv)
+        kf = _keyframe(kk, kd, mp, dict(node_id=ki, node_off=ko, node_feat=kf_))
+        _place(big_ctx, 1, fk, fd)
+        got = _check(big_ctx, 1, kf, None if bad is None else np.asarray(bad, np.uint8), fk, fd, (fi, fo, ff), nnr, ori)
+        assert got[1] == en, (c_, got)
+
+
+def test_frame_above_4096_key_points(big_ctx):
+    rng = np.random.default_rng(17)
+    n = 4600
+    assert n <= big_ctx.geom.kp_cap
+    fd = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    fk = _kps(rng.uniform(0, 1600, n), rng.uniform(0, 1600, n), rng.integers(0, 8, n), rng.uniform(0, 360, n).astype(np.float32))
+    sel = rng.choice(n, 2000, replace=False)
+    kd = fd[sel].copy()
+    flips = rng.integers(0, 256, (2000, 8))
+    for j in range(8):
+        kd[np.arange(2000), flips[:, j] >> 3] ^= (1 << (flips[:, j] & 7)).astype(np.uint8)
+    kk = _kps(fk["x"][sel], fk["y"][sel], fk["octave"][sel], (fk["angle"][sel] + rng.normal(0, 4, 2000).astype(np.float32)) % np.float32(360))
+    kf = _keyframe(kk, kd, np.where(rng.random(2000) < 0.7, np.arange(2000), -1).astype(np.int32), _fv_of(kd, "coarse"))
+    _place(big_ctx, 0, fk, fd)
+    got = _check(big_ctx, 0, kf, None, fk, fd, _fv_of(fd, "coarse"), 0.75, True)
+    assert got[1] > 500
+    again = _check(big_ctx, 0, kf, None, fk, fd, _fv_of(fd, "coarse"), 0.75, True)      # repeatability: the same call twice
+    assert np.array_equal(got[0], again[0]) and got[1] == again[1]
+
+
+def test_argument_errors(big_ctx):
+    ks = synth.keyframe_set(550, n_kf=2, n_pts=800, seed=8)
+    a, f = ks["kfs"][0], ks["kfs"][1]
+    kf = _keyframe(_kps(a["x"], a["y"], a["octave"], a["angle"]), a["desc"], a["mp"], _fv_of(a["desc"], "fine"))
+    K, keep = api.make_keyframe(kf)
+    fk = _kps(f["x"], f["y"], f["octave"], f["angle"])
+    _place(big_ctx, 0, fk, f["desc"])
+    n = len(fk)
+    good = _fv_of(f["desc"], "fine")
+
+    def rc_of(fn):
+        with pytest.raises(api.CmsError) as e:
+            fn()
+        return int(str(e.value).split("(")[1].split(")")[0])
+
+    assert api.search_by_bow(big_ctx, 0, n, good, K)[1] >= 0
+    bad_order = dict(good); bad_order["node_id"] = good["node_id"][::-1].copy()
+    twice = dict(good); twice["node_feat"] = good["node_feat"].copy(); twice["node_feat"][1] = twice["node_feat"][0]
+    too_big = dict(good); too_big["node_feat"] = good["node_feat"].copy(); too_big["node_feat"][0] = n
+    for fvx in (bad_order, twice, too_big):
+        assert rc_of(lambda: api.search_by_bow(big_ctx, 0, n, fvx, K)) == -1
+    assert rc_of(lambda: api.search_by_bow(big_ctx, 2, n, good, K)) == -1                  # b out of range (max_batch 2)
+    assert rc_of(lambda: api.search_by_bow(big_ctx, -1, n, good, K)) == -1
+    assert rc_of(lambda: api.search_by_bow(big_ctx, 0, 16384, good, K)) == -3              # above CMS_AREA_MAXKP
+    big = _keyframe(_kps(np.zeros(4097), np.zeros(4097), np.zeros(4097), np.zeros(4097)), np.zeros((4097, 32), np.uint8), np.zeros(4097, np.int32),
+                    dict(node_id=[0], node_off=[0, 1], node_feat=[0]))
+    KB, keepb = api.make_keyframe(big)
+    assert rc_of(lambda: api.search_by_bow(big_ctx, 0, n, good, KB)) == -3                 # stand-alone key frame above 4096 features
+    cg = api.Context(synth.camera("lafida", 550), nfeatures=2000, max_batch=1)
+    st = api.KeyframeStore(cg, max_keyframes=3, max_features=4096, max_nodes=1024)
+    st.put(0, K)
+    assert st.search_by_bow(big_ctx, [(0, 0, n, good, None)])[0][1] >= 0
+    assert rc_of(lambda: st.search_by_bow(big_ctx, [(1, 0, n, good, None)])) == -1          # empty slot
+    assert rc_of(lambda: st.search_by_bow(big_ctx, [(0, 2, n, good, None)])) == -1          # b out of range
+    for fvx in (bad_order, twice, too_big):
+        assert rc_of(lambda: st.search_by_bow(big_ctx, [(0, 0, n, good, None), (0, 0, n, fvx, None)])) == -1
+    st.close(); cg.close()
+
+
+def test_mirror_search_by_bow_equals_restatement():
+    build.build(verbose=False)
+    api.lib()
+    L = C.CDLL(build.HOST_LIB)
+    L.hm_last_error.restype = C.c_char_p
+    L.hm_extract.argtypes = [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    L.hm_search_by_bow.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 3 + \
+                                  [C.c_float, C.c_int, C.c_void_p]
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    F = 450
+    camd = synth.camera("lafida", F)
+    cam = api.make_camera(camd)
+    assert L.hm_set_camera(C.byref(cam)) == 0
+    W = 3 * F                                                       # a Frame always comes from an ORBextractor: constructing one sizes the shared context
+    img = np.ascontiguousarray(synth.texture(W, W, 70)); msk = np.full((W, W), 255, np.uint8)
+    k0 = np.zeros(3000, KP); d0 = np.zeros((3000, 32), np.uint8)
+    assert L.hm_extract(2000, 1.2, 8, 20, 7, p(img), W, p(msk), W, p(k0), p(d0), 3000) > 0, L.hm_last_error()
+    ks = synth.keyframe_set(F, n_kf=2, n_pts=1700, seed=44)
+    a, f = ks["kfs"][0], ks["kfs"][1]
+    kfv = _fv_of(a["desc"], "coarse"); ffv = _fv_of(f["desc"], "coarse")
+    ang = lambda q: ((q["point"] * 37) % 360).astype(np.float32)   # one angle per scene point: the histogram keeps most matches
+    kk = _kps(a["x"], a["y"], a["octave"], ang(a)); fk = _kps(f["x"], f["y"], f["octave"], ang(f))
+    mp_ids = np.where(a["mp"] >= 0, 1000 + np.arange(len(a["mp"])), -1).astype(np.int64)
+    bad = (np.random.default_rng(2).random(len(mp_ids)) < 0.1).astype(np.uint8)
+    n = len(fk)
+    out = np.full(n, -7, np.int64)
+    kd = np.ascontiguousarray(a["desc"]); fd = np.ascontiguousarray(f["desc"])
+    nm = L.hm_search_by_bow(len(kk), p(kk), p(kd), p(mp_ids), p(bad), len(kfv["node_id"]), p(kfv["node_id"]), p(kfv["node_off"]), p(kfv["node_feat"]),
+                            n, p(fk), p(fd), len(ffv["node_id"]), p(ffv["node_id"]), p(ffv["node_off"]), p(ffv["node_feat"]), 0.7, 1, p(out))
+    assert nm >= 0, L.hm_last_error()
+    kf = _keyframe(kk, kd, a["mp"], kfv)
+    want_idx, want_n = _ref(kf, bad, fk["angle"], fd, ffv, n, 0.7, True)
+    want = np.where(want_idx >= 0, mp_ids[np.maximum(want_idx, 0)], -1)
+    assert nm == want_n and want_n > 50 and np.array_equal(out, want)
