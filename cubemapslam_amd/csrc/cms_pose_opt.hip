@@ -129,6 +129,19 @@ __device__ __forceinline__ void pose_block_sum28(const double* acc, double (*sh)
   __syncthreads();
 }
 
+// sum of v over the workgroup, added in the order in which pose_block_sum28 adds its 28th element (the chi2 of the linearisation pass): a trial
+// that changes no residual -- the projection is cast to float, so a small enough step changes none -- then returns the very bits of currentChi,
+// rho is exactly 0 and the round ends there, as it does in g2o, where both sums are one function.  (block_sum adds the four wavefronts' sums one
+// after the other, pose_block_sum28 in pairs: the two chi2 of an unchanged frame of more than 128 edges differed in the last bit, and the round
+// went on with ten rejected trials or with "accepted" steps that moved the pose by ~1e-8 of the update.)
+__device__ __forceinline__ double pose_block_sum1(double v, double* sh) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();                       // previous readers of sh are done
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
 // (generic variant: edges stay in global memory; used for frames with more than 256 x PO_MAXJ edges)
 extern "C" __global__ void __launch_bounds__(256) k_pose_optimize_g(PoseDev P) {
   __shared__ double sh28[4][28];
@@ -239,7 +252,7 @@ extern "C" __global__ void __launch_bounds__(256) k_pose_optimize_g(PoseDev P) {
               chi += rho0;
             }
           }
-          const double tempChi0 = block_sum(chi, &sh28[0][0]);
+          const double tempChi0 = pose_block_sum1(chi, &sh28[0][0]);
           if (tid == 0) {
             double tempChi = ok2 ? tempChi0 : 1.7976931348623157e308;
             rho = (currentChi - tempChi) / (scale + 1e-3);
@@ -311,7 +324,8 @@ extern "C" __global__ void __launch_bounds__(256) k_pose_optimize_g(PoseDev P) {
 // The same procedure with a frame's edges held in REGISTERS: thread t owns edges t, t + 256, ... (PO_MAXJ of them, i.e. frames of up to
 // 256 x PO_MAXJ edges); world point, measurement, information, face, the persistent error and the outlier flag never go back to memory
 // during the ~80 dependent passes of the four rounds -- the global-memory latency of every pass was most of the kernel's time.
-// Arithmetic and order of operations are those of k_pose_optimize_g above.
+// Arithmetic and order of operations are those of k_pose_optimize_g above: on an MI355X the two return the same bits for every frame of the parity
+// matrix (tests/test_gpu_pose_matrix.py asserts it; profiles/pose_parity_matrix.md) -- a change to one has to be made to the other.
 #define PO_MAXJ 4
 extern "C" __global__ void __launch_bounds__(256) k_pose_optimize(PoseDev P) {
   __shared__ double sh28[4][28];
@@ -437,7 +451,7 @@ extern "C" __global__ void __launch_bounds__(256) k_pose_optimize(PoseDev P) {
               chi += rho0;
             }
           }
-          const double tempChi0 = block_sum(chi, &sh28[0][0]);
+          const double tempChi0 = pose_block_sum1(chi, &sh28[0][0]);
           if (tid == 0) {
             double tempChi = ok2 ? tempChi0 : 1.7976931348623157e308;
             rho = (currentChi - tempChi) / (scale + 1e-3);

@@ -502,7 +502,11 @@ int cms_kfstore_search_by_bow(cms_kfstore* st, cms_ctx* src, int njobs, const cm
  * map point whose key ray passes the FoV test: Xw (world point), obs_uv = GetPosInFace(kp.pt), face = FaceInCubemap(kp.pt),
  * inv_sigma2 = mvInvLevelSigma2[kp.octave]; edge_off[f]..edge_off[f+1] are frame f's edges.  poses7: nf x (tx,ty,tz,qx,qy,qz,qw),
  * world->camera, in/out.  outlier: one byte per edge (pFrame->mvbOutlier).  n_inliers[f] = nInitialCorrespondences - nBad, or 0
- * and an untouched pose when the frame has fewer than 3 edges. */
+ * and an untouched pose when the frame has fewer than 3 edges.
+ * A frame's result is a function of the frame and the four intrinsics alone, to the last bit: it does not depend on the frame's position or
+ * company in the batch (a frame above 1024 edges sends the whole batch through the kernel that keeps the edges in memory instead of in
+ * registers: same bits), nor on the entry point (cms_pose_optimize_batch with few or many frames, upload / launch / fetch, cms_pose_optimize),
+ * nor on what the handle was used for before (tests/test_gpu_pose_matrix.py). */
 typedef struct cms_pose cms_pose;
 typedef struct { int rounds, n_bad; int iterations_done[4]; } cms_pose_stats;
 int cms_pose_create(cms_pose** out, int device, int max_frames, int max_edges);

@@ -11,9 +11,9 @@ import npref_ba as nb
 
 def pose_optimize(pr):
     N = len(pr["Xw"])
+    if N < 3:                                                   # Optimizer.cpp:131-132: the frame's pose is not touched
+        return 0, pr["pose0"].copy(), np.zeros(N, np.uint8), []
     pose0 = pr["pose0"].copy(); pose0[3:] = nb.normalize_rot(pose0[3:])
-    if N < 3:
-        return 0, pose0, np.zeros(N, np.uint8), []
     prob = dict(fx=pr["fx"], fy=pr["fy"], cx=pr["cx"], cy=pr["cy"])
     err = np.zeros((N, 2)); level = np.zeros(N, int); outlier = np.zeros(N, np.uint8)
     use_kernel = True
@@ -57,11 +57,15 @@ def pose_optimize(pr):
                     lam = 1e-5 * np.abs(np.diag(H)).max(); ni = 2.0; nbad_it = 0
                 rho, qmax = 0.0, 0
                 while True:
-                    x = np.linalg.solve(H + lam * np.eye(6), b)
+                    try:
+                        x = np.linalg.solve(H + lam * np.eye(6), b); solved = True
+                    except np.linalg.LinAlgError:                       # optimization_algorithm_levenberg.cpp: a failed solve is a zero
+                        x = np.zeros(6); solved = False                 # step whose chi2 counts as the largest double
                     trial = nb.pose_update(pose, x)
                     compute(edges, trial)
-                    temp = rchi(edges)
-                    rho = (cur - temp) / (float(x @ (lam * x + b)) + 1e-3)
+                    temp = rchi(edges) if solved else np.finfo(np.float64).max
+                    with np.errstate(over="ignore"):
+                        rho = np.float64(cur - temp) / (float(x @ (lam * x + b)) + 1e-3)
                     if rho > 0 and np.isfinite(temp):
                         lam *= max(1.0 / 3.0, min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0)); ni = 2.0; cur = temp; pose = trial
                     else:
