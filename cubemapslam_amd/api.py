@@ -70,6 +70,7 @@ def lib():
         L.cms_frames_upload_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_int]
         L.cms_frames_upload_wait.argtypes = [C.c_void_p]
         L.cms_frames_upload_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.cms_frames_process_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.cms_host_alloc.argtypes = [C.c_void_p, C.c_size_t]
         L.cms_host_free.argtypes = [C.c_void_p]
         L.cms_host_free.restype = None
@@ -173,6 +174,36 @@ def make_camera(d):
     for i in range(5):
         cam.pol[i] = d["pol"][i] if i < len(d["pol"]) else 0.0
     return cam
+
+
+RT_DTYPE = np.dtype([(n, "<u2") for n in ("tx", "ty", "x0", "y0", "nd", "rows", "flags", "pad")])   # cms_remap_tile
+RT_LDS_MAX = 32768      # CMS_RT_LDS_MAX: the LDS budget cms_ctx_create builds the table with
+
+
+def remap_lut_host(cam):
+    """cms_remap_lut_host: the packed remap LUT [3F][3F] u32, built on the host (no device)"""
+    cam = make_camera(cam) if isinstance(cam, dict) else cam
+    W = 3 * cam.face
+    out = np.zeros((W, (W + 3) // 4 * 4), np.uint32)
+    f = lib().cms_remap_lut_host
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    _chk(f(C.byref(cam), _p(out), out.shape[1]), "cms_remap_lut_host")
+    return out[:, :W]
+
+
+def remap_tiles_host(cam, lut, tile_w, tile_h, lds_budget=RT_LDS_MAX):
+    """cms_remap_tiles_host: (tiles as RT_DTYPE records, n_live, lds_bytes) of the remap's tile table, built on the host"""
+    cam = make_camera(cam) if isinstance(cam, dict) else cam
+    lut = np.ascontiguousarray(lut, np.uint32)
+    W = 3 * cam.face
+    cap = ((W + tile_w - 1) // tile_w) * ((W + tile_h - 1) // tile_h)
+    out = np.zeros(cap, RT_DTYPE)
+    n_live, n_all, lds = C.c_int(), C.c_int(), C.c_int()
+    f = lib().cms_remap_tiles_host
+    f.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+    _chk(f(C.byref(cam), _p(lut), lut.strides[0] // 4, tile_w, tile_h, lds_budget, _p(out), cap, C.byref(n_live), C.byref(n_all), C.byref(lds)),
+         "cms_remap_tiles_host")
+    return out[:n_all.value].copy(), n_live.value, lds.value
 
 
 class Context:
@@ -279,6 +310,10 @@ class Context:
     def upload_device(self, d_ptr, B):
         """staging <- device buffer [B][Ih][fisheye_stride] (inputs resident in HBM), asynchronous on the ctx stream"""
         _chk(lib().cms_frames_upload_device(self.h, C.c_void_p(int(d_ptr)), B), "cms_frames_upload_device")
+
+    def process_device(self, d_ptr, B):
+        """process(B) on a device buffer [B][Ih][fisheye_stride] read in place (no staging copy); the caller keeps it untouched until sync()"""
+        _chk(lib().cms_frames_process_device(self.h, C.c_void_p(int(d_ptr)), B), "cms_frames_process_device")
 
     def stream_wait_extracted(self, hip_stream):
         """the given HIP stream waits (on the device) for the extraction of this context's last process() call"""

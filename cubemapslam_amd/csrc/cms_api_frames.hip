@@ -69,6 +69,8 @@ struct cms_ctx {
   int dirty_frames = 0;       // leading frames whose corner blocks may be non-zero (a caller-supplied canvas went through them)
   // device buffers
   uint8_t* d_fish = nullptr; uint32_t* d_lut = nullptr; uint8_t* d_pyr = nullptr; uint8_t* d_mask = nullptr;
+  // remap tile table (cms_remap_tiles.h): rt_mode 0 = k_remap (CMS_REMAP_TILES=0), 1 = tiles staged in LDS, 2 = tiles with direct gathers
+  cms_remap_tile* d_rtiles = nullptr; int rt_mode = 1, rt_tw = 64, rt_live = 0, rt_all = 0, rt_lds = 0;
   CmsResizeTab* d_tab = nullptr; float* d_pattern = nullptr;     // the 256 x 4 test coordinates as floats (what the kernel multiplies)
   uint32_t* d_cand = nullptr; uint16_t* d_node = nullptr; int* d_cand_cnt = nullptr; int* d_overflow = nullptr;
   uint32_t* d_qt_out = nullptr; int* d_qt_cnt = nullptr;
@@ -154,6 +156,25 @@ static void cms_build_lut(const cms_camera& cam, int lut_stride, std::vector<uin
     }
 }
 
+extern "C" int cms_remap_lut_host(const cms_camera* cam, uint32_t* lut, int lut_stride) {
+  if (!cam || !lut || cam->face < 1 || lut_stride < 3 * cam->face) return cms_fail(CMS_ERR_ARG, "cms_remap_lut_host: bad argument");
+  std::vector<uint32_t> v;
+  cms_build_lut(*cam, lut_stride, v);
+  memcpy(lut, v.data(), v.size() * 4);
+  return CMS_OK;
+}
+extern "C" int cms_remap_tiles_host(const cms_camera* cam, const uint32_t* lut, int lut_stride, int tile_w, int tile_h, int lds_budget,
+                                    cms_remap_tile* out, int cap, int* n_live, int* n_all, int* lds_bytes) {
+  if (!cam || !lut || !out || !n_live || !n_all || !lds_bytes || cam->face < 1 || lut_stride < 3 * cam->face || !cms_rt_shape_ok(tile_w, tile_h) || lds_budget < 0)
+    return cms_fail(CMS_ERR_ARG, "cms_remap_tiles_host: bad argument");
+  std::vector<cms_remap_tile> v;
+  cms_rt_build(cam->face, lut, lut_stride, tile_w, tile_h, lds_budget, v, n_live, lds_bytes);
+  *n_all = (int)v.size();
+  if ((int)v.size() > cap) return cms_fail(CMS_ERR_OVERFLOW, "cms_remap_tiles_host: caller capacity too small");
+  memcpy(out, v.data(), v.size() * sizeof(cms_remap_tile));
+  return CMS_OK;
+}
+
 static inline short cms_sat_short(float v) {
   const long iv = lrint((double)v);
   return (short)(iv < -32768 ? -32768 : iv > 32767 ? 32767 : iv);
@@ -183,7 +204,7 @@ static void cms_ctx_free(cms_ctx* c) {
   hipSetDevice(c->device);
   void* ptrs[] = {c->d_fish, c->d_lut, c->d_pyr, c->d_mask, c->d_tab, c->d_pattern, c->d_cand, c->d_node, c->d_cand_cnt,
                   c->d_overflow, c->d_qt_out, c->d_qt_cnt, c->d_kps, c->d_aux, c->d_order, c->d_aux_sorted, c->d_desc, c->d_kp_cnt, c->d_match, c->d_cell_cand,
-                  c->d_cell_cnt, c->d_cells_all, c->d_cells_nz, c->d_area_sorted, c->d_area_cell_start, c->d_area_nvalid, c->d_area_bsum, c->d_area_tmp, c->d_walk_cnt, c->d_rays};
+                  c->d_cell_cnt, c->d_cells_all, c->d_cells_nz, c->d_area_sorted, c->d_area_cell_start, c->d_area_nvalid, c->d_area_bsum, c->d_area_tmp, c->d_walk_cnt, c->d_rays, c->d_rtiles};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->h_fish_stage) (void)hipHostFree(c->h_fish_stage);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -330,6 +351,21 @@ extern "C" int cms_ctx_create(cms_ctx** out, int device, const cms_camera* cam, 
     std::vector<uint32_t> lut;
     cms_build_lut(*cam, c->lut_stride, lut);
     hipMemcpy(c->d_lut, lut.data(), lut.size() * 4, hipMemcpyHostToDevice);
+    // The remap's tile table: camera and face size are fixed for the life of the context.  Developer switches: CMS_REMAP_TILES=0 the row-strip
+    // kernel k_remap, =2 the 2-D tiles with direct gathers only (no LDS staging); CMS_REMAP_TILE_W=32|64|128 the tile shape (x 32 | 16 | 8 rows).
+    {
+      const char* m = getenv("CMS_REMAP_TILES"); const char* tw = getenv("CMS_REMAP_TILE_W");
+      c->rt_mode = m && *m ? atoi(m) : 1;
+      c->rt_tw = tw && *tw ? atoi(tw) : 64;
+      if (c->rt_mode < 0 || c->rt_mode > 2 || !cms_rt_shape_ok(c->rt_tw, CMS_RT_PIXELS / std::max(c->rt_tw, 1))) {
+        cms_ctx_free(c); return cms_fail(CMS_ERR_ARG, "CMS_REMAP_TILES must be 0, 1 or 2 and CMS_REMAP_TILE_W 32, 64 or 128");
+      }
+      std::vector<cms_remap_tile> tiles;
+      cms_rt_build(F, lut.data(), c->lut_stride, c->rt_tw, CMS_RT_PIXELS / c->rt_tw, c->rt_mode == 1 ? CMS_RT_LDS_MAX : 0, tiles, &c->rt_live, &c->rt_lds);
+      c->rt_all = (int)tiles.size();
+      if (hipMalloc((void**)&c->d_rtiles, tiles.size() * sizeof(cms_remap_tile)) != hipSuccess) { cms_ctx_free(c); return cms_fail(CMS_ERR_HIP, "hipMalloc tile table"); }
+      hipMemcpy(c->d_rtiles, tiles.data(), tiles.size() * sizeof(cms_remap_tile), hipMemcpyHostToDevice);
+    }
     std::vector<CmsResizeTab> tab(tab_off);
     for (int l = 1; l < L; ++l) {
       cms_resize_table(g.lv[l - 1].w, g.lv[l].w, true, &tab[g.lv[l].tab_off]);
@@ -526,7 +562,27 @@ extern "C" int cms_set_mask(cms_ctx* c, const uint8_t* mask, int mstride) {
   return CMS_OK;
 }
 
-static int cms_launch_frames(cms_ctx* c, int B, int from_fisheye) {
+// the remap of frames [0, B) of `src` (staging layout) into level 0 of the pyramid buffer
+static void cms_launch_remap(cms_ctx* c, const uint8_t* src, int B, int write_corners, hipStream_t s) {
+  const CmsGeom& g = c->g;
+  const int ngroups = (B + CMS_REMAP_FPT - 1) / CMS_REMAP_FPT;
+  if (c->rt_mode == 0) {
+    dim3 grid((g.W / 4 + 255) / 256 + 1, g.W, std::min(ngroups, CMS_REMAP_ZSPLIT));
+    hipLaunchKernelGGL(k_remap, grid, dim3(256), 0, s, src, c->fish_pitch, c->fstride, c->cam.Iw,
+                       c->cam.Ih, (const uint32_t*)c->d_lut, c->lut_stride, c->d_pyr, g.pyr_bytes, g.W, g.lv[0].stride, g.F, write_corners, B);
+    return;
+  }
+  CmsRemapArgs a;
+  a.fish = src; a.fish_pitch = c->fish_pitch; a.fstride = c->fstride; a.Iw = c->cam.Iw; a.Ih = c->cam.Ih;
+  a.lut = c->d_lut; a.lut_stride = c->lut_stride; a.tiles = c->d_rtiles;
+  a.pyr = c->d_pyr; a.pyr_bytes = g.pyr_bytes; a.W = g.W; a.stride0 = g.lv[0].stride; a.F = g.F; a.write_corners = write_corners; a.B = B;
+  const bool st = c->rt_mode == 1;
+  auto k = c->rt_tw == 32 ? (st ? k_remap_t32 : k_remap_t32d) : c->rt_tw == 64 ? (st ? k_remap_t64 : k_remap_t64d) : (st ? k_remap_t128 : k_remap_t128d);
+  dim3 grid(std::min(ngroups, CMS_REMAP_TILE_ZSPLIT), write_corners ? c->rt_all : c->rt_live, 1);       // the dead tiles are listed last
+  hipLaunchKernelGGL(k, grid, dim3(256), st ? (size_t)c->rt_lds : 0, s, a);
+}
+
+static int cms_launch_frames(cms_ctx* c, int B, int from_fisheye, const uint8_t* d_src = nullptr) {
   c->last_batch = B;
   c->g.skip_zero_cells = from_fisheye ? 1 : 0;   // a caller-supplied canvas (cms_extract) may hold anything in its corner blocks
   // the corner blocks of every level are 0 from cms_ctx_create on and k_remap never writes there; only a caller-supplied canvas
@@ -539,10 +595,8 @@ static int cms_launch_frames(cms_ctx* c, int B, int from_fisheye) {
   hipStream_t s = c->stream;
   if (c->prof) hipEventRecord(c->ev[0], s);
   if (from_fisheye) {
-    if (c->upload_pending) { HIPCHK(hipStreamWaitEvent(s, c->ev_upload_done, 0)); c->upload_pending = false; }   // streamed input (cms_frames_upload_async)
-    dim3 grid((g.W / 4 + 255) / 256 + 1, g.W, std::min((B + CMS_REMAP_FPT - 1) / CMS_REMAP_FPT, CMS_REMAP_ZSPLIT));
-    hipLaunchKernelGGL(k_remap, grid, dim3(256), 0, s, (const uint8_t*)c->d_fish, c->fish_pitch, c->fstride, c->cam.Iw,
-                       c->cam.Ih, (const uint32_t*)c->d_lut, c->lut_stride, c->d_pyr, g.pyr_bytes, g.W, g.lv[0].stride, g.F, clean ? 0 : 1, B);
+    if (c->upload_pending && !d_src) { HIPCHK(hipStreamWaitEvent(s, c->ev_upload_done, 0)); c->upload_pending = false; }   // streamed input (cms_frames_upload_async)
+    cms_launch_remap(c, d_src ? d_src : c->d_fish, B, clean ? 0 : 1, s);
     if (c->copy_stream) { HIPCHK(hipEventRecord(c->ev_remap_done, s)); c->remap_recorded = true; }   // the staging buffer is free from here on
   }
   if (c->prof) hipEventRecord(c->ev[1], s);
@@ -641,6 +695,17 @@ extern "C" int cms_frames_process(cms_ctx* c, int B, int from_fisheye) {
   HIPCHK(hipSetDevice(c->device));
   return cms_launch_frames(c, B, from_fisheye);
 }
+// The resident batch is read where it lies.  k_remap (CMS_REMAP_TILES=0) reads the byte behind a row's last pixel and so needs the slack behind the
+// staging buffer: that switch keeps the copy.
+extern "C" int cms_frames_process_device(cms_ctx* c, const void* d_src, int B) {
+  if (!c || !d_src || ((uintptr_t)d_src & 3) || B < 1 || B > c->max_batch) return cms_fail(CMS_ERR_ARG, "cms_frames_process_device: bad argument");
+  HIPCHK(hipSetDevice(c->device));
+  if (c->rt_mode == 0) {
+    HIPCHK(hipMemcpyAsync(c->d_fish, d_src, c->fish_pitch * (size_t)B, hipMemcpyDeviceToDevice, c->stream));
+    return cms_launch_frames(c, B, 1);
+  }
+  return cms_launch_frames(c, B, 1, (const uint8_t*)d_src);
+}
 extern "C" int cms_frames_sync(cms_ctx* c) {
   if (!c) return cms_fail(CMS_ERR_ARG, "null ctx");
   HIPCHK(hipSetDevice(c->device));
@@ -707,9 +772,7 @@ extern "C" int cms_remap(cms_ctx* c, const uint8_t* fisheye, int fstride, uint8_
   int rc = cms_frames_upload(c, fisheye, fstride, 0, 1);
   if (rc) return rc;
   const CmsGeom& g = c->g;
-  dim3 grid((g.W / 4 + 255) / 256 + 1, g.W, 1);
-  hipLaunchKernelGGL(k_remap, grid, dim3(256), 0, c->stream, (const uint8_t*)c->d_fish, c->fish_pitch, c->fstride, c->cam.Iw,
-                     c->cam.Ih, (const uint32_t*)c->d_lut, c->lut_stride, c->d_pyr, g.pyr_bytes, g.W, g.lv[0].stride, g.F, 1, 1);
+  cms_launch_remap(c, c->d_fish, 1, 1, c->stream);
   const int F = g.F;
   const int fx0[5] = {F, 0, 2 * F, F, F}, fy0[5] = {F, F, F, 0, 2 * F};
   for (int f = 0; f < 5; ++f)

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "cms_types.h"
+#include "cms_remap_tiles.h"
 #include "cms_detmath.h"
 #include "cms_quadtree_core.h"
 
@@ -32,6 +33,9 @@
 #ifndef CMS_REMAP_ZSPLIT
 #define CMS_REMAP_ZSPLIT 64  /* frame groups processed side by side (measured: walking several groups per workgroup to re-use the
                                 decoded LUT entry is slower -- 0.19 ms at 16 groups side by side, 0.23 ms at one) */
+#endif
+#ifndef CMS_REMAP_TILE_ZSPLIT
+#define CMS_REMAP_TILE_ZSPLIT 16  /* the same for the tiled kernels below, where fewer, longer workgroups do pay (see there) */
 #endif
 typedef uint16_t __attribute__((aligned(1))) u16_unaligned;
 extern "C" __global__ void __launch_bounds__(256)
@@ -91,6 +95,154 @@ k_remap(const uint8_t* __restrict__ fish, size_t fish_pitch, int fstride, int Iw
     }
   }
 }
+
+// ------------------------------------------------------------------------------------------------ remap, 2-D tiles
+// k_remap covers a 256 x 1 strip of the canvas per wavefront.  On the side faces a canvas row is an arc through the fisheye image, so the 64
+// lanes of one gather touch 32 different 128-byte lines on average (tools/remap_tile_model.py) and the kernel waits for the address path.
+// Here a workgroup covers a TW x (1024 / TW) tile (cms_remap_tiles.h), whose taps lie in a small source rectangle:
+//   staged (default)  the rectangle of each of the CMS_REMAP_FPT frames is loaded with coalesced dword loads, clamped to the image rows and
+//                     the row stride (nothing outside [fish, fish + B fish_pitch) is read: the source may be a caller's own exact-size
+//                     allocation), and stored dword-interleaved over the frames -- one 16-byte LDS write per thread, and frame f's byte is
+//                     at the same address + 4 f, an immediate offset -- then the four taps are byte reads from LDS;
+//   direct            tiles above the LDS budget, and CMS_REMAP_TILES=2: the 16-bit gathers of k_remap from the 2-D shape.  The pair is
+//                     read one byte (two bytes) earlier and shifted down where X + 1 == Iw (X == Iw), so it never leaves the image row.
+// Unwritten LUT cells (entry 0 == source pixel (0, 0), weight 1) are outside the rectangles: they get the frame's pixel (0, 0), one
+// scalar load per frame.  Rows >= Ih are staged as 0 (BORDER_CONSTANT); columns >= Iw only ever meet the zero weights of x0in / x1in.
+// Grid: x = frame groups side by side (at most CMS_REMAP_TILE_ZSPLIT, a workgroup walks the rest with the decoded LUT entries kept), y = tile.
+// The groups of one tile are neighbours in the dispatch order and share its LUT lines and table entry in L2; measured per 256 frames:
+// groups slowest as in k_remap 0.331 ms, groups fastest 0.317, and 64 / 32 / 16 / 8 / 4 workgroups per tile 0.317 / 0.287 / 0.281 / 0.284 / 0.311.
+// Same integer arithmetic per pixel as k_remap: byte-identical canvases (tests/test_gpu_remap_tiles.py).
+struct CmsRemapArgs {
+  const uint8_t* fish; size_t fish_pitch; int fstride, Iw, Ih;
+  const uint32_t* lut; int lut_stride;
+  const cms_remap_tile* tiles;
+  uint8_t* pyr; size_t pyr_bytes; int W, stride0, F, write_corners, B;
+};
+template <int TW, bool STAGE>
+__device__ __forceinline__ void cms_remap_tile_body(const CmsRemapArgs& a) {
+  static_assert(CMS_REMAP_FPT == CMS_RT_FRAMES, "the LDS layout interleaves CMS_RT_FRAMES frames");
+  extern __shared__ __align__(16) uint8_t rmtile[];
+  constexpr int TH = CMS_RT_PIXELS / TW, TPR = TW / 4;
+  const cms_remap_tile t = a.tiles[blockIdx.y];
+  const int tid = threadIdx.x;
+  const int x0 = t.tx * TW + 4 * (tid % TPR), y = t.ty * TH + tid / TPR;
+  const int F = a.F, W = a.W, Iw = a.Iw, Ih = a.Ih, fstride = a.fstride;
+  const bool inside = x0 < W && y < W;
+  const bool mid_row = (y >= F && y < 2 * F);
+  const bool corner = !mid_row && (x0 + 3 < F || x0 >= 2 * F);     // this thread's quad lies wholly in a corner block
+  const int ngroups = (a.B + CMS_REMAP_FPT - 1) / CMS_REMAP_FPT;
+  uint8_t* const dst0 = a.pyr + (size_t)y * a.stride0 + x0;
+  if (t.flags & CMS_RT_DEAD) {                                       // listed behind the live tiles: only a write_corners launch gets here
+    if (a.write_corners && inside)
+      for (int f = blockIdx.x; f < a.B; f += gridDim.x) *reinterpret_cast<uint32_t*>(dst0 + (size_t)f * a.pyr_bytes) = 0u;
+    return;
+  }
+  const bool store = inside && (!corner || a.write_corners);         // a corner quad's value is 0 below: every pixel of it is invalid
+  uint4 e4 = make_uint4(0, 0, 0, 0);
+  if (inside && !corner) e4 = *reinterpret_cast<const uint4*>(a.lut + (size_t)y * a.lut_stride + x0);
+  const uint32_t e[4] = {e4.x, e4.y, e4.z, e4.w};
+  int X[4], Y[4], w00[4], w01[4], w10[4], w11[4];
+  bool live[4];
+  uint32_t zmask = 0;                                                // bytes that take the frame's pixel (0, 0)
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int x = x0 + i;
+    const bool valid = inside && !corner && x < W && (mid_row || (x >= F && x < 2 * F));   // pixels of a straddling quad inside a corner block get 0
+    live[i] = valid && e[i] != 0u;
+    if (valid && e[i] == 0u) zmask |= 0xFFu << (8 * i);
+    X[i] = e[i] & 0x7FF; Y[i] = (e[i] >> 11) & 0x7FF;
+    const int ax = (e[i] >> 22) & 31, ay = e[i] >> 27;
+    const bool x0in = live[i] && X[i] < Iw, x1in = live[i] && X[i] + 1 < Iw;
+    w00[i] = x0in ? (32 - ay) * (32 - ax) : 0; w01[i] = x1in ? (32 - ay) * ax : 0;
+    w10[i] = x0in ? ay * (32 - ax) : 0;        w11[i] = x1in ? ay * ax : 0;
+  }
+  if (STAGE && !(t.flags & CMS_RT_DIRECT)) {
+    const int nd = t.nd, n = nd * t.rows;
+    const float inv_nd = 1.0f / (float)max(nd, 1);
+    // LDS address of source byte o (row-major in the rectangle) of frame 0: dword o / 4 of all frames side by side
+    int a00[4], a01[4], a10[4], a11[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int o = live[i] ? (Y[i] - t.y0) * (4 * nd) + (X[i] - t.x0) : 0;
+      a00[i] = ((o & ~3) << 2) | (o & 3);
+      a01[i] = (((o + 1) & ~3) << 2) | ((o + 1) & 3);
+      a10[i] = a00[i] + (live[i] ? 16 * nd : 0); a11[i] = a01[i] + (live[i] ? 16 * nd : 0);
+    }
+    for (int fg = blockIdx.x; fg < ngroups; fg += gridDim.x) {
+      const int b0 = fg * CMS_REMAP_FPT, nb = min(CMS_REMAP_FPT, a.B - b0);
+      const uint8_t* src = a.fish + (size_t)b0 * a.fish_pitch;
+      if (fg != (int)blockIdx.x) __syncthreads();                    // the previous group's taps have been read
+      for (int base = 0; base < n; base += 256) {
+        const int idx = base + tid;
+        // idx / nd: (idx + 0.5) / nd is at least 0.5 / nd away from an integer, far more than the float error at these sizes (n <= 2048)
+        const int r = (int)(((float)idx + 0.5f) * inv_nd), gx = t.x0 + 4 * (idx - r * nd), gy = t.y0 + r;
+        const bool in = idx < n && gy < Ih && gx < fstride;
+        const uint32_t so = (uint32_t)__mul24(gy, fstride) + gx;
+        uint32_t v[CMS_REMAP_FPT];
+#pragma unroll
+        for (int f = 0; f < CMS_REMAP_FPT; ++f)
+          v[f] = (in && f < nb) ? *reinterpret_cast<const uint32_t*>(src + (size_t)f * a.fish_pitch + so) : 0u;
+        if (idx < n) reinterpret_cast<uint4*>(rmtile)[idx] = make_uint4(v[0], v[1], v[2], v[3]);
+      }
+      __syncthreads();
+      uint8_t* dst = dst0 + (size_t)b0 * a.pyr_bytes;
+#pragma unroll
+      for (int f = 0; f < CMS_REMAP_FPT; ++f) {
+        if (f >= nb) break;
+        uint32_t out = zmask & ((uint32_t)src[(size_t)f * a.fish_pitch] * 0x01010101u);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          // four byte reads: an unaligned 16-bit LDS read of a pair runs several times slower (tools/probe/lds_unaligned.hip)
+          const int S = w00[i] * (int)rmtile[a00[i] + 4 * f] + w01[i] * (int)rmtile[a01[i] + 4 * f] +
+                        w10[i] * (int)rmtile[a10[i] + 4 * f] + w11[i] * (int)rmtile[a11[i] + 4 * f];
+          out |= (uint32_t)((S + 512) >> 10) << (8 * i);
+        }
+        if (store) *reinterpret_cast<uint32_t*>(dst + (size_t)f * a.pyr_bytes) = out;
+      }
+    }
+    return;
+  }
+  if (!store) return;
+  int soff[4], sh[4];
+  bool ld0[4], ld1[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int adj = min(max(X[i] + 2 - Iw, 0), 2);                   // X <= Iw (cms_build_lut): the pair starts at X - adj >= 0, inside the row
+    soff[i] = Y[i] * fstride + X[i] - adj; sh[i] = 8 * adj;
+    ld0[i] = live[i] && Y[i] < Ih; ld1[i] = live[i] && Y[i] + 1 < Ih;
+  }
+  for (int fg = blockIdx.x; fg < ngroups; fg += gridDim.x) {
+    const int b0 = fg * CMS_REMAP_FPT, nb = min(CMS_REMAP_FPT, a.B - b0);
+    uint8_t* dst = dst0 + (size_t)b0 * a.pyr_bytes;
+#pragma unroll
+    for (int f = 0; f < CMS_REMAP_FPT; ++f) {
+      if (f >= nb) break;
+      const uint8_t* src = a.fish + (size_t)(b0 + f) * a.fish_pitch;
+      uint32_t r0[4], r1[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        r0[i] = ld0[i] ? (uint32_t)*reinterpret_cast<const u16_unaligned*>(src + soff[i]) >> sh[i] : 0u;
+        r1[i] = ld1[i] ? (uint32_t)*reinterpret_cast<const u16_unaligned*>(src + soff[i] + fstride) >> sh[i] : 0u;
+      }
+      uint32_t out = zmask & ((uint32_t)src[0] * 0x01010101u);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int S = w00[i] * (int)(r0[i] & 0xFF) + w01[i] * (int)(r0[i] >> 8) + w10[i] * (int)(r1[i] & 0xFF) + w11[i] * (int)(r1[i] >> 8);
+        out |= (uint32_t)((S + 512) >> 10) << (8 * i);
+      }
+      *reinterpret_cast<uint32_t*>(dst + (size_t)f * a.pyr_bytes) = out;
+    }
+  }
+}
+// one name per shape: the profiles list them as k_remap_t<TW> (staged) and k_remap_t<TW>d (direct gathers only)
+#define CMS_REMAP_TILE_KERNEL(name, TW, STAGE) \
+  extern "C" __global__ void __launch_bounds__(256) name(CmsRemapArgs a) { cms_remap_tile_body<TW, STAGE>(a); }
+CMS_REMAP_TILE_KERNEL(k_remap_t32, 32, true)
+CMS_REMAP_TILE_KERNEL(k_remap_t64, 64, true)
+CMS_REMAP_TILE_KERNEL(k_remap_t128, 128, true)
+CMS_REMAP_TILE_KERNEL(k_remap_t32d, 32, false)
+CMS_REMAP_TILE_KERNEL(k_remap_t64d, 64, false)
+CMS_REMAP_TILE_KERNEL(k_remap_t128d, 128, false)
 
 // ------------------------------------------------------------------------------------------------ resize
 // One workgroup (64 x 4 threads) produces a 256 x CMS_RZ_ROWS destination tile.  The source rectangle it needs (about 310 x 12

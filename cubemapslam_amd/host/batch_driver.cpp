@@ -5,7 +5,7 @@
 // frames/s with two cores against 21 k with eight).  The reference never uses more than two threads per stream (System.cpp:108-127: Tracking +
 // LocalMapping); a host that tracks many streams per GPU is C++.  This file is that host for the bench's synthetic workload:
 //
-//   frame thread (the caller)   cms_pose_launch, cms_frames_upload_device, cms_frames_process, cms_area_grid, the two projection searches with their
+//   frame thread (the caller)   cms_pose_launch, cms_frames_process_device, cms_area_grid, the two projection searches with their
 //                               window queries (TrackWithMotionModel, TrackLocalMap), cms_kfstore_put_from_frames for the batch's key frames,
 //                               cms_frames_sync, cms_pose_fetch -- Tracking.cpp:620-719 for B frames at once
 //   per window group            a MAPPING thread: pending pose write-backs (cms_kfstore_update_poses), cms_kfstore_create_new_map_points,
@@ -263,8 +263,7 @@ void one_step(cbd* d, int i) {
   const cbd_plan& p = d->p;
   const cbd_frame_set& S = p.sets[i & 1];
   chk(cms_pose_launch(p.po), "cms_pose_launch");                  // own stream, overlaps the frame path
-  chk(cms_frames_upload_device(p.ctx, S.d_frames, p.B), "cms_frames_upload_device");
-  chk(cms_frames_process(p.ctx, p.B, 1), "cms_frames_process");
+  chk(cms_frames_process_device(p.ctx, S.d_frames, p.B), "cms_frames_process_device");   // the resident batch is read in place, nothing rewrites it
   // the coming steps' windows are built under this one; this step's groups go to their threads
   auto cur = std::move(d->queue.front()); d->queue.pop_front();
   submit_windows(d, d->queue.empty() ? (cur.first ^ 1) : (d->queue.back().first ^ 1));

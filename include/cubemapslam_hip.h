@@ -119,9 +119,27 @@ int cms_stream_copy_device(cms_ctx* ctx, void* d_dst, const void* d_src, size_t 
 int cms_host_alloc(void** out, size_t bytes);   /* pinned host memory for cms_frames_upload_async */
 void cms_host_free(void* p);
 int cms_frames_process(cms_ctx* ctx, int B, int from_fisheye);
+/* cms_frames_process(B, 1) on a batch that is already resident on the device, read IN PLACE: d_src has the staging layout [B][Ih][fisheye_stride]
+ * (4-byte aligned; an allocation of exactly B * Ih * fisheye_stride bytes is enough, nothing behind it is read) and the remap is its only
+ * reader.  Asynchronous on the ctx stream: the caller must not overwrite d_src until that launch has finished (cms_frames_sync, or an event
+ * behind it).  The staging buffer of cms_frames_input / cms_frames_upload* is neither read nor written. */
+int cms_frames_process_device(cms_ctx* ctx, const void* d_src, int B);
 int cms_frames_sync(cms_ctx* ctx);
 int cms_frames_results(cms_ctx* ctx, void** d_kps, void** d_desc, void** d_counts);
 int cms_frames_fetch(cms_ctx* ctx, int b, cms_keypoint* kps, uint8_t* desc, int cap, int* n);
+
+/* ---- the remap's 2-D tile table, host code only (no device is touched; cms_ctx_create builds the same table once per context).
+ * cms_remap_lut_host  : the packed LUT, one u32 per canvas pixel, X[0:11) | Y[11:22) | ax[22:27) | ay[27:32); lut_stride (in entries) >= 3 face.
+ *                       Cells the reference never writes (System.cpp:316-317) keep 0 == source pixel (0, 0) with weight 1.
+ * cms_remap_tiles_host: one entry per tile_w x tile_h tile of the canvas (32 x 32, 64 x 16 or 128 x 8), live tiles first (*n_live), then the
+ *                       tiles that lie wholly in the corner blocks (flag 2); *n_all entries in all, CMS_ERR_OVERFLOW if cap is too small.
+ *                       (x0, y0) + (4 nd) x rows bytes = the source rectangle that covers the taps X .. X + 1, Y .. Y + 1 of every written
+ *                       entry of the tile's cross pixels (nd = rows = 0: none); flag 1 = it exceeds lds_budget bytes for four frames and the
+ *                       tile gathers from global memory.  *lds_bytes = the largest staged tile. */
+typedef struct { uint16_t tx, ty, x0, y0, nd, rows, flags, pad; } cms_remap_tile;
+int cms_remap_lut_host(const cms_camera* cam, uint32_t* lut, int lut_stride);
+int cms_remap_tiles_host(const cms_camera* cam, const uint32_t* lut, int lut_stride, int tile_w, int tile_h, int lds_budget,
+                         cms_remap_tile* out, int cap, int* n_live, int* n_all, int* lds_bytes);
 
 /* ---- stage-by-stage read-back for the parity tests */
 int cms_debug_lut(cms_ctx* ctx, uint32_t* out, int* stride);

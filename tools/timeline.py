@@ -9,7 +9,7 @@ rows = list(csv.DictReader(op(fn, "rt")))
 for r in rows:
     r["s"] = int(r["Start_Timestamp"]); r["e"] = int(r["End_Timestamp"]); r["n"] = r["Kernel_Name"].split("(")[0]
 rows.sort(key=lambda r: r["s"])
-remaps = [r["s"] for r in rows if r["n"] == "k_remap"]
+remaps = [r["s"] for r in rows if r["n"].startswith("k_remap")]      # k_remap, or the tiled k_remap_t64 ...
 if len(remaps) >= 3:
     t0, t1 = remaps[-2], remaps[-1]
 else:
