@@ -1,19 +1,14 @@
 // cms_api_area.hip -- host side of the frame grid + window query (Frame::AssignFeaturesToGrid / GetFeaturesInArea), included by
-// cms_lib.hip after cms_api_frames.hip (uses cms_ctx, cms_fail, HIPCHK, cms_scratch).
-#include <mutex>
+// cms_lib.hip after cms_api_frames.hip (uses cms_ctx, cms_fail, HIPCHK, cms_scratch and the helpers of cms_api_util.h).  cms_area_args /
+// cms_area_queries / cms_area_launch are the only place that fills and launches the window query's four kernels: the frame entries below and
+// the key-frame store's Fuse (cms_api_tri.hip) go through them.
 #include <vector>
 
 // the rank sort of k_area_grid keeps 8 bytes per key point in LDS: above the 64 KB default for the 3 x nFeatures extractor of the
-// initialisation.  The attribute is per function AND per device; every launcher of the kernel (frame grids, key-frame store) calls this.
+// initialisation.  Every launcher of the kernel (frame grids, key-frame store) calls this.
 static int cms_area_grid_attr(int device) {
-  static std::mutex mu;
   static bool done[64] = {false};
-  std::lock_guard<std::mutex> lk(mu);
-  if (device >= 0 && device < 64 && !done[device]) {
-    HIPCHK(hipFuncSetAttribute((const void*)k_area_grid, hipFuncAttributeMaxDynamicSharedMemorySize, (CMS_AREA_MAXKP + 1) * 8));
-    done[device] = true;
-  }
-  return CMS_OK;
+  return cms_lds_ceiling_once((const void*)k_area_grid, (CMS_AREA_MAXKP + 1) * 8, device, done);
 }
 static int cms_area_reserve(cms_ctx* c) {
   if (c->d_area_sorted) return CMS_OK;
@@ -45,6 +40,43 @@ static int cms_area_bsum_reserve(cms_ctx* c, int nblk) {
   return CMS_OK;
 }
 
+// ---- the window query: ONE place fills the grid side of its arguments and ONE place launches it.
+// cms_area_args: a zeroed CmsAreaArgs over a grid source -- the context's frame grids or a key-frame store's slot grids (kp_cap = the frame
+// stride of kp / sorted_idx); cms_area_queries adds the caller's queries and outputs (device pointers).
+static CmsAreaArgs cms_area_args(const CmsKeyPoint* kp, const uint16_t* sorted_idx, const int* cell_start, int kp_cap, int F, float inv) {
+  CmsAreaArgs a = {};
+  a.kp = kp; a.sorted_idx = sorted_idx; a.cell_start = cell_start; a.kp_cap = kp_cap; a.F = F; a.inv = inv;
+  return a;
+}
+static CmsAreaArgs cms_area_args_frames(const cms_ctx* c, int b) {      // frame b of the context's batch (queries with a q_frame: b = 0)
+  return cms_area_args((const CmsKeyPoint*)c->d_kps + (size_t)b * c->g.kp_cap, c->d_area_sorted + (size_t)b * c->g.kp_cap,
+                       c->d_area_cell_start + (size_t)b * (CMS_AREA_CELLS + 1), c->g.kp_cap, c->g.F, cms_grid_inv(c));
+}
+static void cms_area_queries(CmsAreaArgs& a, int nq, const void* q_frame, const void* qx, const void* qy, const void* qr, const void* qmin, const void* qmax,
+                             void* cnt, void* off, void* idx, int cap, int idx_base) {
+  a.nq = nq; a.q_frame = (const int*)q_frame;
+  a.qx = (const float*)qx; a.qy = (const float*)qy; a.qr = (const float*)qr; a.qmin = (const int*)qmin; a.qmax = (const int*)qmax;
+  a.cnt = (int*)cnt; a.off = (const int*)off; a.idx = (int*)idx; a.cap = cap; a.idx_base = idx_base;
+}
+// count -> block sums -> scan (offsets, *d_total) -> fill.  keep_first_hits: the count pass leaves every query's first CMS_AREA_TMP hits in
+// the context's buffer and the fill pass copies them (32 bytes per query: not for the quarter of a million queries of a store-wide Fuse).
+static int cms_area_launch(cms_ctx* c, hipStream_t s, CmsAreaArgs a, void* d_total, bool keep_first_hits) {
+  const int nq = a.nq, nblk = (nq + 1023) / 1024, qgrid = (nq * CMS_AREA_QL + 255) / 256;
+  int rc = cms_area_bsum_reserve(c, nblk);
+  if (rc) return rc;
+  if (keep_first_hits) {
+    rc = cms_area_tmp_reserve(c, nq);
+    if (rc) return rc;
+    a.tmp = c->d_area_tmp;
+  }
+  hipLaunchKernelGGL(k_area_query, dim3(qgrid), dim3(256), 0, s, a, 0);
+  hipLaunchKernelGGL(k_area_blocksum, dim3(nblk), dim3(1024), 0, s, (const int*)a.cnt, nq, c->d_area_bsum);
+  hipLaunchKernelGGL(k_area_scan, dim3(nblk), dim3(1024), 0, s, (const int*)a.cnt, nq, (const int*)c->d_area_bsum, const_cast<int*>(a.off), (int*)d_total);
+  hipLaunchKernelGGL(k_area_query, dim3(qgrid), dim3(256), 0, s, a, 1);      // (writes at most a.cap candidates; *d_total > cap tells the caller)
+  HIPCHK(hipGetLastError());
+  return CMS_OK;
+}
+
 extern "C" int cms_area_set_keypoints(cms_ctx* c, int b, int n, const cms_keypoint* kps) {
   if (!c || b < 0 || b >= c->max_batch || n < 0 || n > c->g.kp_cap || (n > 0 && !kps)) return cms_fail(CMS_ERR_ARG, "cms_area_set_keypoints: bad argument");
   HIPCHK(hipSetDevice(c->device));
@@ -59,8 +91,7 @@ extern "C" int cms_area_grid(cms_ctx* c, int B) {
   HIPCHK(hipSetDevice(c->device));
   int rc = cms_area_reserve(c);
   if (rc) return rc;
-  const float inv = (float)(3 * CMS_AREA_G) / (float)c->g.W;          // mfGridElementLengthInv (Frame.cpp:149)
-  hipLaunchKernelGGL(k_area_grid, dim3(B), dim3(1024), (size_t)(c->g.kp_cap + 1) * 8, c->stream, (const CmsKeyPoint*)c->d_kps, (const int*)c->d_kp_cnt, c->g.kp_cap, c->g.F, inv,
+  hipLaunchKernelGGL(k_area_grid, dim3(B), dim3(1024), (size_t)(c->g.kp_cap + 1) * 8, c->stream, (const CmsKeyPoint*)c->d_kps, (const int*)c->d_kp_cnt, c->g.kp_cap, c->g.F, cms_grid_inv(c),
                      c->d_area_sorted, c->d_area_cell_start, c->d_area_nvalid);
   HIPCHK(hipGetLastError());
   c->area_frames = B;
@@ -73,29 +104,9 @@ extern "C" int cms_features_in_area_device(cms_ctx* c, int b, int nq, const void
   if (!c || b < 0 || b >= c->area_frames || nq < 0 || cap < 0) return cms_fail(CMS_ERR_ARG, "cms_features_in_area_device: bad argument (cms_area_grid first)");
   if (nq == 0) return CMS_OK;
   HIPCHK(hipSetDevice(c->device));
-  CmsAreaArgs a;
-  a.kp = (const CmsKeyPoint*)c->d_kps + (size_t)b * c->g.kp_cap;
-  a.sorted_idx = c->d_area_sorted + (size_t)b * c->g.kp_cap;
-  a.cell_start = c->d_area_cell_start + (size_t)b * (CMS_AREA_CELLS + 1);
-  a.qx = (const float*)d_qx; a.qy = (const float*)d_qy; a.qr = (const float*)d_qr; a.qmin = (const int*)d_qmin; a.qmax = (const int*)d_qmax;
-  a.q_frame = nullptr; a.kp_cap = c->g.kp_cap;
-  a.nq = nq; a.F = c->g.F; a.inv = (float)(3 * CMS_AREA_G) / (float)c->g.W;
-  a.cnt = (int*)d_cnt_scratch; a.off = (const int*)d_cand_off; a.idx = (int*)d_cand_idx; a.cap = cap; a.idx_base = idx_base;
-  hipStream_t s = c->stream;
-  {
-    const int nblk = (nq + 1023) / 1024, qgrid = (nq * CMS_AREA_QL + 255) / 256;
-    int rcb = cms_area_bsum_reserve(c, nblk);
-    if (rcb) return rcb;
-    rcb = cms_area_tmp_reserve(c, nq);
-    if (rcb) return rcb;
-    a.tmp = c->d_area_tmp;
-    hipLaunchKernelGGL(k_area_query, dim3(qgrid), dim3(256), 0, s, a, 0);
-    hipLaunchKernelGGL(k_area_blocksum, dim3(nblk), dim3(1024), 0, s, (const int*)d_cnt_scratch, nq, c->d_area_bsum);
-    hipLaunchKernelGGL(k_area_scan, dim3(nblk), dim3(1024), 0, s, (const int*)d_cnt_scratch, nq, (const int*)c->d_area_bsum, (int*)d_cand_off, (int*)d_total);
-    hipLaunchKernelGGL(k_area_query, dim3(qgrid), dim3(256), 0, s, a, 1);
-  }
-  HIPCHK(hipGetLastError());
-  return CMS_OK;
+  CmsAreaArgs a = cms_area_args_frames(c, b);
+  cms_area_queries(a, nq, nullptr, d_qx, d_qy, d_qr, d_qmin, d_qmax, d_cnt_scratch, d_cand_off, d_cand_idx, cap, idx_base);
+  return cms_area_launch(c, c->stream, a, d_total, true);
 }
 
 // every query names the frame of the batch it searches (d_qframe); candidate indices are rows of the batch (frame * kp_cap + i)
@@ -105,27 +116,9 @@ extern "C" int cms_features_in_area_batch_device(cms_ctx* c, int nq, const void*
   if (!c || nq < 0 || cap < 0 || c->area_frames < 1 || !d_qframe) return cms_fail(CMS_ERR_ARG, "cms_features_in_area_batch_device: bad argument (cms_area_grid first)");
   if (nq == 0) return CMS_OK;
   HIPCHK(hipSetDevice(c->device));
-  CmsAreaArgs a;
-  a.kp = (const CmsKeyPoint*)c->d_kps; a.sorted_idx = c->d_area_sorted; a.cell_start = c->d_area_cell_start;
-  a.qx = (const float*)d_qx; a.qy = (const float*)d_qy; a.qr = (const float*)d_qr; a.qmin = (const int*)d_qmin; a.qmax = (const int*)d_qmax;
-  a.q_frame = (const int*)d_qframe; a.kp_cap = c->g.kp_cap;
-  a.nq = nq; a.F = c->g.F; a.inv = (float)(3 * CMS_AREA_G) / (float)c->g.W;
-  a.cnt = (int*)d_cnt_scratch; a.off = (const int*)d_cand_off; a.idx = (int*)d_cand_idx; a.cap = cap; a.idx_base = 0;
-  hipStream_t s = c->stream;
-  {
-    const int nblk = (nq + 1023) / 1024, qgrid = (nq * CMS_AREA_QL + 255) / 256;
-    int rcb = cms_area_bsum_reserve(c, nblk);
-    if (rcb) return rcb;
-    rcb = cms_area_tmp_reserve(c, nq);
-    if (rcb) return rcb;
-    a.tmp = c->d_area_tmp;
-    hipLaunchKernelGGL(k_area_query, dim3(qgrid), dim3(256), 0, s, a, 0);
-    hipLaunchKernelGGL(k_area_blocksum, dim3(nblk), dim3(1024), 0, s, (const int*)d_cnt_scratch, nq, c->d_area_bsum);
-    hipLaunchKernelGGL(k_area_scan, dim3(nblk), dim3(1024), 0, s, (const int*)d_cnt_scratch, nq, (const int*)c->d_area_bsum, (int*)d_cand_off, (int*)d_total);
-    hipLaunchKernelGGL(k_area_query, dim3(qgrid), dim3(256), 0, s, a, 1);
-  }
-  HIPCHK(hipGetLastError());
-  return CMS_OK;
+  CmsAreaArgs a = cms_area_args_frames(c, 0);
+  cms_area_queries(a, nq, d_qframe, d_qx, d_qy, d_qr, d_qmin, d_qmax, d_cnt_scratch, d_cand_off, d_cand_idx, cap, 0);
+  return cms_area_launch(c, c->stream, a, d_total, true);
 }
 
 extern "C" int cms_features_in_area(cms_ctx* c, int b, int nq, const float* qx, const float* qy, const float* qr, const int* qmin, const int* qmax,

@@ -1,12 +1,12 @@
 // cms_api_bow.hip -- host side of ORBMatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (src/ORBMatcher.cpp:409-539), included by
 // cms_lib.hip after cms_api_tri.hip (cms_kfstore).  Both entries stage what comes from the host (FeatureVectors, skip flags, job records; for the
-// stand-alone entry the key frame too) in the context's pinned block, make ONE copy to the device, ONE launch of k_search_by_bow and ONE copy back.
+// stand-alone entry the key frame too) in the context's pinned block (laid out with CmsBlock, 4 bytes of slack behind every piece), make ONE copy
+// to the device, ONE launch of k_search_by_bow and ONE copy back.
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
 namespace {
-inline size_t bow_al(size_t v) { return (v + 15) & ~(size_t)15; }
 // a FeatureVector in CSR: node ids strictly ascending, offsets ascending from >= 0, indices in [0, n); unique_of (n bytes of scratch, or NULL) also
 // rejects an index listed twice -- the frame side, where DBoW2 puts every feature into exactly one node
 int bow_check_fv(int n, int nnodes, const int* node_id, const int* node_off, const int* node_feat, std::vector<uint8_t>* unique_of, const char* who) {
@@ -39,13 +39,13 @@ struct BowStage {
 };
 // stage -> device -> launch -> back.  jobs[j] has every device pointer filled except the ones given as offsets in rel[j] (pointer fields that
 // hold an offset into the input block, marked by the caller), which are rebased here once the block's device address is known.
-int bow_run(cms_ctx* c, std::vector<CmsBowJob>& jobs, const std::vector<std::vector<const void**>>& rel, std::vector<BowStage>& pieces, size_t in_bytes,
+int bow_run(cms_ctx* c, std::vector<CmsBowJob>& jobs, const std::vector<std::vector<const void**>>& rel, std::vector<BowStage>& pieces, CmsBlock blk,
             float nnratio, int check_orientation, int* kf_idx, int* n_matches) {
   const int njobs = (int)jobs.size();
   size_t total_n = 0;
   for (const CmsBowJob& q : jobs) total_n += (size_t)q.n;
-  const size_t o_jobs = bow_al(in_bytes), o_idx = o_jobs + bow_al((size_t)njobs * sizeof(CmsBowJob)), o_nm = o_idx + bow_al(total_n * 4 + 4);
-  const size_t bytes = o_nm + bow_al((size_t)njobs * 4);
+  const size_t o_jobs = blk.take((size_t)njobs * sizeof(CmsBowJob)), o_idx = blk.take(total_n * 4, 4), o_nm = blk.take((size_t)njobs * 4);      // behind the staged pieces
+  const size_t bytes = blk.size;
   int rc = cms_scratch(c, bytes);
   if (rc) return rc;
   rc = cms_hstage(c, bytes);
@@ -73,11 +73,11 @@ int bow_run(cms_ctx* c, std::vector<CmsBowJob>& jobs, const std::vector<std::vec
 }
 // host array -> staged piece; the job field receives its offset in the block (rebased by bow_run)
 template <class T>
-void bow_put(std::vector<BowStage>& pieces, size_t& o, std::vector<const void**>& rel, const T*& field, const void* src, size_t bytes) {
-  pieces.push_back(BowStage{src, bytes, o});
-  field = reinterpret_cast<const T*>((uintptr_t)o);
+void bow_put(std::vector<BowStage>& pieces, CmsBlock& blk, std::vector<const void**>& rel, const T*& field, const void* src, size_t bytes) {
+  const size_t at = blk.take(bytes, 4);
+  pieces.push_back(BowStage{src, bytes, at});
+  field = reinterpret_cast<const T*>((uintptr_t)at);
   rel.push_back(reinterpret_cast<const void**>(&field));
-  o += bow_al(bytes + 4);
 }
 }  // namespace
 
@@ -100,23 +100,23 @@ extern "C" int cms_search_by_bow(cms_ctx* c, int b, int n, int nnodes, const int
   std::vector<BowStage> pieces;
   CmsBowJob& q = jobs[0];
   std::memset(&q, 0, sizeof(q));
-  size_t o = 0;
+  CmsBlock blk;
   const size_t kn = (size_t)kf->n;
   const int kfeat = kf->nnodes > 0 ? kf->node_off[kf->nnodes] : 0, ffeat = nnodes > 0 ? node_off[nnodes] : 0;
-  bow_put(pieces, o, rel[0], q.kf_kp, kf->kps, kn * sizeof(CmsKeyPoint));
-  bow_put(pieces, o, rel[0], q.kf_desc, kf->desc, kn * 32);
-  bow_put(pieces, o, rel[0], q.kf_mp, kf->mp, kn * 4);
-  if (kf_skip) bow_put(pieces, o, rel[0], q.kf_skip, kf_skip, kn);
-  bow_put(pieces, o, rel[0], q.kf_nid, kf->node_id, 4 * (size_t)kf->nnodes);
-  bow_put(pieces, o, rel[0], q.kf_noff, kf->node_off, kf->nnodes > 0 ? 4 * ((size_t)kf->nnodes + 1) : 0);
-  bow_put(pieces, o, rel[0], q.kf_nfeat, kf->node_feat, 4 * (size_t)kfeat);
-  bow_put(pieces, o, rel[0], q.f_nid, node_id, 4 * (size_t)nnodes);
-  bow_put(pieces, o, rel[0], q.f_noff, node_off, nnodes > 0 ? 4 * ((size_t)nnodes + 1) : 0);
-  bow_put(pieces, o, rel[0], q.f_nfeat, node_feat, 4 * (size_t)ffeat);
+  bow_put(pieces, blk, rel[0], q.kf_kp, kf->kps, kn * sizeof(CmsKeyPoint));
+  bow_put(pieces, blk, rel[0], q.kf_desc, kf->desc, kn * 32);
+  bow_put(pieces, blk, rel[0], q.kf_mp, kf->mp, kn * 4);
+  if (kf_skip) bow_put(pieces, blk, rel[0], q.kf_skip, kf_skip, kn);
+  bow_put(pieces, blk, rel[0], q.kf_nid, kf->node_id, 4 * (size_t)kf->nnodes);
+  bow_put(pieces, blk, rel[0], q.kf_noff, kf->node_off, kf->nnodes > 0 ? 4 * ((size_t)kf->nnodes + 1) : 0);
+  bow_put(pieces, blk, rel[0], q.kf_nfeat, kf->node_feat, 4 * (size_t)kfeat);
+  bow_put(pieces, blk, rel[0], q.f_nid, node_id, 4 * (size_t)nnodes);
+  bow_put(pieces, blk, rel[0], q.f_noff, node_off, nnodes > 0 ? 4 * ((size_t)nnodes + 1) : 0);
+  bow_put(pieces, blk, rel[0], q.f_nfeat, node_feat, 4 * (size_t)ffeat);
   q.kf_nnodes = kf->nnodes; q.f_nnodes = nnodes; q.n = n;
   const size_t sb = (size_t)b * c->g.kp_cap;
   q.f_kp = (const CmsKeyPoint*)c->d_kps + sb; q.f_desc = (const uint4*)(c->d_desc + 32 * sb);
-  return bow_run(c, jobs, rel, pieces, o, nnratio, check_orientation, kf_idx, n_matches);
+  return bow_run(c, jobs, rel, pieces, blk, nnratio, check_orientation, kf_idx, n_matches);
 }
 
 // Relocalization's candidate loop (Tracking.cpp:1019-1040) or one TrackReferenceKeyFrame per camera stream on resident key frames: ONE launch on
@@ -148,7 +148,7 @@ extern "C" int cms_kfstore_search_by_bow(cms_kfstore* st, cms_ctx* src, int njob
   std::vector<CmsBowJob> dj((size_t)njobs);
   std::vector<std::vector<const void**>> rel((size_t)njobs);
   std::vector<BowStage> pieces;
-  size_t o = 0;
+  CmsBlock blk;
   for (int j = 0; j < njobs; ++j) {
     const cms_bow_job& q = jobs[j];
     const CmsTriKF& k = st->h_kf[(size_t)q.slot];
@@ -156,14 +156,14 @@ extern "C" int cms_kfstore_search_by_bow(cms_kfstore* st, cms_ctx* src, int njob
     std::memset(&d, 0, sizeof(d));
     d.kf_kp = st->d_kp + k.f0; d.kf_desc = (const uint4*)(st->d_desc + 32 * (size_t)k.f0); d.kf_mp = st->d_mp + k.f0;
     d.kf_nid = st->d_nid + k.node0; d.kf_noff = st->d_noff + k.noff0; d.kf_nfeat = st->d_nfeat + k.nfeat0; d.kf_nnodes = k.nnodes;
-    if (q.kf_skip) bow_put(pieces, o, rel[(size_t)j], d.kf_skip, q.kf_skip, (size_t)k.n);
+    if (q.kf_skip) bow_put(pieces, blk, rel[(size_t)j], d.kf_skip, q.kf_skip, (size_t)k.n);
     const int ffeat = q.nnodes > 0 ? q.node_off[q.nnodes] : 0;
-    bow_put(pieces, o, rel[(size_t)j], d.f_nid, q.node_id, 4 * (size_t)q.nnodes);
-    bow_put(pieces, o, rel[(size_t)j], d.f_noff, q.node_off, q.nnodes > 0 ? 4 * ((size_t)q.nnodes + 1) : 0);
-    bow_put(pieces, o, rel[(size_t)j], d.f_nfeat, q.node_feat, 4 * (size_t)ffeat);
+    bow_put(pieces, blk, rel[(size_t)j], d.f_nid, q.node_id, 4 * (size_t)q.nnodes);
+    bow_put(pieces, blk, rel[(size_t)j], d.f_noff, q.node_off, q.nnodes > 0 ? 4 * ((size_t)q.nnodes + 1) : 0);
+    bow_put(pieces, blk, rel[(size_t)j], d.f_nfeat, q.node_feat, 4 * (size_t)ffeat);
     d.f_nnodes = q.nnodes; d.n = q.n;
     const size_t sb = (size_t)q.b * src->g.kp_cap;
     d.f_kp = (const CmsKeyPoint*)src->d_kps + sb; d.f_desc = (const uint4*)(src->d_desc + 32 * sb);
   }
-  return bow_run(src, dj, rel, pieces, o, nnratio, check_orientation, kf_idx, n_matches);
+  return bow_run(src, dj, rel, pieces, blk, nnratio, check_orientation, kf_idx, n_matches);
 }

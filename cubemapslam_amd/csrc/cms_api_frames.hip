@@ -1,5 +1,6 @@
 // cms_api_frames.hip -- host side of the C-ABI for the frame path (context, LUT / table construction, launches).
-// Included by cms_lib.hip (single translation unit together with the kernels).
+// Included by cms_lib.hip (single translation unit together with the kernels).  Includes cms_api_util.h behind cms_ctx: cms_align, CmsBlock (block
+// layouts), cms_retry_capacity and the small argument helpers that every cms_api_*.hip file behind this one uses.
 #include <chrono>
 #include <thread>
 #include <hip/hip_runtime.h>
@@ -197,7 +198,7 @@ static void cms_resize_table(int sn, int dn, bool clamp_frac, CmsResizeTab* out)
   }
 }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+#include "cms_api_util.h"
 
 static void cms_ctx_free(cms_ctx* c) {
   if (!c) return;
@@ -254,15 +255,15 @@ extern "C" int cms_ctx_create(cms_ctx** out, int device, const cms_camera* cam, 
     lv.w = (int)lrint((double)((float)W * c->inv_scale[l]));
     lv.h = lv.w;
     if (lv.w < 2 * CMS_MINB + 30) { delete c; return cms_fail(CMS_ERR_UNSUPPORTED, "pyramid level too small for the FAST cell grid"); }
-    lv.stride = (int)align_up((size_t)lv.w + 8, 128);
+    lv.stride = (int)cms_align((size_t)lv.w + 8, 128);
     lv.off = off;
-    off += align_up((size_t)lv.stride * (lv.h + 1), 256);
+    off += cms_align((size_t)lv.stride * (lv.h + 1), 256);
     const float width = (float)(lv.w - 2 * CMS_MINB), height = (float)(lv.h - 2 * CMS_MINB);
     lv.nCols = (int)(width / 30.f); lv.nRows = (int)(height / 30.f);
     lv.wCell = (int)ceilf(width / lv.nCols); lv.hCell = (int)ceilf(height / lv.nRows);
     lv.cell0 = cell0; cell0 += lv.nCols * lv.nRows;
     lv.cand_cap = (lv.w * lv.h) / 4 + 4096;
-    lv.cand_off = cand_off; cand_off += align_up((size_t)lv.cand_cap, 64);
+    lv.cand_off = cand_off; cand_off += cms_align((size_t)lv.cand_cap, 64);
     lv.kp_off = kp_off; kp_off += lv.quota + 3;
     lv.scale = c->scale[l];
     lv.patch_size = (float)(int)(31 * c->scale[l]);
@@ -277,11 +278,11 @@ extern "C" int cms_ctx_create(cms_ctx** out, int device, const cms_camera* cam, 
   while (g.qt_maxn < maxq + 3) g.qt_maxn <<= 1;
   if (g.qt_maxn > 2048) { delete c; return cms_fail(CMS_ERR_UNSUPPORTED, "per-level feature quota above 2045 is not supported"); }
   g.tile_h = hCellMax + 6;
-  g.tile_stride = (int)align_up((size_t)wCellMax + 6 + 3, 4) + 4;
+  g.tile_stride = (int)cms_align((size_t)wCellMax + 6 + 3, 4) + 4;
   g.sc_h = hCellMax + 2;
-  g.sc_stride = (int)align_up((size_t)wCellMax + 2, 4);
+  g.sc_stride = (int)cms_align((size_t)wCellMax + 2, 4);
   g.list_cap = wCellMax * hCellMax;
-  g.cell_cap = (int)align_up((size_t)((wCellMax + 1) / 2) * ((hCellMax + 1) / 2), 8);   // strict 3x3 maxima cannot be 8-adjacent
+  g.cell_cap = (int)cms_align((size_t)((wCellMax + 1) / 2) * ((hCellMax + 1) / 2), 8);   // strict 3x3 maxima cannot be 8-adjacent
   g.dbg_stop = getenv("CMS_DBG_FAST_STOP") ? atoi(getenv("CMS_DBG_FAST_STOP")) : 0;
   // CMS_DESC_SPATIAL_ORDER=1: k_describe works through the batch's key points band by band of their levels (k_cull builds the walk), an eighth of
   // the walk per XCD: a third of the HBM fetches of the octree's list order (profiles/r02_describe_order.txt: 2.39 GB -> 0.86 GB per 256 frames).
@@ -292,14 +293,14 @@ extern "C" int cms_ctx_create(cms_ctx** out, int device, const cms_camera* cam, 
   g.gauss_column_mode = 0;
   if (wCellMax > 60 || hCellMax > 60) { delete c; return cms_fail(CMS_ERR_UNSUPPORTED, "FAST cell larger than 60 pixels"); }
   if (orb->scale_factor < 1.01f || orb->scale_factor > 1.9f) { delete c; return cms_fail(CMS_ERR_UNSUPPORTED, "scaleFactor must be in [1.01, 1.9]"); }
-  g.fast_cell_lds = (int)align_up((size_t)g.tile_h * g.tile_stride + (size_t)g.sc_h * g.sc_stride + 2 * (size_t)g.list_cap + 16, 16);
+  g.fast_cell_lds = (int)cms_align((size_t)g.tile_h * g.tile_stride + (size_t)g.sc_h * g.sc_stride + 2 * (size_t)g.list_cap + 16, 16);
   c->fast_lds = CMS_FAST_WPB * (size_t)g.fast_cell_lds;
   c->qt_lds = 64 * (size_t)g.qt_maxn + 4 * 512 + 64;
 
-  c->fstride = (int)align_up((size_t)cam->Iw, 64);
+  c->fstride = (int)cms_align((size_t)cam->Iw, 64);
   c->fish_pitch = (size_t)c->fstride * cam->Ih;
-  c->lut_stride = (int)align_up((size_t)W, 4);
-  c->mstride = (int)align_up((size_t)W, 64);
+  c->lut_stride = (int)cms_align((size_t)W, 4);
+  c->mstride = (int)cms_align((size_t)W, 64);
   const size_t B = (size_t)max_batch;
 #define ALLOC(ptr, bytes) do { hipError_t _e = hipMalloc((void**)&(ptr), (bytes)); if (_e != hipSuccess) { cms_ctx_free(c); return cms_fail(CMS_ERR_HIP, "hipMalloc " #ptr, _e); } } while (0)
   // CMS_FRAME_STREAM_PRIORITY=high|low (developer knob): dispatch priority of the frame path's queue against the mapping side's
@@ -610,8 +611,8 @@ static int cms_launch_frames(cms_ctx* c, int B, int from_fisheye, const uint8_t*
     const double ratio = (double)g.lv[l - 1].w / g.lv[l].w;
     if (!rz_single && l + 1 < L) {
       const double ratio2 = (double)g.lv[l].w / g.lv[l + 1].w;
-      const int la = (int)align_up((size_t)ceil(256 * ratio2) + 34, 16);                 // mid rectangle: k_resize's staged width for the tile of level l + 1
-      const int ls = (int)align_up((size_t)ceil((la + 2) * ratio) + 34, 16);             // ... and the src rectangle behind it
+      const int la = (int)cms_align((size_t)ceil(256 * ratio2) + 34, 16);                 // mid rectangle: k_resize's staged width for the tile of level l + 1
+      const int ls = (int)cms_align((size_t)ceil((la + 2) * ratio) + 34, 16);             // ... and the src rectangle behind it
       // rows of mid a tile can need: floor(yb r) - 1 .. ceil((yl + 1) r) + 1 -> CMS_RZ_ROWS r + 4; rows of src behind them likewise (24 and 33 at the
       // pyramid's 1.2; the kernel's buffers hold CMS_RZ2_AROWS / CMS_RZ2_SROWS)
       const int arows = (int)ceil(CMS_RZ_ROWS * ratio2) + 4;
@@ -634,7 +635,7 @@ static int cms_launch_frames(cms_ctx* c, int B, int from_fisheye, const uint8_t*
     }
     const CmsLevel& d = g.lv[l];
     dim3 grid((d.w + 255) / 256, (d.h + CMS_RZ_ROWS - 1) / CMS_RZ_ROWS, B);
-    const int ls = (int)align_up((size_t)ceil(256 * ratio) + 34, 16);    // LDS row stride of the staged source rectangle (16-byte columns)
+    const int ls = (int)cms_align((size_t)ceil(256 * ratio) + 34, 16);    // LDS row stride of the staged source rectangle (16-byte columns)
     const int lrows = (int)ceil(CMS_RZ_ROWS * ratio) + 7;               // the kernel's integer bounds can be one row wider on either side
     hipLaunchKernelGGL(k_resize, grid, block, (size_t)ls * lrows, s, c->d_pyr, g.pyr_bytes, g.lv[l - 1], d,
                        (const CmsResizeTab*)(c->d_tab + d.tab_off), (const CmsResizeTab*)(c->d_tab + d.tab_off + d.w), ls, clean,
@@ -810,7 +811,7 @@ static int cms_remap_extract_impl(cms_ctx* c, const uint8_t* fisheye, int fstrid
   rc = cms_launch_frames(c, 1, 1);
   if (rc) return rc;
   const int m = std::min(cap, c->g.kp_cap);
-  const size_t o_kp = 256, o_desc = o_kp + (((size_t)m * sizeof(cms_keypoint) + 255) & ~(size_t)255), o_rays = o_desc + (((size_t)m * 32 + 255) & ~(size_t)255),
+  const size_t o_kp = 256, o_desc = o_kp + cms_align((size_t)m * sizeof(cms_keypoint)), o_rays = o_desc + cms_align((size_t)m * 32),
                total = o_rays + (rays ? (size_t)m * 12 : 0);
   rc = cms_hstage(c, total);
   if (rc) return rc;
@@ -933,11 +934,10 @@ extern "C" int cms_hamming_best2(cms_ctx* c, const uint8_t* qdesc, int nq, const
   const int ncand = cand_off[nq];
   for (int q = 0; q < nq; ++q)
     if (cand_off[q + 1] - cand_off[q] >= (1 << 22)) return cms_fail(CMS_ERR_UNSUPPORTED, "candidate list longer than 2^22");
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes, 256); return r; };
-  const size_t oq = take((size_t)nq * 32), ot = take((size_t)nt * 32 + 32), ooff = take((size_t)(nq + 1) * 4), oidx = take((size_t)ncand * 4 + 4),
-               olv = take((size_t)nt * 4 + 4), oex = take((size_t)nt + 4), oout = take((size_t)nq * 4 * 5);
-  int rc = cms_scratch(c, o);
+  CmsBlock blk;
+  const size_t oq = blk.take((size_t)nq * 32), ot = blk.take((size_t)nt * 32, 32), ooff = blk.take((size_t)(nq + 1) * 4), oidx = blk.take((size_t)ncand * 4, 4),
+               olv = blk.take((size_t)nt * 4, 4), oex = blk.take((size_t)nt, 4), oout = blk.take((size_t)nq * 4 * 5);
+  int rc = cms_scratch(c, blk.size);
   if (rc) return rc;
   uint8_t* base = (uint8_t*)c->d_match;
   hipStream_t s = c->stream;
@@ -963,10 +963,9 @@ extern "C" int cms_hamming_matrix(cms_ctx* c, const uint8_t* a, int na, const ui
   if (!c || na < 0 || nb < 0) return cms_fail(CMS_ERR_ARG, "cms_hamming_matrix: bad argument");
   if (na == 0 || nb == 0) return CMS_OK;
   HIPCHK(hipSetDevice(c->device));
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes, 256); return r; };
-  const size_t oa = take((size_t)na * 32), ob = take((size_t)nb * 32), oo = take((size_t)na * nb * 2);
-  int rc = cms_scratch(c, o);
+  CmsBlock blk;
+  const size_t oa = blk.take((size_t)na * 32), ob = blk.take((size_t)nb * 32), oo = blk.take((size_t)na * nb * 2);
+  int rc = cms_scratch(c, blk.size);
   if (rc) return rc;
   uint8_t* base = (uint8_t*)c->d_match;
   hipStream_t s = c->stream;

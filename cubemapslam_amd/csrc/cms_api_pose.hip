@@ -7,7 +7,6 @@
 #include <vector>
 #include "../../include/cubemapslam_hip.h"
 
-static inline size_t pose_al(size_t v) { return (v + 255) & ~(size_t)255; }
 struct cms_pose {
   int device = 0, cap_f = 0, cap_e = 0, nf = 0, ne = 0, max_n = 0;   // max_n: most edges of one uploaded frame
   hipStream_t stream = nullptr;
@@ -77,10 +76,10 @@ static int cms_pose_upload_impl(cms_pose* p, int nf, const int* edge_off, const 
   const int* h_off = edge_off; const double* h_X = Xw; const double* h_obs = obs_uv; const double* h_inv = inv_sigma2; const int8_t* h_face = face;
   const double* h_pose = poses7;
   if (staged) {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_off = 0, o_X = al(((size_t)nf + 1) * 4), o_obs = o_X + al((size_t)ne * 24), o_inv = o_obs + al((size_t)ne * 16), o_face = o_inv + al((size_t)ne * 8),
-                 o_pose = o_face + al((size_t)ne), in_bytes = o_pose + al((size_t)nf * 56);
-    const size_t out_bytes = al((size_t)nf * 32) + al((size_t)nf * 56) + al((size_t)ne);
+    CmsBlock blk;
+    const size_t o_off = blk.take(((size_t)nf + 1) * 4), o_X = blk.take((size_t)ne * 24), o_obs = blk.take((size_t)ne * 16), o_inv = blk.take((size_t)ne * 8),
+                 o_face = blk.take((size_t)ne), o_pose = blk.take((size_t)nf * 56), in_bytes = blk.size;
+    const size_t out_bytes = cms_align((size_t)nf * 32) + cms_align((size_t)nf * 56) + cms_align((size_t)ne);
     // the inputs use the first half of the block, the results of cms_pose_optimize_batch the second: EACH must fit its half (a block kept from
     // a smaller call could hold in + out together and still be too short for a result set larger than the inputs)
     if (2 * std::max(in_bytes, out_bytes) > p->h_stage_bytes) {
@@ -134,7 +133,7 @@ extern "C" int cms_pose_launch(cms_pose* p) {
   // each waited for a slot on the busy chip -- 3.5 ms of the step's host thread inside a 12.5 ms step (CMS_BENCH_STEP_TRACE).
   p->fetch_queued = false;
   {
-    const size_t o_res = 0, o_pose = pose_al((size_t)p->nf * 32), o_out = o_pose + pose_al((size_t)p->nf * 56), total = o_out + pose_al((size_t)std::max(p->ne, 1));
+    const size_t o_res = 0, o_pose = cms_align((size_t)p->nf * 32), o_out = o_pose + cms_align((size_t)p->nf * 56), total = o_out + cms_align((size_t)std::max(p->ne, 1));
     if (total > p->h_fetch_bytes) {
       if (p->h_fetch) { HIPCHK(hipStreamSynchronize(s)); (void)hipHostFree(p->h_fetch); }
       p->h_fetch = nullptr; p->h_fetch_bytes = 0;
@@ -157,7 +156,7 @@ extern "C" int cms_pose_fetch(cms_pose* p, double* poses7, uint8_t* outlier, int
   hipStream_t s = p->stream;
   // results through the handle's pinned block, one synchronisation: three copies into the caller's pageable arrays were three staged,
   // waited-for transfers (1.2 ms for 256 frames next to a busy PCIe link, on the thread that drives the frame path)
-  const size_t o_res = 0, o_pose = pose_al((size_t)p->nf * 32), o_out = o_pose + pose_al((size_t)p->nf * 56), total = o_out + pose_al((size_t)std::max(p->ne, 1));
+  const size_t o_res = 0, o_pose = cms_align((size_t)p->nf * 32), o_out = o_pose + cms_align((size_t)p->nf * 56), total = o_out + cms_align((size_t)std::max(p->ne, 1));
   if (p->fetch_queued) {
     HIPCHK(hipEventSynchronize(p->ev_fetch));        // (cms_pose_launch enqueued the copies: the block holds this launch's results until the next launch)
   } else {
@@ -191,9 +190,9 @@ static int cms_pose_optimize_direct(cms_pose* p, int nf, const int* edge_off, co
                                     int* n_inliers, cms_pose_stats* stats) {
   const int ne = edge_off[nf];
   HIPCHK(hipSetDevice(p->device));
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_off = 0, o_X = al(((size_t)nf + 1) * 4), o_obs = o_X + al((size_t)ne * 24), o_inv = o_obs + al((size_t)ne * 16), o_face = o_inv + al((size_t)ne * 8),
-               o_pose = o_face + al((size_t)ne), o_res = o_pose + al((size_t)nf * 56), o_out = o_res + al((size_t)nf * 32), total = o_out + al((size_t)ne);
+  CmsBlock blk;
+  const size_t o_off = blk.take(((size_t)nf + 1) * 4), o_X = blk.take((size_t)ne * 24), o_obs = blk.take((size_t)ne * 16), o_inv = blk.take((size_t)ne * 8),
+               o_face = blk.take((size_t)ne), o_pose = blk.take((size_t)nf * 56), o_res = blk.take((size_t)nf * 32), o_out = blk.take((size_t)ne), total = blk.size;
   // (a block of the direct path's own: the handle's resident batch -- cms_pose_upload + cms_pose_launch, possibly still copying out of h_stage --
   // is not touched by this call, and a cms_pose_fetch afterwards still finds it: p->nf / p->ne stay as they are)
   if (total > p->h_direct_bytes) {

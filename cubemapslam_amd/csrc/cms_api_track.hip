@@ -1,6 +1,6 @@
-#include <mutex>
 // cms_api_track.hip -- host side of the "track local map" step (Frame::isInFrustum + ORBMatcher::SearchByProjection over the local
-// map points, Tracking::SearchLocalPoints), included by cms_lib.hip after cms_api_area.hip.
+// map points, Tracking::SearchLocalPoints), included by cms_lib.hip after cms_api_area.hip.  The host-buffer entries lay their scratch block
+// out with CmsBlock and run inside cms_retry_capacity (cms_api_util.h); track_search_local_args fills k_search_local's arguments for all of them.
 #include <cmath>
 #include <vector>
 
@@ -37,12 +37,28 @@ extern "C" int cms_is_in_frustum_device(cms_ctx* c, int nmp, const void* d_mp_fr
   a.viewing_cos_limit = viewing_cos_limit; a.th = th; a.bounds_scaled = c->dist_bounds_scaled;
   a.log_scale = std::log(c->g.nlevels > 1 ? c->scale[1] : 1.2f);          // mfLogScaleFactor = log(mfScaleFactor), float (Frame.cpp:113)
   a.nlevels = c->g.nlevels; a.F = c->g.F;
-  for (int l = 0; l < 16; ++l) a.sf[l] = l < c->g.nlevels ? c->scale[l] : 0.0f;
+  cms_level_table(a.sf, c, c->scale, 0.0f);
   a.in_view = (uint8_t*)d_in_view; a.proj_x = (float*)d_proj_x; a.proj_y = (float*)d_proj_y; a.level = (int*)d_level; a.view_cos = (float*)d_view_cos;
   a.qr = (float*)d_qr; a.qmin = (int*)d_qmin; a.qmax = (int*)d_qmax;
   hipLaunchKernelGGL(k_in_frustum, dim3((nmp + 255) / 256), dim3(256), 0, c->stream, a);
   HIPCHK(hipGetLastError());
   return CMS_OK;
+}
+
+// the scratch block (fixed part | cap candidate rows | cap pair distances) and the pinned block of one attempt of a host-buffer entry
+static int track_reserve(cms_ctx* c, size_t scratch_bytes, size_t stage_bytes) {
+  const int rc = cms_scratch(c, scratch_bytes);
+  return rc ? rc : cms_hstage(c, stage_bytes);
+}
+// k_search_local's arguments over the context's frames.  total / cap: see CmsSearchLocalArgs (NULL / 0: the candidate lists are complete).
+static CmsSearchLocalArgs track_search_local_args(const cms_ctx* c, const void* mp_off, const void* mp_desc, const void* cand_off, const void* cand_idx, void* pair_dist,
+                                                  int* kp_mp, void* mp_match, void* rounds, float nnratio, int th_high, int frame0, const void* total, int cap) {
+  CmsSearchLocalArgs a = {};
+  a.mp_off = (const int*)mp_off; a.mp_desc = (const uint4*)mp_desc; a.cand_off = (const int*)cand_off; a.cand_idx = (const int*)cand_idx;
+  a.t_desc = (const uint4*)c->d_desc; a.kp = (const CmsKeyPoint*)c->d_kps; a.kp_cap = c->g.kp_cap;
+  a.pair_dist = (uint16_t*)pair_dist; a.kp_mp = kp_mp; a.mp_match = (int*)mp_match; a.rounds = (int*)rounds;
+  a.nnratio = nnratio; a.th_high = th_high; a.frame0 = frame0; a.total = (const int*)total; a.cap = cap;
+  return a;
 }
 
 extern "C" int cms_search_local_points_device(cms_ctx* c, int B, const void* d_mp_off, const void* d_mp_desc, const void* d_cand_off,
@@ -52,14 +68,26 @@ extern "C" int cms_search_local_points_device(cms_ctx* c, int B, const void* d_m
     return cms_fail(CMS_ERR_ARG, "cms_search_local_points_device: bad argument (cms_area_grid first)");
   if (c->g.kp_cap > CMS_TRACK_KPMAX) return cms_fail(CMS_ERR_UNSUPPORTED, "cms_search_local_points_device: more than 4096 key points per frame");
   HIPCHK(hipSetDevice(c->device));
-  CmsSearchLocalArgs a;
-  a.mp_off = (const int*)d_mp_off; a.mp_desc = (const uint4*)d_mp_desc; a.cand_off = (const int*)d_cand_off; a.cand_idx = (const int*)d_cand_idx;
-  a.t_desc = (const uint4*)c->d_desc; a.kp = (const CmsKeyPoint*)c->d_kps; a.kp_cap = c->g.kp_cap;
-  a.pair_dist = (uint16_t*)d_pair_dist; a.kp_mp = (int*)d_kp_mp; a.mp_match = (int*)d_mp_match; a.rounds = (int*)d_rounds;
-  a.nnratio = nnratio; a.th_high = th_high; a.frame0 = 0; a.total = nullptr; a.cap = 0;
+  const CmsSearchLocalArgs a = track_search_local_args(c, d_mp_off, d_mp_desc, d_cand_off, d_cand_idx, d_pair_dist, (int*)d_kp_mp, d_mp_match, d_rounds, nnratio, th_high, 0, nullptr, 0);
   hipLaunchKernelGGL(k_search_local, dim3(B), dim3(1024), 0, c->stream, a);
   HIPCHK(hipGetLastError());
   return CMS_OK;
+}
+
+// ---- what the two one-frame host entries (cms_search_local_points, cms_search_by_projection) share: n points searched in frame b alone
+// staged inputs: every query addresses frame b, ONE list of n points, the caller's kp_mp padded to a frame row
+static void track_stage_one_frame(const cms_ctx* c, uint8_t* h, size_t o_qf, size_t o_mpoff, size_t o_kpmp, int b, int n, int nkp, const int* kp_mp) {
+  { int* qf = reinterpret_cast<int*>(h + o_qf); for (int i = 0; i < n; ++i) qf[i] = b; }
+  { int* mo = reinterpret_cast<int*>(h + o_mpoff); mo[0] = 0; mo[1] = n; }
+  { int* km = reinterpret_cast<int*>(h + o_kpmp); for (int k = 0; k < c->g.kp_cap; ++k) km[k] = k < nkp ? kp_mp[k] : -1; }
+}
+// the kernels index kp_mp by batch row; the block holds frame b's row only, and only frame b's rows are ever touched
+static int* track_kp_mp_of_frame(const cms_ctx* c, uint8_t* p, size_t o_kpmp, int b) { return (int*)(p + o_kpmp) - (size_t)b * c->g.kp_cap; }
+// matches: batch row -> key point index of frame b; returns how many there are
+static int track_rows_to_frame(const cms_ctx* c, int b, int n, const int* rows, int* match) {
+  int nm = 0;
+  for (int i = 0; i < n; ++i) { match[i] = rows[i] >= 0 ? rows[i] - b * c->g.kp_cap : -1; nm += rows[i] >= 0; }
+  return nm;
 }
 
 // One frame, host buffers: isInFrustum for the n map points, window query against frame b's grid, greedy search.  kp_mp: one int per
@@ -80,32 +108,26 @@ extern "C" int cms_search_local_points(cms_ctx* c, int b, const float* pose15, i
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const size_t n4 = (size_t)nmp * 4, kp4 = (size_t)c->g.kp_cap * 4;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   // one block in (pose .. mp_off), one block out (kp_mp .. rounds): one pinned copy each way, no synchronisation in between
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  const size_t o_pose = take(64), o_pos = take(3 * n4), o_nrm = take(3 * n4), o_min = take(n4), o_max = take(n4), o_desc = take((size_t)nmp * 32),
-               o_qf = take(n4), o_mpoff = take(16), o_kpmp = take(kp4);
-  const size_t in_bytes = o;
-  const size_t o_vis = take(nmp), o_px = take(n4), o_py = take(n4), o_lvl = take(n4), o_vc = take(n4), o_match = take(n4), o_tot = take(16), o_rounds = take(16);
-  const size_t out_begin = o_kpmp, out_bytes = o - o_kpmp;
-  const size_t o_qr = take(n4), o_qmin = take(n4), o_qmax = take(n4), o_cnt = take(n4), o_off = take(n4 + 4);
-  const size_t fixed = o;
-  int cap = 64 * nmp + 1024;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    const size_t o_idx = fixed, o_pd = fixed + al((size_t)cap * 4);
-    int rc = cms_scratch(c, o_pd + al((size_t)cap * 2));
-    if (rc) return rc;
-    rc = cms_hstage(c, std::max(in_bytes, out_begin + out_bytes));      // the read-back lands at h + out_begin, not at h
+  CmsBlock blk;
+  const size_t o_pose = blk.take(64), o_pos = blk.take(3 * n4), o_nrm = blk.take(3 * n4), o_min = blk.take(n4), o_max = blk.take(n4), o_desc = blk.take((size_t)nmp * 32),
+               o_qf = blk.take(n4), o_mpoff = blk.take(16), o_kpmp = blk.take(kp4);
+  const size_t in_bytes = blk.size;
+  const size_t o_vis = blk.take(nmp), o_px = blk.take(n4), o_py = blk.take(n4), o_lvl = blk.take(n4), o_vc = blk.take(n4), o_match = blk.take(n4), o_tot = blk.take(16),
+               o_rounds = blk.take(16);
+  const size_t out_begin = o_kpmp, out_bytes = blk.size - o_kpmp;
+  const size_t o_qr = blk.take(n4), o_qmin = blk.take(n4), o_qmax = blk.take(n4), o_cnt = blk.take(n4), o_off = blk.take(n4, 4);
+  const size_t o_idx = blk.size;
+  return cms_retry_capacity(64 * nmp + 1024, "cms_search_local_points", [&](int cap, int& tot) -> int {
+    const size_t o_pd = o_idx + cms_align((size_t)cap * 4);
+    int rc = track_reserve(c, o_pd + cms_align((size_t)cap * 2), std::max(in_bytes, out_begin + out_bytes));      // the read-back lands at h + out_begin, not at h
     if (rc) return rc;
     uint8_t* p = (uint8_t*)c->d_match;
     uint8_t* h = c->h_stage;
     memcpy(h + o_pose, pose15, 60);
     memcpy(h + o_pos, pos, 3 * n4); memcpy(h + o_nrm, normal, 3 * n4); memcpy(h + o_min, min_dist, n4); memcpy(h + o_max, max_dist, n4);
     memcpy(h + o_desc, mp_desc, (size_t)nmp * 32);
-    { int* qf = reinterpret_cast<int*>(h + o_qf); for (int i = 0; i < nmp; ++i) qf[i] = b; }
-    { int* mo = reinterpret_cast<int*>(h + o_mpoff); mo[0] = 0; mo[1] = nmp; }
-    { int* km = reinterpret_cast<int*>(h + o_kpmp); for (int k = 0; k < c->g.kp_cap; ++k) km[k] = k < nkp ? kp_mp[k] : -1; }
+    track_stage_one_frame(c, h, o_qf, o_mpoff, o_kpmp, b, nmp, nkp, kp_mp);
     HIPCHK(hipMemcpyAsync(p, h, in_bytes, hipMemcpyHostToDevice, s));
     rc = cms_is_in_frustum_device(c, nmp, nullptr, p + o_pose, p + o_pos, p + o_nrm, p + o_min, p + o_max, viewing_cos_limit, th, p + o_vis,
                                   p + o_px, p + o_py, p + o_lvl, p + o_vc, p + o_qr, p + o_qmin, p + o_qmax);
@@ -113,38 +135,26 @@ extern "C" int cms_search_local_points(cms_ctx* c, int b, const float* pose15, i
     rc = cms_features_in_area_batch_device(c, nmp, p + o_qf, p + o_px, p + o_py, p + o_qr, p + o_qmin, p + o_qmax, p + o_cnt, p + o_off, p + o_idx,
                                            cap, p + o_tot);
     if (rc) return rc;
-    CmsSearchLocalArgs a;
-    a.mp_off = (const int*)(p + o_mpoff); a.mp_desc = (const uint4*)(p + o_desc); a.cand_off = (const int*)(p + o_off); a.cand_idx = (const int*)(p + o_idx);
-    a.t_desc = (const uint4*)c->d_desc; a.kp = (const CmsKeyPoint*)c->d_kps; a.kp_cap = c->g.kp_cap;
-    a.pair_dist = (uint16_t*)(p + o_pd);
-    a.kp_mp = (int*)(p + o_kpmp) - (size_t)b * c->g.kp_cap;          // indexed by batch row: only frame b's rows are ever touched
-    a.mp_match = (int*)(p + o_match); a.rounds = (int*)(p + o_rounds);
-    a.nnratio = nnratio; a.th_high = th_high; a.frame0 = b; a.total = (const int*)(p + o_tot); a.cap = cap;
     // (window lists longer than `cap` are cut by the query kernel; the search kernel then sees *total > cap and does nothing)
+    const CmsSearchLocalArgs a = track_search_local_args(c, p + o_mpoff, p + o_desc, p + o_off, p + o_idx, p + o_pd, track_kp_mp_of_frame(c, p, o_kpmp, b), p + o_match,
+                                                         p + o_rounds, nnratio, th_high, b, p + o_tot, cap);
     hipLaunchKernelGGL(k_search_local, dim3(1), dim3(1024), 0, s, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h + out_begin, p + out_begin, out_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const int tot = *reinterpret_cast<const int*>(h + o_tot);
-    if (tot > cap) { cap = tot + 64; continue; }               // denser than 64 candidates per window: once more with the exact size
-    const int* match = reinterpret_cast<const int*>(h + o_match);
+    tot = *reinterpret_cast<const int*>(h + o_tot);
+    if (tot > cap) return CMS_OK;
     if (nkp > 0) memcpy(kp_mp, h + o_kpmp, (size_t)nkp * 4);
     if (in_view) memcpy(in_view, h + o_vis, nmp);
     if (proj_x) memcpy(proj_x, h + o_px, n4);
     if (proj_y) memcpy(proj_y, h + o_py, n4);
     if (level) memcpy(level, h + o_lvl, n4);
     if (view_cos) memcpy(view_cos, h + o_vc, n4);
-    int nm = 0;
-    for (int i = 0; i < nmp; ++i) {
-      const int m = match[i];
-      mp_match[i] = m >= 0 ? m - b * c->g.kp_cap : -1;         // batch row -> key point index of frame b
-      nm += m >= 0;
-    }
+    const int nm = track_rows_to_frame(c, b, nmp, reinterpret_cast<const int*>(h + o_match), mp_match);
     if (n_matches) *n_matches = nm;
     if (rounds) *rounds = *reinterpret_cast<const int*>(h + o_rounds);
     return CMS_OK;
-  }
-  return cms_fail(CMS_ERR_OVERFLOW, "cms_search_local_points: candidate lists kept growing");
+  });
 }
 
 // ---- ORBMatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono): device-pointer pieces (asynchronous on the ctx stream) ...
@@ -157,12 +167,8 @@ extern "C" int cms_project_last_frame_device(cms_ctx* c, int n, const void* d_qf
   CmsProjectLastArgs a;
   a.pose12 = (const float*)d_pose12; a.q_frame = (const int*)d_qframe; a.n = n; a.valid = (const uint8_t*)d_valid; a.Xw = (const float*)d_Xw;
   a.oct = (const int*)d_oct; a.th = th; a.F = c->g.F;
-  {
-    const float fov = (float)c->cam.fov_deg;
-    const float pif = 3.1415926535897932384626f;
-    a.cos_fov = std::cos(fov / 2 * (pif / 180));                      // CamModelGeneral::SetCosFovTh
-  }
-  for (int l = 0; l < 16; ++l) a.sf[l] = l < c->g.nlevels ? c->scale[l] : 0.0f;
+  a.cos_fov = cms_cos_fov(c);
+  cms_level_table(a.sf, c, c->scale, 0.0f);
   a.qx = (float*)d_qx; a.qy = (float*)d_qy; a.qr = (float*)d_qr; a.qmin = (int*)d_qmin; a.qmax = (int*)d_qmax;
   hipLaunchKernelGGL(k_project_last, dim3((n + 255) / 256), dim3(256), 0, c->stream, a);
   HIPCHK(hipGetLastError());
@@ -198,58 +204,46 @@ extern "C" int cms_search_by_projection(cms_ctx* c, int b, const float* pose12, 
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const size_t n4 = (size_t)nlast * 4, kp4 = (size_t)c->g.kp_cap * 4;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  const size_t o_pose = take(64), o_valid = take(nlast), o_xw = take(3 * n4), o_oct = take(n4), o_ang = take(n4), o_desc = take((size_t)nlast * 32),
-               o_qf = take(n4), o_mpoff = take(16), o_kpmp = take(kp4);
-  const size_t in_bytes = o;
-  const size_t o_match = take(n4), o_nm = take(16), o_tot = take(16);
-  const size_t out_begin = o_kpmp, out_bytes = o - o_kpmp;
-  const size_t o_qx = take(n4), o_qy = take(n4), o_qr = take(n4), o_qmin = take(n4), o_qmax = take(n4), o_cnt = take(n4), o_off = take(n4 + 4);
-  const size_t fixed = o;
-  int cap = 64 * nlast + 1024;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    const size_t o_idx = fixed, o_pd = fixed + al((size_t)cap * 4);
-    int rc = cms_scratch(c, o_pd + al((size_t)cap * 2));
-    if (rc) return rc;
-    rc = cms_hstage(c, std::max(in_bytes, out_begin + out_bytes));      // the read-back lands at h + out_begin, not at h
+  CmsBlock blk;
+  const size_t o_pose = blk.take(64), o_valid = blk.take(nlast), o_xw = blk.take(3 * n4), o_oct = blk.take(n4), o_ang = blk.take(n4), o_desc = blk.take((size_t)nlast * 32),
+               o_qf = blk.take(n4), o_mpoff = blk.take(16), o_kpmp = blk.take(kp4);
+  const size_t in_bytes = blk.size;
+  const size_t o_match = blk.take(n4), o_nm = blk.take(16), o_tot = blk.take(16);
+  const size_t out_begin = o_kpmp, out_bytes = blk.size - o_kpmp;
+  const size_t o_qx = blk.take(n4), o_qy = blk.take(n4), o_qr = blk.take(n4), o_qmin = blk.take(n4), o_qmax = blk.take(n4), o_cnt = blk.take(n4), o_off = blk.take(n4, 4);
+  const size_t o_idx = blk.size;
+  return cms_retry_capacity(64 * nlast + 1024, "cms_search_by_projection", [&](int cap, int& tot) -> int {
+    const size_t o_pd = o_idx + cms_align((size_t)cap * 4);
+    int rc = track_reserve(c, o_pd + cms_align((size_t)cap * 2), std::max(in_bytes, out_begin + out_bytes));      // the read-back lands at h + out_begin, not at h
     if (rc) return rc;
     uint8_t* p = (uint8_t*)c->d_match;
     uint8_t* h = c->h_stage;
     memcpy(h + o_pose, pose12, 48);
     memcpy(h + o_valid, valid, nlast); memcpy(h + o_xw, Xw, 3 * n4); memcpy(h + o_oct, octave, n4); memcpy(h + o_ang, angle, n4);
     memcpy(h + o_desc, mp_desc, (size_t)nlast * 32);
-    { int* qf = reinterpret_cast<int*>(h + o_qf); for (int i = 0; i < nlast; ++i) qf[i] = b; }
-    { int* mo = reinterpret_cast<int*>(h + o_mpoff); mo[0] = 0; mo[1] = nlast; }
-    { int* km = reinterpret_cast<int*>(h + o_kpmp); for (int k = 0; k < c->g.kp_cap; ++k) km[k] = k < nkp ? kp_mp[k] : -1; }
+    track_stage_one_frame(c, h, o_qf, o_mpoff, o_kpmp, b, nlast, nkp, kp_mp);
     HIPCHK(hipMemcpyAsync(p, h, in_bytes, hipMemcpyHostToDevice, s));
     rc = cms_project_last_frame_device(c, nlast, nullptr, p + o_pose, p + o_valid, p + o_xw, p + o_oct, th, p + o_qx, p + o_qy, p + o_qr, p + o_qmin, p + o_qmax);
     if (rc) return rc;
     rc = cms_features_in_area_batch_device(c, nlast, p + o_qf, p + o_qx, p + o_qy, p + o_qr, p + o_qmin, p + o_qmax, p + o_cnt, p + o_off, p + o_idx, cap, p + o_tot);
     if (rc) return rc;
-    CmsSearchLocalArgs a;
-    a.mp_off = (const int*)(p + o_mpoff); a.mp_desc = (const uint4*)(p + o_desc); a.cand_off = (const int*)(p + o_off); a.cand_idx = (const int*)(p + o_idx);
-    a.t_desc = (const uint4*)c->d_desc; a.kp = (const CmsKeyPoint*)c->d_kps; a.kp_cap = c->g.kp_cap;
-    a.pair_dist = (uint16_t*)(p + o_pd); a.kp_mp = (int*)(p + o_kpmp) - (size_t)b * c->g.kp_cap; a.mp_match = (int*)(p + o_match); a.rounds = nullptr;
-    a.nnratio = -1.0f; a.th_high = th_high; a.frame0 = b; a.total = (const int*)(p + o_tot); a.cap = cap;
+    const CmsSearchLocalArgs a = track_search_local_args(c, p + o_mpoff, p + o_desc, p + o_off, p + o_idx, p + o_pd, track_kp_mp_of_frame(c, p, o_kpmp, b), p + o_match,
+                                                         nullptr, -1.0f, th_high, b, p + o_tot, cap);
     hipLaunchKernelGGL(k_search_local, dim3(1), dim3(1024), 0, s, a);
     CmsRotFilterArgs r;
-    r.mp_off = (const int*)(p + o_mpoff); r.last_angle = (const float*)(p + o_ang); r.kp = (const CmsKeyPoint*)c->d_kps; r.kp_mp = a.kp_mp;
-    r.mp_match = (int*)(p + o_match); r.n_matches = (int*)(p + o_nm); r.check_orientation = check_orientation; r.total = a.total; r.cap = cap;
+    r.mp_off = a.mp_off; r.last_angle = (const float*)(p + o_ang); r.kp = a.kp; r.kp_mp = a.kp_mp;
+    r.mp_match = a.mp_match; r.n_matches = (int*)(p + o_nm); r.check_orientation = check_orientation; r.total = a.total; r.cap = cap;
     hipLaunchKernelGGL(k_rot_filter, dim3(1), dim3(1024), 0, s, r);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h + out_begin, p + out_begin, out_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const int tot = *reinterpret_cast<const int*>(h + o_tot);
-    if (tot > cap) { cap = tot + 64; continue; }
-    const int* m = reinterpret_cast<const int*>(h + o_match);
+    tot = *reinterpret_cast<const int*>(h + o_tot);
+    if (tot > cap) return CMS_OK;
     if (nkp > 0) memcpy(kp_mp, h + o_kpmp, (size_t)nkp * 4);
-    for (int i = 0; i < nlast; ++i) match[i] = m[i] >= 0 ? m[i] - b * c->g.kp_cap : -1;
+    track_rows_to_frame(c, b, nlast, reinterpret_cast<const int*>(h + o_match), match);
     if (n_matches) *n_matches = *reinterpret_cast<const int*>(h + o_nm);
     return CMS_OK;
-  }
-  return cms_fail(CMS_ERR_OVERFLOW, "cms_search_by_projection: candidate lists kept growing");
+  });
 }
 
 // ORBMatcher::SearchForInitialization(Frame& F1, Frame& F2, vbPrevMatched, vnMatches12, windowSize) (src/ORBMatcher.cpp:676-794): F2 is
@@ -263,15 +257,8 @@ extern "C" int cms_search_for_initialization(cms_ctx* c, int b2, int n1, const c
   if (n_matches) *n_matches = 0;
   if (n1 == 0) return CMS_OK;
   HIPCHK(hipSetDevice(c->device));
-  {   // the attribute is per device: one flag per device, like ba_lds_attrs_once / cms_area_reserve
-    static std::mutex mu;
-    static bool done[64] = {false};
-    std::lock_guard<std::mutex> lk(mu);
-    if (c->device >= 0 && c->device < 64 && !done[c->device]) {
-      HIPCHK(hipFuncSetAttribute((const void*)k_init_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-      done[c->device] = true;
-    }
-  }
+  static bool lds_done[64] = {false};
+  { const int rca = cms_lds_ceiling_once((const void*)k_init_greedy, 160 * 1024 - 1024, c->device, lds_done); if (rca) return rca; }
   const size_t lds = (size_t)c->g.kp_cap * 8;
   if (lds > 160 * 1024 - 1024) return cms_fail(CMS_ERR_UNSUPPORTED, "cms_search_for_initialization: too many key points per frame for the LDS tables");
   hipStream_t s = c->stream;
@@ -281,22 +268,17 @@ extern "C" int cms_search_for_initialization(cms_ctx* c, int b2, int n1, const c
   for (int i = 0; i < n1; ++i) matches12[i] = -1;
   if (nq == 0) return CMS_OK;
   const size_t q4 = (size_t)nq * 4, n4 = (size_t)n1 * 4;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  const size_t o_qi = take(q4), o_qx = take(q4), o_qy = take(q4), o_qr = take(q4), o_qmin = take(q4), o_qmax = take(q4), o_qf = take(q4),
-               o_desc = take((size_t)n1 * 32), o_ang = take(n4), o_prev = take(2 * n4);
-  const size_t in_bytes = o;
-  const size_t o_m12 = take(n4), o_nm = take(16), o_tot = take(16);
-  const size_t out_begin = o_prev, out_bytes = o - o_prev;
-  const size_t o_bin = take(n1), o_cnt = take(q4), o_off = take(q4 + 4);
-  const size_t fixed = o;
-  int cap = 128 * nq + 4096;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    const size_t o_idx = fixed, o_pd = fixed + al((size_t)cap * 4);
-    int rc = cms_scratch(c, o_pd + al((size_t)cap * 2));
-    if (rc) return rc;
-    rc = cms_hstage(c, std::max(in_bytes, out_begin + out_bytes));      // the read-back lands at h + out_begin, not at h
+  CmsBlock blk;
+  const size_t o_qi = blk.take(q4), o_qx = blk.take(q4), o_qy = blk.take(q4), o_qr = blk.take(q4), o_qmin = blk.take(q4), o_qmax = blk.take(q4), o_qf = blk.take(q4),
+               o_desc = blk.take((size_t)n1 * 32), o_ang = blk.take(n4), o_prev = blk.take(2 * n4);
+  const size_t in_bytes = blk.size;
+  const size_t o_m12 = blk.take(n4), o_nm = blk.take(16), o_tot = blk.take(16);
+  const size_t out_begin = o_prev, out_bytes = blk.size - o_prev;
+  const size_t o_bin = blk.take(n1), o_cnt = blk.take(q4), o_off = blk.take(q4, 4);
+  const size_t o_idx = blk.size;
+  return cms_retry_capacity(128 * nq + 4096, "cms_search_for_initialization", [&](int cap, int& tot) -> int {
+    const size_t o_pd = o_idx + cms_align((size_t)cap * 4);
+    int rc = track_reserve(c, o_pd + cms_align((size_t)cap * 2), std::max(in_bytes, out_begin + out_bytes));      // the read-back lands at h + out_begin, not at h
     if (rc) return rc;
     uint8_t* p = (uint8_t*)c->d_match;
     uint8_t* h = c->h_stage;
@@ -326,12 +308,11 @@ extern "C" int cms_search_for_initialization(cms_ctx* c, int b2, int n1, const c
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h + out_begin, p + out_begin, out_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const int tot = *reinterpret_cast<const int*>(h + o_tot);
-    if (tot > cap) { cap = tot + 64; continue; }
+    tot = *reinterpret_cast<const int*>(h + o_tot);
+    if (tot > cap) return CMS_OK;
     memcpy(matches12, h + o_m12, n4);
     memcpy(prev_matched, h + o_prev, 2 * n4);
     if (n_matches) *n_matches = *reinterpret_cast<const int*>(h + o_nm);
     return CMS_OK;
-  }
-  return cms_fail(CMS_ERR_OVERFLOW, "cms_search_for_initialization: candidate lists kept growing");
+  });
 }

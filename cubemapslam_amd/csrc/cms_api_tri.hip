@@ -1,5 +1,7 @@
 // cms_api_tri.hip -- host side of LocalMapping::CreateNewMapPoints and of the search half of ORBMatcher::Fuse, included by
-// cms_lib.hip after cms_api_track.hip.
+// cms_lib.hip after cms_api_track.hip.  Scratch blocks are laid out with CmsBlock (TriWork: the work area of a CreateNewMapPoints call); the two
+// Fuse entries fill their kernels' arguments with fuse_project_args / fuse_scan_args, query the windows through cms_area_launch and repeat a call
+// whose candidate lists did not fit through cms_retry_capacity.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -37,12 +39,18 @@ struct TriDev {                                           // device views of the
   const CmsTriKF* kf; const CmsKeyPoint* kp; const uint4* desc; const float* rays; const int* mp; const int* feat_node;
   const int* node_id; const int* node_off; const int* node_feat;
 };
-inline size_t tri_al(size_t v) { return (v + 255) & ~(size_t)255; }
-size_t tri_work_bytes(int njobs, int nneigh, int max_n1, int cap) {
-  const size_t nb = (size_t)njobs * (size_t)cap;
-  return tri_al((size_t)nneigh * sizeof(CmsTriPair) + 16) + tri_al((size_t)njobs * sizeof(CmsTriJob) + 16) + tri_al((size_t)nneigh * 4 + 16) +
-         tri_al((size_t)njobs * 4 + 16) + 3 * tri_al(nb * 4 + 16) + tri_al(nb * 12 + 16) + tri_al((size_t)nneigh * (size_t)max_n1 * sizeof(CmsTriCand) + 16);
-}
+// work area of a CreateNewMapPoints call: inputs (pairs | jobs | pair -> job), outputs (counts | neighbour | idx1 | idx2 | x3d), candidates
+struct TriWork {
+  size_t o_pair, o_job, o_pjob, o_nnew, o_on, o_o1, o_o2, o_ox, o_cand, bytes;
+  TriWork(int njobs, int nneigh, int max_n1, int cap) {
+    const size_t nb = (size_t)njobs * (size_t)cap;
+    CmsBlock blk;
+    o_pair = blk.take((size_t)nneigh * sizeof(CmsTriPair), 16); o_job = blk.take((size_t)njobs * sizeof(CmsTriJob), 16); o_pjob = blk.take((size_t)nneigh * 4, 16);
+    o_nnew = blk.take((size_t)njobs * 4, 16); o_on = blk.take(nb * 4, 16); o_o1 = blk.take(nb * 4, 16); o_o2 = blk.take(nb * 4, 16); o_ox = blk.take(nb * 12, 16);
+    o_cand = blk.take((size_t)nneigh * (size_t)max_n1 * sizeof(CmsTriCand), 16);
+    bytes = blk.size;
+  }
+};
 int tri_check_keyframe(const cms_keyframe& k, const char* who) {
   if (k.n < 0 || k.n > CMS_TRI_MAXF || k.nnodes < 0 || (k.n > 0 && (!k.kps || !k.desc || !k.rays || !k.mp)) ||
       (k.nnodes > 0 && (!k.node_id || !k.node_off || !k.node_feat)))
@@ -94,13 +102,8 @@ int tri_run(cms_ctx* c, const TriDev& dev, const CmsTriKF* hkf, const float* hme
       track_rays_to_cubemap(F, C2[0], C2[1], C2[2], pr.ex, pr.ey);
     }
   }
-  const size_t nb = (size_t)njobs * (size_t)cap;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += tri_al(bytes + 16); return at; };
-  const size_t o_pair = take((size_t)nneigh * sizeof(CmsTriPair)), o_job = take((size_t)njobs * sizeof(CmsTriJob)), o_pjob = take((size_t)nneigh * 4),
-               o_nnew = take((size_t)njobs * 4), o_on = take(nb * 4), o_o1 = take(nb * 4), o_o2 = take(nb * 4), o_ox = take(nb * 12),
-               o_cand = take((size_t)nneigh * (size_t)max_n1 * sizeof(CmsTriCand));
-  (void)o_cand;
+  const TriWork w(njobs, nneigh, max_n1, cap);
+  const size_t o_pair = w.o_pair, o_job = w.o_job, o_pjob = w.o_pjob, o_nnew = w.o_nnew, o_on = w.o_on, o_o1 = w.o_o1, o_o2 = w.o_o2, o_ox = w.o_ox, o_cand = w.o_cand;
   hipStream_t s = c->stream;
   uint8_t* p = work;
   // inputs (pairs | jobs | pair -> job) and outputs (counts | neighbour | idx1 | idx2 | x3d) are contiguous in the work block and mirrored in the
@@ -127,14 +130,10 @@ int tri_run(cms_ctx* c, const TriDev& dev, const CmsTriKF* hkf, const float* hme
   a.kp = dev.kp; a.desc = dev.desc; a.rays = dev.rays; a.mp = dev.mp; a.feat_node = dev.feat_node;
   a.node_id = dev.node_id; a.node_off = dev.node_off; a.node_feat = dev.node_feat;
   a.F = F;
-  {                                                                    // CamModelGeneral::SetCosFovTh (CamModelGeneral.h:224-229), float
-    const float fov = (float)c->cam.fov_deg;
-    const float pif = 3.1415926535897932384626f;
-    a.cos_fov = std::cos(fov / 2 * (pif / 180));
-  }
+  a.cos_fov = cms_cos_fov(c);
   a.ratio_factor = 1.5f * c->scale[1];                                // 1.5f * mpCurrentKeyFrame->mfScaleFactor
   a.check_orientation = check_orientation;
-  for (int l = 0; l < 16; ++l) { a.sf[l] = l < c->g.nlevels ? c->scale[l] : 1.0f; a.sigma2[l] = l < c->g.nlevels ? c->sigma2[l] : 1.0f; }
+  cms_level_table(a.sf, c, c->scale, 1.0f); cms_level_table(a.sigma2, c, c->sigma2, 1.0f);
   a.cap = cap;
   a.n_new = (int*)po; a.out_neigh = (int*)(po + (o_on - o_nnew)); a.out_idx1 = (int*)(po + (o_o1 - o_nnew)); a.out_idx2 = (int*)(po + (o_o2 - o_nnew));
   a.out_x3d = (float*)(po + (o_ox - o_nnew));
@@ -146,7 +145,7 @@ int tri_run(cms_ctx* c, const TriDev& dev, const CmsTriKF* hkf, const float* hme
     hipLaunchKernelGGL(k_tri_resolve, dim3(njobs), dim3(1024), 0, s, a, (const CmsTriCand*)(p + o_cand), max_n1);
   }
   HIPCHK(hipGetLastError());
-  if (copy_engine) HIPCHK(hipMemcpyAsync(hout, p + o_nnew, cap > 0 ? out_bytes : tri_al((size_t)njobs * 4 + 16), hipMemcpyDeviceToHost, s));
+  if (copy_engine) HIPCHK(hipMemcpyAsync(hout, p + o_nnew, cap > 0 ? out_bytes : o_on - o_nnew, hipMemcpyDeviceToHost, s));
   const auto t_1 = std::chrono::steady_clock::now();
   HIPCHK(hipStreamSynchronize(s));
   if (timing) {
@@ -212,12 +211,11 @@ static int tri_flatten_upload(cms_ctx* c, int nkf, KfAt&& kf_at, int n_current, 
     }
   }
   HIPCHK(hipSetDevice(c->device));
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += tri_al(bytes + 16); return at; };
-  const size_t o_kf = take(kfs.size() * sizeof(CmsTriKF)), o_kp = take(kp.size() * sizeof(CmsKeyPoint)), o_desc = take(desc.size()), o_rays = take(rays.size() * 4),
-               o_mp = take(mp.size() * 4), o_fn = take(feat_node.size() * 4), o_nid = take(node_id.size() * 4), o_noff = take(node_off.size() * 4),
-               o_nfeat = take(node_feat.size() * 4);
-  o_work = o;
+  CmsBlock blk;
+  const size_t o_kf = blk.take(kfs.size() * sizeof(CmsTriKF), 16), o_kp = blk.take(kp.size() * sizeof(CmsKeyPoint), 16), o_desc = blk.take(desc.size(), 16),
+               o_rays = blk.take(rays.size() * 4, 16), o_mp = blk.take(mp.size() * 4, 16), o_fn = blk.take(feat_node.size() * 4, 16), o_nid = blk.take(node_id.size() * 4, 16),
+               o_noff = blk.take(node_off.size() * 4, 16), o_nfeat = blk.take(node_feat.size() * 4, 16);
+  o_work = blk.size;
   int rc = cms_scratch(c, o_work + work_bytes(max_n1));
   if (rc) return rc;
   uint8_t* p = (uint8_t*)c->d_match;
@@ -258,7 +256,7 @@ extern "C" int cms_create_new_map_points(cms_ctx* c, int njobs, const cms_keyfra
   size_t o_work = 0;
   int max_n1 = 1;
   int rc = tri_flatten_upload(c, nkf, kf_at, njobs, "cms_create_new_map_points: bad key frame (at most 4096 features)", kfs, median, dev, o_work, max_n1,
-                              [&](int mn1) { return tri_work_bytes(njobs, nneigh, mn1, cap_per_job); });
+                              [&](int mn1) { return TriWork(njobs, nneigh, mn1, cap_per_job).bytes; });
   if (rc) return rc;
   uint8_t* p = (uint8_t*)c->d_match;
   std::vector<int> cur_idx((size_t)njobs), neigh_idx((size_t)nneigh + 1);
@@ -282,12 +280,13 @@ extern "C" int cms_search_for_triangulation(cms_ctx* c, const cms_keyframe* kf1,
   TriDev dev;
   size_t o_work = 0;
   int max_n1 = 1;
-  const size_t o_pair = 0, o_job = tri_al(sizeof(CmsTriPair) + 16), o_m = o_job + tri_al(sizeof(CmsTriJob) + 16);
+  CmsBlock blk;
+  const size_t o_pair = blk.take(sizeof(CmsTriPair), 16), o_job = blk.take(sizeof(CmsTriJob), 16), o_m = blk.size;
   int rc = tri_flatten_upload(c, 2, kf_at, 1, "cms_search_for_triangulation: bad key frame (at most 4096 features)", kfs, median, dev, o_work, max_n1,
-                              [&](int mn1) { return o_m + tri_al((size_t)mn1 * 4 + 16) + 256; });
+                              [&](int mn1) { return o_m + cms_align((size_t)mn1 * 4 + 16) + 256; });
   if (rc) return rc;
   uint8_t* p = (uint8_t*)c->d_match + o_work;
-  const size_t o_n = o_m + tri_al((size_t)max_n1 * 4 + 16);
+  const size_t o_n = o_m + cms_align((size_t)max_n1 * 4 + 16);
   CmsTriPair pr;
   pr.kf2 = 1; pr.skip = 0;
   if (E12) std::memcpy(pr.E12, E12, sizeof(pr.E12));
@@ -306,7 +305,7 @@ extern "C" int cms_search_for_triangulation(cms_ctx* c, const cms_keyframe* kf1,
   a.node_id = dev.node_id; a.node_off = dev.node_off; a.node_feat = dev.node_feat;
   a.F = c->g.F;
   a.check_orientation = check_orientation;
-  for (int l = 0; l < 16; ++l) { a.sf[l] = l < c->g.nlevels ? c->scale[l] : 1.0f; a.sigma2[l] = l < c->g.nlevels ? c->sigma2[l] : 1.0f; }
+  cms_level_table(a.sf, c, c->scale, 1.0f); cms_level_table(a.sigma2, c, c->sigma2, 1.0f);
   hipLaunchKernelGGL(k_tri_search, dim3(1), dim3(1024), 0, s, a, (int*)(p + o_m), (int*)(p + o_n));
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(matches12, p + o_m, (size_t)kf1->n * 4, hipMemcpyDeviceToHost, s));
@@ -422,12 +421,9 @@ extern "C" int cms_kfstore_put(cms_kfstore* st, int slot, const cms_keyframe* kf
   }
   HIPCHK(hipMemcpyAsync(st->d_kf + slot, &d, sizeof(d), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(st->d_kp_cnt + slot, &kf->n, sizeof(int), hipMemcpyHostToDevice, s));
-  {
-    const float inv = (float)(3 * CMS_AREA_G) / (float)c->g.W;          // mfGridElementLengthInv (Frame.cpp:149)
-    hipLaunchKernelGGL(k_area_grid, dim3(1), dim3(1024), (size_t)(st->maxf + 1) * 8, s, (const CmsKeyPoint*)(st->d_kp + f0), (const int*)(st->d_kp_cnt + slot), st->maxf, c->g.F, inv,
-                       st->d_sorted + f0, st->d_cell_start + (size_t)slot * (CMS_AREA_CELLS + 1), st->d_nvalid + slot);
-    HIPCHK(hipGetLastError());
-  }
+  hipLaunchKernelGGL(k_area_grid, dim3(1), dim3(1024), (size_t)(st->maxf + 1) * 8, s, (const CmsKeyPoint*)(st->d_kp + f0), (const int*)(st->d_kp_cnt + slot), st->maxf, c->g.F,
+                     cms_grid_inv(c), st->d_sorted + f0, st->d_cell_start + (size_t)slot * (CMS_AREA_CELLS + 1), st->d_nvalid + slot);
+  HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(s));
   st->h_kf[(size_t)slot] = d; st->h_median[(size_t)slot] = kf->median_depth; st->used[(size_t)slot] = 1;
   return CMS_OK;
@@ -714,7 +710,7 @@ extern "C" int cms_kfstore_create_new_map_points(cms_kfstore* st, int njobs, con
     if (neigh_slot[q] < 0 || neigh_slot[q] >= st->maxkf || !st->used[(size_t)neigh_slot[q]]) return cms_fail(CMS_ERR_ARG, "cms_kfstore_create_new_map_points: empty slot");
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(kfstore_order_behind_puts(st));
-  const size_t need = tri_work_bytes(njobs, nneigh, st->maxf, cap_per_job);
+  const size_t need = TriWork(njobs, nneigh, st->maxf, cap_per_job).bytes;
   if (need > st->work_bytes) {
     if (st->d_work) HIPCHK(hipFree(st->d_work));
     st->d_work = nullptr; st->work_bytes = 0;
@@ -728,6 +724,29 @@ extern "C" int cms_kfstore_create_new_map_points(cms_kfstore* st, int njobs, con
                  out_neigh, out_idx1, out_idx2, out_x3d);
 }
 
+// ---- search half of ORBMatcher::Fuse: the arguments of its two kernels, for one key frame of the context and for jobs on the store alike
+// k_fuse_project: n entries; mp_frame (NULL: all in frame 0 of pose15) names an entry's pose, src (NULL: itself) the map point it stands for
+static CmsFuseArgs fuse_project_args(const cms_ctx* c, int n, float th, const void* pose15, const void* mp_frame, const void* skip, const void* src, const void* P,
+                                     const void* normal, const void* min_dist, const void* max_dist, void* qx, void* qy, void* qr, void* qmin, void* qmax, void* level) {
+  CmsFuseArgs a = {};
+  a.pose15 = (const float*)pose15; a.mp_frame = (const int*)mp_frame; a.n = n; a.skip = (const uint8_t*)skip; a.src = (const int*)src;
+  a.P = (const float*)P; a.normal = (const float*)normal; a.min_dist = (const float*)min_dist; a.max_dist = (const float*)max_dist;
+  a.th = th; a.log_scale = std::log(c->scale[1]); a.nlevels = c->g.nlevels; a.F = c->g.F; a.bounds_scaled = c->dist_bounds_scaled;
+  cms_level_table(a.sf, c, c->scale, 0.0f);
+  a.qx = (float*)qx; a.qy = (float*)qy; a.qr = (float*)qr; a.qmin = (int*)qmin; a.qmax = (int*)qmax; a.level = (int*)level;
+  return a;
+}
+// k_fuse_scan over the windows of `fa`'s projections.  cap / row_slot / maxf: see CmsFuseScanArgs (0 / NULL / 0 for one key frame of the context)
+static CmsFuseScanArgs fuse_scan_args(const cms_ctx* c, const CmsFuseArgs& fa, const void* mp_desc, const void* cand_off, const void* cand_idx, const CmsKeyPoint* kp,
+                                      const void* t_desc, int* best_idx, int* best_dist, int cap, const void* row_slot, int maxf) {
+  CmsFuseScanArgs a = {};
+  a.n = fa.n; a.qx = fa.qx; a.qy = fa.qy; a.level = fa.level; a.src = fa.src; a.mp_desc = (const uint4*)mp_desc;
+  a.cand_off = (const int*)cand_off; a.cand_idx = (const int*)cand_idx; a.kp = kp; a.t_desc = (const uint4*)t_desc;
+  cms_level_table(a.inv_sigma2, c, c->inv_sigma2, 0.0f);
+  a.best_idx = best_idx; a.best_dist = best_dist; a.cap = cap; a.row_slot = (const int*)row_slot; a.maxf = maxf;
+  return a;
+}
+
 // search half of ORBMatcher::Fuse(pKF, vpMapPoints, th) for key frame slot b (cms_area_set_keypoints / _descriptors + cms_area_grid first)
 extern "C" int cms_fuse_search(cms_ctx* c, int b, const float* pose15, int nmp, const uint8_t* skip, const float* pos, const float* normal,
                                const float* min_dist, const float* max_dist, const uint8_t* mp_desc, float th, int* best_idx, int* best_dist) {
@@ -739,19 +758,15 @@ extern "C" int cms_fuse_search(cms_ctx* c, int b, const float* pose15, int nmp, 
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const size_t n4 = (size_t)nmp * 4;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  const size_t o_pose = take(64), o_skip = take(nmp), o_pos = take(3 * n4), o_nrm = take(3 * n4), o_min = take(n4), o_max = take(n4),
-               o_desc = take((size_t)nmp * 32), o_qx = take(n4), o_qy = take(n4), o_qr = take(n4), o_qmin = take(n4), o_qmax = take(n4), o_lvl = take(n4),
-               o_cnt = take(n4), o_off = take(n4 + 4), o_tot = take(16), o_qf = take(n4), o_bi = take(n4), o_bd = take(n4);
-  const size_t fixed = o;
-  int cap = 64 * nmp + 1024;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    int rc = cms_scratch(c, fixed + al((size_t)cap * 4));
+  CmsBlock blk;
+  const size_t o_pose = blk.take(64), o_skip = blk.take(nmp), o_pos = blk.take(3 * n4), o_nrm = blk.take(3 * n4), o_min = blk.take(n4), o_max = blk.take(n4),
+               o_desc = blk.take((size_t)nmp * 32), o_qx = blk.take(n4), o_qy = blk.take(n4), o_qr = blk.take(n4), o_qmin = blk.take(n4), o_qmax = blk.take(n4),
+               o_lvl = blk.take(n4), o_cnt = blk.take(n4), o_off = blk.take(n4, 4), o_tot = blk.take(16), o_qf = blk.take(n4), o_bi = blk.take(n4), o_bd = blk.take(n4);
+  const size_t o_idx = blk.size;
+  return cms_retry_capacity(64 * nmp + 1024, "cms_fuse_search", [&](int cap, int& tot) -> int {
+    int rc = cms_scratch(c, o_idx + cms_align((size_t)cap * 4));
     if (rc) return rc;
     uint8_t* p = (uint8_t*)c->d_match;
-    const size_t o_idx = fixed;
     HIPCHK(hipMemcpyAsync(p + o_pose, pose15, 60, hipMemcpyHostToDevice, s));
     if (skip) HIPCHK(hipMemcpyAsync(p + o_skip, skip, nmp, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_pos, pos, 3 * n4, hipMemcpyHostToDevice, s));
@@ -761,30 +776,17 @@ extern "C" int cms_fuse_search(cms_ctx* c, int b, const float* pose15, int nmp, 
     HIPCHK(hipMemcpyAsync(p + o_desc, mp_desc, (size_t)nmp * 32, hipMemcpyHostToDevice, s));
     const std::vector<int> qf((size_t)nmp, b);
     HIPCHK(hipMemcpyAsync(p + o_qf, qf.data(), n4, hipMemcpyHostToDevice, s));
-    CmsFuseArgs fa;
-    fa.src = nullptr;
-    fa.bounds_scaled = c->dist_bounds_scaled;
-    fa.pose15 = (const float*)(p + o_pose); fa.mp_frame = nullptr; fa.n = nmp; fa.skip = skip ? p + o_skip : nullptr;
-    fa.P = (const float*)(p + o_pos); fa.normal = (const float*)(p + o_nrm); fa.min_dist = (const float*)(p + o_min); fa.max_dist = (const float*)(p + o_max);
-    fa.th = th; fa.log_scale = std::log(c->scale[1]); fa.nlevels = c->g.nlevels; fa.F = c->g.F;
-    for (int l = 0; l < 16; ++l) fa.sf[l] = l < c->g.nlevels ? c->scale[l] : 0.0f;
-    fa.qx = (float*)(p + o_qx); fa.qy = (float*)(p + o_qy); fa.qr = (float*)(p + o_qr); fa.qmin = (int*)(p + o_qmin); fa.qmax = (int*)(p + o_qmax);
-    fa.level = (int*)(p + o_lvl);
+    const CmsFuseArgs fa = fuse_project_args(c, nmp, th, p + o_pose, nullptr, skip ? p + o_skip : nullptr, nullptr, p + o_pos, p + o_nrm, p + o_min, p + o_max,
+                                             p + o_qx, p + o_qy, p + o_qr, p + o_qmin, p + o_qmax, p + o_lvl);
     hipLaunchKernelGGL(k_fuse_project, dim3((nmp + 255) / 256), dim3(256), 0, s, fa);
     HIPCHK(hipGetLastError());
     rc = cms_features_in_area_batch_device(c, nmp, p + o_qf, p + o_qx, p + o_qy, p + o_qr, p + o_qmin, p + o_qmax, p + o_cnt, p + o_off, p + o_idx, cap,
                                            p + o_tot);
     if (rc) return rc;
-    int tot = 0;
     HIPCHK(hipMemcpyAsync(&tot, p + o_tot, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (tot > cap) { cap = tot + 64; continue; }
-    CmsFuseScanArgs sa;
-    sa.cap = 0; sa.src = nullptr; sa.row_slot = nullptr; sa.maxf = 0;
-    sa.n = nmp; sa.qx = (const float*)(p + o_qx); sa.qy = (const float*)(p + o_qy); sa.level = (const int*)(p + o_lvl); sa.mp_desc = (const uint4*)(p + o_desc);
-    sa.cand_off = (const int*)(p + o_off); sa.cand_idx = (const int*)(p + o_idx); sa.kp = (const CmsKeyPoint*)c->d_kps; sa.t_desc = (const uint4*)c->d_desc;
-    for (int l = 0; l < 16; ++l) sa.inv_sigma2[l] = l < c->g.nlevels ? c->inv_sigma2[l] : 0.0f;
-    sa.best_idx = (int*)(p + o_bi); sa.best_dist = (int*)(p + o_bd);
+    if (tot > cap) return CMS_OK;
+    const CmsFuseScanArgs sa = fuse_scan_args(c, fa, p + o_desc, p + o_off, p + o_idx, (const CmsKeyPoint*)c->d_kps, c->d_desc, (int*)(p + o_bi), (int*)(p + o_bd), 0, nullptr, 0);
     hipLaunchKernelGGL(k_fuse_scan, dim3((nmp * 8 + 255) / 256), dim3(256), 0, s, sa);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(best_idx, p + o_bi, n4, hipMemcpyDeviceToHost, s));
@@ -793,8 +795,7 @@ extern "C" int cms_fuse_search(cms_ctx* c, int b, const float* pose15, int nmp, 
     const int base = b * c->g.kp_cap;
     for (int i = 0; i < nmp; ++i) if (best_idx[i] >= 0) best_idx[i] -= base;       // batch row -> key point index of slot b
     return CMS_OK;
-  }
-  return cms_fail(CMS_ERR_OVERFLOW, "cms_fuse_search: candidate lists kept growing");
+  });
 }
 
 // MapPoint::ComputeDistinctiveDescriptors for a batch of map points (host buffers)
@@ -808,8 +809,9 @@ extern "C" int cms_distinctive_descriptors(cms_ctx* c, int npts, const int* obs_
     if (obs_off[p + 1] - obs_off[p] > 65535) return cms_fail(CMS_ERR_UNSUPPORTED, "cms_distinctive_descriptors: more than 65535 observations of one point");
   }
   HIPCHK(hipSetDevice(c->device));
-  const size_t o_off = 0, o_desc = tri_al((size_t)(npts + 1) * 4), o_out = o_desc + tri_al((size_t)nobs * 32 + 32);
-  int rc = cms_scratch(c, o_out + tri_al((size_t)npts * 4));
+  CmsBlock blk;
+  const size_t o_off = blk.take((size_t)(npts + 1) * 4), o_desc = blk.take((size_t)nobs * 32, 32), o_out = blk.take((size_t)npts * 4);
+  int rc = cms_scratch(c, blk.size);
   if (rc) return rc;
   uint8_t* p = (uint8_t*)c->d_match;
   hipStream_t s = c->stream;
@@ -836,16 +838,15 @@ extern "C" int cms_update_normal_and_depth(cms_ctx* c, int npts, const int* obs_
   }
   HIPCHK(hipSetDevice(c->device));
   const size_t n4 = (size_t)npts * 4;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += tri_al(bytes + 16); return at; };
-  const size_t o_off = take(n4 + 4), o_pos = take(3 * n4), o_ow = take((size_t)nobs * 12), o_ref = take(3 * n4), o_lvl = take(n4), o_sf = take(64),
-               o_nrm = take(3 * n4), o_min = take(n4), o_max = take(n4);
-  int rc = cms_scratch(c, o);
+  CmsBlock blk;
+  const size_t o_off = blk.take(n4 + 4, 16), o_pos = blk.take(3 * n4, 16), o_ow = blk.take((size_t)nobs * 12, 16), o_ref = blk.take(3 * n4, 16), o_lvl = blk.take(n4, 16),
+               o_sf = blk.take(64, 16), o_nrm = blk.take(3 * n4, 16), o_min = blk.take(n4, 16), o_max = blk.take(n4, 16);
+  int rc = cms_scratch(c, blk.size);
   if (rc) return rc;
   uint8_t* p = (uint8_t*)c->d_match;
   hipStream_t s = c->stream;
   float sf[16];
-  for (int l = 0; l < 16; ++l) sf[l] = l < c->g.nlevels ? c->scale[l] : 1.0f;
+  cms_level_table(sf, c, c->scale, 1.0f);
   HIPCHK(hipMemcpyAsync(p + o_off, obs_off, n4 + 4, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(p + o_pos, pos, 3 * n4, hipMemcpyHostToDevice, s));
   if (nobs > 0) HIPCHK(hipMemcpyAsync(p + o_ow, obs_Ow, (size_t)nobs * 12, hipMemcpyHostToDevice, s));
@@ -910,13 +911,12 @@ static int kfstore_fuse_core(cms_kfstore* st, int njobs, const int* job_slot, co
   hipStream_t s = c->stream;
   if (!job_set0) npts = nmp;
   const size_t n4 = (size_t)nmp * 4, j4 = (size_t)njobs * 4, p4 = (size_t)npts * 4;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  const size_t o_pose = take(pose.size() * 4), o_joff = take(j4 + 4), o_jslot = take(j4), o_jset = take(j4), o_src = take(n4), o_job = take(n4), o_slot = take(n4), o_skip = take(nmp),
-               o_pos = take(3 * p4), o_nrm = take(3 * p4), o_min = take(p4), o_max = take(p4), o_desc = take((size_t)npts * 32), o_qx = take(n4), o_qy = take(n4), o_qr = take(n4),
-               o_qmin = take(n4), o_qmax = take(n4), o_lvl = take(n4), o_cnt = take(n4), o_off = take(n4 + 4), o_tot = take(16), o_bi = take(n4), o_bd = take(n4);
-  const size_t fixed = o;
+  CmsBlock blk;
+  const size_t o_pose = blk.take(pose.size() * 4), o_joff = blk.take(j4, 4), o_jslot = blk.take(j4), o_jset = blk.take(j4), o_src = blk.take(n4), o_job = blk.take(n4),
+               o_slot = blk.take(n4), o_skip = blk.take(nmp), o_pos = blk.take(3 * p4), o_nrm = blk.take(3 * p4), o_min = blk.take(p4), o_max = blk.take(p4),
+               o_desc = blk.take((size_t)npts * 32), o_qx = blk.take(n4), o_qy = blk.take(n4), o_qr = blk.take(n4), o_qmin = blk.take(n4), o_qmax = blk.take(n4),
+               o_lvl = blk.take(n4), o_cnt = blk.take(n4), o_off = blk.take(n4, 4), o_tot = blk.take(16), o_bi = blk.take(n4), o_bd = blk.take(n4);
+  const size_t o_idx = blk.size;
   bool direct = false;
   {
     hipPointerAttribute_t a1, a2;
@@ -924,12 +924,10 @@ static int kfstore_fuse_core(cms_kfstore* st, int njobs, const int* job_slot, co
       direct = a1.type == hipMemoryTypeHost && a2.type == hipMemoryTypeHost;
     else (void)hipGetLastError();                                  // (a pageable pointer: not an error, just the copies)
   }
-  int cap = 64 * nmp + 1024;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    int rc = cms_scratch(c, fixed + al((size_t)cap * 4));
+  return cms_retry_capacity(64 * nmp + 1024, "cms_kfstore_fuse_search", [&](int cap, int& tot) -> int {
+    int rc = cms_scratch(c, o_idx + cms_align((size_t)cap * 4));
     if (rc) return rc;
     uint8_t* p = (uint8_t*)c->d_match;
-    const size_t o_idx = fixed;
     HIPCHK(hipMemcpyAsync(p + o_pose, pose.data(), pose.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_joff, mp_off, j4 + 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_jslot, job_slot, j4, hipMemcpyHostToDevice, s));
@@ -940,59 +938,32 @@ static int kfstore_fuse_core(cms_kfstore* st, int njobs, const int* job_slot, co
     HIPCHK(hipMemcpyAsync(p + o_min, min_dist, p4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_max, max_dist, p4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_desc, mp_desc, (size_t)npts * 32, hipMemcpyHostToDevice, s));
-    const int* src_dev = job_set0 ? (const int*)(p + o_src) : nullptr;
     hipLaunchKernelGGL(k_fuse_expand_jobs, dim3((nmp + 255) / 256), dim3(256), 0, s, nmp, njobs, (const int*)(p + o_joff), (const int*)(p + o_jslot), (int*)(p + o_job), (int*)(p + o_slot),
                        job_set0 ? (const int*)(p + o_jset) : nullptr, job_set0 ? (int*)(p + o_src) : nullptr);
-    CmsFuseArgs fa;
-    fa.src = src_dev;
-    fa.bounds_scaled = c->dist_bounds_scaled;
-    fa.pose15 = (const float*)(p + o_pose); fa.mp_frame = (const int*)(p + o_job); fa.n = nmp; fa.skip = skip ? p + o_skip : nullptr;
-    fa.P = (const float*)(p + o_pos); fa.normal = (const float*)(p + o_nrm); fa.min_dist = (const float*)(p + o_min); fa.max_dist = (const float*)(p + o_max);
-    fa.th = th; fa.log_scale = std::log(c->scale[1]); fa.nlevels = c->g.nlevels; fa.F = c->g.F;
-    for (int l = 0; l < 16; ++l) fa.sf[l] = l < c->g.nlevels ? c->scale[l] : 0.0f;
-    fa.qx = (float*)(p + o_qx); fa.qy = (float*)(p + o_qy); fa.qr = (float*)(p + o_qr); fa.qmin = (int*)(p + o_qmin); fa.qmax = (int*)(p + o_qmax);
-    fa.level = (int*)(p + o_lvl);
+    const CmsFuseArgs fa = fuse_project_args(c, nmp, th, p + o_pose, p + o_job, skip ? p + o_skip : nullptr, job_set0 ? p + o_src : nullptr, p + o_pos, p + o_nrm, p + o_min,
+                                             p + o_max, p + o_qx, p + o_qy, p + o_qr, p + o_qmin, p + o_qmax, p + o_lvl);
     hipLaunchKernelGGL(k_fuse_project, dim3((nmp + 255) / 256), dim3(256), 0, s, fa);
-    // window query against the grids of the store's slots
-    CmsAreaArgs a;
-    a.tmp = nullptr;
-    a.kp = (const CmsKeyPoint*)st->d_kp; a.sorted_idx = st->d_sorted; a.cell_start = st->d_cell_start;
-    a.qx = fa.qx; a.qy = fa.qy; a.qr = fa.qr; a.qmin = fa.qmin; a.qmax = fa.qmax;
-    a.q_frame = (const int*)(p + o_slot); a.kp_cap = st->maxf;
-    a.nq = nmp; a.F = c->g.F; a.inv = (float)(3 * CMS_AREA_G) / (float)c->g.W;
-    a.cnt = (int*)(p + o_cnt); a.off = (const int*)(p + o_off); a.idx = (int*)(p + o_idx); a.cap = cap; a.idx_base = 0;
-    {
-      const int nblk = (nmp + 1023) / 1024, qgrid = (nmp * CMS_AREA_QL + 255) / 256;
-      rc = cms_area_bsum_reserve(c, nblk);
-      if (rc) return rc;
-      hipLaunchKernelGGL(k_area_query, dim3(qgrid), dim3(256), 0, s, a, 0);
-      hipLaunchKernelGGL(k_area_blocksum, dim3(nblk), dim3(1024), 0, s, (const int*)(p + o_cnt), nmp, c->d_area_bsum);
-      hipLaunchKernelGGL(k_area_scan, dim3(nblk), dim3(1024), 0, s, (const int*)(p + o_cnt), nmp, (const int*)c->d_area_bsum, (int*)(p + o_off), (int*)(p + o_tot));
-      hipLaunchKernelGGL(k_area_query, dim3(qgrid), dim3(256), 0, s, a, 1);      // (writes at most `cap` candidates: a list that does not fit is noticed below)
-    }
+    // window query against the grids of the store's slots (no first-hits buffer: 32 bytes x a quarter of a million queries)
+    CmsAreaArgs a = cms_area_args(st->d_kp, st->d_sorted, st->d_cell_start, st->maxf, c->g.F, cms_grid_inv(c));
+    cms_area_queries(a, nmp, p + o_slot, fa.qx, fa.qy, fa.qr, fa.qmin, fa.qmax, p + o_cnt, p + o_off, p + o_idx, cap, 0);
+    rc = cms_area_launch(c, s, a, p + o_tot, false);
+    if (rc) return rc;
     // The scan is enqueued right behind the windows: the total is looked at together with the results (ONE synchronisation per call; the fill pass
-    // never writes beyond `cap`, and a call whose lists did not fit is simply repeated with room for them)
-    CmsFuseScanArgs sa;
-    sa.cap = cap; sa.src = src_dev; sa.row_slot = (const int*)(p + o_slot); sa.maxf = st->maxf;
-    sa.n = nmp; sa.qx = fa.qx; sa.qy = fa.qy; sa.level = fa.level; sa.mp_desc = (const uint4*)(p + o_desc);
-    sa.cand_off = (const int*)(p + o_off); sa.cand_idx = (const int*)(p + o_idx); sa.kp = (const CmsKeyPoint*)st->d_kp; sa.t_desc = (const uint4*)st->d_desc;
-    for (int l = 0; l < 16; ++l) sa.inv_sigma2[l] = l < c->g.nlevels ? c->inv_sigma2[l] : 0.0f;
-    // result arrays in pinned (device-visible) host memory: the kernels store there themselves -- copies queued behind kernels of the same stream are
+    // never writes beyond `cap`, and a call whose lists did not fit is simply repeated with room for them).
+    // Result arrays in pinned (device-visible) host memory: the kernels store there themselves -- copies queued behind kernels of the same stream are
     // blit kernels of the runtime, two more dependent launches that wait for a slot on a busy chip
-    sa.best_idx = direct ? best_idx : (int*)(p + o_bi); sa.best_dist = direct ? best_dist : (int*)(p + o_bd);
+    const CmsFuseScanArgs sa = fuse_scan_args(c, fa, p + o_desc, p + o_off, p + o_idx, st->d_kp, st->d_desc, direct ? best_idx : (int*)(p + o_bi),
+                                              direct ? best_dist : (int*)(p + o_bd), cap, p + o_slot, st->maxf);
     hipLaunchKernelGGL(k_fuse_scan, dim3((nmp * 8 + 255) / 256), dim3(256), 0, s, sa);      // (stores the key-point index inside the job's key frame: row - slot x maxf)
     HIPCHK(hipGetLastError());
-    int tot = 0;
     HIPCHK(hipMemcpyAsync(&tot, p + o_tot, sizeof(int), hipMemcpyDeviceToHost, s));
     if (!direct) {
       HIPCHK(hipMemcpyAsync(best_idx, p + o_bi, n4, hipMemcpyDeviceToHost, s));
       HIPCHK(hipMemcpyAsync(best_dist, p + o_bd, n4, hipMemcpyDeviceToHost, s));
     }
     HIPCHK(hipStreamSynchronize(s));
-    if (tot > cap) { cap = tot + 64; continue; }
     return CMS_OK;
-  }
-  return cms_fail(CMS_ERR_OVERFLOW, "cms_kfstore_fuse_search: candidate lists kept growing");
+  });
 }
 extern "C" int cms_kfstore_fuse_search(cms_kfstore* st, int njobs, const int* job_slot, const int* mp_off, const uint8_t* skip, const float* pos,
                                        const float* normal, const float* min_dist, const float* max_dist, const uint8_t* mp_desc, float th,

@@ -5,9 +5,9 @@
 //                  unique, n <= 16383: the 3 x nFeatures extractor of the initialisation included) lists the indices cell-major with
 //                  ascending index inside a cell -- the order the
 //                  reference's per-cell vectors have -- and a start offset is written for each of the 5 x 50 x 50 cells.
-//   k_area_query   one thread per query: cms_area_rects() (the reference's 41 unfolding cases as a table, cms_area_table.h)
-//                  yields up to three cell rectangles; the thread walks them exactly like AddCells (ix outer, iy inner, level
-//                  and canvas-distance test) and either counts its candidates (pass 0) or writes them (pass 1).
+//   k_area_query   eight lanes per query: cms_area_rects() (the reference's 41 unfolding cases as a table, cms_area_table.h)
+//                  yields up to three cell rectangles; the lanes take their cell columns in turn and keep AddCells' order (ix outer,
+//                  iy inner, level and canvas-distance test); the query's candidates are counted (pass 0) or written (pass 1).
 //   k_area_scan    exclusive scan of the counts -> CSR offsets.
 // The CSR lists feed k_hamming_best2 directly; candidate order (which decides Hamming ties) equals the reference's.
 #include <hip/hip_runtime.h>

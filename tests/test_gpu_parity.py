@@ -797,6 +797,40 @@ def test_features_in_area_on_extracted_frames_feeds_the_matcher():
     ctx.close()
 
 
+# First-guess candidate capacities of the entries that query windows; an entry whose windows hold more repeats its launches ONCE with the
+# exact size.  Defined by the first argument of each cms_retry_capacity(...) call: `64 * nmp + 1024` in cms_search_local_points,
+# cms_search_by_projection (cubemapslam_amd/csrc/cms_api_track.hip), cms_fuse_search and kfstore_fuse_core (cms_api_tri.hip), and
+# `128 * nq + 4096` in cms_search_for_initialization (cms_api_track.hip).
+def _first_cap(n):
+    return 64 * n + 1024
+
+
+def _first_cap_init(nq):
+    return 128 * nq + 4096
+
+
+def _oracle_window_total(ocam, kx, ky, ko, qx, qy, qr, lo, hi):
+    """candidates of all windows together, by the oracle alone (orc.features_in_area on the oracle's projections and the reference's radii)"""
+    f32 = lambda a: np.ascontiguousarray(a, np.float32); i32 = lambda a: np.ascontiguousarray(a, np.int32)
+    _, idx = orc.features_in_area(ocam, kx, ky, ko, f32(qx), f32(qy), f32(qr), i32(lo), i32(hi), cap=len(qx) * len(kx) + 16)
+    return len(idx)
+
+
+def _local_points_window_total(ocam, kx, ky, ko, sf, fr, th):
+    """ORBMatcher::SearchByProjection(F, vpMapPoints, th): RadiusByViewingCos x th x scale of the predicted level, levels [l - 1, l]"""
+    v = fr["in_view"] > 0
+    r = np.where(fr["view_cos"].astype(np.float64) > 0.998, np.float32(2.5), np.float32(4.0)).astype(np.float32) * np.float32(th) * sf[fr["level"]]
+    return _oracle_window_total(ocam, kx, ky, ko, fr["proj_x"][v], fr["proj_y"][v], r[v], fr["level"][v] - 1, fr["level"][v])
+
+
+def _fuse_window_total(ocam, kx, ky, ko, sf, pose15, skip, pr, th):
+    """ORBMatcher::Fuse: radius th x scale of the predicted level around the projection, every level"""
+    fr = orc.is_in_frustum(ocam, pose15, pr["pos"], pr["normal"], pr["min_dist"], pr["max_dist"])
+    v = (fr["in_view"] > 0) & (np.asarray(skip) == 0)
+    r = np.float32(th) * sf[fr["level"]]
+    return _oracle_window_total(ocam, kx, ky, ko, fr["proj_x"][v], fr["proj_y"][v], r[v], np.full(v.sum(), -1), np.full(v.sum(), -1))
+
+
 def _local_map_case(F, n, seed, order):
     import test_area_emu as te
     kx, ky, ko = te._keypoints(F, n, seed)
@@ -820,6 +854,9 @@ def test_search_local_points_matches_oracle():
         ctx.area_set_keypoints(0, kps[:5]); ctx.area_set_descriptors(0, kd[:5])
         ctx.area_grid(2)
         fr = orc.is_in_frustum(ocam, pr["pose15"], pr["pos"], pr["normal"], pr["min_dist"], pr["max_dist"])
+        if th == 14.0:      # the case that is there for the second attempt really needs one
+            total = _local_points_window_total(ocam, kx, ky, ko, pr["scale_factors"], fr, th)
+            assert total > _first_cap(len(pr["pos"])) + 10000, (total, _first_cap(len(pr["pos"])))
         taken = np.full(len(kx), -1, np.int32); taken[::9] = 10**6
         want_kp = taken.copy()
         want, nm = orc.search_local_points(ocam, kx, ky, ko, kd, pr["scale_factors"], fr, pr["desc"], want_kp, th=th)
@@ -1404,6 +1441,113 @@ def test_kfstore_fuse_search_matches_oracle():
     with pytest.raises(api.CmsError):
         store.fuse_search([(0, jobs[0][1])])                    # empty slot
     store.close(); ctx.close()
+
+
+def test_window_entries_repeat_with_exact_capacity():
+    """The entries that query windows guess 64 candidates per window (128 for the initialisation) and repeat their launches once with the exact
+    size when the device counted more.  Here every entry gets windows that cover a face of a dense F = 150 frame, so the SECOND attempt is the one
+    that returns -- asserted on the CPU, by the oracle's own window lists -- and its results equal the oracle's like the first attempt's do in the
+    entries' own tests: matches, best key points and distances, key-point ownership, vbPrevMatched."""
+    import test_area_emu as te
+    import test_oracle_track as tot
+    F, N, TH = 150, 300, 60.0
+    camd = synth.camera("lafida", F)
+    ocam = orc.make_camera(camd)
+    ctx = api.Context(camd, nfeatures=2000, max_batch=2)
+
+    def frame(seed):
+        kx, ky, ko = te._keypoints(F, 1900, seed)
+        kd = synth.descriptors(len(kx), seed + 1)
+        ka = np.random.default_rng(seed + 2).uniform(0, 360, len(kx)).astype(np.float32)
+        kps = np.zeros(len(kx), api.KP_DTYPE); kps["x"] = kx; kps["y"] = ky; kps["octave"] = ko; kps["angle"] = ka
+        return kx, ky, ko, ka, kd, kps
+
+    def set_frames(kps, kd):      # the frame under test in slot 1, a tiny one in slot 0
+        ctx.area_set_keypoints(1, kps); ctx.area_set_descriptors(1, kd)
+        ctx.area_set_keypoints(0, kps[:3]); ctx.area_set_descriptors(0, kd[:3])
+        ctx.area_grid(2)
+
+    # ---- ORBMatcher::SearchByProjection(CurrentFrame, LastFrame, th): radius th x scale of the last octave, levels [o - 1, o + 1]
+    kx, ky, ko, ka, kd, kps = frame(201)
+    set_frames(kps, kd)
+    pm = synth.motion_model_problem(F, kx, ky, ko, ka, kd, seed=204)
+    pm = {k: (v[:N] if k in ("valid", "Xw", "octave", "angle", "desc") else v) for k, v in pm.items()}
+    sf = pm["scale_factors"]
+    R, t = pm["pose12"][:9].reshape(3, 3), pm["pose12"][9:]
+    Ow = (-(R.T @ t)).astype(np.float32)
+    toward = pm["Xw"] - Ow; toward /= np.linalg.norm(toward, axis=1, keepdims=True)      # seen head-on, any distance: in view = it projects into the cubemap
+    fr = orc.is_in_frustum(ocam, np.concatenate([pm["pose12"], Ow]), pm["Xw"], toward.astype(np.float32), np.zeros(N, np.float32), np.full(N, 1e9, np.float32))
+    v = (fr["in_view"] > 0) & (pm["valid"] > 0)
+    total = _oracle_window_total(ocam, kx, ky, ko, fr["proj_x"][v], fr["proj_y"][v], (np.float32(TH) * sf[pm["octave"]])[v], pm["octave"][v] - 1, pm["octave"][v] + 1)
+    assert total > 2 * _first_cap(N), ("search_by_projection", total, _first_cap(N))
+    for check in (True, False):
+        taken = np.full(len(kx), -1, np.int32); taken[::8] = 10**6
+        want_kp = taken.copy(); got_kp = taken.copy()
+        want, nm = orc.search_by_projection_frames(ocam, pm["pose12"][:9], pm["pose12"][9:], kx, ky, ko, ka, kd, sf, pm["valid"], pm["Xw"], pm["octave"], pm["angle"],
+                                                   pm["desc"], want_kp, th=TH, check_ori=check)
+        got, gn = ctx.search_by_projection(1, pm["pose12"], pm["valid"], pm["Xw"], pm["octave"], pm["angle"], pm["desc"], got_kp, th=TH, check_ori=check)
+        assert np.array_equal(got, want) and gn == nm, ("search_by_projection", check, int((got != want).sum()), gn, nm)
+        assert np.array_equal(got_kp, want_kp) and nm > 50
+
+    # ---- search half of ORBMatcher::Fuse on the same frame
+    pr = synth.local_map_problem(F, kx, ky, ko, kd, seed=205)
+    pr = {k: (v[:N] if k in ("pos", "normal", "min_dist", "max_dist", "desc") else v) for k, v in pr.items()}
+    inv_s2 = (np.float32(1.0) / (sf * sf)).astype(np.float32)
+    skip = (np.arange(N) % 13 == 0).astype(np.uint8)
+    total = _fuse_window_total(ocam, kx, ky, ko, sf, pr["pose15"], skip, pr, TH)
+    assert total > 2 * _first_cap(N), ("fuse_search", total, _first_cap(N))
+    kf = dict(x=kx, y=ky, octave=ko, angle=np.zeros(len(kx), np.float32), desc=kd, mp=np.full(len(kx), -1, np.int32),
+              R=pr["pose15"][:9], t=pr["pose15"][9:12], Ow=pr["pose15"][12:], node_id=np.zeros(0, np.int32), node_off=np.zeros(1, np.int32),
+              node_feat=np.zeros(0, np.int32), median_depth=1.0, rays=np.zeros((len(kx), 3), np.float32))
+    K, _keep = orc.make_keyframe(ocam, kf)
+    wi, wd = orc.fuse_search(ocam, K, skip, pr["pos"], pr["normal"], pr["min_dist"], pr["max_dist"], pr["desc"], TH, sf, inv_s2)
+    gi, gd = api.fuse_search(ctx, 1, pr["pose15"], skip, pr["pos"], pr["normal"], pr["min_dist"], pr["max_dist"], pr["desc"], TH)
+    assert np.array_equal(gi, wi) and np.array_equal(gd, wd), ("fuse_search", int((gi != wi).sum()))
+    assert (wi >= 0).sum() > 100 and (wi[skip > 0] == -1).all()
+
+    # ---- the same search on resident key frames: two slots, three jobs (slot 1 twice), per job and per set
+    store = api.KeyframeStore(ctx, max_keyframes=3, max_features=2048, max_nodes=16)
+    kfs, prs, oks = [kf], [pr], [(K, _keep)]
+    kx2, ky2, ko2, _, kd2, _ = frame(211)
+    pr2 = synth.local_map_problem(F, kx2, ky2, ko2, kd2, seed=215)
+    pr2 = {k: (v[:N] if k in ("pos", "normal", "min_dist", "max_dist", "desc") else v) for k, v in pr2.items()}
+    kfs.append(dict(kf, x=kx2, y=ky2, octave=ko2, desc=kd2, R=pr2["pose15"][:9], t=pr2["pose15"][9:12], Ow=pr2["pose15"][12:]))
+    prs.append(pr2); oks.append(orc.make_keyframe(ocam, kfs[1]))
+    for s in range(2):
+        Ks, _k = api.make_keyframe(kfs[s])
+        store.put(s + 1, Ks)                                    # slots 1 and 2 (slot 0 stays empty)
+    skips = [skip, (np.arange(N) % 11 == 0).astype(np.uint8)]
+    jobs, want, total = [], [], 0
+    for slot_i, src in ((0, 0), (1, 1), (0, 1)):                # the last job searches key frame 0 with the map points made for key frame 1
+        q = prs[src]
+        jobs.append((slot_i + 1, dict(skip=skips[src], pos=q["pos"], normal=q["normal"], min_dist=q["min_dist"], max_dist=q["max_dist"], desc=q["desc"])))
+        want.append(orc.fuse_search(ocam, oks[slot_i][0], skips[src], q["pos"], q["normal"], q["min_dist"], q["max_dist"], q["desc"], TH, sf, inv_s2))
+        total += _fuse_window_total(ocam, kfs[slot_i]["x"], kfs[slot_i]["y"], kfs[slot_i]["octave"], sf, prs[slot_i]["pose15"], skips[src], q, TH)
+    assert total > 2 * _first_cap(3 * N), ("KeyframeStore.fuse_search", total, _first_cap(3 * N))
+    got = store.fuse_search(jobs, th=TH)
+    got_s = store.fuse_search_sets([jobs[0][1], jobs[1][1]], [(1, 0, skips[0]), (2, 1, skips[1]), (1, 1, skips[1])], th=TH)
+    for j in range(3):
+        assert np.array_equal(got[j][0], want[j][0]) and np.array_equal(got[j][1], want[j][1]), ("KeyframeStore.fuse_search", j)
+        assert np.array_equal(got_s[j][0], want[j][0]) and np.array_equal(got_s[j][1], want[j][1]), ("KeyframeStore.fuse_search_sets", j)
+    assert all((want[j][0] >= 0).sum() > 50 for j in range(2))      # (the third job's map points were made for another key frame)
+    store.close()
+
+    # ---- ORBMatcher::SearchForInitialization: every key point at level 0 (only those are searched, and only among level 0), square windows
+    k1, d1, k2, d2 = tot._init_pair(F, 1900, 221)
+    k1 = k1[:400].copy(); d1 = d1[:400].copy()
+    k2 = k2[:1900].copy(); d2 = d2[:1900].copy()                # (F2 has the moved key points, their near-duplicates and strangers: more than a frame slot holds)
+    k1["octave"] = 0; k2["octave"] = 0
+    set_frames(k2, d2)
+    window, nq = 150, len(k1)
+    total = _oracle_window_total(ocam, k2["x"], k2["y"], k2["octave"], k1["x"], k1["y"], np.full(nq, window), np.zeros(nq), np.zeros(nq))
+    assert total > 2 * _first_cap_init(nq), ("search_for_initialization", total, _first_cap_init(nq))
+    for check in (True, False):
+        prev_w = np.stack([k1["x"], k1["y"]], 1).astype(np.float32); prev_g = prev_w.copy()
+        want_m, want_n = orc.search_for_initialization(ocam, k1, d1, k2, d2, prev_w, window, 0.9, check)
+        got_m, got_n = ctx.search_for_initialization(1, k1, d1, prev_g, window, 0.9, check)
+        assert got_n == want_n and np.array_equal(got_m, want_m), ("search_for_initialization", check, got_n, want_n, int((got_m != want_m).sum()))
+        assert np.array_equal(prev_g.view(np.uint32), prev_w.view(np.uint32)) and want_n > 50
+    ctx.close()
 
 
 @pytest.mark.parametrize("knob", ["CMS_BA_NO_FUSED_LIN", "CMS_BA_DETERMINISTIC", "CMS_BA_NO_PERMUTE", "CMS_BA_NO_RUNS", "CMS_BA_RUNS_AS_EDGES",
