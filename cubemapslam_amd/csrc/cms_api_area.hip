@@ -1,6 +1,6 @@
 // cms_api_area.hip -- host side of the frame grid + window query (Frame::AssignFeaturesToGrid / GetFeaturesInArea), included by
 // cms_lib.hip after cms_api_frames.hip (uses cms_ctx, cms_fail, HIPCHK, cms_scratch and the helpers of cms_api_util.h).  cms_area_args /
-// cms_area_queries / cms_area_launch are the only place that fills and launches the window query's four kernels: the frame entries below and
+// cms_area_queries / cms_area_launch are the only place that fills and launches the window query's two kernels: the frame entries below and
 // the key-frame store's Fuse (cms_api_tri.hip) go through them.
 #include <vector>
 
@@ -21,7 +21,9 @@ static int cms_area_reserve(cms_ctx* c) {
   return CMS_OK;
 }
 
-// hit buffer of the query kernel's first pass (CMS_AREA_TMP entries per query)
+// per-context buffers of the window query: the first hits of every query (CMS_AREA_TMP entries each) and one partial sum of counts per
+// search workgroup.  Both are written in full by launch 1 before launch 2 reads them and belong to the context whose stream the call runs
+// on (every caller passes c->stream), so calls on one context are ordered and nothing has to be cleared between them.
 static int cms_area_tmp_reserve(cms_ctx* c, int nq) {
   if ((size_t)nq <= c->area_tmp_cap) return CMS_OK;
   if (c->d_area_tmp) hipFree(c->d_area_tmp);
@@ -31,12 +33,13 @@ static int cms_area_tmp_reserve(cms_ctx* c, int nq) {
   c->area_tmp_cap = cap;
   return CMS_OK;
 }
-static int cms_area_bsum_reserve(cms_ctx* c, int nblk) {
-  if (nblk <= c->area_bsum_cap) return CMS_OK;
-  if (c->d_area_bsum) hipFree(c->d_area_bsum);
-  c->d_area_bsum = nullptr; c->area_bsum_cap = 0;
-  HIPCHK(hipMalloc((void**)&c->d_area_bsum, (size_t)(nblk + 64) * sizeof(int)));
-  c->area_bsum_cap = nblk + 64;
+static int cms_area_psum_reserve(cms_ctx* c, int nparts) {
+  if (nparts <= c->area_psum_cap) return CMS_OK;
+  if (c->d_area_psum) hipFree(c->d_area_psum);
+  c->d_area_psum = nullptr; c->area_psum_cap = 0;
+  const int cap = nparts + nparts / 4 + 64;
+  HIPCHK(hipMalloc((void**)&c->d_area_psum, (size_t)cap * sizeof(int)));
+  c->area_psum_cap = cap;
   return CMS_OK;
 }
 
@@ -56,23 +59,19 @@ static void cms_area_queries(CmsAreaArgs& a, int nq, const void* q_frame, const 
                              void* cnt, void* off, void* idx, int cap, int idx_base) {
   a.nq = nq; a.q_frame = (const int*)q_frame;
   a.qx = (const float*)qx; a.qy = (const float*)qy; a.qr = (const float*)qr; a.qmin = (const int*)qmin; a.qmax = (const int*)qmax;
-  a.cnt = (int*)cnt; a.off = (const int*)off; a.idx = (int*)idx; a.cap = cap; a.idx_base = idx_base;
+  a.cnt = (int*)cnt; a.off = (int*)off; a.idx = (int*)idx; a.cap = cap; a.idx_base = idx_base;
 }
-// count -> block sums -> scan (offsets, *d_total) -> fill.  keep_first_hits: the count pass leaves every query's first CMS_AREA_TMP hits in
-// the context's buffer and the fill pass copies them (32 bytes per query: not for the quarter of a million queries of a store-wide Fuse).
-static int cms_area_launch(cms_ctx* c, hipStream_t s, CmsAreaArgs a, void* d_total, bool keep_first_hits) {
-  const int nq = a.nq, nblk = (nq + 1023) / 1024, qgrid = (nq * CMS_AREA_QL + 255) / 256;
-  int rc = cms_area_bsum_reserve(c, nblk);
+// Two launches, ordered by the stream: the search (counts, first CMS_AREA_TMP hits of every query, one sum of counts per workgroup), then
+// offsets + *d_total + lists per tile of queries (copied first hits; only a query with more candidates than that is searched again).
+static int cms_area_launch(cms_ctx* c, hipStream_t s, CmsAreaArgs a, void* d_total) {
+  const int nq = a.nq, qgrid = cms_area_search_grid(nq);
+  int rc = cms_area_psum_reserve(c, qgrid);
   if (rc) return rc;
-  if (keep_first_hits) {
-    rc = cms_area_tmp_reserve(c, nq);
-    if (rc) return rc;
-    a.tmp = c->d_area_tmp;
-  }
-  hipLaunchKernelGGL(k_area_query, dim3(qgrid), dim3(256), 0, s, a, 0);
-  hipLaunchKernelGGL(k_area_blocksum, dim3(nblk), dim3(1024), 0, s, (const int*)a.cnt, nq, c->d_area_bsum);
-  hipLaunchKernelGGL(k_area_scan, dim3(nblk), dim3(1024), 0, s, (const int*)a.cnt, nq, (const int*)c->d_area_bsum, const_cast<int*>(a.off), (int*)d_total);
-  hipLaunchKernelGGL(k_area_query, dim3(qgrid), dim3(256), 0, s, a, 1);      // (writes at most a.cap candidates; *d_total > cap tells the caller)
+  rc = cms_area_tmp_reserve(c, nq);
+  if (rc) return rc;
+  a.tmp = c->d_area_tmp; a.psum = c->d_area_psum;
+  hipLaunchKernelGGL(k_area_query, dim3(qgrid), dim3(CMS_AREA_QT), 0, s, a);
+  hipLaunchKernelGGL(k_area_lists, dim3(cms_area_tile_grid(nq)), dim3(CMS_AREA_LT), 0, s, a, (int*)d_total);      // (writes at most a.cap candidates; *d_total > cap tells the caller)
   HIPCHK(hipGetLastError());
   return CMS_OK;
 }
@@ -106,7 +105,7 @@ extern "C" int cms_features_in_area_device(cms_ctx* c, int b, int nq, const void
   HIPCHK(hipSetDevice(c->device));
   CmsAreaArgs a = cms_area_args_frames(c, b);
   cms_area_queries(a, nq, nullptr, d_qx, d_qy, d_qr, d_qmin, d_qmax, d_cnt_scratch, d_cand_off, d_cand_idx, cap, idx_base);
-  return cms_area_launch(c, c->stream, a, d_total, true);
+  return cms_area_launch(c, c->stream, a, d_total);
 }
 
 // every query names the frame of the batch it searches (d_qframe); candidate indices are rows of the batch (frame * kp_cap + i)
@@ -118,7 +117,7 @@ extern "C" int cms_features_in_area_batch_device(cms_ctx* c, int nq, const void*
   HIPCHK(hipSetDevice(c->device));
   CmsAreaArgs a = cms_area_args_frames(c, 0);
   cms_area_queries(a, nq, d_qframe, d_qx, d_qy, d_qr, d_qmin, d_qmax, d_cnt_scratch, d_cand_off, d_cand_idx, cap, 0);
-  return cms_area_launch(c, c->stream, a, d_total, true);
+  return cms_area_launch(c, c->stream, a, d_total);
 }
 
 extern "C" int cms_features_in_area(cms_ctx* c, int b, int nq, const float* qx, const float* qy, const float* qr, const int* qmin, const int* qmax,

@@ -943,12 +943,12 @@ static int kfstore_fuse_core(cms_kfstore* st, int njobs, const int* job_slot, co
     const CmsFuseArgs fa = fuse_project_args(c, nmp, th, p + o_pose, p + o_job, skip ? p + o_skip : nullptr, job_set0 ? p + o_src : nullptr, p + o_pos, p + o_nrm, p + o_min,
                                              p + o_max, p + o_qx, p + o_qy, p + o_qr, p + o_qmin, p + o_qmax, p + o_lvl);
     hipLaunchKernelGGL(k_fuse_project, dim3((nmp + 255) / 256), dim3(256), 0, s, fa);
-    // window query against the grids of the store's slots (no first-hits buffer: 32 bytes x a quarter of a million queries)
+    // window query against the grids of the store's slots (the context's first-hits buffer: this call runs on the context's stream)
     CmsAreaArgs a = cms_area_args(st->d_kp, st->d_sorted, st->d_cell_start, st->maxf, c->g.F, cms_grid_inv(c));
     cms_area_queries(a, nmp, p + o_slot, fa.qx, fa.qy, fa.qr, fa.qmin, fa.qmax, p + o_cnt, p + o_off, p + o_idx, cap, 0);
-    rc = cms_area_launch(c, s, a, p + o_tot, false);
+    rc = cms_area_launch(c, s, a, p + o_tot);
     if (rc) return rc;
-    // The scan is enqueued right behind the windows: the total is looked at together with the results (ONE synchronisation per call; the fill pass
+    // The scan is enqueued right behind the windows: the total is looked at together with the results (ONE synchronisation per call; the list kernel
     // never writes beyond `cap`, and a call whose lists did not fit is simply repeated with room for them).
     // Result arrays in pinned (device-visible) host memory: the kernels store there themselves -- copies queued behind kernels of the same stream are
     // blit kernels of the runtime, two more dependent launches that wait for a slot on a busy chip

@@ -34,7 +34,7 @@ static int cms_lds_ceiling_once(const void* kernel, int bytes, int device, bool 
 // The window-query entries guess a candidate capacity (64 per window) and repeat ONCE with the exact size when the device counted more.
 // attempt(cap, total) is one whole attempt: reserve (cms_scratch / cms_hstage may reallocate: block pointers are taken after that), stage the
 // caller's arrays (in/out ones afresh), launch, synchronise, leave the device's candidate total in `total`, and deliver the results only if
-// total <= cap (the fill pass never writes beyond cap, and the searches do nothing on lists that were cut).
+// total <= cap (the list kernel never writes beyond cap, and the searches do nothing on lists that were cut).
 template <class Attempt>
 static int cms_retry_capacity(int cap, const char* entry, Attempt&& attempt) {
   for (int i = 0; i < 2; ++i) {

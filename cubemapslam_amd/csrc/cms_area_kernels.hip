@@ -7,13 +7,18 @@
 //                  reference's per-cell vectors have -- and a start offset is written for each of the 5 x 50 x 50 cells.
 //   k_area_query   eight lanes per query: cms_area_rects() (the reference's 41 unfolding cases as a table, cms_area_table.h)
 //                  yields up to three cell rectangles; the lanes take their cell columns in turn and keep AddCells' order (ix outer,
-//                  iy inner, level and canvas-distance test); the query's candidates are counted (pass 0) or written (pass 1).
-//   k_area_scan    exclusive scan of the counts -> CSR offsets.
+//                  iy inner, level and canvas-distance test).  The ONLY search of nearly every query: it leaves the query's count, its
+//                  first CMS_AREA_TMP candidates (final values, in output order) and one sum of counts per workgroup.
+//   k_area_lists   one workgroup per tile of CMS_AREA_TILE queries: the tile's first offset from the partial sums in front of it, a
+//                  scan of the tile's counts in LDS -> CSR offsets and total, then the tile's lists: copied from the first-hits buffer,
+//                  or, for the rare query with more than CMS_AREA_TMP candidates, searched again (cms_area_search in fill mode).
+//                  Index arithmetic: cms_area_offsets.h.  Two launches per query call, ordered by the stream alone.
 // The CSR lists feed k_hamming_best2 directly; candidate order (which decides Hamming ties) equals the reference's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "cms_types.h"
 #include "cms_area_table.h"
+#include "cms_area_offsets.h"
 
 #define CMS_AREA_CELLS (5 * CMS_AREA_G * CMS_AREA_G)
 #define CMS_AREA_MAXKP 16383
@@ -76,39 +81,33 @@ struct CmsAreaArgs {
   const int* q_frame;           // optional: frame of the batch a query addresses (nullptr: all queries address `kp`'s frame)
   int kp_cap;                   // frame stride of kp / sorted_idx (cell_start: CMS_AREA_CELLS + 1) when q_frame is given
   int nq, F; float inv;
-  int* cnt;                     // pass 0: candidates per query
-  const int* off;               // pass 1: CSR offsets
+  int* cnt;                     // candidates per query (written for every query; 0 for a "no window" query)
+  int* off;                     // CSR offsets (nq + 1)
   int* idx; int cap; int idx_base;
-  int* tmp;                     // optional: nq x CMS_AREA_TMP -- pass 0 leaves the first hits of every query here (final values, in order) and pass 1
-                                // only copies them for the queries that have no more than that (nearly all: ~2 candidates per window on average)
+  int* tmp;                     // nq x CMS_AREA_TMP: the search leaves the first hits of every query here (final values, in order); the list
+                                // kernel only copies them for the queries that have no more than that (nearly all: ~2 candidates per window)
+  int* psum;                    // one sum of counts per search workgroup (plain stores: nothing to clear between calls)
 };
 #define CMS_AREA_TMP 8
 
-// Eight lanes per query (eight queries per wavefront): the lanes of a group take the cell columns ix of a rectangle in turn, so the
-// dependent loads of a query (cell offsets -> index list -> key point) run eight wide; a group-wide prefix sum of the per-column
-// hit counts keeps the output in AddCells' order (ix outer, iy inner, index order inside a cell).
-#define CMS_AREA_QL 8
-extern "C" __global__ void __launch_bounds__(256) k_area_query(CmsAreaArgs a, int pass) {
-  const int gl = threadIdx.x & (CMS_AREA_QL - 1);
-  const int q = (blockIdx.x * blockDim.x + threadIdx.x) / CMS_AREA_QL;
-  const int qq = q < a.nq ? q : 0;
+__device__ __forceinline__ int cms_area_pick(int k, int v0, int v1, int v2) { return k == 0 ? v0 : (k == 1 ? v1 : v2); }      // (values, not addresses)
+
+// The search of one query by the eight lanes `gl` = 0..7 of its group (eight queries per wavefront): the lanes take the cell columns
+// ix of a rectangle in turn, so the dependent loads of a query (cell offsets -> index list -> key point) run eight wide; a group-wide
+// prefix sum of the per-column hit counts keeps the output in AddCells' order (ix outer, iy inner, index order inside a cell).
+// FILL = false: the first CMS_AREA_TMP hits go to a.tmp.  FILL = true: all hits go to a.idx[base ..], in front of a.cap only.
+// Returns the number of hits (the same in all lanes of the group; 0 for !in and for r < 0).  ALL 64 lanes of a wavefront call it
+// together (loop bounds are made wavefront-uniform by shuffles); idle groups pass in = false.
+template <bool FILL>
+__device__ __forceinline__ int cms_area_search(const CmsAreaArgs& a, int qq, bool in, int gl, int base) {
   const float x = a.qx[qq], y = a.qy[qq], r = a.qr[qq];
-  const bool live = q < a.nq && !(r < 0.0f);            // r < 0: "no window" (a map point outside the frustum), empty list
+  const bool live = in && !(r < 0.0f);                    // r < 0: "no window" (a map point outside the frustum), empty list
   const int minLevel = a.qmin[qq], maxLevel = a.qmax[qq];
   const bool check = (minLevel > 0) || (maxLevel >= 0);
-  CmsAreaRectI rc[3];
-  const int base = (pass && live) ? a.off[qq] : 0;
-  bool copied = false;
-  if (pass && a.tmp && live) {                             // the search of pass 0 kept this query's hits: copy, no second search
-    const int c = a.cnt[qq];
-    if (c <= CMS_AREA_TMP) {
-      if (gl < c && base + gl < a.cap) a.idx[base + gl] = a.tmp[(size_t)qq * CMS_AREA_TMP + gl];
-      copied = true;
-    }
-  }
-  const int nr = (live && !copied) ? cms_area_rects(x, y, r, a.F, a.inv, rc) : 0;
+  CmsAreaRectI rc[3] = {};                                 // written and read with constant indices only: registers, not scratch
+  const int nr = live ? cms_area_rects(x, y, r, a.F, a.inv, rc) : 0;
   int n = 0;                                               // hits of the whole query so far (same in all lanes of the group)
-  int* tmpq = (!pass && a.tmp) ? a.tmp + (size_t)qq * CMS_AREA_TMP : nullptr;
+  int* tmpq = a.tmp + (size_t)qq * CMS_AREA_TMP;
   const int fr = a.q_frame ? a.q_frame[qq] : 0;
   const CmsKeyPoint* kp = a.kp + (size_t)fr * a.kp_cap;
   const uint16_t* sorted_idx = a.sorted_idx + (size_t)fr * a.kp_cap;
@@ -117,9 +116,9 @@ extern "C" __global__ void __launch_bounds__(256) k_area_query(CmsAreaArgs a, in
   // the groups of a wavefront walk different rectangle shapes: loop bounds are made group-uniform via shuffles inside the group
   for (int k = 0; k < 3; ++k) {
     const bool has = k < nr;
-    const int x0 = has ? max(0, rc[k].x0) : 0, x1 = has ? min(CMS_AREA_G - 1, rc[k].x1) : -1;
-    const int y0 = has ? max(0, rc[k].y0) : 0, y1 = has ? min(CMS_AREA_G - 1, rc[k].y1) : -1;        // AddCells' clamp
-    const int face = has ? rc[k].face : 0;
+    const int x0 = has ? max(0, cms_area_pick(k, rc[0].x0, rc[1].x0, rc[2].x0)) : 0, x1 = has ? min(CMS_AREA_G - 1, cms_area_pick(k, rc[0].x1, rc[1].x1, rc[2].x1)) : -1;
+    const int y0 = has ? max(0, cms_area_pick(k, rc[0].y0, rc[1].y0, rc[2].y0)) : 0, y1 = has ? min(CMS_AREA_G - 1, cms_area_pick(k, rc[0].y1, rc[1].y1, rc[2].y1)) : -1;        // AddCells' clamp
+    const int face = has ? cms_area_pick(k, rc[0].face, rc[1].face, rc[2].face) : 0;
     const int ncol = (x1 >= x0 && y1 >= y0) ? x1 - x0 + 1 : 0;
     // every group of the wave iterates max-over-wave column chunks; idle groups just carry zeros through the shuffles
     int maxcol = ncol;
@@ -152,7 +151,7 @@ extern "C" __global__ void __launch_bounds__(256) k_area_query(CmsAreaArgs a, in
 #pragma unroll
       for (int o = 1; o < CMS_AREA_QL; o <<= 1) { const int t = __shfl_up(incl, o, CMS_AREA_QL); if (gl >= o) incl += t; }
       const int tot = __shfl(incl, CMS_AREA_QL - 1, CMS_AREA_QL);
-      if (tmpq && nh > 0) {                                 // pass 0: the first CMS_AREA_TMP hits of the query, already in output order
+      if (!FILL && nh > 0) {                                // the first CMS_AREA_TMP hits of the query, already in output order
         int w = n + incl - nh;
         if (w < CMS_AREA_TMP) {
           if (nh <= 4) {
@@ -170,63 +169,105 @@ extern "C" __global__ void __launch_bounds__(256) k_area_query(CmsAreaArgs a, in
           }
         }
       }
-      if (pass && nh > 0) {
+      if (FILL && nh > 0) {
         int w = base + n + incl - nh;
         if (nh <= 4) {
-          if (w < a.cap) a.idx[w] = idx_base + h0;
-          if (nh > 1 && w + 1 < a.cap) a.idx[w + 1] = idx_base + h1;
-          if (nh > 2 && w + 2 < a.cap) a.idx[w + 2] = idx_base + h2;
-          if (nh > 3 && w + 3 < a.cap) a.idx[w + 3] = idx_base + h3;
+          if (cms_area_fits(w, a.cap)) a.idx[w] = idx_base + h0;
+          if (nh > 1 && cms_area_fits(w + 1, a.cap)) a.idx[w + 1] = idx_base + h1;
+          if (nh > 2 && cms_area_fits(w + 2, a.cap)) a.idx[w + 2] = idx_base + h2;
+          if (nh > 3 && cms_area_fits(w + 3, a.cap)) a.idx[w + 3] = idx_base + h3;
         } else {                                            // crowded column: walk it again instead of a bigger local list
           for (int s = s0; s < s1; ++s) {
             const int j = sorted_idx[s];
             const CmsKeyPoint p = kp[j];
             if (check && (p.octave < minLevel || (maxLevel >= 0 && p.octave > maxLevel))) continue;
-            if (fabsf(p.x - x) < r && fabsf(p.y - y) < r) { if (w < a.cap) a.idx[w] = idx_base + j; ++w; }
+            if (fabsf(p.x - x) < r && fabsf(p.y - y) < r) { if (cms_area_fits(w, a.cap)) a.idx[w] = idx_base + j; ++w; }
           }
         }
       }
       n += tot;
     }
   }
-  if (!pass && q < a.nq && gl == 0) a.cnt[q] = n;             // 0 for a "no window" query
+  return n;
 }
 
-// CSR offsets: off[0] = 0, off[q + 1] = sum cnt[0..q], *total = off[nq].  Two launches: per-1024 block sums, then every block adds
-// the sums of the blocks before it (a few hundred values at most) to its own scan.
-extern "C" __global__ void __launch_bounds__(1024) k_area_blocksum(const int* __restrict__ cnt, int nq, int* __restrict__ bsum) {
-  __shared__ int part[16];
-  const int i = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int v = i < nq ? cnt[i] : 0;
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if (lane == 0) part[wv] = v;
+// Launch 1: count + first hits of every query, and the sum of the workgroup's counts in psum[blockIdx.x].
+extern "C" __global__ void __launch_bounds__(CMS_AREA_QT) k_area_query(CmsAreaArgs a) {
+  __shared__ int part[CMS_AREA_QT / 64];
+  const int gl = threadIdx.x & (CMS_AREA_QL - 1);
+  const int q = (blockIdx.x * CMS_AREA_QT + threadIdx.x) / CMS_AREA_QL;
+  const bool in = q < a.nq;
+  const int n = cms_area_search<false>(a, in ? q : 0, in, gl, 0);
+  if (in && gl == 0) a.cnt[q] = n;                            // 0 for a "no window" query
+  int v = n;                                                  // the same in the 8 lanes of a group: these three steps add the 8 groups
+  for (int o = CMS_AREA_QL; o < 64; o <<= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
   __syncthreads();
-  if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < 16; ++w) t += part[w]; bsum[blockIdx.x] = t; }
+  if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < CMS_AREA_QT / 64; ++w) t += part[w]; a.psum[blockIdx.x] = t; }
 }
-extern "C" __global__ void __launch_bounds__(1024) k_area_scan(const int* __restrict__ cnt, int nq, const int* __restrict__ bsum,
-                                                                int* __restrict__ off, int* __restrict__ total) {
-  __shared__ int part[16];
-  __shared__ int s_before;
+
+// Launch 2: CSR offsets (off[0] = 0, off[q + 1] = sum cnt[0..q], *total = off[nq]) and the lists of one tile of queries.
+extern "C" __global__ void __launch_bounds__(CMS_AREA_LT) k_area_lists(CmsAreaArgs a, int* __restrict__ total) {
+  __shared__ int s_cnt[CMS_AREA_TILE], s_off[CMS_AREA_TILE];
+  __shared__ int part[CMS_AREA_TILE_K * CMS_AREA_LW], pbefore[CMS_AREA_LW];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tile = blockIdx.x, q0 = tile * CMS_AREA_TILE;
+  // the counts in front of the tile: whole partial sums of launch 1
   int before = 0;
-  for (int b = tid; b < (int)blockIdx.x; b += 1024) before += bsum[b];
+  {
+    const int4* p4 = (const int4*)a.psum;
+    const int n4 = cms_area_parts_before(tile) / 4;
+    for (int b = tid; b < n4; b += CMS_AREA_LT) { const int4 v = p4[b]; before += (v.x + v.y) + (v.z + v.w); }
+  }
   for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
-  if (lane == 0) part[wv] = before;
-  __syncthreads();
-  if (tid == 0) { int t = 0; for (int w = 0; w < 16; ++w) t += part[w]; s_before = t; }
-  __syncthreads();
-  const int i = blockIdx.x * 1024 + tid;
-  const int v = i < nq ? cnt[i] : 0;
-  int incl = v;
+  if (lane == 0) pbefore[wv] = before;
+  int c[CMS_AREA_TILE_K], incl[CMS_AREA_TILE_K];
 #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+  for (int k = 0; k < CMS_AREA_TILE_K; ++k) {
+    const int q = q0 + cms_area_tile_slot(tid, k);
+    c[k] = q < a.nq ? a.cnt[q] : 0;
+    int s = c[k];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(s, o); if (lane >= o) s += t; }
+    incl[k] = s;
+    if (lane == 63) part[k * CMS_AREA_LW + wv] = s;
+  }
   __syncthreads();
-  if (lane == 63) part[wv] = incl;
+  int tile_base = 0;
+  for (int w = 0; w < CMS_AREA_LW; ++w) tile_base += pbefore[w];
+#pragma unroll
+  for (int k = 0; k < CMS_AREA_TILE_K; ++k) {
+    const int ql = cms_area_tile_slot(tid, k), q = q0 + ql;
+    const int mine = tile_base + cms_area_handover(part, k, wv) + incl[k];
+    s_cnt[ql] = c[k]; s_off[ql] = mine - c[k];
+    if (q < a.nq) a.off[q + 1] = mine;
+    if (q == a.nq - 1 && total) *total = mine;
+  }
+  if (tile == 0 && tid == 0) a.off[0] = 0;
   __syncthreads();
-  int wbase = 0;
-  for (int w = 0; w < wv; ++w) wbase += part[w];
-  const int mine = s_before + wbase + incl;
-  if (i < nq) off[i + 1] = mine;
-  if (i == 0) off[0] = 0;
-  if (i == nq - 1 && total) *total = mine;
+  // the lists: eight lanes per query again, CMS_AREA_LG queries of the tile at a time.  First the copies (nearly every query): the first-hits
+  // rows of four rounds are loaded before any is stored, so four loads are in flight per lane (a row is read whole; only its first cnt
+  // entries were written by launch 1 and only those are stored)
+  const int gl = tid & (CMS_AREA_QL - 1), g = tid / CMS_AREA_QL;
+  const int nt = min(CMS_AREA_TILE, a.nq - q0);
+  for (int t0 = 0; t0 < nt; t0 += 4 * CMS_AREA_LG) {
+    int v[4], w[4]; bool ok[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int ql = t0 + u * CMS_AREA_LG + g;
+      const bool in = ql < nt;
+      const int cq = in ? s_cnt[ql] : 0;
+      w[u] = (in ? s_off[ql] : 0) + gl;
+      ok[u] = cq <= CMS_AREA_TMP && gl < cq && cms_area_fits(w[u], a.cap);
+      v[u] = a.tmp[(size_t)(in ? q0 + ql : q0) * CMS_AREA_TMP + gl];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) if (ok[u]) a.idx[w[u]] = v[u];
+  }
+  // then the few queries with more candidates than the first-hits buffer keeps: searched again, in fill mode
+  for (int t0 = 0; t0 < nt; t0 += CMS_AREA_LG) {
+    const int ql = t0 + g;
+    const bool big = ql < nt && s_cnt[ql] > CMS_AREA_TMP;
+    if (__ballot(big)) cms_area_search<true>(a, big ? q0 + ql : q0, big, gl, big ? s_off[ql] : 0);      // (wavefront-uniform branch: all 64 lanes search, the others idle)
+  }
 }

@@ -129,7 +129,7 @@ AREA_FN int cms_area_rects(float x, float y, float r, int F, float inv, CmsAreaR
     else if (i >= 1 && i < 2 && j >= 2 && j < 3) face = 4;
     else if (i >= 2 && i < 3 && j >= 1 && j < 2) face = 2;
   }
-  if (face < 0) return 0;
+  if (face < 0) { out[0] = out[1] = out[2] = CmsAreaRectI{0, 0, 0, 0, 0}; return 0; }
   const int cornerX = (int)x / F * F, cornerY = (int)y / F * F;
   const float xin = x - (float)cornerX, yin = y - (float)cornerY;
   const float xs = xin - r, xe = xin + r, ys = yin - r, ye = yin + r;
@@ -141,32 +141,42 @@ AREA_FN int cms_area_rects(float x, float y, float r, int F, float inv, CmsAreaR
   v[AV_BO] = (int)floorf((xe - Ff) * inv); v[AV_DO] = (int)floorf((ye - Ff) * inv);
   v[AV_AU] = (int)floorf((xs + Ff) * inv); v[AV_CU] = (int)floorf((ys + Ff) * inv);
   v[AV_AN] = (int)floorf((-xs) * inv); v[AV_CN] = (int)floorf((-ys) * inv);
-  const CmsAreaCase* cs;
-  CmsAreaCase inside;
-  if (xinf && yinf) {
-    inside.n = 1;
-    inside.r[0].face = (int8_t)face; inside.r[0].x0 = vA; inside.r[0].x1 = vB; inside.r[0].y0 = vC; inside.r[0].y1 = vD;
-    cs = &inside;
-  } else if (xinf) {
-    cs = &kAreaXin[face][yo ? 0 : 1];
-  } else if (yinf) {
-    cs = &kAreaYin[face][xo ? 0 : 1];
-  } else {
-    int k;                                                    // the reference's else-if chain (Frame.cpp:506-543 etc.)
-    if (xo && yo) k = 0; else if (xu && yo) k = 1; else if (xo && yu) k = 2; else k = 3;
-    cs = &kAreaCorner[face][k];
-  }
   auto ev = [&](int e) -> int {
     if (e == AE_Z) return 0;
     if (e == AE_G1) return CMS_AREA_G - 1;
     if (e == AE_GG) return CMS_AREA_G;
-    if (e < 3 + AV_COUNT) return v[e - 3];
-    return CMS_AREA_G - v[e - 3 - AV_COUNT] - 1;
+    const bool mirrored = e >= 3 + AV_COUNT;
+    const int i = mirrored ? e - 3 - AV_COUNT : e - 3;
+    int val = 0;                                              // v[i] by constant indices (a dynamic one puts v[] into scratch memory on the device)
+#pragma unroll
+    for (int t = 0; t < AV_COUNT; ++t) val = i == t ? v[t] : val;
+    return mirrored ? CMS_AREA_G - val - 1 : val;
   };
-  for (int k = 0; k < cs->n; ++k) {
-    out[k].face = cs->r[k].face; out[k].x0 = ev(cs->r[k].x0); out[k].x1 = ev(cs->r[k].x1); out[k].y0 = ev(cs->r[k].y0); out[k].y1 = ev(cs->r[k].y1);
+  auto rect = [&](const CmsAreaRect& t) -> CmsAreaRectI { return CmsAreaRectI{t.face, ev(t.x0), ev(t.x1), ev(t.y0), ev(t.y1)}; };
+  // The rectangles are built as values and stored once, unconditionally and with constant indices: on the device out[] then lives in
+  // registers, not in scratch memory (entries behind the returned number are zero).
+  CmsAreaRectI r0 = {0, 0, 0, 0, 0}, r1 = r0, r2 = r0;
+  int n = 1;
+  if (xinf && yinf) {                                         // the window inside its face: one rectangle, no table row
+    r0 = CmsAreaRectI{face, v[AV_A], v[AV_B], v[AV_C], v[AV_D]};
+  } else {
+    const CmsAreaCase* cs;
+    if (xinf) {
+      cs = &kAreaXin[face][yo ? 0 : 1];
+    } else if (yinf) {
+      cs = &kAreaYin[face][xo ? 0 : 1];
+    } else {
+      int k;                                                  // the reference's else-if chain (Frame.cpp:506-543 etc.)
+      if (xo && yo) k = 0; else if (xu && yo) k = 1; else if (xo && yu) k = 2; else k = 3;
+      cs = &kAreaCorner[face][k];
+    }
+    n = cs->n;
+    if (n > 0) r0 = rect(cs->r[0]);
+    if (n > 1) r1 = rect(cs->r[1]);
+    if (n > 2) r2 = rect(cs->r[2]);
   }
-  return cs->n;
+  out[0] = r0; out[1] = r1; out[2] = r2;
+  return n;
 }
 #undef vA
 #undef vB

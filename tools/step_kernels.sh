@@ -10,7 +10,7 @@ rows = {r["Name"]: r for r in csv.DictReader(open(sys.argv[1]))}
 l = [x for x in open(sys.argv[2]) if x.startswith("{")]
 v = json.loads(l[-1])["value"] if l else None
 print("== %s: value under the profiler %s" % (sys.argv[3], v))
-for k in ("kb_ba_lin_schur_runs", "kb_ba_trial_solve3r", "kb_ba_trial_edges", "k_fast_cells", "k_resize", "k_ba_expand_edges_many", "k_ba_results_to_host_many", "k_kf_update_poses", "k_area_query"):
+for k in ("kb_ba_lin_schur_runs", "kb_ba_trial_solve3r", "kb_ba_trial_edges", "k_fast_cells", "k_resize", "k_ba_expand_edges_many", "k_ba_results_to_host_many", "k_kf_update_poses", "k_area_query", "k_area_lists"):
     if k in rows:
         r = rows[k]
         print("   %-28s calls %5s  avg %8.1f us  total %8.2f ms" % (k, r["Calls"], float(r["AverageNs"]) / 1e3, float(r["TotalDurationNs"]) / 1e6))
