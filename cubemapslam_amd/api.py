@@ -978,6 +978,15 @@ def ba_read_many(bas):
     return outs
 
 
+def ba_pool_trim(device=0):
+    """cms_ba_pool_trim: hand the device slabs and pinned blocks that closed windows left in the pool back to the runtime -> bytes released"""
+    n = C.c_size_t(0)
+    L = lib()
+    L.cms_ba_pool_trim.argtypes = [C.c_int, C.c_void_p]
+    _chk(L.cms_ba_pool_trim(int(device), C.byref(n)), "cms_ba_pool_trim")
+    return int(n.value)
+
+
 def ba_set_deterministic(on):
     """cms_ba_set_deterministic: windows created afterwards run the fixed-order (bit-repeatable) kernels, like the reference's single-threaded g2o."""
     _chk(lib().cms_ba_set_deterministic(int(on) if not isinstance(on, bool) else (1 if on else 0)), "cms_ba_set_deterministic")      # (an integer >= 2: workgroups per window)

@@ -17,6 +17,7 @@
 #include <thread>
 #include <pthread.h>
 #include <unordered_map>
+#include "cms_ba_pool.h"
 
 // Every A/B switch of the local-BA host code, read ONCE (first use) so that the choices made when a window is built (which work lists exist)
 // and the choices made when it is optimised (which kernels run) can never disagree.  Tests that flip a switch use a child process.
@@ -76,15 +77,17 @@ static const BaKnobs& ba_knobs() {
   return k;
 }
 
+// what the callers of ba_create (below) may ask of it beyond the public cms_ba_create, and what it tells them (nothing is written through the pointers unless the window was created)
 struct BaExpand;
-static thread_local BaExpand* ba_tl_defer_expand = nullptr;      // cms_ba_create_many: where cms_ba_create leaves the description of a device-planned window's expansion instead of launching it
 struct BaDevPlan;
-static thread_local BaDevPlan* ba_tl_dev_plan = nullptr;      // cms_ba_create_many, CMS_BA_PLAN_ON_DEVICE: where cms_ba_create leaves the description of the window's plan kernel (taken: set to nullptr)
-static thread_local hipStream_t ba_tl_setup_stream = nullptr;      // cms_ba_create_many: the stream the calling thread's windows of this call are set up on (ba_setup_stream_take)
-static thread_local bool ba_tl_inputs_pinned = false;      // cms_ba_create_many, CMS_BA_INPUTS_PINNED: the caller's arrays are pinned and stay alive -- they are copied from where they lie
-static thread_local bool ba_force_rw_tables = false;      // cms_ba_debug_run_fg: build the one-wavefront workgroups' tables whatever the knob says
-static inline bool ba_want_rw_tables() { return ba_knobs().run_wg || ba_force_rw_tables; }
-struct BaBlock { void* p; size_t bytes; };      // a device slab / pinned block of the per-device pool (below)
+struct BaCreateOpts {
+  hipStream_t setup_stream = nullptr;   // cms_ba_create_many: the stream the calling thread's windows of this call are set up on (ba_setup_stream_take)
+  bool inputs_pinned = false;           // CMS_BA_INPUTS_PINNED: the caller's arrays are pinned and stay alive -- they are copied from where they lie
+  bool force_host_plan = false;         // cms_ba_linearize: neither the plan kernel nor ba_plan_fast
+  BaDevPlan* dev_plan = nullptr;        // CMS_BA_PLAN_ON_DEVICE: where to leave the description of the window's plan kernel, if the kernel takes the window
+  BaExpand* defer_expand = nullptr;     // where to leave the description of a device-planned window's expansion instead of launching it
+};
+struct BaCreated { bool expand_deferred = false; };      // (whether dev_plan was written: the window's dev_plan)
 struct cms_ba {
   int device = 0;
   hipStream_t stream = nullptr; bool own_stream = true, pooled_stream = false;
@@ -171,18 +174,24 @@ static int ba_lds_attrs_once(int device) {
   return CMS_OK;
 }
 
-// Streams of destroyed windows are kept for the next window of the device: creating a stream costs ~10 ms of host time (measured with
-// CMS_BA_CREATE_TIMING), a window's whole Levenberg run ~3.
-struct BaStreamPool { std::mutex mu; std::vector<hipStream_t> idle[64]; };
-static BaStreamPool& ba_stream_pool() { static BaStreamPool* p = new BaStreamPool; return *p; }      // never destroyed: no HIP calls at process exit
-static hipStream_t ba_stream_take(int device) {
-  BaStreamPool& pl = ba_stream_pool();
-  std::lock_guard<std::mutex> lk(pl.mu);
-  if (device < 0 || device >= 64 || pl.idle[device].empty()) return nullptr;
-  hipStream_t s = pl.idle[device].back();
-  pl.idle[device].pop_back();
-  return s;
-}
+// ---- what destroyed windows leave for the next window of the device (cms_ba_pool.h: the caches; here: one take / give pair per kind that makes and
+// releases the resources, never under a cache's lock).
+// Streams: creating one costs ~10 ms of host time (measured with CMS_BA_CREATE_TIMING), a window's whole Levenberg run ~3.  Set-up streams of
+// cms_ba_create_many are a list of their own -- such a stream never becomes a window's own stream, windows only reference it (own_stream = false) until
+// cms_ba_set_stream moves them, so it may be handed to the next call while earlier windows still point at it; they are never destroyed.
+// Memory: a window of configs[3] size needs ~50 device buffers: allocated and freed one by one (hipMalloc is cheap, hipFree is not: ~40 us each) a
+// LocalBundleAdjustment call spent 2 ms of its 17 in cms_ba_destroy, and the grouped driver's pinned blocks (hipHostMalloc: ~0.3 ms each) another
+// millisecond.  Windows carve their buffers out of a few slabs (ba_alloc); slabs and pinned blocks wait here (bounded: 16 GB of slabs -- a step of bench.py
+// has ~100 windows of 45 MB alive, and a hipFree in the middle of a step synchronises the device --, 512 pinned blocks / 2 GB per pinned kind).
+struct BaPools {
+  static size_t slab_cap() { const char* v = getenv("CMS_BA_POOL_MB"); return v ? (size_t)std::max(0, atoi(v)) << 20 : (size_t)16 << 30; }
+  BaIdleList<hipStream_t> streams{256}, setup_streams{0};
+  BaIdleList<hipEvent_t> events{1024};
+  BaBlockCache dev{slab_cap(), 0};                                                    // device slabs: CMS_BA_POOL_MB per device (default 16 GB)
+  BaBlockCache pin{(size_t)2 << 30, 512}, stage{(size_t)2 << 30, 512};                // coherent pinned blocks, staging pinned blocks
+};
+static BaPools& ba_pools() { static BaPools* p = new BaPools; return *p; }      // never destroyed: no HIP calls at process exit
+static hipStream_t ba_stream_take(int device) { return ba_pools().streams.take(device); }      // nullptr: none idle, the caller creates one
 // hipStreamSynchronize that can give the core away (CMS_BA_RELAXED_WAIT=1): a short spin for waits of a few microseconds, then queries between 40-us sleeps.  The host threads
 // that build, drive and finish windows outnumber the cores a rank gets (16 window threads + the group threads next to a 16-core quota), and the
 // runtime's own wait spins: measured 1.1 ms of CPU per window in cms_ba_read alone, most of it waiting for a 0.6 MB read-back to get its turn.
@@ -204,24 +213,12 @@ static hipError_t ba_wait_stream(hipStream_t s) {
 // (a stream may come back with work still queued on it -- cms_ba_set_stream hands a window's set-up over to the group's stream with an event, not a
 // host wait: whoever takes the stream next simply queues behind that work.  Only a stream in an error state is destroyed.)
 static void ba_stream_give(int device, hipStream_t s) {
-  BaStreamPool& pl = ba_stream_pool();
-  {
-    const hipError_t q = hipStreamQuery(s);
-    std::lock_guard<std::mutex> lk(pl.mu);
-    if (device >= 0 && device < 64 && pl.idle[device].size() < 256 && (q == hipSuccess || q == hipErrorNotReady)) { pl.idle[device].push_back(s); return; }
-  }
-  hipStreamDestroy(s);
+  const hipError_t q = hipStreamQuery(s);
+  if ((q != hipSuccess && q != hipErrorNotReady) || !ba_pools().streams.give(device, s)) hipStreamDestroy(s);
 }
-// set-up streams of cms_ba_create_many: a pool of their own -- such a stream never becomes a window's own stream, windows only reference it (own_stream = false)
-// until cms_ba_set_stream moves them, so it may be handed to the next call while earlier windows still point at it.  Never destroyed (no HIP calls at exit).
-static BaStreamPool& ba_setup_stream_pool() { static BaStreamPool* p = new BaStreamPool; return *p; }
 static hipStream_t ba_setup_stream_take(int device) {
-  BaStreamPool& pl = ba_setup_stream_pool();
-  {
-    std::lock_guard<std::mutex> lk(pl.mu);
-    if (device >= 0 && device < 64 && !pl.idle[device].empty()) { hipStream_t s = pl.idle[device].back(); pl.idle[device].pop_back(); return s; }
-  }
-  hipStream_t s = nullptr;
+  hipStream_t s = ba_pools().setup_streams.take(device);
+  if (s) return s;
   // CMS_BA_SETUP_PRIORITY=low / high: the set-up streams in another priority class than the frame path's and the groups' (A/B)
   static const char* pr = getenv("CMS_BA_SETUP_PRIORITY");
   int lo = 0, hi = 0;
@@ -229,147 +226,58 @@ static hipStream_t ba_setup_stream_take(int device) {
     return hipStreamCreateWithPriority(&s, hipStreamNonBlocking, pr[0] == 'l' ? lo : hi) == hipSuccess ? s : nullptr;
   return hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess ? s : nullptr;
 }
-static void ba_setup_stream_give(int device, hipStream_t s) {
-  BaStreamPool& pl = ba_setup_stream_pool();
-  std::lock_guard<std::mutex> lk(pl.mu);
-  if (device >= 0 && device < 64) pl.idle[device].push_back(s);
-}
-// events for such hand-overs, pooled like the streams
-struct BaEventPool { std::mutex mu; std::vector<hipEvent_t> idle[64]; };
-static BaEventPool& ba_event_pool() { static BaEventPool* p = new BaEventPool; return *p; }
-static hipEvent_t ba_event_take(int device) {
-  BaEventPool& pl = ba_event_pool();
-  {
-    std::lock_guard<std::mutex> lk(pl.mu);
-    if (device >= 0 && device < 64 && !pl.idle[device].empty()) { hipEvent_t e = pl.idle[device].back(); pl.idle[device].pop_back(); return e; }
-  }
-  hipEvent_t e = nullptr;
+static void ba_setup_stream_give(int device, hipStream_t s) { (void)ba_pools().setup_streams.give(device, s); }
+static hipEvent_t ba_event_take(int device) {      // events for such hand-overs
+  hipEvent_t e = ba_pools().events.take(device);
+  if (e) return e;
   return hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess ? e : nullptr;
 }
-static void ba_event_give(int device, hipEvent_t e) {
-  BaEventPool& pl = ba_event_pool();
-  {
-    std::lock_guard<std::mutex> lk(pl.mu);
-    if (device >= 0 && device < 64 && pl.idle[device].size() < 1024) { pl.idle[device].push_back(e); return; }
-  }
-  hipEventDestroy(e);
-}
+static void ba_event_give(int device, hipEvent_t e) { if (!ba_pools().events.give(device, e)) hipEventDestroy(e); }
 
-// ---- memory of a window comes from a per-device pool.  A window of configs[3] size needs ~50 device buffers: allocated and freed one by
-// one (hipMalloc is cheap, hipFree is not: ~40 us each) a LocalBundleAdjustment call spent 2 ms of its 17 in cms_ba_destroy, and the
-// grouped driver's pinned blocks (hipHostMalloc: ~0.3 ms each) another millisecond.  Windows now carve their buffers out of a few slabs;
-// slabs and pinned blocks of destroyed windows wait in the pool for the next window of the device (bounded: 16 GB of slabs -- a step of bench.py has ~100
-// windows of 45 MB alive, and a hipFree in the middle of a step synchronises the device --, 512 pinned blocks).
-struct BaMemPool {
-  std::mutex mu;
-  std::vector<BaBlock> dev[64], pin[64], stage[64];
-  size_t dev_cached[64] = {0}, pin_cached[64] = {0}, stage_cached[64] = {0};      // bytes held per kind (pinned kinds: at most 2 GB each)
-};
-static BaMemPool& ba_pool() { static BaMemPool* p = new BaMemPool; return *p; }      // never destroyed: no HIP calls at process exit
-static void* ba_pool_take(std::vector<BaBlock>& v, size_t bytes, size_t* got) {      // smallest cached block that is large enough (and not absurdly larger)
-  int best = -1;
-  for (size_t i = 0; i < v.size(); ++i)
-    if (v[i].bytes >= bytes && v[i].bytes <= 4 * bytes + (1u << 20) && (best < 0 || v[i].bytes < v[best].bytes)) best = (int)i;
-  if (best < 0) return nullptr;
-  void* p = v[best].p; *got = v[best].bytes;
-  v[best] = v.back(); v.pop_back();
-  return p;
-}
 // give the cached blocks of a device back to the runtime (all kinds, or only the device slabs); returns the bytes released
 static size_t ba_pool_trim_device(int device, bool pinned_too) {
-  BaMemPool& pl = ba_pool();
-  if (device < 0 || device >= 64) return 0;
-  std::vector<BaBlock> dv, pn, st;
-  {
-    std::lock_guard<std::mutex> lk(pl.mu);
-    dv.swap(pl.dev[device]); pl.dev_cached[device] = 0;
-    if (pinned_too) { pn.swap(pl.pin[device]); st.swap(pl.stage[device]); pl.pin_cached[device] = 0; pl.stage_cached[device] = 0; }
-  }
   size_t n = 0;
-  for (const BaBlock& b : dv) { hipFree(b.p); n += b.bytes; }
-  for (const BaBlock& b : pn) { hipHostFree(b.p); n += b.bytes; }
-  for (const BaBlock& b : st) { hipHostFree(b.p); n += b.bytes; }
+  for (const BaBlock& b : ba_pools().dev.drain(device)) { hipFree(b.p); n += b.bytes; }
+  if (pinned_too)
+    for (BaBlockCache* c : {&ba_pools().pin, &ba_pools().stage})
+      for (const BaBlock& b : c->drain(device)) { hipHostFree(b.p); n += b.bytes; }
   return n;
 }
-// The pool keeps slabs and pinned blocks of destroyed windows for the next window (a hipFree in the middle of a step synchronises the device).
-// Callers that share the device with other allocators can hand them back: bytes released are returned in *released (may be NULL).
+// Callers that share the device with other allocators can hand the cached slabs and pinned blocks back: bytes released are returned in *released (may be NULL).
 extern "C" int cms_ba_pool_trim(int device, size_t* released) {
-  if (device < 0 || device >= 64) return cms_fail(CMS_ERR_ARG, "cms_ba_pool_trim: bad device");
+  if (!ba_pool_device_ok(device)) return cms_fail(CMS_ERR_ARG, "cms_ba_pool_trim: bad device");
   HIPCHK(hipSetDevice(device));
   const size_t n = ba_pool_trim_device(device, true);
   if (released) *released = n;
   return CMS_OK;
 }
-static size_t ba_pool_cap_bytes() {      // CMS_BA_POOL_MB: upper bound of the cached device slabs per device (default 16 GB)
-  static const size_t cap = [] { const char* v = getenv("CMS_BA_POOL_MB"); return v ? (size_t)std::max(0, atoi(v)) << 20 : (size_t)16 << 30; }();
-  return cap;
+// a cached block, or a new one from `alloc`.  When that fails -- a slab: for want of memory -- what sits idle in the device's caches is released (a slab: the
+// slabs, gigabytes maybe; a pinned block: every kind) and it is tried once more
+template <class Alloc> static hipError_t ba_block_take(BaBlockCache& cache, bool pinned, int device, size_t bytes, void** p, size_t* got, Alloc alloc) {
+  BaBlock b;
+  if (cache.take(device, bytes, &b)) { *p = b.p; *got = b.bytes; return hipSuccess; }
+  *got = bytes;
+  hipError_t e = alloc();
+  if (e != hipSuccess && (pinned || e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation)) { (void)hipGetLastError(); if (ba_pool_trim_device(device, pinned) > 0) e = alloc(); }
+  return e;
 }
 static hipError_t ba_dev_take(int device, size_t bytes, void** p, size_t* got) {
-  BaMemPool& pl = ba_pool();
-  if (device >= 0 && device < 64) {
-    std::lock_guard<std::mutex> lk(pl.mu);
-    if ((*p = ba_pool_take(pl.dev[device], bytes, got)) != nullptr) { pl.dev_cached[device] -= *got; return hipSuccess; }
-  }
-  *got = bytes;
-  hipError_t e = hipMalloc(p, bytes);
-  if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {      // gigabytes may sit idle in the cache: release them and try once more
-    (void)hipGetLastError();
-    if (ba_pool_trim_device(device, false) > 0) e = hipMalloc(p, bytes);
-  }
-  return e;
+  return ba_block_take(ba_pools().dev, false, device, bytes, p, got, [&] { return hipMalloc(p, bytes); });
 }
-static void ba_dev_give(int device, void* p, size_t bytes) {
-  BaMemPool& pl = ba_pool();
-  if (device >= 0 && device < 64) {
-    std::lock_guard<std::mutex> lk(pl.mu);
-    if (pl.dev_cached[device] + bytes <= ba_pool_cap_bytes()) { pl.dev[device].push_back({p, bytes}); pl.dev_cached[device] += bytes; return; }
-  }
-  hipFree(p);
-}
+static void ba_dev_give(int device, void* p, size_t bytes) { if (!ba_pools().dev.give(device, {p, bytes})) hipFree(p); }
 // pinned, device-visible, explicitly coherent host memory (the grouped driver's mirrors are written by running kernels)
 static hipError_t ba_pin_take(int device, size_t bytes, void** p, size_t* got) {
-  BaMemPool& pl = ba_pool();
-  if (device >= 0 && device < 64) {
-    std::lock_guard<std::mutex> lk(pl.mu);
-    if ((*p = ba_pool_take(pl.pin[device], bytes, got)) != nullptr) { pl.pin_cached[device] -= *got; return hipSuccess; }
-  }
-  *got = bytes;
-  hipError_t e = hipHostMalloc(p, bytes, hipHostMallocMapped | hipHostMallocCoherent);
-  if (e != hipSuccess) { (void)hipGetLastError(); if (ba_pool_trim_device(device, true) > 0) e = hipHostMalloc(p, bytes, hipHostMallocMapped | hipHostMallocCoherent); }
-  return e;
+  return ba_block_take(ba_pools().pin, true, device, bytes, p, got, [&] { return hipHostMalloc(p, bytes, hipHostMallocMapped | hipHostMallocCoherent); });
 }
+static void ba_pin_give(int device, void* p, size_t bytes) { if (!ba_pools().pin.give(device, {p, bytes})) hipHostFree(p); }
 // plain pinned host memory (not device-coherent): staging blocks of uploads and read-backs.  A copy from / to such memory goes through the DMA
 // engines; the coherent, device-mapped kind above made the runtime copy with a shader kernel (__amd_rocclr_copyBuffer: 1.8 ms of kernel time
 // per bench.py step for the 32 window uploads) -- CMS_BA_STAGE_COHERENT=1 brings that back (A/B)
 static hipError_t ba_stage_take(int device, size_t bytes, void** p, size_t* got) {
-  static const bool coherent = getenv("CMS_BA_STAGE_COHERENT") != nullptr;
-  BaMemPool& pl = ba_pool();
-  if (device >= 0 && device < 64) {
-    std::lock_guard<std::mutex> lk(pl.mu);
-    if ((*p = ba_pool_take(pl.stage[device], bytes, got)) != nullptr) { pl.stage_cached[device] -= *got; return hipSuccess; }
-  }
-  *got = bytes;
-  const unsigned flags = coherent ? (hipHostMallocMapped | hipHostMallocCoherent) : hipHostMallocDefault;
-  hipError_t e = hipHostMalloc(p, bytes, flags);
-  if (e != hipSuccess) { (void)hipGetLastError(); if (ba_pool_trim_device(device, true) > 0) e = hipHostMalloc(p, bytes, flags); }
-  return e;
+  static const unsigned flags = getenv("CMS_BA_STAGE_COHERENT") ? (hipHostMallocMapped | hipHostMallocCoherent) : hipHostMallocDefault;
+  return ba_block_take(ba_pools().stage, true, device, bytes, p, got, [&] { return hipHostMalloc(p, bytes, flags); });
 }
-static void ba_stage_give(int device, void* p, size_t bytes) {
-  BaMemPool& pl = ba_pool();
-  if (device >= 0 && device < 64) {
-    std::lock_guard<std::mutex> lk(pl.mu);
-    if (pl.stage[device].size() < 512 && pl.stage_cached[device] + bytes <= ((size_t)2 << 30)) { pl.stage[device].push_back({p, bytes}); pl.stage_cached[device] += bytes; return; }
-  }
-  hipHostFree(p);
-}
-static void ba_pin_give(int device, void* p, size_t bytes) {
-  BaMemPool& pl = ba_pool();
-  if (device >= 0 && device < 64) {
-    std::lock_guard<std::mutex> lk(pl.mu);
-    if (pl.pin[device].size() < 512 && pl.pin_cached[device] + bytes <= ((size_t)2 << 30)) { pl.pin[device].push_back({p, bytes}); pl.pin_cached[device] += bytes; return; }
-  }
-  hipHostFree(p);
-}
+static void ba_stage_give(int device, void* p, size_t bytes) { if (!ba_pools().stage.give(device, {p, bytes})) hipHostFree(p); }
 
 template <class T> static int ba_alloc(cms_ba* b, T** p, size_t n) {
   // carve from the window's current slab (256-byte granules); the first slab is sized for the window (~170 B per edge, ~400 B per point, the
@@ -390,6 +298,14 @@ template <class T> static int ba_alloc(cms_ba* b, T** p, size_t n) {
   b->slab_off += need;
   return CMS_OK;
 }
+
+// a window's read-back goes through its pinned staging block: poses at 0, points at o_pts, outlier flags at o_flags (256-byte granules); bytes: what creation reserves for it
+struct BaReadLayout { size_t o_pts, o_flags, bytes; };
+static BaReadLayout ba_read_layout(int K, int P, int E) {
+  const size_t poses = (size_t)7 * K * 8, pts = (size_t)3 * P * 8, o_pts = (poses + 255) & ~(size_t)255;
+  return {o_pts, o_pts + ((pts + 255) & ~(size_t)255), poses + 255 + pts + 255 + (size_t)E + 255};
+}
+static bool ba_read_fits(const cms_ba* b) { return b->h_stage && b->h_stage_bytes >= ba_read_layout(b->K, b->P, b->E).o_flags + (size_t)b->E; }
 
 extern "C" void cms_ba_destroy(cms_ba* b) {
   if (!b) return;
@@ -487,7 +403,6 @@ static std::atomic<int>& ba_det_mode() { static std::atomic<int> m{ba_knobs().de
 // (on >= 2: the number of workgroups such windows are cut into -- see the header; 1: the default count)
 extern "C" int cms_ba_set_deterministic(int on) { ba_det_mode().store(on < 0 ? 1 : std::min(on, (int)BA_SE_RANGES)); return CMS_OK; }
 extern "C" int cms_ba_get_deterministic(void) { return ba_det_mode().load(); }
-static thread_local bool ba_tl_force_host_plan = false;      // cms_ba_linearize: the host plan for the window this thread creates next
 static std::atomic<int> ba_plans_in_flight{0};      // windows being planned right now (cms_ba_create / cms_ba_debug_plan calls of all host threads)
 // lanes of one group of 16 -> LDS banks, every lane with four candidate banks: augmenting-path matching, the rest on their least-used bank
 struct BaDiagMatch {
@@ -795,7 +710,7 @@ struct BaPlan {
 };
 template <class Tick>
 static void ba_plan(cms_ba* b, BaPlan& pl, int K, const uint8_t* fixed, int P, int E, const int* e_pose, const int* e_point, const double* e_obs,
-                    const double* e_invsig2, const int8_t* e_face, Tick&& tick) {
+                    const double* e_invsig2, const int8_t* e_face, bool want_rw, Tick&& tick) {      // want_rw: the one-wavefront workgroups' tables too
   std::vector<int>&pose_slot = pl.pose_slot, &prank = pl.prank, &s_pose = pl.s_pose, &s_point = pl.s_point, &pt_off = pl.pt_off, &pose_off = pl.pose_off,
                   &pose_edges = pl.pose_edges, &ce0 = pl.ce0, &pob = pl.pob, &ident = pl.ident, &lone = pl.lone;
   std::vector<double>&s_obs = pl.s_obs, &s_inv = pl.s_inv;
@@ -1113,8 +1028,8 @@ static void ba_plan(cms_ba* b, BaPlan& pl, int K, const uint8_t* fixed, int P, i
         rm_cost[(size_t)c + 1] = rm_cost[c] + (uint32_t)(kn.em_cost_a + kn.em_cost_b * (kmax / 2));
       }
       // ... and for the one-wavefront workgroups (cms_ba_schur_runwg.hip): the accumulators' offsets into the global copy, the cut points of the two classes
-      if (ba_want_rw_tables()) run_fg.assign(std::max<size_t>(runs.size(), 1) * 64 * 24, BA_RW_NONE);
-      for (size_t r = 0; r < runs.size() && ba_want_rw_tables(); ++r) {
+      if (want_rw) run_fg.assign(std::max<size_t>(runs.size(), 1) * 64 * 24, BA_RW_NONE);
+      for (size_t r = 0; r < runs.size() && want_rw; ++r) {
         const int q = runs[r].first;
         BaRunSig rs; rs.kf = 0; rs.fpos8 = 0; rs.fslot8 = 0;
         for (int i = cpo[q]; i < cpo[q + 1]; ++i) { const int sl = pose_slot[e_pose[cpe[i]]]; if (sl >= 0) rs.push(i - cpo[q], sl); }
@@ -1125,7 +1040,7 @@ static void ba_plan(cms_ba* b, BaPlan& pl, int K, const uint8_t* fixed, int P, i
         int n_rmA = 0;
         while (n_rmA < n_rm && ba_rw_class(runs[rm_chunk_run[n_rmA]].kf) == 0) ++n_rmA;
         pl.n_rmA = n_rmA;
-        if (ba_want_rw_tables()) {
+        if (want_rw) {
           rm_cut.assign(2 * (BA_RW_CUTS + 1), 0);
           ba_rw_make_cuts(rm_cost, 0, n_rmA, rm_cut.data());
           ba_rw_make_cuts(rm_cost, n_rmA, n_rm, rm_cut.data() + (BA_RW_CUTS + 1));
@@ -1166,7 +1081,7 @@ extern "C" int cms_ba_debug_plan(int K, const uint8_t* fixed, int P, int E, cons
   BaPlan pl;
   auto t_last = std::chrono::steady_clock::now();
   const bool timing = ba_knobs().create_timing;
-  ba_plan(b, pl, K, fixed, P, E, e_pose, e_point, nullptr, nullptr, nullptr, [&](const char* what) {
+  ba_plan(b, pl, K, fixed, P, E, e_pose, e_point, nullptr, nullptr, nullptr, ba_knobs().run_wg, [&](const char* what) {
     const auto now = std::chrono::steady_clock::now();
     if (timing) fprintf(stderr, "[cms_ba_debug_plan] %s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
     t_last = now;
@@ -1216,9 +1131,13 @@ k_ba_gather(int K, int P, int E, const int* __restrict__ perm, const int* __rest
   for (int i = t0; i < n_gsum_bp; i += gs) gsum_bp[i] = 0.0;
 }
 
-extern "C" int cms_ba_create(cms_ba** out, int device, int K, const double* poses, const uint8_t* fixed, int P,
-                             const double* points, int E, const int* e_pose, const int* e_point, const double* e_obs,
-                             const double* e_invsig2, const int8_t* e_face, double fx, double fy, double cx, double cy) {
+// One window: plan (plan kernel / ba_plan_fast / ba_plan), device memory, one staged upload, the set-up kernel.  w.flags is not looked at: the callers say
+// what they want in `o`; `made` (may be NULL) is only written on success.
+static int ba_create(cms_ba** out, int device, const cms_ba_window& w, const BaCreateOpts& o, BaCreated* made) {
+  const int K = w.K, P = w.P, E = w.E;
+  const double *poses = w.poses, *points = w.points, *e_obs = w.e_obs, *e_invsig2 = w.e_invsig2;
+  const uint8_t* fixed = w.fixed; const int *e_pose = w.e_pose, *e_point = w.e_point; const int8_t* e_face = w.e_face;
+  const double fx = w.fx, fy = w.fy, cx = w.cx, cy = w.cy;
   if (!out || K < 1 || P < 1 || E < 1 || !poses || !fixed || !points || !e_pose || !e_point || !e_obs || !e_invsig2 || !e_face)
     return cms_fail(CMS_ERR_ARG, "cms_ba_create: bad argument");
   *out = nullptr;
@@ -1260,7 +1179,7 @@ extern "C" int cms_ba_create(cms_ba** out, int device, int K, const double* pose
     int lo = 0, hi = 0;
     if (ba_knobs().stream_priority == 'l' && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi)
       BA_HIP(hipStreamCreateWithPriority(&b->stream, hipStreamNonBlocking, lo));
-    else if (ba_tl_setup_stream) { b->stream = ba_tl_setup_stream; b->own_stream = false; }
+    else if (o.setup_stream) { b->stream = o.setup_stream; b->own_stream = false; }
     else {
       b->stream = ba_stream_take(device);
       if (!b->stream) BA_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
@@ -1277,11 +1196,11 @@ extern "C" int cms_ba_create(cms_ba** out, int device, int K, const double* pose
   // it validates the indices in that pass.  Everything else: the host plan, after the validation loop
   // ... or, inside a cms_ba_create_many call with CMS_BA_PLAN_ON_DEVICE, the plan kernel (cms_api_ba_devplan.hip): the host only checks what does not need
   // the observations, the kernel validates the indices and says so in its status word
-  BaDevPlan* const dplan = ba_tl_force_host_plan ? nullptr : ba_tl_dev_plan;
+  const bool want_rw = kn.run_wg;      // the one-wavefront workgroups' tables
   unsigned long long dp_free_mask = 0;
-  const bool devp = dplan && ba_dev_plan_prepare(b, K, fixed, P, E, pl.pose_slot, dp_free_mask);
+  const bool devp = o.dev_plan && !o.force_host_plan && ba_dev_plan_prepare(b, K, fixed, P, E, want_rw, pl.pose_slot, dp_free_mask);
   b->dev_plan = devp;
-  const int fast_rc = devp ? 1 : ba_tl_force_host_plan ? 0 : ba_plan_fast(b, fp, K, fixed, P, E, e_pose, e_point, e_face, tick);
+  const int fast_rc = devp ? 1 : o.force_host_plan ? 0 : ba_plan_fast(b, fp, K, fixed, P, E, e_pose, e_point, e_face, want_rw, tick);
   const bool fast = fast_rc > 0;
   bool bad_index = fast_rc < 0;
   if (!fast && !bad_index)
@@ -1294,7 +1213,7 @@ extern "C" int cms_ba_create(cms_ba** out, int device, int K, const double* pose
   b->fast_plan = fast;
   if (devp) {}
   else if (fast) pl.pose_slot = fp.pose_slot;
-  else ba_plan(b, pl, K, fixed, P, E, e_pose, e_point, e_obs, e_invsig2, e_face, tick);
+  else ba_plan(b, pl, K, fixed, P, E, e_pose, e_point, e_obs, e_invsig2, e_face, want_rw, tick);
   std::vector<int>&pose_slot = pl.pose_slot, &prank = pl.prank, &s_pose = pl.s_pose, &s_point = pl.s_point, &pt_off = pl.pt_off, &pose_off = pl.pose_off, &pose_edges = pl.pose_edges;
   std::vector<double>&s_obs = pl.s_obs, &s_inv = pl.s_inv;
   std::vector<int8_t>& s_face = pl.s_face;
@@ -1307,8 +1226,7 @@ extern "C" int cms_ba_create(cms_ba** out, int device, int K, const double* pose
   auto up = [&](const void* src, size_t bytes, auto** dst) { ups.push_back({src, bytes, reinterpret_cast<void**>(dst), false}); };
   // one of the CALLER's arrays: with CMS_BA_INPUTS_PINNED it is not staged (a memcpy of ~3 MB per 80 k-observation window: as much host time as the
   // whole plan) but copied asynchronously from the caller's pinned memory
-  const bool inputs_pinned = ba_tl_inputs_pinned;
-  auto up_in = [&](const void* src, size_t bytes, auto** dst) { ups.push_back({src, bytes, reinterpret_cast<void**>(dst), inputs_pinned && bytes >= 4096}); };
+  auto up_in = [&](const void* src, size_t bytes, auto** dst) { ups.push_back({src, bytes, reinterpret_cast<void**>(dst), o.inputs_pinned && bytes >= 4096}); };
   if (se_built) {
     const int NP2 = np * (np + 1) / 2;
     // (a deterministic window's first pass parks its workgroups' diagonal sums in `partial` before the first Schur launch: Rt slices of 6 np, and Rt =
@@ -1341,7 +1259,7 @@ extern "C" int cms_ba_create(cms_ba** out, int device, int K, const double* pose
     // what the expansion kernels write: the per-edge words and the runs' tables (run_lane: the vector variant's table, never read on this path)
     BA_TRY(ba_alloc(b, &b->d_se_info, (size_t)E)); BA_TRY(ba_alloc(b, &b->d_run_mf, (size_t)std::max(fp.n_runs, 1) * 64));
     BA_TRY(ba_alloc(b, &b->d_run_fl, (size_t)std::max(fp.n_runs, 1) * 64 * 12)); BA_TRY(ba_alloc(b, &b->d_run_lane, 1));
-    if (ba_want_rw_tables()) BA_TRY(ba_alloc(b, &b->d_run_fg, (size_t)std::max(fp.n_runs, 1) * 64 * 24));
+    if (want_rw) BA_TRY(ba_alloc(b, &b->d_run_fg, (size_t)std::max(fp.n_runs, 1) * 64 * 24));
   } else if (se_built) {
     up(pl.ce0.data(), pl.ce0.size() * sizeof(int), &b->d_se_chunk_e0); up(pl.info.data(), pl.info.size() * sizeof(uint32_t), &b->d_se_info);
     up(pl.pob.data(), pl.pob.size() * sizeof(int), &b->d_se_pob); up(pl.ident.data(), pl.ident.size() * sizeof(int), &b->d_se_chunk_off);
@@ -1593,7 +1511,7 @@ extern "C" int cms_ba_create(cms_ba** out, int device, int K, const double* pose
     staged = total;                                               // the staged entries first (one copy), the caller's pinned arrays behind them (one copy each)
     for (size_t i = 0; i < ups.size(); ++i) if (ups[i].direct) { offs[i] = total; total += (ups[i].bytes + 255) & ~(size_t)255; }
     // (the read-back of cms_ba_read reuses the pinned block: poses, points, flags)
-    const size_t rd_bytes = (size_t)7 * K * 8 + 255 + (size_t)3 * P * 8 + 255 + (size_t)E + 255;
+    const size_t rd_bytes = ba_read_layout(K, P, E).bytes;
     char* dev = nullptr;
     BA_TRY(ba_alloc(b, &dev, std::max(total, (size_t)256)));
     BA_HIP(ba_stage_take(device, std::max(staged, rd_bytes), (void**)&b->h_stage, &b->h_stage_bytes));
@@ -1617,8 +1535,9 @@ extern "C" int cms_ba_create(cms_ba** out, int device, int K, const double* pose
   }
   tick("uploads");
   b->cur = 0;
+  BaExpand x; BaDevPlan dp;      // (they reach o.defer_expand / o.dev_plan at the very end: a call that fails leaves nothing there)
+  const bool defer = fast && o.defer_expand != nullptr;
   if (fast) {
-    BaExpand x;
     x.K = K; x.P = P; x.E = E; x.np = np;
     x.e_pose = b->d_raw_pose; x.e_point = b->d_raw_point; x.e_face = b->d_raw_face; x.cedge = devp ? b->d_cedge : fp.grouped ? nullptr : b->d_cedge; x.cpo = b->d_cpo;
     x.prank = b->d_prank; x.pinv = b->d_pinv; x.pt_off = b->d_pt_off; x.pcopy = b->d_pcopy; x.lo_copy = b->d_lo_copy; x.e_lo0 = devp ? 0 : fp.pt_off[fp.P_rm]; x.pose_slot = b->d_pose_slot;
@@ -1630,7 +1549,6 @@ extern "C" int cms_ba_create(cms_ba** out, int device, int K, const double* pose
     x.ce0 = b->d_se_chunk_e0; x.n_rm = devp ? 0 : fp.n_rm; x.nchunks = devp ? 0 : fp.nchunks; x.run_sig = b->d_run_sig; x.n_runs = devp ? 0 : fp.n_runs; x.run_mf = b->d_run_mf; x.run_fl = b->d_run_fl; x.run_fg = b->d_run_fg;
     if (devp) {
       // scratch of the plan kernel + its description; cms_ba_create_many launches it in front of the expansion
-      BaDevPlan dp;
       memset(&dp, 0, sizeof(dp));
       dp.K = K; dp.P = P; dp.E = E; dp.np = np; dp.chunk_cap = dp_chunk_cap; dp.em_cost_a = kn.em_cost_a; dp.em_cost_b = kn.em_cost_b; dp.free_mask = dp_free_mask;
       dp.e_pose = b->d_raw_pose; dp.e_point = b->d_raw_point; dp.e_face = b->d_raw_face; dp.pose_slot = b->d_pose_slot;
@@ -1643,10 +1561,9 @@ extern "C" int cms_ba_create(cms_ba** out, int device, int K, const double* pose
       dp.counts = b->d_plan_counts; dp.h_counts = b->h_plan_counts;
       static const bool dp_clk = getenv("CMS_BA_DP_CLK") != nullptr;
       if (dp_clk) { BA_TRY(ba_alloc(b, &b->d_plan_clk, 16)); dp.clk = b->d_plan_clk; }
-      *dplan = dp; ba_tl_dev_plan = nullptr;
     }
-    if (ba_tl_defer_expand) { *ba_tl_defer_expand = x; ba_tl_defer_expand = nullptr; }      // cms_ba_create_many launches the group's expansions together
-    else hipLaunchKernelGGL(k_ba_expand_edges, dim3(std::min((std::max(E, P) + 255) / 256, 1024)), dim3(256), 0, b->stream, x);      // (+ the runs' tables)
+    if (!defer)      // (deferred: cms_ba_create_many launches the group's expansions together)
+      hipLaunchKernelGGL(k_ba_expand_edges, dim3(std::min((std::max(E, P) + 255) / 256, 1024)), dim3(256), 0, b->stream, x);      // (+ the runs' tables)
   } else
   hipLaunchKernelGGL(k_ba_gather, dim3(std::min((std::max(E, P) + 255) / 256, 1024)), dim3(256), 0, b->stream, K, P, E, (const int*)b->d_perm, (const int*)b->d_pinv,
                      (const double*)b->d_raw_obs, (const double*)b->d_raw_inv, (const double*)b->d_raw_pts, b->d_e_obs, b->d_e_inv, b->d_pts0,
@@ -1657,8 +1574,17 @@ extern "C" int cms_ba_create(cms_ba** out, int device, int K, const double* pose
   b->gsum_clean = true;
   tick("reset");
   if (timing) fprintf(stderr, "[cms_ba_create] K %d P %d E %d ms:%s\n", K, P, E, t_log.c_str());
+  if (defer) *o.defer_expand = x;
+  if (devp) *o.dev_plan = dp;
+  if (made) made->expand_deferred = defer;
   *out = b;
   return CMS_OK;
+}
+extern "C" int cms_ba_create(cms_ba** out, int device, int K, const double* poses, const uint8_t* fixed, int P,
+                             const double* points, int E, const int* e_pose, const int* e_point, const double* e_obs,
+                             const double* e_invsig2, const int8_t* e_face, double fx, double fy, double cx, double cy) {
+  const cms_ba_window w = {K, poses, fixed, P, points, E, e_pose, e_point, e_obs, e_invsig2, e_face, fx, fy, cx, cy, 0};
+  return ba_create(out, device, w, BaCreateOpts(), nullptr);
 }
 
 // developer / test entry: the plan arrays AS THE DEVICE HOLDS THEM (after the window's set-up has run), whichever planner made them -- for the
@@ -1742,8 +1668,8 @@ extern "C" int cms_ba_read(cms_ba* b, double* poses, double* points, uint8_t* ou
   if (!b) return cms_fail(CMS_ERR_ARG, "null ba");
   HIPCHK(hipSetDevice(b->device));
   // one pinned block (the window's upload staging, sized for this at creation), up to three copies, one synchronisation
-  const size_t o_pose = 0, o_pts = ((size_t)7 * b->K * 8 + 255) & ~(size_t)255, o_flags = o_pts + (((size_t)3 * b->P * 8 + 255) & ~(size_t)255);
-  if (!b->h_stage || b->h_stage_bytes < o_flags + (size_t)b->E) return cms_fail(CMS_ERR_HIP, "cms_ba_read: staging block missing");
+  const size_t o_pose = 0, o_pts = ba_read_layout(b->K, b->P, b->E).o_pts, o_flags = ba_read_layout(b->K, b->P, b->E).o_flags;
+  if (!ba_read_fits(b)) return cms_fail(CMS_ERR_HIP, "cms_ba_read: staging block missing");
   char* h = b->h_stage;
   // A window that runs on a stream it shares with others (cms_ba_set_stream) reads back on a stream taken from the pool: the shared one may
   // be busy with the next windows for milliseconds, and this window's results are complete (optimise returned) unless a reset is pending
@@ -1818,7 +1744,7 @@ extern "C" int cms_ba_create_many(cms_ba** out, int n, int device, const cms_ba_
   std::vector<BaExpand> xs((size_t)n);
   std::vector<BaDevPlan> dps((size_t)n);
   static const bool dev_plan_all = getenv("CMS_BA_DEV_PLAN") != nullptr;      // A/B: every window of every call, whatever its flags say
-  std::vector<char> deferred((size_t)n, 0);
+  std::vector<BaCreated> made((size_t)n);
   std::vector<int> rcs((size_t)n, CMS_OK);
   std::vector<std::string> errs((size_t)n);
   std::atomic<int> next(0);
@@ -1829,23 +1755,19 @@ extern "C" int cms_ba_create_many(cms_ba** out, int n, int device, const cms_ba_
   static const bool shared_stream = getenv("CMS_BA_SETUP_OWN_STREAMS") == nullptr;
   std::mutex ss_mu; std::vector<hipStream_t> ss_taken;
   auto work = [&]() {
+    BaCreateOpts o;
     if (shared_stream && hipSetDevice(device) == hipSuccess) {
-      hipStream_t st = ba_setup_stream_take(device);
-      ba_tl_setup_stream = st;
-      if (st) { std::lock_guard<std::mutex> lk(ss_mu); ss_taken.push_back(st); }
+      o.setup_stream = ba_setup_stream_take(device);
+      if (o.setup_stream) { std::lock_guard<std::mutex> lk(ss_mu); ss_taken.push_back(o.setup_stream); }
     }
-    struct Reset { ~Reset() { ba_tl_setup_stream = nullptr; } } reset_;
     for (;;) {
       const int i = next.fetch_add(1);
       if (i >= n) break;
       memset(&xs[(size_t)i], 0, sizeof(BaExpand));
-      ba_tl_defer_expand = &xs[(size_t)i];
-      ba_tl_dev_plan = (dev_plan_all || (w[i].flags & CMS_BA_PLAN_ON_DEVICE) != 0) ? &dps[(size_t)i] : nullptr;
-      ba_tl_inputs_pinned = (w[i].flags & CMS_BA_INPUTS_PINNED) != 0;
-      rcs[(size_t)i] = cms_ba_create(&out[i], device, w[i].K, w[i].poses, w[i].fixed, w[i].P, w[i].points, w[i].E, w[i].e_pose, w[i].e_point, w[i].e_obs, w[i].e_invsig2,
-                                     w[i].e_face, w[i].fx, w[i].fy, w[i].cx, w[i].cy);
-      deferred[(size_t)i] = ba_tl_defer_expand == nullptr && rcs[(size_t)i] == CMS_OK;      // (taken: a device-planned window; a host-planned one launched its own set-up kernel)
-      ba_tl_defer_expand = nullptr; ba_tl_inputs_pinned = false; ba_tl_dev_plan = nullptr;
+      o.defer_expand = &xs[(size_t)i];
+      o.dev_plan = (dev_plan_all || (w[i].flags & CMS_BA_PLAN_ON_DEVICE) != 0) ? &dps[(size_t)i] : nullptr;
+      o.inputs_pinned = (w[i].flags & CMS_BA_INPUTS_PINNED) != 0;
+      rcs[(size_t)i] = ba_create(&out[i], device, w[i], o, &made[(size_t)i]);
       if (rcs[(size_t)i] != CMS_OK) errs[(size_t)i] = cms_last_error();
     }
   };
@@ -1867,7 +1789,7 @@ extern "C" int cms_ba_create_many(cms_ba** out, int n, int device, const cms_ba_
   for (int i = 0; i < n; ++i) if (rcs[(size_t)i] != CMS_OK) return fail_all(rcs[(size_t)i], errs[(size_t)i].c_str());
   // ---- the deferred expansions: batches of eight on the first window's stream, behind every window's upload; the other windows' streams then wait for it
   std::vector<int> D;
-  for (int i = 0; i < n; ++i) if (deferred[(size_t)i]) D.push_back(i);
+  for (int i = 0; i < n; ++i) if (made[(size_t)i].expand_deferred) D.push_back(i);      // (device-planned windows; a host-planned one launched its own set-up kernel)
   if (D.empty()) return CMS_OK;
   if (hipSetDevice(device) != hipSuccess) return fail_all(CMS_ERR_HIP, "cms_ba_create_many: hipSetDevice");
   static_assert(BA_DP_BATCH == BA_EXPAND_BATCH, "a batch of expansions has one batch of plans in front of it");
@@ -1932,10 +1854,9 @@ extern "C" int cms_ba_create_many(cms_ba** out, int n, int device, const cms_ba_
     if (prc == 1) continue;
     if (prc < 0) return fail_all(CMS_ERR_ARG, "cms_ba_create: edge index / face out of range (unknown-face edges must be culled by the caller)");
     cms_ba_destroy(b); out[i] = nullptr;
-    ba_tl_inputs_pinned = (w[i].flags & CMS_BA_INPUTS_PINNED) != 0;
-    const int rc = cms_ba_create(&out[i], device, w[i].K, w[i].poses, w[i].fixed, w[i].P, w[i].points, w[i].E, w[i].e_pose, w[i].e_point, w[i].e_obs, w[i].e_invsig2,
-                                 w[i].e_face, w[i].fx, w[i].fy, w[i].cx, w[i].cy);
-    ba_tl_inputs_pinned = false;
+    BaCreateOpts o;      // (no set-up stream: the call's set-up streams are through with their batches; the window takes a pooled stream of its own)
+    o.inputs_pinned = (w[i].flags & CMS_BA_INPUTS_PINNED) != 0;
+    const int rc = ba_create(&out[i], device, w[i], o, nullptr);
     if (rc != CMS_OK) { const std::string msg = cms_last_error(); return fail_all(rc, msg.c_str()); }
   }
   return CMS_OK;
@@ -1949,8 +1870,7 @@ extern "C" int cms_ba_read_many(cms_ba** bas, int n, double** poses, double** po
   std::vector<int> F;      // windows the batched kernel takes: device-planned, results complete (nothing pending on a stream of their own), one device
   for (int i = 0; i < n; ++i) {
     cms_ba* b = bas[i];
-    const size_t o_pts = ((size_t)7 * b->K * 8 + 255) & ~(size_t)255, o_flags = o_pts + (((size_t)3 * b->P * 8 + 255) & ~(size_t)255);
-    const bool ok = b->fast_plan && b->device == bas[0]->device && b->h_stage && b->h_stage_bytes >= o_flags + (size_t)b->E && !b->setup_wait_pending &&
+    const bool ok = b->fast_plan && b->device == bas[0]->device && ba_read_fits(b) && !b->setup_wait_pending &&
                     !(b->own_stream && b->async_pending);
     if (ok) F.push_back(i);
     else {
@@ -1974,12 +1894,12 @@ extern "C" int cms_ba_read_many(cms_ba** bas, int n, double** poses, double** po
     for (int k = 0; k < nb; ++k) {
       const int i = F[b0 + k];
       cms_ba* b = bas[i];
-      const size_t o_pts = ((size_t)7 * b->K * 8 + 255) & ~(size_t)255, o_flags = o_pts + (((size_t)3 * b->P * 8 + 255) & ~(size_t)255);
+      const BaReadLayout L = ba_read_layout(b->K, b->P, b->E);
       BaReadJob& q = batch.j[k];
       q.K = b->K; q.P = b->P; q.E = b->E; q.prank = b->d_prank; q.iperm = b->d_iperm; q.poses = b->d_poses[b->cur]; q.pts = b->d_pts[b->cur]; q.flags = b->d_flags;
       q.out_poses = (poses && poses[i]) ? reinterpret_cast<double*>(b->h_stage) : nullptr;
-      q.out_pts = (points && points[i]) ? reinterpret_cast<double*>(b->h_stage + o_pts) : nullptr;
-      q.out_flags = (outlier_flags && outlier_flags[i]) ? reinterpret_cast<uint8_t*>(b->h_stage + o_flags) : nullptr;
+      q.out_pts = (points && points[i]) ? reinterpret_cast<double*>(b->h_stage + L.o_pts) : nullptr;
+      q.out_flags = (outlier_flags && outlier_flags[i]) ? reinterpret_cast<uint8_t*>(b->h_stage + L.o_flags) : nullptr;
       work = std::max(work, std::max(b->E / 4, 3 * b->P));
     }
     for (int k = nb; k < BA_READ_BATCH; ++k) batch.j[k] = batch.j[0];
@@ -1991,11 +1911,11 @@ extern "C" int cms_ba_read_many(cms_ba** bas, int n, double** poses, double** po
   HIPCHK(re);
   for (int i : F) {
     cms_ba* b = bas[i];
-    const size_t o_pts = ((size_t)7 * b->K * 8 + 255) & ~(size_t)255, o_flags = o_pts + (((size_t)3 * b->P * 8 + 255) & ~(size_t)255);
+    const BaReadLayout L = ba_read_layout(b->K, b->P, b->E);
     b->async_pending = false;
     if (poses && poses[i]) memcpy(poses[i], b->h_stage, 7 * (size_t)b->K * sizeof(double));
-    if (points && points[i]) memcpy(points[i], b->h_stage + o_pts, 3 * (size_t)b->P * sizeof(double));
-    if (outlier_flags && outlier_flags[i]) memcpy(outlier_flags[i], b->h_stage + o_flags, (size_t)b->E);
+    if (points && points[i]) memcpy(points[i], b->h_stage + L.o_pts, 3 * (size_t)b->P * sizeof(double));
+    if (outlier_flags && outlier_flags[i]) memcpy(outlier_flags[i], b->h_stage + L.o_flags, (size_t)b->E);
   }
   return CMS_OK;
 }
@@ -2020,9 +1940,10 @@ extern "C" int cms_ba_linearize(int device, int K, const double* poses, const ui
                                 const int8_t* e_face, double fx, double fy, double cx, double cy, int robust, double huber_delta,
                                 double* err, double* Hpp, double* bp, double* Hll, double* bl, double* Hpl, double* robust_chi2_sum) {
   cms_ba* b = nullptr;
-  ba_tl_force_host_plan = true;      // (this entry reports in the caller's order through the host-side permutations, and launches the per-key-frame linearisation)
-  int rc = cms_ba_create(&b, device, K, poses, fixed, P, points, E, e_pose, e_point, e_obs, e_invsig2, e_face, fx, fy, cx, cy);
-  ba_tl_force_host_plan = false;
+  const cms_ba_window w = {K, poses, fixed, P, points, E, e_pose, e_point, e_obs, e_invsig2, e_face, fx, fy, cx, cy, 0};
+  BaCreateOpts o;
+  o.force_host_plan = true;      // (this entry reports in the caller's order through the host-side permutations, and launches the per-key-frame linearisation)
+  int rc = ba_create(&b, device, w, o, nullptr);
   if (rc) return rc;
   if (!b->d_Hpl) {      // the window carries only the edge-major work list: the stored-block buffer this entry reports is allocated here
     rc = ba_alloc(b, &b->d_Hpl, 18 * (size_t)E);

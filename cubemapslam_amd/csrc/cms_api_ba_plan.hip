@@ -213,7 +213,7 @@ static bool ba_fast_plan_allowed(const BaKnobs& kn) {
 
 // returns 1: planned; 0: not a window for this path (the caller runs ba_plan); < 0: error (bad index)
 template <class Tick>
-static int ba_plan_fast(cms_ba* b, BaFastPlan& fp, int K, const uint8_t* fixed, int P, int E, const int* e_pose, const int* e_point, const int8_t* e_face, Tick&& tick) {
+static int ba_plan_fast(cms_ba* b, BaFastPlan& fp, int K, const uint8_t* fixed, int P, int E, const int* e_pose, const int* e_point, const int8_t* e_face, bool want_rw, Tick&& tick) {
   const BaKnobs& kn = ba_knobs();
   if (K > 64 || b->det_points || !ba_fast_plan_allowed(kn)) return 0;
   // ---- the one pass over the observations: validation, observations per point, key-frame set per point, observations per key frame
@@ -410,7 +410,7 @@ static int ba_plan_fast(cms_ba* b, BaFastPlan& fp, int K, const uint8_t* fixed, 
   for (size_t r = 0; r < runs.size(); ++r) fp.run_sig[r] = sig[runs[r].first];
   fp.n_rm = n_rm; fp.n_rmA = n_rmA; fp.n_runs = (int)runs.size(); fp.P_rm = P_rm; fp.nchunks = nchunks;
   fp.rm_cut.clear();
-  if (ba_want_rw_tables()) {
+  if (want_rw) {      // the cut points of the one-wavefront workgroups' two classes
     fp.rm_cut.assign(2 * (BA_RW_CUTS + 1), 0);
     ba_rw_make_cuts(fp.rm_cost, 0, n_rmA, fp.rm_cut.data());
     ba_rw_make_cuts(fp.rm_cost, n_rmA, n_rm, fp.rm_cut.data() + (BA_RW_CUTS + 1));
@@ -441,7 +441,7 @@ extern "C" int cms_ba_debug_plan_fast(int K, const uint8_t* fixed, int P, int E,
   std::vector<int8_t> face(E, 0);
   const bool timing = ba_knobs().create_timing;
   auto t_last = std::chrono::steady_clock::now();
-  const int rc = ba_plan_fast(b, fp, K, fixed, P, E, e_pose, e_point, face.data(), [&](const char* what) {
+  const int rc = ba_plan_fast(b, fp, K, fixed, P, E, e_pose, e_point, face.data(), ba_knobs().run_wg, [&](const char* what) {
     const auto now = std::chrono::steady_clock::now();
     if (timing) fprintf(stderr, "[cms_ba_debug_plan_fast] %s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
     t_last = now;
@@ -478,14 +478,13 @@ extern "C" int cms_ba_debug_run_fg(int K, const uint8_t* fixed, int P, int E, co
   if (K < 1 || P < 1 || E < 1 || !fixed || !e_pose || !e_point || !run_fg_out || !rm_cut_out || !counts) return cms_fail(CMS_ERR_ARG, "cms_ba_debug_run_fg: bad argument");
   for (int e = 0; e < E; ++e)
     if (e_pose[e] < 0 || e_pose[e] >= K || e_point[e] < 0 || e_point[e] >= P) return cms_fail(CMS_ERR_ARG, "cms_ba_debug_run_fg: index out of range");
-  struct Force { Force() { ba_force_rw_tables = true; } ~Force() { ba_force_rw_tables = false; } } force;
   cms_ba* b = new cms_ba;
   b->K = K; b->P = P; b->E = E;
   for (int i = 0; i < 4; ++i) counts[i] = 0;
   if (fast) {
     BaFastPlan fp;
     std::vector<int8_t> face(E, 0);
-    const int rc = ba_plan_fast(b, fp, K, fixed, P, E, e_pose, e_point, face.data(), [](const char*) {});
+    const int rc = ba_plan_fast(b, fp, K, fixed, P, E, e_pose, e_point, face.data(), true, [](const char*) {});      // (the tables whatever the knob says)
     if (rc <= 0) { delete b; counts[0] = -1; return rc < 0 ? cms_fail(CMS_ERR_ARG, "cms_ba_debug_run_fg: index out of range") : CMS_OK; }
     for (int r = 0; r < fp.n_runs; ++r) {
       BaRunSig rs;
@@ -497,7 +496,7 @@ extern "C" int cms_ba_debug_run_fg(int K, const uint8_t* fixed, int P, int E, co
     counts[0] = fp.n_runs; counts[1] = fp.n_rm; counts[2] = fp.n_rmA; counts[3] = b->np;
   } else {
     BaPlan pl;
-    ba_plan(b, pl, K, fixed, P, E, e_pose, e_point, nullptr, nullptr, nullptr, [](const char*) {});
+    ba_plan(b, pl, K, fixed, P, E, e_pose, e_point, nullptr, nullptr, nullptr, true, [](const char*) {});
     if (!pl.se_built) { delete b; counts[0] = -1; return CMS_OK; }
     if (b->n_runs > 0) memcpy(run_fg_out, pl.run_fg.data(), (size_t)b->n_runs * 64 * 24 * sizeof(uint32_t));
     if (!pl.rm_cut.empty()) memcpy(rm_cut_out, pl.rm_cut.data(), pl.rm_cut.size() * sizeof(int));

@@ -1772,6 +1772,46 @@ def _check_window(i, ba, p, st, w=None, tag="window"):
     return _ba_updates_close_or_cascade(p, poses, pts, w, tag="%s %d" % (tag, i))
 
 
+def test_ba_create_options_do_not_outlive_their_call():
+    """What a caller asks of one window's creation -- the plan kernel, pinned inputs, a set-up stream, a deferred expansion (cms_ba_create_many), the host
+    plan (cms_ba_linearize) -- is an argument of that creation and must not reach the next window the host thread builds: a cms_ba_create_many call that
+    fails half way and a cms_ba_linearize call between two creations of the same window, all on one thread; the second window equals the first (plan arrays,
+    who planned it), has a stream of its own and optimises to the oracle's result."""
+    W = synth.ba_problem(K=12, P=3000, obs_per_point=4, F=550, seed=3, views="track")
+    first = api.BundleAdjuster(W)
+    a = first.fetch_plan()
+    flagged = dict(api.pin_problem(W), _plan_on_device=True)
+    bad = dict(W); bad["e_pose"] = W["e_pose"].copy(); bad["e_pose"][7] = 99
+    with pytest.raises(api.CmsError):
+        api.ba_create_many([flagged, bad], threads=1)
+    api.ba_linearize(W)
+    second = api.BundleAdjuster(W)
+    b = second.fetch_plan()
+    assert a["n_runs"] > 0
+    for k in ("device_planned", "plan_kernel", "n_chunks", "n_rm", "n_runs", "np", "rm_points", "R_rm", "R"):
+        assert a[k] == b[k], (k, a[k], b[k])
+    for k in ("pinv", "perm", "info", "pt_off", "e_pose", "e_point", "e_face", "chunk_e0", "rm_chunk", "rm_cost", "run_mf", "run_fl"):
+        assert a[k].shape == b[k].shape and np.array_equal(a[k], b[k]), k
+    assert second.stream
+    _, st = second.optimize()
+    _check_window(0, second, W, st, tag="created after a failed group and a linearisation")
+    first.close(); second.close()
+
+
+def test_ba_pool_trim_releases_what_closed_windows_left():
+    """cms_ba_pool_trim hands the slabs and pinned blocks of closed windows back to the runtime: a closed window leaves at least its first slab (never
+    smaller than 1 MiB, see ba_alloc), a second trim finds nothing, and a window created from the emptied pool optimises to the oracle's result."""
+    api.ba_pool_trim()
+    p = synth.ba_problem(K=5, P=40, obs_per_point=3, F=550, seed=300, views="track")
+    api.BundleAdjuster(p).close()
+    assert api.ba_pool_trim() >= 1 << 20
+    assert api.ba_pool_trim() == 0
+    ba = api.BundleAdjuster(p)
+    _, st = ba.optimize()
+    _check_window(0, ba, p, st, tag="after a trim")
+    ba.close()
+
+
 def test_ba_signature_runs_config4_tracked_windows():
     """Windows whose map points are TRACKED over consecutive key frames (synth.ba_problem(views="track")): most points share their set of
     observing key frames with many others, cms_ba_create turns those sets into runs and the run-major body of kb_ba_lin_schur_runs sums their
