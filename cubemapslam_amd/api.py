@@ -459,6 +459,23 @@ class Context:
                                             C.addressof(nm)), "cms_search_by_projection")
         return match, nm.value
 
+    def search_by_projection_keyframe(self, b, pose12, kf_angle, pos, min_dist, max_dist, mp_desc, kp_mp, th=10.0, orb_dist=100, check_ori=True):
+        """ORBMatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) against frame slot b with a key frame that is not resident
+        -> (match, n_matches).  One entry per listed map point (non-NULL, not bad, not in sAlreadyFound; key-frame order): kf_angle =
+        pKF->mvKeys[i].angle, pos, min_dist, max_dist, mp_desc.  kp_mp int32 per frame key point (>= 0 = holds a map point), updated in place."""
+        a = [np.ascontiguousarray(pose12, np.float32).reshape(12), np.ascontiguousarray(kf_angle, np.float32), np.ascontiguousarray(pos, np.float32).reshape(-1, 3),
+             np.ascontiguousarray(min_dist, np.float32), np.ascontiguousarray(max_dist, np.float32), np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)]
+        n = len(a[1])
+        assert all(len(v) == n for v in a[2:])
+        assert kp_mp.dtype == np.int32 and kp_mp.flags.c_contiguous
+        match = np.full(max(n, 1), -1, np.int32); nm = C.c_int(0)
+        L = lib()
+        L.cms_search_by_projection_keyframe.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_int, C.c_int, C.c_int] +
+                                                        [C.c_void_p] * 3)
+        _chk(L.cms_search_by_projection_keyframe(self.h, b, _p(a[0]), n, *[_p(v) for v in a[1:]], float(th), int(orb_dist), int(check_ori), len(kp_mp), _p(kp_mp),
+                                                 _p(match), C.addressof(nm)), "cms_search_by_projection_keyframe")
+        return match[:n], nm.value
+
     def search_for_initialization(self, b2, k1, d1, prev_matched, window=100, nnratio=0.9, check_ori=True):
         """ORBMatcher::SearchForInitialization(F1, F2 = frame slot b2, vbPrevMatched, vnMatches12, windowSize) -> (matches12, nmatches); prev_matched
         (n1, 2) float32 is updated in place"""
@@ -582,6 +599,12 @@ class BowJob(C.Structure):
     """cms_bow_job (include/cubemapslam_hip.h)"""
     _fields_ = [("slot", C.c_int), ("b", C.c_int), ("n", C.c_int), ("nnodes", C.c_int), ("node_id", C.c_void_p), ("node_off", C.c_void_p),
                 ("node_feat", C.c_void_p), ("kf_skip", C.c_void_p)]
+
+
+class KfProjJob(C.Structure):
+    """cms_kfproj_job (include/cubemapslam_hip.h)"""
+    _fields_ = [("slot", C.c_int), ("b", C.c_int), ("n", C.c_int), ("pose12", C.c_float * 12), ("nmp", C.c_int), ("kf_feat", C.c_void_p), ("pos", C.c_void_p),
+                ("min_dist", C.c_void_p), ("max_dist", C.c_void_p), ("mp_desc", C.c_void_p), ("kp_mp", C.c_void_p), ("match", C.c_void_p)]
 
 
 def _bow_fv(fv):
@@ -760,6 +783,33 @@ class KeyframeStore:
         L.cms_kfstore_search_by_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
         _chk(L.cms_kfstore_search_by_bow(self.h, src_ctx.h, len(jobs), arr, float(nnratio), int(check_orientation), _p(kf_idx), _p(nm)), "cms_kfstore_search_by_bow")
         return [(kf_idx[off[j]:off[j + 1]].copy(), int(nm[j])) for j in range(len(jobs))]
+
+    def search_by_projection(self, src_ctx, jobs, th=10.0, orb_dist=100, check_orientation=True):
+        """cms_kfstore_search_by_projection: ORBMatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) for many (resident key frame,
+        frame) pairs as ONE launch sequence on src_ctx's stream.  jobs: list of dict(slot, b, pose12, kf_feat, pos, min_dist, max_dist, desc, kp_mp):
+        frame b of src_ctx's last batch (len(kp_mp) key points; kp_mp int32, >= 0 = holds a map point, updated in place) and the listed map points of
+        the slot's key frame (kf_feat ascending; non-NULL, not bad, not in sAlreadyFound).  Returns per job (match int32[nmp], n_matches)."""
+        arr = (KfProjJob * max(len(jobs), 1))()
+        keep = []
+        for q, j in zip(arr, jobs):
+            kp_mp = j["kp_mp"]
+            assert kp_mp.dtype == np.int32 and kp_mp.flags.c_contiguous
+            a = [np.ascontiguousarray(j["kf_feat"], np.int32), np.ascontiguousarray(j["pos"], np.float32).reshape(-1, 3), np.ascontiguousarray(j["min_dist"], np.float32),
+                 np.ascontiguousarray(j["max_dist"], np.float32), np.ascontiguousarray(j["desc"], np.uint8).reshape(-1, 32)]
+            n = len(a[0])
+            assert all(len(v) == n for v in a[1:])
+            match = np.full(max(n, 1), -1, np.int32)
+            keep.append((a, match, n))
+            q.slot = j["slot"]; q.b = j["b"]; q.n = len(kp_mp); q.nmp = n
+            q.pose12[:] = [float(v) for v in np.asarray(j["pose12"], np.float32).reshape(12)]
+            q.kf_feat, q.pos, q.min_dist, q.max_dist, q.mp_desc = (v.ctypes.data for v in a)
+            q.kp_mp = kp_mp.ctypes.data; q.match = match.ctypes.data
+        nm = np.zeros(max(len(jobs), 1), np.int32)
+        L = lib()
+        L.cms_kfstore_search_by_projection.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p]
+        _chk(L.cms_kfstore_search_by_projection(self.h, src_ctx.h, len(jobs), arr, float(th), int(orb_dist), int(check_orientation), _p(nm)),
+             "cms_kfstore_search_by_projection")
+        return [(k[1][:k[2]], int(nm[i])) for i, k in enumerate(keep)]
 
 
 def distinctive_descriptors(ctx, obs_off, desc):

@@ -15,7 +15,7 @@ extern "C" int cms_area_set_descriptors(cms_ctx* c, int b, int n, const uint8_t*
 // Which numbers a caller hands over as min_dist / max_dist of a map point: 0 (default) MapPoint::mfMinDistance / mfMaxDistance themselves
 // (private members: a binding needs two accessors), 1 the public MapPoint::GetMinDistanceInvariance() / GetMaxDistanceInvariance()
 // (MapPoint.cpp:375-385: 0.8f / 1.2f already applied) -- the reference's headers stay byte-identical.  Applies to cms_search_local_points,
-// cms_is_in_frustum_device, cms_fuse_search and cms_kfstore_fuse_search of this context.
+// cms_is_in_frustum_device, cms_fuse_search, cms_kfstore_fuse_search and the key-frame SearchByProjection entries (cms_api_reloc.hip) of this context.
 extern "C" int cms_set_distance_bounds_mode(cms_ctx* c, int scaled) {
   if (!c || scaled < 0 || scaled > 1) return cms_fail(CMS_ERR_ARG, "cms_set_distance_bounds_mode: mode must be 0 or 1");
   c->dist_bounds_scaled = scaled;
@@ -178,7 +178,7 @@ extern "C" int cms_rotation_filter_device(cms_ctx* c, int B, const void* d_mp_of
                                           void* d_n_matches, int check_orientation) {
   if (!c || B < 1 || !d_mp_off || !d_last_angle || !d_kp_mp || !d_mp_match) return cms_fail(CMS_ERR_ARG, "cms_rotation_filter_device: bad argument");
   HIPCHK(hipSetDevice(c->device));
-  CmsRotFilterArgs a;
+  CmsRotFilterArgs a = {};
   a.mp_off = (const int*)d_mp_off; a.last_angle = (const float*)d_last_angle; a.kp = (const CmsKeyPoint*)c->d_kps; a.kp_mp = (int*)d_kp_mp;
   a.mp_match = (int*)d_mp_match; a.n_matches = (int*)d_n_matches; a.check_orientation = check_orientation; a.total = nullptr; a.cap = 0;
   hipLaunchKernelGGL(k_rot_filter, dim3(B), dim3(1024), 0, c->stream, a);
@@ -230,7 +230,7 @@ extern "C" int cms_search_by_projection(cms_ctx* c, int b, const float* pose12, 
     const CmsSearchLocalArgs a = track_search_local_args(c, p + o_mpoff, p + o_desc, p + o_off, p + o_idx, p + o_pd, track_kp_mp_of_frame(c, p, o_kpmp, b), p + o_match,
                                                          nullptr, -1.0f, th_high, b, p + o_tot, cap);
     hipLaunchKernelGGL(k_search_local, dim3(1), dim3(1024), 0, s, a);
-    CmsRotFilterArgs r;
+    CmsRotFilterArgs r = {};
     r.mp_off = a.mp_off; r.last_angle = (const float*)(p + o_ang); r.kp = a.kp; r.kp_mp = a.kp_mp;
     r.mp_match = a.mp_match; r.n_matches = (int*)(p + o_nm); r.check_orientation = check_orientation; r.total = a.total; r.cap = cap;
     hipLaunchKernelGGL(k_rot_filter, dim3(1), dim3(1024), 0, s, r);

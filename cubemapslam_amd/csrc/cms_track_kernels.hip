@@ -12,6 +12,9 @@
 //                      candidates has already spoken.  Points decided in one round have disjoint free candidates, so their claims
 //                      cannot collide; the lowest undecided point always qualifies, so the loop ends.  Hamming distances of all
 //                      (point, candidate) pairs are computed once, before the rounds.
+//   k_project_last     windows of the frame-to-frame SearchByProjection (TrackWithMotionModel)
+//   k_project_keyframe windows of the key-frame SearchByProjection (Relocalization's guided search); both are followed by the window query,
+//                      k_search_local without the second-best test, and k_rot_filter
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -28,6 +31,7 @@ struct CmsFrustumArgs {
   float* qr; int* qmin; int* qmax;                                                      // window of SearchByProjection (ORBMatcher.cpp:69-75)
 };
 
+// [host-emulation begin: bounds helpers] -- tests/test_project_keyframe_emu_cpu.py compiles the text between the markers for the host
 // Scale-invariance bounds of a map point (MapPoint.cpp:375-385) and mfMaxDistance itself, from what the caller handed over
 // (cms_set_distance_bounds_mode): the raw members, or the public getters' values
 __device__ __forceinline__ void track_distance_bounds(int scaled, float min_in, float max_in, float& minDistance, float& maxDistance, float& raw_max) {
@@ -63,6 +67,32 @@ __host__ __device__ __forceinline__ int track_rays_to_cubemap(int F, float x, fl
   return face;
 }
 
+// `dist3D = cv::norm(P - Ow)` against the point's invariance bounds, shared by Frame::isInFrustum (Frame.cpp:222-231) and the key-frame
+// SearchByProjection (ORBMatcher.cpp:292-300): float difference, double sum of double squares, sqrt narrowed to float.  Returns false when the
+// distance is outside [minDistance, maxDistance]; raw_max = mfMaxDistance itself for track_predict_scale.
+// mfMaxDistance and the two invariance bounds: handed the public getters' values, the bounds are used as they are and mfMaxDistance is recovered
+// as the float r with 1.2f * r == bound (the product rounds up to two neighbouring r onto one bound when it crosses a power of two; the smaller
+// one is taken -- PredictScale can then differ from the reference only where log(ratio) / log(scale factor) sits within an ulp of an integer)
+__device__ __forceinline__ bool track_distance_in_bounds(int scaled, float min_in, float max_in, const float* PO, float& dist, float& raw_max) {
+  float maxDistance, minDistance;
+  track_distance_bounds(scaled, min_in, max_in, minDistance, maxDistance, raw_max);
+  double s = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) s = __dadd_rn(s, __dmul_rn((double)PO[k], (double)PO[k]));
+  dist = (float)sqrt(s);
+  return !(dist < minDistance || dist > maxDistance);
+}
+// MapPoint::PredictScale (MapPoint.cpp:404-419): ceil(logf(ratio) / mfLogScaleFactor); the float log is taken as the rounded double log (glibc's
+// logf is within 0.82 ulp of it; the two can only part where the quotient sits within an ulp of an integer)
+__device__ __forceinline__ int track_predict_scale(float raw_max, float dist, float log_scale, int nlevels) {
+  const float ratio = raw_max / dist;
+  const float lg = (float)log((double)ratio);
+  int ns = (int)ceilf(lg / log_scale);
+  if (ns < 0) ns = 0; else if (ns >= nlevels) ns = nlevels - 1;
+  return ns;
+}
+
+// [host-emulation end: bounds helpers]
 extern "C" __global__ void __launch_bounds__(256) k_in_frustum(CmsFrustumArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n) return;
@@ -82,30 +112,15 @@ extern "C" __global__ void __launch_bounds__(256) k_in_frustum(CmsFrustumArgs a)
     const int face = track_rays_to_cubemap(a.F, Pc[0], Pc[1], Pc[2], u, v);
     if (face < 0) break;
     if (u < 0.0f || u > mnMax || v < 0.0f || v > mnMax) break;
-    // mfMaxDistance itself (PredictScale's ratio) and the two invariance bounds.  Handed the public getters' values, the bounds are used as
-    // they are and mfMaxDistance is recovered as the float r with 1.2f * r == bound (the product rounds up to two neighbouring r onto one
-    // bound when it crosses a power of two; the smaller one is taken -- PredictScale can then differ from the reference only where
-    // log(ratio) / log(scale factor) sits within an ulp of an integer)
-    float maxd, maxDistance, minDistance;
-    track_distance_bounds(a.bounds_scaled, a.min_dist[i], a.max_dist[i], minDistance, maxDistance, maxd);
     const float PO[3] = {__fsub_rn(px, ps[12]), __fsub_rn(py, ps[13]), __fsub_rn(pz, ps[14])};
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s = __dadd_rn(s, __dmul_rn((double)PO[k], (double)PO[k]));
-    const float dist = (float)sqrt(s);
-    if (dist < minDistance || dist > maxDistance) break;
+    float maxd, dist;
+    if (!track_distance_in_bounds(a.bounds_scaled, a.min_dist[i], a.max_dist[i], PO, dist, maxd)) break;
     double d = 0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) d = __dadd_rn(d, __dmul_rn((double)PO[k], (double)a.normal[3 * (size_t)i + k]));
     vc = (float)(d / (double)dist);
     if (vc < a.viewing_cos_limit) break;
-    // MapPoint::PredictScale (MapPoint.cpp:404-419): ceil(logf(ratio) / mfLogScaleFactor); the float log is taken as the rounded
-    // double log (glibc's logf is within 0.82 ulp of it; the two can only part where the quotient sits within an ulp of an integer)
-    const float ratio = maxd / dist;
-    const float lg = (float)log((double)ratio);
-    int ns = (int)ceilf(lg / a.log_scale);
-    if (ns < 0) ns = 0; else if (ns >= a.nlevels) ns = a.nlevels - 1;
-    lvl = ns; vis = 1;
+    lvl = track_predict_scale(maxd, dist, a.log_scale, a.nlevels); vis = 1;
   } while (false);
   if (!vis) { u = -1.0f; v = -1.0f; vc = 0.0f; }
   a.in_view[i] = vis; a.proj_x[i] = u; a.proj_y[i] = v; a.level[i] = lvl; a.view_cos[i] = vc;
@@ -128,6 +143,7 @@ struct CmsSearchLocalArgs {
   int* rounds;                // per frame (optional): rounds the greedy needed
   float nnratio; int th_high;
   int frame0;                 // key-point rows of workgroup w are those of frame frame0 + w (single-frame entry point)
+  const int* wg_frame;        // optional: workgroup w searches frame wg_frame[w] instead, and kp_mp holds ONE frame row per workgroup (row w)
   const int* total; int cap;  // optional: *total > cap means the candidate lists were cut short -- do nothing, the host repeats the query
 };
 
@@ -142,7 +158,9 @@ extern "C" __global__ void __launch_bounds__(1024) k_search_local(CmsSearchLocal
   const int f = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   if (a.total && *a.total > a.cap) return;
   const int m0 = a.mp_off[f], m1 = a.mp_off[f + 1];
-  const int row0 = (f + a.frame0) * a.kp_cap;
+  const int frame = a.wg_frame ? a.wg_frame[f] : f + a.frame0;
+  const int row0 = frame * a.kp_cap;
+  int* const kp_mp = a.wg_frame ? a.kp_mp + ((ptrdiff_t)f - frame) * a.kp_cap : a.kp_mp;      // indexed by batch row, like the whole-batch array
   // ---- distances of all pairs of this frame, 4 lanes per map point
   {
     const int sub = tid & 3;
@@ -166,7 +184,7 @@ extern "C" __global__ void __launch_bounds__(1024) k_search_local(CmsSearchLocal
       if (a.mp_match[i] != -2) continue;
       for (int c = a.cand_off[i]; c < a.cand_off[i + 1]; ++c) {
         const int row = a.cand_idx[c];
-        if (a.kp_mp[row] < 0) atomicMin(&min_open[row - row0], i);
+        if (kp_mp[row] < 0) atomicMin(&min_open[row - row0], i);
       }
     }
     __syncthreads();
@@ -178,7 +196,7 @@ extern "C" __global__ void __launch_bounds__(1024) k_search_local(CmsSearchLocal
       bool ok = true;
       for (int c = a.cand_off[i]; c < a.cand_off[i + 1] && ok; ++c) {
         const int row = a.cand_idx[c];
-        ok = a.kp_mp[row] >= 0 || min_open[row - row0] == i;
+        ok = kp_mp[row] >= 0 || min_open[row - row0] == i;
       }
       if (ok) a.mp_match[i] = -3; else ++open;
     }
@@ -189,7 +207,7 @@ extern "C" __global__ void __launch_bounds__(1024) k_search_local(CmsSearchLocal
       int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestRow = -1;
       for (int c = a.cand_off[i]; c < a.cand_off[i + 1]; ++c) {
         const int row = a.cand_idx[c];
-        if (a.kp_mp[row] >= 0) continue;
+        if (kp_mp[row] >= 0) continue;
         const int dist = a.pair_dist[c];
         if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = a.kp[row].octave; bestRow = row; }
         else if (dist < bestDist2) { bestLevel2 = a.kp[row].octave; bestDist2 = dist; }
@@ -198,7 +216,7 @@ extern "C" __global__ void __launch_bounds__(1024) k_search_local(CmsSearchLocal
       // nnratio < 0: no second-best test (the frame-to-frame SearchByProjection, ORBMatcher.cpp:207)
       const bool ratio_ok = a.nnratio < 0.0f || !(bestLevel == bestLevel2 && (float)bestDist > __fmul_rn(a.nnratio, (float)bestDist2));
       if (bestDist <= a.th_high && ratio_ok) m = bestRow;
-      if (m >= 0) a.kp_mp[m] = i;
+      if (m >= 0) kp_mp[m] = i;
       a.mp_match[i] = m;
     }
     ++round;
@@ -239,6 +257,63 @@ extern "C" __global__ void __launch_bounds__(256) k_project_last(CmsProjectLastA
   a.qx[i] = u; a.qy[i] = v; a.qr[i] = r; a.qmin[i] = o - 1; a.qmax[i] = o + 1;
 }
 
+// ---- ORBMatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, th, ORBdist)
+// (src/ORBMatcher.cpp:253-378), the guided search of Tracking::Relocalization (Tracking.cpp:1101, :1115).  k_project_keyframe: one thread per
+// listed map point of every job (a job = one key frame searched in one frame row).  x3Dc = Rcw*x3Dw+tcw, zc < cosFovTh and UNKNOWN_FACE dropped
+// (:280-289), dist3D = norm(x3Dw - Ow) against the invariance bounds (:292-300), PredictScale (:302), window th * scale[level] over level - 1 ..
+// level + 1 (:305-307).  No viewing-angle test and no image-bounds test.  Ow = -Rcw.t()*tcw is derived here from the job's pose12 as the reference
+// derives it inside the function (:259; cv::gemm with a transposed operand: double accumulation, one rounding -- the arithmetic the host mirror's
+// UpdatePoseMatrices uses for mOw).  The window query, k_search_local (nnratio < 0, th_high = ORBdist) and k_rot_filter follow; the angle of the
+// key frame's key point (pKF->mvKeys[i].angle, :341) is gathered here for the latter.
+// [host-emulation begin: k_project_keyframe]
+struct CmsProjectKfArgs {
+  int n;                      // listed points of all jobs, job after job
+  const int* pt_job;          // job of every listed point
+  const float* pose12;        // per job: Rcw (9, row major) | tcw (3) of CurrentFrame.mTcw
+  const int* job_frame;       // per job: the frame row it searches
+  const int* job_kp0;         // per job: first key point of its resident key frame in kf_kp, or < 0: angles come in kf_angle
+  const CmsKeyPoint* kf_kp;   // the store's key points (NULL without a store)
+  const int* kf_feat;         // per listed point: feature index inside its key frame (resident jobs)
+  const float* kf_angle;      // per listed point: pKF->mvKeys[feature].angle (jobs without a slot; NULL if there are none)
+  const float* pos; const float* min_dist; const float* max_dist;
+  float th, cos_fov, log_scale; int nlevels, F, bounds_scaled; float sf[16];
+  int* q_frame; float* qx; float* qy; float* qr; int* qmin; int* qmax; float* angle;
+  int* level;                 // optional (debug): predicted level, -1 = dropped
+};
+extern "C" __global__ void __launch_bounds__(256) k_project_keyframe(CmsProjectKfArgs a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const int j = a.pt_job[i];
+  const float* ps = a.pose12 + 12 * (size_t)j;
+  const float p[3] = {a.pos[3 * (size_t)i], a.pos[3 * (size_t)i + 1], a.pos[3 * (size_t)i + 2]};
+  float xc[3], PO[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    float t = __fmul_rn(ps[3 * k], p[0]);
+    t = __fadd_rn(t, __fmul_rn(ps[3 * k + 1], p[1]));
+    t = __fadd_rn(t, __fmul_rn(ps[3 * k + 2], p[2]));
+    xc[k] = (float)((double)t * 1.0 + (double)ps[9 + k] * 1.0);
+    double s = 0;                                                     // Ow[k] = -(column k of Rcw) . tcw
+#pragma unroll
+    for (int r = 0; r < 3; ++r) s = __dadd_rn(s, __dmul_rn((double)ps[3 * r + k], (double)ps[9 + r]));
+    PO[k] = __fsub_rn(p[k], (float)(-1.0 * s));
+  }
+  float u = -1.0f, v = -1.0f, r = -1.0f, maxd, dist;
+  int lvl = -1;
+  if (!(xc[2] < a.cos_fov) && track_rays_to_cubemap(a.F, xc[0], xc[1], xc[2], u, v) >= 0 &&
+      track_distance_in_bounds(a.bounds_scaled, a.min_dist[i], a.max_dist[i], PO, dist, maxd)) {
+    lvl = track_predict_scale(maxd, dist, a.log_scale, a.nlevels);
+    r = __fmul_rn(a.th, a.sf[lvl]);
+  }
+  const int kp0 = a.job_kp0[j];
+  a.angle[i] = kp0 >= 0 ? a.kf_kp[(size_t)kp0 + a.kf_feat[i]].angle : a.kf_angle[i];
+  a.q_frame[i] = a.job_frame[j];
+  a.qx[i] = u; a.qy[i] = v; a.qr[i] = r; a.qmin[i] = lvl - 1; a.qmax[i] = lvl + 1;
+  if (a.level) a.level[i] = lvl;
+}
+
+// [host-emulation end: k_project_keyframe]
+
 // the rotation histogram of the matchers (ORBMatcher.cpp, HISTO_LENGTH = 12): the bin of one match, rot = angle of the reference side's key
 // point - angle of the current one, +360 when negative, round(rot * 1/12), 30 -> 0 ...
 __device__ __forceinline__ int track_rot_bin(float angle_ref, float angle_cur) {
@@ -263,6 +338,7 @@ __device__ __forceinline__ void track_three_maxima(const int* hist, int* keep) {
 struct CmsRotFilterArgs {
   const int* mp_off; const float* last_angle; const CmsKeyPoint* kp; int* kp_mp; int* mp_match; int* n_matches; int check_orientation;
   const int* total; int cap;  // as in CmsSearchLocalArgs
+  const int* wg_frame; int kp_cap;   // as in CmsSearchLocalArgs (wg_frame == NULL: kp_mp covers the whole batch)
 };
 extern "C" __global__ void __launch_bounds__(1024) k_rot_filter(CmsRotFilterArgs a) {
   __shared__ int hist[32];
@@ -271,6 +347,7 @@ extern "C" __global__ void __launch_bounds__(1024) k_rot_filter(CmsRotFilterArgs
   const int f = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   if (a.total && *a.total > a.cap) return;
   const int m0 = a.mp_off[f], m1 = a.mp_off[f + 1];
+  int* const kp_mp = a.wg_frame ? a.kp_mp + ((ptrdiff_t)f - a.wg_frame[f]) * a.kp_cap : a.kp_mp;
   if (tid < 32) hist[tid] = 0;
   if (tid == 0) s_n = 0;
   __syncthreads();
@@ -288,7 +365,7 @@ extern "C" __global__ void __launch_bounds__(1024) k_rot_filter(CmsRotFilterArgs
     if (row < 0) continue;
     if (a.check_orientation) {
       const int b = bin_of(i, row);
-      if (b != keep[0] && b != keep[1] && b != keep[2]) { a.kp_mp[row] = -1; a.mp_match[i] = -1; continue; }
+      if (b != keep[0] && b != keep[1] && b != keep[2]) { kp_mp[row] = -1; a.mp_match[i] = -1; continue; }
     }
     ++mine;
   }

@@ -424,6 +424,55 @@ int ORBMatcher::SearchByBoW(const KeyFrameView& pKF, FrameView& F, std::vector<l
   return nm;
 }
 
+int ORBMatcher::SearchByProjection(FrameView& CurrentFrame, const KeyFrameView& pKF, const std::set<long>& sAlreadyFound, float th, int ORBdist) {
+  const int N = (int)CurrentFrame.mvKeys.size(), NK = (int)pKF.mvKeys.size();
+  if (N == 0) return 0;
+  if (CurrentFrame.mTcw.rows != 4 || CurrentFrame.mTcw.cols != 4 || CurrentFrame.mTcw.type() != cv::CV_32F) throw std::runtime_error("SearchByProjection: mTcw must be 4x4 CV_32F");
+  if ((int)pKF.mvMapPoints.size() != NK) throw std::runtime_error("SearchByProjection: pKF.mvMapPoints must have one entry per key point");
+  cms_ctx* ctx = SharedContext(g_ctx_orb.nfeatures, g_ctx_orb.scale_factor, g_ctx_orb.nlevels, g_ctx_orb.ini_th_fast, g_ctx_orb.min_th_fast);
+  float pose12[12];
+  for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) pose12[3 * r + c] = CurrentFrame.mTcw.at<float>(r, c); pose12[9 + r] = CurrentFrame.mTcw.at<float>(r, 3); }
+  // the list of :268-276: a map point, not bad, not already found -- in key-point order
+  std::vector<int> feat;
+  for (int i = 0; i < NK; ++i) {
+    const long id = pKF.mvpMapPoints[i];
+    if (id < 0 || (i < (int)pKF.mvbMapPointBad.size() && pKF.mvbMapPointBad[i]) || sAlreadyFound.count(id)) continue;
+    feat.push_back(i);
+  }
+  const int M = (int)feat.size();
+  if (M == 0) return 0;
+  std::vector<float> ang(M), pos(3 * (size_t)M), dmin(M), dmax(M);
+  std::vector<uint8_t> mpd(32 * (size_t)M);
+  for (int k = 0; k < M; ++k) {
+    const MapPointView& mp = pKF.mvMapPoints[feat[k]];
+    ang[k] = pKF.mvKeys[feat[k]].angle;
+    for (int c = 0; c < 3; ++c) pos[3 * (size_t)k + c] = mp.mWorldPos.at<float>(c, 0);
+    dmin[k] = mp.mfMinDistance; dmax[k] = mp.mfMaxDistance;
+    std::memcpy(&mpd[32 * (size_t)k], mp.mDescriptor.ptr<uint8_t>(0), 32);
+  }
+  std::vector<cms_keypoint> kps(N);
+  std::vector<uint8_t> tdesc(32 * (size_t)N);
+  std::vector<int> kp_mp(N, -1), match(M, -1);
+  for (int j = 0; j < N; ++j) {
+    const cv::KeyPoint& k = CurrentFrame.mvKeys[j];
+    kps[j].x = k.pt.x; kps[j].y = k.pt.y; kps[j].size = k.size; kps[j].angle = k.angle; kps[j].response = k.response; kps[j].octave = k.octave;
+    std::memcpy(&tdesc[32 * (size_t)j], CurrentFrame.mDescriptors.ptr<uint8_t>(j), 32);
+    if (CurrentFrame.mvpMapPoints[j] >= 0) kp_mp[j] = 0x40000000;      // any map point (:320), no Observations() test
+  }
+  int nm = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    int rc = cms_area_set_keypoints(ctx, 0, N, kps.data());
+    if (rc == CMS_OK) rc = cms_area_set_descriptors(ctx, 0, N, tdesc.data());
+    if (rc == CMS_OK) rc = cms_area_grid(ctx, 1);
+    if (rc == CMS_OK) rc = cms_search_by_projection_keyframe(ctx, 0, pose12, M, ang.data(), pos.data(), dmin.data(), dmax.data(), mpd.data(), th, ORBdist,
+                                                            mbCheckOrientation ? 1 : 0, N, kp_mp.data(), match.data(), &nm);
+    if (rc != CMS_OK) throw std::runtime_error(std::string("cms_search_by_projection_keyframe: ") + cms_last_error());
+  }
+  for (int k = 0; k < M; ++k) if (match[k] >= 0) CurrentFrame.mvpMapPoints[match[k]] = pKF.mvpMapPoints[feat[k]];
+  return nm;
+}
+
 int ORBMatcher::SearchByProjection(FrameView& Cur, const FrameView& Last, float th, bool) {
   const int N2 = (int)Cur.mvKeys.size();
   if (!Last.mvMapPointPos.empty() && Cur.mTcw.rows == 4 && Cur.mTcw.cols == 4 && N2 > 0) {

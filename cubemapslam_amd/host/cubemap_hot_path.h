@@ -17,6 +17,7 @@
 #ifndef CMS_CUBEMAP_HOT_PATH_H
 #define CMS_CUBEMAP_HOT_PATH_H
 #include <string>
+#include <set>
 #include <vector>
 #include "cubemapslam_hip.h"
 #include "mini_cv.h"
@@ -143,6 +144,12 @@ class ORBMatcher {
   // node, best / second best with mfNNratio, a frame feature taken once, rotation histogram.  vpMapPointMatches[i] = id of the map point frame key
   // point i receives, or -1; returns nmatches.  (cms_search_by_bow: F's key points and descriptors go to the device first)
   int SearchByBoW(const KeyFrameView& pKF, FrameView& F, std::vector<long>& vpMapPointMatches);
+  // ORBMatcher.cpp:253-378, Tracking.cpp:1101 / :1115 (Relocalization's guided search): the map points of pKF that are not bad and not in
+  // sAlreadyFound (ids), in key-point order (:268-276), projected with CurrentFrame.mTcw; windows th * scale[predicted level] over level +-1, key
+  // points that hold a map point skipped, best Hamming <= ORBdist, rotation histogram with pKF's key-point angles.  Reads pKF.mvMapPoints for the
+  // points' position, distances and descriptor.  Fills CurrentFrame.mvpMapPoints with the matched ids, returns nmatches.
+  // (cms_search_by_projection_keyframe: the frame's key points and descriptors go to the device first)
+  int SearchByProjection(FrameView& CurrentFrame, const KeyFrameView& pKF, const std::set<long>& sAlreadyFound, float th, int ORBdist);
   static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 12;
 
  protected:
@@ -208,6 +215,9 @@ struct KeyFrameView {
   cv::Mat Tcw;                                           // 4x4 CV_32F
   std::vector<std::pair<unsigned, std::vector<unsigned>>> mFeatVec;   // ascending node id
   float medianDepth = 1.0f;                              // ComputeSceneMedianDepth(2)
+  // per key point with mvpMapPoints[i] >= 0: what SearchByProjection(Frame&, KeyFrame*, ...) reads of that map point (GetWorldPos, GetDescriptor,
+  // mfMinDistance / mfMaxDistance); empty for the callers that do not need it
+  std::vector<MapPointView> mvMapPoints;
 };
 struct NewMapPoint { int neighbour; int idx1, idx2; cv::Vec3f x3D; };
 

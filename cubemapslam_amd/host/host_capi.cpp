@@ -258,6 +258,42 @@ extern "C" int hm_search_by_bow(int nk, const cms_keypoint* kk, const uint8_t* k
     for (int i = 0; i < n; ++i) out_mp[i] = m[i];
     return nm;)
 }
+// ORBMatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) through the mirror: the key frame (nk key points, map-point ids mp
+// (-1 = none), bad flags or NULL, and per key point the map point's position / mfMinDistance / mfMaxDistance / descriptor), sAlreadyFound as nfound
+// ids, the frame (n key points, frame_mp[n] = mvpMapPoints as ids, in/out) and its pose Tcw (16 floats, row major)
+extern "C" int hm_search_by_projection_keyframe(int nk, const cms_keypoint* kk, const long* mp, const uint8_t* bad, const float* mp_pos, const float* mp_min,
+                                                const float* mp_max, const uint8_t* mp_desc, int nfound, const long* found, int n, const cms_keypoint* fk,
+                                                const uint8_t* fd, long* frame_mp, float* Tcw, float th, int orb_dist, int check_ori) {
+  HM_TRY(
+    KeyFrameView kf;
+    FrameView f;
+    kf.mvKeys.resize(nk); kf.mvMapPoints.resize(nk);
+    kf.mvpMapPoints.assign(mp, mp + nk);
+    if (bad) kf.mvbMapPointBad.assign(bad, bad + nk);
+    for (int i = 0; i < nk; ++i) {
+      kf.mvKeys[i].pt = cv::Point2f(kk[i].x, kk[i].y); kf.mvKeys[i].angle = kk[i].angle; kf.mvKeys[i].octave = kk[i].octave;
+      MapPointView& v = kf.mvMapPoints[i];
+      v.mnId = mp[i]; v.mfMinDistance = mp_min[i]; v.mfMaxDistance = mp_max[i];
+      v.mWorldPos.create(3, 1, cv::CV_32F);
+      for (int c = 0; c < 3; ++c) v.mWorldPos.at<float>(c, 0) = mp_pos[3 * (size_t)i + c];
+      v.mDescriptor.create(1, 32, cv::CV_8U);
+      std::memcpy(v.mDescriptor.ptr<uint8_t>(0), mp_desc + 32 * (size_t)i, 32);
+    }
+    f.mvKeys.resize(n);
+    f.mDescriptors.create(n > 0 ? n : 1, 32, cv::CV_8U);
+    for (int i = 0; i < n; ++i) {
+      f.mvKeys[i].pt = cv::Point2f(fk[i].x, fk[i].y); f.mvKeys[i].angle = fk[i].angle; f.mvKeys[i].octave = fk[i].octave; f.mvKeys[i].size = fk[i].size;
+      f.mvKeys[i].response = fk[i].response;
+      std::memcpy(f.mDescriptors.ptr<uint8_t>(i), fd + (size_t)i * 32, 32);
+    }
+    f.mvpMapPoints.assign(frame_mp, frame_mp + n);
+    f.mTcw = cv::Mat(4, 4, cv::CV_32F, Tcw, 16);
+    const std::set<long> sFound(found, found + nfound);
+    ORBMatcher matcher(0.9f, check_ori != 0);
+    const int nm = matcher.SearchByProjection(f, kf, sFound, th, orb_dist);
+    for (int i = 0; i < n; ++i) frame_mp[i] = f.mvpMapPoints[i];
+    return nm;)
+}
 // LocalMapping::CreateNewMapPoints through the mirror: key frame 0 is the current one, 1..nkf-1 its neighbours.  Flat inputs:
 // feat_off[nkf+1]; per feature kps/desc/rays/mp; Tcw nkf x 16; FeatureVector per key frame as node_off2[nkf+1] into (node_id, node_cnt)
 // and the features of the nodes concatenated in node_feat; median_depth[nkf].  Outputs up to cap records.

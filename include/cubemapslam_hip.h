@@ -348,7 +348,7 @@ int cms_features_in_area_batch_device(cms_ctx* ctx, int nq, const void* d_qframe
  * takes every 1024th point of its frame). */
 int cms_area_set_descriptors(cms_ctx* ctx, int b, int n, const uint8_t* desc);
 /* What the caller hands over as min_dist / max_dist of a map point (cms_search_local_points, cms_is_in_frustum_device, cms_fuse_search,
- * cms_kfstore_fuse_search of this context): scaled = 0 (default) MapPoint::mfMinDistance / mfMaxDistance themselves -- private members, a binding
+ * cms_kfstore_fuse_search, cms_search_by_projection_keyframe and, for the frame context, cms_kfstore_search_by_projection of this context): scaled = 0 (default) MapPoint::mfMinDistance / mfMaxDistance themselves -- private members, a binding
  * needs two one-line accessors; scaled = 1 the public MapPoint::GetMinDistanceInvariance() / GetMaxDistanceInvariance() (src/MapPoint.cpp:375-385:
  * 0.8f / 1.2f already applied), so that the reference's headers stay byte-identical.  With scaled = 1 the bounds of Frame::isInFrustum / Fuse
  * are exactly the getters' values; mfMaxDistance (the numerator of MapPoint::PredictScale, :387-419) is recovered as the float r with
@@ -511,6 +511,47 @@ typedef struct {
 } cms_bow_job;
 int cms_kfstore_search_by_bow(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_job* jobs, float nnratio,
                               int check_orientation, int* kf_idx /* sum of jobs[j].n, job after job */, int* n_matches /* njobs */);
+
+/* ---- ORBMatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, const float th, const int ORBdist)
+ * (include/ORBMatcher.h:64, src/ORBMatcher.cpp:253-378), the guided search of Tracking::Relocalization: twice per accepted PnP pose
+ * (src/Tracking.cpp:1101 with th 10 / ORBdist 100, :1115 with th 3 / ORBdist 64), between the PoseOptimization calls (cms_pose_*) and behind the candidate
+ * loop (cms_kfstore_search_by_bow).  The caller lists, in the order of pKF->GetMapPointMatches() (:268-276), the key frame's map points that are non-NULL,
+ * not bad and not in sAlreadyFound: kf_feat (their key-frame feature indices, strictly ascending -- the order decides the greedy), pos = GetWorldPos(),
+ * min_dist / max_dist as cms_set_distance_bounds_mode says (default: mfMinDistance / mfMaxDistance), mp_desc = GetDescriptor().  Per listed point:
+ * x3Dc = Rcw*x3Dw+tcw; dropped when zc < cosFovTh, on UNKNOWN_FACE, or when dist3D = norm(x3Dw - Ow) is outside the invariance bounds (there is no
+ * viewing-angle test and no image-bounds test); PredictScale; window th * mvScaleFactors[level] over levels level - 1 .. level + 1; candidates in
+ * GetFeaturesInArea's order, key points with kp_mp >= 0 skipped (CurrentFrame.mvpMapPoints[i2] != NULL: ANY map point, no Observations() test), first
+ * strict minimum, accepted when bestDist <= ORBdist (no second-best test); an accepted key point is taken for all later entries; then the rotation
+ * histogram over pKF->mvKeys[i].angle - CurrentFrame.mvKeys[bestIdx2].angle when check_orientation (ComputeThreeMaxima, :905-946).
+ * pose12 = Rcw (9 floats, row major) | tcw (3) of CurrentFrame.mTcw.  Ow is derived from it on the device exactly as :259 does (-Rcw.t()*tcw: cv::gemm
+ * with a transposed operand accumulates in double and rounds once) -- the caller hands no camera centre over.
+ * kp_mp: one int per key point of the frame, in/out: >= 0 on entry <=> CurrentFrame.mvpMapPoints[i] != NULL; a new match stores the index into the
+ * job's list; a match the histogram removes is back to -1.  n (nkp) is the row's key-point count: key points of the row from n on count as free, and a
+ * match with one of them is reported in match[] but has no entry in kp_mp.  match[k] = frame key point of listed point k or -1 (after the histogram); n_matches =
+ * nmatches as returned by the reference.  The frame is row b of the context's last batch (cms_frames_process, or cms_area_set_keypoints +
+ * cms_area_set_descriptors; cms_area_grid first).  Limit: kp_cap <= 4096 as for the sibling greedy searches (CMS_ERR_UNSUPPORTED); any number of
+ * listed points.  Synchronous: Tracking decides on nGood + nadditional at once.
+ * cms_kfstore_search_by_projection: resident key frames, many (key frame, frame) pairs -- one lost camera stream each -- as ONE launch sequence on
+ * src's stream: one upload, projection, window query, greedy, histogram, one read-back.  The slot supplies mvKeys[].angle and the feature count.
+ * Two jobs naming the same frame row are CMS_ERR_ARG (the reference's second call sees the first one's matches and another pose), so are kf_feat that
+ * do not strictly ascend or reach the slot's feature count.  nmp == 0: zero matches, kp_mp untouched.  Stream rule as cms_kfstore_search_by_bow:
+ * nothing is enqueued on the store's stream; src's stream waits on the device for the cms_kfstore_put_from_frame(s) copies that filled the named slots.
+ * cms_search_by_projection_keyframe: one pair with a key frame that is not resident; kf_angle[k] = pKF->mvKeys[kf_feat[k]].angle from the caller. */
+typedef struct {
+  int slot;                  /* resident key frame */
+  int b, n;                  /* frame: row b of src's last batch, n key points */
+  float pose12[12];          /* Rcw | tcw of CurrentFrame.mTcw */
+  int nmp;                   /* listed map points */
+  const int* kf_feat;        /* nmp key-frame feature indices, strictly ascending */
+  const float* pos; const float* min_dist; const float* max_dist; const uint8_t* mp_desc;   /* per listed point (pos: 3 floats, mp_desc: 32 bytes) */
+  int* kp_mp;                /* n ints, in/out */
+  int* match;                /* nmp ints, out */
+} cms_kfproj_job;
+int cms_kfstore_search_by_projection(cms_kfstore* st, cms_ctx* src, int njobs, const cms_kfproj_job* jobs, float th, int orb_dist,
+                                     int check_orientation, int* n_matches /* njobs */);
+int cms_search_by_projection_keyframe(cms_ctx* ctx, int b, const float* pose12, int nmp, const float* kf_angle, const float* pos,
+                                      const float* min_dist, const float* max_dist, const uint8_t* mp_desc, float th, int orb_dist,
+                                      int check_orientation, int nkp, int* kp_mp, int* match, int* n_matches);
 
 /* ---- pose-only optimisation: Optimizer::PoseOptimization(Frame*) (src/Optimizer.cpp:48-190), the per-frame solver Tracking calls
  * 1-3 times per frame (Tracking.cpp:585,647,688).  Edge = EdgeSE3ProjectXYZMultiPinholeOnlyPose

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <set>
 #include <mutex>
 #include <stdexcept>
 
@@ -546,5 +547,58 @@ int SearchByBoW(cms_kfstore* store, cms_ctx* frameCtx, KeyFrame* pKF, Frame& F, 
   SearchByBoWCandidates(store, frameCtx, one, F, m, discarded, n, nnratio, checkOri);
   vpMapPointMatches = m[0].empty() ? std::vector<MapPoint*>(F.N, static_cast<MapPoint*>(NULL)) : m[0];
   return n[0];
+}
+
+// ------------------------------------------------------------------------------------------------ Tracking::Relocalization: the guided search
+int SearchByProjection(cms_kfstore* store, cms_ctx* frameCtx, Frame& CurrentFrame, KeyFrame* pKF, const std::set<MapPoint*>& sAlreadyFound, float th, int ORBdist,
+                       bool checkOri) {
+  // the list of ORBMatcher.cpp:268-276: the key frame's map points that are not bad and not already found, in key-point order
+  const std::vector<MapPoint*> vpMPs = pKF->GetMapPointMatches();
+  std::vector<int> feat;
+  std::vector<MapPoint*> pts;
+  for (size_t i = 0; i < vpMPs.size(); ++i) {
+    MapPoint* pMP = vpMPs[i];
+    if (!pMP || pMP->isBad() || sAlreadyFound.count(pMP)) continue;
+    feat.push_back((int)i); pts.push_back(pMP);
+  }
+  const int n = (int)pts.size();
+  if (n == 0) return 0;
+  std::vector<float> pos((size_t)n * 3), dmin(n), dmax(n), angle(n);
+  std::vector<uint8_t> desc((size_t)n * 32);
+  for (int k = 0; k < n; ++k) {
+    const cv::Mat x = pts[k]->GetWorldPos();
+    for (int c = 0; c < 3; ++c) pos[3 * (size_t)k + c] = x.at<float>(c);
+    dmin[k] = pts[k]->GetMinDistanceInvariance();                  // the public getters: frameCtx is in cms_set_distance_bounds_mode(ctx, 1) like every context
+    dmax[k] = pts[k]->GetMaxDistanceInvariance();                  // the bridge sets up
+    const cv::Mat d = pts[k]->GetDescriptor();
+    std::memcpy(&desc[(size_t)k * 32], d.data, 32);
+    angle[k] = pKF->mvKeys[feat[k]].angle;
+  }
+  const int N = CurrentFrame.N;
+  std::vector<int> kp_mp(N), match(n, -1);
+  for (int i = 0; i < N; ++i) kp_mp[i] = CurrentFrame.mvpMapPoints[i] ? (1 << 30) : -1;      // any map point (:320): no Observations() test here
+  int nm = 0;
+  StoreBook& b = book(store);
+  {
+    // locked from the look-up to the end of the device call, like SearchByBoWCandidates
+    std::lock_guard<std::mutex> lk(b.mu);
+    const int slot = slot_locked(b, pKF);
+    if (slot >= 0) {
+      cms_kfproj_job q;
+      q.slot = slot; q.b = 0; q.n = N;
+      for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) q.pose12[3 * r + c] = CurrentFrame.mTcw.at<float>(r, c); q.pose12[9 + r] = CurrentFrame.mTcw.at<float>(r, 3); }
+      q.nmp = n; q.kf_feat = feat.data(); q.pos = pos.data(); q.min_dist = dmin.data(); q.max_dist = dmax.data(); q.mp_desc = desc.data();
+      q.kp_mp = kp_mp.data(); q.match = match.data();
+      check(cms_kfstore_search_by_projection(store, frameCtx, 1, &q, th, ORBdist, checkOri ? 1 : 0, &nm), "cms_kfstore_search_by_projection");
+    } else {
+      // a key frame that never entered the store: its key-point angles travel with the call
+      float pose12[12];
+      for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) pose12[3 * r + c] = CurrentFrame.mTcw.at<float>(r, c); pose12[9 + r] = CurrentFrame.mTcw.at<float>(r, 3); }
+      check(cms_search_by_projection_keyframe(frameCtx, 0, pose12, n, angle.data(), pos.data(), dmin.data(), dmax.data(), desc.data(), th, ORBdist, checkOri ? 1 : 0, N,
+                                              kp_mp.data(), match.data(), &nm), "cms_search_by_projection_keyframe");
+    }
+  }
+  for (int k = 0; k < n; ++k) if (match[k] >= 0) CurrentFrame.mvpMapPoints[match[k]] = pts[k];      // :336 (what the histogram removed is -1 again: :370)
+  return nm;
 }
 }  // namespace Hip

@@ -3,6 +3,7 @@
 // Not built in this repository (syntax-checked against the reference's headers by tests/test_integration_syntax.py), see integration/README.md.  Each function is the new body of the reference function it names.
 #ifndef CUBEMAP_HIP_BRIDGE_H
 #define CUBEMAP_HIP_BRIDGE_H
+#include <set>
 #include <vector>
 #include <opencv2/opencv.hpp>
 #include "cubemapslam_hip.h"
@@ -73,5 +74,13 @@ int SearchByBoW(cms_kfstore* store, cms_ctx* frameCtx, KeyFrame* pKF, Frame& F, 
 void SearchByBoWCandidates(cms_kfstore* store, cms_ctx* frameCtx, const std::vector<KeyFrame*>& vpCandidateKFs, Frame& F,
                            std::vector<std::vector<MapPoint*> >& vvpMapPointMatches, std::vector<bool>& vbDiscarded, std::vector<int>& nmatches,
                            float nnratio, bool checkOri);
+// ---- Tracking::Relocalization's guided search, ORBMatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBMatcher.cpp:253-378;
+// Tracking.cpp:1101 with th 10 / ORBdist 100, :1115 with th 3 / ORBdist 64), on the FRAME thread: CurrentFrame is the frame `frameCtx` extracted last
+// (slot 0 of its batch, cms_area_grid done) with the pose PnP / PoseOptimization left in mTcw.  The key frame's slot comes from the store's
+// KeyFrame* -> slot book and supplies the key-point angles; a key frame that is not resident goes through cms_search_by_projection_keyframe with the
+// angles from the host.  Fills CurrentFrame.mvpMapPoints like the reference and returns nmatches.  Between the two calls the PoseOptimization calls
+// are Hip::PoseOptimization; PnPsolver is the one step of Relocalization that stays on the host.
+int SearchByProjection(cms_kfstore* store, cms_ctx* frameCtx, Frame& CurrentFrame, KeyFrame* pKF, const std::set<MapPoint*>& sAlreadyFound, float th, int ORBdist,
+                       bool checkOri);
 }  // namespace Hip
 #endif
