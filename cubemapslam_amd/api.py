@@ -1162,3 +1162,114 @@ def pose_optimize(prob, n=None, device=0):
     _chk(lib().cms_pose_optimize(device, n, _p(Xw), _p(obs), _p(inv), _p(face), prob["fx"], prob["fy"], prob["cx"], prob["cy"],
                                  _p(pose), _p(out), _p(ninl), C.byref(st)), "cms_pose_optimize")
     return int(ninl[0]), pose, out[:n], st
+
+
+class PnpJob(C.Structure):
+    """cms_pnp_job (include/cubemapslam_hip.h)"""
+    _fields_ = [("N", C.c_int), ("p3d", C.c_void_p), ("p2d", C.c_void_p), ("bearing", C.c_void_p), ("sigma2", C.c_void_p), ("kp_idx", C.c_void_p),
+                ("b", C.c_int), ("n", C.c_int), ("th2", C.c_float), ("min_inliers", C.c_int), ("max_its", C.c_int), ("min_set", C.c_int),
+                ("n_iterations", C.c_int), ("n_draws", C.c_int), ("draws", C.c_void_p), ("iterations", C.c_int), ("best_inliers", C.c_int),
+                ("best_Tcw", C.c_float * 12), ("best_mask", C.c_void_p), ("status", C.c_int), ("no_more", C.c_int), ("n_inliers", C.c_int),
+                ("iterations_run", C.c_int), ("Tcw", C.c_float * 12), ("inliers", C.c_void_p)]
+
+
+def ransac_parameters(N, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4):
+    """cms_pnp_ransac_parameters: PnPsolver::SetRansacParameters without the per-point part -> (min_inliers, max_its, epsilon)"""
+    mi, it, ep = C.c_int(), C.c_int(), C.c_float()
+    L = lib()
+    L.cms_pnp_ransac_parameters.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    _chk(L.cms_pnp_ransac_parameters(int(N), float(probability), int(min_inliers), int(max_iterations), int(min_set), float(epsilon), C.byref(mi), C.byref(it),
+                                     C.byref(ep)), "cms_pnp_ransac_parameters")
+    return mi.value, it.value, ep.value
+
+
+def pnp_job_state(prob, n_iterations, draws, th2=5.991, min_set=4):
+    """The arrays of one PnPsolver as a dict a PnpJob points into: prob has p3d (N x 3), p2d (N x 2), bearing (N x 3), sigma2 (N), min_inliers,
+    max_its, and optionally the state carried from an earlier call (iterations, best_inliers, best_Tcw, best_mask).  draws: 4 ints per iteration."""
+    N = len(prob["p3d"])
+    f32 = lambda a, shape: np.ascontiguousarray(np.asarray(a, np.float32).reshape(shape))
+    s = dict(N=N, p3d=f32(prob["p3d"], (N, 3)), p2d=f32(prob["p2d"], (N, 2)), bearing=f32(prob["bearing"], (N, 3)), sigma2=f32(prob["sigma2"], (N,)),
+             draws=np.ascontiguousarray(np.asarray(draws, np.int32).ravel()), th2=float(th2), min_inliers=int(prob["min_inliers"]), max_its=int(prob["max_its"]),
+             min_set=int(min_set), n_iterations=int(n_iterations), iterations=int(prob.get("iterations", 0)), best_inliers=int(prob.get("best_inliers", 0)),
+             best_Tcw=np.array(prob.get("best_Tcw", np.zeros(12)), np.float32).ravel().copy(),
+             best_mask=np.array(prob.get("best_mask", np.zeros(N)), np.uint8).ravel().copy(), inliers=np.zeros(max(N, 1), np.uint8))
+    if len(s["best_mask"]) == 0:
+        s["best_mask"] = np.zeros(1, np.uint8)
+    return s
+
+
+def pnp_jobs(states):
+    """(PnpJob * n) over pnp_job_state() dicts; the dicts own the memory"""
+    arr = (PnpJob * len(states))()
+    for q, s in zip(arr, states):
+        q.N = s["N"]; q.p3d = _p(s["p3d"]); q.p2d = _p(s["p2d"]); q.bearing = _p(s["bearing"]); q.sigma2 = _p(s["sigma2"])
+        q.kp_idx = _p(s["kp_idx"]) if s.get("kp_idx") is not None else None; q.b = int(s.get("b", 0)); q.n = int(s.get("n", 0))
+        q.th2 = s["th2"]; q.min_inliers = s["min_inliers"]; q.max_its = s["max_its"]; q.min_set = s["min_set"]; q.n_iterations = s["n_iterations"]
+        q.n_draws = len(s["draws"]); q.draws = _p(s["draws"]) if len(s["draws"]) else None
+        q.iterations = s["iterations"]; q.best_inliers = s["best_inliers"]; q.best_Tcw[:] = [float(v) for v in s["best_Tcw"]]; q.best_mask = _p(s["best_mask"])
+        q.inliers = _p(s["inliers"])
+    return arr
+
+
+def pnp_results(arr, states):
+    """What a call left in the job records, one dict per job (arrays copied)"""
+    out = []
+    for q, s in zip(arr, states):
+        N = s["N"]
+        out.append(dict(status=q.status, no_more=q.no_more, n_inliers=q.n_inliers, iterations=q.iterations, iterations_run=q.iterations_run,
+                        best_inliers=q.best_inliers, Tcw=np.array(q.Tcw[:], np.float32), best_Tcw=np.array(q.best_Tcw[:], np.float32),
+                        inliers=s["inliers"][:N].copy(), best_mask=s["best_mask"][:N].copy()))
+    return out
+
+
+def pnp_first_difference(want, got):
+    """Two lists of result dicts compared bit for bit (arrays by their bytes, so NaN equals NaN): None, or (job, key, wanted, got) of the first difference"""
+    for j, (w, g) in enumerate(zip(want, got)):
+        for k in w:
+            a, b = w[k], g[k]
+            if isinstance(a, np.ndarray):
+                a = np.ascontiguousarray(a); b = np.ascontiguousarray(b)
+                if a.shape != b.shape or a.dtype != b.dtype or a.tobytes() != b.tobytes():
+                    return j, k, a, b
+            elif a != b:
+                return j, k, a, b
+    return None
+
+
+class PnPSolver:
+    """PnPsolver::iterate for many solvers in one launch sequence (cms_pnp_*).  jobs: a (PnpJob * n) array, e.g. from pnp_jobs()."""
+
+    def __init__(self, max_jobs, max_corr_total, max_hyp_total, device=0):
+        self.h = C.c_void_p()
+        L = lib()
+        L.cms_pnp_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.cms_pnp_destroy.argtypes = [C.c_void_p]
+        L.cms_pnp_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _chk(L.cms_pnp_create(C.byref(self.h), device, max_jobs, max_corr_total, max_hyp_total), "cms_pnp_create")
+
+    def close(self):
+        if self.h:
+            lib().cms_pnp_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def iterate(self, ctx, jobs):
+        _chk(lib().cms_pnp_iterate(self.h, ctx.h, len(jobs), jobs), "cms_pnp_iterate")
+        return jobs
+
+    def iterate_frames(self, ctx, jobs):
+        """cms_pnp_iterate_frames: p2d / bearing / sigma2 gathered on the device from row b of ctx's last batch through kp_idx"""
+        lib().cms_pnp_iterate_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _chk(lib().cms_pnp_iterate_frames(self.h, ctx.h, len(jobs), jobs), "cms_pnp_iterate_frames")
+        return jobs
+
+    def run(self, ctx, states, frames=False):
+        """One call over pnp_job_state() dicts -> one result dict per job (the states' in/out arrays are updated in place)"""
+        arr = pnp_jobs(states)
+        (self.iterate_frames if frames else self.iterate)(ctx, arr)
+        return pnp_results(arr, states)

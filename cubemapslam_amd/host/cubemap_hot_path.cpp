@@ -745,4 +745,78 @@ void Optimizer::LocalBundleAdjustment(LocalBAWindow* win, bool* pbStopFlag) {
     for (int i = 0; i < 3; ++i) win->mappoints[p].Xw.at<float>(i, 0) = (float)points[3 * p + i];
 }
 
+
+// ------------------------------------------------------------------------------------------------ PnPsolver (src/PnPsolver.cpp)
+extern "C" int hm_pnp_iterate_host(int F, int njobs, cms_pnp_job* jobs);      // pnp_host.cpp: the host build of csrc/cms_pnp_core.h
+
+PnPsolver::PnPsolver(const FrameView& F, const std::vector<long>& vpMapPointMatches) {
+  nMatches_ = vpMapPointMatches.size();
+  for (size_t i = 0, iend = vpMapPointMatches.size(); i < iend; i++) {      // :83-108
+    if (vpMapPointMatches[i] < 0) continue;                                  // pMP == NULL
+    if (!F.mvbMapPointBad.empty() && F.mvbMapPointBad[i]) continue;          // pMP->isBad()
+    const cv::KeyPoint& kp = F.mvKeys[i];
+    mvP2D.push_back(kp.pt);
+    mvSigma2.push_back(F.mvLevelSigma2[kp.octave]);
+    mvBearings.push_back(F.mvKeyRays[i]);
+    mvP3Dw.push_back(F.mvMapPointPos[i]);
+    mvKeyPointIndices.push_back(i);
+  }
+  draw = [](int min, int max) { const int d = max - min + 1; return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min; };
+  SetRansacParameters();
+}
+
+void PnPsolver::SetRansacParameters(double probability, int minInliers, int maxIterations, int minSet, float epsilon, float th2) {
+  N = (int)mvBearings.size();
+  mRansacMinSet = minSet; mRansacTh2 = th2;
+  if (cms_pnp_ransac_parameters(N, probability, minInliers, maxIterations, minSet, epsilon, &mRansacMinInliers, &mRansacMaxIts, &mRansacEpsilon))
+    throw std::runtime_error(std::string("cms_pnp_ransac_parameters: ") + cms_last_error());
+  mvbBestInliers.assign((size_t)N, 0);
+}
+
+cv::Mat PnPsolver::find(std::vector<bool>& vbInliers, int& nInliers) {
+  bool bFlag;
+  return iterate(mRansacMaxIts, bFlag, vbInliers, nInliers);
+}
+
+cv::Mat PnPsolver::iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+  bNoMore = false; vbInliers.clear(); nInliers = 0;
+  if (N < mRansacMinInliers) { bNoMore = true; return cv::Mat(); }      // :175-179
+  const int H = std::max(std::max(mRansacMaxIts - mnIterations, nIterations), 0);
+  std::vector<int> draws((size_t)H * 4);
+  for (int i = 0; i < H; ++i)
+    for (int k = 0; k < 4; ++k) draws[(size_t)i * 4 + k] = draw(0, N - k - 1);      // RandomInt(0, vAvailableIndices.size()-1), :195
+  std::vector<uint8_t> inliers((size_t)N + 1, 0);
+  mvbBestInliers.resize((size_t)N + 1, 0);
+  cms_pnp_job q = {};
+  q.N = N; q.p3d = N ? &mvP3Dw[0](0) : nullptr; q.p2d = N ? &mvP2D[0].x : nullptr; q.bearing = N ? &mvBearings[0](0) : nullptr; q.sigma2 = mvSigma2.data();
+  q.th2 = mRansacTh2; q.min_inliers = mRansacMinInliers; q.max_its = mRansacMaxIts; q.min_set = mRansacMinSet; q.n_iterations = nIterations;
+  q.n_draws = (int)draws.size(); q.draws = draws.data();
+  q.iterations = mnIterations; q.best_inliers = mnBestInliers; std::memcpy(q.best_Tcw, mBestTcw, sizeof(mBestTcw)); q.best_mask = mvbBestInliers.data();
+  q.inliers = inliers.data();
+  if (engine == HOST_CORE) {
+    const int rc = hm_pnp_iterate_host(CamModelGeneral::GetCamera()->GetCubeFaceWidth(), 1, &q);
+    if (rc) throw std::runtime_error("PnPsolver::iterate: the job was refused (" + std::to_string(rc) + ")");
+  } else {
+    cms_ctx* ctx = SharedContext(g_ctx_orb.nfeatures > 0 ? g_ctx_orb.nfeatures : 1000, g_ctx_orb.nfeatures > 0 ? g_ctx_orb.scale_factor : 1.2f,
+                                 g_ctx_orb.nfeatures > 0 ? g_ctx_orb.nlevels : 8, g_ctx_orb.nfeatures > 0 ? g_ctx_orb.ini_th_fast : 20,
+                                 g_ctx_orb.nfeatures > 0 ? g_ctx_orb.min_th_fast : 7);
+    cms_pnp* h = nullptr;
+    if (cms_pnp_create(&h, 0, 1, std::max(N, 1), std::max(H, 1))) throw std::runtime_error(std::string("cms_pnp_create: ") + cms_last_error());
+    const int rc = cms_pnp_iterate(h, ctx, 1, &q);
+    cms_pnp_destroy(h);
+    if (rc) throw std::runtime_error(std::string("cms_pnp_iterate: ") + cms_last_error());
+  }
+  mnIterations = q.iterations; mnBestInliers = q.best_inliers; std::memcpy(mBestTcw, q.best_Tcw, sizeof(mBestTcw));
+  bNoMore = q.no_more != 0;
+  if (q.status == 0) return cv::Mat();
+  nInliers = q.n_inliers;
+  vbInliers = std::vector<bool>(nMatches_, false);      // :232-237, :250-255
+  for (int i = 0; i < N; i++)
+    if (inliers[(size_t)i]) vbInliers[mvKeyPointIndices[(size_t)i]] = true;
+  cv::Mat Tcw(4, 4, cv::CV_32F);
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 4; ++c) Tcw.at<float>(r, c) = r < 3 ? (c < 3 ? q.Tcw[3 * r + c] : q.Tcw[9 + r]) : (c == 3 ? 1.0f : 0.0f);
+  return Tcw;
+}
+
 }  // namespace CubemapSLAM

@@ -16,6 +16,7 @@
 // fields those methods read.
 #ifndef CMS_CUBEMAP_HOT_PATH_H
 #define CMS_CUBEMAP_HOT_PATH_H
+#include <functional>
 #include <string>
 #include <set>
 #include <vector>
@@ -110,6 +111,11 @@ struct FrameView {
   std::vector<cv::Vec3f> mvMapPointPos;
   cv::Mat mMapPointDescriptors;         // N x 32 CV_8U
   std::vector<std::pair<unsigned, std::vector<unsigned>>> mFeatVec;   // Frame::ComputeBoW: ascending node id (SearchByBoW)
+  // PnPsolver only: mvKeyRays, mvLevelSigma2, and for the map point a candidate's SearchByBoW matched to key point i (vpMapPointMatches[i] >= 0)
+  // its GetWorldPos() in mvMapPointPos[i] and isBad() in mvbMapPointBad[i] (empty = none is bad)
+  std::vector<cv::Vec3f> mvKeyRays;
+  std::vector<float> mvLevelSigma2;
+  std::vector<uint8_t> mvbMapPointBad;
 };
 
 struct KeyFrameView;
@@ -168,6 +174,35 @@ struct MapPointView {
   bool mbTrackInView = false;
   float mTrackProjX = -1, mTrackProjY = -1, mTrackViewCos = 0;
   int mnTrackScaleLevel = -1;
+};
+
+// PnPsolver (include/PnPsolver.h, src/PnPsolver.cpp) under the reference's names: the constructor's filtering and order (:83-108), SetRansacParameters
+// with the header's defaults, find / iterate returning the 4 x 4 CV_32F pose or an empty cv::Mat, vbInliers expanded through mvKeyPointIndices.
+// iterate() makes the call's draws first -- 4 per iteration the loop of :184 may need -- through the replaceable `draw` (default: DUtils::Random::RandomInt,
+// DUtils/Random.cpp:47-50), then runs the loop in one cms_pnp_iterate call on the shared context's device (engine DEVICE, the default) or through the
+// host build of the same core (engine HOST_CORE: the definition of record, no GPU needed).  When a call ends early the draws behind the accepting
+// iteration are discarded: the contract is the reference's loop on the same draws, not the same rand() consumption.
+class PnPsolver {
+ public:
+  enum Engine { DEVICE = 0, HOST_CORE = 1 };
+  PnPsolver(const FrameView& F, const std::vector<long>& vpMapPointMatches);
+  void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4, float th2 = 5.991);
+  cv::Mat find(std::vector<bool>& vbInliers, int& nInliers);
+  cv::Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers);
+  std::function<int(int, int)> draw;      // RandomInt(min, max)
+  Engine engine = DEVICE;
+  // the reference's members, for callers and tests that look at them
+  std::vector<cv::Point2f> mvP2D;
+  std::vector<cv::Vec3f> mvBearings, mvP3Dw;
+  std::vector<float> mvSigma2;
+  std::vector<size_t> mvKeyPointIndices;
+  int N = 0, mnIterations = 0, mnBestInliers = 0, mRansacMinInliers = 0, mRansacMaxIts = 0, mRansacMinSet = 4;
+  float mRansacEpsilon = 0, mRansacTh2 = 5.991f;
+  std::vector<uint8_t> mvbBestInliers;
+  float mBestTcw[12] = {0};
+
+ private:
+  size_t nMatches_ = 0;      // mvpMapPointMatches.size(): the length of vbInliers
 };
 
 // Tracking::SearchLocalPoints (src/Tracking.cpp:794-846): Frame::isInFrustum(pMP, 0.5) for every local map point, then

@@ -457,3 +457,38 @@ extern "C" int hm_write_tracking_summary(const char* path, float* times, int n, 
     if (console && console_len > 0) { std::strncpy(console, text.c_str(), console_len - 1); console[console_len - 1] = 0; }
     return 0;)
 }
+
+// PnPsolver through the mirror: n key points (kps, rays), the matched map point per key point (mp < 0 = none, bad, pos), the pyramid's sigma2.
+// draws: the values the replaceable draw function hands out in order (it must not run dry).  Outputs: key_idx[N] = mvKeyPointIndices (returns N through
+// *N_out), vb[n] = vbInliers (all zero when empty), Tcw16, state[4] = bNoMore, nInliers, mnIterations, found; returns 0, or -1 with hm_last_error().
+extern "C" int hm_pnp_mirror(int engine, int n, const cms_keypoint* kps, const float* rays, const long* mp, const uint8_t* bad, const float* pos, int nlevels,
+                             const float* sigma2, double probability, int minInliers, int maxIterations, float epsilon, float th2, int calls, const int* nIterations,
+                             int n_draws, const int* draws, int* N_out, int* key_idx, uint8_t* vb, float* Tcw16, int* state) {
+  HM_TRY(
+    FrameView f;
+    f.mvKeys.resize(n); f.mvKeyRays.resize(n); f.mvMapPointPos.resize(n);
+    for (int i = 0; i < n; ++i) {
+      f.mvKeys[i].pt = cv::Point2f(kps[i].x, kps[i].y); f.mvKeys[i].octave = kps[i].octave;
+      for (int c = 0; c < 3; ++c) { f.mvKeyRays[i](c) = rays[3 * (size_t)i + c]; f.mvMapPointPos[i](c) = pos[3 * (size_t)i + c]; }
+    }
+    f.mvLevelSigma2.assign(sigma2, sigma2 + nlevels);
+    if (bad) f.mvbMapPointBad.assign(bad, bad + n);
+    PnPsolver solver(f, std::vector<long>(mp, mp + n));
+    solver.engine = engine ? PnPsolver::HOST_CORE : PnPsolver::DEVICE;
+    solver.SetRansacParameters(probability, minInliers, maxIterations, 4, epsilon, th2);
+    int next = 0;
+    solver.draw = [&](int lo, int hi) { if (next >= n_draws) throw std::runtime_error("hm_pnp_mirror: out of draws"); const int v = draws[next++]; if (v < lo || v > hi) throw std::runtime_error("hm_pnp_mirror: draw out of range"); return v; };
+    *N_out = solver.N;
+    for (int i = 0; i < solver.N; ++i) key_idx[i] = (int)solver.mvKeyPointIndices[i];
+    std::vector<bool> vbInliers; int nInliers = 0; bool bNoMore = false; cv::Mat T;
+    for (int c = 0; c < calls; ++c) {
+      T = solver.iterate(nIterations[c], bNoMore, vbInliers, nInliers);
+      if (!T.empty() || bNoMore) break;
+    }
+    std::memset(vb, 0, n);
+    for (size_t i = 0; i < vbInliers.size(); ++i) vb[i] = vbInliers[i] ? 1 : 0;
+    std::memset(Tcw16, 0, 64);
+    if (!T.empty()) for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) Tcw16[4 * r + c] = T.at<float>(r, c);
+    state[0] = bNoMore; state[1] = nInliers; state[2] = solver.mnIterations; state[3] = T.empty() ? 0 : 1; state[4] = next;
+    return 0;)
+}

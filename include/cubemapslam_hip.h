@@ -553,6 +553,58 @@ int cms_search_by_projection_keyframe(cms_ctx* ctx, int b, const float* pose12, 
                                       const float* min_dist, const float* max_dist, const uint8_t* mp_desc, float th, int orb_dist,
                                       int check_orientation, int nkp, int* kp_mp, int* match, int* n_matches);
 
+/* ---- PnPsolver (include/PnPsolver.h, src/PnPsolver.cpp), the EPnP RANSAC of Tracking::Relocalization (src/Tracking.cpp:1034-1060), between
+ * cms_kfstore_search_by_bow and cms_pose_optimize.  The result of a four-point EPnP is defined by the SVD that picks a basis of MtM's null space
+ * (DESIGN.md "PnPsolver"), so the definition of record is the project's own core, csrc/cms_pnp_core.h: one source, built for the host
+ * (libcubemapslam_host.so: hm_pnp_iterate_host) and for the device, which is held to the host build bit for bit.
+ * cms_pnp_ransac_parameters: SetRansacParameters (:123-159) without the per-point part: int truncation of N*epsilon (float product), the two lower
+ *   bounds, epsilon raised to min_inliers/N (float), nIterations = 1 if min_inliers == N else ceil(log(1-p)/log(1-pow(epsilon,3))) in double (a value
+ *   no int holds -- NaN for N < minSet -- converts as x86 does, to INT_MIN), max_its = max(1, min(nIterations, maxIterations)).  Host only.
+ * cms_pnp_iterate: PnPsolver::iterate (:167-261) with Refine (:263-309) and CheckInliers (:312-343) for njobs solvers -- one lost camera stream and
+ *   candidate key frame each -- as ONE launch sequence on the handle's stream: one pinned block up, every hypothesis of every job in parallel
+ *   (compute_pose on the four drawn points), one wavefront per hypothesis for CheckInliers, then one workgroup per job replays the loop in order
+ *   (best on >, Refine on the best mask, accepted on > min_inliers, exhaustion), one block back.  Synchronous: Tracking decides on the result at once.
+ *   Per job the call may need H = max(max_its - iterations, n_iterations) hypotheses if N >= min_inliers, else 0 (the `while` of :184); the caller
+ *   makes the 4*H draws beforehand: draws[4*i + k] = the k-th DUtils::Random::RandomInt(0, size - 1) of iteration i, so 0 <= draws[4*i+k] <= N-1-k.
+ *   The contract is "the reference's loop on the same draws": when a call ends early the draws behind the accepting iteration are discarded, and the
+ *   process's rand() stream is further along than the reference's would be.
+ *   status: 1 = Refine accepted (Tcw = mRefinedTcw, inliers = mvbRefinedInliers, n_inliers = mnRefinedInliers), 2 = iterations used up with a best
+ *   (Tcw = mBestTcw, inliers = mvbBestInliers), 0 = empty cv::Mat (Tcw and inliers zeroed).  no_more = bNoMore.  iterations_run = nCurrentIterations.
+ *   iterations / best_inliers / best_Tcw / best_mask carry mnIterations / mnBestInliers / mBestTcw / mvbBestInliers from call to call; a new solver
+ *   starts with zeros.  Tcw = R (9, row major) | t (3), floats converted from double per element.  inliers / best_mask are per correspondence; the
+ *   caller expands them through mvKeyPointIndices.
+ *   Checked before anything is enqueued (CMS_ERR_ARG): draws out of range, n_draws < 4*H, a total of correspondences / hypotheses / jobs above what
+ *   cms_pnp_create was given, best_mask not consistent with best_inliers, min_inliers < 4 (SetRansacParameters never gives it), max_its or n_iterations
+ *   outside [0, 2^20].  min_set != 4 is CMS_ERR_UNSUPPORTED (the reference passes no other value).
+ *   ctx supplies the face size F and the device; nothing is enqueued on its stream.
+ * cms_pnp_iterate_frames: the same, with the 2-D side of every correspondence gathered on the device from the context's resident rows instead of
+ *   travelling from the host: correspondence i of a job is key point kp_idx[i] (mvKeyPointIndices) of row b of ctx's last batch (cms_frames_process /
+ *   cms_extract), n = the row's key-point count as the caller fetched it: mvP2D = mvKeys[kp_idx[i]].pt, mvBearings = the key ray (what
+ *   cms_frames_fetch_rays reads), mvSigma2 = mvLevelSigma2[octave].  p2d / bearing / sigma2 are ignored.  kp_idx outside [0, n), n above the context's
+ *   kp_cap or b beyond its batch are CMS_ERR_ARG.  The whole sequence runs on ctx's stream, behind whatever filled the rows (the rule of
+ *   cms_kfstore_search_by_projection); one caller at a time per context and per handle.  Synchronous. */
+int cms_pnp_ransac_parameters(int N, double probability, int minInliers, int maxIterations, int minSet, float epsilon,
+                              int* min_inliers, int* max_its, float* epsilon_out);
+typedef struct cms_pnp cms_pnp;
+int cms_pnp_create(cms_pnp** out, int device, int max_jobs, int max_corr_total, int max_hyp_total);
+void cms_pnp_destroy(cms_pnp* p);
+typedef struct {
+  int N;                      /* correspondences (PnPsolver ctor order: key points with a map point that is not bad) */
+  const float* p3d;           /* N x 3  mvP3Dw */
+  const float* p2d;           /* N x 2  mvP2D   | cms_pnp_iterate_frames: ignored, gathered from the frame row */
+  const float* bearing;       /* N x 3  mvBearings = mvKeyRays | same */
+  const float* sigma2;        /* N      mvSigma2 (mvLevelSigma2[octave]) | same */
+  const int* kp_idx;          /* cms_pnp_iterate_frames only: mvKeyPointIndices (N) */
+  int b, n;                   /* cms_pnp_iterate_frames only: row b of ctx's last batch, n key points */
+  float th2; int min_inliers, max_its, min_set;
+  int n_iterations;           /* iterate()'s argument */
+  int n_draws; const int* draws;   /* successive DUtils::Random::RandomInt(0, size-1) values, four per iteration */
+  int iterations, best_inliers; float best_Tcw[12]; uint8_t* best_mask;   /* in/out: mnIterations, mnBestInliers, mBestTcw (R row major | t), mvbBestInliers (N bytes) */
+  int status, no_more, n_inliers, iterations_run; float Tcw[12]; uint8_t* inliers;   /* out; inliers: N bytes, by correspondence */
+} cms_pnp_job;
+int cms_pnp_iterate(cms_pnp* p, cms_ctx* ctx /* F */, int njobs, cms_pnp_job* jobs);
+int cms_pnp_iterate_frames(cms_pnp* p, cms_ctx* ctx, int njobs, cms_pnp_job* jobs);
+
 /* ---- pose-only optimisation: Optimizer::PoseOptimization(Frame*) (src/Optimizer.cpp:48-190), the per-frame solver Tracking calls
  * 1-3 times per frame (Tracking.cpp:585,647,688).  Edge = EdgeSE3ProjectXYZMultiPinholeOnlyPose
  * (include/g2o_cubemap_vertices_edges.h:42-88, src/g2o_cubemap_vertices_edges.cpp:61-134).  One workgroup per frame runs all four

@@ -18,6 +18,7 @@
 #include "Map.h"
 #include "MapPoint.h"
 #include "ORBMatcher.h"
+#include "ThirdParty/DBoW2/DUtils/Random.h"
 
 namespace Hip {
 namespace {
@@ -601,4 +602,91 @@ int SearchByProjection(cms_kfstore* store, cms_ctx* frameCtx, Frame& CurrentFram
   for (int k = 0; k < n; ++k) if (match[k] >= 0) CurrentFrame.mvpMapPoints[match[k]] = pts[k];      // :336 (what the histogram removed is -1 again: :370)
   return nm;
 }
+
+// ---- PnPsolver (src/PnPsolver.cpp)
+PnPsolver::PnPsolver(const Frame& F, const std::vector<MapPoint*>& vpMapPointMatches)
+    : mnMatches(vpMapPointMatches.size()), mnKeys(F.mvKeys.size()), N(0), mnIterations(0), mnBestInliers(0), mRansacMinInliers(0), mRansacMaxIts(0), mRansacMinSet(4),
+      mRansacEpsilon(0), mRansacTh2(5.991f) {
+  std::memset(mBestTcw, 0, sizeof(mBestTcw));
+  for (size_t i = 0, iend = vpMapPointMatches.size(); i < iend; i++) {      // :83-108
+    MapPoint* pMP = vpMapPointMatches[i];
+    if (!pMP || pMP->isBad()) continue;
+    const cv::Mat Pos = pMP->GetWorldPos();
+    mvP3Dw.push_back(Pos.at<float>(0)); mvP3Dw.push_back(Pos.at<float>(1)); mvP3Dw.push_back(Pos.at<float>(2));
+    mvKeyPointIndices.push_back((int)i);
+  }
+  SetRansacParameters();
+}
+
+void PnPsolver::SetRansacParameters(double probability, int minInliers, int maxIterations, int minSet, float epsilon, float th2) {
+  N = (int)mvKeyPointIndices.size();
+  mRansacMinSet = minSet; mRansacTh2 = th2;
+  check(cms_pnp_ransac_parameters(N, probability, minInliers, maxIterations, minSet, epsilon, &mRansacMinInliers, &mRansacMaxIts, &mRansacEpsilon), "cms_pnp_ransac_parameters");
+  mvbBestInliers.assign((size_t)N + 1, 0);
+  mvbInliers.assign((size_t)N + 1, 0);
+}
+
+void PnPsolver::FillJob(cms_pnp_job& q, int nIterations) {
+  std::memset(&q, 0, sizeof(q));
+  int H = 0;
+  if (N >= mRansacMinInliers) H = std::max(std::max(mRansacMaxIts - mnIterations, nIterations), 0);      // the `while` of :184
+  mvDraws.resize((size_t)H * 4);
+  for (int i = 0; i < H; ++i)
+    for (int k = 0; k < 4; ++k) mvDraws[(size_t)i * 4 + k] = DUtils::Random::RandomInt(0, N - k - 1);      // :195
+  q.N = N; q.p3d = mvP3Dw.data(); q.kp_idx = mvKeyPointIndices.data(); q.b = 0; q.n = (int)mnKeys;
+  q.th2 = mRansacTh2; q.min_inliers = mRansacMinInliers; q.max_its = mRansacMaxIts; q.min_set = mRansacMinSet; q.n_iterations = nIterations;
+  q.n_draws = (int)mvDraws.size(); q.draws = mvDraws.data();
+  q.iterations = mnIterations; q.best_inliers = mnBestInliers; std::memcpy(q.best_Tcw, mBestTcw, sizeof(mBestTcw)); q.best_mask = mvbBestInliers.data();
+  q.inliers = mvbInliers.data();
+}
+
+cv::Mat PnPsolver::TakeResult(const cms_pnp_job& q, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+  mnIterations = q.iterations; mnBestInliers = q.best_inliers; std::memcpy(mBestTcw, q.best_Tcw, sizeof(mBestTcw));
+  bNoMore = q.no_more != 0; vbInliers.clear(); nInliers = 0;
+  if (q.status == 0) return cv::Mat();
+  nInliers = q.n_inliers;
+  vbInliers = std::vector<bool>(mnMatches, false);      // :232-237, :250-255
+  for (int i = 0; i < N; i++)
+    if (mvbInliers[(size_t)i]) vbInliers[(size_t)mvKeyPointIndices[(size_t)i]] = true;
+  cv::Mat Tcw = cv::Mat::eye(4, 4, CV_32F);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) Tcw.at<float>(r, c) = q.Tcw[3 * r + c];
+    Tcw.at<float>(r, 3) = q.Tcw[9 + r];
+  }
+  return Tcw;
+}
+
+cv::Mat PnPsolver::iterate(cms_pnp* pnp, cms_ctx* frameCtx, int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+  cms_pnp_job q;
+  FillJob(q, nIterations);
+  check(cms_pnp_iterate_frames(pnp, frameCtx, 1, &q), "cms_pnp_iterate_frames");
+  return TakeResult(q, bNoMore, vbInliers, nInliers);
+}
+
+cv::Mat PnPsolver::find(cms_pnp* pnp, cms_ctx* frameCtx, std::vector<bool>& vbInliers, int& nInliers) {
+  bool bFlag;
+  return iterate(pnp, frameCtx, mRansacMaxIts, bFlag, vbInliers, nInliers);
+}
+
+cms_pnp* CreatePnP(int maxSolvers, int maxCorrespondences, int maxHypotheses) {
+  cms_pnp* pnp = nullptr;
+  check(cms_pnp_create(&pnp, g_device, maxSolvers, maxCorrespondences, maxHypotheses), "cms_pnp_create");
+  return pnp;
+}
+
+void IteratePnP(cms_pnp* pnp, cms_ctx* frameCtx, const std::vector<PnPsolver*>& vpSolvers, int nIterations, std::vector<cv::Mat>& vTcw, std::vector<bool>& vbNoMore,
+                std::vector<std::vector<bool> >& vvbInliers, std::vector<int>& vnInliers) {
+  const size_t n = vpSolvers.size();
+  vTcw.assign(n, cv::Mat()); vbNoMore.assign(n, false); vvbInliers.assign(n, std::vector<bool>()); vnInliers.assign(n, 0);
+  if (n == 0) return;
+  std::vector<cms_pnp_job> jobs(n);
+  for (size_t i = 0; i < n; ++i) vpSolvers[i]->FillJob(jobs[i], nIterations);      // the candidates' draws in the candidates' order, as the reference's loop makes them
+  check(cms_pnp_iterate_frames(pnp, frameCtx, (int)n, jobs.data()), "cms_pnp_iterate_frames");
+  for (size_t i = 0; i < n; ++i) {
+    bool bNoMore = false;
+    vTcw[i] = vpSolvers[i]->TakeResult(jobs[i], bNoMore, vvbInliers[i], vnInliers[i]);
+    vbNoMore[i] = bNoMore;
+  }
+}
+
 }  // namespace Hip

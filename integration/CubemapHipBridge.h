@@ -79,8 +79,38 @@ void SearchByBoWCandidates(cms_kfstore* store, cms_ctx* frameCtx, const std::vec
 // (slot 0 of its batch, cms_area_grid done) with the pose PnP / PoseOptimization left in mTcw.  The key frame's slot comes from the store's
 // KeyFrame* -> slot book and supplies the key-point angles; a key frame that is not resident goes through cms_search_by_projection_keyframe with the
 // angles from the host.  Fills CurrentFrame.mvpMapPoints like the reference and returns nmatches.  Between the two calls the PoseOptimization calls
-// are Hip::PoseOptimization; PnPsolver is the one step of Relocalization that stays on the host.
+// are Hip::PoseOptimization, and the pose comes from Hip::PnPsolver / Hip::IteratePnP below.
 int SearchByProjection(cms_kfstore* store, cms_ctx* frameCtx, Frame& CurrentFrame, KeyFrame* pKF, const std::set<MapPoint*>& sAlreadyFound, float th, int ORBdist,
                        bool checkOri);
+// ---- PnPsolver (include/PnPsolver.h, src/PnPsolver.cpp) with the reference's surface, for Tracking::Relocalization (Tracking.cpp:1034-1067).  The
+// constructor filters and orders as :83-108 does; iterate() makes the call's draws with DUtils::Random::RandomInt -- four per iteration the loop of :184
+// may need -- and runs the loop on the device.  The 2-D side (mvKeys[i].pt, mvKeyRays[i], mvLevelSigma2[octave]) is gathered on the device from the
+// frame `frameCtx` extracted last (slot 0 of its batch), so F must be that frame.  When a call ends early the draws behind the accepting iteration are
+// discarded: the reference's loop on the same draws, not the same rand() consumption.
+class PnPsolver {
+ public:
+  PnPsolver(const Frame& F, const std::vector<MapPoint*>& vpMapPointMatches);
+  void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4, float th2 = 5.991);
+  cv::Mat find(cms_pnp* pnp, cms_ctx* frameCtx, std::vector<bool>& vbInliers, int& nInliers);
+  cv::Mat iterate(cms_pnp* pnp, cms_ctx* frameCtx, int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers);
+
+  // what IteratePnP needs of a solver
+  void FillJob(cms_pnp_job& q, int nIterations);      // makes the draws
+  cv::Mat TakeResult(const cms_pnp_job& q, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers);
+
+ private:
+  std::vector<float> mvP3Dw;                 // N x 3
+  std::vector<int> mvKeyPointIndices;
+  size_t mnMatches, mnKeys;
+  int N, mnIterations, mnBestInliers, mRansacMinInliers, mRansacMaxIts, mRansacMinSet;
+  float mRansacEpsilon, mRansacTh2, mBestTcw[12];
+  std::vector<uint8_t> mvbBestInliers, mvbInliers;
+  std::vector<int> mvDraws;
+};
+cms_pnp* CreatePnP(int maxSolvers, int maxCorrespondences, int maxHypotheses);
+// One pass of Tracking.cpp:1049-1067 over the candidates that are not discarded, as ONE cms_pnp_iterate_frames call: per solver i what
+// vpSolvers[i]->iterate(nIterations, bNoMore, vbInliers, nInliers) returns (an empty cv::Mat when there is no pose yet).
+void IteratePnP(cms_pnp* pnp, cms_ctx* frameCtx, const std::vector<PnPsolver*>& vpSolvers, int nIterations, std::vector<cv::Mat>& vTcw,
+                std::vector<bool>& vbNoMore, std::vector<std::vector<bool> >& vvbInliers, std::vector<int>& vnInliers);
 }  // namespace Hip
 #endif
