@@ -1273,3 +1273,91 @@ class PnPSolver:
         arr = pnp_jobs(states)
         (self.iterate_frames if frames else self.iterate)(ctx, arr)
         return pnp_results(arr, states)
+
+
+class InitJob(C.Structure):
+    """cms_init_job (include/cubemapslam_hip.h)"""
+    _fields_ = [("n1", C.c_int), ("n2", C.c_int), ("keys1", C.c_void_p), ("rays1", C.c_void_p), ("keys2", C.c_void_p), ("rays2", C.c_void_p),
+                ("matches12", C.c_void_p), ("b", C.c_int), ("sigma", C.c_float), ("iterations", C.c_int), ("n_draws", C.c_int), ("draws", C.c_void_p),
+                ("status", C.c_int), ("R21", C.c_float * 9), ("t21", C.c_float * 3), ("p3d", C.c_void_p), ("triangulated", C.c_void_p),
+                ("best_iteration", C.c_int), ("score", C.c_float), ("n_inliers", C.c_int), ("nGood", C.c_int * 4), ("parallax", C.c_float * 4),
+                ("winner", C.c_int)]
+
+
+def init_job_state(prob, draws, sigma=1.0, iterations=None, b=0):
+    """The arrays of one Initializer attempt as a dict an InitJob points into: prob has keys1 (n1 x 2), rays1 (n1 x 3), keys2 (n2 x 2), rays2 (n2 x 3)
+    and matches12 (n1, -1 = none).  draws: 8 ints per iteration.  The output arrays start from a pattern, so that an untouched record shows."""
+    f32 = lambda a, w: np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, w))
+    k1, r1, k2, r2 = f32(prob["keys1"], 2), f32(prob["rays1"], 3), f32(prob["keys2"], 2), f32(prob["rays2"], 3)
+    n1 = len(k1)
+    d = np.ascontiguousarray(np.asarray(draws, np.int32).ravel())
+    return dict(n1=n1, n2=int(prob.get("n2", len(k2))), keys1=k1, rays1=r1, keys2=k2, rays2=r2, matches12=np.ascontiguousarray(prob["matches12"], np.int32),
+                b=int(b), sigma=float(sigma), iterations=int(len(d) // 8 if iterations is None else iterations), draws=d,
+                p3d=np.full((max(n1, 1), 3), 7.0, np.float32), triangulated=np.full(max(n1, 1), 9, np.uint8))
+
+
+def init_jobs(states):
+    """(InitJob * n) over init_job_state() dicts; the dicts own the memory.  The scalar outputs start from -7."""
+    arr = (InitJob * len(states))()
+    for q, s in zip(arr, states):
+        q.n1 = s["n1"]; q.n2 = s["n2"]; q.keys1 = _p(s["keys1"]); q.rays1 = _p(s["rays1"]); q.keys2 = _p(s["keys2"]); q.rays2 = _p(s["rays2"])
+        q.matches12 = _p(s["matches12"]); q.b = s["b"]; q.sigma = s["sigma"]; q.iterations = s["iterations"]
+        q.n_draws = len(s["draws"]); q.draws = _p(s["draws"]) if len(s["draws"]) else None
+        q.p3d = _p(s["p3d"]); q.triangulated = _p(s["triangulated"])
+        q.status = -7; q.best_iteration = -7; q.winner = -7; q.n_inliers = -7
+    return arr
+
+
+def init_results(arr, states):
+    """What a call left in the job records, one dict per job (arrays copied)"""
+    out = []
+    for q, s in zip(arr, states):
+        n1 = s["n1"]
+        out.append(dict(status=q.status, best_iteration=q.best_iteration, n_inliers=q.n_inliers, winner=q.winner, score=np.array([q.score], np.float32),
+                        nGood=np.array(q.nGood[:], np.int32), parallax=np.array(q.parallax[:], np.float32), R21=np.array(q.R21[:], np.float32),
+                        t21=np.array(q.t21[:], np.float32), p3d=s["p3d"][:n1].copy(), triangulated=s["triangulated"][:n1].copy()))
+    return out
+
+
+init_first_difference = pnp_first_difference      # result dicts compared bit for bit: None, or (job, key, wanted, got)
+
+
+class TwoViewInitializer:
+    """Initializer::InitializeWithRays for many streams in one launch sequence (cms_init_*).  jobs: an (InitJob * n) array, e.g. from init_jobs()."""
+
+    def __init__(self, max_jobs, max_matches_total, max_keys1_total, max_hyp_total, device=0):
+        self.h = C.c_void_p()
+        L = lib()
+        L.cms_init_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.cms_init_destroy.argtypes = [C.c_void_p]
+        L.cms_init_two_view.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.cms_init_two_view_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _chk(L.cms_init_create(device, max_jobs, max_matches_total, max_keys1_total, max_hyp_total, C.byref(self.h)), "cms_init_create")
+
+    def close(self):
+        if self.h:
+            lib().cms_init_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def two_view(self, ctx, jobs, frames=False):
+        L = lib()
+        _chk((L.cms_init_two_view_frames if frames else L.cms_init_two_view)(self.h, ctx.h, len(jobs), jobs), "cms_init_two_view")
+        return jobs
+
+    def run(self, ctx, states):
+        """One call over init_job_state() dicts -> one result dict per job"""
+        arr = init_jobs(states)
+        self.two_view(ctx, arr)
+        return init_results(arr, states)
+
+    def run_frames(self, ctx, states):
+        """cms_init_two_view_frames: key points and key rays of frame 2 taken on the device from row b of ctx's last batch (n2 = its count)"""
+        arr = init_jobs(states)
+        self.two_view(ctx, arr, frames=True)
+        return init_results(arr, states)

@@ -819,4 +819,94 @@ cv::Mat PnPsolver::iterate(int nIterations, bool& bNoMore, std::vector<bool>& vb
   return Tcw;
 }
 
+// ------------------------------------------------------------------------------------------------ Initializer (src/Initializer.cpp)
+extern "C" int hm_init_two_view_host(int F, float cos_fov, int njobs, cms_init_job* jobs);      // init_host.cpp: the host build of csrc/cms_init_core.h
+
+Initializer::Initializer(const FrameView& ReferenceFrame, float sigma, int iterations) {
+  mvKeys1 = ReferenceFrame.mvKeys;
+  mvKeyRays1 = ReferenceFrame.mvKeyRays;
+  mSigma = sigma;
+  mSigma2 = sigma * sigma;
+  mMaxIterations = iterations;
+  draw = [](int min, int max) {
+    static const bool seeded = (srand(0), true);      // DUtils::Random::SeedRandOnce(0), :90
+    (void)seeded;
+    const int d = max - min + 1;
+    return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min;
+  };
+}
+
+bool Initializer::InitializeWithRays(const FrameView& CurrentFrame, const std::vector<int>& vMatches12, cv::Mat& R21, cv::Mat& t21,
+                                     std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated) {
+  mvKeys2 = CurrentFrame.mvKeys;
+  mvKeyRays2 = CurrentFrame.mvKeyRays;
+  mvMatches12.clear();
+  mvMatches12.reserve(mvKeys2.size());
+  mvbMatched1.resize(mvKeys1.size());
+  for (size_t i = 0, iend = vMatches12.size(); i < iend; i++) {      // :64-73
+    if (vMatches12[i] >= 0) {
+      mvMatches12.push_back(std::make_pair((int)i, vMatches12[i]));
+      mvbMatched1[i] = true;
+    } else
+      mvbMatched1[i] = false;
+  }
+  const int N = (int)mvMatches12.size();
+  R21 = cv::Mat(); t21 = cv::Mat();
+  mnBestIteration = -1; mnInliers = 0; mnWinner = -1; mfScore = 0;
+  for (int h = 0; h < 4; ++h) { mnGood[h] = 0; mfParallax[h] = 0; }
+  if (N < 8 || mMaxIterations < 1 || vMatches12.size() != mvKeys1.size()) return false;
+  std::vector<size_t> vAllIndices, vAvailableIndices;
+  vAllIndices.reserve(N);
+  for (int i = 0; i < N; i++) vAllIndices.push_back(i);
+  mvSets = std::vector<std::vector<size_t>>(mMaxIterations, std::vector<size_t>(8, 0));
+  std::vector<int> draws((size_t)mMaxIterations * 8);
+  for (int it = 0; it < mMaxIterations; it++) {      // :92-107
+    vAvailableIndices = vAllIndices;
+    for (size_t j = 0; j < 8; j++) {
+      const int randi = draw(0, (int)vAvailableIndices.size() - 1);
+      draws[(size_t)it * 8 + j] = randi;
+      mvSets[it][j] = vAvailableIndices[randi];
+      vAvailableIndices[randi] = vAvailableIndices.back();
+      vAvailableIndices.pop_back();
+    }
+  }
+  const size_t n1 = mvKeys1.size(), n2 = mvKeys2.size();
+  std::vector<float> keys1(2 * n1), keys2(2 * n2), p3d(3 * n1);
+  std::vector<uint8_t> tri(n1);
+  for (size_t i = 0; i < n1; ++i) { keys1[2 * i] = mvKeys1[i].pt.x; keys1[2 * i + 1] = mvKeys1[i].pt.y; }
+  for (size_t i = 0; i < n2; ++i) { keys2[2 * i] = mvKeys2[i].pt.x; keys2[2 * i + 1] = mvKeys2[i].pt.y; }
+  cms_init_job q = {};
+  q.n1 = (int)n1; q.n2 = (int)n2; q.keys1 = keys1.data(); q.rays1 = &mvKeyRays1[0](0); q.keys2 = keys2.data(); q.rays2 = n2 ? &mvKeyRays2[0](0) : nullptr;
+  q.matches12 = vMatches12.data(); q.sigma = mSigma; q.iterations = mMaxIterations; q.n_draws = (int)draws.size(); q.draws = draws.data();
+  q.p3d = p3d.data(); q.triangulated = tri.data();
+  if (engine == HOST_CORE) {
+    const int rc = hm_init_two_view_host(CamModelGeneral::GetCamera()->GetCubeFaceWidth(), CamModelGeneral::GetCamera()->GetCosFovTh(), 1, &q);
+    if (rc) throw std::runtime_error("Initializer::InitializeWithRays: the job was refused (" + std::to_string(rc) + ")");
+  } else {
+    cms_ctx* ctx = SharedContext(g_ctx_orb.nfeatures > 0 ? g_ctx_orb.nfeatures : 1000, g_ctx_orb.nfeatures > 0 ? g_ctx_orb.scale_factor : 1.2f,
+                                 g_ctx_orb.nfeatures > 0 ? g_ctx_orb.nlevels : 8, g_ctx_orb.nfeatures > 0 ? g_ctx_orb.ini_th_fast : 20,
+                                 g_ctx_orb.nfeatures > 0 ? g_ctx_orb.min_th_fast : 7);
+    cms_init* h = nullptr;
+    if (cms_init_create(0, 1, N, (int)n1, mMaxIterations, &h)) throw std::runtime_error(std::string("cms_init_create: ") + cms_last_error());
+    const int rc = cms_init_two_view(h, ctx, 1, &q);
+    cms_init_destroy(h);
+    if (rc) throw std::runtime_error(std::string("cms_init_two_view: ") + cms_last_error());
+  }
+  mnBestIteration = q.best_iteration; mnInliers = q.n_inliers; mnWinner = q.winner; mfScore = q.score;
+  for (int h = 0; h < 4; ++h) { mnGood[h] = q.nGood[h]; mfParallax[h] = q.parallax[h]; }
+  if (q.status != 1) return false;
+  vP3D.resize(n1);
+  vbTriangulated = std::vector<bool>(n1, false);
+  for (size_t i = 0; i < n1; ++i) {
+    vP3D[i] = cv::Point3f(p3d[3 * i], p3d[3 * i + 1], p3d[3 * i + 2]);
+    vbTriangulated[i] = tri[i] != 0;
+  }
+  R21 = cv::Mat(3, 3, cv::CV_32F); t21 = cv::Mat(3, 1, cv::CV_32F);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) R21.at<float>(r, c) = q.R21[3 * r + c];
+    t21.at<float>(r, 0) = q.t21[r];
+  }
+  return true;
+}
+
 }  // namespace CubemapSLAM

@@ -205,6 +205,35 @@ class PnPsolver {
   size_t nMatches_ = 0;      // mvpMapPointMatches.size(): the length of vbInliers
 };
 
+// Initializer (include/Initializer.h, src/Initializer.cpp) under the reference's names, for Tracking::MonocularInitialization (Tracking.cpp:409, :443): the
+// constructor keeps the reference frame's key points and key rays, InitializeWithRays filters vMatches12 into mvMatches12 (:61-73), makes the
+// 8 * mMaxIterations draws through the replaceable `draw` and resolves them into mvSets by swap-and-pop (:92-107), then runs FindEssential and
+// ReconstructE in one cms_init_two_view call on the shared context's device (engine DEVICE, the default) or through the host build of the same core
+// (engine HOST_CORE: the definition of record, no GPU needed).  The default draw seeds rand() with 0 once per process (DUtils::Random::SeedRandOnce(0))
+// and applies DUtils::Random::RandomInt's formula (Random.cpp:38-50).  On false R21 and t21 are empty and vP3D / vbTriangulated are left as they
+// were, like the reference; fewer than 8 matches return false (the reference would index an empty vector).
+class Initializer {
+ public:
+  enum Engine { DEVICE = 0, HOST_CORE = 1 };
+  Initializer(const FrameView& ReferenceFrame, float sigma = 1.0, int iterations = 200);
+  bool InitializeWithRays(const FrameView& CurrentFrame, const std::vector<int>& vMatches12, cv::Mat& R21, cv::Mat& t21, std::vector<cv::Point3f>& vP3D,
+                          std::vector<bool>& vbTriangulated);
+  std::function<int(int, int)> draw;      // RandomInt(min, max)
+  Engine engine = DEVICE;
+  // the reference's members, for callers and tests that look at them
+  std::vector<cv::KeyPoint> mvKeys1, mvKeys2;
+  std::vector<cv::Vec3f> mvKeyRays1, mvKeyRays2;
+  typedef std::pair<int, int> Match;
+  std::vector<Match> mvMatches12;
+  std::vector<bool> mvbMatched1;
+  std::vector<std::vector<size_t>> mvSets;
+  float mSigma, mSigma2;
+  int mMaxIterations;
+  // diagnostics of the last attempt (cms_init_job): iteration of the best hypothesis, its score and inliers, nGood / parallax of the four motions, winner
+  int mnBestIteration = -1, mnInliers = 0, mnGood[4] = {0, 0, 0, 0}, mnWinner = -1;
+  float mfScore = 0, mfParallax[4] = {0, 0, 0, 0};
+};
+
 // Tracking::SearchLocalPoints (src/Tracking.cpp:794-846): Frame::isInFrustum(pMP, 0.5) for every local map point, then
 // ORBMatcher(0.8).SearchByProjection(mCurrentFrame, mvpLocalMapPoints, th).  Both halves run on the device in one call
 // (cms_search_local_points); F.mTcw is the 4x4 CV_32F pose (Frame::SetPose), F.mvpMapPoints gets the id of the matched point.

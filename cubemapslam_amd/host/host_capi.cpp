@@ -492,3 +492,39 @@ extern "C" int hm_pnp_mirror(int engine, int n, const cms_keypoint* kps, const f
     state[0] = bNoMore; state[1] = nInliers; state[2] = solver.mnIterations; state[3] = T.empty() ? 0 : 1; state[4] = next;
     return 0;)
 }
+
+// Initializer through the mirror: the reference frame (n1 key points, rays) and the current frame (n2), vMatches12 (n1).  draws: the values the
+// replaceable draw function hands out in order (it must not run dry; n_draws < 0 keeps the class's default draw).  vP3D / vbTriangulated go in holding the caller's pattern, so that "left as they
+// were" shows.  Outputs: R21 (9, zeros when empty), t21 (3), p3d (3 per entry of vP3D), tri, sets[8 * iterations] = mvSets, state[0..11] = found, draws
+// used, N, vP3D.size(), vbTriangulated.size(), best iteration, inliers, winner, nGood[4]; diag[0..4] = score, parallax[4].  Returns 0, or -1 with
+// hm_last_error().
+extern "C" int hm_init_mirror(int engine, int n1, const cms_keypoint* kps1, const float* rays1, int n2, const cms_keypoint* kps2, const float* rays2,
+                              const int* matches12, float sigma, int iterations, int n_draws, const int* draws, float* R21, float* t21, int p3d_len, float* p3d,
+                              int tri_len, uint8_t* tri, int* sets, int* state, float* diag) {
+  HM_TRY(
+    FrameView f1, f2;
+    f1.mvKeys.resize(n1); f1.mvKeyRays.resize(n1); f2.mvKeys.resize(n2); f2.mvKeyRays.resize(n2);
+    for (int i = 0; i < n1; ++i) { f1.mvKeys[i].pt = cv::Point2f(kps1[i].x, kps1[i].y); for (int c = 0; c < 3; ++c) f1.mvKeyRays[i](c) = rays1[3 * (size_t)i + c]; }
+    for (int i = 0; i < n2; ++i) { f2.mvKeys[i].pt = cv::Point2f(kps2[i].x, kps2[i].y); for (int c = 0; c < 3; ++c) f2.mvKeyRays[i](c) = rays2[3 * (size_t)i + c]; }
+    Initializer ini(f1, sigma, iterations);
+    ini.engine = engine ? Initializer::HOST_CORE : Initializer::DEVICE;
+    int next = 0;
+    if (n_draws >= 0) ini.draw = [&](int lo, int hi) { if (next >= n_draws) throw std::runtime_error("hm_init_mirror: out of draws"); const int v = draws[next++]; if (v < lo || v > hi) throw std::runtime_error("hm_init_mirror: draw out of range"); return v; };
+    std::vector<cv::Point3f> vP3D((size_t)p3d_len);
+    std::vector<bool> vbTriangulated((size_t)tri_len);
+    for (int i = 0; i < p3d_len; ++i) vP3D[i] = cv::Point3f(p3d[3 * i], p3d[3 * i + 1], p3d[3 * i + 2]);
+    for (int i = 0; i < tri_len; ++i) vbTriangulated[i] = tri[i] != 0;
+    cv::Mat R, t;
+    const bool found = ini.InitializeWithRays(f2, std::vector<int>(matches12, matches12 + n1), R, t, vP3D, vbTriangulated);
+    for (int k = 0; k < 9; ++k) R21[k] = R.empty() ? 0.0f : R.at<float>(k / 3, k % 3);
+    for (int k = 0; k < 3; ++k) t21[k] = t.empty() ? 0.0f : t.at<float>(k, 0);
+    for (size_t i = 0; i < vP3D.size() && (int)i < std::max(p3d_len, n1); ++i) { p3d[3 * i] = vP3D[i].x; p3d[3 * i + 1] = vP3D[i].y; p3d[3 * i + 2] = vP3D[i].z; }
+    for (size_t i = 0; i < vbTriangulated.size() && (int)i < std::max(tri_len, n1); ++i) tri[i] = vbTriangulated[i] ? 1 : 0;
+    for (size_t it = 0; it < ini.mvSets.size() && (int)it < iterations; ++it)
+      for (int k = 0; k < 8; ++k) sets[8 * it + k] = (int)ini.mvSets[it][k];
+    state[0] = found; state[1] = next; state[2] = (int)ini.mvMatches12.size(); state[3] = (int)vP3D.size(); state[4] = (int)vbTriangulated.size();
+    state[5] = ini.mnBestIteration; state[6] = ini.mnInliers; state[7] = ini.mnWinner;
+    for (int h = 0; h < 4; ++h) { state[8 + h] = ini.mnGood[h]; diag[1 + h] = ini.mfParallax[h]; }
+    diag[0] = ini.mfScore;
+    return 0;)
+}

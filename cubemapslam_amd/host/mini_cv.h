@@ -17,6 +17,8 @@ enum { INTER_LINEAR = 1, BORDER_CONSTANT = 0 };
 
 template <class T> struct Point_ { T x = 0, y = 0; Point_() {} Point_(T a, T b) : x(a), y(b) {} };
 typedef Point_<float> Point2f;
+template <class T> struct Point3_ { T x = 0, y = 0, z = 0; Point3_() {} Point3_(T a, T b, T c) : x(a), y(b), z(c) {} };
+typedef Point3_<float> Point3f;
 template <class T, int N> struct Vec {
   T v[N];
   T& operator()(int i) { return v[i]; }

@@ -605,6 +605,48 @@ typedef struct {
 int cms_pnp_iterate(cms_pnp* p, cms_ctx* ctx /* F */, int njobs, cms_pnp_job* jobs);
 int cms_pnp_iterate_frames(cms_pnp* p, cms_ctx* ctx, int njobs, cms_pnp_job* jobs);
 
+/* ---- Initializer (include/Initializer.h, src/Initializer.cpp), the two-view essential-matrix RANSAC of Tracking::MonocularInitialization
+ * (src/Tracking.cpp:443), behind cms_search_for_initialization.  ComputeE21 takes the last row of a FULL_UV SVD of an 8 x 9 matrix, which OpenCV
+ * completes from a basis nobody can pin (DESIGN.md "Initializer"), so the definition of record is the project's own core, csrc/cms_init_core.h: one
+ * source, built for the host (libcubemapslam_host.so: hm_init_two_view_host) and for the device, which is held to the host build bit for bit.
+ * cms_init_two_view: InitializeWithRays (:53-116) with FindEssential, ComputeE21, CheckEssiential, ReconstructE, DecomposeE, CheckRT and Triangulate
+ *   for njobs initializers -- one camera stream each -- as ONE launch sequence on ctx's stream: one pinned block up, every hypothesis of every job
+ *   in parallel (k_init_hypotheses), one wavefront per hypothesis for CheckEssiential (k_init_check), one workgroup per job for the selection, DecomposeE
+ *   and the four CheckRT passes (k_init_select), one block back; ReconstructE's decision (with the acos of the parallax) is taken on the host.
+ *   Synchronous: Tracking decides on the result at once.
+ *   keys are pt.x, pt.y pairs; matches12[i] = key point of frame 2 matched to key point i of frame 1, or -1 (the vector SearchForInitialization
+ *   fills).  The N matches are those with matches12[i] >= 0, in index order (mvMatches12).  The caller makes the draws: draws[8*it + k] = the k-th
+ *   DUtils::Random::RandomInt(0, size - 1) of iteration it, size = N, N-1, ..., N-7, so 0 <= draws[8*it + k] <= N-1-k; the call resolves them by the
+ *   reference's swap-and-pop (:92-107).
+ *   status 1: initialised -- R21 (row major), t21, p3d (vP3D, n1 x 3) and triangulated (vbTriangulated, n1 bytes), both indexed by the key point of
+ *   frame 1; an entry never written is (0,0,0) / 0.  status 0: the reference returns false; R21, t21, p3d and triangulated are zeroed.  Diagnostics
+ *   either way: best_iteration (first iteration of maximal score under >, -1 when no score exceeds 0), score, n_inliers of its mask, nGood[4] and
+ *   parallax[4] (degrees) of the hypotheses (R1,t) (R2,t) (R1,-t) (R2,-t), winner = 0..3 or -1.
+ *   Checked before anything is enqueued (CMS_ERR_ARG, the records untouched): fewer than 8 matches (the reference would index an empty vector;
+ *   Tracking asks for 100), iterations < 1, n_draws < 8*iterations, a draw out of range, a match index outside [-1, n2), a null array, totals of
+ *   jobs / matches / key points of frame 1 / hypotheses above what cms_init_create was given.
+ * cms_init_two_view_frames: the same with frame 2 taken on the device from row b of ctx's last batch (cms_frames_process / cms_extract), n2 = the
+ *   row's key-point count as the caller fetched it; keys2 / rays2 are ignored.  n2 above the context's kp_cap or b beyond its batch are CMS_ERR_ARG.
+ * One caller at a time per context and per handle. */
+typedef struct cms_init cms_init;
+int cms_init_create(int device, int max_jobs, int max_matches_total, int max_keys1_total, int max_hyp_total, cms_init** out);
+void cms_init_destroy(cms_init* p);
+typedef struct {
+  int n1, n2;                 /* key points of the reference frame (1) and of the current frame (2) */
+  const float* keys1;         /* n1 x 2  mvKeys1[i].pt */
+  const float* rays1;         /* n1 x 3  mvKeyRays1 */
+  const float* keys2;         /* n2 x 2  | cms_init_two_view_frames: ignored, taken from the frame row */
+  const float* rays2;         /* n2 x 3  | same */
+  const int* matches12;       /* n1 */
+  int b;                      /* cms_init_two_view_frames only: row b of ctx's last batch */
+  float sigma; int iterations;
+  int n_draws; const int* draws;   /* eight per iteration */
+  int status; float R21[9], t21[3]; float* p3d; uint8_t* triangulated;   /* out; p3d n1 x 3 floats, triangulated n1 bytes */
+  int best_iteration; float score; int n_inliers, nGood[4]; float parallax[4]; int winner;   /* out: diagnostics */
+} cms_init_job;
+int cms_init_two_view(cms_init* p, cms_ctx* ctx /* F, field of view, stream */, int njobs, cms_init_job* jobs);
+int cms_init_two_view_frames(cms_init* p, cms_ctx* ctx, int njobs, cms_init_job* jobs);
+
 /* ---- pose-only optimisation: Optimizer::PoseOptimization(Frame*) (src/Optimizer.cpp:48-190), the per-frame solver Tracking calls
  * 1-3 times per frame (Tracking.cpp:585,647,688).  Edge = EdgeSE3ProjectXYZMultiPinholeOnlyPose
  * (include/g2o_cubemap_vertices_edges.h:42-88, src/g2o_cubemap_vertices_edges.cpp:61-134).  One workgroup per frame runs all four

@@ -689,4 +689,76 @@ void IteratePnP(cms_pnp* pnp, cms_ctx* frameCtx, const std::vector<PnPsolver*>& 
   }
 }
 
+// ---- Initializer (src/Initializer.cpp)
+Initializer::Initializer(const Frame& ReferenceFrame, float sigma, int iterations) : mSigma(sigma), mMaxIterations(iterations) {
+  const size_t n1 = ReferenceFrame.mvKeys.size();
+  mvKeys1.resize(2 * n1); mvKeyRays1.resize(3 * n1);
+  for (size_t i = 0; i < n1; ++i) {
+    mvKeys1[2 * i] = ReferenceFrame.mvKeys[i].pt.x; mvKeys1[2 * i + 1] = ReferenceFrame.mvKeys[i].pt.y;
+    for (int c = 0; c < 3; ++c) mvKeyRays1[3 * i + c] = ReferenceFrame.mvKeyRays[i](c);
+  }
+}
+
+bool Initializer::FillJob(cms_init_job& q, const Frame& CurrentFrame, const std::vector<int>& vMatches12, bool fromFrameRow) {
+  std::memset(&q, 0, sizeof(q));
+  const size_t n1 = mvKeys1.size() / 2, n2 = CurrentFrame.mvKeys.size();
+  if (vMatches12.size() != n1) throw std::runtime_error("Hip::Initializer: vMatches12 must have one entry per key point of the reference frame");
+  int N = 0;
+  for (size_t i = 0; i < n1; ++i)
+    if (vMatches12[i] >= 0) ++N;      // mvMatches12 (:61-73)
+  if (N < 8 || mMaxIterations < 1) return false;
+  mvMatches12 = vMatches12;
+  if (!fromFrameRow) {
+    mvKeys2.resize(2 * n2); mvKeyRays2.resize(3 * n2);
+    for (size_t i = 0; i < n2; ++i) {
+      mvKeys2[2 * i] = CurrentFrame.mvKeys[i].pt.x; mvKeys2[2 * i + 1] = CurrentFrame.mvKeys[i].pt.y;
+      for (int c = 0; c < 3; ++c) mvKeyRays2[3 * i + c] = CurrentFrame.mvKeyRays[i](c);
+    }
+  }
+#ifndef STUB_DUTILS_RANDOM_H      // the declarations-only stand-in of tools/check_integration_syntax.py names RandomInt alone
+  DUtils::Random::SeedRandOnce(0);      // :90
+#endif
+  mvDraws.resize((size_t)mMaxIterations * 8);
+  for (int it = 0; it < mMaxIterations; it++)
+    for (int j = 0; j < 8; j++) mvDraws[(size_t)it * 8 + j] = DUtils::Random::RandomInt(0, N - j - 1);      // RandomInt(0, vAvailableIndices.size()-1), :99
+  mvP3D.assign(3 * n1, 0.0f); mvbTriangulated.assign(n1, 0);
+  q.n1 = (int)n1; q.n2 = (int)n2; q.keys1 = mvKeys1.data(); q.rays1 = mvKeyRays1.data();
+  q.keys2 = fromFrameRow ? NULL : mvKeys2.data(); q.rays2 = fromFrameRow ? NULL : mvKeyRays2.data();
+  q.matches12 = mvMatches12.data(); q.b = 0; q.sigma = mSigma; q.iterations = mMaxIterations; q.n_draws = (int)mvDraws.size(); q.draws = mvDraws.data();
+  q.p3d = mvP3D.data(); q.triangulated = mvbTriangulated.data();
+  return true;
+}
+
+bool Initializer::TakeResult(const cms_init_job& q, cv::Mat& R21, cv::Mat& t21, std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated) {
+  R21 = cv::Mat(); t21 = cv::Mat();      // :307-308
+  if (q.status != 1) return false;
+  const size_t n1 = mvKeys1.size() / 2;
+  vP3D.resize(n1);
+  vbTriangulated = std::vector<bool>(n1, false);
+  for (size_t i = 0; i < n1; ++i) {
+    vP3D[i] = cv::Point3f(mvP3D[3 * i], mvP3D[3 * i + 1], mvP3D[3 * i + 2]);
+    vbTriangulated[i] = mvbTriangulated[i] != 0;
+  }
+  R21 = cv::Mat(3, 3, CV_32F); t21 = cv::Mat(3, 1, CV_32F);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) R21.at<float>(r, c) = q.R21[3 * r + c];
+    t21.at<float>(r) = q.t21[r];
+  }
+  return true;
+}
+
+bool Initializer::InitializeWithRays(cms_init* init, cms_ctx* frameCtx, const Frame& CurrentFrame, const std::vector<int>& vMatches12, cv::Mat& R21, cv::Mat& t21,
+                                     std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated) {
+  cms_init_job q;
+  if (!FillJob(q, CurrentFrame, vMatches12, true)) { R21 = cv::Mat(); t21 = cv::Mat(); return false; }
+  check(cms_init_two_view_frames(init, frameCtx, 1, &q), "cms_init_two_view_frames");
+  return TakeResult(q, R21, t21, vP3D, vbTriangulated);
+}
+
+cms_init* CreateInitializer(int maxJobs, int maxMatches, int maxKeys1, int maxHypotheses) {
+  cms_init* init = nullptr;
+  check(cms_init_create(g_device, maxJobs, maxMatches, maxKeys1, maxHypotheses, &init), "cms_init_create");
+  return init;
+}
+
 }  // namespace Hip

@@ -112,5 +112,28 @@ cms_pnp* CreatePnP(int maxSolvers, int maxCorrespondences, int maxHypotheses);
 // vpSolvers[i]->iterate(nIterations, bNoMore, vbInliers, nInliers) returns (an empty cv::Mat when there is no pose yet).
 void IteratePnP(cms_pnp* pnp, cms_ctx* frameCtx, const std::vector<PnPsolver*>& vpSolvers, int nIterations, std::vector<cv::Mat>& vTcw,
                 std::vector<bool>& vbNoMore, std::vector<std::vector<bool> >& vvbInliers, std::vector<int>& vnInliers);
+// ---- Initializer (include/Initializer.h, src/Initializer.cpp) with the reference's surface, for Tracking::MonocularInitialization (Tracking.cpp:409
+// constructs it from the first frame, :443 calls InitializeWithRays with mvIniMatches).  The constructor keeps mvKeys / mvKeyRays of the reference
+// frame; InitializeWithRays makes the 8 * iterations draws with DUtils::Random::RandomInt behind SeedRandOnce(0), as :90-107 does, and runs
+// FindEssential and ReconstructE on the device in one call.  Key points and key rays of CurrentFrame are taken on the device from the frame `frameCtx`
+// extracted last (slot 0 of its batch), so CurrentFrame must be that frame -- the frame Hip::SearchForInitialization has just searched.  On false
+// R21 and t21 are empty and vP3D / vbTriangulated are untouched, like the reference; fewer than eight matches return false.
+// FillJob / TakeResult let a host with many streams put one job per stream into a single cms_init_two_view call.
+class Initializer {
+ public:
+  Initializer(const Frame& ReferenceFrame, float sigma = 1.0, int iterations = 200);
+  bool InitializeWithRays(cms_init* init, cms_ctx* frameCtx, const Frame& CurrentFrame, const std::vector<int>& vMatches12, cv::Mat& R21, cv::Mat& t21,
+                          std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated);
+  bool FillJob(cms_init_job& q, const Frame& CurrentFrame, const std::vector<int>& vMatches12, bool fromFrameRow);      // makes the draws; false: fewer than 8 matches
+  bool TakeResult(const cms_init_job& q, cv::Mat& R21, cv::Mat& t21, std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated);
+
+ private:
+  std::vector<float> mvKeys1, mvKeyRays1, mvKeys2, mvKeyRays2, mvP3D;      // pt.x, pt.y pairs; rays x, y, z
+  std::vector<int> mvMatches12, mvDraws;
+  std::vector<uint8_t> mvbTriangulated;
+  float mSigma;
+  int mMaxIterations;
+};
+cms_init* CreateInitializer(int maxJobs, int maxMatches, int maxKeys1, int maxHypotheses);
 }  // namespace Hip
 #endif
