@@ -523,6 +523,27 @@ class Context:
         return out
 
 
+    def compute_bow(self, vocab, rows, n, levelsup=4):
+        """cms_frames_compute_bow: Frame::ComputeBoW for rows `rows` (n[i] key points each) of the last batch in one launch sequence; the results stay
+        resident per row (fetch_bow, KeyframeStore.search_by_bow_frames)."""
+        rows = np.ascontiguousarray(rows, np.int32); n = np.ascontiguousarray(n, np.int32)
+        assert len(rows) == len(n)
+        L = lib()
+        L.cms_frames_compute_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _chk(L.cms_frames_compute_bow(self.h, vocab.h, int(levelsup), len(rows), _p(rows), _p(n)), "cms_frames_compute_bow")
+
+    def fetch_bow(self, b):
+        """cms_frames_fetch_bow: dict(word_id, word_val, node_id, node_off, node_feat) of row b (mBowVec and mFeatVec as arrays)"""
+        L = lib()
+        L.cms_frames_fetch_bow.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        nw, nn = C.c_int(), C.c_int()
+        cap = self.geom.kp_cap
+        o = _bow_arrays(cap, cap, cap)
+        _chk(L.cms_frames_fetch_bow(self.h, b, C.byref(nw), _p(o["word_id"]), _p(o["word_val"]), len(o["word_id"]), C.byref(nn), _p(o["node_id"]), _p(o["node_off"]),
+                                    _p(o["node_feat"]), len(o["node_id"]), cap), "cms_frames_fetch_bow")
+        return _bow_trim(o, nw.value, nn.value)
+
+
 class PinnedArray:
     """uint8 numpy array over pinned host memory from cms_host_alloc (freed with the object)"""
 
@@ -631,6 +652,92 @@ def search_by_bow(ctx, b, n, fv, K, skip=None, nnratio=0.7, check_orientation=Tr
     _chk(L.cms_search_by_bow(ctx.h, b, n, len(nid), _p(nid), _p(noff), _p(nfeat), C.byref(K), _p(sk), float(nnratio), int(check_orientation), _p(kf_idx),
                              C.byref(nm)), "cms_search_by_bow")
     return kf_idx[:n].copy(), nm.value
+
+
+def _bow_arrays(nw, nn, nf):
+    return dict(word_id=np.zeros(nw, np.int32), word_val=np.zeros(nw, np.float64), node_id=np.zeros(nn, np.int32), node_off=np.zeros(nn + 1, np.int32),
+                node_feat=np.zeros(max(nf, 1), np.int32))
+
+
+def _bow_trim(o, nw, nn):
+    noff = o["node_off"][:nn + 1].copy()
+    return dict(word_id=o["word_id"][:nw].copy(), word_val=o["word_val"][:nw].copy(), node_id=o["node_id"][:nn].copy(), node_off=noff,
+                node_feat=o["node_feat"][:int(noff[nn])].copy())
+
+
+def load_vocabulary_text(path):
+    """ORBvoc.txt's format (DBoW2 loadFromTextFile) -> dict(k, L, scoring, weighting, parent, is_leaf, desc, weight) with node 0 = the root.  Empty
+    lines are skipped; the tree's shape is checked by Vocabulary / cms_vocab_create."""
+    with open(path, "r") as f:
+        lines = [ln for ln in f.read().split("\n")]
+    if not lines or not lines[0].split():
+        raise CmsError("vocabulary text: empty file")
+    hdr = [int(v) for v in lines[0].split()]
+    if len(hdr) < 4:
+        raise CmsError("vocabulary text: not a correct text file (header)")
+    rows = [ln.split() for ln in lines[1:] if ln.strip()]
+    for i, r in enumerate(rows):
+        if len(r) < 35:
+            raise CmsError("vocabulary text: line %d ends early" % (i + 2))
+    n = len(rows) + 1
+    parent = np.zeros(n, np.int32); is_leaf = np.zeros(n, np.uint8); desc = np.zeros((n, 32), np.uint8); weight = np.zeros(n, np.float64)
+    if rows:
+        parent[1:] = [int(r[0]) for r in rows]; is_leaf[1:] = [1 if int(r[1]) > 0 else 0 for r in rows]
+        desc[1:] = np.array([[int(v) & 255 for v in r[2:34]] for r in rows], np.uint8); weight[1:] = [float(r[34]) for r in rows]
+    return dict(k=hdr[0], L=hdr[1], scoring=hdr[2], weighting=hdr[3], parent=parent, is_leaf=is_leaf, desc=desc, weight=weight)
+
+
+class Vocabulary:
+    """cms_vocab: the DBoW2 vocabulary tree on one device (read-only, shared by any number of contexts and stores of that device).  Arrays as the text
+    format holds them: node 0 is the root, parent[i] < i, is_leaf marks the words, desc n_nodes x 32 bytes, weight float64."""
+
+    def __init__(self, k, L, scoring, weighting, parent, is_leaf, desc, weight, device=0):
+        self.h = C.c_void_p()
+        parent = np.ascontiguousarray(parent, np.int32); is_leaf = np.ascontiguousarray(is_leaf, np.uint8)
+        desc = np.ascontiguousarray(desc, np.uint8); weight = np.ascontiguousarray(weight, np.float64)
+        assert len(is_leaf) == len(parent) and len(weight) == len(parent) and desc.size == 32 * len(parent)
+        L_ = lib()
+        L_.cms_vocab_create.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4
+        L_.cms_vocab_destroy.argtypes = [C.c_void_p]
+        L_.cms_vocab_destroy.restype = None
+        L_.cms_vocab_info.argtypes = [C.c_void_p, C.c_void_p]
+        L_.cms_vocab_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        _chk(L_.cms_vocab_create(C.byref(self.h), device, int(k), int(L), int(scoring), int(weighting), len(parent), _p(parent), _p(is_leaf), _p(desc), _p(weight)),
+             "cms_vocab_create")
+
+    @classmethod
+    def from_dict(cls, t, device=0):
+        return cls(t["k"], t["L"], t["scoring"], t["weighting"], t["parent"], t["is_leaf"], t["desc"], t["weight"], device=device)
+
+    @classmethod
+    def from_text_file(cls, path, device=0):
+        return cls.from_dict(load_vocabulary_text(path), device=device)
+
+    def close(self):
+        if self.h:
+            lib().cms_vocab_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        a = np.zeros(7, np.int32)
+        _chk(lib().cms_vocab_info(self.h, _p(a)), "cms_vocab_info")
+        return dict(zip(("k", "L", "scoring", "weighting", "nodes", "words", "device"), (int(v) for v in a)))
+
+    def transform(self, ctx, desc, levelsup=4):
+        """cms_vocab_transform: descriptors from the host (n x 32 uint8) -> dict(word_id, word_val, node_id, node_off, node_feat)"""
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n = len(desc)
+        o = _bow_arrays(max(n, 1), max(n, 1), n)
+        nw, nn = C.c_int(), C.c_int()
+        _chk(lib().cms_vocab_transform(self.h, ctx.h, n, _p(desc) if n else None, int(levelsup), C.byref(nw), _p(o["word_id"]), _p(o["word_val"]), C.byref(nn),
+                                       _p(o["node_id"]), _p(o["node_off"]), _p(o["node_feat"])), "cms_vocab_transform")
+        return _bow_trim(o, nw.value, nn.value)
 
 
 class KeyframeStore:
@@ -782,6 +889,46 @@ class KeyframeStore:
         L = lib()
         L.cms_kfstore_search_by_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
         _chk(L.cms_kfstore_search_by_bow(self.h, src_ctx.h, len(jobs), arr, float(nnratio), int(check_orientation), _p(kf_idx), _p(nm)), "cms_kfstore_search_by_bow")
+        return [(kf_idx[off[j]:off[j + 1]].copy(), int(nm[j])) for j in range(len(jobs))]
+
+    def compute_bow(self, vocab, slots, levelsup=4):
+        """cms_kfstore_compute_bow: KeyFrame::ComputeBoW on the resident descriptors of `slots`; the FeatureVector goes into the slots' layout, the
+        BowVector stays per slot (fetch_bow).  CMS_ERR_OVERFLOW (CmsError) when a FeatureVector exceeds max_nodes: no slot is changed."""
+        slots = np.ascontiguousarray(slots, np.int32)
+        L = lib()
+        L.cms_kfstore_compute_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _chk(L.cms_kfstore_compute_bow(self.h, vocab.h, int(levelsup), len(slots), _p(slots)), "cms_kfstore_compute_bow")
+
+    def fetch_bow(self, slot, cap=16384, feature_vector=False):
+        """cms_kfstore_fetch_bow: (word_id int32, word_val float64) of the slot's BowVector; feature_vector=True: the dict of Context.fetch_bow instead
+        (mBowVec and mFeatVec as arrays)"""
+        o = _bow_arrays(cap, cap, cap)
+        nw, nn = C.c_int(), C.c_int()
+        L = lib()
+        L.cms_kfstore_fetch_bow.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        fv = feature_vector
+        _chk(L.cms_kfstore_fetch_bow(self.h, slot, C.byref(nw), _p(o["word_id"]), _p(o["word_val"]), cap, C.byref(nn), _p(o["node_id"]) if fv else None,
+                                     _p(o["node_off"]) if fv else None, _p(o["node_feat"]) if fv else None, cap, cap), "cms_kfstore_fetch_bow")
+        if fv:
+            return _bow_trim(o, nw.value, nn.value)
+        return o["word_id"][:nw.value].copy(), o["word_val"][:nw.value].copy()
+
+    def search_by_bow_frames(self, src_ctx, jobs, nnratio=0.7, check_orientation=True):
+        """cms_kfstore_search_by_bow_frames: search_by_bow with the frame's FeatureVector taken from the row's resident result (Context.compute_bow).
+        jobs: list of (slot, b, n, skip).  Returns per job (kf_idx int32[n], n_matches)."""
+        arr = (BowJob * max(len(jobs), 1))()
+        keep = []
+        for q, (slot, b, n, skip) in zip(arr, jobs):
+            sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+            keep.append(sk)
+            q.slot = slot; q.b = b; q.n = n; q.nnodes = 0
+            q.node_id = None; q.node_off = None; q.node_feat = None; q.kf_skip = None if sk is None else sk.ctypes.data
+        off = np.concatenate([[0], np.cumsum([int(j[2]) for j in jobs])]).astype(np.int64)
+        kf_idx = np.full(max(int(off[-1]), 1), -1, np.int32); nm = np.zeros(max(len(jobs), 1), np.int32)
+        L = lib()
+        L.cms_kfstore_search_by_bow_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+        _chk(L.cms_kfstore_search_by_bow_frames(self.h, src_ctx.h, len(jobs), arr, float(nnratio), int(check_orientation), _p(kf_idx), _p(nm)),
+             "cms_kfstore_search_by_bow_frames")
         return [(kf_idx[off[j]:off[j + 1]].copy(), int(nm[j])) for j in range(len(jobs))]
 
     def search_by_projection(self, src_ctx, jobs, th=10.0, orb_dist=100, check_orientation=True):

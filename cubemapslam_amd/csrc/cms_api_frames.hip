@@ -34,6 +34,11 @@ static bool cms_cu_mask_from_env(uint32_t* words, int* n_words) {
   return n > 0;
 }
 
+// resident BoW results of the context's frame rows (cms_api_vocab.hip: cms_frames_compute_bow), allocated on first use
+struct CmsCtxBow;
+static void cms_ctx_bow_free(CmsCtxBow* b);
+static void cms_ctx_bow_invalidate(CmsCtxBow* b);      // a new batch: the rows' results belong to the frames they were computed from
+
 static thread_local std::string g_cms_err;
 static int cms_fail(int code, const char* what, hipError_t e = hipSuccess) {
   char buf[512];
@@ -98,6 +103,7 @@ struct cms_ctx {
   bool desc_spatial = false;         // k_describe works through the batch's key points in spatial order, an eighth of the walk per XCD (CMS_DESC_SPATIAL_ORDER=1)
   hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t fast_lds = 0, qt_lds = 0;
+  CmsCtxBow* bow = nullptr;      // BowVector / FeatureVector per frame row (cms_frames_compute_bow)
 };
 
 // ---- camera model, host side (System::CreateUndistortRectifyMap -> CamModelGeneral::CubemapToFisheye, see
@@ -207,6 +213,7 @@ static void cms_ctx_free(cms_ctx* c) {
                   c->d_overflow, c->d_qt_out, c->d_qt_cnt, c->d_kps, c->d_aux, c->d_order, c->d_aux_sorted, c->d_desc, c->d_kp_cnt, c->d_match, c->d_cell_cand,
                   c->d_cell_cnt, c->d_cells_all, c->d_cells_nz, c->d_area_sorted, c->d_area_cell_start, c->d_area_nvalid, c->d_area_psum, c->d_area_tmp, c->d_walk_cnt, c->d_rays, c->d_rtiles};
   for (void* p : ptrs) if (p) hipFree(p);
+  cms_ctx_bow_free(c->bow);
   if (c->h_fish_stage) (void)hipHostFree(c->h_fish_stage);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   for (int i = 0; i < 8; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -585,6 +592,7 @@ static void cms_launch_remap(cms_ctx* c, const uint8_t* src, int B, int write_co
 
 static int cms_launch_frames(cms_ctx* c, int B, int from_fisheye, const uint8_t* d_src = nullptr) {
   c->last_batch = B;
+  cms_ctx_bow_invalidate(c->bow);
   c->g.skip_zero_cells = from_fisheye ? 1 : 0;   // a caller-supplied canvas (cms_extract) may hold anything in its corner blocks
   // the corner blocks of every level are 0 from cms_ctx_create on and k_remap never writes there; only a caller-supplied canvas
   // can dirty them, in which case the next remapped launch rewrites the zeros in full

@@ -316,8 +316,12 @@ extern "C" int cms_search_for_triangulation(cms_ctx* c, const cms_keyframe* kf1,
 
 // ---- resident key frames: the map's key frames live on the device in fixed-size slots (features, FeatureVector, pose); a call names
 // slots, so nothing but ~100 bytes per (current, neighbour) pair travels to the device per CreateNewMapPoints.
+struct CmsStoreBow;      // the slots' BowVectors and the scratch of cms_kfstore_compute_bow (cms_api_vocab.hip), allocated on first use
+static void cms_store_bow_free(CmsStoreBow* b);
+static void cms_store_bow_invalidate(CmsStoreBow* b, int slot);      // a slot is refilled: its BowVector belonged to the key frame it held
 struct cms_kfstore {
   cms_ctx* c = nullptr;
+  CmsStoreBow* bow = nullptr;
   int maxkf = 0, maxf = 0, maxn = 0;
   CmsTriKF* d_kf = nullptr; CmsKeyPoint* d_kp = nullptr; uint8_t* d_desc = nullptr; float* d_rays = nullptr; int* d_mp = nullptr; int* d_fn = nullptr;
   int* d_nid = nullptr; int* d_noff = nullptr; int* d_nfeat = nullptr;
@@ -351,6 +355,7 @@ extern "C" void cms_kfstore_destroy(cms_kfstore* st) {
   void* bufs[] = {st->d_kf, st->d_kp, st->d_desc, st->d_rays, st->d_mp, st->d_fn, st->d_nid, st->d_noff, st->d_nfeat, st->d_work,
                   st->d_sorted, st->d_cell_start, st->d_nvalid, st->d_kp_cnt};
   for (void* b : bufs) if (b) (void)hipFree(b);
+  cms_store_bow_free(st->bow);
   if (st->h_ff) (void)hipHostFree(st->h_ff);
   if (st->h_items) (void)hipHostFree(st->h_items);
   if (st->h_upd) (void)hipHostFree(st->h_upd);
@@ -426,6 +431,7 @@ extern "C" int cms_kfstore_put(cms_kfstore* st, int slot, const cms_keyframe* kf
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(s));
   st->h_kf[(size_t)slot] = d; st->h_median[(size_t)slot] = kf->median_depth; st->used[(size_t)slot] = 1;
+  cms_store_bow_invalidate(st->bow, slot);
   return CMS_OK;
 }
 
@@ -590,6 +596,7 @@ extern "C" int cms_kfstore_put_from_frames(cms_kfstore* st, cms_ctx* src, int n_
     const cms_kf_from_frame& q = items[i];
     st->ff_call[(size_t)q.slot] = call;
     st->h_kf[(size_t)q.slot] = h_items[i].kf; st->h_median[(size_t)q.slot] = q.median_depth; st->used[(size_t)q.slot] = 1;
+    cms_store_bow_invalidate(st->bow, q.slot);
   }
   st->items_call[gen] = call;
   return CMS_OK;

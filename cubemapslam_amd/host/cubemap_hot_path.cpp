@@ -9,6 +9,7 @@
 #include <fstream>
 #include <iomanip>
 #include <stdexcept>
+#include "../csrc/cms_vocab_core.h"
 
 namespace CubemapSLAM {
 
@@ -48,6 +49,7 @@ void CamModelGeneral::GetPosInFace(double& u, double& v, double uCubemap, double
 // ------------------------------------------------------------------------------------------------ shared device context
 static std::mutex g_ctx_mutex;
 static cms_ctx* g_ctx = nullptr;
+static const int kSharedDevice = 0;      // the device of the shared context (and of what works with it: ORBVocabulary's device handle)
 static cms_orb_params g_ctx_orb{};
 static cms_camera g_ctx_cam{};      // the camera the shared context was built for (SetCamParams zero-fills the record first: comparable byte for byte)
 cms_ctx* SharedContext(int nfeatures, float scaleFactor, int nlevels, int iniThFAST, int minThFAST) {
@@ -58,7 +60,7 @@ cms_ctx* SharedContext(int nfeatures, float scaleFactor, int nlevels, int iniThF
   // size) gets a new one -- until round 6 only the extractor parameters were compared, and the mirror kept searching with the OLD camera's LUT and grid
   if (g_ctx && std::memcmp(&orb, &g_ctx_orb, sizeof(orb)) == 0 && std::memcmp(&g_ctx_cam, &CamModelGeneral::GetCamera()->params(), sizeof(cms_camera)) == 0) return g_ctx;
   if (g_ctx) { cms_ctx_destroy(g_ctx); g_ctx = nullptr; }
-  const int rc = cms_ctx_create(&g_ctx, 0, &CamModelGeneral::GetCamera()->params(), &orb, 1);
+  const int rc = cms_ctx_create(&g_ctx, kSharedDevice, &CamModelGeneral::GetCamera()->params(), &orb, 1);
   if (rc != CMS_OK) throw std::runtime_error(std::string("cms_ctx_create: ") + cms_last_error());
   g_ctx_orb = orb; g_ctx_cam = CamModelGeneral::GetCamera()->params();
   return g_ctx;
@@ -907,6 +909,108 @@ bool Initializer::InitializeWithRays(const FrameView& CurrentFrame, const std::v
     t21.at<float>(r, 0) = q.t21[r];
   }
   return true;
+}
+
+// ---- ORBVocabulary (DBoW2::TemplatedVocabulary) and Frame / KeyFrame::ComputeBoW
+struct ORBVocabulary::Impl {
+  VocabularyText text;
+  CmsVocabTree tree;
+  bool loaded = false;
+  cms_vocab* dev = nullptr;
+};
+ORBVocabulary::ORBVocabulary() : impl_(new Impl()) {}
+ORBVocabulary::~ORBVocabulary() {
+  if (impl_->dev) cms_vocab_destroy(impl_->dev);
+  delete impl_;
+}
+bool ORBVocabulary::setTree(const VocabularyText& t) {
+  CmsVocabTree tree;
+  const char* why = cms_vocab_relayout(t.k, t.L, t.scoring, t.weighting, t.nodes(), t.parent.data(), t.is_leaf.data(), t.desc.data(), t.weight.data(), &tree);
+  if (why) { error_ = why; return false; }
+  if (impl_->dev) { cms_vocab_destroy(impl_->dev); impl_->dev = nullptr; }
+  impl_->text = t; impl_->tree = std::move(tree); impl_->loaded = true;
+  error_.clear();
+  return true;
+}
+bool ORBVocabulary::loadFromTextFile(const std::string& filename) {
+  VocabularyText t;
+  if (!LoadVocabularyText(filename, &t, &error_)) return false;
+  return setTree(t);
+}
+void ORBVocabulary::saveToTextFile(const std::string& filename) const {
+  std::ofstream f(filename.c_str(), std::ios::binary);
+  f << FormatVocabularyText(impl_->text);
+}
+bool ORBVocabulary::empty() const { return !impl_->loaded || impl_->tree.n_words == 0; }
+unsigned ORBVocabulary::size() const { return impl_->loaded ? (unsigned)impl_->tree.n_words : 0u; }
+const VocabularyText& ORBVocabulary::tree() const { return impl_->text; }
+cms_vocab* ORBVocabulary::deviceHandle() const {
+  if (empty()) throw std::runtime_error("ORBVocabulary: empty vocabulary");
+  if (!impl_->dev) {
+    const VocabularyText& t = impl_->text;
+    if (cms_vocab_create(&impl_->dev, kSharedDevice, t.k, t.L, t.scoring, t.weighting, t.nodes(), t.parent.data(), t.is_leaf.data(), t.desc.data(), t.weight.data()) != CMS_OK)
+      throw std::runtime_error(std::string("cms_vocab_create failed: ") + cms_last_error());
+  }
+  return impl_->dev;
+}
+void ORBVocabulary::transform(const std::vector<cv::Mat>& features, BowVector& v, FeatureVector& fv, int levelsup) const {
+  v.clear();
+  fv.clear();
+  if (empty()) return;      // :1134
+  const int n = (int)features.size();
+  std::vector<uint8_t> desc(32 * (size_t)std::max(n, 1));
+  for (int i = 0; i < n; ++i) std::memcpy(desc.data() + 32 * (size_t)i, features[(size_t)i].data, 32);
+  CmsVocabResult r;
+  if (engine == HOST_CORE) {
+    cms_vocab_transform_host(impl_->tree.view(), n, desc.data(), levelsup, &r);
+  } else {
+    // the shared context as the extractor sized it, or System's default one when the vocabulary is the first to need it (System.cpp loads it first)
+    cms_ctx* ctx = g_ctx_orb.nfeatures > 0 ? SharedContext(g_ctx_orb.nfeatures, g_ctx_orb.scale_factor, g_ctx_orb.nlevels, g_ctx_orb.ini_th_fast, g_ctx_orb.min_th_fast)
+                                           : SharedContext(2000, 1.2f, 8, 20, 7);
+    cms_vocab* dev = deviceHandle();
+    const size_t cap = (size_t)std::max(n, 1);
+    r.word_id.resize(cap); r.word_val.resize(cap); r.node_id.resize(cap); r.node_off.resize(cap + 1); r.node_feat.resize(cap);
+    int nwords = 0, nnodes = 0;
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (cms_vocab_transform(dev, ctx, n, desc.data(), levelsup, &nwords, r.word_id.data(), r.word_val.data(), &nnodes, r.node_id.data(), r.node_off.data(),
+                            r.node_feat.data()) != CMS_OK)
+      throw std::runtime_error(std::string("cms_vocab_transform failed: ") + cms_last_error());
+    r.word_id.resize((size_t)nwords); r.word_val.resize((size_t)nwords); r.node_id.resize((size_t)nnodes); r.node_off.resize((size_t)nnodes + 1);
+  }
+  for (size_t i = 0; i < r.word_id.size(); ++i) v.push_back(std::make_pair((unsigned)r.word_id[i], r.word_val[i]));
+  for (size_t e = 0; e < r.node_id.size(); ++e)
+    fv.push_back(std::make_pair((unsigned)r.node_id[e], std::vector<unsigned>(r.node_feat.begin() + r.node_off[e], r.node_feat.begin() + r.node_off[e + 1])));
+}
+// L1Scoring::score (ScoringObject.cpp:23-68); lower_bound on a map is the first entry with an id not smaller
+double ORBVocabulary::score(const BowVector& v1, const BowVector& v2) const {
+  if (impl_->loaded && impl_->text.scoring != CMS_VOC_L1_NORM) throw std::runtime_error("ORBVocabulary::score: only L1 scoring is supported");
+  size_t i = 0, j = 0;
+  double score = 0;
+  while (i < v1.size() && j < v2.size()) {
+    const double vi = v1[i].second, wi = v2[j].second;
+    if (v1[i].first == v2[j].first) {
+      score += fabs(vi - wi) - fabs(vi) - fabs(wi);
+      ++i; ++j;
+    } else if (v1[i].first < v2[j].first) {
+      while (i < v1.size() && v1[i].first < v2[j].first) ++i;
+    } else {
+      while (j < v2.size() && v2[j].first < v1[i].first) ++j;
+    }
+  }
+  score = -score / 2.0;
+  return score;
+}
+// one 1 x 32 header per descriptor row (what Converter::toDescriptorVector hands to transform)
+static std::vector<cv::Mat> descriptor_rows(const cv::Mat& m) {
+  std::vector<cv::Mat> rows((size_t)std::max(m.rows, 0));
+  for (size_t r = 0; r < rows.size(); ++r) rows[r] = m.row((int)r);
+  return rows;
+}
+void FrameView::ComputeBoW(const ORBVocabulary& voc) {
+  if (mBowVec.empty()) voc.transform(descriptor_rows(mDescriptors), mBowVec, mFeatVec, 4);
+}
+void KeyFrameView::ComputeBoW(const ORBVocabulary& voc) {
+  if (mBowVec.empty() || mFeatVec.empty()) voc.transform(descriptor_rows(mDescriptors), mBowVec, mFeatVec, 4);
 }
 
 }  // namespace CubemapSLAM

@@ -10,6 +10,8 @@
 //   ORBMatcher(nnratio, checkOri) / DescriptorDistance / SearchByProjection(CurrentFrame, LastFrame, th, mono)
 //                                                                   include/ORBMatcher.h:46-84, src/ORBMatcher.cpp:130-251,951-967
 //   Optimizer::LocalBundleAdjustment(...)                           include/Optimizer.h:50, src/Optimizer.cpp:192-451
+//   ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>) loadFromTextFile / saveToTextFile / transform / score
+//                                                                   include/ORBVocabulary.h, Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h
 //
 // The pointer-graph types the reference passes around (Frame, KeyFrame, MapPoint, Map) are out of scope (SURVEY.md
 // section 2); the two methods that take them receive plain views instead (FrameView, LocalBAWindow) holding exactly the
@@ -21,9 +23,44 @@
 #include <set>
 #include <vector>
 #include "cubemapslam_hip.h"
+#include "io_formats.h"
 #include "mini_cv.h"
 
 namespace CubemapSLAM {
+
+// DBoW2::BowVector (std::map<WordId, WordValue>) and DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned>>) in std::map order
+typedef std::vector<std::pair<unsigned, double>> BowVector;
+typedef std::vector<std::pair<unsigned, std::vector<unsigned>>> FeatureVector;
+
+// ORBVocabulary under the reference's names.  loadFromTextFile reads ORBvoc.txt's format (io_formats.h; false with the reason in error() for a file
+// the loader refuses -- unlike the reference it skips empty lines and checks the tree), saveToTextFile writes the reference's bytes.  transform runs
+// on the shared context's device (engine DEVICE, the default: cms_vocab_transform) or through the host build of the same core (engine HOST_CORE:
+// csrc/cms_vocab_core.h, the definition of record, no GPU needed).  score is L1Scoring::score (ScoringObject.cpp:23-68); the other scoring types
+// throw std::runtime_error.
+class ORBVocabulary {
+ public:
+  enum Engine { DEVICE = 0, HOST_CORE = 1 };
+  ORBVocabulary();
+  ~ORBVocabulary();
+  ORBVocabulary(const ORBVocabulary&) = delete;
+  ORBVocabulary& operator=(const ORBVocabulary&) = delete;
+  bool loadFromTextFile(const std::string& filename);
+  void saveToTextFile(const std::string& filename) const;
+  bool setTree(const VocabularyText& tree);      // the same checks as loadFromTextFile, from arrays
+  bool empty() const;
+  unsigned size() const;                         // number of words
+  void transform(const std::vector<cv::Mat>& features, BowVector& v, FeatureVector& fv, int levelsup) const;
+  double score(const BowVector& v1, const BowVector& v2) const;
+  const VocabularyText& tree() const;
+  const std::string& error() const { return error_; }
+  cms_vocab* deviceHandle() const;               // created on first use on the shared context's device (device 0)
+  mutable Engine engine = DEVICE;
+
+ private:
+  struct Impl;
+  Impl* impl_;
+  std::string error_;
+};
 
 class CamModelGeneral {
  public:
@@ -111,6 +148,9 @@ struct FrameView {
   std::vector<cv::Vec3f> mvMapPointPos;
   cv::Mat mMapPointDescriptors;         // N x 32 CV_8U
   std::vector<std::pair<unsigned, std::vector<unsigned>>> mFeatVec;   // Frame::ComputeBoW: ascending node id (SearchByBoW)
+  BowVector mBowVec;
+  // Frame.cpp:719-726: transform(toDescriptorVector(mDescriptors), mBowVec, mFeatVec, 4) when mBowVec is empty
+  void ComputeBoW(const ORBVocabulary& voc);
   // PnPsolver only: mvKeyRays, mvLevelSigma2, and for the map point a candidate's SearchByBoW matched to key point i (vpMapPointMatches[i] >= 0)
   // its GetWorldPos() in mvMapPointPos[i] and isBad() in mvbMapPointBad[i] (empty = none is bad)
   std::vector<cv::Vec3f> mvKeyRays;
@@ -278,6 +318,9 @@ struct KeyFrameView {
   std::vector<uint8_t> mvbMapPointBad;                   // per key point: the map point isBad() (SearchByBoW); empty = none is bad
   cv::Mat Tcw;                                           // 4x4 CV_32F
   std::vector<std::pair<unsigned, std::vector<unsigned>>> mFeatVec;   // ascending node id
+  BowVector mBowVec;
+  // KeyFrame.cpp:94-103: the same transform when mBowVec or mFeatVec is empty
+  void ComputeBoW(const ORBVocabulary& voc);
   float medianDepth = 1.0f;                              // ComputeSceneMedianDepth(2)
   // per key point with mvpMapPoints[i] >= 0: what SearchByProjection(Frame&, KeyFrame*, ...) reads of that map point (GetWorldPos, GetDescriptor,
   // mfMinDistance / mfMaxDistance); empty for the callers that do not need it

@@ -4,6 +4,7 @@
 #include <stdexcept>
 #include "cubemap_hot_path.h"
 #include "io_formats.h"
+#include "../csrc/cms_vocab_core.h"
 using namespace CubemapSLAM;
 
 static thread_local std::string g_err;
@@ -526,5 +527,112 @@ extern "C" int hm_init_mirror(int engine, int n1, const cms_keypoint* kps1, cons
     state[5] = ini.mnBestIteration; state[6] = ini.mnInliers; state[7] = ini.mnWinner;
     for (int h = 0; h < 4; ++h) { state[8 + h] = ini.mnGood[h]; diag[1 + h] = ini.mfParallax[h]; }
     diag[0] = ini.mfScore;
+    return 0;)
+}
+
+// ---- ORBVocabulary (tests/vocab_hostlib.py): the mirror class, the text format and the host build of csrc/cms_vocab_core.h
+extern "C" int hm_vocab_create(void** out, int k, int L, int scoring, int weighting, int n_nodes, const int* parent, const uint8_t* is_leaf, const uint8_t* desc,
+                               const double* weight) {
+  HM_TRY(
+    if (n_nodes < 1) throw std::runtime_error("vocabulary: no nodes");
+    VocabularyText t;
+    t.k = k; t.L = L; t.scoring = scoring; t.weighting = weighting;
+    t.parent.assign(parent, parent + n_nodes); t.is_leaf.assign(is_leaf, is_leaf + n_nodes); t.desc.assign(desc, desc + 32 * (size_t)n_nodes);
+    t.weight.assign(weight, weight + n_nodes);
+    ORBVocabulary* v = new ORBVocabulary();
+    if (!v->setTree(t)) { const std::string why = v->error(); delete v; throw std::runtime_error(why); }
+    *out = v;
+    return 0;)
+}
+extern "C" int hm_vocab_load(void** out, const char* path) {
+  HM_TRY(
+    ORBVocabulary* v = new ORBVocabulary();
+    if (!v->loadFromTextFile(path)) { const std::string why = v->error(); delete v; throw std::runtime_error(why); }
+    *out = v;
+    return 0;)
+}
+extern "C" int hm_vocab_save(void* voc, const char* path) {
+  HM_TRY(static_cast<ORBVocabulary*>(voc)->saveToTextFile(path); return 0;)
+}
+extern "C" void hm_vocab_destroy(void* voc) { delete static_cast<ORBVocabulary*>(voc); }
+// info[6]: k, L, scoring, weighting, nodes, words
+extern "C" int hm_vocab_info(void* voc, int* info) {
+  HM_TRY(
+    const ORBVocabulary* v = static_cast<ORBVocabulary*>(voc);
+    const VocabularyText& t = v->tree();
+    info[0] = t.k; info[1] = t.L; info[2] = t.scoring; info[3] = t.weighting; info[4] = t.nodes(); info[5] = (int)v->size();
+    return 0;)
+}
+extern "C" int hm_vocab_arrays(void* voc, int* parent, uint8_t* is_leaf, uint8_t* desc, double* weight) {
+  HM_TRY(
+    const VocabularyText& t = static_cast<ORBVocabulary*>(voc)->tree();
+    std::memcpy(parent, t.parent.data(), 4 * t.parent.size()); std::memcpy(is_leaf, t.is_leaf.data(), t.is_leaf.size());
+    std::memcpy(desc, t.desc.data(), t.desc.size()); std::memcpy(weight, t.weight.data(), 8 * t.weight.size());
+    return 0;)
+}
+// ORBVocabulary::transform through the named engine (0 = device, 1 = host core); arrays of n entries, node_off n + 1
+extern "C" int hm_vocab_transform(void* voc, int engine, int n, const uint8_t* desc, int levelsup, int* nwords, int* word_id, double* word_val, int* nnodes,
+                                  int* node_id, int* node_off, int* node_feat) {
+  HM_TRY(
+    ORBVocabulary* v = static_cast<ORBVocabulary*>(voc);
+    v->engine = engine ? ORBVocabulary::HOST_CORE : ORBVocabulary::DEVICE;
+    std::vector<cv::Mat> feats((size_t)n);
+    for (int i = 0; i < n; ++i) feats[(size_t)i] = cv::Mat(1, 32, cv::CV_8U, const_cast<uint8_t*>(desc) + 32 * (size_t)i, 32);
+    BowVector bv;
+    FeatureVector fv;
+    v->transform(feats, bv, fv, levelsup);
+    *nwords = (int)bv.size(); *nnodes = (int)fv.size();
+    for (size_t i = 0; i < bv.size(); ++i) { word_id[i] = (int)bv[i].first; word_val[i] = bv[i].second; }
+    int at = 0;
+    node_off[0] = 0;
+    for (size_t e = 0; e < fv.size(); ++e) {
+      node_id[e] = (int)fv[e].first;
+      for (unsigned f : fv[e].second) node_feat[at++] = (int)f;
+      node_off[e + 1] = at;
+    }
+    return 0;)
+}
+// Frame::ComputeBoW (keyframe == 0) / KeyFrame::ComputeBoW (keyframe != 0) through the host core with mBowVec / mFeatVec holding a marker entry
+// beforehand when pre_bow / pre_fv say so: out[0] = 1 when the vectors were recomputed, out[1] / out[2] = their sizes afterwards
+extern "C" int hm_vocab_compute_bow_guard(void* voc, int keyframe, int n, const uint8_t* desc, int pre_bow, int pre_fv, int* out) {
+  HM_TRY(
+    ORBVocabulary* v = static_cast<ORBVocabulary*>(voc);
+    v->engine = ORBVocabulary::HOST_CORE;
+    cv::Mat D(std::max(n, 1), 32, cv::CV_8U, const_cast<uint8_t*>(desc), 32);
+    if (n == 0) D.rows = 0;
+    const unsigned marker = 0xFFFFFFFFu;
+    BowVector bv;
+    FeatureVector fv;
+    if (pre_bow) bv.push_back(std::make_pair(marker, -1.0));
+    if (pre_fv) fv.push_back(std::make_pair(marker, std::vector<unsigned>()));
+    if (keyframe) { KeyFrameView k; k.mDescriptors = D; k.mBowVec = bv; k.mFeatVec = fv; k.ComputeBoW(*v); bv = k.mBowVec; fv = k.mFeatVec; }
+    else { FrameView f; f.mDescriptors = D; f.mBowVec = bv; f.mFeatVec = fv; f.ComputeBoW(*v); bv = f.mBowVec; fv = f.mFeatVec; }
+    const bool kept = (pre_bow && !bv.empty() && bv[0].first == marker) || (pre_fv && !fv.empty() && fv[0].first == marker);
+    out[0] = kept ? 0 : 1; out[1] = (int)bv.size(); out[2] = (int)fv.size();
+    return 0;)
+}
+extern "C" int hm_vocab_score(void* voc, int n1, const int* id1, const double* val1, int n2, const int* id2, const double* val2, double* out) {
+  HM_TRY(
+    BowVector a, b;
+    for (int i = 0; i < n1; ++i) a.push_back(std::make_pair((unsigned)id1[i], val1[i]));
+    for (int i = 0; i < n2; ++i) b.push_back(std::make_pair((unsigned)id2[i], val2[i]));
+    *out = static_cast<ORBVocabulary*>(voc)->score(a, b);
+    return 0;)
+}
+// the core's single-descriptor descent, feature by feature: word id, node id and the word's weight
+extern "C" int hm_vocab_descend(void* voc, int n, const uint8_t* desc, int levelsup, int* word, int* nid, double* weight) {
+  HM_TRY(
+    const VocabularyText& t = static_cast<ORBVocabulary*>(voc)->tree();
+    CmsVocabTree tree;
+    const char* why = cms_vocab_relayout(t.k, t.L, t.scoring, t.weighting, t.nodes(), t.parent.data(), t.is_leaf.data(), t.desc.data(), t.weight.data(), &tree);
+    if (why) throw std::runtime_error(why);
+    const CmsVocabView view = tree.view();
+    for (int i = 0; i < n; ++i) {
+      uint32_t f[8];
+      std::memcpy(f, desc + 32 * (size_t)i, 32);
+      int leaf;
+      cms_vocab_descend(view, f, levelsup, &word[i], &nid[i], &leaf);
+      weight[i] = view.word_weight[word[i]];
+    }
     return 0;)
 }

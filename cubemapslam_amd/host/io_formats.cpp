@@ -152,4 +152,70 @@ std::string WriteTrackingSummary(const std::string& perfSavingPath, std::vector<
   return console.str();
 }
 
+bool ParseVocabularyText(const std::string& text, VocabularyText* out, std::string* why) {
+  auto fail = [&](const std::string& m) { if (why) *why = m; return false; };
+  size_t pos = 0;
+  auto next_line = [&](std::string& line) {
+    if (pos >= text.size()) return false;
+    const size_t e = text.find('\n', pos);
+    line = text.substr(pos, e == std::string::npos ? std::string::npos : e - pos);
+    pos = e == std::string::npos ? text.size() : e + 1;
+    return true;
+  };
+  auto blank = [](const std::string& l) { return l.find_first_not_of(" \t\r") == std::string::npos; };
+  std::string line;
+  if (!next_line(line)) return fail("vocabulary text: empty file");
+  VocabularyText v;
+  {
+    std::stringstream ss(line);
+    int n1 = -1, n2 = -1;
+    v.k = -1; v.L = -1;
+    ss >> v.k >> v.L >> n1 >> n2;
+    if (ss.fail() || v.k < 0 || v.k > 20 || v.L < 1 || v.L > 10 || n1 < 0 || n1 > 5 || n2 < 0 || n2 > 3)
+      return fail("vocabulary text: not a correct text file (header: k 0..20, L 1..10, scoring 0..5, weighting 0..3)");
+    v.scoring = n1; v.weighting = n2;
+  }
+  v.parent.assign(1, 0); v.is_leaf.assign(1, 0); v.desc.assign(32, 0); v.weight.assign(1, 0.0);
+  int lineno = 1;
+  while (next_line(line)) {
+    ++lineno;
+    if (blank(line)) continue;
+    const char* p = line.c_str();
+    char* end = nullptr;
+    long vals[34];
+    for (int i = 0; i < 34; ++i) {
+      vals[i] = std::strtol(p, &end, 10);
+      if (end == p) return fail("vocabulary text: line " + std::to_string(lineno) + " ends early (parent, leaf flag, 32 descriptor bytes, weight)");
+      p = end;
+    }
+    const double w = std::strtod(p, &end);
+    if (end == p) return fail("vocabulary text: line " + std::to_string(lineno) + " has no weight");
+    v.parent.push_back((int)vals[0]); v.is_leaf.push_back(vals[1] > 0 ? 1 : 0);
+    for (int i = 0; i < 32; ++i) v.desc.push_back((uint8_t)vals[2 + i]);
+    v.weight.push_back(w);
+  }
+  *out = std::move(v);
+  return true;
+}
+
+bool LoadVocabularyText(const std::string& path, VocabularyText* out, std::string* why) {
+  std::ifstream f(path.c_str(), std::ios::binary);
+  if (!f) { if (why) *why = "vocabulary text: cannot open " + path; return false; }
+  std::stringstream ss;
+  ss << f.rdbuf();
+  return ParseVocabularyText(ss.str(), out, why);
+}
+
+std::string FormatVocabularyText(const VocabularyText& v) {
+  std::ostringstream f;
+  f << v.k << " " << v.L << " " << " " << v.scoring << " " << v.weighting << std::endl;
+  for (size_t i = 1; i < v.parent.size(); ++i) {
+    f << v.parent[i] << " ";
+    f << (v.is_leaf[i] ? 1 : 0) << " ";
+    for (int j = 0; j < 32; ++j) f << (int)v.desc[32 * i + (size_t)j] << " ";      // FORB::toString
+    f << " " << (double)v.weight[i] << std::endl;
+  }
+  return f.str();
+}
+
 }  // namespace CubemapSLAM

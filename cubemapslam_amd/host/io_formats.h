@@ -3,6 +3,7 @@
 //   image lists            Examples/cubemap_lafida.cpp:91-107 ("<timestamp> <path>" per line, directory stripped) and
 //                          Examples/cubemap_fangshan.cpp:93-101 ("<timestamp>_<suffix>" file names, one per line)
 //   tracking-time summary  Examples/cubemap_lafida.cpp:160-179
+//   vocabulary text        DBoW2 TemplatedVocabulary.h:1338-1449 (loadFromTextFile / saveToTextFile: ORBvoc.txt)
 // (the TUM key-frame trajectory writer, src/System.cpp:238-268, lives in System::SaveKeyFrameTrajectoryTUM.)
 #ifndef CUBEMAPSLAM_IO_FORMATS_H
 #define CUBEMAPSLAM_IO_FORMATS_H
@@ -41,6 +42,25 @@ ImageList LoadImageListFangshan(const std::string& path);   // cubemap_fangshan.
 // cubemap_lafida.cpp:160-179: sorts the times, median = v[n/2], mean = float sum / n; writes the perf file and returns the text
 // the reference prints to stdout.  vTimesTrack is sorted in place like the reference does.
 std::string WriteTrackingSummary(const std::string& perfSavingPath, std::vector<float>& vTimesTrack, int frame_counter);
+
+// The vocabulary tree as the text format holds it (TemplatedVocabulary.h:1338-1449): a header line "k L  scoring weighting", then one line per node
+// from node 1 on, "parent leaf d0 .. d31  weight".  Node 0 is the root; arrays have one entry per node (the root's are zero).
+struct VocabularyText {
+  int k = 0, L = 0, scoring = 0, weighting = 0;
+  std::vector<int> parent;
+  std::vector<uint8_t> is_leaf;
+  std::vector<uint8_t> desc;        // nodes x 32
+  std::vector<double> weight;
+  int nodes() const { return (int)parent.size(); }
+};
+// The parser reads what loadFromTextFile reads, with one known difference: empty lines are skipped (the reference turns a trailing empty line
+// into an extra child of the root with an uninitialised descriptor).  A header outside the reference's ranges (:1359) or a node line that ends
+// early is refused with the reason in *why; the tree's shape is checked by cms_vocab_relayout (csrc/cms_vocab_core.h).
+bool ParseVocabularyText(const std::string& text, VocabularyText* out, std::string* why);
+bool LoadVocabularyText(const std::string& path, VocabularyText* out, std::string* why);
+// saveToTextFile's bytes (:1429-1449): "<k> <L>  <scoring> <weighting>\n", then "<parent> <0|1> <32 bytes, each followed by a space> <weight>\n"
+// with the weight in the stream's default format (6 significant digits)
+std::string FormatVocabularyText(const VocabularyText& v);
 
 }  // namespace CubemapSLAM
 #endif

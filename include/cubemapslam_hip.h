@@ -512,6 +512,55 @@ typedef struct {
 int cms_kfstore_search_by_bow(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_job* jobs, float nnratio,
                               int check_orientation, int* kf_idx /* sum of jobs[j].n, job after job */, int* n_matches /* njobs */);
 
+/* ---- Frame::ComputeBoW (src/Frame.cpp:719-726; Tracking.cpp:570, :993) and KeyFrame::ComputeBoW (src/KeyFrame.cpp:94-103; LocalMapping.cpp:142,
+ * Tracking.cpp:472-473): mpORBvocabulary->transform(descriptors, mBowVec, mFeatVec, 4) (DBoW2 TemplatedVocabulary.h:1127-1259) on the device, so that
+ * SearchByBoW and CreateNewMapPoints take the FeatureVector from where the descriptors already are.  The numeric definition is csrc/cms_vocab_core.h
+ * (one source for the host build and the kernels); every output is bit-equal to the host build's: word ids ascending with their double values,
+ * node ids ascending, a node's features in feature order.  A feature whose word has weight <= 0 enters neither vector.  A descent that ends on a leaf
+ * above level L - levelsup reports that leaf as the feature's node (the reference leaves the id unset).
+ *
+ * cms_vocab: the tree on one device, read-only after creation, shared by any number of contexts and stores of that device.  The arrays are the text
+ * format's (loadFromTextFile, :1338-1424): node 0 is the root (its entries are not read), node i > 0 has parent[i] < i, is_leaf[i] != 0 marks a word, word
+ * ids count the leaves in node order, children are in ascending node id, desc is n_nodes x 32 bytes, weight n_nodes doubles.  CMS_ERR_ARG (with the
+ * reason in cms_last_error) for k outside 0..20, L outside 1..10, scoring outside 0..5, weighting outside 0..3, a parent id that is not smaller than the
+ * node's own, a leaf with children, an inner node without, more than k children, no words, or more than 2^21 nodes.
+ * cms_vocab_info: info[7] = k, L, scoring, weighting, nodes, words, device. */
+typedef struct cms_vocab cms_vocab;
+int cms_vocab_create(cms_vocab** out, int device, int k, int L, int scoring, int weighting, int n_nodes, const int* parent, const uint8_t* is_leaf,
+                     const uint8_t* desc, const double* weight);
+void cms_vocab_destroy(cms_vocab* v);
+int cms_vocab_info(const cms_vocab* v, int* info);
+/* Developer aid (tools/prof_bow_transform.py), one thread at a time: while on, every ComputeBoW call of the process records events around its two
+ * launches; after the call cms_vocab_profile_get gives ms2[0] = k_vocab_descend and ms2[1] = k_vocab_build of the last one. */
+int cms_vocab_profile_enable(int on);
+int cms_vocab_profile_get(float* ms2);
+/* Stand-alone: n descriptors from the host (n x 32 bytes, n <= 16383: more is CMS_ERR_UNSUPPORTED), on ctx's stream.  word_id / word_val / node_id /
+ * node_feat hold up to n entries, node_off n + 1; node_off[*nnodes] is the number of features listed.  levelsup >= 0. */
+int cms_vocab_transform(cms_vocab* v, cms_ctx* ctx, int n, const uint8_t* desc, int levelsup, int* nwords, int* word_id, double* word_val, int* nnodes,
+                        int* node_id, int* node_off, int* node_feat);
+/* Frame rows rows[i] of ctx (n[i] key points each, as cms_frames_fetch reports them), all in one launch sequence on ctx's stream; the descriptors
+ * are read where cms_frames_process (or cms_area_set_descriptors) left them and the results stay resident per row until the next batch is processed.  Synchronous: the call
+ * returns with the rows' counts known to the host.  A row named twice, a count beyond the row or a vocabulary on another device is CMS_ERR_ARG. */
+int cms_frames_compute_bow(cms_ctx* ctx, cms_vocab* v, int levelsup, int n_rows, const int* rows, const int* n);
+/* What the host needs for mBowVec, mFeatVec and KeyFrameDatabase.  *nwords / *nnodes are always delivered; a capacity that cannot hold its array
+ * (node_off needs node_cap + 1 entries, node_feat up to the row's key-point count) makes the call CMS_ERR_OVERFLOW with nothing copied.  A row without
+ * a computed BoW is CMS_ERR_ARG. */
+int cms_frames_fetch_bow(cms_ctx* ctx, int b, int* nwords, int* word_id, double* word_val, int word_cap, int* nnodes, int* node_id, int* node_off,
+                         int* node_feat, int node_cap, int feat_cap);
+/* KeyFrame::ComputeBoW on the resident descriptors of the named slots: writes feat_node / node_feat / node_id / node_off and the record's node count
+ * in the slot's layout -- after cms_kfstore_put_from_frames(... nnodes = 0 ...) and this call a slot is byte-identical to one put with the
+ * host-computed FeatureVector -- and keeps the BowVector per slot (cms_kfstore_fetch_bow).  On the store's stream, synchronous.  If any slot's
+ * FeatureVector has more nodes than the store's max_nodes the call is CMS_ERR_OVERFLOW and NO slot is changed. */
+int cms_kfstore_compute_bow(cms_kfstore* st, cms_vocab* v, int levelsup, int n_slots, const int* slots);
+/* The slot's BowVector and, when node_off is not NULL, its FeatureVector (nnodes may be NULL), with capacities as cms_frames_fetch_bow.  A slot that
+ * was refilled (cms_kfstore_put / put_from_frame(s)) since its last cms_kfstore_compute_bow has no BowVector: CMS_ERR_ARG. */
+int cms_kfstore_fetch_bow(cms_kfstore* st, int slot, int* nwords, int* word_id, double* word_val, int word_cap, int* nnodes, int* node_id, int* node_off,
+                          int* node_feat, int node_cap, int feat_cap);
+/* cms_kfstore_search_by_bow with the frame side's FeatureVector taken from the row's resident result (cms_frames_compute_bow): the jobs' nnodes /
+ * node_id / node_off / node_feat are not read.  A row without a computed BoW, or one computed for another n, is CMS_ERR_ARG. */
+int cms_kfstore_search_by_bow_frames(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_job* jobs, float nnratio, int check_orientation,
+                                     int* kf_idx, int* n_matches);
+
 /* ---- ORBMatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, const float th, const int ORBdist)
  * (include/ORBMatcher.h:64, src/ORBMatcher.cpp:253-378), the guided search of Tracking::Relocalization: twice per accepted PnP pose
  * (src/Tracking.cpp:1101 with th 10 / ORBdist 100, :1115 with th 3 / ORBdist 64), between the PoseOptimization calls (cms_pose_*) and behind the candidate

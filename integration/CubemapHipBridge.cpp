@@ -5,11 +5,16 @@
 #include "CubemapHipBridge.h"
 
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <fstream>
+#include <sstream>
 #include <map>
 #include <set>
 #include <mutex>
 #include <stdexcept>
+#include <unistd.h>
 
 #include "CamModelGeneral.h"
 #include "Converter.h"
@@ -759,6 +764,91 @@ cms_init* CreateInitializer(int maxJobs, int maxMatches, int maxKeys1, int maxHy
   cms_init* init = nullptr;
   check(cms_init_create(g_device, maxJobs, maxMatches, maxKeys1, maxHypotheses, &init), "cms_init_create");
   return init;
+}
+
+// ------------------------------------------------------------------------------------------------ ComputeBoW
+cms_vocab* CreateVocabulary(const ORBVocabulary& voc, const std::string& scratchPrefix) {
+  if (voc.empty()) throw std::runtime_error("Hip::CreateVocabulary: empty vocabulary");
+  // one file per process and call: two processes in one directory must not share it
+  static int calls = 0;
+  std::ostringstream name;
+  name << scratchPrefix << "." << (long)getpid() << "." << calls++ << ".txt";
+  const std::string scratchFile = name.str();
+  voc.saveToTextFile(scratchFile);
+  std::string text;
+  {
+    std::ifstream f(scratchFile.c_str(), std::ios::binary);
+    if (!f) throw std::runtime_error("Hip::CreateVocabulary: cannot write or read back " + scratchFile + " (pass a prefix in a writable directory)");
+    std::stringstream ss;
+    ss << f.rdbuf();
+    text = ss.str();
+  }
+  std::remove(scratchFile.c_str());
+  // "k L  scoring weighting", then per node "parent leaf d0 .. d31  weight" (TemplatedVocabulary.h:1429-1449); node 0 is the root
+  const char* p = text.c_str();
+  char* end = nullptr;
+  long hdr[4];
+  for (int i = 0; i < 4; ++i) { hdr[i] = std::strtol(p, &end, 10); if (end == p) throw std::runtime_error("Hip::CreateVocabulary: bad header"); p = end; }
+  std::vector<int> parent(1, 0);
+  std::vector<uint8_t> leaf(1, 0), desc(32, 0);
+  std::vector<double> weight(1, 0.0);
+  for (;;) {
+    const long pid = std::strtol(p, &end, 10);
+    if (end == p) break;      // the end of the text
+    p = end;
+    long v[33];
+    for (int i = 0; i < 33; ++i) { v[i] = std::strtol(p, &end, 10); if (end == p) throw std::runtime_error("Hip::CreateVocabulary: a node line ends early"); p = end; }
+    const double w = std::strtod(p, &end);
+    if (end == p) throw std::runtime_error("Hip::CreateVocabulary: a node line has no weight");
+    p = end;
+    parent.push_back((int)pid); leaf.push_back(v[0] > 0 ? 1 : 0);
+    for (int i = 0; i < 32; ++i) desc.push_back((uint8_t)v[1 + i]);
+    weight.push_back(w);
+  }
+  cms_vocab* out = nullptr;
+  check(cms_vocab_create(&out, g_device, (int)hdr[0], (int)hdr[1], (int)hdr[2], (int)hdr[3], (int)parent.size(), parent.data(), leaf.data(), desc.data(), weight.data()),
+        "cms_vocab_create");
+  return out;
+}
+
+namespace {
+void fill_vectors(int nwords, const std::vector<int>& wid, const std::vector<double>& wval, int nnodes, const std::vector<int>& nid, const std::vector<int>& noff,
+                  const std::vector<int>& nfeat, DBoW2::BowVector& bow, DBoW2::FeatureVector* fv) {
+  bow.clear();
+  for (int i = 0; i < nwords; ++i) bow.insert(bow.end(), std::make_pair((DBoW2::WordId)wid[i], wval[i]));
+  if (!fv) return;
+  fv->clear();
+  for (int e = 0; e < nnodes; ++e)
+    fv->insert(fv->end(), std::make_pair((DBoW2::NodeId)nid[e], std::vector<unsigned int>(nfeat.begin() + noff[e], nfeat.begin() + noff[e + 1])));
+}
+}  // namespace
+
+void ComputeBoW(cms_vocab* vocab, cms_ctx* frameCtx, Frame& F) {
+  if (!F.mBowVec.empty()) return;      // Frame.cpp:721
+  const int row = 0, n = F.N;
+  check(cms_frames_compute_bow(frameCtx, vocab, 4, 1, &row, &n), "cms_frames_compute_bow");
+  const size_t cap = (size_t)std::max(n, 1);
+  std::vector<int> wid(cap), nid(cap), noff(cap + 1), nfeat(cap);
+  std::vector<double> wval(cap);
+  int nwords = 0, nnodes = 0;
+  check(cms_frames_fetch_bow(frameCtx, 0, &nwords, wid.data(), wval.data(), (int)cap, &nnodes, nid.data(), noff.data(), nfeat.data(), (int)cap, (int)cap), "cms_frames_fetch_bow");
+  fill_vectors(nwords, wid, wval, nnodes, nid, noff, nfeat, F.mBowVec, &F.mFeatVec);
+}
+
+void ComputeBoW(cms_vocab* vocab, cms_kfstore* store, KeyFrame* pKF) {
+  if (!pKF->mBowVec.empty() && !pKF->mFeatVec.empty()) return;      // KeyFrame.cpp:96
+  StoreBook& b = book(store);
+  std::lock_guard<std::mutex> lk(b.mu);      // the slot is neither released nor refilled while the call runs
+  const int slot = slot_locked(b, pKF);
+  if (slot < 0) throw std::runtime_error("Hip::ComputeBoW: the key frame is not in the store");
+  check(cms_kfstore_compute_bow(store, vocab, 4, 1, &slot), "cms_kfstore_compute_bow");
+  const size_t cap = (size_t)std::max(pKF->N, 1);
+  std::vector<int> wid(cap), nid(cap), noff(cap + 1), nfeat(cap);
+  std::vector<double> wval(cap);
+  int nwords = 0, nnodes = 0;
+  check(cms_kfstore_fetch_bow(store, slot, &nwords, wid.data(), wval.data(), (int)cap, &nnodes, nid.data(), noff.data(), nfeat.data(), (int)cap, (int)cap),
+        "cms_kfstore_fetch_bow");
+  fill_vectors(nwords, wid, wval, nnodes, nid, noff, nfeat, pKF->mBowVec, &pKF->mFeatVec);
 }
 
 }  // namespace Hip

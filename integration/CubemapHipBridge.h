@@ -7,6 +7,7 @@
 #include <vector>
 #include <opencv2/opencv.hpp>
 #include "cubemapslam_hip.h"
+#include "ORBVocabulary.h"
 
 class Frame;
 class KeyFrame;
@@ -135,5 +136,18 @@ class Initializer {
   int mMaxIterations;
 };
 cms_init* CreateInitializer(int maxJobs, int maxMatches, int maxKeys1, int maxHypotheses);
+// ---- ComputeBoW (src/Frame.cpp:719-726, src/KeyFrame.cpp:94-103; Tracking.cpp:570, :993, :472-473, LocalMapping.cpp:142): the vocabulary's
+// transform(descriptors, mBowVec, mFeatVec, 4) on the device.  CreateVocabulary sends the tree to the device once, at start-up.  DBoW2 keeps its nodes
+// protected and offers no accessor, so the tree travels through the text format: saveToTextFile into "<scratchPrefix>.<pid>.<call>.txt" (about 140 MB
+// for ORBvoc.txt; the directory must be writable), read back, removed.  PRECISION: saveToTextFile prints weights with 6 significant digits.  A
+// vocabulary that was itself loaded from such a text file (ORBvoc.txt: what System does) reaches the device with exactly the host's weights; one that
+// was trained in this process or loaded from the binary / YAML formats does not -- save and reload it as text on the host first, or the device's
+// BowVector values differ from the host's in the seventh digit.  ComputeBoW(vocab, frameCtx, F) is
+// Frame::ComputeBoW for the frame `frameCtx` extracted last (slot 0 of its batch, F.N key points): it fills F.mBowVec / F.mFeatVec when mBowVec is
+// empty and leaves the FeatureVector resident for cms_kfstore_search_by_bow_frames.  ComputeBoW(vocab, store, pKF) is KeyFrame::ComputeBoW for a key
+// frame that entered the store (InsertKeyFrame): it fills pKF->mBowVec / mFeatVec when either is empty and leaves the slot's FeatureVector resident.
+cms_vocab* CreateVocabulary(const ORBVocabulary& voc, const std::string& scratchPrefix = "cms_vocabulary_upload");
+void ComputeBoW(cms_vocab* vocab, cms_ctx* frameCtx, Frame& F);
+void ComputeBoW(cms_vocab* vocab, cms_kfstore* store, KeyFrame* pKF);
 }  // namespace Hip
 #endif
