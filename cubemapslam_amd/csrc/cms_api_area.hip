@@ -1,5 +1,5 @@
 // cms_api_area.hip -- host side of the frame grid + window query (Frame::AssignFeaturesToGrid / GetFeaturesInArea), included by
-// cms_lib.hip after cms_api_frames.hip (uses cms_ctx, cms_fail, HIPCHK, cms_scratch and the helpers of cms_api_util.h).  cms_area_args /
+// cms_lib.hip after cms_api_frames.hip (uses cms_ctx, cms_fail, HIPCHK, the context's CmsStage and the helpers of cms_api_util.h).  cms_area_args /
 // cms_area_queries / cms_area_launch are the only place that fills and launches the window query's two kernels: the frame entries below and
 // the key-frame store's Fuse (cms_api_tri.hip) go through them.
 #include <vector>
@@ -130,10 +130,10 @@ extern "C" int cms_features_in_area(cms_ctx* c, int b, int nq, const float* qx, 
   HIPCHK(hipSetDevice(c->device));
   const size_t qb = (size_t)nq * 4;
   const size_t bytes = 5 * qb + qb /*cnt*/ + (qb + 4) /*off*/ + (size_t)cap * 4 + 64;
-  int rc = cms_scratch(c, bytes);
-  if (rc) return rc;
-  uint8_t* p = (uint8_t*)c->d_match;
   hipStream_t s = c->stream;
+  int rc = c->stage.reserve(s, bytes, 0);
+  if (rc) return rc;
+  uint8_t* p = c->stage.d;
   void* dq[5];
   const void* hq[5] = {qx, qy, qr, qmin, qmax};
   for (int i = 0; i < 5; ++i) { dq[i] = p; p += qb; HIPCHK(hipMemcpyAsync(dq[i], hq[i], qb, hipMemcpyHostToDevice, s)); }

@@ -1,7 +1,7 @@
 // cms_api_bow.hip -- host side of ORBMatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (src/ORBMatcher.cpp:409-539), included by
-// cms_lib.hip after cms_api_tri.hip (cms_kfstore).  Both entries stage what comes from the host (FeatureVectors, skip flags, job records; for the
-// stand-alone entry the key frame too) in the context's pinned block (laid out with CmsBlock, 4 bytes of slack behind every piece), make ONE copy
-// to the device, ONE launch of k_search_by_bow and ONE copy back.
+// cms_lib.hip after cms_api_tri.hip (cms_kfstore).  The stand-alone entry here and the resident ones (cms_api_vocab.hip, over bow_run) stage what
+// comes from the host (FeatureVectors, skip flags, job records; for the stand-alone entry the key frame too) in the pinned block of the context's
+// CmsStage (laid out with CmsBlock, 4 bytes of slack behind every piece), make ONE copy to the device, ONE launch of k_search_by_bow and ONE copy back.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -40,19 +40,18 @@ struct BowStage {
 // stage -> device -> launch -> back.  jobs[j] has every device pointer filled except the ones given as offsets in rel[j] (pointer fields that
 // hold an offset into the input block, marked by the caller), which are rebased here once the block's device address is known.
 int bow_run(cms_ctx* c, std::vector<CmsBowJob>& jobs, const std::vector<std::vector<const void**>>& rel, std::vector<BowStage>& pieces, CmsBlock blk,
-            float nnratio, int check_orientation, int* kf_idx, int* n_matches) {
+            float nnratio, int check_orientation, int* kf_idx, int* n_matches, const char* who) {
   const int njobs = (int)jobs.size();
   size_t total_n = 0;
   for (const CmsBowJob& q : jobs) total_n += (size_t)q.n;
   const size_t o_jobs = blk.take((size_t)njobs * sizeof(CmsBowJob)), o_idx = blk.take(total_n * 4, 4), o_nm = blk.take((size_t)njobs * 4);      // behind the staged pieces
   const size_t bytes = blk.size;
-  int rc = cms_scratch(c, bytes);
+  hipStream_t s = c->stream;
+  int rc = c->stage.reserve(s, bytes, bytes);
   if (rc) return rc;
-  rc = cms_hstage(c, bytes);
-  if (rc) return rc;
-  uint8_t* p = (uint8_t*)c->d_match;
-  uint8_t* h = c->h_stage;
-  for (const BowStage& s : pieces) if (s.bytes) std::memcpy(h + s.at, s.src, s.bytes);
+  uint8_t* p = c->stage.d;
+  uint8_t* h = c->stage.h;
+  for (const BowStage& g : pieces) if (g.bytes) std::memcpy(h + g.at, g.src, g.bytes);
   size_t cursor = 0;
   for (int j = 0; j < njobs; ++j) {
     CmsBowJob& q = jobs[(size_t)j];
@@ -61,12 +60,12 @@ int bow_run(cms_ctx* c, std::vector<CmsBowJob>& jobs, const std::vector<std::vec
     cursor += (size_t)q.n;
   }
   std::memcpy(h + o_jobs, jobs.data(), (size_t)njobs * sizeof(CmsBowJob));
-  hipStream_t s = c->stream;
-  HIPCHK(hipMemcpyAsync(p, h, o_idx, hipMemcpyHostToDevice, s));
+  rc = c->stage.up(s, o_idx, who);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_search_by_bow, dim3(njobs), dim3(CMS_BOW_THREADS), 0, s, (const CmsBowJob*)(p + o_jobs), nnratio, check_orientation);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(h + o_idx, p + o_idx, bytes - o_idx, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  rc = c->stage.back_and_wait(s, o_idx, bytes, who);
+  if (rc) return rc;
   if (total_n) std::memcpy(kf_idx, h + o_idx, total_n * 4);
   std::memcpy(n_matches, h + o_nm, (size_t)njobs * 4);
   return CMS_OK;
@@ -116,54 +115,5 @@ extern "C" int cms_search_by_bow(cms_ctx* c, int b, int n, int nnodes, const int
   q.kf_nnodes = kf->nnodes; q.f_nnodes = nnodes; q.n = n;
   const size_t sb = (size_t)b * c->g.kp_cap;
   q.f_kp = (const CmsKeyPoint*)c->d_kps + sb; q.f_desc = (const uint4*)(c->d_desc + 32 * sb);
-  return bow_run(c, jobs, rel, pieces, blk, nnratio, check_orientation, kf_idx, n_matches);
-}
-
-// Relocalization's candidate loop (Tracking.cpp:1019-1040) or one TrackReferenceKeyFrame per camera stream on resident key frames: ONE launch on
-// src's stream.  Nothing is enqueued on the store's stream; the copies of cms_kfstore_put_from_frame(s) that filled a named slot are waited for on
-// the device (their events: the copy may still be in flight when it ran on another context's stream).
-extern "C" int cms_kfstore_search_by_bow(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_job* jobs, float nnratio, int check_orientation,
-                                         int* kf_idx, int* n_matches) {
-  if (!st || !src || njobs < 0 || (njobs > 0 && (!jobs || !n_matches))) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow: bad argument");
-  if (njobs == 0) return CMS_OK;
-  if (src->device != st->c->device) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow: the frame context and the store must share the device");
-  std::vector<uint8_t> seen;
-  size_t total_n = 0;
-  for (int j = 0; j < njobs; ++j) {
-    const cms_bow_job& q = jobs[j];
-    if (q.slot < 0 || q.slot >= st->maxkf || !st->used[(size_t)q.slot]) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow: empty slot");
-    int rc = bow_check_frame(src, q.b, q.n, "cms_kfstore_search_by_bow: bad frame");
-    if (rc) return rc;
-    rc = bow_check_fv(q.n, q.nnodes, q.node_id, q.node_off, q.node_feat, &seen, "cms_kfstore_search_by_bow: bad frame FeatureVector");
-    if (rc) return rc;
-    total_n += (size_t)q.n;
-  }
-  if (total_n > 0 && !kf_idx) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow: bad argument");
-  HIPCHK(hipSetDevice(src->device));
-  hipStream_t s = src->stream;
-  for (int j = 0; j < njobs; ++j) {
-    const auto& call = st->ff_call[(size_t)jobs[j].slot];
-    if (call) HIPCHK(hipStreamWaitEvent(s, call->ev, 0));
-  }
-  std::vector<CmsBowJob> dj((size_t)njobs);
-  std::vector<std::vector<const void**>> rel((size_t)njobs);
-  std::vector<BowStage> pieces;
-  CmsBlock blk;
-  for (int j = 0; j < njobs; ++j) {
-    const cms_bow_job& q = jobs[j];
-    const CmsTriKF& k = st->h_kf[(size_t)q.slot];
-    CmsBowJob& d = dj[(size_t)j];
-    std::memset(&d, 0, sizeof(d));
-    d.kf_kp = st->d_kp + k.f0; d.kf_desc = (const uint4*)(st->d_desc + 32 * (size_t)k.f0); d.kf_mp = st->d_mp + k.f0;
-    d.kf_nid = st->d_nid + k.node0; d.kf_noff = st->d_noff + k.noff0; d.kf_nfeat = st->d_nfeat + k.nfeat0; d.kf_nnodes = k.nnodes;
-    if (q.kf_skip) bow_put(pieces, blk, rel[(size_t)j], d.kf_skip, q.kf_skip, (size_t)k.n);
-    const int ffeat = q.nnodes > 0 ? q.node_off[q.nnodes] : 0;
-    bow_put(pieces, blk, rel[(size_t)j], d.f_nid, q.node_id, 4 * (size_t)q.nnodes);
-    bow_put(pieces, blk, rel[(size_t)j], d.f_noff, q.node_off, q.nnodes > 0 ? 4 * ((size_t)q.nnodes + 1) : 0);
-    bow_put(pieces, blk, rel[(size_t)j], d.f_nfeat, q.node_feat, 4 * (size_t)ffeat);
-    d.f_nnodes = q.nnodes; d.n = q.n;
-    const size_t sb = (size_t)q.b * src->g.kp_cap;
-    d.f_kp = (const CmsKeyPoint*)src->d_kps + sb; d.f_desc = (const uint4*)(src->d_desc + 32 * sb);
-  }
-  return bow_run(src, dj, rel, pieces, blk, nnratio, check_orientation, kf_idx, n_matches);
+  return bow_run(c, jobs, rel, pieces, blk, nnratio, check_orientation, kf_idx, n_matches, "cms_search_by_bow");
 }

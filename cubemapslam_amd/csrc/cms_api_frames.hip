@@ -1,6 +1,6 @@
 // cms_api_frames.hip -- host side of the C-ABI for the frame path (context, LUT / table construction, launches).
 // Included by cms_lib.hip (single translation unit together with the kernels).  Includes cms_api_util.h behind cms_ctx: cms_align, CmsBlock (block
-// layouts), cms_retry_capacity and the small argument helpers that every cms_api_*.hip file behind this one uses.
+// layouts), the HIP side of CmsStage (cms_stage.h: the context's scratch and pinned staging blocks), cms_retry_capacity and the small argument helpers that every cms_api_*.hip file behind this one uses.
 #include <chrono>
 #include <thread>
 #include <hip/hip_runtime.h>
@@ -13,6 +13,7 @@
 #include <vector>
 #include "../../include/cubemapslam_hip.h"
 #include "cms_types.h"
+#include "cms_stage.h"
 #include "orb_pattern.inc"
 
 // CMS_CTX_CU_MASK=w0,w1,...,w7 (hex words, bit i of word j = compute unit 32 j + i of the runtime's enumeration): streams created while it is set
@@ -38,6 +39,9 @@ static bool cms_cu_mask_from_env(uint32_t* words, int* n_words) {
 struct CmsCtxBow;
 static void cms_ctx_bow_free(CmsCtxBow* b);
 static void cms_ctx_bow_invalidate(CmsCtxBow* b);      // a new batch: the rows' results belong to the frames they were computed from
+
+struct CmsHipMem;      // cms_api_util.h
+using CmsStage = CmsStageT<CmsHipMem>;
 
 static thread_local std::string g_cms_err;
 static int cms_fail(int code, const char* what, hipError_t e = hipSuccess) {
@@ -93,11 +97,9 @@ struct cms_ctx {
   int dist_bounds_scaled = 0;      // cms_set_distance_bounds_mode: map points' distance bounds come from the public MapPoint getters
   hipEvent_t ev_block = nullptr; int last_batch = 0;                     // cms_frames_sync after a large batch polls this event between short sleeps instead of spinning
   hipEvent_t ev_extracted = nullptr; bool extracted_recorded = false;   // end of the last cms_frames_process (cms_stream_wait_extracted)
-  uint8_t* h_stage = nullptr; size_t h_stage_bytes = 0;          // pinned staging of the one-frame host entries (one copy each way)
   CmsKeyPoint* d_kps = nullptr; uint32_t* d_aux = nullptr; uint8_t* d_desc = nullptr; int* d_kp_cnt = nullptr;
   uint32_t* d_order = nullptr; uint32_t* d_aux_sorted = nullptr; int* d_walk_cnt = nullptr; float* d_rays = nullptr;      // the batch's key-point walk: the order k_describe works in (k_cull)
-  // match scratch
-  void* d_match = nullptr; size_t match_bytes = 0;
+  CmsStage stage;      // scratch block and pinned staging of the host-buffer entries (one copy each way), on `stream`
   // profiling
   bool prof = false;
   bool desc_spatial = false;         // k_describe works through the batch's key points in spatial order, an eighth of the walk per XCD (CMS_DESC_SPATIAL_ORDER=1)
@@ -210,12 +212,12 @@ static void cms_ctx_free(cms_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   void* ptrs[] = {c->d_fish, c->d_lut, c->d_pyr, c->d_mask, c->d_tab, c->d_pattern, c->d_cand, c->d_node, c->d_cand_cnt,
-                  c->d_overflow, c->d_qt_out, c->d_qt_cnt, c->d_kps, c->d_aux, c->d_order, c->d_aux_sorted, c->d_desc, c->d_kp_cnt, c->d_match, c->d_cell_cand,
+                  c->d_overflow, c->d_qt_out, c->d_qt_cnt, c->d_kps, c->d_aux, c->d_order, c->d_aux_sorted, c->d_desc, c->d_kp_cnt, c->d_cell_cand,
                   c->d_cell_cnt, c->d_cells_all, c->d_cells_nz, c->d_area_sorted, c->d_area_cell_start, c->d_area_nvalid, c->d_area_psum, c->d_area_tmp, c->d_walk_cnt, c->d_rays, c->d_rtiles};
   for (void* p : ptrs) if (p) hipFree(p);
   cms_ctx_bow_free(c->bow);
   if (c->h_fish_stage) (void)hipHostFree(c->h_fish_stage);
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
+  c->stage.release();
   for (int i = 0; i < 8; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
   if (c->ev_extracted) hipEventDestroy(c->ev_extracted);
   if (c->ev_block) hipEventDestroy(c->ev_block);
@@ -801,7 +803,6 @@ extern "C" int cms_extract(cms_ctx* c, const uint8_t* cubemap, int cstride, cms_
   if (rc) return rc;
   return cms_frames_fetch(c, 0, kps, desc, cap, n);
 }
-static int cms_hstage(cms_ctx* c, size_t bytes);
 // One frame, host buffers in and out: ONE synchronisation.  The image leaves from the pinned upload staging without a wait, the kernels follow,
 // and overflow flag | key-point count | key points | descriptors come back as four asynchronous copies into the pinned result staging behind
 // them (the upload, cms_frames_sync and cms_frames_fetch one after the other were five synchronous round trips of 15-20 us each).
@@ -821,10 +822,10 @@ static int cms_remap_extract_impl(cms_ctx* c, const uint8_t* fisheye, int fstrid
   const int m = std::min(cap, c->g.kp_cap);
   const size_t o_kp = 256, o_desc = o_kp + cms_align((size_t)m * sizeof(cms_keypoint)), o_rays = o_desc + cms_align((size_t)m * 32),
                total = o_rays + (rays ? (size_t)m * 12 : 0);
-  rc = cms_hstage(c, total);
-  if (rc) return rc;
-  uint8_t* h = c->h_stage;
   hipStream_t s = c->stream;
+  rc = c->stage.reserve(s, 0, total);
+  if (rc) return rc;
+  uint8_t* h = c->stage.h;
   HIPCHK(hipMemcpyAsync(h, c->d_overflow, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(h + 64, c->d_kp_cnt, sizeof(int), hipMemcpyDeviceToHost, s));
   if (m > 0 && kps) HIPCHK(hipMemcpyAsync(h + o_kp, c->d_kps, (size_t)m * sizeof(cms_keypoint), hipMemcpyDeviceToHost, s));
@@ -916,22 +917,6 @@ extern "C" int cms_hamming_best2_device(cms_ctx* c, const void* qdesc, const voi
   HIPCHK(hipGetLastError());
   return CMS_OK;
 }
-static int cms_scratch(cms_ctx* c, size_t bytes) {
-  if (bytes <= c->match_bytes) return CMS_OK;
-  if (c->d_match) hipFree(c->d_match);
-  c->d_match = nullptr; c->match_bytes = 0;
-  HIPCHK(hipMalloc(&c->d_match, bytes));
-  c->match_bytes = bytes;
-  return CMS_OK;
-}
-static int cms_hstage(cms_ctx* c, size_t bytes) {
-  if (bytes <= c->h_stage_bytes) return CMS_OK;
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  c->h_stage = nullptr; c->h_stage_bytes = 0;
-  HIPCHK(hipHostMalloc((void**)&c->h_stage, bytes + bytes / 2));
-  c->h_stage_bytes = bytes + bytes / 2;
-  return CMS_OK;
-}
 extern "C" int cms_hamming_best2(cms_ctx* c, const uint8_t* qdesc, int nq, const uint8_t* tdesc, int nt, const int* cand_off,
                                  const int* cand_idx, const int* t_level, const uint8_t* t_excluded, int* best_idx, int* best_dist,
                                  int* best_level, int* second_dist, int* second_level) {
@@ -945,10 +930,10 @@ extern "C" int cms_hamming_best2(cms_ctx* c, const uint8_t* qdesc, int nq, const
   CmsBlock blk;
   const size_t oq = blk.take((size_t)nq * 32), ot = blk.take((size_t)nt * 32, 32), ooff = blk.take((size_t)(nq + 1) * 4), oidx = blk.take((size_t)ncand * 4, 4),
                olv = blk.take((size_t)nt * 4, 4), oex = blk.take((size_t)nt, 4), oout = blk.take((size_t)nq * 4 * 5);
-  int rc = cms_scratch(c, blk.size);
-  if (rc) return rc;
-  uint8_t* base = (uint8_t*)c->d_match;
   hipStream_t s = c->stream;
+  int rc = c->stage.reserve(s, blk.size, 0);
+  if (rc) return rc;
+  uint8_t* base = c->stage.d;
   HIPCHK(hipMemcpyAsync(base + oq, qdesc, (size_t)nq * 32, hipMemcpyHostToDevice, s));
   if (nt > 0) HIPCHK(hipMemcpyAsync(base + ot, tdesc, (size_t)nt * 32, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(base + ooff, cand_off, (size_t)(nq + 1) * 4, hipMemcpyHostToDevice, s));
@@ -973,10 +958,10 @@ extern "C" int cms_hamming_matrix(cms_ctx* c, const uint8_t* a, int na, const ui
   HIPCHK(hipSetDevice(c->device));
   CmsBlock blk;
   const size_t oa = blk.take((size_t)na * 32), ob = blk.take((size_t)nb * 32), oo = blk.take((size_t)na * nb * 2);
-  int rc = cms_scratch(c, blk.size);
-  if (rc) return rc;
-  uint8_t* base = (uint8_t*)c->d_match;
   hipStream_t s = c->stream;
+  int rc = c->stage.reserve(s, blk.size, 0);
+  if (rc) return rc;
+  uint8_t* base = c->stage.d;
   HIPCHK(hipMemcpyAsync(base + oa, a, (size_t)na * 32, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(base + ob, b, (size_t)nb * 32, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_hamming_matrix, dim3((nb + 15) / 16, (na + 15) / 16), dim3(256), 0, s, (const uint4*)(base + oa), na,

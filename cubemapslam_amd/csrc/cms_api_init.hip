@@ -1,6 +1,6 @@
 // cms_api_init.hip -- host side of the Initializer (src/Initializer.cpp): the cms_init handle, cms_init_two_view and cms_init_two_view_frames
 // (k_init_gather in front); included by cms_lib.hip behind cms_api_frames.hip (cms_ctx, cms_fail, HIPCHK, CmsBlock) and cms_init_kernels.hip.  All
-// jobs of a call are ONE launch sequence on the context's stream: one pinned block up, k_init_hypotheses, k_init_check, k_init_select, one pinned
+// jobs of a call are ONE launch sequence on the context's stream: one pinned block up (the handle's CmsStage), k_init_hypotheses, k_init_check, k_init_select, one pinned
 // block back; ReconstructE's decision (cms_init_core.h, host only) is then taken per job.  Everything that becomes a device index (draws, match
 // indices, counts, offsets) is checked on the host before anything is enqueued (cms_init_job_check.h).
 #include <cstring>
@@ -9,43 +9,26 @@
 
 struct cms_init {
   int device = 0, max_jobs = 0, max_matches = 0, max_keys1 = 0, max_hyp = 0;
-  uint8_t* d = nullptr; size_t d_bytes = 0;      // one device block, grown on demand
-  uint8_t* h = nullptr; size_t h_bytes = 0;      // one pinned block, grown on demand
+  CmsStage blocks;      // one device block and one pinned block, grown on demand
 };
 
 static void cms_init_free(cms_init* p) {
   if (!p) return;
   hipSetDevice(p->device);
-  if (p->d) (void)hipFree(p->d);
-  if (p->h) (void)hipHostFree(p->h);
+  p->blocks.release();
   delete p;
 }
 
 extern "C" int cms_init_create(int device, int max_jobs, int max_matches_total, int max_keys1_total, int max_hyp_total, cms_init** out) {
   if (!out || max_jobs < 1 || max_matches_total < 1 || max_keys1_total < 1 || max_hyp_total < 1) return cms_fail(CMS_ERR_ARG, "cms_init_create: bad argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
-    return cms_fail(CMS_ERR_NO_DEVICE, "cms_init_create: no HIP device (the initializer's device path has no CPU fallback)");
+  const int rcd = cms_check_device(device, "cms_init_create: no HIP device (the initializer's device path has no CPU fallback)");
+  if (rcd) return rcd;
   cms_init* p = new cms_init();
   p->device = device; p->max_jobs = max_jobs; p->max_matches = max_matches_total; p->max_keys1 = max_keys1_total; p->max_hyp = max_hyp_total;
   *out = p;
   return CMS_OK;
 }
 extern "C" void cms_init_destroy(cms_init* p) { cms_init_free(p); }
-
-static int cms_init_reserve(cms_init* p, hipStream_t s, size_t dev_bytes, size_t host_bytes) {
-  if (dev_bytes > p->d_bytes) {
-    if (p->d) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(p->d)); p->d = nullptr; p->d_bytes = 0; }
-    HIPCHK(hipMalloc((void**)&p->d, dev_bytes + dev_bytes / 2));
-    p->d_bytes = dev_bytes + dev_bytes / 2;
-  }
-  if (host_bytes > p->h_bytes) {
-    if (p->h) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipHostFree(p->h)); p->h = nullptr; p->h_bytes = 0; }
-    HIPCHK(hipHostMalloc((void**)&p->h, host_bytes + host_bytes / 2));
-    p->h_bytes = host_bytes + host_bytes / 2;
-  }
-  return CMS_OK;
-}
 
 // frames: cms_init_two_view_frames -- frame 2 is gathered on the device from the context's resident rows
 static int cms_init_run(cms_init* p, cms_ctx* c, int njobs, cms_init_job* jobs, bool frames) {
@@ -75,14 +58,14 @@ static int cms_init_run(cms_init* p, cms_ctx* c, int njobs, cms_init_job* jobs, 
                o_kp1 = blk.take(M * 8), o_ray2 = blk.take(M * 12), o_kp2 = blk.take(M * 8), o_second = blk.take(M * 4), o_mjob = blk.take(M * 4), o_jrow = blk.take(J_ * 4);
   const size_t in_bytes = blk.size;
   const size_t o_out = blk.take(J_ * sizeof(CmsInitOutDev)), o_p3d = blk.take(K1 * 48), o_good = blk.take(K1 * 4);
-  const size_t out_begin = o_out, out_bytes = blk.size - o_out;
+  const size_t out_begin = o_out, out_end = blk.size;
   const size_t o_E = blk.take(Hn * 36), o_score = blk.take(Hn * 4), o_hmask = blk.take((size_t)words * 8), o_keys = blk.take(M * 4);
   HIPCHK(hipSetDevice(p->device));
   hipStream_t s = c->stream;
-  int rc = cms_init_reserve(p, s, blk.size, out_begin + out_bytes);
+  int rc = p->blocks.reserve(s, blk.size, out_end);
   if (rc) return rc;
-  uint8_t* h = p->h;
-  uint8_t* d = p->d;
+  uint8_t* h = p->blocks.h;
+  uint8_t* d = p->blocks.d;
   std::memset(h, 0, in_bytes);
   std::memcpy(h + o_jobs, jd.data(), J_ * sizeof(CmsInitJobDev));
   for (int j = 0; j < njobs; ++j) {
@@ -109,7 +92,8 @@ static int cms_init_run(cms_init* p, cms_ctx* c, int njobs, cms_init_job* jobs, 
       ++k;
     }
   }
-  HIPCHK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+  rc = p->blocks.up(s, in_bytes, "cms_init_two_view");
+  if (rc) return rc;
   if (frames) {
     CmsInitGatherArgs ga = {};
     ga.nmatch = (int)nm; ga.kp_cap = c->g.kp_cap;
@@ -132,8 +116,8 @@ static int cms_init_run(cms_init* p, cms_ctx* c, int njobs, cms_init_job* jobs, 
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_init_select, dim3(njobs), dim3(CMS_INIT_SELECT_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(h + out_begin, d + out_begin, out_bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  rc = p->blocks.back_and_wait(s, out_begin, out_end, "cms_init_two_view");
+  if (rc) return rc;
   for (int j = 0; j < njobs; ++j) {
     const CmsInitJobDev& g = jd[(size_t)j];
     const CmsInitOutDev& o = reinterpret_cast<const CmsInitOutDev*>(h + o_out)[j];

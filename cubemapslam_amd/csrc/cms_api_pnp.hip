@@ -1,7 +1,7 @@
 // cms_api_pnp.hip -- host side of PnPsolver (src/PnPsolver.cpp): cms_pnp_ransac_parameters, the cms_pnp handle, cms_pnp_iterate and
 // cms_pnp_iterate_frames (k_pnp_gather in front, the context's stream instead of the handle's); included by
 // cms_lib.hip behind cms_api_frames.hip (cms_ctx, cms_fail, HIPCHK, CmsBlock) and cms_pnp_kernels.hip.  All jobs of a call are ONE launch
-// sequence on the handle's stream: one pinned block up, k_pnp_hypotheses, k_pnp_inliers, k_pnp_select, one pinned block back.  Everything that
+// sequence on the handle's stream: one pinned block up (the handle's CmsStage), k_pnp_hypotheses, k_pnp_inliers, k_pnp_select, one pinned block back.  Everything that
 // becomes a device index (draws, counts, offsets) is checked on the host before anything is enqueued (cms_pnp_job_check.h).
 #include <climits>
 #include <cmath>
@@ -12,15 +12,13 @@
 struct cms_pnp {
   int device = 0, max_jobs = 0, max_corr = 0, max_hyp = 0;
   hipStream_t stream = nullptr;
-  uint8_t* d = nullptr; size_t d_bytes = 0;      // one device block, grown on demand
-  uint8_t* h = nullptr; size_t h_bytes = 0;      // one pinned block, grown on demand
+  CmsStage blocks;      // one device block and one pinned block, grown on demand
 };
 
 static void cms_pnp_free(cms_pnp* p) {
   if (!p) return;
   hipSetDevice(p->device);
-  if (p->d) (void)hipFree(p->d);
-  if (p->h) (void)hipHostFree(p->h);
+  p->blocks.release();
   if (p->stream) (void)hipStreamDestroy(p->stream);
   delete p;
 }
@@ -47,9 +45,8 @@ extern "C" int cms_pnp_ransac_parameters(int N, double probability, int minInlie
 
 extern "C" int cms_pnp_create(cms_pnp** out, int device, int max_jobs, int max_corr_total, int max_hyp_total) {
   if (!out || max_jobs < 1 || max_corr_total < 1 || max_hyp_total < 1) return cms_fail(CMS_ERR_ARG, "cms_pnp_create: bad argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
-    return cms_fail(CMS_ERR_NO_DEVICE, "cms_pnp_create: no HIP device (the PnP solver's device path has no CPU fallback)");
+  const int rcd = cms_check_device(device, "cms_pnp_create: no HIP device (the PnP solver's device path has no CPU fallback)");
+  if (rcd) return rcd;
   HIPCHK(hipSetDevice(device));
   cms_pnp* p = new cms_pnp();
   p->device = device; p->max_jobs = max_jobs; p->max_corr = max_corr_total; p->max_hyp = max_hyp_total;
@@ -58,20 +55,6 @@ extern "C" int cms_pnp_create(cms_pnp** out, int device, int max_jobs, int max_c
   return CMS_OK;
 }
 extern "C" void cms_pnp_destroy(cms_pnp* p) { cms_pnp_free(p); }
-
-static int cms_pnp_reserve(cms_pnp* p, size_t dev_bytes, size_t host_bytes) {
-  if (dev_bytes > p->d_bytes) {
-    if (p->d) { HIPCHK(hipStreamSynchronize(p->stream)); HIPCHK(hipFree(p->d)); p->d = nullptr; p->d_bytes = 0; }
-    HIPCHK(hipMalloc((void**)&p->d, dev_bytes + dev_bytes / 2));
-    p->d_bytes = dev_bytes + dev_bytes / 2;
-  }
-  if (host_bytes > p->h_bytes) {
-    if (p->h) { HIPCHK(hipStreamSynchronize(p->stream)); HIPCHK(hipHostFree(p->h)); p->h = nullptr; p->h_bytes = 0; }
-    HIPCHK(hipHostMalloc((void**)&p->h, host_bytes + host_bytes / 2));
-    p->h_bytes = host_bytes + host_bytes / 2;
-  }
-  return CMS_OK;
-}
 
 // frames: cms_pnp_iterate_frames -- the 2-D side is gathered on the device from the context's resident rows, and the whole sequence runs on the
 // context's stream (behind whatever filled the rows), as cms_kfstore_search_by_projection does
@@ -104,13 +87,14 @@ static int cms_pnp_run(cms_pnp* p, cms_ctx* c, int njobs, cms_pnp_job* jobs, boo
                o_cjob = blk.take(C_ * 4), o_kpi = blk.take(C_ * 4), o_jrow = blk.take(J_ * 4), o_jth2 = blk.take(J_ * 4);
   const size_t in_bytes = blk.size;
   const size_t o_out = blk.take(J_ * sizeof(CmsPnpOutDev)), o_bout = blk.take(MW * 8), o_rout = blk.take(MW * 8);
-  const size_t out_begin = o_out, out_bytes = blk.size - o_out;
+  const size_t out_begin = o_out, out_end = blk.size;
   const size_t o_rt = blk.take(Hn * 96), o_cnt = blk.take(Hn * 4), o_hmask = blk.take((size_t)words * 8), o_rows = blk.take(C_ * 15 * 8);
   HIPCHK(hipSetDevice(p->device));
-  int rc = cms_pnp_reserve(p, blk.size, out_begin + out_bytes);
+  hipStream_t s = frames ? c->stream : p->stream;
+  int rc = p->blocks.reserve(s, blk.size, out_end);
   if (rc) return rc;
-  uint8_t* h = p->h;
-  uint8_t* d = p->d;
+  uint8_t* h = p->blocks.h;
+  uint8_t* d = p->blocks.d;
   std::memset(h, 0, in_bytes);
   std::memcpy(h + o_jobs, jd.data(), J_ * sizeof(CmsPnpJobDev));
   for (int j = 0; j < njobs; ++j) {
@@ -136,8 +120,8 @@ static int cms_pnp_run(cms_pnp* p, cms_ctx* c, int njobs, cms_pnp_job* jobs, boo
     for (size_t i = 0; i < n; ++i)
       if (q.best_mask[i]) bw[i >> 6] |= 1ull << (i & 63);
   }
-  hipStream_t s = frames ? c->stream : p->stream;
-  HIPCHK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+  rc = p->blocks.up(s, in_bytes, "cms_pnp_iterate");
+  if (rc) return rc;
   if (frames && corr > 0) {
     CmsPnpGatherArgs ga = {};
     ga.ncorr = (int)corr; ga.kp_cap = c->g.kp_cap; ga.nlevels = c->g.nlevels;
@@ -167,8 +151,8 @@ static int cms_pnp_run(cms_pnp* p, cms_ctx* c, int njobs, cms_pnp_job* jobs, boo
   }
   hipLaunchKernelGGL(k_pnp_select, dim3(njobs), dim3(CMS_PNP_SELECT_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(h + out_begin, d + out_begin, out_bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  rc = p->blocks.back_and_wait(s, out_begin, out_end, "cms_pnp_iterate");
+  if (rc) return rc;
   for (int j = 0; j < njobs; ++j) {
     cms_pnp_job& q = jobs[j];
     const CmsPnpJobDev& g = jd[(size_t)j];

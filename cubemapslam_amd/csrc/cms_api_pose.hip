@@ -1,5 +1,6 @@
 // cms_api_pose.hip -- host side of the pose-only optimisation (Optimizer::PoseOptimization, Optimizer.cpp:48-190).
-// Persistent device buffers + one stream per handle; a batch of frames is one launch of k_pose_optimize (cms_pose_opt.hip).
+// Persistent device buffers + one stream per handle; a batch of frames is one launch of k_pose_optimize (cms_pose_opt.hip).  The handle's three
+// pinned blocks are pinned-only CmsStages (cms_stage.h).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
@@ -13,10 +14,10 @@ struct cms_pose {
   int* d_off = nullptr; double* d_Xw = nullptr; double* d_obs = nullptr; double* d_inv = nullptr; int8_t* d_face = nullptr;
   uint8_t* d_out = nullptr; double* d_err = nullptr; double* d_poses = nullptr; double* d_poses0 = nullptr; int* d_res = nullptr;
   double fx = 0, fy = 0, cx = 0, cy = 0;
-  uint8_t* h_stage = nullptr; size_t h_stage_bytes = 0;     // pinned staging of cms_pose_optimize_batch (inputs out, results back: no pageable copies)
-  uint8_t* h_fetch = nullptr; size_t h_fetch_bytes = 0;     // pinned landing block of cms_pose_fetch
+  CmsStage h_stage;                                         // pinned staging of cms_pose_optimize_batch's inputs (no pageable copies)
+  CmsStage h_fetch;                                         // pinned landing block of cms_pose_fetch
   hipEvent_t ev_fetch = nullptr; bool fetch_queued = false; // the results' copies into h_fetch were enqueued by cms_pose_launch right behind the kernel (ev_fetch: their end)
-  uint8_t* h_direct = nullptr; size_t h_direct_bytes = 0;   // pinned block of the direct (few frames) path: its own, so that a staged upload still copying out of h_stage is never overwritten
+  CmsStage h_direct;                                        // pinned block of the direct (few frames) path: its own, so that a staged upload still copying out of h_stage is never overwritten
 };
 
 static void cms_pose_free(cms_pose* p) {
@@ -24,9 +25,7 @@ static void cms_pose_free(cms_pose* p) {
   hipSetDevice(p->device);
   void* ptrs[] = {p->d_off, p->d_Xw, p->d_obs, p->d_inv, p->d_face, p->d_out, p->d_err, p->d_poses, p->d_poses0, p->d_res};
   for (void* q : ptrs) if (q) hipFree(q);
-  if (p->h_stage) (void)hipHostFree(p->h_stage);
-  if (p->h_fetch) (void)hipHostFree(p->h_fetch);
-  if (p->h_direct) (void)hipHostFree(p->h_direct);
+  p->h_stage.release(); p->h_fetch.release(); p->h_direct.release();
   if (p->ev_fetch) (void)hipEventDestroy(p->ev_fetch);
   if (p->stream) hipStreamDestroy(p->stream);
   delete p;
@@ -34,9 +33,8 @@ static void cms_pose_free(cms_pose* p) {
 
 extern "C" int cms_pose_create(cms_pose** out, int device, int max_frames, int max_edges) {
   if (!out || max_frames < 1 || max_edges < 1) return cms_fail(CMS_ERR_ARG, "cms_pose_create: bad argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
-    return cms_fail(CMS_ERR_NO_DEVICE, "cms_pose_create: no HIP device (the pose optimisation has no CPU fallback)");
+  const int rcd = cms_check_device(device, "cms_pose_create: no HIP device (the pose optimisation has no CPU fallback)");
+  if (rcd) return rcd;
   HIPCHK(hipSetDevice(device));
   cms_pose* p = new cms_pose();
   p->device = device; p->cap_f = max_frames; p->cap_e = max_edges;
@@ -79,17 +77,9 @@ static int cms_pose_upload_impl(cms_pose* p, int nf, const int* edge_off, const 
     CmsBlock blk;
     const size_t o_off = blk.take(((size_t)nf + 1) * 4), o_X = blk.take((size_t)ne * 24), o_obs = blk.take((size_t)ne * 16), o_inv = blk.take((size_t)ne * 8),
                  o_face = blk.take((size_t)ne), o_pose = blk.take((size_t)nf * 56), in_bytes = blk.size;
-    const size_t out_bytes = cms_align((size_t)nf * 32) + cms_align((size_t)nf * 56) + cms_align((size_t)ne);
-    // the inputs use the first half of the block, the results of cms_pose_optimize_batch the second: EACH must fit its half (a block kept from
-    // a smaller call could hold in + out together and still be too short for a result set larger than the inputs)
-    if (2 * std::max(in_bytes, out_bytes) > p->h_stage_bytes) {
-      if (p->h_stage) (void)hipHostFree(p->h_stage);
-      p->h_stage = nullptr; p->h_stage_bytes = 0;
-      const size_t want = 4 * std::max(in_bytes, out_bytes);
-      HIPCHK(hipHostMalloc((void**)&p->h_stage, want));
-      p->h_stage_bytes = want;
-    }
-    uint8_t* h = p->h_stage;
+    const int rc = p->h_stage.reserve(s, 0, in_bytes);      // (the results land in h_fetch)
+    if (rc) return rc;
+    uint8_t* h = p->h_stage.h;
     memcpy(h + o_off, edge_off, ((size_t)nf + 1) * 4);
     if (ne > 0) { memcpy(h + o_X, Xw, (size_t)ne * 24); memcpy(h + o_obs, obs_uv, (size_t)ne * 16); memcpy(h + o_inv, inv_sigma2, (size_t)ne * 8); memcpy(h + o_face, face, (size_t)ne); }
     memcpy(h + o_pose, poses7, (size_t)nf * 56);
@@ -115,6 +105,20 @@ extern "C" int cms_pose_upload(cms_pose* p, int nf, const int* edge_off, const d
                                const int8_t* face, double fx, double fy, double cx, double cy, const double* poses7) {
   return cms_pose_upload_impl(p, nf, edge_off, Xw, obs_uv, inv_sigma2, face, fx, fy, cx, cy, poses7, false);
 }
+// the landing block of a batch's results: 8 ints per frame | 7 doubles per frame | one outlier flag per edge
+struct PoseLanding { size_t o_res, o_pose, o_out, total; };
+static PoseLanding pose_landing(int nf, int ne) {
+  PoseLanding l;
+  l.o_res = 0; l.o_pose = cms_align((size_t)nf * 32); l.o_out = l.o_pose + cms_align((size_t)nf * 56); l.total = l.o_out + cms_align((size_t)std::max(ne, 1));
+  return l;
+}
+// the kernel's 8 ints per frame -> what the caller asked for
+static void pose_unpack(const int* res, int nf, int* n_inliers, cms_pose_stats* stats) {
+  for (int f = 0; f < nf; ++f) {
+    if (n_inliers) n_inliers[f] = res[8 * f];
+    if (stats) { stats[f].n_bad = res[8 * f + 1]; stats[f].rounds = res[8 * f + 2]; for (int i = 0; i < 4; ++i) stats[f].iterations_done[i] = res[8 * f + 4 + i]; }
+  }
+}
 extern "C" int cms_pose_launch(cms_pose* p) {
   if (!p || p->nf < 1) return cms_fail(CMS_ERR_ARG, "cms_pose_launch: nothing uploaded");
   HIPCHK(hipSetDevice(p->device));
@@ -133,18 +137,14 @@ extern "C" int cms_pose_launch(cms_pose* p) {
   // each waited for a slot on the busy chip -- 3.5 ms of the step's host thread inside a 12.5 ms step (CMS_BENCH_STEP_TRACE).
   p->fetch_queued = false;
   {
-    const size_t o_res = 0, o_pose = cms_align((size_t)p->nf * 32), o_out = o_pose + cms_align((size_t)p->nf * 56), total = o_out + cms_align((size_t)std::max(p->ne, 1));
-    if (total > p->h_fetch_bytes) {
-      if (p->h_fetch) { HIPCHK(hipStreamSynchronize(s)); (void)hipHostFree(p->h_fetch); }
-      p->h_fetch = nullptr; p->h_fetch_bytes = 0;
-      HIPCHK(hipHostMalloc((void**)&p->h_fetch, 2 * total));
-      p->h_fetch_bytes = 2 * total;
-    }
+    const PoseLanding l = pose_landing(p->nf, p->ne);
+    const int rc = p->h_fetch.reserve(s, 0, l.total);
+    if (rc) return rc;
     if (!p->ev_fetch) HIPCHK(hipEventCreateWithFlags(&p->ev_fetch, hipEventDisableTiming));
-    uint8_t* h = p->h_fetch;
-    HIPCHK(hipMemcpyAsync(h + o_res, p->d_res, (size_t)p->nf * 8 * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h + o_pose, p->d_poses, (size_t)p->nf * 7 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (p->ne > 0) HIPCHK(hipMemcpyAsync(h + o_out, p->d_out, (size_t)p->ne, hipMemcpyDeviceToHost, s));
+    uint8_t* h = p->h_fetch.h;
+    HIPCHK(hipMemcpyAsync(h + l.o_res, p->d_res, (size_t)p->nf * 8 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h + l.o_pose, p->d_poses, (size_t)p->nf * 7 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (p->ne > 0) HIPCHK(hipMemcpyAsync(h + l.o_out, p->d_out, (size_t)p->ne, hipMemcpyDeviceToHost, s));
     HIPCHK(hipEventRecord(p->ev_fetch, s));
     p->fetch_queued = true;
   }
@@ -156,30 +156,22 @@ extern "C" int cms_pose_fetch(cms_pose* p, double* poses7, uint8_t* outlier, int
   hipStream_t s = p->stream;
   // results through the handle's pinned block, one synchronisation: three copies into the caller's pageable arrays were three staged,
   // waited-for transfers (1.2 ms for 256 frames next to a busy PCIe link, on the thread that drives the frame path)
-  const size_t o_res = 0, o_pose = cms_align((size_t)p->nf * 32), o_out = o_pose + cms_align((size_t)p->nf * 56), total = o_out + cms_align((size_t)std::max(p->ne, 1));
+  const PoseLanding l = pose_landing(p->nf, p->ne);
   if (p->fetch_queued) {
     HIPCHK(hipEventSynchronize(p->ev_fetch));        // (cms_pose_launch enqueued the copies: the block holds this launch's results until the next launch)
   } else {
-    if (total > p->h_fetch_bytes) {
-      if (p->h_fetch) (void)hipHostFree(p->h_fetch);
-      p->h_fetch = nullptr; p->h_fetch_bytes = 0;
-      HIPCHK(hipHostMalloc((void**)&p->h_fetch, 2 * total));
-      p->h_fetch_bytes = 2 * total;
-    }
-    uint8_t* hq = p->h_fetch;
-    HIPCHK(hipMemcpyAsync(hq + o_res, p->d_res, (size_t)p->nf * 8 * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (poses7) HIPCHK(hipMemcpyAsync(hq + o_pose, p->d_poses, (size_t)p->nf * 7 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (outlier && p->ne > 0) HIPCHK(hipMemcpyAsync(hq + o_out, p->d_out, (size_t)p->ne, hipMemcpyDeviceToHost, s));
+    const int rc = p->h_fetch.reserve(s, 0, l.total);
+    if (rc) return rc;
+    uint8_t* hq = p->h_fetch.h;
+    HIPCHK(hipMemcpyAsync(hq + l.o_res, p->d_res, (size_t)p->nf * 8 * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (poses7) HIPCHK(hipMemcpyAsync(hq + l.o_pose, p->d_poses, (size_t)p->nf * 7 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (outlier && p->ne > 0) HIPCHK(hipMemcpyAsync(hq + l.o_out, p->d_out, (size_t)p->ne, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
   }
-  uint8_t* h = p->h_fetch;
-  const int* res = (const int*)(h + o_res);
-  if (poses7) memcpy(poses7, h + o_pose, (size_t)p->nf * 56);
-  if (outlier && p->ne > 0) memcpy(outlier, h + o_out, (size_t)p->ne);
-  for (int f = 0; f < p->nf; ++f) {
-    if (n_inliers) n_inliers[f] = res[8 * f];
-    if (stats) { stats[f].n_bad = res[8 * f + 1]; stats[f].rounds = res[8 * f + 2]; for (int i = 0; i < 4; ++i) stats[f].iterations_done[i] = res[8 * f + 4 + i]; }
-  }
+  uint8_t* h = p->h_fetch.h;
+  if (poses7) memcpy(poses7, h + l.o_pose, (size_t)p->nf * 56);
+  if (outlier && p->ne > 0) memcpy(outlier, h + l.o_out, (size_t)p->ne);
+  pose_unpack((const int*)(h + l.o_res), p->nf, n_inliers, stats);
   return CMS_OK;
 }
 // A handful of frames (tracking's one call per frame: ~600 edges, 30 KB): the kernel reads its edges straight from the handle's pinned block -- once,
@@ -195,13 +187,9 @@ static int cms_pose_optimize_direct(cms_pose* p, int nf, const int* edge_off, co
                o_face = blk.take((size_t)ne), o_pose = blk.take((size_t)nf * 56), o_res = blk.take((size_t)nf * 32), o_out = blk.take((size_t)ne), total = blk.size;
   // (a block of the direct path's own: the handle's resident batch -- cms_pose_upload + cms_pose_launch, possibly still copying out of h_stage --
   // is not touched by this call, and a cms_pose_fetch afterwards still finds it: p->nf / p->ne stay as they are)
-  if (total > p->h_direct_bytes) {
-    if (p->h_direct) { HIPCHK(hipStreamSynchronize(p->stream)); (void)hipHostFree(p->h_direct); }
-    p->h_direct = nullptr; p->h_direct_bytes = 0;
-    HIPCHK(hipHostMalloc((void**)&p->h_direct, 4 * total));
-    p->h_direct_bytes = 4 * total;
-  }
-  uint8_t* h = p->h_direct;
+  const int rc = p->h_direct.reserve(p->stream, 0, total);
+  if (rc) return rc;
+  uint8_t* h = p->h_direct.h;
   memcpy(h + o_off, edge_off, ((size_t)nf + 1) * 4);
   if (ne > 0) { memcpy(h + o_X, Xw, (size_t)ne * 24); memcpy(h + o_obs, obs_uv, (size_t)ne * 16); memcpy(h + o_inv, inv_sigma2, (size_t)ne * 8); memcpy(h + o_face, face, (size_t)ne); }
   memcpy(h + o_pose, poses7, (size_t)nf * 56);
@@ -212,13 +200,9 @@ static int cms_pose_optimize_direct(cms_pose* p, int nf, const int* edge_off, co
   hipLaunchKernelGGL(k_pose_optimize, dim3(nf), dim3(256), 0, p->stream, d);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(p->stream));
-  const int* res = (const int*)(h + o_res);
   memcpy(poses7, h + o_pose, (size_t)nf * 56);
   if (outlier && ne > 0) memcpy(outlier, h + o_out, (size_t)ne);
-  for (int f = 0; f < nf; ++f) {
-    if (n_inliers) n_inliers[f] = res[8 * f];
-    if (stats) { stats[f].n_bad = res[8 * f + 1]; stats[f].rounds = res[8 * f + 2]; for (int i = 0; i < 4; ++i) stats[f].iterations_done[i] = res[8 * f + 4 + i]; }
-  }
+  pose_unpack((const int*)(h + o_res), nf, n_inliers, stats);
   return CMS_OK;
 }
 extern "C" int cms_pose_optimize_batch(cms_pose* p, int nf, const int* edge_off, const double* Xw, const double* obs_uv, const double* inv_sigma2,

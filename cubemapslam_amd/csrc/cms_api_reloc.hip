@@ -1,7 +1,7 @@
 // cms_api_reloc.hip -- host side of ORBMatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, th,
 // ORBdist) (src/ORBMatcher.cpp:253-378), the guided search Tracking::Relocalization runs twice per accepted PnP pose (Tracking.cpp:1101, :1115);
 // included by cms_lib.hip after cms_api_bow.hip (cms_kfstore, cms_api_track.hip's helpers).  All jobs of a call are ONE launch sequence on the frame
-// context's stream: one staged block up, k_project_keyframe, the window query, k_search_local (one workgroup per job, no second-best test),
+// context's stream: one staged block up (the context's CmsStage), k_project_keyframe, the window query, k_search_local (one workgroup per job, no second-best test),
 // k_rot_filter, one block back -- inside cms_retry_capacity like cms_search_by_projection.
 #include <algorithm>
 #include <cstring>
@@ -20,27 +20,26 @@ int reloc_run(cms_ctx* c, cms_kfstore* st, int njobs, const cms_kfproj_job* jobs
   if (c->g.nlevels > 16) return cms_fail(CMS_ERR_UNSUPPORTED, "SearchByProjection (key frame): more than 16 pyramid levels");
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  if (st)
-    for (int j = 0; j < njobs; ++j) {
-      const auto& call = st->ff_call[(size_t)jobs[j].slot];
-      if (call) HIPCHK(hipStreamWaitEvent(s, call->ev, 0));
-    }
+  if (st) {
+    const int rc = kfstore_wait_puts(st, s, njobs, [&](int j) { return jobs[j].slot; });
+    if (rc) return rc;
+  }
   const size_t n4 = (size_t)n * 4, j4 = (size_t)njobs * 4, kp4 = (size_t)kp_cap * 4;
   CmsBlock blk;
   const size_t o_pose = blk.take(12 * j4), o_jframe = blk.take(j4), o_jkp0 = blk.take(j4), o_mpoff = blk.take(j4, 4), o_ptjob = blk.take(n4), o_feat = blk.take(n4),
                o_pos = blk.take(3 * n4), o_min = blk.take(n4), o_max = blk.take(n4), o_desc = blk.take((size_t)n * 32), o_kpmp = blk.take(njobs * kp4);
   const size_t in_bytes = blk.size;
   const size_t o_match = blk.take(n4), o_nm = blk.take(j4), o_tot = blk.take(16);
-  const size_t out_begin = o_kpmp, out_bytes = blk.size - o_kpmp;
+  const size_t out_begin = o_kpmp, out_end = blk.size;
   const size_t o_qf = blk.take(n4), o_qx = blk.take(n4), o_qy = blk.take(n4), o_qr = blk.take(n4), o_qmin = blk.take(n4), o_qmax = blk.take(n4), o_ang = blk.take(n4),
                o_cnt = blk.take(n4), o_off = blk.take(n4, 4);
   const size_t o_idx = blk.size;
   return cms_retry_capacity(64 * n + 1024, who, [&](int cap, int& tot) -> int {
     const size_t o_pd = o_idx + cms_align((size_t)cap * 4);
-    int rc = track_reserve(c, o_pd + cms_align((size_t)cap * 2), std::max(in_bytes, out_begin + out_bytes));      // the read-back lands at h + out_begin, not at h
+    int rc = c->stage.reserve(s, o_pd + cms_align((size_t)cap * 2), out_end);
     if (rc) return rc;
-    uint8_t* p = (uint8_t*)c->d_match;
-    uint8_t* h = c->h_stage;
+    uint8_t* p = c->stage.d;
+    uint8_t* h = c->stage.h;
     std::memcpy(h + o_mpoff, mp_off.data(), j4 + 4);
     for (int j = 0; j < njobs; ++j) {
       const cms_kfproj_job& q = jobs[j];
@@ -57,7 +56,8 @@ int reloc_run(cms_ctx* c, cms_kfstore* st, int njobs, const cms_kfproj_job* jobs
       std::memcpy(h + o_pos + 12 * m0, q.pos, 12 * m); std::memcpy(h + o_min + 4 * m0, q.min_dist, 4 * m); std::memcpy(h + o_max + 4 * m0, q.max_dist, 4 * m);
       std::memcpy(h + o_desc + 32 * m0, q.mp_desc, 32 * m);
     }
-    HIPCHK(hipMemcpyAsync(p, h, in_bytes, hipMemcpyHostToDevice, s));
+    rc = c->stage.up(s, in_bytes, who);
+    if (rc) return rc;
     CmsProjectKfArgs a = {};
     a.n = n; a.pt_job = (const int*)(p + o_ptjob); a.pose12 = (const float*)(p + o_pose); a.job_frame = (const int*)(p + o_jframe); a.job_kp0 = (const int*)(p + o_jkp0);
     a.kf_kp = st ? st->d_kp : nullptr; a.kf_feat = (const int*)(p + o_feat); a.kf_angle = (const float*)(p + o_feat);
@@ -80,8 +80,8 @@ int reloc_run(cms_ctx* c, cms_kfstore* st, int njobs, const cms_kfproj_job* jobs
     r.check_orientation = check_orientation; r.total = g.total; r.cap = cap; r.wg_frame = g.wg_frame; r.kp_cap = kp_cap;
     hipLaunchKernelGGL(k_rot_filter, dim3(njobs), dim3(1024), 0, s, r);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h + out_begin, p + out_begin, out_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    rc = c->stage.back_and_wait(s, out_begin, out_end, who);
+    if (rc) return rc;
     tot = *reinterpret_cast<const int*>(h + o_tot);
     if (tot > cap) return CMS_OK;
     for (int j = 0; j < njobs; ++j) {

@@ -1,6 +1,7 @@
 // cms_api_track.hip -- host side of the "track local map" step (Frame::isInFrustum + ORBMatcher::SearchByProjection over the local
 // map points, Tracking::SearchLocalPoints), included by cms_lib.hip after cms_api_area.hip.  The host-buffer entries lay their scratch block
-// out with CmsBlock and run inside cms_retry_capacity (cms_api_util.h); track_search_local_args fills k_search_local's arguments for all of them.
+// out with CmsBlock, hold it and its pinned twin in the context's CmsStage and run inside cms_retry_capacity (cms_api_util.h);
+// track_search_local_args fills k_search_local's arguments for all of them.
 #include <cmath>
 #include <vector>
 
@@ -45,11 +46,6 @@ extern "C" int cms_is_in_frustum_device(cms_ctx* c, int nmp, const void* d_mp_fr
   return CMS_OK;
 }
 
-// the scratch block (fixed part | cap candidate rows | cap pair distances) and the pinned block of one attempt of a host-buffer entry
-static int track_reserve(cms_ctx* c, size_t scratch_bytes, size_t stage_bytes) {
-  const int rc = cms_scratch(c, scratch_bytes);
-  return rc ? rc : cms_hstage(c, stage_bytes);
-}
 // k_search_local's arguments over the context's frames.  total / cap: see CmsSearchLocalArgs (NULL / 0: the candidate lists are complete).
 static CmsSearchLocalArgs track_search_local_args(const cms_ctx* c, const void* mp_off, const void* mp_desc, const void* cand_off, const void* cand_idx, void* pair_dist,
                                                   int* kp_mp, void* mp_match, void* rounds, float nnratio, int th_high, int frame0, const void* total, int cap) {
@@ -115,20 +111,21 @@ extern "C" int cms_search_local_points(cms_ctx* c, int b, const float* pose15, i
   const size_t in_bytes = blk.size;
   const size_t o_vis = blk.take(nmp), o_px = blk.take(n4), o_py = blk.take(n4), o_lvl = blk.take(n4), o_vc = blk.take(n4), o_match = blk.take(n4), o_tot = blk.take(16),
                o_rounds = blk.take(16);
-  const size_t out_begin = o_kpmp, out_bytes = blk.size - o_kpmp;
+  const size_t out_begin = o_kpmp, out_end = blk.size;
   const size_t o_qr = blk.take(n4), o_qmin = blk.take(n4), o_qmax = blk.take(n4), o_cnt = blk.take(n4), o_off = blk.take(n4, 4);
   const size_t o_idx = blk.size;
   return cms_retry_capacity(64 * nmp + 1024, "cms_search_local_points", [&](int cap, int& tot) -> int {
     const size_t o_pd = o_idx + cms_align((size_t)cap * 4);
-    int rc = track_reserve(c, o_pd + cms_align((size_t)cap * 2), std::max(in_bytes, out_begin + out_bytes));      // the read-back lands at h + out_begin, not at h
+    int rc = c->stage.reserve(s, o_pd + cms_align((size_t)cap * 2), out_end);
     if (rc) return rc;
-    uint8_t* p = (uint8_t*)c->d_match;
-    uint8_t* h = c->h_stage;
+    uint8_t* p = c->stage.d;
+    uint8_t* h = c->stage.h;
     memcpy(h + o_pose, pose15, 60);
     memcpy(h + o_pos, pos, 3 * n4); memcpy(h + o_nrm, normal, 3 * n4); memcpy(h + o_min, min_dist, n4); memcpy(h + o_max, max_dist, n4);
     memcpy(h + o_desc, mp_desc, (size_t)nmp * 32);
     track_stage_one_frame(c, h, o_qf, o_mpoff, o_kpmp, b, nmp, nkp, kp_mp);
-    HIPCHK(hipMemcpyAsync(p, h, in_bytes, hipMemcpyHostToDevice, s));
+    rc = c->stage.up(s, in_bytes, "cms_search_local_points");
+    if (rc) return rc;
     rc = cms_is_in_frustum_device(c, nmp, nullptr, p + o_pose, p + o_pos, p + o_nrm, p + o_min, p + o_max, viewing_cos_limit, th, p + o_vis,
                                   p + o_px, p + o_py, p + o_lvl, p + o_vc, p + o_qr, p + o_qmin, p + o_qmax);
     if (rc) return rc;
@@ -140,8 +137,8 @@ extern "C" int cms_search_local_points(cms_ctx* c, int b, const float* pose15, i
                                                          p + o_rounds, nnratio, th_high, b, p + o_tot, cap);
     hipLaunchKernelGGL(k_search_local, dim3(1), dim3(1024), 0, s, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h + out_begin, p + out_begin, out_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    rc = c->stage.back_and_wait(s, out_begin, out_end, "cms_search_local_points");
+    if (rc) return rc;
     tot = *reinterpret_cast<const int*>(h + o_tot);
     if (tot > cap) return CMS_OK;
     if (nkp > 0) memcpy(kp_mp, h + o_kpmp, (size_t)nkp * 4);
@@ -209,20 +206,21 @@ extern "C" int cms_search_by_projection(cms_ctx* c, int b, const float* pose12, 
                o_qf = blk.take(n4), o_mpoff = blk.take(16), o_kpmp = blk.take(kp4);
   const size_t in_bytes = blk.size;
   const size_t o_match = blk.take(n4), o_nm = blk.take(16), o_tot = blk.take(16);
-  const size_t out_begin = o_kpmp, out_bytes = blk.size - o_kpmp;
+  const size_t out_begin = o_kpmp, out_end = blk.size;
   const size_t o_qx = blk.take(n4), o_qy = blk.take(n4), o_qr = blk.take(n4), o_qmin = blk.take(n4), o_qmax = blk.take(n4), o_cnt = blk.take(n4), o_off = blk.take(n4, 4);
   const size_t o_idx = blk.size;
   return cms_retry_capacity(64 * nlast + 1024, "cms_search_by_projection", [&](int cap, int& tot) -> int {
     const size_t o_pd = o_idx + cms_align((size_t)cap * 4);
-    int rc = track_reserve(c, o_pd + cms_align((size_t)cap * 2), std::max(in_bytes, out_begin + out_bytes));      // the read-back lands at h + out_begin, not at h
+    int rc = c->stage.reserve(s, o_pd + cms_align((size_t)cap * 2), out_end);
     if (rc) return rc;
-    uint8_t* p = (uint8_t*)c->d_match;
-    uint8_t* h = c->h_stage;
+    uint8_t* p = c->stage.d;
+    uint8_t* h = c->stage.h;
     memcpy(h + o_pose, pose12, 48);
     memcpy(h + o_valid, valid, nlast); memcpy(h + o_xw, Xw, 3 * n4); memcpy(h + o_oct, octave, n4); memcpy(h + o_ang, angle, n4);
     memcpy(h + o_desc, mp_desc, (size_t)nlast * 32);
     track_stage_one_frame(c, h, o_qf, o_mpoff, o_kpmp, b, nlast, nkp, kp_mp);
-    HIPCHK(hipMemcpyAsync(p, h, in_bytes, hipMemcpyHostToDevice, s));
+    rc = c->stage.up(s, in_bytes, "cms_search_by_projection");
+    if (rc) return rc;
     rc = cms_project_last_frame_device(c, nlast, nullptr, p + o_pose, p + o_valid, p + o_xw, p + o_oct, th, p + o_qx, p + o_qy, p + o_qr, p + o_qmin, p + o_qmax);
     if (rc) return rc;
     rc = cms_features_in_area_batch_device(c, nlast, p + o_qf, p + o_qx, p + o_qy, p + o_qr, p + o_qmin, p + o_qmax, p + o_cnt, p + o_off, p + o_idx, cap, p + o_tot);
@@ -235,8 +233,8 @@ extern "C" int cms_search_by_projection(cms_ctx* c, int b, const float* pose12, 
     r.mp_match = a.mp_match; r.n_matches = (int*)(p + o_nm); r.check_orientation = check_orientation; r.total = a.total; r.cap = cap;
     hipLaunchKernelGGL(k_rot_filter, dim3(1), dim3(1024), 0, s, r);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h + out_begin, p + out_begin, out_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    rc = c->stage.back_and_wait(s, out_begin, out_end, "cms_search_by_projection");
+    if (rc) return rc;
     tot = *reinterpret_cast<const int*>(h + o_tot);
     if (tot > cap) return CMS_OK;
     if (nkp > 0) memcpy(kp_mp, h + o_kpmp, (size_t)nkp * 4);
@@ -273,15 +271,15 @@ extern "C" int cms_search_for_initialization(cms_ctx* c, int b2, int n1, const c
                o_desc = blk.take((size_t)n1 * 32), o_ang = blk.take(n4), o_prev = blk.take(2 * n4);
   const size_t in_bytes = blk.size;
   const size_t o_m12 = blk.take(n4), o_nm = blk.take(16), o_tot = blk.take(16);
-  const size_t out_begin = o_prev, out_bytes = blk.size - o_prev;
+  const size_t out_begin = o_prev, out_end = blk.size;
   const size_t o_bin = blk.take(n1), o_cnt = blk.take(q4), o_off = blk.take(q4, 4);
   const size_t o_idx = blk.size;
   return cms_retry_capacity(128 * nq + 4096, "cms_search_for_initialization", [&](int cap, int& tot) -> int {
     const size_t o_pd = o_idx + cms_align((size_t)cap * 4);
-    int rc = track_reserve(c, o_pd + cms_align((size_t)cap * 2), std::max(in_bytes, out_begin + out_bytes));      // the read-back lands at h + out_begin, not at h
+    int rc = c->stage.reserve(s, o_pd + cms_align((size_t)cap * 2), out_end);
     if (rc) return rc;
-    uint8_t* p = (uint8_t*)c->d_match;
-    uint8_t* h = c->h_stage;
+    uint8_t* p = c->stage.d;
+    uint8_t* h = c->stage.h;
     {
       int* hq = reinterpret_cast<int*>(h + o_qi); float* hx = reinterpret_cast<float*>(h + o_qx); float* hy = reinterpret_cast<float*>(h + o_qy);
       float* hr = reinterpret_cast<float*>(h + o_qr); int* hmin = reinterpret_cast<int*>(h + o_qmin); int* hmax = reinterpret_cast<int*>(h + o_qmax);
@@ -294,7 +292,8 @@ extern "C" int cms_search_for_initialization(cms_ctx* c, int b2, int n1, const c
       memcpy(h + o_desc, desc1, (size_t)n1 * 32);
       memcpy(h + o_prev, prev_matched, 2 * n4);
     }
-    HIPCHK(hipMemcpyAsync(p, h, in_bytes, hipMemcpyHostToDevice, s));
+    rc = c->stage.up(s, in_bytes, "cms_search_for_initialization");
+    if (rc) return rc;
     rc = cms_features_in_area_batch_device(c, nq, p + o_qf, p + o_qx, p + o_qy, p + o_qr, p + o_qmin, p + o_qmax, p + o_cnt, p + o_off, p + o_idx, cap, p + o_tot);
     if (rc) return rc;
     CmsInitArgs a;
@@ -306,8 +305,8 @@ extern "C" int cms_search_for_initialization(cms_ctx* c, int b2, int n1, const c
     hipLaunchKernelGGL(k_init_dist, dim3(nq), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_init_greedy, dim3(1), dim3(64), lds, s, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h + out_begin, p + out_begin, out_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    rc = c->stage.back_and_wait(s, out_begin, out_end, "cms_search_for_initialization");
+    if (rc) return rc;
     tot = *reinterpret_cast<const int*>(h + o_tot);
     if (tot > cap) return CMS_OK;
     memcpy(matches12, h + o_m12, n4);

@@ -1,7 +1,7 @@
 // cms_api_tri.hip -- host side of LocalMapping::CreateNewMapPoints and of the search half of ORBMatcher::Fuse, included by
-// cms_lib.hip after cms_api_track.hip.  Scratch blocks are laid out with CmsBlock (TriWork: the work area of a CreateNewMapPoints call); the two
-// Fuse entries fill their kernels' arguments with fuse_project_args / fuse_scan_args, query the windows through cms_area_launch and repeat a call
-// whose candidate lists did not fit through cms_retry_capacity.
+// cms_lib.hip after cms_api_track.hip.  Scratch blocks live in the context's CmsStage and are laid out with CmsBlock (TriWork: the work area of a
+// CreateNewMapPoints call); the two Fuse entries fill their kernels' arguments with fuse_project_args / fuse_scan_args, query the windows through
+// cms_area_launch and repeat a call whose candidate lists did not fit through cms_retry_capacity.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -113,10 +113,10 @@ int tri_run(cms_ctx* c, const TriDev& dev, const CmsTriKF* hkf, const float* hme
   // what made it 3 ms there was not the transfers but the Python wrapper's per-call arrays (see api.KeyframeStore.create_new_map_points).
   static const bool copy_engine = getenv("CMS_TRI_COPY_ENGINE") != nullptr;
   const size_t in_bytes = o_nnew, out_bytes = o_cand - o_nnew;
-  int rcs = cms_hstage(c, in_bytes + out_bytes);
+  int rcs = c->stage.reserve(s, 0, in_bytes + out_bytes);
   if (rcs) return rcs;
-  uint8_t* hin = c->h_stage;
-  uint8_t* hout = c->h_stage + in_bytes;
+  uint8_t* hin = c->stage.h;
+  uint8_t* hout = c->stage.h + in_bytes;
   if (nneigh > 0) {
     memcpy(hin + o_pair, pairs.data(), (size_t)nneigh * sizeof(CmsTriPair));
     memcpy(hin + o_pjob, pair_job.data(), (size_t)nneigh * 4);
@@ -216,10 +216,10 @@ static int tri_flatten_upload(cms_ctx* c, int nkf, KfAt&& kf_at, int n_current, 
                o_rays = blk.take(rays.size() * 4, 16), o_mp = blk.take(mp.size() * 4, 16), o_fn = blk.take(feat_node.size() * 4, 16), o_nid = blk.take(node_id.size() * 4, 16),
                o_noff = blk.take(node_off.size() * 4, 16), o_nfeat = blk.take(node_feat.size() * 4, 16);
   o_work = blk.size;
-  int rc = cms_scratch(c, o_work + work_bytes(max_n1));
-  if (rc) return rc;
-  uint8_t* p = (uint8_t*)c->d_match;
   hipStream_t s = c->stream;
+  int rc = c->stage.reserve(s, o_work + work_bytes(max_n1), 0);
+  if (rc) return rc;
+  uint8_t* p = c->stage.d;
   auto up = [&](size_t at, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(p + at, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess; };
   HIPCHK(up(o_kf, kfs.data(), kfs.size() * sizeof(CmsTriKF)));
   HIPCHK(up(o_kp, kp.data(), kp.size() * sizeof(CmsKeyPoint)));
@@ -258,7 +258,7 @@ extern "C" int cms_create_new_map_points(cms_ctx* c, int njobs, const cms_keyfra
   int rc = tri_flatten_upload(c, nkf, kf_at, njobs, "cms_create_new_map_points: bad key frame (at most 4096 features)", kfs, median, dev, o_work, max_n1,
                               [&](int mn1) { return TriWork(njobs, nneigh, mn1, cap_per_job).bytes; });
   if (rc) return rc;
-  uint8_t* p = (uint8_t*)c->d_match;
+  uint8_t* p = c->stage.d;
   std::vector<int> cur_idx((size_t)njobs), neigh_idx((size_t)nneigh + 1);
   for (int j = 0; j < njobs; ++j) cur_idx[(size_t)j] = j;
   for (int q = 0; q < nneigh; ++q) neigh_idx[(size_t)q] = njobs + q;
@@ -285,7 +285,7 @@ extern "C" int cms_search_for_triangulation(cms_ctx* c, const cms_keyframe* kf1,
   int rc = tri_flatten_upload(c, 2, kf_at, 1, "cms_search_for_triangulation: bad key frame (at most 4096 features)", kfs, median, dev, o_work, max_n1,
                               [&](int mn1) { return o_m + cms_align((size_t)mn1 * 4 + 16) + 256; });
   if (rc) return rc;
-  uint8_t* p = (uint8_t*)c->d_match + o_work;
+  uint8_t* p = c->stage.d + o_work;
   const size_t o_n = o_m + cms_align((size_t)max_n1 * 4 + 16);
   CmsTriPair pr;
   pr.kf2 = 1; pr.skip = 0;
@@ -349,6 +349,16 @@ struct cms_kfstore {
 };
 
 static hipError_t kfstore_order_behind_puts(cms_kfstore* st);
+// `stream` waits (on the device) for the cms_kfstore_put_from_frame(s) copies that last filled the slots the call's jobs name: the events are per
+// slot, so this also holds when the copy ran on another context's stream
+template <class SlotOfJob>
+static int kfstore_wait_puts(const cms_kfstore* st, hipStream_t stream, int njobs, SlotOfJob&& slot_of_job) {
+  for (int j = 0; j < njobs; ++j) {
+    const auto& call = st->ff_call[(size_t)slot_of_job(j)];
+    if (call) HIPCHK(hipStreamWaitEvent(stream, call->ev, 0));
+  }
+  return CMS_OK;
+}
 extern "C" void cms_kfstore_destroy(cms_kfstore* st) {
   if (!st) return;
   if (st->c) (void)hipSetDevice(st->c->device);
@@ -771,9 +781,9 @@ extern "C" int cms_fuse_search(cms_ctx* c, int b, const float* pose15, int nmp, 
                o_lvl = blk.take(n4), o_cnt = blk.take(n4), o_off = blk.take(n4, 4), o_tot = blk.take(16), o_qf = blk.take(n4), o_bi = blk.take(n4), o_bd = blk.take(n4);
   const size_t o_idx = blk.size;
   return cms_retry_capacity(64 * nmp + 1024, "cms_fuse_search", [&](int cap, int& tot) -> int {
-    int rc = cms_scratch(c, o_idx + cms_align((size_t)cap * 4));
+    int rc = c->stage.reserve(s, o_idx + cms_align((size_t)cap * 4), 0);
     if (rc) return rc;
-    uint8_t* p = (uint8_t*)c->d_match;
+    uint8_t* p = c->stage.d;
     HIPCHK(hipMemcpyAsync(p + o_pose, pose15, 60, hipMemcpyHostToDevice, s));
     if (skip) HIPCHK(hipMemcpyAsync(p + o_skip, skip, nmp, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_pos, pos, 3 * n4, hipMemcpyHostToDevice, s));
@@ -818,10 +828,10 @@ extern "C" int cms_distinctive_descriptors(cms_ctx* c, int npts, const int* obs_
   HIPCHK(hipSetDevice(c->device));
   CmsBlock blk;
   const size_t o_off = blk.take((size_t)(npts + 1) * 4), o_desc = blk.take((size_t)nobs * 32, 32), o_out = blk.take((size_t)npts * 4);
-  int rc = cms_scratch(c, blk.size);
-  if (rc) return rc;
-  uint8_t* p = (uint8_t*)c->d_match;
   hipStream_t s = c->stream;
+  int rc = c->stage.reserve(s, blk.size, 0);
+  if (rc) return rc;
+  uint8_t* p = c->stage.d;
   HIPCHK(hipMemcpyAsync(p + o_off, obs_off, (size_t)(npts + 1) * 4, hipMemcpyHostToDevice, s));
   if (nobs > 0) HIPCHK(hipMemcpyAsync(p + o_desc, desc, (size_t)nobs * 32, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_distinctive, dim3((npts + 3) / 4), dim3(256), 0, s, npts, (const int*)(p + o_off), (const uint4*)(p + o_desc), (int*)(p + o_out));
@@ -848,10 +858,10 @@ extern "C" int cms_update_normal_and_depth(cms_ctx* c, int npts, const int* obs_
   CmsBlock blk;
   const size_t o_off = blk.take(n4 + 4, 16), o_pos = blk.take(3 * n4, 16), o_ow = blk.take((size_t)nobs * 12, 16), o_ref = blk.take(3 * n4, 16), o_lvl = blk.take(n4, 16),
                o_sf = blk.take(64, 16), o_nrm = blk.take(3 * n4, 16), o_min = blk.take(n4, 16), o_max = blk.take(n4, 16);
-  int rc = cms_scratch(c, blk.size);
-  if (rc) return rc;
-  uint8_t* p = (uint8_t*)c->d_match;
   hipStream_t s = c->stream;
+  int rc = c->stage.reserve(s, blk.size, 0);
+  if (rc) return rc;
+  uint8_t* p = c->stage.d;
   float sf[16];
   cms_level_table(sf, c, c->scale, 1.0f);
   HIPCHK(hipMemcpyAsync(p + o_off, obs_off, n4 + 4, hipMemcpyHostToDevice, s));
@@ -932,9 +942,9 @@ static int kfstore_fuse_core(cms_kfstore* st, int njobs, const int* job_slot, co
     else (void)hipGetLastError();                                  // (a pageable pointer: not an error, just the copies)
   }
   return cms_retry_capacity(64 * nmp + 1024, "cms_kfstore_fuse_search", [&](int cap, int& tot) -> int {
-    int rc = cms_scratch(c, o_idx + cms_align((size_t)cap * 4));
+    int rc = c->stage.reserve(s, o_idx + cms_align((size_t)cap * 4), 0);
     if (rc) return rc;
-    uint8_t* p = (uint8_t*)c->d_match;
+    uint8_t* p = c->stage.d;
     HIPCHK(hipMemcpyAsync(p + o_pose, pose.data(), pose.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_joff, mp_off, j4 + 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_jslot, job_slot, j4, hipMemcpyHostToDevice, s));

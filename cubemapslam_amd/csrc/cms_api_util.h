@@ -11,6 +11,23 @@ struct CmsBlock {
   size_t size = 0;
   size_t take(size_t bytes, size_t pad = 0) { const size_t at = size; size += cms_align(bytes + pad); return at; }
 };
+// The HIP side of CmsStage (cms_stage.h): pinned blocks with hipHostMalloc's default flags (non-coherent: fast copies).
+struct CmsHipMem {
+  static int take(void** p, size_t bytes, bool pinned) { HIPCHK(pinned ? hipHostMalloc(p, bytes) : hipMalloc(p, bytes)); return CMS_OK; }
+  static int give(void* p, bool pinned) { HIPCHK(pinned ? hipHostFree(p) : hipFree(p)); return CMS_OK; }
+  static int wait(void* stream) { HIPCHK(hipStreamSynchronize((hipStream_t)stream)); return CMS_OK; }
+  static int copy(void* dst, const void* src, size_t bytes, bool to_device, void* stream) {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, (hipStream_t)stream));
+    return CMS_OK;
+  }
+  static int range_error(const char* who) { return cms_fail(CMS_ERR_HIP, (std::string(who) + ": a staged copy reaches beyond its block").c_str()); }
+};
+// a `create` entry's device test; `what` is the entry's own message
+static int cms_check_device(int device, const char* what) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev) return cms_fail(CMS_ERR_NO_DEVICE, what);
+  return CMS_OK;
+}
 // 16-entry per-level table of a kernel's argument struct: src[l] for the context's levels, `pad` behind them
 static inline void cms_level_table(float* dst, const cms_ctx* c, const float* src, float pad) {
   for (int l = 0; l < 16; ++l) dst[l] = l < c->g.nlevels ? src[l] : pad;
@@ -32,7 +49,7 @@ static int cms_lds_ceiling_once(const void* kernel, int bytes, int device, bool 
 }
 
 // The window-query entries guess a candidate capacity (64 per window) and repeat ONCE with the exact size when the device counted more.
-// attempt(cap, total) is one whole attempt: reserve (cms_scratch / cms_hstage may reallocate: block pointers are taken after that), stage the
+// attempt(cap, total) is one whole attempt: reserve (CmsStage::reserve may reallocate: block pointers are taken after that), stage the
 // caller's arrays (in/out ones afresh), launch, synchronise, leave the device's candidate total in `total`, and deliver the results only if
 // total <= cap (the list kernel never writes beyond cap, and the searches do nothing on lists that were cut).
 template <class Attempt>

@@ -1,5 +1,5 @@
 // cms_api_vocab.hip -- host side of Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cpp:719-726, src/KeyFrame.cpp:94-103): the cms_vocab handle
-// and the entries that run ORBVocabulary::transform on the device.  Included by cms_lib.hip behind cms_api_bow.hip (cms_ctx, cms_kfstore, bow_run)
+// and the entries that run ORBVocabulary::transform on the device.  Included by cms_lib.hip behind cms_api_bow.hip (cms_ctx and its CmsStage, cms_kfstore, bow_run)
 // and cms_vocab_kernels.hip.  A call is ONE launch of k_vocab_descend over all features of all its rows and ONE launch of k_vocab_build (a
 // workgroup per row); everything that becomes a device index (rows, slots, counts) is checked on the host before anything is enqueued.  The calls
 // end with the rows' three counts on the host (words, nodes, listed features): the next step of the caller -- SearchByBoW, the key-frame database,
@@ -26,9 +26,8 @@ extern "C" int cms_vocab_create(cms_vocab** out, int device, int k, int L, int s
   CmsVocabTree t;
   const char* why = cms_vocab_relayout(k, L, scoring, weighting, n_nodes, parent, is_leaf, desc, weight, &t);
   if (why) return cms_fail(CMS_ERR_ARG, (std::string("cms_vocab_create: ") + why).c_str());
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
-    return cms_fail(CMS_ERR_NO_DEVICE, "cms_vocab_create: no HIP device (the vocabulary's device path has no CPU fallback)");
+  const int rcd = cms_check_device(device, "cms_vocab_create: no HIP device (the vocabulary's device path has no CPU fallback)");
+  if (rcd) return rcd;
   HIPCHK(hipSetDevice(device));
   cms_vocab* v = new cms_vocab();
   v->device = device; v->group = k <= 16 ? 16 : 32;
@@ -131,21 +130,20 @@ extern "C" int cms_vocab_transform(cms_vocab* v, cms_ctx* c, int n, const uint8_
   CmsBlock blk;
   const size_t o_row = blk.take(sizeof(CmsVocRow)), o_desc = blk.take(32 * (size_t)n), in_bytes = blk.size;
   const size_t o_cnt = blk.take(16), o_out = blk.take(l.bytes);
-  rc = cms_scratch(c, blk.size);
+  hipStream_t s = c->stream;
+  rc = c->stage.reserve(s, blk.size, blk.size);
   if (rc) return rc;
-  rc = cms_hstage(c, blk.size);
-  if (rc) return rc;
-  uint8_t* d = (uint8_t*)c->d_match;
-  uint8_t* h = c->h_stage;
+  uint8_t* d = c->stage.d;
+  uint8_t* h = c->stage.h;
   const CmsVocRow row = voc_row_at(d + o_out, l, d + o_desc, n, false, (int*)(d + o_cnt));
   std::memcpy(h + o_row, &row, sizeof(row));
   if (n > 0) std::memcpy(h + o_desc, desc, 32 * (size_t)n);
-  hipStream_t s = c->stream;
-  HIPCHK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+  rc = c->stage.up(s, in_bytes, "cms_vocab_transform");
+  if (rc) return rc;
   rc = voc_launch(v, s, (const CmsVocRow*)(d + o_row), 1, n, levelsup);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(h + o_cnt, d + o_cnt, blk.size - o_cnt, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  rc = c->stage.back_and_wait(s, o_cnt, blk.size, "cms_vocab_transform");
+  if (rc) return rc;
   const int* cnt = (const int*)(h + o_cnt);
   const uint8_t* o = h + o_out;
   *nwords = cnt[0]; *nnodes = cnt[1];
@@ -257,15 +255,14 @@ extern "C" int cms_frames_fetch_bow(cms_ctx* c, int b, int* nwords, int* word_id
 // when every slot of the call fits the store's max_nodes.
 struct CmsStoreBow {
   int* d_word_id = nullptr; double* d_word_val = nullptr; int* d_nwords = nullptr;      // BowVector per slot (max_features entries)
-  uint8_t* d_tmp = nullptr; size_t tmp_bytes = 0;
-  uint8_t* h = nullptr; size_t h_bytes = 0;
+  CmsStage tmp;      // the call's scratch (row table | commit records | counts | rows) and the pinned copy of its head
   std::vector<int> nwords, nfeat;      // nwords < 0: the slot has no BowVector; nfeat: features its FeatureVector lists
 };
 static void cms_store_bow_free(CmsStoreBow* b) {
   if (!b) return;
-  void* bufs[] = {b->d_word_id, b->d_word_val, b->d_nwords, b->d_tmp};
+  void* bufs[] = {b->d_word_id, b->d_word_val, b->d_nwords};
   for (void* p : bufs) if (p) (void)hipFree(p);
-  if (b->h) (void)hipHostFree(b->h);
+  b->tmp.release();
   delete b;
 }
 
@@ -305,19 +302,13 @@ extern "C" int cms_kfstore_compute_bow(cms_kfstore* st, cms_vocab* v, int levels
   CmsBlock blk;
   const size_t o_rows = blk.take(S * sizeof(CmsVocRow)), o_commit = blk.take(S * sizeof(CmsVocCommit)), in_bytes = blk.size;
   const size_t o_cnt = blk.take(S * 12), head_bytes = blk.size, o_out = blk.take(S * l.bytes);
-  if (blk.size > w->tmp_bytes) {
-    if (w->d_tmp) { HIPCHK(hipFree(w->d_tmp)); w->d_tmp = nullptr; w->tmp_bytes = 0; }
-    HIPCHK(hipMalloc((void**)&w->d_tmp, blk.size));
-    w->tmp_bytes = blk.size;
-  }
-  if (head_bytes > w->h_bytes) {
-    if (w->h) { HIPCHK(hipHostFree(w->h)); w->h = nullptr; w->h_bytes = 0; }
-    HIPCHK(hipHostMalloc((void**)&w->h, head_bytes));
-    w->h_bytes = head_bytes;
-  }
-  uint8_t* d = w->d_tmp;
-  CmsVocRow* hr = reinterpret_cast<CmsVocRow*>(w->h + o_rows);
-  CmsVocCommit* hcm = reinterpret_cast<CmsVocCommit*>(w->h + o_commit);
+  hipStream_t s = c->stream;
+  rc = w->tmp.reserve(s, blk.size, head_bytes);
+  if (rc) return rc;
+  uint8_t* d = w->tmp.d;
+  uint8_t* h = w->tmp.h;
+  CmsVocRow* hr = reinterpret_cast<CmsVocRow*>(h + o_rows);
+  CmsVocCommit* hcm = reinterpret_cast<CmsVocCommit*>(h + o_commit);
   int max_n = 0;
   for (int i = 0; i < n_slots; ++i) {
     const CmsTriKF& k = st->h_kf[(size_t)slots[i]];
@@ -330,13 +321,13 @@ extern "C" int cms_kfstore_compute_bow(cms_kfstore* st, cms_vocab* v, int levels
     cm.o_word_id = w->d_word_id + (size_t)slots[i] * Fq; cm.o_word_val = w->d_word_val + (size_t)slots[i] * Fq; cm.o_nwords = w->d_nwords + slots[i];
     max_n = std::max(max_n, k.n);
   }
-  hipStream_t s = c->stream;
-  HIPCHK(hipMemcpyAsync(d, w->h, in_bytes, hipMemcpyHostToDevice, s));
+  rc = w->tmp.up(s, in_bytes, "cms_kfstore_compute_bow");
+  if (rc) return rc;
   rc = voc_launch(v, s, (const CmsVocRow*)(d + o_rows), n_slots, max_n, levelsup);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(w->h + o_cnt, d + o_cnt, S * 12, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  const int* cnt = reinterpret_cast<const int*>(w->h + o_cnt);
+  rc = w->tmp.back_and_wait(s, o_cnt, o_cnt + S * 12, "cms_kfstore_compute_bow");
+  if (rc) return rc;
+  const int* cnt = reinterpret_cast<const int*>(h + o_cnt);
   for (int i = 0; i < n_slots; ++i)
     if (cnt[3 * i + 1] > st->maxn) return cms_fail(CMS_ERR_OVERFLOW, "cms_kfstore_compute_bow: a FeatureVector has more nodes than the store's max_nodes (no slot was changed)");
   hipLaunchKernelGGL(k_vocab_commit, dim3(n_slots), dim3(CMS_VOC_THREADS), 0, s, (const CmsVocCommit*)(d + o_commit));
@@ -378,29 +369,36 @@ extern "C" int cms_kfstore_fetch_bow(cms_kfstore* st, int slot, int* nwords, int
   return CMS_OK;
 }
 
-// cms_kfstore_search_by_bow with the frame side's FeatureVector taken from the row's resident result (the jobs' node arrays are not read)
-extern "C" int cms_kfstore_search_by_bow_frames(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_job* jobs, float nnratio, int check_orientation,
-                                                int* kf_idx, int* n_matches) {
-  if (!st || !src || njobs < 0 || (njobs > 0 && (!jobs || !n_matches))) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow_frames: bad argument");
+// Relocalization's candidate loop (Tracking.cpp:1019-1040) or one TrackReferenceKeyFrame per camera stream on resident key frames: ONE launch on
+// src's stream.  Nothing is enqueued on the store's stream; the copies of cms_kfstore_put_from_frame(s) that filled a named slot are waited for on
+// the device (their events: the copy may still be in flight when it ran on another context's stream).
+// frames: cms_kfstore_search_by_bow_frames -- the frame side's FeatureVector is taken from the row's resident result (the jobs' node arrays are not read)
+static int kfstore_search_by_bow_run(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_job* jobs, float nnratio, int check_orientation, int* kf_idx,
+                                     int* n_matches, bool frames) {
+  const std::string who = frames ? "cms_kfstore_search_by_bow_frames" : "cms_kfstore_search_by_bow";
+  if (!st || !src || njobs < 0 || (njobs > 0 && (!jobs || !n_matches))) return cms_fail(CMS_ERR_ARG, (who + ": bad argument").c_str());
   if (njobs == 0) return CMS_OK;
-  if (src->device != st->c->device) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow_frames: the frame context and the store must share the device");
+  if (src->device != st->c->device) return cms_fail(CMS_ERR_ARG, (who + ": the frame context and the store must share the device").c_str());
+  std::vector<uint8_t> seen;
   size_t total_n = 0;
   for (int j = 0; j < njobs; ++j) {
     const cms_bow_job& q = jobs[j];
-    if (q.slot < 0 || q.slot >= st->maxkf || !st->used[(size_t)q.slot]) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow_frames: empty slot");
-    const int rc = bow_check_frame(src, q.b, q.n, "cms_kfstore_search_by_bow_frames: bad frame");
+    if (q.slot < 0 || q.slot >= st->maxkf || !st->used[(size_t)q.slot]) return cms_fail(CMS_ERR_ARG, (who + ": empty slot").c_str());
+    int rc = bow_check_frame(src, q.b, q.n, (who + ": bad frame").c_str());
     if (rc) return rc;
-    if (!src->bow || src->bow->n[(size_t)q.b] < 0) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow_frames: no BoW computed for the frame row (cms_frames_compute_bow first)");
-    if (src->bow->n[(size_t)q.b] != q.n) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow_frames: the row's BoW was computed for another key-point count");
+    if (frames) {
+      if (!src->bow || src->bow->n[(size_t)q.b] < 0) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow_frames: no BoW computed for the frame row (cms_frames_compute_bow first)");
+      if (src->bow->n[(size_t)q.b] != q.n) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow_frames: the row's BoW was computed for another key-point count");
+    } else {
+      rc = bow_check_fv(q.n, q.nnodes, q.node_id, q.node_off, q.node_feat, &seen, "cms_kfstore_search_by_bow: bad frame FeatureVector");
+      if (rc) return rc;
+    }
     total_n += (size_t)q.n;
   }
-  if (total_n > 0 && !kf_idx) return cms_fail(CMS_ERR_ARG, "cms_kfstore_search_by_bow_frames: bad argument");
+  if (total_n > 0 && !kf_idx) return cms_fail(CMS_ERR_ARG, (who + ": bad argument").c_str());
   HIPCHK(hipSetDevice(src->device));
-  hipStream_t s = src->stream;
-  for (int j = 0; j < njobs; ++j) {
-    const auto& call = st->ff_call[(size_t)jobs[j].slot];
-    if (call) HIPCHK(hipStreamWaitEvent(s, call->ev, 0));
-  }
+  int rc = kfstore_wait_puts(st, src->stream, njobs, [&](int j) { return jobs[j].slot; });
+  if (rc) return rc;
   std::vector<CmsBowJob> dj((size_t)njobs);
   std::vector<std::vector<const void**>> rel((size_t)njobs);
   std::vector<BowStage> pieces;
@@ -413,10 +411,27 @@ extern "C" int cms_kfstore_search_by_bow_frames(cms_kfstore* st, cms_ctx* src, i
     d.kf_kp = st->d_kp + k.f0; d.kf_desc = (const uint4*)(st->d_desc + 32 * (size_t)k.f0); d.kf_mp = st->d_mp + k.f0;
     d.kf_nid = st->d_nid + k.node0; d.kf_noff = st->d_noff + k.noff0; d.kf_nfeat = st->d_nfeat + k.nfeat0; d.kf_nnodes = k.nnodes;
     if (q.kf_skip) bow_put(pieces, blk, rel[(size_t)j], d.kf_skip, q.kf_skip, (size_t)k.n);
-    const CmsVocRow r = cms_ctx_bow_row(src, q.b, q.n);
-    d.f_nid = r.node_id; d.f_noff = r.node_off; d.f_nfeat = r.node_feat; d.f_nnodes = src->bow->nnodes[(size_t)q.b]; d.n = q.n;
+    if (frames) {
+      const CmsVocRow r = cms_ctx_bow_row(src, q.b, q.n);
+      d.f_nid = r.node_id; d.f_noff = r.node_off; d.f_nfeat = r.node_feat; d.f_nnodes = src->bow->nnodes[(size_t)q.b];
+    } else {
+      const int ffeat = q.nnodes > 0 ? q.node_off[q.nnodes] : 0;
+      bow_put(pieces, blk, rel[(size_t)j], d.f_nid, q.node_id, 4 * (size_t)q.nnodes);
+      bow_put(pieces, blk, rel[(size_t)j], d.f_noff, q.node_off, q.nnodes > 0 ? 4 * ((size_t)q.nnodes + 1) : 0);
+      bow_put(pieces, blk, rel[(size_t)j], d.f_nfeat, q.node_feat, 4 * (size_t)ffeat);
+      d.f_nnodes = q.nnodes;
+    }
+    d.n = q.n;
     const size_t sb = (size_t)q.b * src->g.kp_cap;
     d.f_kp = (const CmsKeyPoint*)src->d_kps + sb; d.f_desc = (const uint4*)(src->d_desc + 32 * sb);
   }
-  return bow_run(src, dj, rel, pieces, blk, nnratio, check_orientation, kf_idx, n_matches);
+  return bow_run(src, dj, rel, pieces, blk, nnratio, check_orientation, kf_idx, n_matches, who.c_str());
+}
+extern "C" int cms_kfstore_search_by_bow(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_job* jobs, float nnratio, int check_orientation,
+                                         int* kf_idx, int* n_matches) {
+  return kfstore_search_by_bow_run(st, src, njobs, jobs, nnratio, check_orientation, kf_idx, n_matches, false);
+}
+extern "C" int cms_kfstore_search_by_bow_frames(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_job* jobs, float nnratio, int check_orientation,
+                                                int* kf_idx, int* n_matches) {
+  return kfstore_search_by_bow_run(st, src, njobs, jobs, nnratio, check_orientation, kf_idx, n_matches, true);
 }

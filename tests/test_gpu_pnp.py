@@ -182,9 +182,10 @@ def test_golden_cases_on_the_device(ctx, solver):
     same(want, got)
 
 
-def test_iterate_frames_gathers_from_the_resident_row():
-    """cms_pnp_iterate_frames (key point, key ray and level sigma2 gathered on the device from the row the extractor left) against cms_pnp_iterate and
-    the host loop on the same data fetched to the host: two jobs on one row with different mvKeyPointIndices"""
+@pytest.fixture(scope="module")
+def frame_row():
+    """A context whose row 0 holds an extracted frame, and two PnP jobs on it with different mvKeyPointIndices: (context, key-point count,
+    states(frames) -> fresh job records, for cms_pnp_iterate_frames or with the row's data fetched to the host)"""
     camd = synth.camera("lafida", 150)
     c = api.Context(camd, nfeatures=800, max_batch=1, device=0)
     try:
@@ -212,10 +213,20 @@ def test_iterate_frames_gathers_from_the_resident_row():
                     s.update(kp_idx=idx, b=0, n=n, p2d=np.zeros((N, 2), np.float32), bearing=np.zeros((N, 3), np.float32), sigma2=np.zeros(N, np.float32))
                 out.append(s)
             return out
-        F150 = 150
-        rc, want = hl.iterate_host(F150, states(False))
-        assert rc == 0
-        S = api.PnPSolver(4, 1024, 512)
+        yield c, n, states
+    finally:
+        c.close()
+
+
+def test_iterate_frames_gathers_from_the_resident_row(frame_row):
+    """cms_pnp_iterate_frames (key point, key ray and level sigma2 gathered on the device from the row the extractor left) against cms_pnp_iterate and
+    the host loop on the same data fetched to the host: two jobs on one row with different mvKeyPointIndices"""
+    c, n, states = frame_row
+    F150 = 150
+    rc, want = hl.iterate_host(F150, states(False))
+    assert rc == 0
+    S = api.PnPSolver(4, 1024, 512)
+    try:
         same(want, S.run(c, states(False)))
         got = S.run(c, states(True), frames=True)
         same(want, got)
@@ -224,9 +235,32 @@ def test_iterate_frames_gathers_from_the_resident_row():
         assert api.lib().cms_pnp_iterate_frames(S.h, c.h, 2, api.pnp_jobs(bad)) == -1
         bad = states(True); bad[1]["b"] = 1
         assert api.lib().cms_pnp_iterate_frames(S.h, c.h, 2, api.pnp_jobs(bad)) == -1
-        S.close()
     finally:
-        c.close()
+        S.close()
+
+
+def test_handle_reuse(ctx, frame_row):
+    """One handle through a large call, a small one and the large one again on its own stream, with calls on a frame context's stream in between (the
+    same pair of blocks used from the other stream): the blocks are grown once and reused, and every result is that of a fresh handle"""
+    fc, _, frame_states = frame_row
+    large = noisy_states([60, 65, 7, 130, 64, 257, 321, 20, 63, 129], 40)
+    small = noisy_states([20], 47)
+    calls = [(ctx, large, False), (fc, lambda: frame_states(True), True), (ctx, small, False), (fc, lambda: frame_states(True), True), (ctx, large, False)]
+
+    def fresh(c, make, frames):
+        S = api.PnPSolver(16, 4096, 2048)
+        try:
+            return S.run(c, make(), frames=frames)
+        finally:
+            S.close()
+    want = [fresh(*call) for call in calls[:3]]
+    want += [want[1], want[0]]
+    S = api.PnPSolver(16, 4096, 2048)
+    try:
+        for (c, make, frames), w in zip(calls, want):
+            same(w, S.run(c, make(), frames=frames))
+    finally:
+        S.close()
 
 
 def test_mirror_class_on_the_device():

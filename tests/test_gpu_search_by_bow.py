@@ -190,20 +190,25 @@ CASES = [  # the hand-built cases of test_search_by_bow_cpu.py: (kf rows, frame 
 EXPECT_N = [0, 3, 1, 0, 0, 1, 3, 11, 11, 12, 1, 1, 1]
 
 
+def hand_built(c_):
+    """a row of CASES -> (key frame, skip flags, frame key points, frame descriptors, frame FeatureVector, nnratio, orientation check)"""
+    kr, fr_, kfv, ffv, ka, fa, hm, bad, nnr, ori = c_
+    nk, n = len(kr), len(fr_)
+    kd = np.zeros((nk, 32), np.uint8)
+    fd = np.stack([desc_at(d, 7 * i) for i, d in enumerate(fr_)])
+    kk = _kps(np.full(nk, 100.0), np.full(nk, 100.0), np.zeros(nk), np.zeros(nk) if ka is None else ka)
+    fk = _kps(np.full(n, 100.0), np.full(n, 100.0), np.zeros(n), np.zeros(n) if fa is None else fa)
+    mp = np.where(np.ones(nk, bool) if hm is None else np.asarray(hm, bool), np.arange(nk), -1).astype(np.int32)
+    ki, ko, kf_ = fv(kfv)
+    kf = _keyframe(kk, kd, mp, dict(node_id=ki, node_off=ko, node_feat=kf_))
+    return kf, None if bad is None else np.asarray(bad, np.uint8), fk, fd, fv(ffv), nnr, ori
+
+
 def test_hand_built_cases_through_the_device(big_ctx):
     for c_, en in zip(CASES, EXPECT_N):
-        kr, fr_, kfv, ffv, ka, fa, hm, bad, nnr, ori = c_
-        nk, n = len(kr), len(fr_)
-        kd = np.zeros((nk, 32), np.uint8)
-        fd = np.stack([desc_at(d, 7 * i) for i, d in enumerate(fr_)])
-        kk = _kps(np.full(nk, 100.0), np.full(nk, 100.0), np.zeros(nk), np.zeros(nk) if ka is None else ka)
-        fk = _kps(np.full(n, 100.0), np.full(n, 100.0), np.zeros(n), np.zeros(n) if fa is None else fa)
-        mp = np.where(np.ones(nk, bool) if hm is None else np.asarray(hm, bool), np.arange(nk), -1).astype(np.int32)
-        ki, ko, kf_ = fv(kfv)
-        fi, fo, ff = fv(ffv)
-        kf = _keyframe(kk, kd, mp, dict(node_id=ki, node_off=ko, node_feat=kf_))
+        kf, skip, fk, fd, ffv, nnr, ori = hand_built(c_)
         _place(big_ctx, 1, fk, fd)
-        got = _check(big_ctx, 1, kf, None if bad is None else np.asarray(bad, np.uint8), fk, fd, (fi, fo, ff), nnr, ori)
+        got = _check(big_ctx, 1, kf, skip, fk, fd, ffv, nnr, ori)
         assert got[1] == en, (c_, got)
 
 
