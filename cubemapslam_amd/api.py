@@ -628,6 +628,44 @@ class KfProjJob(C.Structure):
                 ("min_dist", C.c_void_p), ("max_dist", C.c_void_p), ("mp_desc", C.c_void_p), ("kp_mp", C.c_void_p), ("match", C.c_void_p)]
 
 
+class KfdbJob(C.Structure):
+    """cms_kfdb_job (include/cubemapslam_hip.h)"""
+    _fields_ = [("mode", C.c_int), ("group", C.c_int), ("query", C.c_int), ("b", C.c_int), ("slot", C.c_int), ("nwords", C.c_int), ("word_id", C.c_void_p),
+                ("word_val", C.c_void_p), ("min_score", C.c_float), ("n_connected", C.c_int), ("connected", C.c_void_p)]
+
+
+KFDB_RELOC, KFDB_LOOP = 0, 1
+KFDB_QUERY = {"row": 0, "slot": 1, "words": 2}
+
+
+def kfdb_jobs(jobs):
+    """cms_kfdb_job records from dicts: mode (KFDB_RELOC / KFDB_LOOP), group, query = ("row", b) | ("slot", s) | ("words", ids, vals), and for
+    KFDB_LOOP min_score and connected (slots).  Returns (array, the numpy arrays the records point into: keep them until the call has returned)."""
+    arr = (KfdbJob * max(len(jobs), 1))()
+    keep = []
+    for q, j in zip(arr, jobs):
+        form = j["query"]
+        q.mode = int(j["mode"]); q.group = int(j.get("group", 0)); q.query = KFDB_QUERY[form[0]]
+        if form[0] == "row":
+            q.b = int(form[1])
+        elif form[0] == "slot":
+            q.slot = int(form[1])
+        else:
+            ids = np.ascontiguousarray(form[1], np.int32); vals = np.ascontiguousarray(form[2], np.float64)
+            assert len(ids) == len(vals)
+            keep += [ids, vals]
+            q.nwords = len(ids); q.word_id = ids.ctypes.data if len(ids) else None; q.word_val = vals.ctypes.data if len(ids) else None
+        conn = np.ascontiguousarray(j.get("connected", ()), np.int32)
+        keep.append(conn)
+        q.min_score = float(j.get("min_score", 0.0)); q.n_connected = len(conn); q.connected = conn.ctypes.data if len(conn) else None
+    return arr, keep
+
+
+def kfdb_results(njobs, K, cap, cand, n_cand, common, score):
+    """per job (candidate slots, common words int32[K], score bits uint32[K]) from the arrays of cms_kfdb_detect"""
+    return [([int(c) for c in cand[j, :min(int(n_cand[j]), cap)]], common[j].copy(), score[j].view(np.uint32).copy()) for j in range(njobs)]
+
+
 def _bow_fv(fv):
     """a FeatureVector as CSR int32 arrays: fv = dict(node_id, node_off, node_feat) or the tuple (node_id, node_off, node_feat)"""
     if isinstance(fv, dict):
@@ -745,6 +783,7 @@ class KeyframeStore:
 
     def __init__(self, ctx, max_keyframes, max_features=2048, max_nodes=2048):
         self.ctx = ctx
+        self.max_keyframes = int(max_keyframes)
         self.h = C.c_void_p()
         _chk(lib().cms_kfstore_create(C.byref(self.h), ctx.h, max_keyframes, max_features, max_nodes), "cms_kfstore_create")
 
@@ -930,6 +969,79 @@ class KeyframeStore:
         _chk(L.cms_kfstore_search_by_bow_frames(self.h, src_ctx.h, len(jobs), arr, float(nnratio), int(check_orientation), _p(kf_idx), _p(nm)),
              "cms_kfstore_search_by_bow_frames")
         return [(kf_idx[off[j]:off[j + 1]].copy(), int(nm[j])) for j in range(len(jobs))]
+
+    # ---- KeyFrameDatabase over the slots (cms_kfdb_*)
+    def set_bow(self, slot, word_id, word_val):
+        """cms_kfstore_set_bow: the BowVector the host computed for the key frame in `slot` (ids ascending)"""
+        ids = np.ascontiguousarray(word_id, np.int32); vals = np.ascontiguousarray(word_val, np.float64)
+        assert len(ids) == len(vals)
+        L = lib()
+        L.cms_kfstore_set_bow.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _chk(L.cms_kfstore_set_bow(self.h, int(slot), len(ids), _p(ids) if len(ids) else None, _p(vals) if len(ids) else None), "cms_kfstore_set_bow")
+
+    def db_add(self, slots, groups=None):
+        """cms_kfdb_add: KeyFrameDatabase::add for the key frames in `slots`; groups: one int >= 0 per slot (default 0)"""
+        slots = np.ascontiguousarray(slots, np.int32)
+        groups = np.zeros(len(slots), np.int32) if groups is None else np.ascontiguousarray(groups, np.int32)
+        assert len(groups) == len(slots)
+        L = lib()
+        L.cms_kfdb_add.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _chk(L.cms_kfdb_add(self.h, len(slots), _p(slots), _p(groups)), "cms_kfdb_add")
+
+    def db_erase(self, slots):
+        """cms_kfdb_erase: KeyFrameDatabase::erase (a slot that is not in the database is left alone)"""
+        slots = np.ascontiguousarray(slots, np.int32)
+        L = lib()
+        L.cms_kfdb_erase.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _chk(L.cms_kfdb_erase(self.h, len(slots), _p(slots)), "cms_kfdb_erase")
+
+    def db_clear(self, group=-1):
+        """cms_kfdb_clear: KeyFrameDatabase::clear of one group, or of all (-1)"""
+        L = lib()
+        L.cms_kfdb_clear.argtypes = [C.c_void_p, C.c_int]
+        _chk(L.cms_kfdb_clear(self.h, int(group)), "cms_kfdb_clear")
+
+    def db_set_covisibles(self, slots, neigh):
+        """cms_kfdb_set_covisibles: GetBestCovisibilityKeyFrames(10) per slot as slots, neigh int32[n, 10], best first, -1 padded"""
+        slots = np.ascontiguousarray(slots, np.int32); neigh = np.ascontiguousarray(neigh, np.int32).reshape(-1, 10)
+        assert len(neigh) == len(slots)
+        L = lib()
+        L.cms_kfdb_set_covisibles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _chk(L.cms_kfdb_set_covisibles(self.h, len(slots), _p(slots), _p(neigh)), "cms_kfdb_set_covisibles")
+
+    def detect_candidates(self, src_ctx, jobs, cand_cap=None, diag=True):
+        """cms_kfdb_detect: DetectRelocalizationCandidates / DetectLoopCandidates for many queries as ONE launch sequence on src_ctx's stream.  jobs: see
+        kfdb_jobs.  Returns per job (candidate slots, common words int32[K] or None, score bits uint32[K] or None); self.last_n_cand holds the counts,
+        also when the call raises CMS_ERR_OVERFLOW (CmsError)."""
+        K = self.max_keyframes
+        cap = K if cand_cap is None else int(cand_cap)
+        nj = len(jobs)
+        arr, keep = kfdb_jobs(jobs)
+        cand = np.full((max(nj, 1), max(cap, 1)), -1, np.int32); n_cand = np.zeros(max(nj, 1), np.int32)
+        common = np.zeros((max(nj, 1), K), np.int32) if diag else None
+        score = np.zeros((max(nj, 1), K), np.float32) if diag else None
+        L = lib()
+        L.cms_kfdb_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        self.last_n_cand = n_cand
+        if cap == 0:
+            cand = np.full((max(nj, 1), 1), -1, np.int32)
+        t0 = time.perf_counter()
+        rc = L.cms_kfdb_detect(self.h, src_ctx.h, nj, arr, cap, _p(cand), _p(n_cand), _p(common), _p(score))
+        self.last_call_ms = 1e3 * (time.perf_counter() - t0)
+        _chk(rc, "cms_kfdb_detect")
+        if not diag:
+            return [([int(c) for c in cand[j, :int(n_cand[j])]], None, None) for j in range(nj)]
+        return kfdb_results(nj, K, cap, cand, n_cand, common, score)
+
+    def bow_score(self, slot_a, slot_b):
+        """cms_kfstore_bow_score: ORBVocabulary::score of the BowVectors of pairs of slots (DetectLoop's score() loop), float64[npairs]"""
+        a = np.ascontiguousarray(slot_a, np.int32); b = np.ascontiguousarray(slot_b, np.int32)
+        assert len(a) == len(b)
+        out = np.zeros(max(len(a), 1), np.float64)
+        L = lib()
+        L.cms_kfstore_bow_score.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _chk(L.cms_kfstore_bow_score(self.h, len(a), _p(a), _p(b), _p(out)), "cms_kfstore_bow_score")
+        return out[:len(a)]
 
     def search_by_projection(self, src_ctx, jobs, th=10.0, orb_dist=100, check_orientation=True):
         """cms_kfstore_search_by_projection: ORBMatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) for many (resident key frame,

@@ -319,9 +319,14 @@ extern "C" int cms_search_for_triangulation(cms_ctx* c, const cms_keyframe* kf1,
 struct CmsStoreBow;      // the slots' BowVectors and the scratch of cms_kfstore_compute_bow (cms_api_vocab.hip), allocated on first use
 static void cms_store_bow_free(CmsStoreBow* b);
 static void cms_store_bow_invalidate(CmsStoreBow* b, int slot);      // a slot is refilled: its BowVector belonged to the key frame it held
+struct CmsStoreKfdb;     // the key-frame database over the slots (cms_api_kfdb.hip): host table, its mutex and the slots' reloc_score; made with the store
+static CmsStoreKfdb* cms_store_kfdb_new(int max_keyframes);
+static void cms_store_kfdb_free(CmsStoreKfdb* d);
+static void cms_store_kfdb_refill(CmsStoreKfdb* d, int slot);      // a slot is refilled: the key frame it held leaves the database
 struct cms_kfstore {
   cms_ctx* c = nullptr;
   CmsStoreBow* bow = nullptr;
+  CmsStoreKfdb* kfdb = nullptr;
   int maxkf = 0, maxf = 0, maxn = 0;
   CmsTriKF* d_kf = nullptr; CmsKeyPoint* d_kp = nullptr; uint8_t* d_desc = nullptr; float* d_rays = nullptr; int* d_mp = nullptr; int* d_fn = nullptr;
   int* d_nid = nullptr; int* d_noff = nullptr; int* d_nfeat = nullptr;
@@ -366,6 +371,7 @@ extern "C" void cms_kfstore_destroy(cms_kfstore* st) {
                   st->d_sorted, st->d_cell_start, st->d_nvalid, st->d_kp_cnt};
   for (void* b : bufs) if (b) (void)hipFree(b);
   cms_store_bow_free(st->bow);
+  cms_store_kfdb_free(st->kfdb);
   if (st->h_ff) (void)hipHostFree(st->h_ff);
   if (st->h_items) (void)hipHostFree(st->h_items);
   if (st->h_upd) (void)hipHostFree(st->h_upd);
@@ -397,6 +403,8 @@ extern "C" int cms_kfstore_create(cms_kfstore** out, cms_ctx* c, int max_keyfram
   KF_ALLOC(st->d_nvalid, K * sizeof(int));
   KF_ALLOC(st->d_kp_cnt, K * sizeof(int));
 #undef KF_ALLOC
+  st->kfdb = cms_store_kfdb_new(max_keyframes);
+  if (!st->kfdb) { cms_kfstore_destroy(st); return cms_fail(CMS_ERR_HIP, "cms_kfstore_create: out of device memory"); }
   st->h_kf.assign(K, CmsTriKF{}); st->h_median.assign(K, 1.0f); st->used.assign(K, 0); st->busy.assign(K, 0);
   st->ff_call.assign(K, nullptr);      // (here, not at the first put from a frame: cms_kfstore_search_by_bow reads it from the frame thread)
   *out = st;
@@ -442,6 +450,7 @@ extern "C" int cms_kfstore_put(cms_kfstore* st, int slot, const cms_keyframe* kf
   HIPCHK(hipStreamSynchronize(s));
   st->h_kf[(size_t)slot] = d; st->h_median[(size_t)slot] = kf->median_depth; st->used[(size_t)slot] = 1;
   cms_store_bow_invalidate(st->bow, slot);
+  cms_store_kfdb_refill(st->kfdb, slot);
   return CMS_OK;
 }
 
@@ -607,6 +616,7 @@ extern "C" int cms_kfstore_put_from_frames(cms_kfstore* st, cms_ctx* src, int n_
     st->ff_call[(size_t)q.slot] = call;
     st->h_kf[(size_t)q.slot] = h_items[i].kf; st->h_median[(size_t)q.slot] = q.median_depth; st->used[(size_t)q.slot] = 1;
     cms_store_bow_invalidate(st->bow, q.slot);
+    cms_store_kfdb_refill(st->kfdb, q.slot);
   }
   st->items_call[gen] = call;
   return CMS_OK;

@@ -270,6 +270,21 @@ static void cms_store_bow_invalidate(CmsStoreBow* b, int slot) {
   if (b) b->nwords[(size_t)slot] = -1;
 }
 
+// the slots' BowVector arrays, allocated by the first call that gives a slot one (cms_kfstore_compute_bow, cms_kfstore_set_bow)
+static int cms_store_bow_reserve(cms_kfstore* st, const char* oom) {
+  if (st->bow) return CMS_OK;
+  const size_t K = (size_t)st->maxkf, Fq = (size_t)st->maxf;
+  CmsStoreBow* b = new CmsStoreBow();
+  if (hipMalloc((void**)&b->d_word_id, K * Fq * 4) != hipSuccess || hipMalloc((void**)&b->d_word_val, K * Fq * 8) != hipSuccess ||
+      hipMalloc((void**)&b->d_nwords, K * 4) != hipSuccess) {
+    cms_store_bow_free(b);
+    return cms_fail(CMS_ERR_HIP, oom);
+  }
+  b->nwords.assign(K, -1); b->nfeat.assign(K, 0);
+  st->bow = b;
+  return CMS_OK;
+}
+
 extern "C" int cms_kfstore_compute_bow(cms_kfstore* st, cms_vocab* v, int levelsup, int n_slots, const int* slots) {
   if (!st || n_slots < 0 || n_slots > st->maxkf || (n_slots > 0 && !slots)) return cms_fail(CMS_ERR_ARG, "cms_kfstore_compute_bow: bad argument");
   cms_ctx* c = st->c;
@@ -286,17 +301,9 @@ extern "C" int cms_kfstore_compute_bow(cms_kfstore* st, cms_vocab* v, int levels
   if (n_slots == 0) return CMS_OK;
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(kfstore_order_behind_puts(st));
-  const size_t K = (size_t)st->maxkf, Fq = (size_t)st->maxf, S = (size_t)n_slots;
-  if (!st->bow) {
-    CmsStoreBow* b = new CmsStoreBow();
-    if (hipMalloc((void**)&b->d_word_id, K * Fq * 4) != hipSuccess || hipMalloc((void**)&b->d_word_val, K * Fq * 8) != hipSuccess ||
-        hipMalloc((void**)&b->d_nwords, K * 4) != hipSuccess) {
-      cms_store_bow_free(b);
-      return cms_fail(CMS_ERR_HIP, "cms_kfstore_compute_bow: out of device memory");
-    }
-    b->nwords.assign(K, -1); b->nfeat.assign(K, 0);
-    st->bow = b;
-  }
+  const size_t Fq = (size_t)st->maxf, S = (size_t)n_slots;
+  rc = cms_store_bow_reserve(st, "cms_kfstore_compute_bow: out of device memory");
+  if (rc) return rc;
   CmsStoreBow* w = st->bow;
   const VocRowLayout l = voc_row_layout(st->maxf);
   CmsBlock blk;

@@ -9,7 +9,9 @@
 #include <fstream>
 #include <iomanip>
 #include <stdexcept>
+#include <map>
 #include "../csrc/cms_vocab_core.h"
+#include "../csrc/cms_kfdb_core.h"
 
 namespace CubemapSLAM {
 
@@ -1011,6 +1013,122 @@ void FrameView::ComputeBoW(const ORBVocabulary& voc) {
 }
 void KeyFrameView::ComputeBoW(const ORBVocabulary& voc) {
   if (mBowVec.empty() || mFeatVec.empty()) voc.transform(descriptor_rows(mDescriptors), mBowVec, mFeatVec, 4);
+}
+
+
+// ---- KeyFrameDatabase (src/KeyFrameDatabase.cpp)
+struct KeyFrameDatabase::Impl {
+  const ORBVocabulary* voc;
+  int max_keyframes, max_features;
+  CmsKfdbHost host;                          // HOST_CORE; also the slot table of both engines (which slot holds which view)
+  std::map<KeyFrameView*, int> slot_of;      // key frames in the database
+  std::vector<KeyFrameView*> kf_of;
+  cms_kfstore* store = nullptr;              // DEVICE, made by the first add
+  Impl(const ORBVocabulary& v, int K, int Fq) : voc(&v), max_keyframes(K), max_features(Fq), host(K, Fq), kf_of((size_t)K, nullptr) {}
+  cms_ctx* ctx() const {
+    return g_ctx_orb.nfeatures > 0 ? SharedContext(g_ctx_orb.nfeatures, g_ctx_orb.scale_factor, g_ctx_orb.nlevels, g_ctx_orb.ini_th_fast, g_ctx_orb.min_th_fast)
+                                   : SharedContext(2000, 1.2f, 8, 20, 7);
+  }
+  void need_l1() const {
+    if (!voc->empty() && voc->tree().scoring != CMS_VOC_L1_NORM) throw std::runtime_error("KeyFrameDatabase: only L1 scoring is supported");
+  }
+  std::vector<KeyFrameView*> detect(Engine engine, int mode, const BowVector& bow, float min_score, const std::vector<KeyFrameView*>& connected) {
+    need_l1();
+    std::vector<int> ids(bow.size() + 1), conn;
+    std::vector<double> vals(bow.size() + 1);
+    for (size_t i = 0; i < bow.size(); ++i) { ids[i] = (int)bow[i].first; vals[i] = bow[i].second; }
+    for (KeyFrameView* c : connected) { auto it = slot_of.find(c); if (it != slot_of.end()) conn.push_back(it->second); }
+    std::vector<int> cand;
+    if (engine == HOST_CORE) {
+      CmsKfdbQuery q;
+      q.mode = mode; q.group = 0; q.bow = CmsKfdbBow{(int)bow.size(), ids.data(), vals.data()}; q.min_score = min_score; q.n_connected = (int)conn.size(); q.connected = conn.data();
+      host.detect(q, &cand, nullptr, nullptr);
+    } else if (store) {
+      cms_kfdb_job j = {};
+      j.mode = mode; j.group = 0; j.query = CMS_KFDB_QUERY_WORDS; j.nwords = (int)bow.size(); j.word_id = ids.data(); j.word_val = vals.data();
+      j.min_score = min_score; j.n_connected = (int)conn.size(); j.connected = conn.data();
+      cand.resize((size_t)max_keyframes);
+      int n = 0;
+      cms_ctx* c = ctx();
+      std::lock_guard<std::mutex> lock(g_ctx_mutex);
+      if (cms_kfdb_detect(store, c, 1, &j, max_keyframes, cand.data(), &n, nullptr, nullptr) != CMS_OK)
+        throw std::runtime_error(std::string("cms_kfdb_detect failed: ") + cms_last_error());
+      cand.resize((size_t)n);
+    }
+    std::vector<KeyFrameView*> out;
+    for (int s : cand) out.push_back(kf_of[(size_t)s]);
+    return out;
+  }
+};
+KeyFrameDatabase::KeyFrameDatabase(const ORBVocabulary& voc, int max_keyframes, int max_features) : impl_(new Impl(voc, max_keyframes, max_features)) {}
+KeyFrameDatabase::~KeyFrameDatabase() {
+  if (impl_->store) cms_kfstore_destroy(impl_->store);
+  delete impl_;
+}
+void KeyFrameDatabase::add(KeyFrameView* pKF) {
+  Impl& m = *impl_;
+  if (!pKF || m.slot_of.count(pKF)) throw std::runtime_error("KeyFrameDatabase::add: null key frame, or one that is in the database already");
+  int slot = 0;
+  while (slot < m.max_keyframes && m.kf_of[(size_t)slot]) ++slot;
+  if (slot == m.max_keyframes) throw std::runtime_error("KeyFrameDatabase::add: more key frames than max_keyframes");
+  const size_t n = pKF->mBowVec.size();
+  std::vector<int> ids(n + 1);
+  std::vector<double> vals(n + 1);
+  for (size_t i = 0; i < n; ++i) { ids[i] = (int)pKF->mBowVec[i].first; vals[i] = pKF->mBowVec[i].second; }
+  const int group = 0;
+  m.host.refill(slot);
+  if (m.host.set_bow(slot, (int)n, ids.data(), vals.data())) throw std::runtime_error("KeyFrameDatabase::add: the BowVector does not ascend or has more words than max_features");
+  if (engine == DEVICE) {
+    cms_ctx* c = m.ctx();
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!m.store && cms_kfstore_create(&m.store, c, m.max_keyframes, m.max_features, m.max_features) != CMS_OK)
+      throw std::runtime_error(std::string("cms_kfstore_create failed: ") + cms_last_error());
+    KfPack pack;
+    const cms_keyframe k = pack_keyframe(*pKF, pack);
+    if (cms_kfstore_put(m.store, slot, &k) != CMS_OK || cms_kfstore_set_bow(m.store, slot, (int)n, ids.data(), vals.data()) != CMS_OK ||
+        cms_kfdb_add(m.store, 1, &slot, &group) != CMS_OK)
+      throw std::runtime_error(std::string("KeyFrameDatabase::add failed: ") + cms_last_error());
+  }
+  m.host.add(1, &slot, &group);
+  m.slot_of[pKF] = slot; m.kf_of[(size_t)slot] = pKF;
+}
+void KeyFrameDatabase::erase(KeyFrameView* pKF) {
+  Impl& m = *impl_;
+  auto it = m.slot_of.find(pKF);
+  if (it == m.slot_of.end()) return;
+  const int slot = it->second;
+  m.host.erase(1, &slot);
+  if (m.store && cms_kfdb_erase(m.store, 1, &slot) != CMS_OK) throw std::runtime_error(std::string("cms_kfdb_erase failed: ") + cms_last_error());
+  m.kf_of[(size_t)slot] = nullptr;
+  m.slot_of.erase(it);
+}
+void KeyFrameDatabase::clear() {
+  Impl& m = *impl_;
+  m.host.clear(-1);
+  if (m.store && cms_kfdb_clear(m.store, -1) != CMS_OK) throw std::runtime_error(std::string("cms_kfdb_clear failed: ") + cms_last_error());
+  m.slot_of.clear();
+  std::fill(m.kf_of.begin(), m.kf_of.end(), nullptr);
+}
+void KeyFrameDatabase::SetBestCovisibilityKeyFrames(KeyFrameView* pKF, const std::vector<KeyFrameView*>& best) {
+  Impl& m = *impl_;
+  auto it = m.slot_of.find(pKF);
+  if (it == m.slot_of.end()) throw std::runtime_error("KeyFrameDatabase::SetBestCovisibilityKeyFrames: the key frame is not in the database");
+  int neigh[CMS_KFDB_COVIS];
+  std::fill(neigh, neigh + CMS_KFDB_COVIS, -1);
+  int n = 0;
+  for (KeyFrameView* b : best) {      // (a covisible outside the database contributes nothing: it keeps no place)
+    auto jt = m.slot_of.find(b);
+    if (n < CMS_KFDB_COVIS && jt != m.slot_of.end()) neigh[n++] = jt->second;
+  }
+  const int slot = it->second;
+  m.host.set_covisibles(1, &slot, neigh);
+  if (m.store && cms_kfdb_set_covisibles(m.store, 1, &slot, neigh) != CMS_OK) throw std::runtime_error(std::string("cms_kfdb_set_covisibles failed: ") + cms_last_error());
+}
+std::vector<KeyFrameView*> KeyFrameDatabase::DetectRelocalizationCandidates(FrameView* F) {
+  return impl_->detect(engine, CMS_KFDB_RELOC, F->mBowVec, 0.0f, std::vector<KeyFrameView*>());
+}
+std::vector<KeyFrameView*> KeyFrameDatabase::DetectLoopCandidates(KeyFrameView* pKF, float minScore, const std::vector<KeyFrameView*>& connected) {
+  return impl_->detect(engine, CMS_KFDB_LOOP, pKF->mBowVec, minScore, connected);
 }
 
 }  // namespace CubemapSLAM

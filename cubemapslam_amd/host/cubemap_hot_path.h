@@ -327,6 +327,33 @@ struct KeyFrameView {
   std::vector<MapPointView> mvMapPoints;
 };
 struct NewMapPoint { int neighbour; int idx1, idx2; cv::Vec3f x3D; };
+// KeyFrameDatabase under the reference's names (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cpp) on KeyFrameView handles.  Two engines like the
+// vocabulary's: DEVICE (the default) keeps the key frames in a cms_kfstore on the shared context's device with the BowVectors the views carry
+// (cms_kfstore_put, cms_kfstore_set_bow, cms_kfdb_add) and answers with cms_kfdb_detect; HOST_CORE is the host build of csrc/cms_kfdb_core.h, the
+// definition of record, no GPU needed.  Choose the engine before the first add: each engine answers from the key frames it was given.  The view has no
+// covisibility graph, so SetBestCovisibilityKeyFrames hands over what pKF->GetBestCovisibilityKeyFrames(10) returns, and DetectLoopCandidates takes
+// pKF->GetConnectedKeyFrames() as an argument.  A vocabulary whose scoring is not L1 throws std::runtime_error, as ORBVocabulary::score does; so does a
+// key frame beyond max_keyframes or with more words or features than max_features.
+class KeyFrameDatabase {
+ public:
+  enum Engine { DEVICE = 0, HOST_CORE = 1 };
+  explicit KeyFrameDatabase(const ORBVocabulary& voc, int max_keyframes = 256, int max_features = 2048);
+  ~KeyFrameDatabase();
+  KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+  KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+  void add(KeyFrameView* pKF);             // :45-51 (pKF->mBowVec must be computed)
+  void erase(KeyFrameView* pKF);           // :53-72
+  void clear();                            // :74-78
+  void SetBestCovisibilityKeyFrames(KeyFrameView* pKF, const std::vector<KeyFrameView*>& best);
+  std::vector<KeyFrameView*> DetectRelocalizationCandidates(FrameView* F);                                                    // :204-314
+  std::vector<KeyFrameView*> DetectLoopCandidates(KeyFrameView* pKF, float minScore, const std::vector<KeyFrameView*>& connected);   // :81-202
+  Engine engine = DEVICE;
+
+ private:
+  struct Impl;
+  Impl* impl_;
+};
+
 
 class LocalMapping {
  public:

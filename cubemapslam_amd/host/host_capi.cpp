@@ -5,6 +5,7 @@
 #include "cubemap_hot_path.h"
 #include "io_formats.h"
 #include "../csrc/cms_vocab_core.h"
+#include "../csrc/cms_kfdb_core.h"
 using namespace CubemapSLAM;
 
 static thread_local std::string g_err;
@@ -634,5 +635,123 @@ extern "C" int hm_vocab_descend(void* voc, int n, const uint8_t* desc, int level
       cms_vocab_descend(view, f, levelsup, &word[i], &nid[i], &leaf);
       weight[i] = view.word_weight[word[i]];
     }
+    return 0;)
+}
+
+// ---- KeyFrameDatabase (tests/kfdb_hostlib.py): the host build of csrc/cms_kfdb_core.h, the definition of record of cms_kfdb_detect.  The calls mirror
+// the C-ABI's (cms_kfstore_set_bow, cms_kfdb_*) on a handle of its own; they return 0, -1 (CMS_ERR_ARG, nothing changed) or -4 (CMS_ERR_OVERFLOW).
+extern "C" int hm_kfdb_create(void** out, int max_keyframes, int max_features) {
+  HM_TRY(
+    if (!out || max_keyframes < 1 || max_features < 1) throw std::runtime_error("hm_kfdb_create: bad argument");
+    *out = new CmsKfdbHost(max_keyframes, max_features);
+    return 0;)
+}
+extern "C" void hm_kfdb_destroy(void* db) { delete static_cast<CmsKfdbHost*>(db); }
+extern "C" int hm_kfdb_set_bow(void* db, int slot, int nwords, const int* word_id, const double* word_val) {
+  CmsKfdbHost* d = static_cast<CmsKfdbHost*>(db);
+  if (d->slot_ok(slot) && d->slots[(size_t)slot].in_db) return -1;
+  return d->set_bow(slot, nwords, word_id, word_val);
+}
+// what cms_kfstore_put* does to the slot's BowVector and its database entry
+extern "C" int hm_kfdb_refill(void* db, int slot) {
+  CmsKfdbHost* d = static_cast<CmsKfdbHost*>(db);
+  if (!d->slot_ok(slot)) return -1;
+  d->refill(slot);
+  return 0;
+}
+extern "C" int hm_kfdb_add(void* db, int n, const int* slots, const int* groups) { return static_cast<CmsKfdbHost*>(db)->add(n, slots, groups); }
+extern "C" int hm_kfdb_erase(void* db, int n, const int* slots) { return static_cast<CmsKfdbHost*>(db)->erase(n, slots); }
+extern "C" int hm_kfdb_clear(void* db, int group) { static_cast<CmsKfdbHost*>(db)->clear(group); return 0; }
+extern "C" int hm_kfdb_set_covisibles(void* db, int n, const int* slots, const int* neigh) { return static_cast<CmsKfdbHost*>(db)->set_covisibles(n, slots, neigh); }
+// cms_kfdb_detect's arguments; a job names a slot (CMS_KFDB_QUERY_SLOT) or carries its words (CMS_KFDB_QUERY_WORDS): there are no frame rows here
+extern "C" int hm_kfdb_detect(void* db, int njobs, const cms_kfdb_job* jobs, int cand_cap, int* cand_slot, int* n_cand, int* diag_common, float* diag_score) {
+  HM_TRY(
+    CmsKfdbHost* d = static_cast<CmsKfdbHost*>(db);
+    const size_t K = d->slots.size();
+    for (int j = 0; j < njobs; ++j) {
+      const cms_kfdb_job& q = jobs[j];
+      if ((q.mode != CMS_KFDB_RELOC && q.mode != CMS_KFDB_LOOP) || q.group < 0) return -1;
+      if (q.query == CMS_KFDB_QUERY_SLOT) { if (!d->slot_ok(q.slot) || !d->slots[(size_t)q.slot].has_bow) return -1; }
+      else if (q.query == CMS_KFDB_QUERY_WORDS) { if (q.nwords < 0 || !cms_kfdb_bow_ok(q.nwords, q.word_id)) return -1; }
+      else return -1;
+      if (q.mode == CMS_KFDB_LOOP)
+        for (int i = 0; i < q.n_connected; ++i) if (!d->slot_ok(q.connected[i])) return -1;
+    }
+    bool overflow = false;
+    for (int j = 0; j < njobs; ++j) {
+      const cms_kfdb_job& q = jobs[j];
+      CmsKfdbQuery hq;
+      hq.mode = q.mode; hq.group = q.group; hq.min_score = q.min_score; hq.n_connected = q.mode == CMS_KFDB_LOOP ? q.n_connected : 0; hq.connected = q.connected;
+      hq.bow = q.query == CMS_KFDB_QUERY_SLOT ? d->bow(q.slot) : CmsKfdbBow{q.nwords, q.word_id, q.word_val};
+      std::vector<int> cand;
+      d->detect(hq, &cand, diag_common ? diag_common + (size_t)j * K : nullptr, diag_score ? diag_score + (size_t)j * K : nullptr);
+      n_cand[j] = (int)cand.size();
+      if ((int)cand.size() > cand_cap) overflow = true;
+      for (int i = 0; i < std::min((int)cand.size(), cand_cap); ++i) cand_slot[(size_t)j * cand_cap + i] = cand[(size_t)i];
+    }
+    return overflow ? -4 : 0;)
+}
+extern "C" int hm_kfdb_bow_score(void* db, int npairs, const int* slot_a, const int* slot_b, double* score) {
+  CmsKfdbHost* d = static_cast<CmsKfdbHost*>(db);
+  for (int i = 0; i < npairs; ++i)
+    if (!d->slot_ok(slot_a[i]) || !d->slot_ok(slot_b[i]) || !d->slots[(size_t)slot_a[i]].has_bow || !d->slots[(size_t)slot_b[i]].has_bow) return -1;
+  for (int i = 0; i < npairs; ++i) score[i] = cms_kfdb_score_host(d->bow(slot_a[i]), d->bow(slot_b[i]));
+  return 0;
+}
+// the core's score of two BowVectors (against ORBVocabulary::score: hm_vocab_score)
+extern "C" int hm_kfdb_score(int n1, const int* id1, const double* val1, int n2, const int* id2, const double* val2, double* out) {
+  *out = cms_kfdb_score_host(CmsKfdbBow{n1, id1, val1}, CmsKfdbBow{n2, id2, val2});
+  return 0;
+}
+
+// ORB_SLAM2::KeyFrameDatabase of the mirror through the named engine (0 = device, 1 = host core): n_kf key frames of n_feat descriptors each enter in
+// order (their BoW from the vocabulary's host core, levelsup 1), covis holds n_kf x 10 key-frame indices (-1 padded); then one
+// DetectRelocalizationCandidates for a frame of nq descriptors and one DetectLoopCandidates for key frame loop_query.  The candidates come back as
+// key-frame indices (arrays of n_kf).
+extern "C" int hm_kfdb_mirror(void* voc, int engine, int n_kf, int n_feat, const uint8_t* descs, const int* covis, int nq, const uint8_t* qdesc, int loop_query,
+                              float min_score, int n_conn, const int* conn, int* reloc, int* n_reloc, int* loop, int* n_loop) {
+  HM_TRY(
+    ORBVocabulary* v = static_cast<ORBVocabulary*>(voc);
+    v->engine = ORBVocabulary::HOST_CORE;
+    std::vector<KeyFrameView> kfs((size_t)n_kf);
+    KeyFrameDatabase db(*v, n_kf + 1, 2048);
+    db.engine = engine ? KeyFrameDatabase::HOST_CORE : KeyFrameDatabase::DEVICE;
+    auto index_of = [&](KeyFrameView* k) { return (int)(k - kfs.data()); };
+    for (int i = 0; i < n_kf; ++i) {
+      KeyFrameView& k = kfs[(size_t)i];
+      k.mnId = i;
+      k.mDescriptors = cv::Mat(n_feat, 32, cv::CV_8U, const_cast<uint8_t*>(descs) + 32 * (size_t)i * n_feat, 32);
+      k.mvKeys.resize((size_t)n_feat);
+      for (int f = 0; f < n_feat; ++f) { k.mvKeys[(size_t)f].pt.x = 10.f + (float)(f % 100); k.mvKeys[(size_t)f].pt.y = 10.f + (float)(f / 100); }
+      cv::Vec3f ray;
+      ray.v[0] = 0.f; ray.v[1] = 0.f; ray.v[2] = 1.f;
+      k.mvKeyRays.assign((size_t)n_feat, ray);
+      k.mvpMapPoints.assign((size_t)n_feat, -1);
+      k.Tcw = cv::Mat::zeros(4, 4, cv::CV_32F);
+      for (int r = 0; r < 4; ++r) k.Tcw.at<float>(r, r) = 1.f;
+      v->transform(std::vector<cv::Mat>(), k.mBowVec, k.mFeatVec, 1);
+      std::vector<cv::Mat> rows((size_t)n_feat);
+      for (int f = 0; f < n_feat; ++f) rows[(size_t)f] = k.mDescriptors.row(f);
+      v->transform(rows, k.mBowVec, k.mFeatVec, 1);
+      db.add(&k);
+    }
+    for (int i = 0; i < n_kf; ++i) {
+      std::vector<KeyFrameView*> best;
+      for (int c = 0; c < 10; ++c) if (covis[i * 10 + c] >= 0) best.push_back(&kfs[(size_t)covis[i * 10 + c]]);
+      db.SetBestCovisibilityKeyFrames(&kfs[(size_t)i], best);
+    }
+    FrameView F;
+    std::vector<cv::Mat> rows((size_t)nq);
+    cv::Mat Q(std::max(nq, 1), 32, cv::CV_8U, const_cast<uint8_t*>(qdesc), 32);
+    for (int f = 0; f < nq; ++f) rows[(size_t)f] = Q.row(f);
+    v->transform(rows, F.mBowVec, F.mFeatVec, 1);
+    const std::vector<KeyFrameView*> r = db.DetectRelocalizationCandidates(&F);
+    *n_reloc = (int)r.size();
+    for (size_t i = 0; i < r.size(); ++i) reloc[i] = index_of(r[i]);
+    std::vector<KeyFrameView*> connected;
+    for (int i = 0; i < n_conn; ++i) connected.push_back(&kfs[(size_t)conn[i]]);
+    const std::vector<KeyFrameView*> l = db.DetectLoopCandidates(&kfs[(size_t)loop_query], min_score, connected);
+    *n_loop = (int)l.size();
+    for (size_t i = 0; i < l.size(); ++i) loop[i] = index_of(l[i]);
     return 0;)
 }

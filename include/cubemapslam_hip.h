@@ -561,6 +561,63 @@ int cms_kfstore_fetch_bow(cms_kfstore* st, int slot, int* nwords, int* word_id, 
 int cms_kfstore_search_by_bow_frames(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_job* jobs, float nnratio, int check_orientation,
                                      int* kf_idx, int* n_matches);
 
+/* ---- KeyFrameDatabase (src/KeyFrameDatabase.cpp) over the resident key frames of a store: DetectRelocalizationCandidates (:204-314; Tracking.cpp:997)
+ * and DetectLoopCandidates (:81-202; LoopClosing.cpp:140) on the device, between cms_frames_compute_bow and cms_kfstore_search_by_bow_frames, so that
+ * Relocalization's chain never fetches a BowVector.  The numeric definition is csrc/cms_kfdb_core.h (one source for the host build and the kernels);
+ * candidates, common-word counts and scores are bit-equal to the host build's.  Scoring is L1 (ScoringObject.cpp:23-68), the reference's; there is no
+ * other.
+ *
+ * An entry is a slot with a BowVector, a group >= 0 (one per map or camera stream: a query sees its own group only), its add order, a persistent
+ * reloc_score (KeyFrame::mRelocScore; 0.0f from add on, where the reference reads an uninitialised float) and up to 10 covisible slots.
+ * lKFsSharingWords is ordered by (smallest common word id, add order) -- the order in which the reference meets the key frames in its inverted
+ * file -- and the candidates come back as a subsequence of it.  Several jobs of one call are evaluated as if one after the other in job order.
+ *
+ * Threading: cms_kfdb_add / erase / clear / set_covisibles touch a host table under the database's mutex and enqueue nothing; the mapping thread may
+ * call them while the frame thread is in cms_kfdb_detect, which takes its snapshot under the same mutex.  Calls of cms_kfdb_detect on one store
+ * are serialised. */
+/* cms_kfstore_set_bow: the BowVector the host computed for the key frame in `slot` (KeyFrame::mBowVec; cms_kfstore_compute_bow gives a slot its own).
+ * Ids >= 0 and strictly ascending, at most max_features entries, the slot filled and not in the database: otherwise CMS_ERR_ARG and the slot is
+ * unchanged.  On the store's stream, synchronous. */
+int cms_kfstore_set_bow(cms_kfstore* st, int slot, int nwords, const int* word_id, const double* word_val);
+/* KeyFrameDatabase::add (:45-51; LoopClosing.cpp:115, :145, :214), erase (:53-72; KeyFrame.cpp:569) and clear (:74-78; Tracking.cpp:1176; group -1:
+ * every group).  add of a slot without a BowVector, in the database already or named twice is CMS_ERR_ARG and adds none; erase of a slot that is not
+ * in it does nothing, as in the reference; erase + add moves an entry to the back of the add order and zeroes its reloc_score.  A slot that is
+ * refilled (cms_kfstore_put / put_from_frame(s)) leaves the database and loses its covisibles: both belonged to the key frame it held. */
+int cms_kfdb_add(cms_kfstore* st, int n, const int* slots, const int* groups);
+int cms_kfdb_erase(cms_kfstore* st, int n, const int* slots);
+int cms_kfdb_clear(cms_kfstore* st, int group);
+/* pKF->GetBestCovisibilityKeyFrames(10) (:156, :270) per named slot as slots: neigh holds n x 10, best first, padded with -1.  A covisible that is not
+ * in the database, or not in the query's group, contributes nothing. */
+int cms_kfdb_set_covisibles(cms_kfstore* st, int n, const int* slots, const int* neigh);
+#define CMS_KFDB_RELOC 0
+#define CMS_KFDB_LOOP 1
+#define CMS_KFDB_QUERY_ROW 0     /* row b of src's last batch, its resident BowVector (cms_frames_compute_bow) */
+#define CMS_KFDB_QUERY_SLOT 1    /* the BowVector of a store slot (DetectLoopCandidates' pKF) */
+#define CMS_KFDB_QUERY_WORDS 2   /* nwords / word_id / word_val from the host: ids >= 0, strictly ascending, at most 16383 */
+typedef struct cms_kfdb_job {
+  int mode, group, query;
+  int b, slot;
+  int nwords; const int* word_id; const double* word_val;
+  float min_score; int n_connected; const int* connected;      /* LOOP: minScore and the slots of pKF->GetConnectedKeyFrames() (:83) */
+} cms_kfdb_job;
+/* One upload, one launch sequence on src's stream -- the frame thread's, under the rules of cms_kfstore_search_by_bow: nothing is enqueued on the
+ * store's stream -- one copy back, one wait.  cand_slot receives njobs x cand_cap slots, n_cand[j] is always delivered; a job with more candidates than
+ * cand_cap makes the call CMS_ERR_OVERFLOW (the first cand_cap are delivered).  diag_common / diag_score may be NULL; otherwise njobs x max_keyframes
+ * each: common words per slot, and `float si` with -1 where the slot was not scored.  RELOC: every scored entry's reloc_score is overwritten; a
+ * covisible that shares a word with the query adds its reloc_score (:278-286) -- the one an EARLIER query left if it fell under this query's
+ * threshold.  LOOP: connected slots never enter the list; an entry below min_score is left out but still adds to a neighbour's sum (:164-171);
+ * bestAccScore starts at min_score.  CMS_ERR_ARG: a row without a computed BoW, an empty slot or one without a BowVector, unsorted words, a store on
+ * another device than src.  More than 16384 key frames in the database is CMS_ERR_UNSUPPORTED. */
+int cms_kfdb_detect(cms_kfstore* st, cms_ctx* src, int njobs, const cms_kfdb_job* jobs, int cand_cap, int* cand_slot, int* n_cand, int* diag_common,
+                    float* diag_score);
+/* The score() loop of LoopClosing::DetectLoop (LoopClosing.cpp:125-138): score[i] = mpORBVocabulary->score(BowVec of slot_a[i], BowVec of slot_b[i]), the
+ * same ordered sum as a double.  On the store's stream, synchronous. */
+int cms_kfstore_bow_score(cms_kfstore* st, int npairs, const int* slot_a, const int* slot_b, double* score);
+/* Developer aid (tools/prof_kfdb.py), one thread at a time: while on, every cms_kfdb_detect records events around its launch sequence; after the call
+ * cms_kfdb_profile_get gives its milliseconds. */
+int cms_kfdb_profile_enable(int on);
+int cms_kfdb_profile_get(float* ms);
+
 /* ---- ORBMatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, const float th, const int ORBdist)
  * (include/ORBMatcher.h:64, src/ORBMatcher.cpp:253-378), the guided search of Tracking::Relocalization: twice per accepted PnP pose
  * (src/Tracking.cpp:1101 with th 10 / ORBdist 100, :1115 with th 3 / ORBdist 64), between the PoseOptimization calls (cms_pose_*) and behind the candidate

@@ -275,6 +275,10 @@ std::mutex g_books_mutex;
 StoreBook& book(cms_kfstore* st) { std::lock_guard<std::mutex> lk(g_books_mutex); return g_books[st]; }
 int slot_locked(StoreBook& b, KeyFrame* k) { const auto it = b.slot.find(k); return it == b.slot.end() ? -1 : it->second; }      // b.mu held
 int slot_of(StoreBook& b, KeyFrame* k) { std::lock_guard<std::mutex> lk(b.mu); return slot_locked(b, k); }
+struct DbBook { std::set<KeyFrame*> in_db; std::mutex mu; };      // which resident key frames are in the store's KeyFrameDatabase (Hip::AddToDatabase)
+std::map<cms_kfstore*, DbBook> g_db_books;
+std::mutex g_db_books_mutex;
+DbBook& db_book(cms_kfstore* st) { std::lock_guard<std::mutex> lk(g_db_books_mutex); return g_db_books[st]; }
 void pose_floats(KeyFrame* k, float* R9, float* t3, float* O3) {
   const cv::Mat R = k->GetRotation(), t = k->GetTranslation(), O = k->GetCameraCenter();
   for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) R9[3 * r + c] = R.at<float>(r, c); t3[r] = t.at<float>(r); O3[r] = O.at<float>(r); }
@@ -332,6 +336,11 @@ void ReleaseKeyFrame(cms_kfstore* store, KeyFrame* pKF) {
   std::lock_guard<std::mutex> lk(b.mu);
   const auto it = b.slot.find(pKF);
   if (it == b.slot.end()) return;
+  {      // a key frame that leaves the store leaves its database
+    DbBook& d = db_book(store);
+    std::lock_guard<std::mutex> lk2(d.mu);
+    if (d.in_db.erase(pKF)) check(cms_kfdb_erase(store, 1, &it->second), "cms_kfdb_erase");
+  }
   b.free_slots.push_back(it->second);
   b.slot.erase(it);
 }
@@ -849,6 +858,102 @@ void ComputeBoW(cms_vocab* vocab, cms_kfstore* store, KeyFrame* pKF) {
   check(cms_kfstore_fetch_bow(store, slot, &nwords, wid.data(), wval.data(), (int)cap, &nnodes, nid.data(), noff.data(), nfeat.data(), (int)cap, (int)cap),
         "cms_kfstore_fetch_bow");
   fill_vectors(nwords, wid, wval, nnodes, nid, noff, nfeat, pKF->mBowVec, &pKF->mFeatVec);
+}
+
+// ------------------------------------------------------------------------------------------------ KeyFrameDatabase
+namespace {
+
+// one cms_kfdb_detect job; the covisibles of every database key frame are refreshed first (the reference reads them at the call, :156, :270)
+std::vector<KeyFrame*> detect_candidates(cms_kfstore* store, cms_ctx* frameCtx, cms_kfdb_job& job) {
+  StoreBook& b = book(store);
+  DbBook& d = db_book(store);
+  std::lock_guard<std::mutex> lk(b.mu);      // no slot of the database is refilled or released while the call runs
+  std::lock_guard<std::mutex> lk2(d.mu);
+  std::map<int, KeyFrame*> kf_of;
+  std::vector<int> slots, neigh;
+  for (KeyFrame* k : d.in_db) {
+    const int s = slot_locked(b, k);
+    if (s < 0) continue;
+    kf_of[s] = k;
+    slots.push_back(s);
+    int row[10] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1}, n = 0;
+    for (KeyFrame* c : k->GetBestCovisibilityKeyFrames(10)) {      // (one that is not in the database contributes nothing: it keeps no place)
+      const int cs = slot_locked(b, c);
+      if (cs >= 0 && d.in_db.count(c) && n < 10) row[n++] = cs;
+    }
+    neigh.insert(neigh.end(), row, row + 10);
+  }
+  if (slots.empty()) return std::vector<KeyFrame*>();
+  check(cms_kfdb_set_covisibles(store, (int)slots.size(), slots.data(), neigh.data()), "cms_kfdb_set_covisibles");
+  std::vector<int> cand(slots.size());
+  int n_cand = 0;
+  check(cms_kfdb_detect(store, frameCtx, 1, &job, (int)cand.size(), cand.data(), &n_cand, NULL, NULL), "cms_kfdb_detect");
+  std::vector<KeyFrame*> out;
+  for (int i = 0; i < n_cand; ++i) out.push_back(kf_of[cand[i]]);
+  return out;
+}
+}  // namespace
+
+void AddToDatabase(cms_kfstore* store, KeyFrame* pKF) {
+  StoreBook& b = book(store);
+  DbBook& d = db_book(store);
+  std::lock_guard<std::mutex> lk(b.mu);
+  const int slot = slot_locked(b, pKF);
+  if (slot < 0) throw std::runtime_error("Hip::AddToDatabase: the key frame is not resident (Hip::ProcessNewKeyFrame first)");
+  std::vector<int> ids;
+  std::vector<double> vals;
+  for (DBoW2::BowVector::const_iterator it = pKF->mBowVec.begin(); it != pKF->mBowVec.end(); ++it) { ids.push_back((int)it->first); vals.push_back(it->second); }
+  check(cms_kfstore_set_bow(store, slot, (int)ids.size(), ids.data(), vals.data()), "cms_kfstore_set_bow");
+  const int group = 0;
+  check(cms_kfdb_add(store, 1, &slot, &group), "cms_kfdb_add");
+  std::lock_guard<std::mutex> lk2(d.mu);
+  d.in_db.insert(pKF);
+}
+void EraseFromDatabase(cms_kfstore* store, KeyFrame* pKF) {
+  StoreBook& b = book(store);
+  DbBook& d = db_book(store);
+  std::lock_guard<std::mutex> lk(b.mu);
+  std::lock_guard<std::mutex> lk2(d.mu);
+  if (!d.in_db.erase(pKF)) return;      // KeyFrameDatabase::erase of a key frame that is not in it does nothing
+  const int slot = slot_locked(b, pKF);
+  if (slot >= 0) check(cms_kfdb_erase(store, 1, &slot), "cms_kfdb_erase");
+}
+void ClearDatabase(cms_kfstore* store) {
+  DbBook& d = db_book(store);
+  std::lock_guard<std::mutex> lk(d.mu);
+  check(cms_kfdb_clear(store, -1), "cms_kfdb_clear");
+  d.in_db.clear();
+}
+std::vector<KeyFrame*> DetectRelocalizationCandidates(cms_kfstore* store, cms_ctx* frameCtx, Frame& F) {
+  cms_kfdb_job job = cms_kfdb_job();
+  job.mode = CMS_KFDB_RELOC; job.group = 0; job.query = CMS_KFDB_QUERY_ROW; job.b = 0;
+  return detect_candidates(store, frameCtx, job);
+}
+std::vector<KeyFrame*> DetectLoopCandidates(cms_kfstore* store, cms_ctx* frameCtx, KeyFrame* pKF, float minScore) {
+  StoreBook& b = book(store);
+  const int slot = slot_of(b, pKF);
+  if (slot < 0) throw std::runtime_error("Hip::DetectLoopCandidates: the key frame is not resident (Hip::ProcessNewKeyFrame first)");
+  std::vector<int> connected;
+  for (KeyFrame* c : pKF->GetConnectedKeyFrames()) { const int cs = slot_of(b, c); if (cs >= 0) connected.push_back(cs); }
+  cms_kfdb_job job = cms_kfdb_job();
+  job.mode = CMS_KFDB_LOOP; job.group = 0; job.query = CMS_KFDB_QUERY_SLOT; job.slot = slot;
+  job.min_score = minScore; job.n_connected = (int)connected.size(); job.connected = connected.empty() ? NULL : connected.data();
+  return detect_candidates(store, frameCtx, job);
+}
+std::vector<double> LoopScore(cms_kfstore* store, KeyFrame* pKF, const std::vector<KeyFrame*>& vpOthers) {
+  StoreBook& b = book(store);
+  std::lock_guard<std::mutex> lk(b.mu);
+  const int slot = slot_locked(b, pKF);
+  if (slot < 0) throw std::runtime_error("Hip::LoopScore: the key frame is not resident");
+  std::vector<int> a, o;
+  for (KeyFrame* k : vpOthers) {
+    const int s = slot_locked(b, k);
+    if (s < 0) throw std::runtime_error("Hip::LoopScore: a key frame is not resident");
+    a.push_back(slot); o.push_back(s);
+  }
+  std::vector<double> score(a.size());
+  if (!a.empty()) check(cms_kfstore_bow_score(store, (int)a.size(), a.data(), o.data(), score.data()), "cms_kfstore_bow_score");
+  return score;
 }
 
 }  // namespace Hip

@@ -149,5 +149,21 @@ cms_init* CreateInitializer(int maxJobs, int maxMatches, int maxKeys1, int maxHy
 cms_vocab* CreateVocabulary(const ORBVocabulary& voc, const std::string& scratchPrefix = "cms_vocabulary_upload");
 void ComputeBoW(cms_vocab* vocab, cms_ctx* frameCtx, Frame& F);
 void ComputeBoW(cms_vocab* vocab, cms_kfstore* store, KeyFrame* pKF);
+// ---- KeyFrameDatabase (src/KeyFrameDatabase.cpp) over the key frames resident in `store`: the database is the store's (cms_kfdb_*), so
+// Tracking::Relocalization goes from Hip::ComputeBoW to Hip::SearchByBoWCandidates without fetching a BowVector.  AddToDatabase / EraseFromDatabase /
+// ClearDatabase stand where the reference calls mpKeyFrameDB->add (LoopClosing.cpp:115, :145, :214), ->erase (KeyFrame.cpp:569) and ->clear
+// (Tracking.cpp:1176); a key frame enters with pKF->mBowVec (as Hip::ComputeBoW or the host's ComputeBoW left it) and must be resident
+// (Hip::ProcessNewKeyFrame).  Hip::ReleaseKeyFrame of a key frame that is still in the database erases it first.
+// DetectRelocalizationCandidates (:204-314; Tracking.cpp:997): F is the frame `frameCtx` extracted last, after Hip::ComputeBoW(vocab, frameCtx, F) -- the
+// query is the row's resident BowVector.  DetectLoopCandidates (:81-202; LoopClosing.cpp:140): pKF must be resident; its connected key frames are
+// taken from pKF->GetConnectedKeyFrames().  Both hand the device every database key frame's GetBestCovisibilityKeyFrames(10) as it is at the call,
+// run on frameCtx's stream (cms_kfdb_detect) and return the candidates in the reference's order.  LoopScore is the score() loop of
+// LoopClosing::DetectLoop (:125-138) for pKF against its covisibles, on the store's stream.
+void AddToDatabase(cms_kfstore* store, KeyFrame* pKF);
+void EraseFromDatabase(cms_kfstore* store, KeyFrame* pKF);
+void ClearDatabase(cms_kfstore* store);
+std::vector<KeyFrame*> DetectRelocalizationCandidates(cms_kfstore* store, cms_ctx* frameCtx, Frame& F);
+std::vector<KeyFrame*> DetectLoopCandidates(cms_kfstore* store, cms_ctx* frameCtx, KeyFrame* pKF, float minScore);
+std::vector<double> LoopScore(cms_kfstore* store, KeyFrame* pKF, const std::vector<KeyFrame*>& vpOthers);
 }  // namespace Hip
 #endif

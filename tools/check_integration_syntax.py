@@ -39,7 +39,8 @@ def main(ref_inc):
         for i, (fname, old, new) in enumerate((("OrbExtractorHip.h", "cms_extract(ctx,", "cms_extrakt(ctx,"), ("CubemapHipBridge.cpp", "cms_area_grid(ctx, 1)", "cms_area_grid(ctx)"),
                                                ("CubemapHipBridge.cpp", "cms_kfstore_fuse_search_sets(store, 2, set_off,", "cms_kfstore_fuse_search_sets(store, set_off,"),
                                                ("CubemapHipBridge.cpp", "cms_pnp_iterate_frames(pnp, frameCtx, (int)n, jobs.data())", "cms_pnp_iterate_frame(pnp, frameCtx, (int)n, jobs.data())"),
-                                               ("CubemapHipBridge.cpp", "cms_init_two_view_frames(init, frameCtx, 1, &q)", "cms_init_two_view_frame(init, frameCtx, 1, &q)"))):
+                                               ("CubemapHipBridge.cpp", "cms_init_two_view_frames(init, frameCtx, 1, &q)", "cms_init_two_view_frame(init, frameCtx, 1, &q)"),
+                                               ("CubemapHipBridge.cpp", "cms_kfdb_detect(store, frameCtx, 1, &job,", "cms_kfdb_detect(store, 1, &job,"))):
             d = os.path.join(td, "broken_%d" % i)
             shutil.copytree(os.path.join(ROOT, "integration"), d)
             src = open(os.path.join(d, fname)).read()
