@@ -1534,6 +1534,110 @@ class PnPSolver:
         return pnp_results(arr, states)
 
 
+class Sim3Job(C.Structure):
+    """cms_sim3_job (include/cubemapslam_hip.h)"""
+    _fields_ = [("N", C.c_int), ("x3dc1", C.c_void_p), ("x3dc2", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p), ("fix_scale", C.c_int),
+                ("min_inliers", C.c_int), ("max_its", C.c_int), ("n_iterations", C.c_int), ("n_draws", C.c_int), ("draws", C.c_void_p), ("iterations", C.c_int),
+                ("best_inliers", C.c_int), ("best_R", C.c_float * 9), ("best_t", C.c_float * 3), ("best_s", C.c_float), ("best_T12", C.c_float * 12),
+                ("best_mask", C.c_void_p), ("status", C.c_int), ("no_more", C.c_int), ("n_inliers", C.c_int), ("iterations_run", C.c_int), ("T12", C.c_float * 12),
+                ("inliers", C.c_void_p)]
+
+
+def sim3_ransac_parameters(N, probability=0.99, min_inliers=6, max_iterations=300):
+    """cms_sim3_ransac_parameters: Sim3Solver::SetRansacParameters -> max_its"""
+    it = C.c_int()
+    L = lib()
+    L.cms_sim3_ransac_parameters.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]
+    _chk(L.cms_sim3_ransac_parameters(int(N), float(probability), int(min_inliers), int(max_iterations), C.byref(it)), "cms_sim3_ransac_parameters")
+    return it.value
+
+
+_SIM3_BEST = (("best_R", 9), ("best_t", 3), ("best_T12", 12))
+
+
+def sim3_job_state(prob, n_iterations, draws):
+    """The arrays of one Sim3Solver as a dict a Sim3Job points into: prob has x3dc1, x3dc2 (N x 3), max_err1, max_err2 (N), min_inliers, max_its,
+    optionally fix_scale and the state carried from an earlier call (iterations, best_inliers, best_R, best_t, best_s, best_T12, best_mask).
+    draws: 3 ints per iteration."""
+    N = len(prob["x3dc1"])
+    f32 = lambda a, shape: np.ascontiguousarray(np.asarray(a, np.float32).reshape(shape))
+    s = dict(N=N, x3dc1=f32(prob["x3dc1"], (N, 3)), x3dc2=f32(prob["x3dc2"], (N, 3)), max_err1=f32(prob["max_err1"], (N,)), max_err2=f32(prob["max_err2"], (N,)),
+             draws=np.ascontiguousarray(np.asarray(draws, np.int32).ravel()), fix_scale=int(prob.get("fix_scale", 0)), min_inliers=int(prob["min_inliers"]),
+             max_its=int(prob["max_its"]), n_iterations=int(n_iterations), iterations=int(prob.get("iterations", 0)), best_inliers=int(prob.get("best_inliers", 0)),
+             best_s=np.array([prob.get("best_s", 0.0)], np.float32),
+             best_mask=np.array(prob.get("best_mask", np.zeros(N)), np.uint8).ravel().copy(), inliers=np.zeros(max(N, 1), np.uint8))
+    for k, n in _SIM3_BEST:
+        s[k] = np.array(prob.get(k, np.zeros(n)), np.float32).ravel().copy()
+    if len(s["best_mask"]) == 0:
+        s["best_mask"] = np.zeros(1, np.uint8)
+    return s
+
+
+def sim3_jobs(states):
+    """(Sim3Job * n) over sim3_job_state() dicts; the dicts own the memory"""
+    arr = (Sim3Job * len(states))()
+    for q, s in zip(arr, states):
+        q.N = s["N"]; q.x3dc1 = _p(s["x3dc1"]); q.x3dc2 = _p(s["x3dc2"]); q.max_err1 = _p(s["max_err1"]); q.max_err2 = _p(s["max_err2"])
+        q.fix_scale = s["fix_scale"]; q.min_inliers = s["min_inliers"]; q.max_its = s["max_its"]; q.n_iterations = s["n_iterations"]
+        q.n_draws = len(s["draws"]); q.draws = _p(s["draws"]) if len(s["draws"]) else None
+        q.iterations = s["iterations"]; q.best_inliers = s["best_inliers"]; q.best_mask = _p(s["best_mask"]); q.inliers = _p(s["inliers"])
+        for k, n in _SIM3_BEST:      # by bytes: a carried NaN keeps its bits
+            C.memmove(getattr(q, k), _p(s[k]), 4 * n)
+        C.memmove(C.byref(q, Sim3Job.best_s.offset), _p(s["best_s"]), 4)
+    return arr
+
+
+def sim3_results(arr, states):
+    """What a call left in the job records, one dict per job (arrays copied)"""
+    out = []
+    for q, s in zip(arr, states):
+        N = s["N"]
+        r = dict(status=q.status, no_more=q.no_more, n_inliers=q.n_inliers, iterations=q.iterations, iterations_run=q.iterations_run,
+                 best_inliers=q.best_inliers, T12=np.frombuffer(bytes(q.T12), np.float32).copy(),
+                 best_s=np.frombuffer(C.string_at(C.addressof(q) + Sim3Job.best_s.offset, 4), np.float32).copy(),
+                 inliers=s["inliers"][:N].copy(), best_mask=s["best_mask"][:N].copy())
+        for k, _ in _SIM3_BEST:
+            r[k] = np.frombuffer(bytes(getattr(q, k)), np.float32).copy()
+        out.append(r)
+    return out
+
+
+sim3_first_difference = pnp_first_difference      # result dicts compared bit for bit: None, or (job, key, wanted, got)
+
+
+class Sim3Solver:
+    """Sim3Solver::iterate for many solvers in one launch sequence (cms_sim3_*).  jobs: a (Sim3Job * n) array, e.g. from sim3_jobs()."""
+
+    def __init__(self, max_jobs, max_corr_total, max_hyp_total, device=0):
+        self.h = C.c_void_p()
+        L = lib()
+        L.cms_sim3_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.cms_sim3_destroy.argtypes = [C.c_void_p]
+        L.cms_sim3_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _chk(L.cms_sim3_create(C.byref(self.h), device, max_jobs, max_corr_total, max_hyp_total), "cms_sim3_create")
+
+    def close(self):
+        if self.h:
+            lib().cms_sim3_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def iterate(self, ctx, jobs):
+        _chk(lib().cms_sim3_iterate(self.h, ctx.h, len(jobs), jobs), "cms_sim3_iterate")
+        return jobs
+
+    def run(self, ctx, states):
+        """One call over sim3_job_state() dicts -> one result dict per job (the states' in/out arrays are updated in place)"""
+        arr = sim3_jobs(states)
+        self.iterate(ctx, arr)
+        return sim3_results(arr, states)
+
+
 class InitJob(C.Structure):
     """cms_init_job (include/cubemapslam_hip.h)"""
     _fields_ = [("n1", C.c_int), ("n2", C.c_int), ("keys1", C.c_void_p), ("rays1", C.c_void_p), ("keys2", C.c_void_p), ("rays2", C.c_void_p),

@@ -12,6 +12,7 @@
 #include <map>
 #include "../csrc/cms_vocab_core.h"
 #include "../csrc/cms_kfdb_core.h"
+#include "../csrc/cms_sim3_core.h"      // the gemm rule (cms_sim3_row) and TransformRaysToCubemap for the constructor's filter
 
 namespace CubemapSLAM {
 
@@ -822,6 +823,112 @@ cv::Mat PnPsolver::iterate(int nIterations, bool& bNoMore, std::vector<bool>& vb
     for (int c = 0; c < 4; ++c) Tcw.at<float>(r, c) = r < 3 ? (c < 3 ? q.Tcw[3 * r + c] : q.Tcw[9 + r]) : (c == 3 ? 1.0f : 0.0f);
   return Tcw;
 }
+
+// ------------------------------------------------------------------------------------------------ Sim3Solver (src/Sim3Solver.cpp)
+extern "C" int hm_sim3_iterate_host(int F, int njobs, cms_sim3_job* jobs);      // sim3_host.cpp: the host build of csrc/cms_sim3_core.h
+
+Sim3Solver::Sim3Solver(const Sim3KeyFrameView& pKF1, const Sim3KeyFrameView& pKF2, const std::vector<int>& vpMatched12, const bool bFixScale) : mbFixScale(bFixScale) {
+  const std::vector<int>& vpKeyFrameMP1 = pKF1.mvpMapPointMatches;
+  mN1 = (int)vpMatched12.size();
+  const int F = CamModelGeneral::GetCamera()->GetCubeFaceWidth();
+  for (int i1 = 0; i1 < mN1; i1++) {      // :66-127
+    if (vpMatched12[i1] < 0) continue;
+    if (i1 >= (int)vpKeyFrameMP1.size() || vpKeyFrameMP1[i1] < 0) continue;      // !pMP1
+    const Sim3MapPointView& pMP1 = pKF1.mvMapPoints[(size_t)vpKeyFrameMP1[i1]];
+    const Sim3MapPointView& pMP2 = pKF2.mvMapPoints[(size_t)vpMatched12[i1]];
+    if (pMP1.mbBad || pMP2.mbBad) continue;
+    const int indexKF1 = pMP1.mnIndexInKeyFrame, indexKF2 = pMP2.mnIndexInKeyFrame;
+    if (indexKF1 < 0 || indexKF2 < 0) continue;
+    cv::Vec3f X3D1c, X3D2c;
+    float u, v;
+    for (int r = 0; r < 3; ++r) X3D1c(r) = cms_sim3_row(pKF1.Rcw + 3 * r, pMP1.mWorldPos(0), pMP1.mWorldPos(1), pMP1.mWorldPos(2), pKF1.tcw[r]);
+    track_rays_to_cubemap(F, X3D1c(0), X3D1c(1), X3D1c(2), u, v);
+    if (u < 0 || v < 0) continue;
+    for (int r = 0; r < 3; ++r) X3D2c(r) = cms_sim3_row(pKF2.Rcw + 3 * r, pMP2.mWorldPos(0), pMP2.mWorldPos(1), pMP2.mWorldPos(2), pKF2.tcw[r]);
+    track_rays_to_cubemap(F, X3D2c(0), X3D2c(1), X3D2c(2), u, v);
+    if (u < 0 || v < 0) continue;
+    mvX3Dc1.push_back(X3D1c);
+    mvX3Dc2.push_back(X3D2c);
+    const float sigmaSquare1 = pKF1.mvLevelSigma2[(size_t)pKF1.mvKeyOctaves[(size_t)indexKF1]];
+    const float sigmaSquare2 = pKF2.mvLevelSigma2[(size_t)pKF2.mvKeyOctaves[(size_t)indexKF2]];
+    mvnMaxError1.push_back(9.210 * sigmaSquare1);
+    mvnMaxError2.push_back(9.210 * sigmaSquare2);
+    mvnIndices1.push_back((size_t)i1);
+  }
+  draw = [](int min, int max) { const int d = max - min + 1; return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min; };
+  SetRansacParameters();
+}
+
+void Sim3Solver::SetRansacParameters(double probability, int minInliers, int maxIterations) {
+  mRansacProb = probability;
+  mRansacMinInliers = minInliers;
+  N = (int)mvX3Dc1.size();
+  if (cms_sim3_ransac_parameters(N, probability, minInliers, maxIterations, &mRansacMaxIts))
+    throw std::runtime_error(std::string("cms_sim3_ransac_parameters: ") + cms_last_error());
+  mnIterations = 0;
+  mvbBestInliers.resize((size_t)N + 1, 0);
+}
+
+cv::Mat Sim3Solver::find(std::vector<bool>& vbInliers12, int& nInliers) {
+  bool bFlag;
+  return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers);
+}
+
+cv::Mat Sim3Solver::iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+  bNoMore = false; vbInliers = std::vector<bool>((size_t)mN1, false); nInliers = 0;
+  if (N < mRansacMinInliers) { bNoMore = true; return cv::Mat(); }      // :170-174
+  if (mRansacMinInliers < 3) throw std::runtime_error("Sim3Solver::iterate: minInliers below the three pairs of a hypothesis");
+  const int H = std::max(std::max(mRansacMaxIts - mnIterations, nIterations), 0);
+  std::vector<int> draws((size_t)H * 3);
+  for (int i = 0; i < H; ++i)
+    for (int k = 0; k < 3; ++k) draws[(size_t)i * 3 + k] = draw(0, N - k - 1);      // RandomInt(0, vAvailableIndices.size()-1), :192
+  std::vector<uint8_t> inliers((size_t)N + 1, 0);
+  cms_sim3_job q = {};
+  q.N = N; q.x3dc1 = N ? &mvX3Dc1[0](0) : nullptr; q.x3dc2 = N ? &mvX3Dc2[0](0) : nullptr; q.max_err1 = mvnMaxError1.data(); q.max_err2 = mvnMaxError2.data();
+  q.fix_scale = mbFixScale ? 1 : 0; q.min_inliers = mRansacMinInliers; q.max_its = mRansacMaxIts; q.n_iterations = nIterations;
+  q.n_draws = (int)draws.size(); q.draws = draws.data();
+  q.iterations = mnIterations; q.best_inliers = mnBestInliers; q.best_mask = mvbBestInliers.data(); q.inliers = inliers.data();
+  std::memcpy(q.best_R, mBestRotation, sizeof(mBestRotation)); std::memcpy(q.best_t, mBestTranslation, sizeof(mBestTranslation));
+  std::memcpy(&q.best_s, &mBestScale, sizeof(float)); std::memcpy(q.best_T12, mBestT12, sizeof(mBestT12));
+  if (engine == HOST_CORE) {
+    const int rc = hm_sim3_iterate_host(CamModelGeneral::GetCamera()->GetCubeFaceWidth(), 1, &q);
+    if (rc) throw std::runtime_error("Sim3Solver::iterate: the job was refused (" + std::to_string(rc) + ")");
+  } else {
+    cms_ctx* ctx = SharedContext(g_ctx_orb.nfeatures > 0 ? g_ctx_orb.nfeatures : 1000, g_ctx_orb.nfeatures > 0 ? g_ctx_orb.scale_factor : 1.2f,
+                                 g_ctx_orb.nfeatures > 0 ? g_ctx_orb.nlevels : 8, g_ctx_orb.nfeatures > 0 ? g_ctx_orb.ini_th_fast : 20,
+                                 g_ctx_orb.nfeatures > 0 ? g_ctx_orb.min_th_fast : 7);
+    cms_sim3* h = nullptr;
+    if (cms_sim3_create(&h, 0, 1, std::max(N, 1), std::max(H, 1))) throw std::runtime_error(std::string("cms_sim3_create: ") + cms_last_error());
+    const int rc = cms_sim3_iterate(h, ctx, 1, &q);
+    cms_sim3_destroy(h);
+    if (rc) throw std::runtime_error(std::string("cms_sim3_iterate: ") + cms_last_error());
+  }
+  mnIterations = q.iterations; mnBestInliers = q.best_inliers;
+  std::memcpy(mBestRotation, q.best_R, sizeof(mBestRotation)); std::memcpy(mBestTranslation, q.best_t, sizeof(mBestTranslation));
+  std::memcpy(&mBestScale, &q.best_s, sizeof(float)); std::memcpy(mBestT12, q.best_T12, sizeof(mBestT12));
+  bNoMore = q.no_more != 0;
+  if (q.status == 0) return cv::Mat();
+  nInliers = q.n_inliers;
+  for (int i = 0; i < N; i++)      // :219-221
+    if (inliers[(size_t)i]) vbInliers[mvnIndices1[(size_t)i]] = true;
+  cv::Mat T12(4, 4, cv::CV_32F);
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 4; ++c) T12.at<float>(r, c) = r < 3 ? q.T12[4 * r + c] : (c == 3 ? 1.0f : 0.0f);
+  return T12;
+}
+
+cv::Mat Sim3Solver::GetEstimatedRotation() {
+  cv::Mat R(3, 3, cv::CV_32F);
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) R.at<float>(r, c) = mBestRotation[3 * r + c];
+  return R;
+}
+cv::Mat Sim3Solver::GetEstimatedTranslation() {
+  cv::Mat t(3, 1, cv::CV_32F);
+  for (int r = 0; r < 3; ++r) t.at<float>(r, 0) = mBestTranslation[r];
+  return t;
+}
+float Sim3Solver::GetEstimatedScale() { return mBestScale; }
 
 // ------------------------------------------------------------------------------------------------ Initializer (src/Initializer.cpp)
 extern "C" int hm_init_two_view_host(int F, float cos_fov, int njobs, cms_init_job* jobs);      // init_host.cpp: the host build of csrc/cms_init_core.h

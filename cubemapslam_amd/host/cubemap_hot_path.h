@@ -245,6 +245,52 @@ class PnPsolver {
   size_t nMatches_ = 0;      // mvpMapPointMatches.size(): the length of vbInliers
 };
 
+// What Sim3Solver's constructor (src/Sim3Solver.cpp:41-136) reads of a key frame and of its map points: GetRotation / GetTranslation, mvKeys[i].octave,
+// mvLevelSigma2, GetMapPointMatches() (key frame 1 only) and per map point GetWorldPos(), isBad() and GetIndexInKeyFrame(this key frame).
+struct Sim3MapPointView {
+  cv::Vec3f mWorldPos;
+  bool mbBad = false;
+  int mnIndexInKeyFrame = -1;
+};
+struct Sim3KeyFrameView {
+  float Rcw[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tcw[3] = {0, 0, 0};
+  std::vector<int> mvKeyOctaves;               // mvKeys[i].octave
+  std::vector<float> mvLevelSigma2;
+  std::vector<Sim3MapPointView> mvMapPoints;   // the map points this key frame's side of the matches refers to
+  std::vector<int> mvpMapPointMatches;         // per key point: index into mvMapPoints, -1 = none (GetMapPointMatches)
+};
+
+// Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cpp) under the reference's names, for LoopClosing::ComputeSim3 (LoopClosing.cpp:270-330): the
+// constructor's filtering and order (:66-127; vpMatched12[i1] = index into pKF2.mvMapPoints of the map point matched to key point i1 of pKF1, -1 = none),
+// Rcw Xw + tcw per point, mvnMaxError = 9.210 * sigma2, SetRansacParameters with the header's defaults, iterate / find returning the 4 x 4 CV_32F
+// mBestT12 or an empty cv::Mat, vbInliers expanded through mvnIndices1 to size mN1, GetEstimatedRotation / Translation / Scale.  iterate() makes the
+// call's draws first -- three per iteration, for max(mRansacMaxIts - mnIterations, nIterations) iterations -- through the replaceable `draw`
+// (default: DUtils::Random::RandomInt), then runs the loop in one cms_sim3_iterate call on the shared context's device (engine DEVICE, the default) or
+// through the host build of the same core (engine HOST_CORE: the definition of record, no GPU needed; an explicit choice, never a fall-back).  The
+// contract is the reference's loop on the same draws, not the same rand() consumption.
+class Sim3Solver {
+ public:
+  enum Engine { DEVICE = 0, HOST_CORE = 1 };
+  Sim3Solver(const Sim3KeyFrameView& pKF1, const Sim3KeyFrameView& pKF2, const std::vector<int>& vpMatched12, const bool bFixScale = true);
+  void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300);
+  cv::Mat find(std::vector<bool>& vbInliers12, int& nInliers);
+  cv::Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers);
+  cv::Mat GetEstimatedRotation();
+  cv::Mat GetEstimatedTranslation();
+  float GetEstimatedScale();
+  std::function<int(int, int)> draw;      // RandomInt(min, max)
+  Engine engine = DEVICE;
+  // the reference's members, for callers and tests that look at them
+  std::vector<cv::Vec3f> mvX3Dc1, mvX3Dc2;
+  std::vector<float> mvnMaxError1, mvnMaxError2;
+  std::vector<size_t> mvnIndices1;
+  int N = 0, mN1 = 0, mnIterations = 0, mnBestInliers = 0, mRansacMinInliers = 0, mRansacMaxIts = 0;
+  double mRansacProb = 0;
+  bool mbFixScale = true;
+  std::vector<uint8_t> mvbBestInliers;
+  float mBestRotation[9] = {0}, mBestTranslation[3] = {0}, mBestScale = 0, mBestT12[12] = {0};
+};
+
 // Initializer (include/Initializer.h, src/Initializer.cpp) under the reference's names, for Tracking::MonocularInitialization (Tracking.cpp:409, :443): the
 // constructor keeps the reference frame's key points and key rays, InitializeWithRays filters vMatches12 into mvMatches12 (:61-73), makes the
 // 8 * mMaxIterations draws through the replaceable `draw` and resolves them into mvSets by swap-and-pop (:92-107), then runs FindEssential and

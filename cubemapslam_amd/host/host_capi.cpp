@@ -495,6 +495,57 @@ extern "C" int hm_pnp_mirror(int engine, int n, const cms_keypoint* kps, const f
     return 0;)
 }
 
+// Sim3Solver through the mirror.  Per key frame k = 1, 2: Tcw (3 x 4: Rcw | tcw), sigma2 (nlevels), octave (nk key points), pos (np map points x 3), bad
+// and index_in_kf (np).  mp1[nk1] = GetMapPointMatches() of key frame 1 as indices into its map points, matched12[n1] = indices into key frame 2's.
+// draws: the values the replaceable draw function hands out in order (it must not run dry).  Outputs: idx1[N] = mvnIndices1 (N through *N_out),
+// x12[N x 6] = mvX3Dc1 | mvX3Dc2, vb[n1] = vbInliers, T16 (zeros when empty), Rts[13] = GetEstimatedRotation | Translation | Scale, state[6] =
+// bNoMore, nInliers, mnIterations, found, draws used, mRansacMaxIts; returns 0, or -1 with hm_last_error().
+extern "C" int hm_sim3_mirror(int engine, int n1, int nk1, int nk2, int nlevels, int np1, int np2, const float* Tcw1, const float* sigma2_1, const int* octave1,
+                              const float* pos1, const uint8_t* bad1, const int* index1, const float* Tcw2, const float* sigma2_2, const int* octave2, const float* pos2,
+                              const uint8_t* bad2, const int* index2, const int* mp1, const int* matched12, int fix_scale, double probability, int minInliers,
+                              int maxIterations, int calls, const int* nIterations, int n_draws, const int* draws, int* N_out, int* idx1, float* x12, uint8_t* vb,
+                              float* T16, float* Rts, int* state) {
+  HM_TRY(
+    auto fill = [&](Sim3KeyFrameView& k, int nk, int np, const float* Tcw, const float* sigma2, const int* octave, const float* pos, const uint8_t* bad, const int* index) {
+      for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) k.Rcw[3 * r + c] = Tcw[4 * r + c]; k.tcw[r] = Tcw[4 * r + 3]; }
+      k.mvLevelSigma2.assign(sigma2, sigma2 + nlevels);
+      k.mvKeyOctaves.assign(octave, octave + nk);
+      k.mvMapPoints.resize(np);
+      for (int i = 0; i < np; ++i) {
+        for (int c = 0; c < 3; ++c) k.mvMapPoints[i].mWorldPos(c) = pos[3 * (size_t)i + c];
+        k.mvMapPoints[i].mbBad = bad[i] != 0; k.mvMapPoints[i].mnIndexInKeyFrame = index[i];
+      }
+    };
+    Sim3KeyFrameView k1; Sim3KeyFrameView k2;
+    fill(k1, nk1, np1, Tcw1, sigma2_1, octave1, pos1, bad1, index1);
+    fill(k2, nk2, np2, Tcw2, sigma2_2, octave2, pos2, bad2, index2);
+    k1.mvpMapPointMatches.assign(mp1, mp1 + nk1);
+    Sim3Solver solver(k1, k2, std::vector<int>(matched12, matched12 + n1), fix_scale != 0);
+    solver.engine = engine ? Sim3Solver::HOST_CORE : Sim3Solver::DEVICE;
+    solver.SetRansacParameters(probability, minInliers, maxIterations);
+    int next = 0;
+    solver.draw = [&](int lo, int hi) { if (next >= n_draws) throw std::runtime_error("hm_sim3_mirror: out of draws"); const int v = draws[next++]; if (v < lo || v > hi) throw std::runtime_error("hm_sim3_mirror: draw out of range"); return v; };
+    *N_out = solver.N;
+    for (int i = 0; i < solver.N; ++i) {
+      idx1[i] = (int)solver.mvnIndices1[i];
+      for (int c = 0; c < 3; ++c) { x12[6 * (size_t)i + c] = solver.mvX3Dc1[i](c); x12[6 * (size_t)i + 3 + c] = solver.mvX3Dc2[i](c); }
+    }
+    std::vector<bool> vbInliers; int nInliers = 0; bool bNoMore = false; cv::Mat T;
+    for (int c = 0; c < calls; ++c) {
+      T = solver.iterate(nIterations[c], bNoMore, vbInliers, nInliers);
+      if (!T.empty() || bNoMore) break;
+    }
+    std::memset(vb, 0, n1);
+    for (size_t i = 0; i < vbInliers.size(); ++i) vb[i] = vbInliers[i] ? 1 : 0;
+    std::memset(T16, 0, 64);
+    if (!T.empty()) for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = T.at<float>(r, c);
+    cv::Mat R = solver.GetEstimatedRotation(); cv::Mat t = solver.GetEstimatedTranslation();
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) Rts[3 * r + c] = R.at<float>(r, c); Rts[9 + r] = t.at<float>(r, 0); }
+    Rts[12] = solver.GetEstimatedScale();
+    state[0] = bNoMore; state[1] = nInliers; state[2] = solver.mnIterations; state[3] = T.empty() ? 0 : 1; state[4] = next; state[5] = solver.mRansacMaxIts;
+    return 0;)
+}
+
 // Initializer through the mirror: the reference frame (n1 key points, rays) and the current frame (n2), vMatches12 (n1).  draws: the values the
 // replaceable draw function hands out in order (it must not run dry; n_draws < 0 keeps the class's default draw).  vP3D / vbTriangulated go in holding the caller's pattern, so that "left as they
 // were" shows.  Outputs: R21 (9, zeros when empty), t21 (3), p3d (3 per entry of vP3D), tri, sets[8 * iterations] = mvSets, state[0..11] = found, draws

@@ -711,6 +711,49 @@ typedef struct {
 int cms_pnp_iterate(cms_pnp* p, cms_ctx* ctx /* F */, int njobs, cms_pnp_job* jobs);
 int cms_pnp_iterate_frames(cms_pnp* p, cms_ctx* ctx, int njobs, cms_pnp_job* jobs);
 
+/* ---- Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cpp), the Horn RANSAC of LoopClosing::ComputeSim3 (src/LoopClosing.cpp:287-345), behind
+ * cms_kfdb_detect.  cv::eigen and cv::Rodrigues are not in the tree and libm's atan2 / sin / cos differ from the device's in ulps (DESIGN.md
+ * "Sim3Solver"), so the definition of record is the project's own core, csrc/cms_sim3_core.h: one source, built for the host
+ * (libcubemapslam_host.so: hm_sim3_iterate_host) and for the device, which is held to the host build bit for bit.
+ * cms_sim3_ransac_parameters: SetRansacParameters (:138-162): epsilon = (float)minInliers / N, nIterations = 1 if minInliers == N else
+ *   ceil(log(1-p)/log(1-pow(epsilon,3))) in double (a value no int holds -- NaN, or inf for N = 0 -- converts as x86 does, to INT_MIN),
+ *   max_its = max(1, min(nIterations, maxIterations)).  Host only.
+ * cms_sim3_iterate: Sim3Solver::iterate (:164-231) with ComputeSim3 (:250-361) and CheckInliers (:364-394) for njobs solvers -- one loop candidate
+ *   each -- as ONE launch sequence on the handle's stream: one pinned block up, one wavefront per hypothesis (the Horn solve on the three drawn
+ *   pairs, then the two-way inlier test over the correspondences), one wavefront per job replaying the loop in order (best on >=, accepted on
+ *   > min_inliers), one block back.  Synchronous.  ctx supplies the face size F and the device; nothing is enqueued on its stream.
+ *   x3dc1 / x3dc2 are mvX3Dc1 / mvX3Dc2: the matched map points in the frames of key frame 1 and 2, in the constructor's order (:66-127), both
+ *   projecting into a face; max_err1 / max_err2 are mvnMaxError1 / 2 = (float)(9.210 * sigma2).  mvP1im1 / mvP2im2 are computed inside the call.
+ *   The loop is `while (mnIterations < max_its && nCurrentIterations < n_iterations)`, so a call evaluates at most
+ *   min(max_its - iterations, n_iterations) hypotheses.  The caller makes the draws beforehand, three per iteration: draws[3*i + k] = the k-th
+ *   DUtils::Random::RandomInt(0, size - 1) of iteration i, so 0 <= draws[3*i+k] <= N-1-k.  The call asks for 3*H of them with
+ *   H = max(max_its - iterations, n_iterations) if N >= min_inliers, else 0, and checks all of them; draws behind the last iteration run are discarded.
+ *   status: 1 = a hypothesis with more than min_inliers inliers that is the best so far (T12 = mBestT12, rows 0..2 of the 4 x 4 [sR | t] row
+ *   major; inliers = its mask; n_inliers), 0 = empty cv::Mat (T12 and inliers zeroed).  no_more = bNoMore.  iterations_run = nCurrentIterations.
+ *   iterations / best_inliers / best_R / best_t / best_s / best_T12 / best_mask carry mnIterations / mnBestInliers / mBestRotation /
+ *   mBestTranslation / mBestScale / mBestT12 / mvbBestInliers from call to call; a new solver starts with zeros.  N < min_inliers gives no_more
+ *   and touches nothing else.  inliers / best_mask are per correspondence; the caller expands them through mvnIndices1.
+ *   Checked before anything is enqueued (CMS_ERR_ARG, the records untouched): a draw out of range, n_draws < 3*H, a total of jobs /
+ *   correspondences / hypotheses above what cms_sim3_create was given, best_mask not consistent with best_inliers, min_inliers < 3,
+ *   max_its or n_iterations outside [0, 2^20], a null array.  One caller at a time per handle. */
+int cms_sim3_ransac_parameters(int N, double probability, int minInliers, int maxIterations, int* max_its);
+typedef struct cms_sim3 cms_sim3;
+int cms_sim3_create(cms_sim3** out, int device, int max_jobs, int max_corr_total, int max_hyp_total);
+void cms_sim3_destroy(cms_sim3* p);
+typedef struct {
+  int N;                      /* correspondences (Sim3Solver ctor order) */
+  const float* x3dc1;         /* N x 3  mvX3Dc1 */
+  const float* x3dc2;         /* N x 3  mvX3Dc2 */
+  const float* max_err1;      /* N      mvnMaxError1 */
+  const float* max_err2;      /* N      mvnMaxError2 */
+  int fix_scale, min_inliers, max_its;
+  int n_iterations;           /* iterate()'s argument */
+  int n_draws; const int* draws;   /* successive DUtils::Random::RandomInt(0, size-1) values, three per iteration */
+  int iterations, best_inliers; float best_R[9], best_t[3], best_s, best_T12[12]; uint8_t* best_mask;   /* in/out */
+  int status, no_more, n_inliers, iterations_run; float T12[12]; uint8_t* inliers;   /* out; inliers: N bytes, by correspondence */
+} cms_sim3_job;
+int cms_sim3_iterate(cms_sim3* p, cms_ctx* ctx /* F */, int njobs, cms_sim3_job* jobs);
+
 /* ---- Initializer (include/Initializer.h, src/Initializer.cpp), the two-view essential-matrix RANSAC of Tracking::MonocularInitialization
  * (src/Tracking.cpp:443), behind cms_search_for_initialization.  ComputeE21 takes the last row of a FULL_UV SVD of an 8 x 9 matrix, which OpenCV
  * completes from a basis nobody can pin (DESIGN.md "Initializer"), so the definition of record is the project's own core, csrc/cms_init_core.h: one

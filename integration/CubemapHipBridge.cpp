@@ -703,6 +703,122 @@ void IteratePnP(cms_pnp* pnp, cms_ctx* frameCtx, const std::vector<PnPsolver*>& 
   }
 }
 
+// ---- Sim3Solver (src/Sim3Solver.cpp)
+Sim3Solver::Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatched12, const bool bFixScale)
+    : N(0), mN1((int)vpMatched12.size()), mnIterations(0), mnBestInliers(0), mRansacMinInliers(0), mRansacMaxIts(0), mbFixScale(bFixScale), mBestScale(0) {
+  std::memset(mBestRotation, 0, sizeof(mBestRotation)); std::memset(mBestTranslation, 0, sizeof(mBestTranslation)); std::memset(mBestT12, 0, sizeof(mBestT12));
+  const std::vector<MapPoint*> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+  const cv::Mat Rcw1 = pKF1->GetRotation(), tcw1 = pKF1->GetTranslation(), Rcw2 = pKF2->GetRotation(), tcw2 = pKF2->GetTranslation();
+  for (int i1 = 0; i1 < mN1; i1++) {      // :66-127
+    if (!vpMatched12[i1]) continue;
+    MapPoint* pMP1 = vpKeyFrameMP1[i1];
+    MapPoint* pMP2 = vpMatched12[i1];
+    if (!pMP1) continue;
+    if (pMP1->isBad() || pMP2->isBad()) continue;
+    const int indexKF1 = pMP1->GetIndexInKeyFrame(pKF1), indexKF2 = pMP2->GetIndexInKeyFrame(pKF2);
+    if (indexKF1 < 0 || indexKF2 < 0) continue;
+    const cv::KeyPoint& kp1 = pKF1->mvKeys[indexKF1];
+    const cv::KeyPoint& kp2 = pKF2->mvKeys[indexKF2];
+    float u, v;
+    const cv::Mat X3D1c = Rcw1 * pMP1->GetWorldPos() + tcw1;
+    CamModelGeneral::GetCamera()->TransformRaysToCubemap(u, v, X3D1c.at<float>(0), X3D1c.at<float>(1), X3D1c.at<float>(2));
+    if (u < 0 || v < 0) continue;
+    const cv::Mat X3D2c = Rcw2 * pMP2->GetWorldPos() + tcw2;
+    CamModelGeneral::GetCamera()->TransformRaysToCubemap(u, v, X3D2c.at<float>(0), X3D2c.at<float>(1), X3D2c.at<float>(2));
+    if (u < 0 || v < 0) continue;
+    for (int c = 0; c < 3; ++c) { mvX3Dc1.push_back(X3D1c.at<float>(c)); mvX3Dc2.push_back(X3D2c.at<float>(c)); }
+    mvnMaxError1.push_back(9.210 * pKF1->mvLevelSigma2[kp1.octave]);
+    mvnMaxError2.push_back(9.210 * pKF2->mvLevelSigma2[kp2.octave]);
+    mvnIndices1.push_back(i1);
+  }
+  SetRansacParameters();
+}
+
+void Sim3Solver::SetRansacParameters(double probability, int minInliers, int maxIterations) {
+  N = (int)mvnIndices1.size();
+  mRansacMinInliers = minInliers;
+  check(cms_sim3_ransac_parameters(N, probability, minInliers, maxIterations, &mRansacMaxIts), "cms_sim3_ransac_parameters");
+  mnIterations = 0;
+  mvbBestInliers.resize((size_t)N + 1, 0);
+  mvbInliers.assign((size_t)N + 1, 0);
+}
+
+void Sim3Solver::FillJob(cms_sim3_job& q, int nIterations) {
+  std::memset(&q, 0, sizeof(q));
+  int H = 0;
+  if (N >= mRansacMinInliers) H = std::max(std::max(mRansacMaxIts - mnIterations, nIterations), 0);      // what cms_sim3_iterate asks for
+  mvDraws.resize((size_t)H * 3);
+  for (int i = 0; i < H; ++i)
+    for (int k = 0; k < 3; ++k) mvDraws[(size_t)i * 3 + k] = DUtils::Random::RandomInt(0, N - k - 1);      // :192
+  q.N = N; q.x3dc1 = mvX3Dc1.data(); q.x3dc2 = mvX3Dc2.data(); q.max_err1 = mvnMaxError1.data(); q.max_err2 = mvnMaxError2.data();
+  q.fix_scale = mbFixScale ? 1 : 0; q.min_inliers = mRansacMinInliers; q.max_its = mRansacMaxIts; q.n_iterations = nIterations;
+  q.n_draws = (int)mvDraws.size(); q.draws = mvDraws.data();
+  q.iterations = mnIterations; q.best_inliers = mnBestInliers; q.best_mask = mvbBestInliers.data(); q.inliers = mvbInliers.data();
+  std::memcpy(q.best_R, mBestRotation, sizeof(mBestRotation)); std::memcpy(q.best_t, mBestTranslation, sizeof(mBestTranslation));
+  q.best_s = mBestScale; std::memcpy(q.best_T12, mBestT12, sizeof(mBestT12));
+}
+
+cv::Mat Sim3Solver::TakeResult(const cms_sim3_job& q, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+  mnIterations = q.iterations; mnBestInliers = q.best_inliers;
+  std::memcpy(mBestRotation, q.best_R, sizeof(mBestRotation)); std::memcpy(mBestTranslation, q.best_t, sizeof(mBestTranslation));
+  mBestScale = q.best_s; std::memcpy(mBestT12, q.best_T12, sizeof(mBestT12));
+  bNoMore = q.no_more != 0; vbInliers = std::vector<bool>((size_t)mN1, false); nInliers = 0;      // :166-168
+  if (q.status == 0) return cv::Mat();
+  nInliers = q.n_inliers;
+  for (int i = 0; i < N; i++)      // :219-221
+    if (mvbInliers[(size_t)i]) vbInliers[(size_t)mvnIndices1[(size_t)i]] = true;
+  cv::Mat T12 = cv::Mat::eye(4, 4, CV_32F);
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) T12.at<float>(r, c) = q.T12[4 * r + c];
+  return T12;
+}
+
+cv::Mat Sim3Solver::iterate(cms_sim3* sim3, cms_ctx* frameCtx, int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+  cms_sim3_job q;
+  FillJob(q, nIterations);
+  check(cms_sim3_iterate(sim3, frameCtx, 1, &q), "cms_sim3_iterate");
+  return TakeResult(q, bNoMore, vbInliers, nInliers);
+}
+
+cv::Mat Sim3Solver::find(cms_sim3* sim3, cms_ctx* frameCtx, std::vector<bool>& vbInliers12, int& nInliers) {
+  bool bFlag;
+  return iterate(sim3, frameCtx, mRansacMaxIts, bFlag, vbInliers12, nInliers);
+}
+
+cv::Mat Sim3Solver::GetEstimatedRotation() {
+  cv::Mat R(3, 3, CV_32F);
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) R.at<float>(r, c) = mBestRotation[3 * r + c];
+  return R;
+}
+cv::Mat Sim3Solver::GetEstimatedTranslation() {
+  cv::Mat t(3, 1, CV_32F);
+  for (int r = 0; r < 3; ++r) t.at<float>(r) = mBestTranslation[r];
+  return t;
+}
+float Sim3Solver::GetEstimatedScale() { return mBestScale; }
+
+cms_sim3* CreateSim3(int maxSolvers, int maxCorrespondences, int maxHypotheses) {
+  cms_sim3* sim3 = nullptr;
+  check(cms_sim3_create(&sim3, g_device, maxSolvers, maxCorrespondences, maxHypotheses), "cms_sim3_create");
+  return sim3;
+}
+
+void IterateSim3(cms_sim3* sim3, cms_ctx* frameCtx, const std::vector<Sim3Solver*>& vpSolvers, int nIterations, std::vector<cv::Mat>& vScm, std::vector<bool>& vbNoMore,
+                 std::vector<std::vector<bool> >& vvbInliers, std::vector<int>& vnInliers) {
+  const size_t n = vpSolvers.size();
+  vScm.assign(n, cv::Mat()); vbNoMore.assign(n, false); vvbInliers.assign(n, std::vector<bool>()); vnInliers.assign(n, 0);
+  if (n == 0) return;
+  std::vector<cms_sim3_job> jobs(n);
+  for (size_t i = 0; i < n; ++i) vpSolvers[i]->FillJob(jobs[i], nIterations);      // the candidates' draws in the candidates' order, as the reference's loop makes them
+  check(cms_sim3_iterate(sim3, frameCtx, (int)n, jobs.data()), "cms_sim3_iterate");
+  for (size_t i = 0; i < n; ++i) {
+    bool bNoMore = false;
+    vScm[i] = vpSolvers[i]->TakeResult(jobs[i], bNoMore, vvbInliers[i], vnInliers[i]);
+    vbNoMore[i] = bNoMore;
+  }
+}
+
 // ---- Initializer (src/Initializer.cpp)
 Initializer::Initializer(const Frame& ReferenceFrame, float sigma, int iterations) : mSigma(sigma), mMaxIterations(iterations) {
   const size_t n1 = ReferenceFrame.mvKeys.size();

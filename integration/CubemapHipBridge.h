@@ -113,6 +113,42 @@ cms_pnp* CreatePnP(int maxSolvers, int maxCorrespondences, int maxHypotheses);
 // vpSolvers[i]->iterate(nIterations, bNoMore, vbInliers, nInliers) returns (an empty cv::Mat when there is no pose yet).
 void IteratePnP(cms_pnp* pnp, cms_ctx* frameCtx, const std::vector<PnPsolver*>& vpSolvers, int nIterations, std::vector<cv::Mat>& vTcw,
                 std::vector<bool>& vbNoMore, std::vector<std::vector<bool> >& vvbInliers, std::vector<int>& vnInliers);
+// ---- Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cpp) with the reference's surface, for LoopClosing::ComputeSim3 (LoopClosing.cpp:273-345).  The
+// constructor filters and orders as :66-127 does (with the reference's own cv::Mat arithmetic for Rcw Xw + tcw and its TransformRaysToCubemap);
+// iterate() makes the call's draws with DUtils::Random::RandomInt -- three per iteration, for max(mRansacMaxIts - mnIterations, nIterations)
+// iterations -- and runs the loop on the device.  When a call ends early the draws behind the accepting iteration are discarded: the reference's loop
+// on the same draws, not the same rand() consumption.  The frame context supplies the face size and the device only.
+class Sim3Solver {
+ public:
+  Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatched12, const bool bFixScale = true);
+  void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300);
+  cv::Mat find(cms_sim3* sim3, cms_ctx* frameCtx, std::vector<bool>& vbInliers12, int& nInliers);
+  cv::Mat iterate(cms_sim3* sim3, cms_ctx* frameCtx, int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers);
+  cv::Mat GetEstimatedRotation();
+  cv::Mat GetEstimatedTranslation();
+  float GetEstimatedScale();
+
+  // what IterateSim3 needs of a solver
+  void FillJob(cms_sim3_job& q, int nIterations);      // makes the draws
+  cv::Mat TakeResult(const cms_sim3_job& q, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers);
+
+ private:
+  std::vector<float> mvX3Dc1, mvX3Dc2;       // N x 3
+  std::vector<float> mvnMaxError1, mvnMaxError2;
+  std::vector<int> mvnIndices1;
+  int N, mN1, mnIterations, mnBestInliers, mRansacMinInliers, mRansacMaxIts;
+  bool mbFixScale;
+  float mBestRotation[9], mBestTranslation[3], mBestScale, mBestT12[12];
+  std::vector<uint8_t> mvbBestInliers, mvbInliers;
+  std::vector<int> mvDraws;
+};
+cms_sim3* CreateSim3(int maxSolvers, int maxCorrespondences, int maxHypotheses);
+// One pass of LoopClosing.cpp:287-345 over the candidates that are not discarded, as ONE cms_sim3_iterate call: per solver i what
+// vpSolvers[i]->iterate(nIterations, bNoMore, vbInliers, nInliers) returns (an empty cv::Mat when there is no Sim3 yet).  The reference stops the
+// pass at the first candidate OptimizeSim3 accepts; here the later candidates' iterations of that pass have run as well, which changes nothing the
+// reference reads afterwards (the solvers are deleted).
+void IterateSim3(cms_sim3* sim3, cms_ctx* frameCtx, const std::vector<Sim3Solver*>& vpSolvers, int nIterations, std::vector<cv::Mat>& vScm,
+                 std::vector<bool>& vbNoMore, std::vector<std::vector<bool> >& vvbInliers, std::vector<int>& vnInliers);
 // ---- Initializer (include/Initializer.h, src/Initializer.cpp) with the reference's surface, for Tracking::MonocularInitialization (Tracking.cpp:409
 // constructs it from the first frame, :443 calls InitializeWithRays with mvIniMatches).  The constructor keeps mvKeys / mvKeyRays of the reference
 // frame; InitializeWithRays makes the 8 * iterations draws with DUtils::Random::RandomInt behind SeedRandOnce(0), as :90-107 does, and runs

@@ -1,0 +1,172 @@
+"""ctypes access to the host build of the Sim3 core (libcubemapslam_host.so: cubemapslam_amd/host/sim3_host.cpp) for the Sim3 tests."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from cubemapslam_amd import api
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_H = None
+p = lambda a: a.ctypes.data_as(C.c_void_p)
+
+
+class Stages(C.Structure):
+    """CmsSim3Stages (cubemapslam_amd/csrc/cms_sim3_core.h)"""
+    _fields_ = [("O1", C.c_float * 3), ("O2", C.c_float * 3), ("Pr1", C.c_float * 9), ("Pr2", C.c_float * 9), ("M", C.c_float * 9), ("N", C.c_float * 16),
+                ("evals", C.c_double * 4), ("evecs", C.c_double * 16), ("sweeps", C.c_int), ("chosen", C.c_int), ("q", C.c_float * 4), ("P3", C.c_float * 9),
+                ("nom", C.c_double), ("den", C.c_double)]
+
+
+class Motion(C.Structure):
+    """CmsSim3Motion"""
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("s", C.c_float), ("T12", C.c_float * 12), ("T21", C.c_float * 12)]
+
+
+def H():
+    global _H
+    if _H is None:
+        _H = C.CDLL(os.path.join(ROOT, "cubemapslam_amd", "lib", "libcubemapslam_host.so"))
+        _H.hm_sim3_iterate_host.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        _H.hm_sim3_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _H.hm_sim3_compute.restype = None
+        _H.hm_sim3_check_inliers.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 7
+        _H.hm_sim3_jacobi4.argtypes = [C.c_void_p, C.c_void_p]
+        _H.hm_sim3_quat_to_R.argtypes = [C.c_void_p, C.c_void_p]
+        _H.hm_sim3_resolve_draws.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        assert _H.hm_sim3_stages_size() == C.sizeof(Stages) and _H.hm_sim3_motion_size() == C.sizeof(Motion)
+    return _H
+
+
+def iterate_host(F, states):
+    """hm_sim3_iterate_host over api.sim3_job_state() dicts -> (rc, results)"""
+    arr = api.sim3_jobs(states)
+    rc = H().hm_sim3_iterate_host(F, len(states), arr)
+    return rc, (api.sim3_results(arr, states) if rc == 0 else None)
+
+
+def unpack(st, m):
+    g = lambda o, name, shape, dt: np.frombuffer(bytes(getattr(o, name)), dt).reshape(shape).copy()
+    return dict(O1=g(st, "O1", 3, np.float32), O2=g(st, "O2", 3, np.float32), Pr1=g(st, "Pr1", (3, 3), np.float32), Pr2=g(st, "Pr2", (3, 3), np.float32),
+                M=g(st, "M", (3, 3), np.float32), N=g(st, "N", (4, 4), np.float32), evals=g(st, "evals", 4, np.float64), evecs=g(st, "evecs", (4, 4), np.float64),
+                sweeps=st.sweeps, chosen=st.chosen, q=g(st, "q", 4, np.float32), P3=g(st, "P3", (3, 3), np.float32), nom=st.nom, den=st.den,
+                R=g(m, "R", (3, 3), np.float32), t=g(m, "t", 3, np.float32), s=np.float32(m.s), T12=g(m, "T12", (3, 4), np.float32), T21=g(m, "T21", (3, 4), np.float32))
+
+
+def compute(P1, P2, fix_scale=False, lib=None, name="hm_sim3_compute"):
+    """One ComputeSim3 of the core on three pairs (3 points x 3 coordinates, one point per row) -> dict of every stage"""
+    P1 = np.ascontiguousarray(P1, np.float32); P2 = np.ascontiguousarray(P2, np.float32)
+    st = Stages(); m = Motion()
+    getattr(lib or H(), name)(p(P1), p(P2), 1 if fix_scale else 0, C.byref(m), C.byref(st))
+    return unpack(st, m)
+
+
+def jacobi4(A):
+    """The core's eigen decomposition of a symmetric 4 x 4 -> (eigenvalues = the diagonal left, V with eigenvectors as columns, sweeps)"""
+    A = np.ascontiguousarray(A, np.float64).copy(); V = np.zeros((4, 4))
+    n = H().hm_sim3_jacobi4(p(A), p(V))
+    return np.diag(A).copy(), V, n
+
+
+def quat_to_R(q):
+    q = np.ascontiguousarray(q, np.float32); R = np.zeros((3, 3), np.float32)
+    H().hm_sim3_quat_to_R(p(q), p(R))
+    return R
+
+
+def resolve_draws(N, row):
+    row = np.ascontiguousarray(row, np.int32); idx = np.zeros(3, np.int32)
+    H().hm_sim3_resolve_draws(N, p(row), p(idx))
+    return list(idx)
+
+
+def check_inliers(F, T12, T21, x1, x2, me1, me2):
+    out = np.zeros(len(x1), np.uint8)
+    a = [np.ascontiguousarray(v, np.float32) for v in (T12, T21, x1, x2, me1, me2)]
+    c = H().hm_sim3_check_inliers(F, len(x1), *[p(v) for v in a], p(out))
+    assert c == int(out.sum())
+    return out.astype(bool)
+
+
+def mirror(engine, camd, kf1, kf2, matched12, fix_scale, n_iterations, draws, probability=0.99, min_inliers=20, max_iterations=300):
+    """class Sim3Solver of cubemap_hot_path.h through hm_sim3_mirror.  kf = dict(Tcw (3 x 4 float32: Rcw | tcw), sigma2 (levels), octave (per key point),
+    mp (per key point: index into pos or -1), pos (world positions), bad (per map point), index_in_kf (per map point: GetIndexInKeyFrame or -1));
+    matched12[i1] = map point of key frame 2 matched to key point i1 of key frame 1, or -1.  One iterate() per entry of n_iterations until a
+    result or bNoMore.  engine 1 = the host build of the core, 0 = the device."""
+    L = H()
+    L.hm_last_error.restype = C.c_char_p
+    assert L.hm_set_camera(C.byref(api.make_camera(camd))) == 0, L.hm_last_error()
+    n1 = len(matched12)
+    arrs = []
+    for kf in (kf1, kf2):
+        arrs += [np.ascontiguousarray(kf["Tcw"], np.float32), np.ascontiguousarray(kf["sigma2"], np.float32), np.ascontiguousarray(kf["octave"], np.int32),
+                 np.ascontiguousarray(kf["pos"], np.float32), np.ascontiguousarray(kf["bad"], np.uint8), np.ascontiguousarray(kf["index_in_kf"], np.int32)]
+    mp1 = np.ascontiguousarray(kf1["mp"], np.int32); m12 = np.ascontiguousarray(matched12, np.int32)
+    its = np.ascontiguousarray(n_iterations, np.int32); dr = np.ascontiguousarray(draws, np.int32).ravel()
+    N = C.c_int(); idx1 = np.zeros(max(n1, 1), np.int32); vb = np.zeros(max(n1, 1), np.uint8); T = np.zeros(16, np.float32); Rts = np.zeros(13, np.float32)
+    state = np.zeros(6, np.int32); x12 = np.zeros((max(n1, 1), 6), np.float32)
+    L.hm_sim3_mirror.argtypes = [C.c_int] * 7 + [C.c_void_p] * 14 + [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 8
+    assert len(mp1) == len(kf1["octave"]) and len(kf1["sigma2"]) == len(kf2["sigma2"])
+    rc = L.hm_sim3_mirror(engine, n1, len(kf1["octave"]), len(kf2["octave"]), len(arrs[1]), len(kf1["bad"]), len(kf2["bad"]), *[p(a) for a in arrs], p(mp1), p(m12),
+                          1 if fix_scale else 0, probability, min_inliers,
+                          max_iterations, len(its), p(its), len(dr), p(dr), C.byref(N), p(idx1), p(x12), p(vb), p(T), p(Rts), p(state))
+    assert rc == 0, L.hm_last_error()
+    n = N.value
+    return dict(N=n, indices1=idx1[:n].copy(), x3dc1=x12[:n, :3].copy(), x3dc2=x12[:n, 3:].copy(), vbInliers=vb[:n1].copy(), T12=T.reshape(4, 4).copy(), R=Rts[:9].copy(),
+                t=Rts[9:12].copy(), s=Rts[12:13].copy(), no_more=int(state[0]), n_inliers=int(state[1]), iterations=int(state[2]), found=int(state[3]),
+                draws_used=int(state[4]), max_its=int(state[5]))
+
+
+def camera_points(Tcw, pos):
+    """Rcw Xw + tcw as the mirror computes it: double products summed upwards, the translation added last, narrowed once"""
+    T = np.asarray(Tcw, np.float32).astype(np.float64); X = np.asarray(pos, np.float32).astype(np.float64)
+    return np.stack([(((T[k, 0] * X[:, 0] + T[k, 1] * X[:, 1]) + T[k, 2] * X[:, 2]) + T[k, 3]).astype(np.float32) for k in range(3)], 1)
+
+
+def mirror_case(seed=21, N=90, fix_scale=False):
+    """Two key frames and the matches of a loop candidate for the mirror class: key frame 1 has n1 key points of which some hold no map point, some
+    a bad one, some one that does not know its key point (GetIndexInKeyFrame < 0), some one behind every face; vpMatched12 has holes, bad points,
+    points without an index and points behind every face of key frame 2.  Returns (camd, kf1, kf2, matched12, kept): kept = the key points of key
+    frame 1 the constructor keeps, in order."""
+    import sim3_cases as sc
+    from cubemapslam_amd import synth
+    pr = sc.problem(seed, N=N, outliers=0.3, fix_scale=int(fix_scale))      # fix_scale: the true scale is 1
+    rng = np.random.default_rng(seed)
+    n1 = N + 20
+    where = np.sort(rng.choice(n1, N, replace=False))                 # key points of key frame 1 that hold the problem's correspondences
+    kfs = []
+    for x in (pr["x3dc1"], pr["x3dc2"]):
+        R = synth._rot(rng.normal(size=3), rng.uniform(-0.6, 0.6)); t = rng.uniform(-2, 2, 3)
+        Tcw = np.hstack([R, t[:, None]]).astype(np.float32)
+        pos = ((x.astype(np.float64) - Tcw[:, 3].astype(np.float64)) @ Tcw[:, :3].astype(np.float64)).astype(np.float32)      # Xw = R^T (Xc - t)
+        order = rng.permutation(N)                                    # the map points are stored in an order of their own
+        nk = N + 30
+        kfs.append(dict(Tcw=Tcw, sigma2=(np.float32(1.2) ** (2 * np.arange(8))).astype(np.float32), octave=rng.integers(0, 8, nk).astype(np.int32),
+                        pos=pos[order].copy(), bad=np.zeros(N, np.uint8), index_in_kf=rng.permutation(nk)[:N].astype(np.int32), slot=np.argsort(order)))
+    kf1, kf2 = kfs
+    kf1["octave"] = rng.integers(0, 8, n1).astype(np.int32); kf1["index_in_kf"] = rng.permutation(n1)[:N].astype(np.int32)
+    mp1 = np.full(n1, -1, np.int32); mp1[where] = kf1["slot"]
+    m12 = np.full(n1, -1, np.int32); m12[where] = kf2["slot"]
+    kf1["mp"] = mp1
+    pick = rng.permutation(where)
+    drop = dict(no_match=pick[0:5], no_own=pick[5:9], bad1=pick[9:13], bad2=pick[13:17], noidx1=pick[17:20], noidx2=pick[20:23], behind1=pick[23:26], behind2=pick[26:29])
+    m12[drop["no_match"]] = -1
+    stray = np.setdiff1d(np.arange(n1), where)[:3]; m12[stray] = kf2["slot"][:3]      # a match on a key point without an own map point
+    mp1[drop["no_own"]] = -1
+    kf1["bad"][mp1[drop["bad1"]]] = 1; kf2["bad"][m12[drop["bad2"]]] = 1
+    kf1["index_in_kf"][mp1[drop["noidx1"]]] = -1; kf2["index_in_kf"][m12[drop["noidx2"]]] = -1
+    for kf, slots in ((kf1, mp1[drop["behind1"]]), (kf2, m12[drop["behind2"]])):
+        T = kf["Tcw"].astype(np.float64)
+        for s in slots:                                              # camera-frame (0.1, -0.2, -3): in no face's branch, u = v = -1
+            kf["pos"][s] = ((np.array([0.1, -0.2, -3.0]) - T[:, 3]) @ T[:, :3]).astype(np.float32)
+    gone = np.concatenate(list(drop.values()))
+    kept = np.array([i for i in where if i not in set(gone.tolist())], np.int32)
+    return synth.camera("lafida", sc.F), kf1, kf2, m12, kept
+
+
+def mirror_job(kf1, kf2, m12, kept):
+    """The job arrays Sim3Solver's constructor should make of the kept key points"""
+    import sim3_cases as sc
+    s1 = kf1["mp"][kept]; s2 = np.asarray(m12)[kept]
+    return dict(x3dc1=camera_points(kf1["Tcw"], kf1["pos"][s1]), x3dc2=camera_points(kf2["Tcw"], kf2["pos"][s2]),
+                max_err1=sc.max_error(kf1["sigma2"][kf1["octave"][kf1["index_in_kf"][s1]]]), max_err2=sc.max_error(kf2["sigma2"][kf2["octave"][kf2["index_in_kf"][s2]]]))
