@@ -18,6 +18,7 @@
 #include <pthread.h>
 #include <unordered_map>
 #include "cms_ba_pool.h"
+#include "cms_ba_group_kind.h"
 
 // Every A/B switch of the local-BA host code, read ONCE (first use) so that the choices made when a window is built (which work lists exist)
 // and the choices made when it is optimised (which kernels run) can never disagree.  Tests that flip a switch use a child process.
@@ -110,6 +111,7 @@ struct cms_ba {
   int* d_pair_s1 = nullptr; int* d_pair_s2 = nullptr; int* d_pair_off = nullptr; int2* d_tup = nullptr;
   int* d_pair_chunk_off = nullptr; int2* d_chunk_range = nullptr; double* d_chunk_sum = nullptr; int* d_pair_of_block = nullptr;
   int npairs = 0, nchunks = 0; size_t solve_lds = 0, blk_lds = 0, blk3_lds = 0; bool solve_in_lds = false, solve_blk = false, solve_blk3 = false;
+  bool solve_presum = false;      // the slice-summing trial solve adds the slices into LDS first (kb_ba_trial_solve3rp): decided from this window alone (ba_plan_sizes), part of the group key
   // per-point Schur work lists (sp.R == 0: not available for this window, the tuple-chunk kernel is used)
   BaSp sp = {};
   int* d_sp_bat_e0 = nullptr; uint32_t* d_sp_off = nullptr; uint32_t* d_sp_list = nullptr; int* d_sp_slot_pair = nullptr; int* d_sp_tup_base = nullptr;
@@ -685,8 +687,9 @@ static void ba_plan_sizes(cms_ba* b, int K, int P, int E, int np) {
   b->nblk_e = (E + 255) / 256; b->nblk_p = (P + 127) / 128;
   b->blk_lds = ((size_t)36 * (np * (np + 1) / 2) + 72 * (size_t)np + 2 * (size_t)n + 8) * sizeof(double);
   b->solve_blk = np >= 1 && np * (np + 1) / 2 <= 384 && b->blk_lds <= BA_LDS_CEILING;
-  b->blk3_lds = ((size_t)BA_S3_STRIDE * (np * (np - 1) / 2) + 36 * (size_t)np + 2 * (size_t)BA_S3_STRIDE * np + 36 + 3 * (size_t)n + 8) * sizeof(double);
+  b->blk3_lds = ba_solve3_lds(np, BA_S3_STRIDE);
   b->solve_blk3 = b->solve_blk && ba_s3_threads(np) <= 1024 && 6 * np <= 60 * BA_S3_NY && b->blk3_lds <= BA_LDS_CEILING;      // (np <= 25)
+  b->solve_presum = ba_solve_presum_fits(b->solve_blk3, b->blk3_lds, np * (np + 1) / 2, BA_LDS_CEILING);      // (np <= 20)
 }
 // LDS of the edge-major / run-major Schur kernels without the per-wavefront part: the copy of the reduced system + the key frames' rotations
 static size_t ba_se_fixed_lds(int K, int np) {

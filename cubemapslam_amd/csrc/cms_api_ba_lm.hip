@@ -464,14 +464,20 @@ static int ba_optimize_stage_batched_dev(cms_ba** bas, int n, std::vector<BaLm>&
   const int rw_units1 = std::max(8, std::min(BA_RW_CUTS, ba_device_cus(bas[0]->device) * ba_knobs().rw_waves_cu1 / std::max(n, 1)));
   // linearisation inside the Schur kernel (cms_ba_schur_edges.hip, FUSED): needs the edge-major kernels and the three-lane solve
   const bool fused = gm.fused;
-  // the range slices summed by the solve kernel's assembly (kb_ba_trial_solve3r) instead of by a launch of their own
+  // the range slices summed by the solve kernel's assembly (kb_ba_trial_solve3r) instead of by a launch of their own (the two sum in different orders:
+  // a deterministic group's windows are all on one side of solve_reduce_max, ba_solve_sums_slices in the group key, so the largest count decides for each)
   const bool solve_reduces = fused && (gm.gsum || (!ba_knobs().separate_reduce && max_seR <= ba_knobs().solve_reduce_max));
   dyn.fused_lin = fused ? 1 : 0;
   {
-    // slices (deterministic windows, CMS_BA_NO_GLOBAL_SUM): the solve kernel adds them into LDS with all its threads first, where the LDS allows it (<= 21 free key frames)
-    static const bool no_presum = getenv("CMS_BA_NO_SOLVE_PRESUM") != nullptr;      // developer A/B
-    const size_t need = lds3 + (size_t)max_np2 * 42 * sizeof(double);
-    if (use_s3 && solve_reduces && !gm.gsum && !no_presum && need <= BA_LDS_CEILING) { dyn.solve_presum = 1; lds3 = need; }
+    // slices (deterministic windows, CMS_BA_NO_GLOBAL_SUM): the solve kernel adds them into LDS with all its threads first, where the LDS allows it: <= 20 free
+    // key frames (20: 78 912 + 210 x 336 = 149 472 bytes; 21: 86 032 + 231 x 336 = 163 648 > BA_LDS_CEILING).  The two kernels round differently, so the choice
+    // belongs to the WINDOW (cms_ba::solve_presum, fixed at its creation from its own sizes) and not to the group's largest window: deterministic windows of
+    // both choices never share a group (ba_group_kind), every other group presums only if all its windows do.  The launch carries the largest window's need
+    static const bool no_presum = getenv("CMS_BA_NO_SOLVE_PRESUM") != nullptr;      // developer A/B (the whole process: every window, whatever its company)
+    bool presum = use_s3 && solve_reduces && !gm.gsum && !no_presum;
+    size_t need = 0;
+    for (int w = 0; w < n; ++w) { presum = presum && bas[w]->solve_presum; need = std::max(need, ba_solve3_presum_lds(bas[w]->blk3_lds, bas[w]->grp_se.npairs2)); }
+    if (presum) { dyn.solve_presum = 1; lds3 = std::max(lds3, need); }      // (every window's need fits, CMS_BA_SOLVE_LDS_KB is capped at the ceiling: so does the maximum)
   }
   // (deterministic windows, se.det: kb_ba_first_pass adds the key frames' diagonal sums -- lambda starts from their maximum -- in chunk and slice order)
   const bool first_pass = fused && use_te && first_round && !ba_knobs().separate_first_pass;      // (a stage's windows all start at it == 0)
@@ -641,6 +647,15 @@ static int ba_classify_batched(cms_ba** bas, int n, int set_level, std::vector<i
 }
 
 static int ba_optimize_group(cms_ba** bas, int n, int its_robust, int its_final, const volatile uint8_t* stop, cms_ba_stats* stats);
+// Slices the Schur launch of a deterministic window's group leaves for the window: its share is det_ranges workgroups whatever the group
+// (ba_group_ranges), split the way ba_upload_items splits it (the run-major body only where the group's windows -- all of one kind -- have runs and
+// full workgroups)
+static int ba_det_slices(const cms_ba* b) {
+  BaSe se = b->se;
+  if (!(b->rm_lds > 0 && b->se_waves == BA_SE_THREADS / 64 && !ba_knobs().runs_as_edges)) se.n_rm = 0;
+  ba_se_split(se, std::max(2, b->det_ranges));
+  return se.R_rm + se.R;
+}
 // Windows are independent problems; the grouped driver wants a group of one kind (one device; all with the edge-major work list, or none:
 // a window that has it carries no other list) of at most BA_MAX_GROUP windows.  A call that mixes kinds is run as several groups, one
 // after the other -- same results, the caller's order of `stats` kept.
@@ -649,12 +664,15 @@ extern "C" int cms_ba_optimize_many(cms_ba** bas, int n, int its_robust, int its
   for (int w = 0; w < n; ++w) if (!bas[w]) return cms_fail(CMS_ERR_ARG, "null ba");
   // (device-planned windows among themselves: their groups always run the fused kernels, which is all they carry lists for)
   // (a deterministic window's sums must not depend on its company: windows that would change the group's kernels -- fewer wavefronts per workgroup,
-  // no signature runs -- form groups of their own)
+  // no signature runs, the other slice-summing solve kernel, the slices summed by a launch of their own -- form groups of their own: ba_group_kind,
+  // cms_ba_group_kind.h)
   auto kind = [&](int w) {
     const cms_ba* b = bas[w];
-    int k = b->device * 8 + (b->fast_plan ? 4 : 0) + (b->se.nchunks > 0 ? 2 : 0) + (b->deterministic ? 1 : 0);
-    if (b->deterministic) k += 1024 * (1 + (b->det_points ? 1 : 0) + 2 * (b->rm_lds > 0 ? 1 : 0) + 4 * std::max(0, std::min(15, b->se_waves)) + 64 * b->det_ranges);
-    return k;
+    BaKindIn in;
+    in.device = b->device; in.fast_plan = b->fast_plan; in.edge_list = b->se.nchunks > 0; in.deterministic = b->deterministic;
+    in.det_points = b->det_points; in.has_runs = b->rm_lds > 0; in.se_waves = b->se_waves; in.det_ranges = b->det_ranges; in.solve_presum = b->solve_presum;
+    in.solve_sums_slices = b->deterministic && !b->det_points && b->se.nchunks > 0 && ba_solve_sums_slices(ba_det_slices(b), ba_knobs().solve_reduce_max);
+    return ba_group_kind(in);
   };
   bool one = n <= BA_MAX_GROUP;
   for (int w = 1; w < n && one; ++w) one = kind(w) == kind(0);

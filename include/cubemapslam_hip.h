@@ -289,7 +289,8 @@ int cms_ba_pool_trim(int device, size_t* released);
  * pair-owner kernel (kb_ba_schur_points, CMS_BA_DET_POINTS=1 selects it for all) -- deterministic as well.  The choice is taken at cms_ba_create and
  * travels with the window; windows of both kinds may be passed to one cms_ba_optimize_many call (they run as separate groups).  Process-wide; the
  * environment variable CMS_BA_DETERMINISTIC=1 gives the initial value.  cms_ba_get_deterministic returns the current setting.
- * on >= 2 also says into how many workgroups such a window is cut (1: the default, 16 -- a group of sixteen windows fills the chip once; at most 128).  The count is
+ * on >= 2 also says into how many workgroups such a window is cut (1: the default, 16 -- a group of sixteen windows fills the chip once; at most 128: a larger value is
+ * clamped to 128 without an error, and cms_ba_get_deterministic then returns 128).  The count is
  * fixed when the window is created, because the bits depend on it.  A host that optimises ONE window per call (the reference's LocalMapping thread) should pass 64:
  * 2.4 instead of 3.5 ms per 80 k-observation window (default path 1.7 ms); sixteen windows in lock-step then take 6.1 instead of 4.8 ms. */
 int cms_ba_set_deterministic(int on);

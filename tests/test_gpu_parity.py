@@ -664,14 +664,104 @@ def test_ba_deterministic_mode_with_a_workgroup_count_of_the_callers_choice():
         _ba_updates_close_or_cascade(prob, g["poses"], g["points"], w, tag="deterministic, chosen workgroup count")
 
 
+def _ba_presum_line_windows():
+    """Windows on both sides of the line at which the trial solve stops summing the Schur slices into LDS first (20 free key frames: yes, 21: no).
+    P = 2500 is enough: 140-150 chunks per window, cut into 15 or 16 workgroups (18 chunks, nine workgroups for E), so every Schur launch ends
+    with several slices and the two solve kernels really add differently.  With 20 or 21 free key frames the run-major buffers no longer fit, so
+    the tracked windows A and B carry no runs either; E is small enough that no observation signature fills a run.  G (19 free) has runs."""
+    sh = dict(A=dict(K=21, P=2500, seed=121, views="track"), B=dict(K=22, P=2500, seed=122, views="track"), C=dict(K=21, P=2500, seed=123, views="random"),
+              D=dict(K=22, P=2500, seed=124, views="random"), E=dict(K=12, P=300, seed=125, views="random"), G=dict(K=20, P=2500, seed=126, views="track"))
+    return {name: synth.ba_problem(F=550, obs_per_point=4, **s) for name, s in sh.items()}
+
+
+def test_ba_deterministic_windows_across_the_presum_line_keep_their_bits():
+    """include/cubemapslam_hip.h, cms_ba_set_deterministic: "Same input, same bits: run after run, alone or in any group of a cms_ba_optimize_many call".
+    A window of 20 free key frames has its Schur slices summed into LDS by the solve kernel's threads first (v = s0 + s1 + ..., a -= v), one of 21
+    has them subtracted one by one in the assembly loop (a -= s0, a -= s1, ...): different roundings.  Which of the two a window gets must follow
+    from the window alone -- windows of both sides in ONE call (same wavefront count, no runs, same workgroup count: nothing else tells them apart)
+    must give the bits they give alone, in every order, created one by one or by cms_ba_create_many with the plan made on the device, with 16
+    workgroups per window and with 64 (the slices then go through kb_ba_schur_edges_reduce -- unless a window has so few chunks that it leaves at
+    most 24 slices, which the solve kernel sums itself: such a window next to a large one is the third company here).  Alone runs: iteration
+    counts and flags are the oracle's, the estimates pass the default path's bar.  cms_ba_set_deterministic(500) is clamped to 128."""
+    probs = _ba_presum_line_windows()
+    for name, p in probs.items():      # the kinds cms_ba_optimize_many groups by, as far as the host plan shows them: runs (rm_lds > 0) only in G
+        pl = api.ba_plan(p["fixed"], len(p["points"]), p["e_pose"], p["e_point"])
+        assert pl["usable"] and (pl["n_rm"] > 0) == (name == "G") and pl["n_chunks"] >= 18, (name, pl["n_rm"], pl["n_chunks"])
+        assert pl["np"] == len(p["poses"]) - 1
+
+    def same(o, g, what):
+        for k, arr in enumerate(("poses", "points")):
+            assert np.array_equal(o[k], g[arr]), (what, arr, "max difference %.3g" % np.abs(o[k] - g[arr]).max())
+
+    def in_company(order, alone, create_many=False):
+        if create_many:
+            bas = api.ba_create_many([dict(probs[n], _plan_on_device=True) for n in order])
+        else:
+            bas = [api.BundleAdjuster(probs[n]) for n in order]
+        try:
+            rc, stats = api.ba_optimize_many(list(bas), (5, 10))
+            assert rc == 0
+            outs = api.ba_read_many(bas) if create_many else [ba.read() for ba in bas]
+        finally:
+            for ba in bas:
+                ba.close()
+        for n, o, st in zip(order, outs, stats):
+            what = "window %s in %s%s" % (n, "".join(order), " (cms_ba_create_many)" if create_many else "")
+            same(o, alone[n], what)
+            assert list(st.iterations_done) == list(alone[n]["stats"].iterations_done), what
+
+    L = api.lib()
+    try:
+        api.ba_set_deterministic(True)
+        alone = {n: api.ba_run(p) for n, p in probs.items()}
+        for n, p in probs.items():
+            g = api.ba_run(p)
+            for arr in ("poses", "points", "outliers"):
+                assert np.array_equal(g[arr], alone[n][arr]), ("window %s alone, second run" % n, arr)
+        for order in ("AB", "BA", "CD", "AD", "EB", "AAB", "ABCDEG", "GDECBA"):
+            in_company(order, alone)
+        for order in ("ABA", "DC"):
+            in_company(order, alone, create_many=True)
+        api.ba_set_deterministic(64)
+        alone64 = {n: api.ba_run(probs[n]) for n in "ABCE"}
+        in_company("AB", alone64)
+        # E's 18 chunks make 18 slices, which the solve kernel sums itself; C's 64 go through kb_ba_schur_edges_reduce (four strided partial sums per
+        # element): who sums a window's slices must follow from the window's own count, not from the largest in the call
+        in_company("EC", alone64)
+        in_company("CE", alone64)
+        # more workgroups than a window's Schur launch can have: clamped to 128, not refused
+        api.ba_set_deterministic(128)
+        a128 = api.ba_run(probs["A"])
+        api.ba_set_deterministic(500)
+        assert L.cms_ba_get_deterministic() == 128
+        a500 = api.ba_run(probs["A"])
+        for arr in ("poses", "points", "outliers"):
+            assert np.array_equal(a500[arr], a128[arr]), ("window A under 500 and under 128 workgroups", arr)
+    finally:
+        api.ba_set_deterministic(False)
+    for n in "ABCD":
+        p, g = probs[n], alone[n]
+        w = orc.ba_run(p)
+        assert list(g["stats"].iterations_done) == list(w["stats"].iterations_done) and np.array_equal(g["outliers"], w["outliers"]), n
+        _ba_updates_close_or_cascade(p, g["poses"], g["points"], w, tag="deterministic window %s, K=%d %s" % (n, len(p["poses"]), "track" if n in "AB" else "random"))
+
+
 def test_ba_deterministic_mode_on_windows_of_every_solver_path():
     """Deterministic windows the fixed-order fused chain does not take fall back to deterministic kernels of their own -- 27 and 29 free key frames (no
     three-lane solve: the pair-owner kernel on the host's full plan), 39 (register-tiled scalar solve) -- and small or odd windows (two key frames, a
-    single free one, 25 free = the three-lane solve's limit, fewer wavefronts per workgroup) run the fixed-order kernels: three runs give the same bits,
+    single free one, 20 and 21 free = the two sides of the solve kernel's slice pre-sum, 25 free = the three-lane solve's limit, fewer wavefronts per
+    workgroup) run the fixed-order kernels: three runs give the same bits,
     iteration counts and flags are the oracle's, the estimates pass the default path's bar."""
     shapes = [dict(K=2, P=120, obs_per_point=2, seed=7), dict(K=3, P=300, obs_per_point=3, seed=8), dict(K=26, P=1500, obs_per_point=5, seed=16),
               dict(K=28, P=1500, obs_per_point=5, seed=3), dict(K=30, P=2000, obs_per_point=5, seed=5), dict(K=40, P=2500, obs_per_point=6, seed=4),
-              dict(K=23, P=4000, obs_per_point=4, seed=31, views="track"), dict(K=25, P=5000, obs_per_point=4, seed=32, views="track")]
+              dict(K=23, P=4000, obs_per_point=4, seed=31, views="track"), dict(K=25, P=5000, obs_per_point=4, seed=32, views="track"),
+              # 20 and 21 free key frames: the last window whose solve kernel sums the slices into LDS first, and the first whose does not.
+              # Seed 35 and not 34, chosen on the oracle alone: tracked windows of this size are chaotic at float-rounding level in the reference
+              # itself (see _ba_updates_close_or_cascade), and the helper measures that with ONE perturbation of the oracle's input.  On seed 34 that
+              # one sample shows no cascade (0 points beyond 1e-4) while the median of 24 perturbations is 25 points and the maximum 32 (worst
+              # 5.2e-4), so there the helper's bar says nothing about the window; seed 35 is the next one whose sample is no tamer than the
+              # median of the 24 (0 points both: the oracle mostly agrees with itself to 1e-8 there)
+              dict(K=21, P=2500, obs_per_point=4, seed=33, views="track"), dict(K=22, P=2500, obs_per_point=4, seed=35, views="track")]
     for sh in shapes:
         prob = synth.ba_problem(F=550, **sh)
         api.ba_set_deterministic(True)
