@@ -165,6 +165,28 @@ def _chk(rc, what):
     return rc
 
 
+class _Handle:
+    """Life cycle of a handle of the library: _create fills self.h through the class's create entry, close() hands it to the destroy entry once,
+    and __del__ swallows whatever a close at interpreter exit raises"""
+    _entries = None      # (create, destroy)
+
+    def _create(self, *args, out_last=False):
+        self.h = C.c_void_p()
+        args = args + (C.byref(self.h),) if out_last else (C.byref(self.h),) + args
+        _chk(getattr(lib(), self._entries[0])(*args), self._entries[0])
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(lib(), self._entries[1])(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def make_camera(d):
     cam = Camera()
     for k in ("c", "d", "e", "u0", "v0", "Iw", "Ih", "face", "fov_deg"):
@@ -206,29 +228,18 @@ def remap_tiles_host(cam, lut, tile_w, tile_h, lds_budget=RT_LDS_MAX):
     return out[:n_all.value].copy(), n_live.value, lds.value
 
 
-class Context:
+class Context(_Handle):
     """cms_ctx: remap LUT + extractor tables + device buffers for up to max_batch frames."""
+    _entries = ("cms_ctx_create", "cms_ctx_destroy")
 
     def __init__(self, cam, nfeatures=2000, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7, max_batch=1, device=0):
         self.cam = make_camera(cam) if isinstance(cam, dict) else cam
         self.orb = OrbParams(nfeatures, scale_factor, nlevels, ini_th, min_th)
-        self.h = C.c_void_p()
-        _chk(lib().cms_ctx_create(C.byref(self.h), device, C.byref(self.cam), C.byref(self.orb), max_batch), "cms_ctx_create")
+        self._create(device, C.byref(self.cam), C.byref(self.orb), max_batch)
         self.geom = Geometry()
         _chk(lib().cms_ctx_geometry(self.h, C.byref(self.geom)), "cms_ctx_geometry")
         self.W = self.geom.W
         self.max_batch = max_batch
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().cms_ctx_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def stream(self):
@@ -725,12 +736,12 @@ def load_vocabulary_text(path):
     return dict(k=hdr[0], L=hdr[1], scoring=hdr[2], weighting=hdr[3], parent=parent, is_leaf=is_leaf, desc=desc, weight=weight)
 
 
-class Vocabulary:
+class Vocabulary(_Handle):
     """cms_vocab: the DBoW2 vocabulary tree on one device (read-only, shared by any number of contexts and stores of that device).  Arrays as the text
     format holds them: node 0 is the root, parent[i] < i, is_leaf marks the words, desc n_nodes x 32 bytes, weight float64."""
+    _entries = ("cms_vocab_create", "cms_vocab_destroy")
 
     def __init__(self, k, L, scoring, weighting, parent, is_leaf, desc, weight, device=0):
-        self.h = C.c_void_p()
         parent = np.ascontiguousarray(parent, np.int32); is_leaf = np.ascontiguousarray(is_leaf, np.uint8)
         desc = np.ascontiguousarray(desc, np.uint8); weight = np.ascontiguousarray(weight, np.float64)
         assert len(is_leaf) == len(parent) and len(weight) == len(parent) and desc.size == 32 * len(parent)
@@ -740,8 +751,7 @@ class Vocabulary:
         L_.cms_vocab_destroy.restype = None
         L_.cms_vocab_info.argtypes = [C.c_void_p, C.c_void_p]
         L_.cms_vocab_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
-        _chk(L_.cms_vocab_create(C.byref(self.h), device, int(k), int(L), int(scoring), int(weighting), len(parent), _p(parent), _p(is_leaf), _p(desc), _p(weight)),
-             "cms_vocab_create")
+        self._create(device, int(k), int(L), int(scoring), int(weighting), len(parent), _p(parent), _p(is_leaf), _p(desc), _p(weight))
 
     @classmethod
     def from_dict(cls, t, device=0):
@@ -750,17 +760,6 @@ class Vocabulary:
     @classmethod
     def from_text_file(cls, path, device=0):
         return cls.from_dict(load_vocabulary_text(path), device=device)
-
-    def close(self):
-        if self.h:
-            lib().cms_vocab_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self):
         a = np.zeros(7, np.int32)
@@ -778,24 +777,14 @@ class Vocabulary:
         return _bow_trim(o, nw.value, nn.value)
 
 
-class KeyframeStore:
+class KeyframeStore(_Handle):
     """cms_kfstore: key frames resident on the device in slots"""
+    _entries = ("cms_kfstore_create", "cms_kfstore_destroy")
 
     def __init__(self, ctx, max_keyframes, max_features=2048, max_nodes=2048):
         self.ctx = ctx
         self.max_keyframes = int(max_keyframes)
-        self.h = C.c_void_p()
-        _chk(lib().cms_kfstore_create(C.byref(self.h), ctx.h, max_keyframes, max_features, max_nodes), "cms_kfstore_create")
-
-    def close(self):
-        if self.h:
-            lib().cms_kfstore_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(ctx.h, max_keyframes, max_features, max_nodes)
 
     def put(self, slot, K):
         _chk(lib().cms_kfstore_put(self.h, slot, C.byref(K)), "cms_kfstore_put")
@@ -1096,18 +1085,16 @@ def fuse_search(ctx, b, pose15, skip, pos, normal, min_dist, max_dist, desc, th)
     return bi, bd
 
 
-class BundleAdjuster:
+class BundleAdjuster(_Handle):
     """cms_ba: one local-BA window resident on the device."""
+    _entries = ("cms_ba_create", "cms_ba_destroy")
 
     def __init__(self, prob, device=0):
         self.prob = prob
         self.K, self.P, self.E = len(prob["poses"]), len(prob["points"]), len(prob["e_pose"])
-        self.h = C.c_void_p()
         poses = np.ascontiguousarray(prob["poses"], np.float64); pts = np.ascontiguousarray(prob["points"], np.float64)
-        _chk(lib().cms_ba_create(C.byref(self.h), device, self.K, _p(poses), _p(prob["fixed"]), self.P, _p(pts), self.E,
-                                 _p(prob["e_pose"]), _p(prob["e_point"]), _p(np.ascontiguousarray(prob["e_obs"], np.float64)),
-                                 _p(prob["e_invsig2"]), _p(prob["e_face"]), prob["fx"], prob["fy"], prob["cx"], prob["cy"]),
-             "cms_ba_create")
+        self._create(device, self.K, _p(poses), _p(prob["fixed"]), self.P, _p(pts), self.E, _p(prob["e_pose"]), _p(prob["e_point"]),
+                     _p(np.ascontiguousarray(prob["e_obs"], np.float64)), _p(prob["e_invsig2"]), _p(prob["e_face"]), prob["fx"], prob["fy"], prob["cx"], prob["cy"])
 
     @classmethod
     def from_handle(cls, prob, handle):
@@ -1165,17 +1152,6 @@ class BundleAdjuster:
         ms = C.c_double(0); n = C.c_long(0)
         _chk(lib().cms_ba_profile_get(self.h, C.byref(ms), C.byref(n)), "cms_ba_profile_get")
         return ms.value, n.value
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().cms_ba_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def ba_compose_chunks(fixed, n_points, e_pose, e_point, lookahead=48):
@@ -1346,24 +1322,13 @@ class PoseStats(C.Structure):
     _fields_ = [("rounds", C.c_int), ("n_bad", C.c_int), ("iterations_done", C.c_int * 4)]
 
 
-class PoseOptimizer:
+class PoseOptimizer(_Handle):
     """Optimizer::PoseOptimization for a batch of frames (cms_pose_*): problems are dicts like synth.pose_problem()."""
+    _entries = ("cms_pose_create", "cms_pose_destroy")
 
     def __init__(self, max_frames, max_edges, device=0):
-        self.h = C.c_void_p()
-        _chk(lib().cms_pose_create(C.byref(self.h), device, max_frames, max_edges), "cms_pose_create")
+        self._create(device, max_frames, max_edges)
         self.nf = 0
-
-    def close(self):
-        if self.h:
-            lib().cms_pose_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def stream(self):
         return lib().cms_pose_stream(self.h)
@@ -1495,27 +1460,16 @@ def pnp_first_difference(want, got):
     return None
 
 
-class PnPSolver:
+class PnPSolver(_Handle):
     """PnPsolver::iterate for many solvers in one launch sequence (cms_pnp_*).  jobs: a (PnpJob * n) array, e.g. from pnp_jobs()."""
+    _entries = ("cms_pnp_create", "cms_pnp_destroy")
 
     def __init__(self, max_jobs, max_corr_total, max_hyp_total, device=0):
-        self.h = C.c_void_p()
         L = lib()
         L.cms_pnp_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.cms_pnp_destroy.argtypes = [C.c_void_p]
         L.cms_pnp_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        _chk(L.cms_pnp_create(C.byref(self.h), device, max_jobs, max_corr_total, max_hyp_total), "cms_pnp_create")
-
-    def close(self):
-        if self.h:
-            lib().cms_pnp_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(device, max_jobs, max_corr_total, max_hyp_total)
 
     def iterate(self, ctx, jobs):
         _chk(lib().cms_pnp_iterate(self.h, ctx.h, len(jobs), jobs), "cms_pnp_iterate")
@@ -1605,27 +1559,16 @@ def sim3_results(arr, states):
 sim3_first_difference = pnp_first_difference      # result dicts compared bit for bit: None, or (job, key, wanted, got)
 
 
-class Sim3Solver:
+class Sim3Solver(_Handle):
     """Sim3Solver::iterate for many solvers in one launch sequence (cms_sim3_*).  jobs: a (Sim3Job * n) array, e.g. from sim3_jobs()."""
+    _entries = ("cms_sim3_create", "cms_sim3_destroy")
 
     def __init__(self, max_jobs, max_corr_total, max_hyp_total, device=0):
-        self.h = C.c_void_p()
         L = lib()
         L.cms_sim3_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.cms_sim3_destroy.argtypes = [C.c_void_p]
         L.cms_sim3_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        _chk(L.cms_sim3_create(C.byref(self.h), device, max_jobs, max_corr_total, max_hyp_total), "cms_sim3_create")
-
-    def close(self):
-        if self.h:
-            lib().cms_sim3_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(device, max_jobs, max_corr_total, max_hyp_total)
 
     def iterate(self, ctx, jobs):
         _chk(lib().cms_sim3_iterate(self.h, ctx.h, len(jobs), jobs), "cms_sim3_iterate")
@@ -1685,28 +1628,17 @@ def init_results(arr, states):
 init_first_difference = pnp_first_difference      # result dicts compared bit for bit: None, or (job, key, wanted, got)
 
 
-class TwoViewInitializer:
+class TwoViewInitializer(_Handle):
     """Initializer::InitializeWithRays for many streams in one launch sequence (cms_init_*).  jobs: an (InitJob * n) array, e.g. from init_jobs()."""
+    _entries = ("cms_init_create", "cms_init_destroy")
 
     def __init__(self, max_jobs, max_matches_total, max_keys1_total, max_hyp_total, device=0):
-        self.h = C.c_void_p()
         L = lib()
         L.cms_init_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.cms_init_destroy.argtypes = [C.c_void_p]
         L.cms_init_two_view.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.cms_init_two_view_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        _chk(L.cms_init_create(device, max_jobs, max_matches_total, max_keys1_total, max_hyp_total, C.byref(self.h)), "cms_init_create")
-
-    def close(self):
-        if self.h:
-            lib().cms_init_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(device, max_jobs, max_matches_total, max_keys1_total, max_hyp_total, out_last=True)
 
     def two_view(self, ctx, jobs, frames=False):
         L = lib()

@@ -2,45 +2,37 @@
 // (k_init_gather in front); included by cms_lib.hip behind cms_api_frames.hip (cms_ctx, cms_fail, HIPCHK, CmsBlock) and cms_init_kernels.hip.  All
 // jobs of a call are ONE launch sequence on the context's stream: one pinned block up (the handle's CmsStage), k_init_hypotheses, k_init_check, k_init_select, one pinned
 // block back; ReconstructE's decision (cms_init_core.h, host only) is then taken per job.  Everything that becomes a device index (draws, match
-// indices, counts, offsets) is checked on the host before anything is enqueued (cms_init_job_check.h).
+// indices, counts, offsets) is checked on the host before anything is enqueued (cms_init_job_check.h).  The handle base, the head of an entry and the
+// staging of the draws are cms_api_ransac.h, shared with the PnP and Sim3 entries.
 #include <cstring>
 #include <vector>
 #include "cms_init_job_check.h"
 
-struct cms_init {
-  int device = 0, max_jobs = 0, max_matches = 0, max_keys1 = 0, max_hyp = 0;
-  CmsStage blocks;      // one device block and one pinned block, grown on demand
+struct cms_init : CmsRansacHandle {      // no stream of its own: the entries run on the context's
+  int max_matches = 0, max_keys1 = 0, max_hyp = 0;
 };
-
-static void cms_init_free(cms_init* p) {
-  if (!p) return;
-  hipSetDevice(p->device);
-  p->blocks.release();
-  delete p;
-}
 
 extern "C" int cms_init_create(int device, int max_jobs, int max_matches_total, int max_keys1_total, int max_hyp_total, cms_init** out) {
   if (!out || max_jobs < 1 || max_matches_total < 1 || max_keys1_total < 1 || max_hyp_total < 1) return cms_fail(CMS_ERR_ARG, "cms_init_create: bad argument");
   const int rcd = cms_check_device(device, "cms_init_create: no HIP device (the initializer's device path has no CPU fallback)");
   if (rcd) return rcd;
   cms_init* p = new cms_init();
-  p->device = device; p->max_jobs = max_jobs; p->max_matches = max_matches_total; p->max_keys1 = max_keys1_total; p->max_hyp = max_hyp_total;
+  p->max_matches = max_matches_total; p->max_keys1 = max_keys1_total; p->max_hyp = max_hyp_total;
+  (void)p->open(device, max_jobs, false, "cms_init_create");
   *out = p;
   return CMS_OK;
 }
-extern "C" void cms_init_destroy(cms_init* p) { cms_init_free(p); }
+extern "C" void cms_init_destroy(cms_init* p) { cms_ransac_free(p); }
 
 // frames: cms_init_two_view_frames -- frame 2 is gathered on the device from the context's resident rows
 static int cms_init_run(cms_init* p, cms_ctx* c, int njobs, cms_init_job* jobs, bool frames) {
-  if (!p || !c || njobs < 0 || (njobs > 0 && !jobs)) return cms_fail(CMS_ERR_ARG, "cms_init_two_view: bad argument");
-  if (njobs == 0) return CMS_OK;
-  if (c->device != p->device) return cms_fail(CMS_ERR_ARG, "cms_init_two_view: the context and the handle must share the device");
-  if (njobs > p->max_jobs) return cms_fail(CMS_ERR_ARG, "cms_init_two_view: more jobs than the handle was created for");
+  int rc = cms_ransac_check_entry(p, c, njobs, jobs, "cms_init_two_view");
+  if (rc || njobs == 0) return rc;
   std::vector<CmsInitJobDev> jd((size_t)njobs);
   long long nm = 0, hyp = 0, words = 0, nk = 0;
   for (int j = 0; j < njobs; ++j) {
     int N = 0;
-    const int rc = cms_init_check_job(jobs[j], &N, frames);
+    rc = cms_init_check_job(jobs[j], &N, frames);
     if (rc) return cms_fail(rc, "cms_init_two_view: bad job (null array, fewer than 8 matches, a match index outside [-1, n2), iterations < 1, fewer than 8*iterations draws, or a draw outside [0, N-1-k])");
     const cms_init_job& q = jobs[j];
     if (frames && (q.b >= c->max_batch || q.n2 > c->g.kp_cap)) return cms_fail(CMS_ERR_ARG, "cms_init_two_view_frames: frame row or key-point count beyond the context's");
@@ -62,7 +54,7 @@ static int cms_init_run(cms_init* p, cms_ctx* c, int njobs, cms_init_job* jobs, 
   const size_t o_E = blk.take(Hn * 36), o_score = blk.take(Hn * 4), o_hmask = blk.take((size_t)words * 8), o_keys = blk.take(M * 4);
   HIPCHK(hipSetDevice(p->device));
   hipStream_t s = c->stream;
-  int rc = p->blocks.reserve(s, blk.size, out_end);
+  rc = p->blocks.reserve(s, blk.size, out_end);
   if (rc) return rc;
   uint8_t* h = p->blocks.h;
   uint8_t* d = p->blocks.d;
@@ -71,9 +63,7 @@ static int cms_init_run(cms_init* p, cms_ctx* c, int njobs, cms_init_job* jobs, 
   for (int j = 0; j < njobs; ++j) {
     const cms_init_job& q = jobs[j];
     const CmsInitJobDev& g = jd[(size_t)j];
-    int* hj = reinterpret_cast<int*>(h + o_hjob) + g.hyp0;
-    for (int k = 0; k < g.H; ++k) hj[k] = j;
-    std::memcpy(h + o_draws + 32 * (size_t)g.hyp0, q.draws, 32 * (size_t)g.H);
+    cms_ransac_stage_draws<8>(reinterpret_cast<int*>(h + o_hjob) + g.hyp0, reinterpret_cast<int*>(h + o_draws) + 8 * (size_t)g.hyp0, j, g.H, q.draws);
     reinterpret_cast<int*>(h + o_jrow)[j] = frames ? q.b : 0;
     int* first = reinterpret_cast<int*>(h + o_first) + g.m0;
     int* second = reinterpret_cast<int*>(h + o_second) + g.m0;

@@ -2,26 +2,15 @@
 // cms_pnp_iterate_frames (k_pnp_gather in front, the context's stream instead of the handle's); included by
 // cms_lib.hip behind cms_api_frames.hip (cms_ctx, cms_fail, HIPCHK, CmsBlock) and cms_pnp_kernels.hip.  All jobs of a call are ONE launch
 // sequence on the handle's stream: one pinned block up (the handle's CmsStage), k_pnp_hypotheses, k_pnp_inliers, k_pnp_select, one pinned block back.  Everything that
-// becomes a device index (draws, counts, offsets) is checked on the host before anything is enqueued (cms_pnp_job_check.h).
-#include <climits>
-#include <cmath>
+// becomes a device index (draws, counts, offsets) is checked on the host before anything is enqueued (cms_pnp_job_check.h).  The handle base, the
+// head of an entry and the staging of the draws are cms_api_ransac.h, shared with the Sim3 and two-view entries.
 #include <cstring>
 #include <vector>
 #include "cms_pnp_job_check.h"
 
-struct cms_pnp {
-  int device = 0, max_jobs = 0, max_corr = 0, max_hyp = 0;
-  hipStream_t stream = nullptr;
-  CmsStage blocks;      // one device block and one pinned block, grown on demand
+struct cms_pnp : CmsRansacHandle {
+  int max_corr = 0, max_hyp = 0;
 };
-
-static void cms_pnp_free(cms_pnp* p) {
-  if (!p) return;
-  hipSetDevice(p->device);
-  p->blocks.release();
-  if (p->stream) (void)hipStreamDestroy(p->stream);
-  delete p;
-}
 
 extern "C" int cms_pnp_ransac_parameters(int N, double probability, int minInliers, int maxIterations, int minSet, float epsilon, int* min_inliers,
                                          int* max_its, float* epsilon_out) {
@@ -31,12 +20,7 @@ extern "C" int cms_pnp_ransac_parameters(int N, double probability, int minInlie
   if (nMinInliers < minInliers) nMinInliers = minInliers;
   if (nMinInliers < minSet) nMinInliers = minSet;
   if (mRansacEpsilon < (float)nMinInliers / N) mRansacEpsilon = (float)nMinInliers / N;
-  int nIterations;
-  if (nMinInliers == N) nIterations = 1;
-  else {
-    const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)mRansacEpsilon, 3.0)));
-    nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : INT_MIN;      // what cvttsd2si leaves for NaN and for values no int holds
-  }
+  const int nIterations = nMinInliers == N ? 1 : cms_ransac_iterations(probability, mRansacEpsilon);
   *min_inliers = nMinInliers;
   *max_its = std::max(1, std::min(nIterations, maxIterations));
   if (epsilon_out) *epsilon_out = mRansacEpsilon;
@@ -47,27 +31,25 @@ extern "C" int cms_pnp_create(cms_pnp** out, int device, int max_jobs, int max_c
   if (!out || max_jobs < 1 || max_corr_total < 1 || max_hyp_total < 1) return cms_fail(CMS_ERR_ARG, "cms_pnp_create: bad argument");
   const int rcd = cms_check_device(device, "cms_pnp_create: no HIP device (the PnP solver's device path has no CPU fallback)");
   if (rcd) return rcd;
-  HIPCHK(hipSetDevice(device));
   cms_pnp* p = new cms_pnp();
-  p->device = device; p->max_jobs = max_jobs; p->max_corr = max_corr_total; p->max_hyp = max_hyp_total;
-  if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess) { cms_pnp_free(p); return cms_fail(CMS_ERR_HIP, "cms_pnp_create: hipStreamCreate"); }
+  p->max_corr = max_corr_total; p->max_hyp = max_hyp_total;
+  const int rc = p->open(device, max_jobs, true, "cms_pnp_create");
+  if (rc) { cms_ransac_free(p); return rc; }
   *out = p;
   return CMS_OK;
 }
-extern "C" void cms_pnp_destroy(cms_pnp* p) { cms_pnp_free(p); }
+extern "C" void cms_pnp_destroy(cms_pnp* p) { cms_ransac_free(p); }
 
 // frames: cms_pnp_iterate_frames -- the 2-D side is gathered on the device from the context's resident rows, and the whole sequence runs on the
 // context's stream (behind whatever filled the rows), as cms_kfstore_search_by_projection does
 static int cms_pnp_run(cms_pnp* p, cms_ctx* c, int njobs, cms_pnp_job* jobs, bool frames) {
-  if (!p || !c || njobs < 0 || (njobs > 0 && !jobs)) return cms_fail(CMS_ERR_ARG, "cms_pnp_iterate: bad argument");
-  if (njobs == 0) return CMS_OK;
-  if (c->device != p->device) return cms_fail(CMS_ERR_ARG, "cms_pnp_iterate: the context and the handle must share the device");
-  if (njobs > p->max_jobs) return cms_fail(CMS_ERR_ARG, "cms_pnp_iterate: more jobs than the handle was created for");
+  int rc = cms_ransac_check_entry(p, c, njobs, jobs, "cms_pnp_iterate");
+  if (rc || njobs == 0) return rc;
   std::vector<CmsPnpJobDev> jd((size_t)njobs);
   long long corr = 0, hyp = 0, words = 0, mwords = 0;
   for (int j = 0; j < njobs; ++j) {
     int H = 0;
-    const int rc = cms_pnp_check_job(jobs[j], &H, frames);
+    rc = cms_pnp_check_job(jobs[j], &H, frames);
     if (rc == CMS_ERR_UNSUPPORTED) return cms_fail(rc, "cms_pnp_iterate: min_set must be 4 (Refine is the n-point path)");
     if (rc) return cms_fail(rc, "cms_pnp_iterate: bad job (null array, draw outside [0, N-1-k], fewer than 4*H draws, or best_mask against best_inliers)");
     const cms_pnp_job& q = jobs[j];
@@ -91,7 +73,7 @@ static int cms_pnp_run(cms_pnp* p, cms_ctx* c, int njobs, cms_pnp_job* jobs, boo
   const size_t o_rt = blk.take(Hn * 96), o_cnt = blk.take(Hn * 4), o_hmask = blk.take((size_t)words * 8), o_rows = blk.take(C_ * 15 * 8);
   HIPCHK(hipSetDevice(p->device));
   hipStream_t s = frames ? c->stream : p->stream;
-  int rc = p->blocks.reserve(s, blk.size, out_end);
+  rc = p->blocks.reserve(s, blk.size, out_end);
   if (rc) return rc;
   uint8_t* h = p->blocks.h;
   uint8_t* d = p->blocks.d;
@@ -100,9 +82,7 @@ static int cms_pnp_run(cms_pnp* p, cms_ctx* c, int njobs, cms_pnp_job* jobs, boo
   for (int j = 0; j < njobs; ++j) {
     const cms_pnp_job& q = jobs[j];
     const CmsPnpJobDev& g = jd[(size_t)j];
-    int* hj = reinterpret_cast<int*>(h + o_hjob) + g.hyp0;
-    for (int k = 0; k < g.H; ++k) hj[k] = j;
-    if (g.H > 0) std::memcpy(h + o_draws + 16 * (size_t)g.hyp0, q.draws, 16 * (size_t)g.H);
+    cms_ransac_stage_draws<4>(reinterpret_cast<int*>(h + o_hjob) + g.hyp0, reinterpret_cast<int*>(h + o_draws) + 4 * (size_t)g.hyp0, j, g.H, q.draws);
     if (q.N == 0) continue;
     const size_t c0 = (size_t)g.corr0, n = (size_t)q.N;
     std::memcpy(h + o_p3d + 12 * c0, q.p3d, 12 * n);
@@ -116,9 +96,7 @@ static int cms_pnp_run(cms_pnp* p, cms_ctx* c, int njobs, cms_pnp_job* jobs, boo
       float* me = reinterpret_cast<float*>(h + o_maxe) + c0;
       for (size_t i = 0; i < n; ++i) me[i] = q.sigma2[i] * q.th2;      // mvMaxError[i] = mvSigma2[i]*th2 (:158), float
     }
-    unsigned long long* bw = reinterpret_cast<unsigned long long*>(h + o_bin) + g.mword0;
-    for (size_t i = 0; i < n; ++i)
-      if (q.best_mask[i]) bw[i >> 6] |= 1ull << (i & 63);
+    cms_mask_pack(q.best_mask, q.N, reinterpret_cast<unsigned long long*>(h + o_bin) + g.mword0);
   }
   rc = p->blocks.up(s, in_bytes, "cms_pnp_iterate");
   if (rc) return rc;
@@ -165,11 +143,11 @@ static int cms_pnp_run(cms_pnp* p, cms_ctx* c, int njobs, cms_pnp_job* jobs, boo
     const unsigned long long* ro = reinterpret_cast<const unsigned long long*>(h + o_rout) + g.mword0;
     q.iterations = o.iterations; q.iterations_run = o.iterations_run; q.best_inliers = o.best_inliers; q.no_more = o.no_more; q.status = o.status;
     std::memcpy(q.best_Tcw, o.best_Tcw, sizeof(q.best_Tcw));
-    for (int i = 0; i < q.N; ++i) q.best_mask[i] = (uint8_t)((bo[i >> 6] >> (i & 63)) & 1ull);
+    cms_mask_unpack(bo, q.N, q.best_mask);
     if (o.status == 1) {
       q.n_inliers = o.n_inliers;
       std::memcpy(q.Tcw, o.Tcw, sizeof(q.Tcw));
-      for (int i = 0; i < q.N; ++i) q.inliers[i] = (uint8_t)((ro[i >> 6] >> (i & 63)) & 1ull);
+      cms_mask_unpack(ro, q.N, q.inliers);
     } else if (o.status == 2) {
       q.n_inliers = q.best_inliers;
       std::memcpy(q.Tcw, q.best_Tcw, sizeof(q.Tcw));

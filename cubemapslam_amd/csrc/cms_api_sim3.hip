@@ -2,36 +2,20 @@
 // included by cms_lib.hip behind cms_api_frames.hip (cms_ctx, cms_fail, HIPCHK, CmsBlock, CmsStage) and cms_sim3_kernels.hip.  All jobs of a
 // call are ONE launch sequence on the handle's stream: one pinned block up (the handle's CmsStage), k_sim3_hypotheses, k_sim3_select, one
 // pinned block back.  Everything that becomes a device index (draws, counts, offsets) is checked on the host before anything is enqueued
-// (cms_sim3_job_check.h).
-#include <climits>
-#include <cmath>
+// (cms_sim3_job_check.h).  The handle base, the head of an entry and the staging of the draws are cms_api_ransac.h, shared with the PnP and
+// two-view entries.
 #include <cstring>
 #include <vector>
 #include "cms_sim3_job_check.h"
 
-struct cms_sim3 {
-  int device = 0, max_jobs = 0, max_corr = 0, max_hyp = 0;
-  hipStream_t stream = nullptr;
-  CmsStage blocks;      // one device block and one pinned block, grown on demand
+struct cms_sim3 : CmsRansacHandle {
+  int max_corr = 0, max_hyp = 0;
 };
-
-static void cms_sim3_free(cms_sim3* p) {
-  if (!p) return;
-  hipSetDevice(p->device);
-  p->blocks.release();
-  if (p->stream) (void)hipStreamDestroy(p->stream);
-  delete p;
-}
 
 extern "C" int cms_sim3_ransac_parameters(int N, double probability, int minInliers, int maxIterations, int* max_its) {
   if (N < 0 || !max_its) return cms_fail(CMS_ERR_ARG, "cms_sim3_ransac_parameters: bad argument");
   const float epsilon = (float)minInliers / N;
-  int nIterations;
-  if (minInliers == N) nIterations = 1;
-  else {
-    const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
-    nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : INT_MIN;      // what cvttsd2si leaves for NaN and for values no int holds
-  }
+  const int nIterations = minInliers == N ? 1 : cms_ransac_iterations(probability, epsilon);
   *max_its = std::max(1, std::min(nIterations, maxIterations));
   return CMS_OK;
 }
@@ -40,25 +24,23 @@ extern "C" int cms_sim3_create(cms_sim3** out, int device, int max_jobs, int max
   if (!out || max_jobs < 1 || max_corr_total < 1 || max_hyp_total < 1) return cms_fail(CMS_ERR_ARG, "cms_sim3_create: bad argument");
   const int rcd = cms_check_device(device, "cms_sim3_create: no HIP device (the Sim3 solver's device path has no CPU fallback)");
   if (rcd) return rcd;
-  HIPCHK(hipSetDevice(device));
   cms_sim3* p = new cms_sim3();
-  p->device = device; p->max_jobs = max_jobs; p->max_corr = max_corr_total; p->max_hyp = max_hyp_total;
-  if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess) { cms_sim3_free(p); return cms_fail(CMS_ERR_HIP, "cms_sim3_create: hipStreamCreate"); }
+  p->max_corr = max_corr_total; p->max_hyp = max_hyp_total;
+  const int rc = p->open(device, max_jobs, true, "cms_sim3_create");
+  if (rc) { cms_ransac_free(p); return rc; }
   *out = p;
   return CMS_OK;
 }
-extern "C" void cms_sim3_destroy(cms_sim3* p) { cms_sim3_free(p); }
+extern "C" void cms_sim3_destroy(cms_sim3* p) { cms_ransac_free(p); }
 
 extern "C" int cms_sim3_iterate(cms_sim3* p, cms_ctx* c, int njobs, cms_sim3_job* jobs) {
-  if (!p || !c || njobs < 0 || (njobs > 0 && !jobs)) return cms_fail(CMS_ERR_ARG, "cms_sim3_iterate: bad argument");
-  if (njobs == 0) return CMS_OK;
-  if (c->device != p->device) return cms_fail(CMS_ERR_ARG, "cms_sim3_iterate: the context and the handle must share the device");
-  if (njobs > p->max_jobs) return cms_fail(CMS_ERR_ARG, "cms_sim3_iterate: more jobs than the handle was created for");
+  int rc = cms_ransac_check_entry(p, c, njobs, jobs, "cms_sim3_iterate");
+  if (rc || njobs == 0) return rc;
   std::vector<CmsSim3JobDev> jd((size_t)njobs);
   long long corr = 0, hyp = 0, words = 0, mwords = 0;
   for (int j = 0; j < njobs; ++j) {
     int H = 0, R = 0;
-    const int rc = cms_sim3_check_job(jobs[j], &H, &R);
+    rc = cms_sim3_check_job(jobs[j], &H, &R);
     if (rc) return cms_fail(rc, "cms_sim3_iterate: bad job (null array, draw outside [0, N-1-k], fewer than 3*H draws, best_mask against best_inliers, or a parameter out of range)");
     const cms_sim3_job& q = jobs[j];
     CmsSim3JobDev& d = jd[(size_t)j];
@@ -79,7 +61,7 @@ extern "C" int cms_sim3_iterate(cms_sim3* p, cms_ctx* c, int njobs, cms_sim3_job
   const size_t o_mot = blk.take(Hn * 100), o_cnt = blk.take(Hn * 4), o_hmask = blk.take((size_t)words * 8);
   HIPCHK(hipSetDevice(p->device));
   hipStream_t s = p->stream;
-  int rc = p->blocks.reserve(s, blk.size, out_end);
+  rc = p->blocks.reserve(s, blk.size, out_end);
   if (rc) return rc;
   uint8_t* h = p->blocks.h;
   uint8_t* d = p->blocks.d;
@@ -88,16 +70,12 @@ extern "C" int cms_sim3_iterate(cms_sim3* p, cms_ctx* c, int njobs, cms_sim3_job
   for (int j = 0; j < njobs; ++j) {
     const cms_sim3_job& q = jobs[j];
     const CmsSim3JobDev& g = jd[(size_t)j];
-    int* hj = reinterpret_cast<int*>(h + o_hjob) + g.hyp0;
-    for (int k = 0; k < g.H; ++k) hj[k] = j;
-    if (g.H > 0) std::memcpy(h + o_draws + 12 * (size_t)g.hyp0, q.draws, 12 * (size_t)g.H);
+    cms_ransac_stage_draws<3>(reinterpret_cast<int*>(h + o_hjob) + g.hyp0, reinterpret_cast<int*>(h + o_draws) + 3 * (size_t)g.hyp0, j, g.H, q.draws);
     if (q.N == 0) continue;
     const size_t c0 = (size_t)g.corr0, n = (size_t)q.N;
     std::memcpy(h + o_x1 + 12 * c0, q.x3dc1, 12 * n); std::memcpy(h + o_x2 + 12 * c0, q.x3dc2, 12 * n);
     std::memcpy(h + o_me1 + 4 * c0, q.max_err1, 4 * n); std::memcpy(h + o_me2 + 4 * c0, q.max_err2, 4 * n);
-    unsigned long long* bw = reinterpret_cast<unsigned long long*>(h + o_bin) + g.mword0;
-    for (size_t i = 0; i < n; ++i)
-      if (q.best_mask[i]) bw[i >> 6] |= 1ull << (i & 63);
+    cms_mask_pack(q.best_mask, q.N, reinterpret_cast<unsigned long long*>(h + o_bin) + g.mword0);
   }
   rc = p->blocks.up(s, in_bytes, "cms_sim3_iterate");
   if (rc) return rc;
@@ -126,7 +104,7 @@ extern "C" int cms_sim3_iterate(cms_sim3* p, cms_ctx* c, int njobs, cms_sim3_job
     const unsigned long long* bo = reinterpret_cast<const unsigned long long*>(h + o_bout) + g.mword0;
     q.iterations = o.iterations; q.iterations_run = o.iterations_run; q.best_inliers = o.best_inliers; q.no_more = o.no_more; q.status = o.status;
     std::memcpy(q.best_R, o.best, 36); std::memcpy(q.best_t, o.best + 9, 12); q.best_s = o.best[12]; std::memcpy(q.best_T12, o.best + 13, 48);
-    for (int i = 0; i < q.N; ++i) q.best_mask[i] = (uint8_t)((bo[i >> 6] >> (i & 63)) & 1ull);
+    cms_mask_unpack(bo, q.N, q.best_mask);
     if (o.status == 1) {
       q.n_inliers = o.n_inliers;
       std::memcpy(q.T12, q.best_T12, sizeof(q.T12));

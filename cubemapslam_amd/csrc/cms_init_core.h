@@ -22,6 +22,7 @@
 #include <float.h>
 #include <math.h>
 #include "cms_cubemap_project.h"      // CMS_HD, track_rays_to_cubemap = CamModelGeneral::TransformRaysToCubemap
+#include "cms_ransac_core.h"          // cms_ransac_resolve_draws: the draws of one iteration
 
 #if defined(__HIPCC__)
 #define CMS_INIT_UNROLL _Pragma("unroll")
@@ -457,24 +458,8 @@ CMS_HD float cms_init_cos_from_key(unsigned k) {
 // th2 of CheckRT as ReconstructE passes it (:300): 4.0*mSigma2 in double, narrowed by the float parameter
 CMS_HD float cms_init_th2(float sigma) { return (float)(4.0 * (double)(sigma * sigma)); }
 
-// The eight draws of one iteration (:92-107): idx = avail[randi]; avail[randi] = avail.back(); pop -- without the array of N: at most eight places
-// differ from the identity.  draws[k] must lie in [0, N - 1 - k] (the callers check).
-CMS_HD void cms_init_resolve_draws(int N, const int* draws, int* idx) {
-  int pos[8], val[8];
-  CMS_INIT_UNROLL
-  for (int k = 0; k < 8; ++k) {
-    const int size = N - k, r = draws[k], last = size - 1;
-    int vr = r, vl = last;
-    CMS_INIT_UNROLL
-    for (int q = 0; q < 8; ++q) {      // later entries override earlier ones
-      if (q < k && pos[q] == r) vr = val[q];
-      if (q < k && pos[q] == last) vl = val[q];
-    }
-    idx[k] = vr;
-    pos[k] = r;
-    val[k] = vl;
-  }
-}
+// The eight draws of one iteration by the reference's swap-and-pop (cms_ransac_core.h)
+CMS_HD void cms_init_resolve_draws(int N, const int* draws, int* idx) { cms_ransac_resolve_draws<8>(N, draws, idx); }
 
 // ---- host only (plain `inline`: no device code is made of them): what the device leaves to the host.  Both the library's host side and the host
 // build of the core call these.

@@ -1,8 +1,9 @@
 // cms_init_job_check.h -- what cms_init_two_view checks per job before anything is enqueued, and the number of matches N (mvMatches12.size(),
 // Initializer.cpp:61-75).  Host code, shared by the C-ABI entry (cms_api_init.hip) and the host loop (host/init_host.cpp), so both refuse the same
-// records.  Needs cms_init_job (include/cubemapslam_hip.h) before it.
+// records.  The draw rule is that of the PnP and Sim3 checks (cms_ransac_job_check.h).  Needs cms_init_job (include/cubemapslam_hip.h) before it.
 #ifndef CMS_INIT_JOB_CHECK_H
 #define CMS_INIT_JOB_CHECK_H
+#include "cms_ransac_job_check.h"
 // frames: frame 2 comes from a resident frame row (cms_init_two_view_frames): keys2 / rays2 are not read
 static inline int cms_init_check_job(const cms_init_job& q, int* N_out, bool frames = false) {
   if (q.n1 < 1 || q.n2 < 1 || q.iterations < 1 || q.iterations > (1 << 20) || q.n_draws < 0) return CMS_ERR_ARG;
@@ -15,11 +16,7 @@ static inline int cms_init_check_job(const cms_init_job& q, int* N_out, bool fra
   }
   *N_out = N;
   if (N < 8) return CMS_ERR_ARG;      // the reference pops from an empty vAvailableIndices; Tracking never gets here below 100 matches
-  if ((long long)q.n_draws < 8LL * q.iterations) return CMS_ERR_ARG;
-  for (int i = 0; i < q.iterations; ++i)
-    for (int k = 0; k < 8; ++k)
-      if (q.draws[8 * i + k] < 0 || q.draws[8 * i + k] > N - 1 - k) return CMS_ERR_ARG;
-  return CMS_OK;
+  return cms_ransac_check_draws(q.draws, q.n_draws, q.iterations, 8, N);
 }
 
 // What is left of ReconstructE (:305-375) once the four CheckRT passes are done, for both callers: the decision of cms_init_core.h on nGood[4] and the

@@ -22,6 +22,7 @@
 #include <float.h>
 #include <math.h>
 #include "cms_cubemap_project.h"      // CMS_HD, track_rays_to_cubemap = CamModelGeneral::TransformRaysToCubemap
+#include "cms_ransac_core.h"          // cms_ransac_resolve_draws: the draws of one iteration
 
 // What compute_pose leaves behind for a caller that wants to see the stages (the CPU tests); the kernels pass NULL.
 struct CmsPnpStages {
@@ -565,21 +566,7 @@ CMS_HD bool cms_pnp_is_inlier(int F, const double* R, const double* t, const flo
   return error2 < max_error;
 }
 
-// The four draws of one iteration (:190-204): idx = avail[randi]; avail[randi] = avail.back(); pop -- without the array of N: at most four
-// places differ from the identity.  draws[k] must lie in [0, N - 1 - k] (the callers check).
-CMS_HD void cms_pnp_resolve_draws(int N, const int* draws, int* idx) {
-  int pos[4], val[4];
-  for (int k = 0; k < 4; ++k) {
-    const int size = N - k, r = draws[k], last = size - 1;
-    int vr = r, vl = last;
-    for (int q = 0; q < k; ++q) {      // later entries override earlier ones
-      if (pos[q] == r) vr = val[q];
-      if (pos[q] == last) vl = val[q];
-    }
-    idx[k] = vr;
-    pos[k] = r;
-    val[k] = vl;
-  }
-}
+// The four draws of one iteration by the reference's swap-and-pop (cms_ransac_core.h)
+CMS_HD void cms_pnp_resolve_draws(int N, const int* draws, int* idx) { cms_ransac_resolve_draws<4>(N, draws, idx); }
 
 #endif

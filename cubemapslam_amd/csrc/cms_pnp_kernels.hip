@@ -5,7 +5,7 @@
 //                      the four points, R | t stored as doubles.  32 lanes per workgroup; MtM and the eigenvector matrix (2 x 144 doubles per
 //                      lane) live in LDS, 289 doubles apart so that the lanes of a workgroup fall on different banks
 //   k_pnp_inliers      one wavefront per (job, hypothesis): CheckInliers, lanes stride over the correspondences, the 64-bit ballot is the mask
-//                      word, the count is the sum of the popcounts
+//                      word, the count is the sum of the popcounts (cms_ransac_mask_sweep of cms_ransac_core.h, as in the Refine below)
 //   k_pnp_select       one workgroup per job replays the loop over its hypotheses in order: best on >, Refine on the best mask (recomputed only
 //                      when the best changed since the last failed Refine -- it is a function of the mask alone), accepted on > min_inliers.  The
 //                      EPnP over the best inliers is the scalar core run by the first lane on the job's scratch rows, CheckInliers behind it runs
@@ -107,18 +107,10 @@ extern "C" __global__ void __launch_bounds__(64) k_pnp_inliers(CmsPnpArgs a) {
   for (int k = 0; k < 9; ++k) R[k] = rt[k];
   for (int k = 0; k < 3; ++k) t[k] = rt[9 + k];
   unsigned long long* mask = a.hyp_mask + J.word0 + (long long)(g - J.hyp0) * J.words;
-  int count = 0;
-  for (int w = 0; w < J.words; ++w) {
-    const int i = w * 64 + lane;
-    bool in = false;
-    if (i < J.N) {
-      const size_t c = (size_t)J.corr0 + (size_t)i;
-      in = cms_pnp_is_inlier(a.F, R, t, a.p3d + 3 * c, a.p2d + 2 * c, a.max_error[c]);
-    }
-    const unsigned long long m = __ballot(in);
-    if (lane == 0) mask[w] = m;
-    count += __popcll(m);
-  }
+  const int count = cms_ransac_mask_sweep(J.N, J.words, 0, 1, lane, mask, [&](int i) {
+    const size_t c = (size_t)J.corr0 + (size_t)i;
+    return cms_pnp_is_inlier(a.F, R, t, a.p3d + 3 * c, a.p2d + 2 * c, a.max_error[c]);
+  });
   if (lane == 0) a.hyp_count[g] = count;
 }
 
@@ -182,18 +174,10 @@ extern "C" __global__ void __launch_bounds__(CMS_PNP_SELECT_THREADS) k_pnp_selec
       double R[9], t[3];
       for (int k = 0; k < 9; ++k) R[k] = s_R[k];
       for (int k = 0; k < 3; ++k) t[k] = s_t[k];
-      int count = 0;
-      for (int w = wave; w < J.words; w += CMS_PNP_SELECT_THREADS / 64) {
-        const int i = w * 64 + lane;
-        bool in = false;
-        if (i < J.N) {
-          const size_t c = (size_t)J.corr0 + (size_t)i;
-          in = cms_pnp_is_inlier(a.F, R, t, a.p3d + 3 * c, a.p2d + 2 * c, a.max_error[c]);
-        }
-        const unsigned long long m = __ballot(in);
-        if (lane == 0) refined_out[w] = m;
-        count += __popcll(m);
-      }
+      const int count = cms_ransac_mask_sweep(J.N, J.words, wave, CMS_PNP_SELECT_THREADS / 64, lane, refined_out, [&](int i) {
+        const size_t c = (size_t)J.corr0 + (size_t)i;
+        return cms_pnp_is_inlier(a.F, R, t, a.p3d + 3 * c, a.p2d + 2 * c, a.max_error[c]);
+      });
       if (lane == 0 && count) atomicAdd(&s_count, count);
     }
     __syncthreads();

@@ -27,6 +27,7 @@
 #include <float.h>
 #include <math.h>
 #include "cms_cubemap_project.h"      // CMS_HD, track_rays_to_cubemap = CamModelGeneral::TransformRaysToCubemap
+#include "cms_ransac_core.h"          // cms_ransac_resolve_draws: the draws of one iteration
 
 #define CMS_SIM3_SWEEPS 16
 
@@ -207,21 +208,7 @@ CMS_HD bool cms_sim3_is_inlier(int F, const float* T12, const float* T21, const 
   return err1 < max_err1 && err2 < max_err2;
 }
 
-// The three draws of one iteration (:190-201): idx = avail[randi]; avail[randi] = avail.back(); pop -- without the array of N: at most three
-// places differ from the identity.  draws[k] must lie in [0, N - 1 - k] (the callers check).
-CMS_HD void cms_sim3_resolve_draws(int N, const int* draws, int* idx) {
-  int pos[3], val[3];
-  for (int k = 0; k < 3; ++k) {
-    const int size = N - k, r = draws[k], last = size - 1;
-    int vr = r, vl = last;
-    for (int q = 0; q < k; ++q) {      // later entries override earlier ones
-      if (pos[q] == r) vr = val[q];
-      if (pos[q] == last) vl = val[q];
-    }
-    idx[k] = vr;
-    pos[k] = r;
-    val[k] = vl;
-  }
-}
+// The three draws of one iteration by the reference's swap-and-pop (cms_ransac_core.h)
+CMS_HD void cms_sim3_resolve_draws(int N, const int* draws, int* idx) { cms_ransac_resolve_draws<3>(N, draws, idx); }
 
 #endif

@@ -4,7 +4,8 @@
 //                      compute_sim3 of cms_sim3_core.h on the three pairs: the solve is a few dozen floats of state and no memory, the lanes
 //                      do the same operations on the same values, so the wavefront holds T12 / T21 in registers without a second launch or a
 //                      round trip through memory (lane 0 stores R, t, s, T12 for the replay).  Then CheckInliers: lanes stride over the
-//                      correspondences, the 64-bit ballot is the mask word, the count is the sum of the popcounts
+//                      correspondences, the 64-bit ballot is the mask word, the count is the sum of the popcounts (cms_ransac_mask_sweep of
+//                      cms_ransac_core.h)
 //   k_sim3_select      one wavefront per job replays the loop over its hypotheses in order.  There is no Refine, so the replay is a prefix
 //                      maximum over the counts in chunks of 64, seeded with the carried-in best: hypothesis h replaces the best when
 //                      count[h] >= the maximum before it, and the call ends at the first such h with count[h] > min_inliers
@@ -65,18 +66,10 @@ extern "C" __global__ void __launch_bounds__(64) k_sim3_hypotheses(CmsSim3Args a
     for (int k = 0; k < 12; ++k) o[13 + k] = m.T12[k];
   }
   unsigned long long* mask = a.hyp_mask + J.word0 + (long long)(g - J.hyp0) * J.words;
-  int count = 0;
-  for (int w = 0; w < J.words; ++w) {
-    const int i = w * 64 + lane;
-    bool in = false;
-    if (i < J.N) {
-      const size_t c = (size_t)J.corr0 + (size_t)i;
-      in = cms_sim3_is_inlier(a.F, m.T12, m.T21, a.x1 + 3 * c, a.x2 + 3 * c, a.me1[c], a.me2[c]);
-    }
-    const unsigned long long b = __ballot(in);
-    if (lane == 0) mask[w] = b;
-    count += __popcll(b);
-  }
+  const int count = cms_ransac_mask_sweep(J.N, J.words, 0, 1, lane, mask, [&](int i) {
+    const size_t c = (size_t)J.corr0 + (size_t)i;
+    return cms_sim3_is_inlier(a.F, m.T12, m.T21, a.x1 + 3 * c, a.x2 + 3 * c, a.me1[c], a.me2[c]);
+  });
   if (lane == 0) a.hyp_count[g] = count;
 }
 

@@ -1,14 +1,12 @@
 """ctypes access to the host build of the Initializer core (libcubemapslam_host.so: cubemapslam_amd/host/init_host.cpp) for the Initializer tests."""
 import ctypes as C
-import os
 
 import numpy as np
 
 from cubemapslam_amd import api
+from hostlib import load, p
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _H = None
-p = lambda a: a.ctypes.data_as(C.c_void_p)
 f32 = lambda a: np.ascontiguousarray(a, np.float32)
 
 
@@ -21,7 +19,7 @@ class Stages(C.Structure):
 def H():
     global _H
     if _H is None:
-        _H = C.CDLL(os.path.join(ROOT, "cubemapslam_amd", "lib", "libcubemapslam_host.so"))
+        _H = load()
         _H.hm_init_cos_fov.argtypes = [C.c_double]; _H.hm_init_cos_fov.restype = C.c_float
         _H.hm_init_two_view_host.argtypes = [C.c_int, C.c_float, C.c_int, C.c_void_p]
         _H.hm_init_compute_e21.argtypes = [C.c_void_p] * 4

@@ -1,21 +1,19 @@
 """ctypes access to the host build of the key-frame database core (libcubemapslam_host.so: csrc/cms_kfdb_core.h through host_capi.cpp's hm_kfdb_*
 functions) for the key-frame database tests.  HostDatabase is a backend of kfdb_cases.run."""
 import ctypes as C
-import os
 
 import numpy as np
 
 from cubemapslam_amd import api
+from hostlib import load, p
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _H = None
-p = lambda a: a.ctypes.data_as(C.c_void_p)
 
 
 def H():
     global _H
     if _H is None:
-        _H = C.CDLL(os.path.join(ROOT, "cubemapslam_amd", "lib", "libcubemapslam_host.so"))
+        _H = load()
         _H.hm_kfdb_create.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _H.hm_kfdb_destroy.argtypes = [C.c_void_p]; _H.hm_kfdb_destroy.restype = None
         _H.hm_kfdb_set_bow.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -27,7 +25,6 @@ def H():
         _H.hm_kfdb_detect.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
         _H.hm_kfdb_bow_score.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _H.hm_kfdb_score.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _H.hm_last_error.restype = C.c_char_p
         _H.hm_kfdb_mirror.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 5
     return _H
 

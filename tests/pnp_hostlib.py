@@ -1,14 +1,12 @@
 """ctypes access to the host build of the PnP core (libcubemapslam_host.so: cubemapslam_amd/host/pnp_host.cpp) for the PnP tests."""
 import ctypes as C
-import os
 
 import numpy as np
 
 from cubemapslam_amd import api
+from hostlib import load, p
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _H = None
-p = lambda a: a.ctypes.data_as(C.c_void_p)
 
 
 class Stages(C.Structure):
@@ -21,7 +19,7 @@ class Stages(C.Structure):
 def H():
     global _H
     if _H is None:
-        _H = C.CDLL(os.path.join(ROOT, "cubemapslam_amd", "lib", "libcubemapslam_host.so"))
+        _H = load()
         _H.hm_pnp_iterate_host.argtypes = [C.c_int, C.c_int, C.c_void_p]
         _H.hm_pnp_compute_pose.argtypes = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
         _H.hm_pnp_check_inliers.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6

@@ -1,14 +1,12 @@
 """ctypes access to the host build of the Sim3 core (libcubemapslam_host.so: cubemapslam_amd/host/sim3_host.cpp) for the Sim3 tests."""
 import ctypes as C
-import os
 
 import numpy as np
 
 from cubemapslam_amd import api
+from hostlib import load, p
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _H = None
-p = lambda a: a.ctypes.data_as(C.c_void_p)
 
 
 class Stages(C.Structure):
@@ -26,7 +24,7 @@ class Motion(C.Structure):
 def H():
     global _H
     if _H is None:
-        _H = C.CDLL(os.path.join(ROOT, "cubemapslam_amd", "lib", "libcubemapslam_host.so"))
+        _H = load()
         _H.hm_sim3_iterate_host.argtypes = [C.c_int, C.c_int, C.c_void_p]
         _H.hm_sim3_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _H.hm_sim3_compute.restype = None

@@ -100,6 +100,28 @@ def test_hand_built_loop_cases(ctx, solver):
     assert want[0]["best_inliers"] == 13 and want[0]["status"] == 2 and np.array_equal(want[0]["best_mask"], bad_mask)
 
 
+def test_inlier_sweep_word_counts(ctx, solver):
+    """The inlier sweep (cms_ransac_mask_sweep) in k_pnp_inliers and in the Refine of k_pnp_select, whose four waves take the words w, w + 4, ...:
+    1, 1, 2, 3 and 5 mask words in one call (N = 63, 64, 65, 129, 257), exact correspondences plus far outliers, 6 to 10 hypotheses per job.  The
+    seeds were chosen with the host loop alone so that Refine is reached, accepted and refused."""
+    sizes = (63, 64, 65, 129, 257)
+
+    def make():
+        out = []
+        for seed0 in (209, 208):
+            for j, N in enumerate(sizes):
+                pr = pc.exact_problem(seed0 + j, N - N // 5, N // 5)
+                pr.update(min_inliers=N // 2, max_its=6 + j)
+                out.append(api.pnp_job_state(pr, 5, pc.draws(seed0 + 100 + j, N, 6 + j)))
+        return out
+    want, got = both(ctx, solver, make)
+    st = [w["status"] for w in want]
+    # Refine accepted on 2 and 3 words and on 5 (more words than waves); refused on the best of all 10 hypotheses of the first 257 (status 2)
+    assert st[2] == 1 and st[3] == 1 and st[9] == 1 and st[4] == 2 and want[4]["iterations_run"] == 10, st
+    assert want[0]["status"] == 1 and want[0]["n_inliers"] > want[0]["best_inliers"]      # the refined mask is not the best mask
+    same(want, got)
+
+
 def test_two_calls_equal_one(ctx, solver):
     sizes = [60, 130]
     mk = noisy_states(sizes, 90, its=24)

@@ -94,6 +94,22 @@ def test_hand_built_loop_cases(ctx, solver):
     assert [w["status"] for w in want] == [0, 0, 1, 0, 1] and want[1]["best_inliers"] == n_in and want[3]["best_inliers"] == 13 and np.array_equal(got[3]["best_mask"], mask)
 
 
+def test_inlier_sweep_word_counts(ctx, solver):
+    """The inlier sweep (cms_ransac_mask_sweep) in k_sim3_hypotheses: 1, 1, 2, 3 and 5 mask words in one call (N = 63, 64, 65, 129, 257), exact
+    correspondences plus far outliers, 6 to 10 hypotheses per job; hypotheses with an outlier among the three pairs come before the accepted one"""
+    def make():
+        out = []
+        for j, N in enumerate((63, 64, 65, 129, 257)):
+            pr = sc.exact_problem(206 + j, N - N // 5, N // 5)
+            pr.update(min_inliers=N // 2, max_its=6 + j)
+            out.append(api.sim3_job_state(pr, 6 + j, sc.draws(306 + j, N, 6 + j)))
+        return out
+    want, got = both(ctx, solver, make)
+    assert [w["status"] for w in want] == [1] * 5 and [w["iterations_run"] for w in want] == [3, 2, 1, 4, 2]
+    assert [w["n_inliers"] for w in want] == [N - N // 5 for N in (63, 64, 65, 129, 257)]
+    same(want, got)
+
+
 def test_two_calls_equal_one(ctx, solver):
     def base():
         return [state(90, 25, 40, outliers=0.3, max_its=40), state(91, 130, 40, min_inliers=129, max_its=40)]      # nothing is ever accepted: the state is carried

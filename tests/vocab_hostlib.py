@@ -1,13 +1,12 @@
 """ctypes access to the host side of ComputeBoW (libcubemapslam_host.so: the ORBVocabulary mirror class, the text format of io_formats.h and the host
 build of csrc/cms_vocab_core.h through host_capi.cpp's hm_vocab_* functions) for the vocabulary tests."""
 import ctypes as C
-import os
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from hostlib import load, p
+
 _H = None
-p = lambda a: a.ctypes.data_as(C.c_void_p)
 DEVICE, HOST_CORE = 0, 1
 
 
@@ -18,8 +17,7 @@ class VocabError(RuntimeError):
 def H():
     global _H
     if _H is None:
-        _H = C.CDLL(os.path.join(ROOT, "cubemapslam_amd", "lib", "libcubemapslam_host.so"))
-        _H.hm_last_error.restype = C.c_char_p
+        _H = load()
         _H.hm_vocab_create.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4
         _H.hm_vocab_load.argtypes = [C.c_void_p, C.c_char_p]
         _H.hm_vocab_save.argtypes = [C.c_void_p, C.c_char_p]
