@@ -633,6 +633,11 @@ class BowJob(C.Structure):
                 ("node_feat", C.c_void_p), ("kf_skip", C.c_void_p)]
 
 
+class BowKfJob(C.Structure):
+    """cms_bow_kf_job (include/cubemapslam_hip.h)"""
+    _fields_ = [("slot1", C.c_int), ("n1", C.c_int), ("slot2", C.c_int), ("n2", C.c_int), ("skip1", C.c_void_p), ("skip2", C.c_void_p)]
+
+
 class KfProjJob(C.Structure):
     """cms_kfproj_job (include/cubemapslam_hip.h)"""
     _fields_ = [("slot", C.c_int), ("b", C.c_int), ("n", C.c_int), ("pose12", C.c_float * 12), ("nmp", C.c_int), ("kf_feat", C.c_void_p), ("pos", C.c_void_p),
@@ -918,6 +923,26 @@ class KeyframeStore(_Handle):
         L.cms_kfstore_search_by_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
         _chk(L.cms_kfstore_search_by_bow(self.h, src_ctx.h, len(jobs), arr, float(nnratio), int(check_orientation), _p(kf_idx), _p(nm)), "cms_kfstore_search_by_bow")
         return [(kf_idx[off[j]:off[j + 1]].copy(), int(nm[j])) for j in range(len(jobs))]
+
+    def search_by_bow_keyframes(self, src_ctx, jobs, nnratio=0.75, check_orientation=True):
+        """cms_kfstore_search_by_bow_keyframes: ORBMatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (LoopClosing::ComputeSim3) for many pairs of resident key
+        frames in ONE launch on src_ctx's stream.  jobs: list of (slot1, n1, slot2, n2, skip1, skip2): the slots with their stored key-point counts,
+        skip None or one byte per feature of the slot's key frame (!= 0: the map point is bad).  Returns per job (idx2 int32[n1]: the key-frame-2
+        feature whose map point key point i of key frame 1 receives, or -1; n_matches)."""
+        arr = (BowKfJob * max(len(jobs), 1))()
+        keep = []
+        for q, (slot1, n1, slot2, n2, skip1, skip2) in zip(arr, jobs):
+            sk = [None if v is None else np.ascontiguousarray(v, np.uint8) for v in (skip1, skip2)]
+            keep.append(sk)
+            q.slot1 = slot1; q.n1 = n1; q.slot2 = slot2; q.n2 = n2
+            q.skip1 = None if sk[0] is None else sk[0].ctypes.data; q.skip2 = None if sk[1] is None else sk[1].ctypes.data
+        off = np.concatenate([[0], np.cumsum([max(int(j[1]), 0) for j in jobs])]).astype(np.int64)
+        idx2 = np.full(max(int(off[-1]), 1), -1, np.int32); nm = np.zeros(max(len(jobs), 1), np.int32)
+        L = lib()
+        L.cms_kfstore_search_by_bow_keyframes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+        _chk(L.cms_kfstore_search_by_bow_keyframes(self.h, src_ctx.h, len(jobs), arr, float(nnratio), int(check_orientation), _p(idx2), _p(nm)),
+             "cms_kfstore_search_by_bow_keyframes")
+        return [(idx2[off[j]:off[j + 1]].copy(), int(nm[j])) for j in range(len(jobs))]
 
     def compute_bow(self, vocab, slots, levelsup=4):
         """cms_kfstore_compute_bow: KeyFrame::ComputeBoW on the resident descriptors of `slots`; the FeatureVector goes into the slots' layout, the

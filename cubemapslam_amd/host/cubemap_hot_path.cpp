@@ -54,6 +54,7 @@ static std::mutex g_ctx_mutex;
 static cms_ctx* g_ctx = nullptr;
 static const int kSharedDevice = 0;      // the device of the shared context (and of what works with it: ORBVocabulary's device handle)
 static cms_orb_params g_ctx_orb{};
+static cms_kfstore* g_bow_kf_store = nullptr;      // ORBMatcher::SearchByBoW(pKF1, pKF2, ...): two slots on the shared context, made by the first call
 static cms_camera g_ctx_cam{};      // the camera the shared context was built for (SetCamParams zero-fills the record first: comparable byte for byte)
 cms_ctx* SharedContext(int nfeatures, float scaleFactor, int nlevels, int iniThFAST, int minThFAST) {
   std::lock_guard<std::mutex> lock(g_ctx_mutex);
@@ -62,6 +63,7 @@ cms_ctx* SharedContext(int nfeatures, float scaleFactor, int nlevels, int iniThF
   // the context belongs to (camera, extractor parameters): a process that configures the camera singleton again (another sequence, another face
   // size) gets a new one -- until round 6 only the extractor parameters were compared, and the mirror kept searching with the OLD camera's LUT and grid
   if (g_ctx && std::memcmp(&orb, &g_ctx_orb, sizeof(orb)) == 0 && std::memcmp(&g_ctx_cam, &CamModelGeneral::GetCamera()->params(), sizeof(cms_camera)) == 0) return g_ctx;
+  if (g_bow_kf_store) { cms_kfstore_destroy(g_bow_kf_store); g_bow_kf_store = nullptr; }      // (it lives on the context that goes)
   if (g_ctx) { cms_ctx_destroy(g_ctx); g_ctx = nullptr; }
   const int rc = cms_ctx_create(&g_ctx, kSharedDevice, &CamModelGeneral::GetCamera()->params(), &orb, 1);
   if (rc != CMS_OK) throw std::runtime_error(std::string("cms_ctx_create: ") + cms_last_error());
@@ -426,6 +428,43 @@ int ORBMatcher::SearchByBoW(const KeyFrameView& pKF, FrameView& F, std::vector<l
     if (rc != CMS_OK) throw std::runtime_error(std::string("cms_search_by_bow: ") + cms_last_error());
   }
   for (int i = 0; i < N; ++i) if (kf_idx[i] >= 0) vpMapPointMatches[i] = pKF.mvpMapPoints[kf_idx[i]];
+  return nm;
+}
+
+int ORBMatcher::SearchByBoW(const KeyFrameView& pKF1, const KeyFrameView& pKF2, std::vector<long>& vpMatches12) {
+  const int N1 = (int)pKF1.mvKeys.size(), N2 = (int)pKF2.mvKeys.size();
+  vpMatches12.assign(N1, -1);
+  if (N1 == 0 || N2 == 0) return 0;
+  cms_ctx* ctx = SharedContext(g_ctx_orb.nfeatures, g_ctx_orb.scale_factor, g_ctx_orb.nlevels, g_ctx_orb.ini_th_fast, g_ctx_orb.min_th_fast);
+  // a view as cms_keyframe (key points, descriptors, map-point slots, mFeatVec; the search reads neither rays nor pose) and its skip flags
+  struct Side { KfPack p; std::vector<uint8_t> skip; cms_keyframe k; };
+  auto pack = [](const KeyFrameView& kf, Side& s) {
+    const int N = (int)kf.mvKeys.size();
+    KeyFrameView v;
+    v.mvKeys = kf.mvKeys; v.mDescriptors = kf.mDescriptors; v.mvpMapPoints = kf.mvpMapPoints; v.mFeatVec = kf.mFeatVec;
+    v.mvKeyRays.assign(N, cv::Vec3f());
+    float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    v.Tcw = cv::Mat(4, 4, cv::CV_32F, eye, 16);
+    s.k = pack_keyframe(v, s.p);
+    s.skip.assign(N + 1, 0);
+    for (int i = 0; i < N && i < (int)kf.mvbMapPointBad.size(); ++i) s.skip[i] = kf.mvbMapPointBad[i];
+  };
+  Side s1, s2;
+  pack(pKF1, s1); pack(pKF2, s2);
+  std::vector<int> idx2(N1, -1);
+  int nm = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!g_bow_kf_store && cms_kfstore_create(&g_bow_kf_store, ctx, 2, 4096, 4096) != CMS_OK)
+      throw std::runtime_error(std::string("cms_kfstore_create: ") + cms_last_error());
+    cms_bow_kf_job q;
+    q.slot1 = 0; q.n1 = N1; q.slot2 = 1; q.n2 = N2; q.skip1 = s1.skip.data(); q.skip2 = s2.skip.data();
+    int rc = cms_kfstore_put(g_bow_kf_store, 0, &s1.k);
+    if (rc == CMS_OK) rc = cms_kfstore_put(g_bow_kf_store, 1, &s2.k);
+    if (rc == CMS_OK) rc = cms_kfstore_search_by_bow_keyframes(g_bow_kf_store, ctx, 1, &q, mfNNratio, mbCheckOrientation ? 1 : 0, idx2.data(), &nm);
+    if (rc != CMS_OK) throw std::runtime_error(std::string("cms_kfstore_search_by_bow_keyframes: ") + cms_last_error());
+  }
+  for (int i = 0; i < N1; ++i) if (idx2[i] >= 0) vpMatches12[i] = pKF2.mvpMapPoints[idx2[i]];
   return nm;
 }
 

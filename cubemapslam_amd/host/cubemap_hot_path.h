@@ -190,6 +190,11 @@ class ORBMatcher {
   // node, best / second best with mfNNratio, a frame feature taken once, rotation histogram.  vpMapPointMatches[i] = id of the map point frame key
   // point i receives, or -1; returns nmatches.  (cms_search_by_bow: F's key points and descriptors go to the device first)
   int SearchByBoW(const KeyFrameView& pKF, FrameView& F, std::vector<long>& vpMapPointMatches);
+  // ORBMatcher.cpp:541-674, LoopClosing.cpp:264: features of pKF1 with a map point that is not bad against pKF2's features of the same vocabulary
+  // node that hold one too and are not taken yet, best < TH_LOW (strict) and the mfNNratio test, rotation histogram.  vpMatches12[i] = id of pKF2's
+  // map point key point i of pKF1 receives, or -1; returns nmatches.  (cms_kfstore_search_by_bow_keyframes: both views go into a small store of the
+  // shared context first; the device path only, as everywhere in the mirror)
+  int SearchByBoW(const KeyFrameView& pKF1, const KeyFrameView& pKF2, std::vector<long>& vpMatches12);
   // ORBMatcher.cpp:253-378, Tracking.cpp:1101 / :1115 (Relocalization's guided search): the map points of pKF that are not bad and not in
   // sAlreadyFound (ids), in key-point order (:268-276), projected with CurrentFrame.mTcw; windows th * scale[predicted level] over level +-1, key
   // points that hold a map point skipped, best Hamming <= ORBdist, rotation histogram with pKF's key-point angles.  Reads pKF.mvMapPoints for the

@@ -260,6 +260,36 @@ extern "C" int hm_search_by_bow(int nk, const cms_keypoint* kk, const uint8_t* k
     for (int i = 0; i < n; ++i) out_mp[i] = m[i];
     return nm;)
 }
+// ORBMatcher::SearchByBoW(pKF1, pKF2, vpMatches12) through the mirror: two key frames (n features, map-point ids mp (-1 = none), bad flags or NULL,
+// FeatureVector as CSR); out_mp[n1] = the id of key frame 2's matched map point or -1
+extern "C" int hm_search_by_bow_keyframes(int n1, const cms_keypoint* k1, const uint8_t* d1, const long* mp1, const uint8_t* bad1, int nodes1, const int* nid1,
+                                          const int* noff1, const int* nfeat1, int n2, const cms_keypoint* k2, const uint8_t* d2, const long* mp2,
+                                          const uint8_t* bad2, int nodes2, const int* nid2, const int* noff2, const int* nfeat2, float nnratio, int check_ori,
+                                          long* out_mp) {
+  HM_TRY(
+    auto view = [](KeyFrameView& kf, int n, const cms_keypoint* k, const uint8_t* desc, const long* mp, const uint8_t* bad, int nn, const int* nid, const int* noff,
+                   const int* nfeat) {
+      kf.mvKeys.resize(n);
+      kf.mDescriptors.create(n > 0 ? n : 1, 32, cv::CV_8U);
+      for (int i = 0; i < n; ++i) {
+        kf.mvKeys[i].pt = cv::Point2f(k[i].x, k[i].y); kf.mvKeys[i].angle = k[i].angle; kf.mvKeys[i].octave = k[i].octave; kf.mvKeys[i].size = k[i].size;
+        kf.mvKeys[i].response = k[i].response;
+        std::memcpy(kf.mDescriptors.ptr<uint8_t>(i), desc + (size_t)i * 32, 32);
+      }
+      kf.mvpMapPoints.assign(mp, mp + n);
+      if (bad) kf.mvbMapPointBad.assign(bad, bad + n);
+      for (int e = 0; e < nn; ++e) kf.mFeatVec.emplace_back((unsigned)nid[e], std::vector<unsigned>(nfeat + noff[e], nfeat + noff[e + 1]));
+    };
+    KeyFrameView kf1;
+    KeyFrameView kf2;
+    view(kf1, n1, k1, d1, mp1, bad1, nodes1, nid1, noff1, nfeat1);
+    view(kf2, n2, k2, d2, mp2, bad2, nodes2, nid2, noff2, nfeat2);
+    std::vector<long> m;
+    ORBMatcher matcher(nnratio, check_ori != 0);
+    const int nm = matcher.SearchByBoW(kf1, kf2, m);
+    for (int i = 0; i < n1; ++i) out_mp[i] = m[i];
+    return nm;)
+}
 // ORBMatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) through the mirror: the key frame (nk key points, map-point ids mp
 // (-1 = none), bad flags or NULL, and per key point the map point's position / mfMinDistance / mfMaxDistance / descriptor), sAlreadyFound as nfound
 // ids, the frame (n key points, frame_mp[n] = mvpMapPoints as ids, in/out) and its pose Tcw (16 floats, row major)

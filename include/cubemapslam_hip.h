@@ -513,6 +513,34 @@ typedef struct {
 int cms_kfstore_search_by_bow(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_job* jobs, float nnratio,
                               int check_orientation, int* kf_idx /* sum of jobs[j].n, job after job */, int* n_matches /* njobs */);
 
+/* ---- ORBMatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (include/ORBMatcher.h:68, src/ORBMatcher.cpp:541-674),
+ * the matcher of LoopClosing::ComputeSim3 (LoopClosing.cpp:251-279, ORBMatcher(0.75, true), once per loop candidate), between cms_kfdb_detect and
+ * cms_sim3_iterate, on resident key frames: all candidates of a pass in ONE launch.  A contract of its own, not cms_kfstore_search_by_bow with other
+ * parameters: only vocabulary nodes present in both FeatureVectors take part, in ascending id order; per common node key frame 1's features with a
+ * map point (the slot's mp >= 0) that is not bad (skip1) are taken in list order, each against the node's key-frame-2 features that are not taken
+ * yet (vbMatched2), hold a map point and are not bad (skip2) -- a feature filtered this way is neither best nor second best; best < second best,
+ * both from 256, the first minimum in list order wins; accepted when best < TH_LOW (50, strict) and (float)best < nnratio * (float)second (one float
+ * multiply); then the rotation histogram over angle1 - angle2 when check_orientation (HISTO_LENGTH 12, ComputeThreeMaxima).  idx2[i] (one per key
+ * point of key frame 1) = the key-frame-2 feature whose map point it receives, or -1: the caller maps it to its MapPoint*.  *n_matches = nmatches
+ * after the histogram.  Malformed FeatureVectors (the store accepts any CSR): an entry of a node's list takes part only if that node is the one the
+ * slot's feat_node records for the feature (the last entry that lists it), and a feature of key frame 1 that holds a match is not matched again.
+ * For every FeatureVector DBoW2 produces this changes nothing; for one that lists a feature twice the result is defined by the store's contents.
+ * Runs on src's stream -- the loop-closing thread's -- and enqueues nothing on the store's: src's stream waits on the device for the copies of
+ * cms_kfstore_put_from_frame(s) that filled the named slots.  Synchronous: the caller decides on nmatches < 20 at once.  One copy up (skip flags, job
+ * records), one launch, one copy back.  Checked before anything is enqueued, CMS_ERR_ARG with the reason in cms_last_error: a slot out of range or not
+ * filled, n1 / n2 that is not the slot's stored key-point count, a context on another device than the store's.  njobs == 0 is CMS_OK with no launch;
+ * slot1 == slot2 is allowed (the search only reads the store); a slot without nodes gives zero matches.  Threading as cms_kfstore_search_by_bow: no
+ * concurrent call refills, updates or releases a slot that the search names. */
+typedef struct {
+  int slot1, n1;            /* mpCurrentKF: store slot and its stored key-point count */
+  int slot2, n2;            /* the candidate */
+  const uint8_t* skip1;     /* NULL, or n1 bytes: != 0 <=> pMP->isBad() */
+  const uint8_t* skip2;     /* NULL, or n2 bytes */
+} cms_bow_kf_job;
+int cms_kfstore_search_by_bow_keyframes(cms_kfstore* st, cms_ctx* src, int njobs, const cms_bow_kf_job* jobs,
+                                        float nnratio, int check_orientation,
+                                        int* idx2 /* sum of n1, job after job */, int* n_matches /* njobs */);
+
 /* ---- Frame::ComputeBoW (src/Frame.cpp:719-726; Tracking.cpp:570, :993) and KeyFrame::ComputeBoW (src/KeyFrame.cpp:94-103; LocalMapping.cpp:142,
  * Tracking.cpp:472-473): mpORBvocabulary->transform(descriptors, mBowVec, mFeatVec, 4) (DBoW2 TemplatedVocabulary.h:1127-1259) on the device, so that
  * SearchByBoW and CreateNewMapPoints take the FeatureVector from where the descriptors already are.  The numeric definition is csrc/cms_vocab_core.h

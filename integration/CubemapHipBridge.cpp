@@ -564,6 +564,60 @@ int SearchByBoW(cms_kfstore* store, cms_ctx* frameCtx, KeyFrame* pKF, Frame& F, 
   return n[0];
 }
 
+// ------------------------------------------------------------------------------------------------ LoopClosing::ComputeSim3: SearchByBoW on resident key frames
+void SearchByBoWLoopCandidates(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pCurrentKF, const std::vector<KeyFrame*>& vpCandidateKFs,
+                               std::vector<std::vector<MapPoint*> >& vvpMapPointMatches, std::vector<bool>& vbDiscarded, std::vector<int>& nmatches,
+                               float nnratio, bool checkOri) {
+  StoreBook& b = book(store);
+  const size_t nKFs = vpCandidateKFs.size();
+  vvpMapPointMatches.assign(nKFs, std::vector<MapPoint*>());
+  vbDiscarded.assign(nKFs, false);
+  nmatches.assign(nKFs, 0);
+  const std::vector<MapPoint*> vpMapPoints1 = pCurrentKF->GetMapPointMatches();
+  const int n1 = (int)vpMapPoints1.size();
+  std::vector<uint8_t> skip1;
+  bad_flags(vpMapPoints1, skip1);
+  std::vector<cms_bow_kf_job> jobs;
+  std::vector<size_t> job_kf;
+  std::vector<std::vector<MapPoint*> > kf_points;
+  std::vector<std::vector<uint8_t> > skips;
+  std::vector<int> idx2, nm;
+  {
+    // locked from the look-up to the end of the device call, like SearchByBoWCandidates
+    std::lock_guard<std::mutex> lk(b.mu);
+    const int slot1 = slot_locked(b, pCurrentKF);
+    for (size_t i = 0; i < nKFs; ++i) {
+      KeyFrame* pKF = vpCandidateKFs[i];
+      pKF->SetNotErase();                                                    // LoopClosing.cpp:256
+      const int slot2 = slot_locked(b, pKF);
+      if (pKF->isBad() || slot1 < 0 || slot2 < 0) { vbDiscarded[i] = true; continue; }      // :258-262 (and a key frame that never entered the store)
+      kf_points.push_back(pKF->GetMapPointMatches());
+      skips.push_back(std::vector<uint8_t>());
+      bad_flags(kf_points.back(), skips.back());
+      cms_bow_kf_job q;
+      q.slot1 = slot1; q.n1 = n1; q.slot2 = slot2; q.n2 = (int)kf_points.back().size();
+      q.skip1 = skip1.data(); q.skip2 = NULL;
+      jobs.push_back(q); job_kf.push_back(i);
+    }
+    for (size_t j = 0; j < jobs.size(); ++j) jobs[j].skip2 = skips[j].data();      // (skips no longer moves)
+    idx2.assign(jobs.size() * (size_t)n1 + 1, -1); nm.assign(jobs.size() + 1, 0);
+    if (!jobs.empty())
+      check(cms_kfstore_search_by_bow_keyframes(store, ctx, (int)jobs.size(), jobs.data(), nnratio, checkOri ? 1 : 0, idx2.data(), nm.data()),
+            "cms_kfstore_search_by_bow_keyframes");
+  }
+  for (size_t j = 0; j < job_kf.size(); ++j) {
+    const size_t i = job_kf[j];
+    std::vector<MapPoint*>& out = vvpMapPointMatches[i];
+    out.assign(n1, static_cast<MapPoint*>(NULL));
+    for (int f = 0; f < n1; ++f) {
+      const int k = idx2[j * (size_t)n1 + f];
+      if (k >= 0) out[f] = kf_points[j][k];
+    }
+    nmatches[i] = nm[j];
+    if (nm[j] < 20) vbDiscarded[i] = true;                                   // LoopClosing.cpp:266-270
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ Tracking::Relocalization: the guided search
 int SearchByProjection(cms_kfstore* store, cms_ctx* frameCtx, Frame& CurrentFrame, KeyFrame* pKF, const std::set<MapPoint*>& sAlreadyFound, float th, int ORBdist,
                        bool checkOri) {

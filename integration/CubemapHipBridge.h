@@ -113,6 +113,16 @@ cms_pnp* CreatePnP(int maxSolvers, int maxCorrespondences, int maxHypotheses);
 // vpSolvers[i]->iterate(nIterations, bNoMore, vbInliers, nInliers) returns (an empty cv::Mat when there is no pose yet).
 void IteratePnP(cms_pnp* pnp, cms_ctx* frameCtx, const std::vector<PnPsolver*>& vpSolvers, int nIterations, std::vector<cv::Mat>& vTcw,
                 std::vector<bool>& vbNoMore, std::vector<std::vector<bool> >& vvbInliers, std::vector<int>& vnInliers);
+// ---- LoopClosing::ComputeSim3's matcher, ORBMatcher(0.75, true).SearchByBoW(mpCurrentKF, pKF, vvpMapPointMatches[i]) (ORBMatcher.cpp:541-674), for all loop
+// candidates as ONE device call on the LOOP-CLOSING thread's context `ctx`: the body of LoopClosing.cpp:251-279 up to the solver set-up.  Every candidate
+// gets SetNotErase() as in the reference; vbDiscarded[i] for candidates that are bad (as the reference), not resident, or below 20 matches (all of them
+// when the current key frame is not resident); vvpMapPointMatches[i][idx1] = the candidate's map point key point idx1 of pCurrentKF receives, or NULL,
+// and nmatches[i], as SearchByBoW gives them.  A feature takes part where the slot's map-point entry is set and GetMapPointMatches() still holds a
+// point that is not bad -- on both sides.  Nothing runs on the store's stream (cms_kfstore_search_by_bow_keyframes); the store's book is locked from
+// the look-up to the end of the call, like SearchByBoWCandidates.  The caller then sets up a Hip::Sim3Solver per candidate that is not discarded.
+void SearchByBoWLoopCandidates(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pCurrentKF, const std::vector<KeyFrame*>& vpCandidateKFs,
+                               std::vector<std::vector<MapPoint*> >& vvpMapPointMatches, std::vector<bool>& vbDiscarded, std::vector<int>& nmatches,
+                               float nnratio, bool checkOri);
 // ---- Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cpp) with the reference's surface, for LoopClosing::ComputeSim3 (LoopClosing.cpp:273-345).  The
 // constructor filters and orders as :66-127 does (with the reference's own cv::Mat arithmetic for Rcw Xw + tcw and its TransformRaysToCubemap);
 // iterate() makes the call's draws with DUtils::Random::RandomInt -- three per iteration, for max(mRansacMaxIts - mnIterations, nIterations)

@@ -1,13 +1,15 @@
-"""Host-to-host time of ORBMatcher::SearchByBoW on the device (cms_search_by_bow / cms_kfstore_search_by_bow): each call is synchronous, so the
-wall clock around it covers staging, the copy up, the launch, the copy back and the synchronisation.  Three shapes, warmed up, >= 50 repetitions:
+"""Host-to-host time of ORBMatcher::SearchByBoW on the device (cms_search_by_bow / cms_kfstore_search_by_bow, and cms_kfstore_search_by_bow_keyframes
+for the (KeyFrame, KeyFrame) overload): each call is synchronous, so the wall clock around it covers staging, the copy up, the launch, the copy back
+and the synchronisation.  The shapes, warmed up, >= 50 repetitions:
 
   one job of 2000 against 2000 features (TrackReferenceKeyFrame), resident and stand-alone
   32 jobs in one call (Relocalization's candidate loop: ~4 candidates for each of 8 frames)
   one job whose frame holds 16383 key points (the frame grid's limit)
+  key frame against key frame (LoopClosing::ComputeSim3): one job of 2000 against 2000 features, and 8 candidates in one call
 
     python tools/prof_bow.py [--reps 200] [--out FILE.json]
 
-Kernel time: run the same under `rocprofv3 --kernel-trace --stats -d DIR -o bow -- python tools/prof_bow.py` (k_search_by_bow)."""
+Kernel time: run the same under `rocprofv3 --kernel-trace --stats -d DIR -o bow -- python tools/prof_bow.py` (k_search_by_bow, k_search_by_bow_kf)."""
 import argparse
 import json
 import os
@@ -95,6 +97,19 @@ def main():
     fvb = fv_of(fd, nodes=800)
     jb = [(0, 0, 16383, fvb, None)]
     res["one_job_16383_frame_keypoints_resident"] = dict(timed(lambda: st.search_by_bow(big, jb), a.reps), n_matches=st.search_by_bow(big, jb)[0][1])
+    # LoopClosing::ComputeSim3: the current key frame (slot 0) against 8 loop candidates, second views of the same points with their own map points
+    for c in range(8):
+        ck, cd = feature_set(rng, 2000, base=kfd)
+        cmp_ = np.where(rng.random(2000) < 0.7, np.arange(2000), -1).astype(np.int32)
+        cand = dict(kf, x=ck["x"], y=ck["y"], octave=ck["octave"], angle=ck["angle"], desc=cd, mp=cmp_, **fv_of(cd))
+        KC, keep_c = api.make_keyframe(cand)
+        st.put(32 + c, KC)
+    kjob1 = [(0, 2000, 32, 2000, None, None)]
+    res["keyframes_one_job_2000x2000"] = dict(timed(lambda: st.search_by_bow_keyframes(ctx, kjob1, nnratio=0.75), a.reps),
+                                              n_matches=st.search_by_bow_keyframes(ctx, kjob1, nnratio=0.75)[0][1])
+    kjobs = [(0, 2000, 32 + c, 2000, None, None) for c in range(8)]
+    res["keyframes_8_jobs_one_call"] = dict(timed(lambda: st.search_by_bow_keyframes(ctx, kjobs, nnratio=0.75), a.reps), jobs=len(kjobs),
+                                            n_matches=int(sum(g[1] for g in st.search_by_bow_keyframes(ctx, kjobs, nnratio=0.75))))
     for k, v in res.items():
         print("%-42s median %8.1f us  p10 %8.1f  p90 %8.1f  (n_matches %s)" % (k, v["median_us"], v["p10_us"], v["p90_us"], v["n_matches"]), flush=True)
     if a.out:
