@@ -638,6 +638,12 @@ class BowKfJob(C.Structure):
     _fields_ = [("slot1", C.c_int), ("n1", C.c_int), ("slot2", C.c_int), ("n2", C.c_int), ("skip1", C.c_void_p), ("skip2", C.c_void_p)]
 
 
+class Sim3SearchJob(C.Structure):
+    """cms_sim3_search_job (include/cubemapslam_hip.h)"""
+    _fields_ = [("slot1", C.c_int), ("n1", C.c_int), ("slot2", C.c_int), ("n2", C.c_int), ("s12", C.c_float), ("R12", C.c_float * 9), ("t12", C.c_float * 3),
+                ("off1", C.c_int), ("off2", C.c_int)]
+
+
 class KfProjJob(C.Structure):
     """cms_kfproj_job (include/cubemapslam_hip.h)"""
     _fields_ = [("slot", C.c_int), ("b", C.c_int), ("n", C.c_int), ("pose12", C.c_float * 12), ("nmp", C.c_int), ("kf_feat", C.c_void_p), ("pos", C.c_void_p),
@@ -943,6 +949,39 @@ class KeyframeStore(_Handle):
         _chk(L.cms_kfstore_search_by_bow_keyframes(self.h, src_ctx.h, len(jobs), arr, float(nnratio), int(check_orientation), _p(idx2), _p(nm)),
              "cms_kfstore_search_by_bow_keyframes")
         return [(idx2[off[j]:off[j + 1]].copy(), int(nm[j])) for j in range(len(jobs))]
+
+    def search_by_sim3(self, src_ctx, jobs, th=7.5, z_as_written=True, out=None, n_mp=None):
+        """cms_kfstore_search_by_sim3: ORBMatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (LoopClosing::ComputeSim3) for many pairs of
+        resident key frames in ONE call on src_ctx's stream.  jobs: list of dict(slot1, slot2, s12, R12, t12, mp1, mp2); mp1 / mp2 = per key point of that
+        key frame dict(skip, pos, min_dist, max_dist, desc), skip != 0 <=> no map point, already matched or bad (the other arrays are read only where
+        skip == 0).  n1 / n2 are the lengths of the skip arrays unless the job gives them.  z_as_written: the depth of line :1507 as the reference
+        has it.  out: (idx2, n_found) arrays to receive the results (pinned ones, say); off1 / off2 of a job and n_mp default to the concatenation
+        this wrapper builds.  Returns per job (idx2 int32[n1]: the key point of key frame 2
+        whose map point key point i of key frame 1 receives, or -1; n_found)."""
+        nj = len(jobs)
+        arr = (Sim3SearchJob * max(nj, 1))()
+        parts = []
+        at = 0
+        for q, j in zip(arr, jobs):
+            n1, n2 = len(j["mp1"]["skip"]), len(j["mp2"]["skip"])
+            q.slot1 = j["slot1"]; q.slot2 = j["slot2"]; q.n1 = j.get("n1", n1); q.n2 = j.get("n2", n2); q.s12 = float(j["s12"])
+            q.R12[:] = [float(v) for v in np.asarray(j["R12"], np.float32).reshape(9)]; q.t12[:] = [float(v) for v in np.asarray(j["t12"], np.float32).reshape(3)]
+            q.off1 = j.get("off1", at); q.off2 = j.get("off2", at + n1)
+            at += n1 + n2
+            parts += [j["mp1"], j["mp2"]]
+
+        def cat(k, dt, tail):
+            if not parts:
+                return np.zeros((0,) + tail, dt)
+            return np.ascontiguousarray(np.concatenate([np.asarray(m[k], dt).reshape((-1,) + tail) for m in parts]), dt)
+        a = [cat("skip", np.uint8, ()), cat("pos", np.float32, (3,)), cat("min_dist", np.float32, ()), cat("max_dist", np.float32, ()), cat("desc", np.uint8, (32,))]
+        off = np.concatenate([[0], np.cumsum([max(int(q.n1), 0) for q in arr[:nj]])]).astype(np.int64)
+        idx2, nf = out if out is not None else (np.full(max(int(off[-1]), 1), -1, np.int32), np.zeros(max(nj, 1), np.int32))
+        L = lib()
+        L.cms_kfstore_search_by_sim3.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+        _chk(L.cms_kfstore_search_by_sim3(self.h, src_ctx.h, nj, arr, at if n_mp is None else n_mp, *[_p(v) for v in a], float(th), int(bool(z_as_written)), _p(idx2), _p(nf)),
+             "cms_kfstore_search_by_sim3")
+        return [(idx2[off[k]:off[k + 1]].copy(), int(nf[k])) for k in range(nj)]
 
     def compute_bow(self, vocab, slots, levelsup=4):
         """cms_kfstore_compute_bow: KeyFrame::ComputeBoW on the resident descriptors of `slots`; the FeatureVector goes into the slots' layout, the

@@ -54,7 +54,7 @@ static std::mutex g_ctx_mutex;
 static cms_ctx* g_ctx = nullptr;
 static const int kSharedDevice = 0;      // the device of the shared context (and of what works with it: ORBVocabulary's device handle)
 static cms_orb_params g_ctx_orb{};
-static cms_kfstore* g_bow_kf_store = nullptr;      // ORBMatcher::SearchByBoW(pKF1, pKF2, ...): two slots on the shared context, made by the first call
+static cms_kfstore* g_bow_kf_store = nullptr;      // ORBMatcher::SearchByBoW(pKF1, pKF2, ...) and SearchBySim3: two slots on the shared context, made by the first call
 static cms_camera g_ctx_cam{};      // the camera the shared context was built for (SetCamParams zero-fills the record first: comparable byte for byte)
 cms_ctx* SharedContext(int nfeatures, float scaleFactor, int nlevels, int iniThFAST, int minThFAST) {
   std::lock_guard<std::mutex> lock(g_ctx_mutex);
@@ -466,6 +466,67 @@ int ORBMatcher::SearchByBoW(const KeyFrameView& pKF1, const KeyFrameView& pKF2, 
   }
   for (int i = 0; i < N1; ++i) if (idx2[i] >= 0) vpMatches12[i] = pKF2.mvpMapPoints[idx2[i]];
   return nm;
+}
+
+int ORBMatcher::SearchBySim3(const KeyFrameView& pKF1, const KeyFrameView& pKF2, std::vector<long>& vpMatches12, float s12, const cv::Mat& R12, const cv::Mat& t12,
+                             float th, bool zAsWritten) {
+  const int N1 = (int)pKF1.mvKeys.size(), N2 = (int)pKF2.mvKeys.size();
+  if ((int)vpMatches12.size() != N1) throw std::runtime_error("SearchBySim3: vpMatches12 must have one entry per key point of pKF1");
+  if ((int)pKF1.mvMapPoints.size() != N1 || (int)pKF2.mvMapPoints.size() != N2) throw std::runtime_error("SearchBySim3: mvMapPoints must have one entry per key point");
+  if (R12.rows != 3 || R12.cols != 3 || R12.type() != cv::CV_32F || t12.rows != 3 || t12.cols != 1 || t12.type() != cv::CV_32F)
+    throw std::runtime_error("SearchBySim3: R12 must be 3x3 and t12 3x1, CV_32F");
+  if (N1 == 0 || N2 == 0) return 0;
+  cms_ctx* ctx = SharedContext(g_ctx_orb.nfeatures, g_ctx_orb.scale_factor, g_ctx_orb.nlevels, g_ctx_orb.ini_th_fast, g_ctx_orb.min_th_fast);
+  // :1387-1400 on ids: a key point of pKF1 that holds a match already, and the key point of pKF2 that observes the matched point (GetIndexInKeyFrame)
+  std::vector<uint8_t> matched1(N1, 0), matched2(N2, 0);
+  std::map<long, int> index_in_kf2;
+  for (int i = N2 - 1; i >= 0; --i) if (pKF2.mvpMapPoints[i] >= 0) index_in_kf2[pKF2.mvpMapPoints[i]] = i;
+  for (int i = 0; i < N1; ++i) {
+    if (vpMatches12[i] < 0) continue;
+    matched1[i] = 1;
+    const auto it = index_in_kf2.find(vpMatches12[i]);
+    if (it != index_in_kf2.end()) matched2[it->second] = 1;
+  }
+  // a view as cms_keyframe (key points, descriptors, pose; the search reads neither rays nor the FeatureVector) and its map-point records
+  const int M = N1 + N2;
+  std::vector<uint8_t> skip(M, 1), mpd(32 * (size_t)M, 0);
+  std::vector<float> pos(3 * (size_t)M, 0.0f), dmin(M, 0.0f), dmax(M, 0.0f);
+  struct Side { KfPack p; cms_keyframe k; };
+  auto pack = [&](const KeyFrameView& kf, const std::vector<uint8_t>& matched, int at, Side& s) {
+    const int N = (int)kf.mvKeys.size();
+    KeyFrameView v;
+    v.mvKeys = kf.mvKeys; v.mDescriptors = kf.mDescriptors; v.mvpMapPoints = kf.mvpMapPoints; v.Tcw = kf.Tcw;
+    v.mvKeyRays.assign(N, cv::Vec3f());
+    s.k = pack_keyframe(v, s.p);
+    for (int i = 0; i < N; ++i) {
+      if (kf.mvpMapPoints[i] < 0 || matched[i] || (i < (int)kf.mvbMapPointBad.size() && kf.mvbMapPointBad[i])) continue;      // !pMP || vbAlreadyMatched[i] || pMP->isBad()
+      const MapPointView& mp = kf.mvMapPoints[i];
+      const size_t r = (size_t)at + i;
+      skip[r] = 0;
+      for (int c = 0; c < 3; ++c) pos[3 * r + c] = mp.mWorldPos.at<float>(c, 0);
+      dmin[r] = mp.mfMinDistance; dmax[r] = mp.mfMaxDistance;
+      std::memcpy(&mpd[32 * r], mp.mDescriptor.ptr<uint8_t>(0), 32);
+    }
+  };
+  Side s1, s2;
+  pack(pKF1, matched1, 0, s1); pack(pKF2, matched2, N1, s2);
+  cms_sim3_search_job q;
+  q.slot1 = 0; q.n1 = N1; q.slot2 = 1; q.n2 = N2; q.s12 = s12; q.off1 = 0; q.off2 = N1;
+  for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) q.R12[3 * r + c] = R12.at<float>(r, c); q.t12[r] = t12.at<float>(r, 0); }
+  std::vector<int> idx2(N1, -1);
+  int nFound = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!g_bow_kf_store && cms_kfstore_create(&g_bow_kf_store, ctx, 2, 4096, 4096) != CMS_OK)
+      throw std::runtime_error(std::string("cms_kfstore_create: ") + cms_last_error());
+    int rc = cms_kfstore_put(g_bow_kf_store, 0, &s1.k);
+    if (rc == CMS_OK) rc = cms_kfstore_put(g_bow_kf_store, 1, &s2.k);
+    if (rc == CMS_OK) rc = cms_kfstore_search_by_sim3(g_bow_kf_store, ctx, 1, &q, M, skip.data(), pos.data(), dmin.data(), dmax.data(), mpd.data(), th, zAsWritten ? 1 : 0,
+                                                      idx2.data(), &nFound);
+    if (rc != CMS_OK) throw std::runtime_error(std::string("cms_kfstore_search_by_sim3: ") + cms_last_error());
+  }
+  for (int i = 0; i < N1; ++i) if (idx2[i] >= 0) vpMatches12[i] = pKF2.mvpMapPoints[idx2[i]];      // :1579
+  return nFound;
 }
 
 int ORBMatcher::SearchByProjection(FrameView& CurrentFrame, const KeyFrameView& pKF, const std::set<long>& sAlreadyFound, float th, int ORBdist) {

@@ -201,6 +201,15 @@ class ORBMatcher {
   // points' position, distances and descriptor.  Fills CurrentFrame.mvpMapPoints with the matched ids, returns nmatches.
   // (cms_search_by_projection_keyframe: the frame's key points and descriptors go to the device first)
   int SearchByProjection(FrameView& CurrentFrame, const KeyFrameView& pKF, const std::set<long>& sAlreadyFound, float th, int ORBdist);
+  // ORBMatcher.cpp:1365-1586, LoopClosing.cpp:322: the map points of each key frame that are not bad and not matched yet (vpMatches12 on entry, and
+  // through it the key points of pKF2 that observe a matched point: :1390-1400 on ids) are carried into the other camera by the similarity
+  // (s12, R12 3x3, t12 3x1, CV_32F), projected, and matched inside windows th * scale[predicted level] over octaves level - 1 and level, best Hamming
+  // <= TH_HIGH; a pair is kept where both directions agree.  Reads pKF.mvMapPoints (position, distances, descriptor) and Tcw of both views.
+  // vpMatches12[i1] receives the id of pKF2's map point; returns nFound.  zAsWritten: the depth of the 2 -> 1 projection is component 1, line :1507
+  // as the reference has it (the default: the product's contract is the reference's result); false takes component 2.
+  // (cms_kfstore_search_by_sim3: both views go into the small store of the shared context first; the device path only)
+  int SearchBySim3(const KeyFrameView& pKF1, const KeyFrameView& pKF2, std::vector<long>& vpMatches12, float s12, const cv::Mat& R12, const cv::Mat& t12, float th,
+                   bool zAsWritten = true);
   static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 12;
 
  protected:

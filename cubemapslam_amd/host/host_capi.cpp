@@ -326,6 +326,43 @@ extern "C" int hm_search_by_projection_keyframe(int nk, const cms_keypoint* kk, 
     for (int i = 0; i < n; ++i) frame_mp[i] = f.mvpMapPoints[i];
     return nm;)
 }
+// ORBMatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) through the mirror: per key frame n key points with descriptors, its pose Tcw
+// (16 floats, row major), map-point ids mp (-1 = none), bad flags or NULL, and per key point the map point's position / mfMinDistance /
+// mfMaxDistance / descriptor; R12 9 floats row major, t12 3; matches12[n1] = vpMatches12 as ids, in/out
+extern "C" int hm_search_by_sim3(int n1, const cms_keypoint* k1, const uint8_t* d1, float* Tcw1, const long* mp1, const uint8_t* bad1, const float* pos1, const float* min1,
+                                 const float* max1, const uint8_t* mpd1, int n2, const cms_keypoint* k2, const uint8_t* d2, float* Tcw2, const long* mp2,
+                                 const uint8_t* bad2, const float* pos2, const float* min2, const float* max2, const uint8_t* mpd2, float s12, float* R12, float* t12,
+                                 float th, int z_as_written, long* matches12) {
+  HM_TRY(
+    auto view = [](KeyFrameView& kf, int n, const cms_keypoint* k, const uint8_t* desc, float* Tcw, const long* mp, const uint8_t* bad, const float* pos, const float* mn,
+                   const float* mx, const uint8_t* mpd) {
+      kf.mvKeys.resize(n); kf.mvMapPoints.resize(n);
+      kf.mDescriptors.create(n > 0 ? n : 1, 32, cv::CV_8U);
+      kf.mvpMapPoints.assign(mp, mp + n);
+      if (bad) kf.mvbMapPointBad.assign(bad, bad + n);
+      kf.Tcw = cv::Mat(4, 4, cv::CV_32F, Tcw, 16);
+      for (int i = 0; i < n; ++i) {
+        kf.mvKeys[i].pt = cv::Point2f(k[i].x, k[i].y); kf.mvKeys[i].angle = k[i].angle; kf.mvKeys[i].octave = k[i].octave; kf.mvKeys[i].size = k[i].size;
+        kf.mvKeys[i].response = k[i].response;
+        std::memcpy(kf.mDescriptors.ptr<uint8_t>(i), desc + (size_t)i * 32, 32);
+        MapPointView& v = kf.mvMapPoints[i];
+        v.mnId = mp[i]; v.mfMinDistance = mn[i]; v.mfMaxDistance = mx[i];
+        v.mWorldPos.create(3, 1, cv::CV_32F);
+        for (int c = 0; c < 3; ++c) v.mWorldPos.at<float>(c, 0) = pos[3 * (size_t)i + c];
+        v.mDescriptor.create(1, 32, cv::CV_8U);
+        std::memcpy(v.mDescriptor.ptr<uint8_t>(0), mpd + 32 * (size_t)i, 32);
+      }
+    };
+    KeyFrameView kf1;
+    KeyFrameView kf2;
+    view(kf1, n1, k1, d1, Tcw1, mp1, bad1, pos1, min1, max1, mpd1);
+    view(kf2, n2, k2, d2, Tcw2, mp2, bad2, pos2, min2, max2, mpd2);
+    std::vector<long> m(matches12, matches12 + n1);
+    ORBMatcher matcher(0.75f, true);
+    const int nm = matcher.SearchBySim3(kf1, kf2, m, s12, cv::Mat(3, 3, cv::CV_32F, R12, 12), cv::Mat(3, 1, cv::CV_32F, t12, 4), th, z_as_written != 0);
+    for (int i = 0; i < n1; ++i) matches12[i] = m[i];
+    return nm;)
+}
 // LocalMapping::CreateNewMapPoints through the mirror: key frame 0 is the current one, 1..nkf-1 its neighbours.  Flat inputs:
 // feat_off[nkf+1]; per feature kps/desc/rays/mp; Tcw nkf x 16; FeatureVector per key frame as node_off2[nkf+1] into (node_id, node_cnt)
 // and the features of the nodes concatenated in node_feat; median_depth[nkf].  Outputs up to cap records.

@@ -783,6 +783,40 @@ typedef struct {
 } cms_sim3_job;
 int cms_sim3_iterate(cms_sim3* p, cms_ctx* ctx /* F */, int njobs, cms_sim3_job* jobs);
 
+/* ---- ORBMatcher::SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12, s12, R12, t12, th) (include/ORBMatcher.h,
+ * src/ORBMatcher.cpp:1365-1586), the guided matcher LoopClosing::ComputeSim3 runs on every hypothesis Sim3Solver::iterate accepts
+ * (src/LoopClosing.cpp:312-322, th = 7.5), behind cms_sim3_iterate, on resident key frames: every accepted hypothesis of a pass in ONE call.
+ * Per job: sR12 = s12*R12, sR21 = (1.0/s12)*R12.t(), t21 = -sR21*t12 (:1377-1379; csrc/cms_sim3_search_core.h states the arithmetic).  Direction
+ * 1 -> 2 (:1406-1484), per key point i1 of key frame 1 with skip == 0: p3Dc2 = sR21*(R1w*p3Dw + t1w) + t21, dropped on z < 0, projected
+ * (TransformRaysToCubemap), dropped outside [0, 3F)^2, dist3D = norm(p3Dc2) against the point's scale-invariance distances, PredictScale, window
+ * th * mvScaleFactors[level] in key frame 2 (GetFeaturesInArea without level arguments, its order), candidates of octave level - 1 or level, first
+ * strict Hamming minimum from INT_MAX, accepted when <= TH_HIGH (100).  No viewing-angle test, no reprojection gate, no taken flag.  Direction 2 -> 1
+ * (:1487-1565) mirrors it with sR12 | t12 into key frame 1.  z_as_written != 0: the depth handed to the projection of direction 2 -> 1 is
+ * component 1, line :1507 as the reference has it (`z = p3Dc1.at<float>(1)`); 0: component 2, upstream ORB-SLAM2's text.  The depth test and the norm
+ * use the true vector either way.  Agreement (:1567-1583): idx2[i1] = vnMatch1[i1] where vnMatch2[vnMatch1[i1]] == i1, else -1; n_found = their number.
+ * One stated difference: a ray no face takes (UNKNOWN_FACE) makes the reference's assert abort; here u = v = -1 and the point is dropped.
+ * The poses R1w | t1w, R2w | t2w are the slots' own (cms_kfstore_put*, cms_kfstore_update_poses).  The store holds no world positions, so the map
+ * points travel, as for cms_kfstore_fuse_search: record off1 + i1 of the n_mp-long arrays belongs to key point i1 of key frame 1, off2 + i2 to key
+ * point i2 of key frame 2.  skip != 0 <=> !pMP || vbAlreadyMatched[i] || pMP->isBad() (the pointer work of :1390-1400 is the caller's); pos, min_dist,
+ * max_dist (as src's cms_set_distance_bounds_mode says) and mp_desc are read only where skip == 0.  A job's records are key frame 1's, then key
+ * frame 2's, and the jobs' records follow each other in call order: off1 >= the end of the job before, off2 >= off1 + n1, off2 + n2 <= n_mp.
+ * idx2: job after job, n1 entries each; n_found[njobs].  Both may be pageable or pinned host memory.
+ * Runs on src's stream with src's staging block -- the loop-closing thread's -- and enqueues nothing on the store's: src's stream waits on the
+ * device for the copies of cms_kfstore_put_from_frame(s) that filled the named slots.  Four launches (projection, window query, scan, agreement), one
+ * synchronisation; a call whose candidate lists did not fit is repeated once with room for them.  Synchronous.  Checked before anything is enqueued,
+ * CMS_ERR_ARG with the reason in cms_last_error: a slot out of range or not filled, n1 / n2 that is not the slot's stored key-point count, offsets
+ * that do not ascend or reach beyond n_mp, s12 zero or not finite, th negative or not finite, more than 16 levels, a context on another device
+ * than the store's.  njobs == 0 is CMS_OK with no launch; n1 == 0 or n2 == 0 gives zero matches; slot1 == slot2 is allowed.  Threading as
+ * cms_kfstore_search_by_bow_keyframes. */
+typedef struct {
+  int slot1, n1, slot2, n2;     /* resident key frames (mpCurrentKF, pKF) and their stored key-point counts */
+  float s12, R12[9], t12[3];    /* Sim3Solver::GetEstimatedScale / Rotation (row major) / Translation */
+  int off1, off2;               /* first entry of key frame 1's / 2's per-key-point map-point records in the arrays below */
+} cms_sim3_search_job;
+int cms_kfstore_search_by_sim3(cms_kfstore* st, cms_ctx* src, int njobs, const cms_sim3_search_job* jobs, int n_mp,
+                               const uint8_t* skip, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* mp_desc,
+                               float th, int z_as_written, int* idx2, int* n_found);
+
 /* ---- Initializer (include/Initializer.h, src/Initializer.cpp), the two-view essential-matrix RANSAC of Tracking::MonocularInitialization
  * (src/Tracking.cpp:443), behind cms_search_for_initialization.  ComputeE21 takes the last row of a FULL_UV SVD of an 8 x 9 matrix, which OpenCV
  * completes from a basis nobody can pin (DESIGN.md "Initializer"), so the definition of record is the project's own core, csrc/cms_init_core.h: one

@@ -618,6 +618,83 @@ void SearchByBoWLoopCandidates(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pCurr
   }
 }
 
+// ------------------------------------------------------------------------------------------------ LoopClosing::ComputeSim3: SearchBySim3 on resident key frames
+void SearchBySim3(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pCurrentKF, const std::vector<KeyFrame*>& vpKFs, std::vector<std::vector<MapPoint*> >& vvpMatches12,
+                  const std::vector<float>& vs12, const std::vector<cv::Mat>& vR12, const std::vector<cv::Mat>& vt12, float th, std::vector<int>& vnFound,
+                  bool zAsWritten) {
+  StoreBook& b = book(store);
+  const size_t nH = vpKFs.size();
+  if (vvpMatches12.size() != nH || vs12.size() != nH || vR12.size() != nH || vt12.size() != nH) throw std::runtime_error("Hip::SearchBySim3: one entry per hypothesis");
+  vnFound.assign(nH, 0);
+  const std::vector<MapPoint*> vpMapPoints1 = pCurrentKF->GetMapPointMatches();
+  const int N1 = (int)vpMapPoints1.size();
+  std::vector<cms_sim3_search_job> jobs;
+  std::vector<size_t> job_h;
+  std::vector<std::vector<MapPoint*> > kf_points;
+  std::vector<uint8_t> skip, desc;
+  std::vector<float> pos, dmin, dmax;
+  // one record per key point: skip <=> !pMP || vbAlreadyMatched[i] || pMP->isBad() (ORBMatcher.cpp:1410-1414, :1491-1495)
+  auto records = [&](const std::vector<MapPoint*>& pts, const std::vector<bool>& matched) {
+    for (size_t i = 0; i < pts.size(); ++i) {
+      MapPoint* p = pts[i];
+      const bool out = !p || matched[i] || p->isBad();
+      skip.push_back(out ? 1 : 0);
+      if (out) { pos.insert(pos.end(), 3, 0.0f); dmin.push_back(0.0f); dmax.push_back(0.0f); desc.insert(desc.end(), 32, 0); continue; }
+      const cv::Mat x = p->GetWorldPos();
+      for (int c = 0; c < 3; ++c) pos.push_back(x.at<float>(c));
+      dmin.push_back(p->GetMinDistanceInvariance()); dmax.push_back(p->GetMaxDistanceInvariance());      // (every context of the bridge runs in distance-bounds mode 1)
+      const cv::Mat d = p->GetDescriptor();
+      desc.insert(desc.end(), d.data, d.data + 32);
+    }
+  };
+  std::vector<int> idx2, nf;
+  {
+    // locked from the look-up to the end of the device call, like SearchByBoWLoopCandidates
+    std::lock_guard<std::mutex> lk(b.mu);
+    const int slot1 = slot_locked(b, pCurrentKF);
+    for (size_t h = 0; h < nH; ++h) {
+      KeyFrame* pKF = vpKFs[h];
+      const int slot2 = slot_locked(b, pKF);
+      if (slot1 < 0 || slot2 < 0) throw std::runtime_error("Hip::SearchBySim3: a key frame is not in the store");
+      if ((int)vvpMatches12[h].size() != N1) throw std::runtime_error("Hip::SearchBySim3: vpMatches12 must have one entry per key point of the current key frame");
+      kf_points.push_back(pKF->GetMapPointMatches());
+      const std::vector<MapPoint*>& vpMapPoints2 = kf_points.back();
+      const int N2 = (int)vpMapPoints2.size();
+      std::vector<bool> vbAlreadyMatched1(N1, false), vbAlreadyMatched2(N2, false);      // :1387-1400
+      for (int i = 0; i < N1; ++i) {
+        MapPoint* pMP = vvpMatches12[h][i];
+        if (pMP) {
+          vbAlreadyMatched1[i] = true;
+          const int i2 = pMP->GetIndexInKeyFrame(pKF);
+          if (i2 >= 0 && i2 < N2) vbAlreadyMatched2[i2] = true;
+        }
+      }
+      cms_sim3_search_job q;
+      q.slot1 = slot1; q.n1 = N1; q.slot2 = slot2; q.n2 = N2; q.s12 = vs12[h];
+      for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) q.R12[3 * r + c] = vR12[h].at<float>(r, c); q.t12[r] = vt12[h].at<float>(r); }
+      q.off1 = (int)skip.size();
+      records(vpMapPoints1, vbAlreadyMatched1);
+      q.off2 = (int)skip.size();
+      records(vpMapPoints2, vbAlreadyMatched2);
+      jobs.push_back(q); job_h.push_back(h);
+    }
+    idx2.assign(jobs.size() * (size_t)N1 + 1, -1); nf.assign(jobs.size() + 1, 0);
+    skip.push_back(0); pos.push_back(0.0f); dmin.push_back(0.0f); dmax.push_back(0.0f); desc.push_back(0);      // (never empty: data() stays valid)
+    if (!jobs.empty())
+      check(cms_kfstore_search_by_sim3(store, ctx, (int)jobs.size(), jobs.data(), (int)skip.size() - 1, skip.data(), pos.data(), dmin.data(), dmax.data(), desc.data(), th,
+                                       zAsWritten ? 1 : 0, idx2.data(), nf.data()),
+            "cms_kfstore_search_by_sim3");
+  }
+  for (size_t j = 0; j < job_h.size(); ++j) {
+    const size_t h = job_h[j];
+    for (int i1 = 0; i1 < N1; ++i1) {
+      const int k = idx2[j * (size_t)N1 + i1];
+      if (k >= 0) vvpMatches12[h][i1] = kf_points[j][k];                     // :1579
+    }
+    vnFound[h] = nf[j];
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ Tracking::Relocalization: the guided search
 int SearchByProjection(cms_kfstore* store, cms_ctx* frameCtx, Frame& CurrentFrame, KeyFrame* pKF, const std::set<MapPoint*>& sAlreadyFound, float th, int ORBdist,
                        bool checkOri) {

@@ -123,6 +123,17 @@ void IteratePnP(cms_pnp* pnp, cms_ctx* frameCtx, const std::vector<PnPsolver*>& 
 void SearchByBoWLoopCandidates(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pCurrentKF, const std::vector<KeyFrame*>& vpCandidateKFs,
                                std::vector<std::vector<MapPoint*> >& vvpMapPointMatches, std::vector<bool>& vbDiscarded, std::vector<int>& nmatches,
                                float nnratio, bool checkOri);
+// ---- LoopClosing::ComputeSim3's guided matcher, matcher.SearchBySim3(mpCurrentKF, pKF, vpMapPointMatches, s, R, t, 7.5) (ORBMatcher.cpp:1365-1586), for
+// one or several accepted hypotheses as ONE device call on the LOOP-CLOSING thread's context `ctx`: the body of LoopClosing.cpp:312-322 behind the
+// inlier copy.  Hypothesis h: candidate vpKFs[h] with s12 / R12 / t12 as Sim3Solver's GetEstimatedScale / Rotation / Translation give them and
+// vvpMatches12[h] = the inlier matches of :312-317 (one entry per key point of pCurrentKF), which receives the new matches as the reference's vector
+// does; vnFound[h] = what SearchBySim3 returns.  vbAlreadyMatched1 / 2 are built here with GetIndexInKeyFrame (:1390-1400); positions, the distance
+// getters' values and descriptors of the map points travel with the call.  zAsWritten = true is the reference's line :1507 (the default: the
+// contract is the reference's result).  Both key frames must be resident; nothing runs on the store's stream (cms_kfstore_search_by_sim3), and the
+// store's book is locked from the look-up to the end of the call.  The caller goes on with Optimizer::OptimizeSim3, which stays host code.
+void SearchBySim3(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pCurrentKF, const std::vector<KeyFrame*>& vpKFs, std::vector<std::vector<MapPoint*> >& vvpMatches12,
+                  const std::vector<float>& vs12, const std::vector<cv::Mat>& vR12, const std::vector<cv::Mat>& vt12, float th, std::vector<int>& vnFound,
+                  bool zAsWritten = true);
 // ---- Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cpp) with the reference's surface, for LoopClosing::ComputeSim3 (LoopClosing.cpp:273-345).  The
 // constructor filters and orders as :66-127 does (with the reference's own cv::Mat arithmetic for Rcw Xw + tcw and its TransformRaysToCubemap);
 // iterate() makes the call's draws with DUtils::Random::RandomInt -- three per iteration, for max(mRansacMaxIts - mnIterations, nIterations)

@@ -43,7 +43,8 @@ def main(ref_inc):
                                                ("CubemapHipBridge.cpp", "cms_sim3_iterate(sim3, frameCtx, (int)n, jobs.data())", "cms_sim3_iterat(sim3, frameCtx, (int)n, jobs.data())"),
                                                ("CubemapHipBridge.cpp", "cms_kfdb_detect(store, frameCtx, 1, &job,", "cms_kfdb_detect(store, 1, &job,"),
                                                ("CubemapHipBridge.cpp", "cms_kfstore_search_by_bow_keyframes(store, ctx, (int)jobs.size(),",
-                                                "cms_kfstore_search_by_bow_keyframes(store, (int)jobs.size(),"))):
+                                                "cms_kfstore_search_by_bow_keyframes(store, (int)jobs.size(),"),
+                                               ("CubemapHipBridge.cpp", "cms_kfstore_search_by_sim3(store, ctx, (int)jobs.size(),", "cms_kfstore_search_by_sim3(store, (int)jobs.size(),"))):
             d = os.path.join(td, "broken_%d" % i)
             shutil.copytree(os.path.join(ROOT, "integration"), d)
             src = open(os.path.join(d, fname)).read()
