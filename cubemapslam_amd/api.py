@@ -1645,6 +1645,77 @@ class Sim3Solver(_Handle):
         return sim3_results(arr, states)
 
 
+SIM3_OPT_AS_WRITTEN, SIM3_OPT_ANALYTIC = 0, 1
+
+
+class Sim3OptJob(C.Structure):
+    """cms_sim3_opt_job (include/cubemapslam_hip.h)"""
+    _fields_ = [("N", C.c_int), ("x3dc1", C.c_void_p), ("x3dc2", C.c_void_p), ("kp1", C.c_void_p), ("kp2", C.c_void_p), ("inv_sigma2_1", C.c_void_p),
+                ("inv_sigma2_2", C.c_void_p), ("R12", C.c_double * 9), ("t12", C.c_double * 3), ("s12", C.c_double), ("th2", C.c_float), ("fix_scale", C.c_int),
+                ("jacobian", C.c_int), ("n_inliers", C.c_int), ("keep", C.c_void_p), ("q12", C.c_double * 4), ("t12_out", C.c_double * 3), ("s12_out", C.c_double),
+                ("n_correspondences", C.c_int), ("n_bad", C.c_int), ("iterations", C.c_int * 2)]
+
+
+def sim3_opt_job_state(prob, th2=10.0, fix_scale=None, jacobian=SIM3_OPT_AS_WRITTEN):
+    """The arrays of one OptimizeSim3 call as a dict a Sim3OptJob points into: prob has x3dc1, x3dc2 (N x 3), kp1, kp2 (N x 2), inv_sigma2_1,
+    inv_sigma2_2 (N), R12 (3 x 3), t12, s12 and optionally fix_scale.  keep starts from a pattern, so that an untouched record shows."""
+    N = len(prob["x3dc1"])
+    f32 = lambda a, shape: np.ascontiguousarray(np.array(a, np.float32).reshape(shape))      # copies: a caller may edit a state
+    return dict(N=N, x3dc1=f32(prob["x3dc1"], (N, 3)), x3dc2=f32(prob["x3dc2"], (N, 3)), kp1=f32(prob["kp1"], (N, 2)), kp2=f32(prob["kp2"], (N, 2)),
+                inv_sigma2_1=f32(prob["inv_sigma2_1"], (N,)), inv_sigma2_2=f32(prob["inv_sigma2_2"], (N,)),
+                R12=np.array(prob["R12"], np.float64).reshape(9).copy(), t12=np.array(prob["t12"], np.float64).reshape(3).copy(), s12=float(prob["s12"]),
+                th2=float(th2), fix_scale=int(prob.get("fix_scale", 0) if fix_scale is None else fix_scale), jacobian=int(jacobian),
+                keep=np.full(max(N, 1), 7, np.uint8))
+
+
+def sim3_opt_jobs(states):
+    """(Sim3OptJob * n) over sim3_opt_job_state() dicts; the dicts own the memory.  The scalar outputs start from -7."""
+    arr = (Sim3OptJob * max(len(states), 1))()
+    for q, s in zip(arr, states):
+        q.N = s["N"]
+        for k in ("x3dc1", "x3dc2", "kp1", "kp2", "inv_sigma2_1", "inv_sigma2_2", "keep"):
+            setattr(q, k, _p(s[k]) if s[k] is not None else None)
+        C.memmove(q.R12, _p(s["R12"]), 72); C.memmove(q.t12, _p(s["t12"]), 24)
+        q.s12 = s["s12"]; q.th2 = s["th2"]; q.fix_scale = s["fix_scale"]; q.jacobian = s["jacobian"]
+        q.n_inliers = -7; q.n_correspondences = -7; q.n_bad = -7; q.iterations[0] = -7; q.iterations[1] = -7
+    return arr
+
+
+def sim3_opt_results(arr, states):
+    """What a call left in the job records, one dict per job (arrays copied)"""
+    out = []
+    for q, s in zip(arr, states):
+        out.append(dict(n_inliers=q.n_inliers, n_correspondences=q.n_correspondences, n_bad=q.n_bad, iterations=np.array(q.iterations[:], np.int32),
+                        keep=s["keep"][:s["N"]].copy(), q12=np.frombuffer(bytes(q.q12), np.float64).copy(), t12=np.frombuffer(bytes(q.t12_out), np.float64).copy(),
+                        s12=np.frombuffer(C.string_at(C.addressof(q) + Sim3OptJob.s12_out.offset, 8), np.float64).copy()))
+    return out
+
+
+sim3_opt_first_difference = pnp_first_difference      # result dicts compared bit for bit: None, or (job, key, wanted, got)
+
+
+class Sim3Optimizer(_Handle):
+    """Optimizer::OptimizeSim3 for many hypotheses in one launch (cms_sim3_opt_*).  jobs: a (Sim3OptJob * n) array, e.g. from sim3_opt_jobs()."""
+    _entries = ("cms_sim3_opt_create", "cms_sim3_opt_destroy")
+
+    def __init__(self, max_jobs, max_corr_total, device=0):
+        L = lib()
+        L.cms_sim3_opt_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.cms_sim3_opt_destroy.argtypes = [C.c_void_p]
+        L.cms_sim3_optimize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        self._create(device, max_jobs, max_corr_total)
+
+    def optimize(self, ctx, jobs, njobs=None):
+        _chk(lib().cms_sim3_optimize(self.h, ctx.h, len(jobs) if njobs is None else njobs, jobs), "cms_sim3_optimize")
+        return jobs
+
+    def run(self, ctx, states):
+        """One call over sim3_opt_job_state() dicts -> one result dict per job"""
+        arr = sim3_opt_jobs(states)
+        self.optimize(ctx, arr, len(states))
+        return sim3_opt_results(arr, states)
+
+
 class InitJob(C.Structure):
     """cms_init_job (include/cubemapslam_hip.h)"""
     _fields_ = [("n1", C.c_int), ("n2", C.c_int), ("keys1", C.c_void_p), ("rays1", C.c_void_p), ("keys2", C.c_void_p), ("rays2", C.c_void_p),

@@ -1030,6 +1030,61 @@ cv::Mat Sim3Solver::GetEstimatedTranslation() {
 }
 float Sim3Solver::GetEstimatedScale() { return mBestScale; }
 
+// ------------------------------------------------------------------------------------------------ Optimizer::OptimizeSim3 (src/Optimizer.cpp:888-1091)
+extern "C" int hm_sim3_optimize_host(int F, int njobs, cms_sim3_opt_job* jobs);      // sim3_opt_host.cpp: the host build of csrc/cms_sim3_opt_core.h
+extern "C" const char* hm_sim3_opt_last_reason();
+
+Sim3OptGraph Optimizer::CollectSim3Graph(const Sim3OptKeyFrameView& pKF1, const Sim3OptKeyFrameView& pKF2, const std::vector<int>& vpMatches1) {
+  Sim3OptGraph g;
+  const int N = (int)vpMatches1.size();
+  const std::vector<int>& vpMapPoints1 = pKF1.mvpMapPointMatches;
+  for (int i = 0; i < N; i++) {      // :941-1028
+    if (vpMatches1[i] < 0) continue;                                                     // !vpMatches1[i]
+    if (i >= (int)vpMapPoints1.size() || vpMapPoints1[i] < 0) continue;                  // !pMP1
+    const Sim3MapPointView& pMP1 = pKF1.mvMapPoints[(size_t)vpMapPoints1[i]];
+    const Sim3MapPointView& pMP2 = pKF2.mvMapPoints[(size_t)vpMatches1[i]];
+    const int i2 = pMP2.mnIndexInKeyFrame;                                               // pMP2->GetIndexInKeyFrame(pKF2)
+    if (pMP1.mbBad || pMP2.mbBad || i2 < 0) continue;
+    for (int r = 0; r < 3; ++r) g.x3dc1.push_back(cms_sim3_row(pKF1.Rcw + 3 * r, pMP1.mWorldPos(0), pMP1.mWorldPos(1), pMP1.mWorldPos(2), pKF1.tcw[r]));
+    for (int r = 0; r < 3; ++r) g.x3dc2.push_back(cms_sim3_row(pKF2.Rcw + 3 * r, pMP2.mWorldPos(0), pMP2.mWorldPos(1), pMP2.mWorldPos(2), pKF2.tcw[r]));
+    g.kp1.push_back(pKF1.mvKeyPts[(size_t)i].x); g.kp1.push_back(pKF1.mvKeyPts[(size_t)i].y);
+    g.kp2.push_back(pKF2.mvKeyPts[(size_t)i2].x); g.kp2.push_back(pKF2.mvKeyPts[(size_t)i2].y);
+    g.invSigma2_1.push_back(pKF1.mvInvLevelSigma2[(size_t)pKF1.mvKeyOctaves[(size_t)i]]);
+    g.invSigma2_2.push_back(pKF2.mvInvLevelSigma2[(size_t)pKF2.mvKeyOctaves[(size_t)i2]]);
+    g.vnIndexEdge.push_back((size_t)i);
+  }
+  return g;
+}
+
+int Optimizer::OptimizeSim3(const Sim3OptKeyFrameView& pKF1, const Sim3OptKeyFrameView& pKF2, std::vector<int>& vpMatches1, Sim3Value& g2oS12, const float th2,
+                            const bool bFixScale, Engine engine, int jacobian) {
+  Sim3OptGraph g = CollectSim3Graph(pKF1, pKF2, vpMatches1);
+  const int n = (int)g.vnIndexEdge.size();
+  std::vector<uint8_t> keep((size_t)n + 1, 1);
+  for (std::vector<float>* v : {&g.x3dc1, &g.x3dc2, &g.kp1, &g.kp2, &g.invSigma2_1, &g.invSigma2_2}) v->push_back(0.0f);      // (never empty: data() stays valid)
+  cms_sim3_opt_job q = {};
+  q.N = n; q.x3dc1 = g.x3dc1.data(); q.x3dc2 = g.x3dc2.data(); q.kp1 = g.kp1.data(); q.kp2 = g.kp2.data(); q.inv_sigma2_1 = g.invSigma2_1.data(); q.inv_sigma2_2 = g.invSigma2_2.data();
+  std::memcpy(q.R12, g2oS12.R, sizeof(q.R12)); std::memcpy(q.t12, g2oS12.t, sizeof(q.t12)); q.s12 = g2oS12.s;
+  q.th2 = th2; q.fix_scale = bFixScale ? 1 : 0; q.jacobian = jacobian; q.keep = keep.data();
+  if (engine == HOST_CORE) {
+    const int rc = hm_sim3_optimize_host(CamModelGeneral::GetCamera()->GetCubeFaceWidth(), 1, &q);
+    if (rc) throw std::runtime_error(std::string("Optimizer::OptimizeSim3: the job was refused: ") + hm_sim3_opt_last_reason());
+  } else {
+    cms_ctx* ctx = SharedContext(g_ctx_orb.nfeatures > 0 ? g_ctx_orb.nfeatures : 1000, g_ctx_orb.nfeatures > 0 ? g_ctx_orb.scale_factor : 1.2f,
+                                 g_ctx_orb.nfeatures > 0 ? g_ctx_orb.nlevels : 8, g_ctx_orb.nfeatures > 0 ? g_ctx_orb.ini_th_fast : 20,
+                                 g_ctx_orb.nfeatures > 0 ? g_ctx_orb.min_th_fast : 7);
+    cms_sim3_opt* h = nullptr;
+    if (cms_sim3_opt_create(&h, 0, 1, std::max(n, 1))) throw std::runtime_error(std::string("cms_sim3_opt_create: ") + cms_last_error());
+    const int rc = cms_sim3_optimize(h, ctx, 1, &q);
+    cms_sim3_opt_destroy(h);
+    if (rc) throw std::runtime_error(std::string("cms_sim3_optimize: ") + cms_last_error());
+  }
+  for (int k = 0; k < n; ++k)
+    if (!keep[(size_t)k]) vpMatches1[g.vnIndexEdge[(size_t)k]] = -1;      // vpMatches1[idx] = NULL (:1046, :1080)
+  std::memcpy(g2oS12.q, q.q12, sizeof(g2oS12.q)); std::memcpy(g2oS12.t, q.t12_out, sizeof(g2oS12.t)); g2oS12.s = q.s12_out;
+  return q.n_inliers;
+}
+
 // ------------------------------------------------------------------------------------------------ Initializer (src/Initializer.cpp)
 extern "C" int hm_init_two_view_host(int F, float cos_fov, int njobs, cms_init_job* jobs);      // init_host.cpp: the host build of csrc/cms_init_core.h
 

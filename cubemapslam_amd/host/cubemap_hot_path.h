@@ -422,8 +422,35 @@ class LocalMapping {
   static std::vector<NewMapPoint> CreateNewMapPoints(const KeyFrameView& current, const std::vector<const KeyFrameView*>& vpNeighKFs);
 };
 
+// What Optimizer::OptimizeSim3 (src/Optimizer.cpp:888-1091) reads of a key frame beyond what Sim3Solver does: mvKeys[i].pt and mvInvLevelSigma2.
+struct Sim3OptKeyFrameView : Sim3KeyFrameView {
+  std::vector<cv::Point2f> mvKeyPts;           // mvKeys[i].pt, cubemap image coordinates
+  std::vector<float> mvInvLevelSigma2;
+};
+// g2oS12.  In: R (row major) | t | s, what LoopClosing.cpp:324 hands g2o::Sim3(R, t, s).  Out: q (x y z w) | t | s, the optimised estimate; R is left alone.
+struct Sim3Value {
+  double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0}, s = 1;
+  double q[4] = {0, 0, 0, 1};
+};
+// The graph of :939-1028 as the arrays of one cms_sim3_opt_job; vnIndexEdge[k] = the key point of key frame 1 (entry of vpMatches1) behind pair k
+struct Sim3OptGraph {
+  std::vector<float> x3dc1, x3dc2, kp1, kp2, invSigma2_1, invSigma2_2;
+  std::vector<size_t> vnIndexEdge;
+};
+
 class Optimizer {
  public:
+  enum Engine { DEVICE = 0, HOST_CORE = 1 };
+  // Optimizer.cpp:888-1091.  vpMatches1[i] = index into pKF2.mvMapPoints of the map point matched to key point i of pKF1, -1 = NULL; entries the
+  // reference nulls (:1046, :1080) become -1.  The pointer work of :941-978 is CollectSim3Graph: !pMP1 || !pMP2, isBad, GetIndexInKeyFrame(pKF2) < 0,
+  // P3D1c / P3D2c = Rcw Xw + tcw by the gemm rule of Sim3Solver's constructor, mvKeys[i].pt / mvKeys[i2].pt, mvInvLevelSigma2[octave].  The rest is
+  // one cms_sim3_optimize call on the shared context's device (engine DEVICE, the default) or the host build of the same core (engine HOST_CORE: the
+  // definition of record, no GPU needed; an explicit choice, never a fall-back).  jacobian: CMS_SIM3_OPT_AS_WRITTEN (the reference's numeric
+  // Jacobian) or CMS_SIM3_OPT_ANALYTIC.  Returns nIn; 0 with g2oS12's q | t | s = the start when fewer than 10 pairs survive the first round.
+  static int OptimizeSim3(const Sim3OptKeyFrameView& pKF1, const Sim3OptKeyFrameView& pKF2, std::vector<int>& vpMatches1, Sim3Value& g2oS12, const float th2,
+                          const bool bFixScale, Engine engine = DEVICE, int jacobian = 0);
+  static Sim3OptGraph CollectSim3Graph(const Sim3OptKeyFrameView& pKF1, const Sim3OptKeyFrameView& pKF2, const std::vector<int>& vpMatches1);
+
   // Optimizer.cpp:48-190: edges collected exactly like :80-127 (rays with z < cosFovTh skipped, face + in-face measurement of
   // the key point, invSigma2 of its octave, map point through float), the four optimisation rounds run in one GPU kernel
   // (cms_pose_optimize), the pose is written back through float (Converter::toCvMat).  Returns nInitialCorrespondences - nBad.

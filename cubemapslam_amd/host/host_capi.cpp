@@ -613,6 +613,51 @@ extern "C" int hm_sim3_mirror(int engine, int n1, int nk1, int nk2, int nlevels,
     return 0;)
 }
 
+// Optimizer::OptimizeSim3 through the mirror.  Per key frame k = 1, 2: Tcw (3 x 4: Rcw | tcw), inv_sigma2 (nlevels), octave and kpts (nk key points, x y),
+// pos / bad / index_in_kf (np map points).  mp1[nk1] = GetMapPointMatches() of key frame 1, matches1[n1] in/out = vpMatches1 as indices into key frame
+// 2's map points (-1 = NULL).  S12[13] = R | t | s in.  Outputs: *N_out and idx[N] = vnIndexEdge, x12[N x 6] = P3D1c | P3D2c, kp12[N x 4] = kp1 | kp2,
+// is12[N x 2] = both invSigma2 (room for n1 pairs each), out8 = q (x y z w) | t | s, *n_inliers.  Returns 0, or -1 with hm_last_error().
+extern "C" int hm_sim3_opt_mirror(int engine, int jacobian, int n1, int nk1, int nk2, int nlevels, int np1, int np2, const float* Tcw1, const float* inv_sigma2_1,
+                                  const int* octave1, const float* kpts1, const float* pos1, const uint8_t* bad1, const int* index1, const float* Tcw2,
+                                  const float* inv_sigma2_2, const int* octave2, const float* kpts2, const float* pos2, const uint8_t* bad2, const int* index2,
+                                  const int* mp1, int* matches1, const double* S12, float th2, int fix_scale, int* N_out, int* idx, float* x12, float* kp12, float* is12,
+                                  double* out8, int* n_inliers) {
+  HM_TRY(
+    auto fill = [&](Sim3OptKeyFrameView& k, int nk, int np, const float* Tcw, const float* inv, const int* octave, const float* kpts, const float* pos, const uint8_t* bad,
+                    const int* index) {
+      for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) k.Rcw[3 * r + c] = Tcw[4 * r + c]; k.tcw[r] = Tcw[4 * r + 3]; }
+      k.mvInvLevelSigma2.assign(inv, inv + nlevels);
+      k.mvKeyOctaves.assign(octave, octave + nk);
+      k.mvKeyPts.resize(nk);
+      for (int i = 0; i < nk; ++i) k.mvKeyPts[i] = cv::Point2f(kpts[2 * (size_t)i], kpts[2 * (size_t)i + 1]);
+      k.mvMapPoints.resize(np);
+      for (int i = 0; i < np; ++i) {
+        for (int c = 0; c < 3; ++c) k.mvMapPoints[i].mWorldPos(c) = pos[3 * (size_t)i + c];
+        k.mvMapPoints[i].mbBad = bad[i] != 0; k.mvMapPoints[i].mnIndexInKeyFrame = index[i];
+      }
+    };
+    Sim3OptKeyFrameView k1; Sim3OptKeyFrameView k2;
+    fill(k1, nk1, np1, Tcw1, inv_sigma2_1, octave1, kpts1, pos1, bad1, index1);
+    fill(k2, nk2, np2, Tcw2, inv_sigma2_2, octave2, kpts2, pos2, bad2, index2);
+    k1.mvpMapPointMatches.assign(mp1, mp1 + nk1);
+    std::vector<int> vpMatches1(matches1, matches1 + n1);
+    const Sim3OptGraph g = Optimizer::CollectSim3Graph(k1, k2, vpMatches1);
+    const int N = (int)g.vnIndexEdge.size();
+    *N_out = N;
+    for (int k = 0; k < N; ++k) {
+      idx[k] = (int)g.vnIndexEdge[(size_t)k];
+      for (int c = 0; c < 3; ++c) { x12[6 * (size_t)k + c] = g.x3dc1[3 * (size_t)k + c]; x12[6 * (size_t)k + 3 + c] = g.x3dc2[3 * (size_t)k + c]; }
+      for (int c = 0; c < 2; ++c) { kp12[4 * (size_t)k + c] = g.kp1[2 * (size_t)k + c]; kp12[4 * (size_t)k + 2 + c] = g.kp2[2 * (size_t)k + c]; }
+      is12[2 * (size_t)k] = g.invSigma2_1[(size_t)k]; is12[2 * (size_t)k + 1] = g.invSigma2_2[(size_t)k];
+    }
+    Sim3Value S;
+    std::memcpy(S.R, S12, 72); std::memcpy(S.t, S12 + 9, 24); S.s = S12[12];
+    *n_inliers = Optimizer::OptimizeSim3(k1, k2, vpMatches1, S, th2, fix_scale != 0, engine ? Optimizer::HOST_CORE : Optimizer::DEVICE, jacobian);
+    std::memcpy(matches1, vpMatches1.data(), sizeof(int) * (size_t)n1);
+    std::memcpy(out8, S.q, 32); std::memcpy(out8 + 4, S.t, 24); out8[7] = S.s;
+    return 0;)
+}
+
 // Initializer through the mirror: the reference frame (n1 key points, rays) and the current frame (n2), vMatches12 (n1).  draws: the values the
 // replaceable draw function hands out in order (it must not run dry; n_draws < 0 keeps the class's default draw).  vP3D / vbTriangulated go in holding the caller's pattern, so that "left as they
 // were" shows.  Outputs: R21 (9, zeros when empty), t21 (3), p3d (3 per entry of vP3D), tri, sets[8 * iterations] = mvSets, state[0..11] = found, draws

@@ -817,6 +817,48 @@ int cms_kfstore_search_by_sim3(cms_kfstore* st, cms_ctx* src, int njobs, const c
                                const uint8_t* skip, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* mp_desc,
                                float th, int z_as_written, int* idx2, int* n_found);
 
+/* ---- Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cpp:888-1091), which LoopClosing::ComputeSim3 runs on
+ * every hypothesis behind cms_kfstore_search_by_sim3 (src/LoopClosing.cpp:324-326; the candidate is kept on >= 20 inliers): every accepted hypothesis
+ * of a pass as ONE launch, one workgroup per job with both optimize() rounds, the Levenberg accept / reject loop and the two classifications inside
+ * the kernel.  g2o is not in the tree and libm's exp / sin / cos differ from the device's in ulps, so the definition of record is the project's own
+ * core, csrc/cms_sim3_opt_core.h (DESIGN.md "OptimizeSim3"): one source, built for the host (libcubemapslam_host.so: hm_sim3_optimize_host) and for
+ * the device, which is held to the host build bit for bit.
+ *   The graph (:939-1028): per kept correspondence k the fixed points x3dc1[k] = R1w*P3D1w + t1w and x3dc2[k] = R2w*P3D2w + t2w (float, widened),
+ *   e12 = EdgeSim3ProjectXYZMultiPinhole with obs kp1[k] (face = FaceInCubemap, _measurementInFace = GetPosInFace in double, information =
+ *   inv_sigma2_1[k] * I), e21 = EdgeInverseSim3ProjectXYZMultiPinhole with kp2[k] / inv_sigma2_2[k]; Huber on both with delta = (float)sqrt(th2).
+ *   The pointer work of :941-978 (!pMP1 || !pMP2, isBad, GetIndexInKeyFrame < 0) is the caller's: the N records are the correspondences the loop
+ *   keeps, in key-point order of key frame 1.  The start is Sim3(R12, t12, s12) as :324 builds gScm.
+ *   optimize(5); pairs with chi2_12 > th2 || chi2_21 > th2 go (keep[k] = 0 <=> vpMatches1[idx] = NULL); fewer than 10 left: n_inliers = 0 and the
+ *   Sim3 out is the start (:1061); else optimize(nBad > 0 ? 10 : 5), the final classification, n_inliers = nIn.  Huber stays on in both rounds.
+ *   jacobian: CMS_SIM3_OPT_AS_WRITTEN (0) -- both edges have linearizeOplus commented out, so g2o differentiates them numerically with delta = 1e-9
+ *   through a projection that returns float: the Jacobian is almost entirely exact zeros, and the call is mostly an inlier filter around the start.
+ *   CMS_SIM3_OPT_ANALYTIC (1): the analytic derivative of the double projection; errors and chi2 go through the float projection either way.
+ *   Out: n_inliers (the reference's return value), keep (N bytes), q12 (x y z w) | t12_out | s12_out = the optimised g2oS12, n_correspondences (= N),
+ *   n_bad (the first classification's), iterations[2] = Levenberg iterations run by the two optimize() calls.
+ *   Synchronous; one launch sequence per call on the handle's stream: one pinned block up, one launch, one block back.  ctx supplies the face size
+ *   F and the device; nothing is enqueued on its stream.  Checked before anything is enqueued (CMS_ERR_ARG, the reason in cms_last_error, the
+ *   records untouched): a null array, more jobs / correspondences than cms_sim3_opt_create was given, th2 or s12 not finite or <= 0, jacobian
+ *   outside {0, 1}, a context on another device, a key point that lies in no face -- one stated difference: the reference's computeError calls
+ *   exit() there.  njobs == 0 is CMS_OK with no launch; N == 0 returns 0 inliers.  One caller at a time per handle. */
+#define CMS_SIM3_OPT_AS_WRITTEN 0
+#define CMS_SIM3_OPT_ANALYTIC 1
+typedef struct cms_sim3_opt cms_sim3_opt;
+int cms_sim3_opt_create(cms_sim3_opt** out, int device, int max_jobs, int max_corr_total);
+void cms_sim3_opt_destroy(cms_sim3_opt* p);
+typedef struct {
+  int N;                        /* kept correspondences, in key-point order of key frame 1 */
+  const float* x3dc1;           /* N x 3  P3D1c */
+  const float* x3dc2;           /* N x 3  P3D2c */
+  const float* kp1;             /* N x 2  pKF1->mvKeys[i].pt, cubemap image coordinates */
+  const float* kp2;             /* N x 2  pKF2->mvKeys[i2].pt */
+  const float* inv_sigma2_1;    /* N      pKF1->mvInvLevelSigma2[kp1.octave] */
+  const float* inv_sigma2_2;    /* N      pKF2->mvInvLevelSigma2[kp2.octave] */
+  double R12[9], t12[3], s12;   /* the start: Sim3Solver's estimate, R row major */
+  float th2; int fix_scale, jacobian;
+  int n_inliers; uint8_t* keep; double q12[4], t12_out[3], s12_out; int n_correspondences, n_bad, iterations[2];   /* out */
+} cms_sim3_opt_job;
+int cms_sim3_optimize(cms_sim3_opt* p, cms_ctx* ctx /* F */, int njobs, cms_sim3_opt_job* jobs);
+
 /* ---- Initializer (include/Initializer.h, src/Initializer.cpp), the two-view essential-matrix RANSAC of Tracking::MonocularInitialization
  * (src/Tracking.cpp:443), behind cms_search_for_initialization.  ComputeE21 takes the last row of a FULL_UV SVD of an 8 x 9 matrix, which OpenCV
  * completes from a basis nobody can pin (DESIGN.md "Initializer"), so the definition of record is the project's own core, csrc/cms_init_core.h: one

@@ -950,6 +950,77 @@ void IterateSim3(cms_sim3* sim3, cms_ctx* frameCtx, const std::vector<Sim3Solver
   }
 }
 
+// ------------------------------------------------------------------------------------------------ LoopClosing::ComputeSim3: Optimizer::OptimizeSim3
+cms_sim3_opt* CreateSim3Optimizer(int maxHypotheses, int maxCorrespondences) {
+  cms_sim3_opt* opt = nullptr;
+  check(cms_sim3_opt_create(&opt, g_device, maxHypotheses, maxCorrespondences), "cms_sim3_opt_create");
+  return opt;
+}
+
+void OptimizeSim3Candidates(cms_sim3_opt* opt, cms_ctx* ctx, KeyFrame* pKF1, const std::vector<KeyFrame*>& vpKF2, std::vector<std::vector<MapPoint*> >& vvpMatches1,
+                            const std::vector<cv::Mat>& vR12, const std::vector<cv::Mat>& vt12, const std::vector<float>& vs12, float th2, bool bFixScale,
+                            std::vector<Sim3Estimate>& vS12, std::vector<int>& vnInliers, int jacobian) {
+  const size_t nH = vpKF2.size();
+  if (vvpMatches1.size() != nH || vR12.size() != nH || vt12.size() != nH || vs12.size() != nH) throw std::runtime_error("Hip::OptimizeSim3Candidates: one entry per hypothesis");
+  vS12.assign(nH, Sim3Estimate()); vnInliers.assign(nH, 0);
+  if (nH == 0) return;
+  struct Arrays { std::vector<float> x1, x2, k1, k2, i1, i2; std::vector<uint8_t> keep; std::vector<size_t> vnIndexEdge; };
+  std::vector<Arrays> arr(nH);
+  std::vector<cms_sim3_opt_job> jobs(nH);
+  const cv::Mat R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation();
+  const std::vector<MapPoint*> vpMapPoints1 = pKF1->GetMapPointMatches();
+  for (size_t h = 0; h < nH; ++h) {
+    KeyFrame* pKF2 = vpKF2[h];
+    Arrays& a = arr[h];
+    const cv::Mat R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
+    const int N = (int)vvpMatches1[h].size();
+    for (int i = 0; i < N; ++i) {      // :941-1028
+      MapPoint* pMP2 = vvpMatches1[h][i];
+      if (!pMP2) continue;
+      MapPoint* pMP1 = vpMapPoints1[i];
+      const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+      if (!pMP1 || pMP1->isBad() || pMP2->isBad() || i2 < 0) continue;
+      const cv::Mat P3D1c = R1w * pMP1->GetWorldPos() + t1w, P3D2c = R2w * pMP2->GetWorldPos() + t2w;
+      const cv::KeyPoint& kp1 = pKF1->mvKeys[i];
+      const cv::KeyPoint& kp2 = pKF2->mvKeys[i2];
+      for (int c = 0; c < 3; ++c) { a.x1.push_back(P3D1c.at<float>(c)); a.x2.push_back(P3D2c.at<float>(c)); }
+      a.k1.push_back(kp1.pt.x); a.k1.push_back(kp1.pt.y); a.k2.push_back(kp2.pt.x); a.k2.push_back(kp2.pt.y);
+      a.i1.push_back(pKF1->mvInvLevelSigma2[kp1.octave]); a.i2.push_back(pKF2->mvInvLevelSigma2[kp2.octave]);
+      a.vnIndexEdge.push_back((size_t)i);
+    }
+    const int n = (int)a.vnIndexEdge.size();
+    a.keep.assign((size_t)n + 1, 1);
+    a.x1.push_back(0.0f); a.x2.push_back(0.0f); a.k1.push_back(0.0f); a.k2.push_back(0.0f); a.i1.push_back(0.0f); a.i2.push_back(0.0f);      // (never empty: data() stays valid)
+    cms_sim3_opt_job& q = jobs[h];
+    std::memset(&q, 0, sizeof(q));
+    q.N = n; q.x3dc1 = a.x1.data(); q.x3dc2 = a.x2.data(); q.kp1 = a.k1.data(); q.kp2 = a.k2.data(); q.inv_sigma2_1 = a.i1.data(); q.inv_sigma2_2 = a.i2.data();
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) q.R12[3 * r + c] = vR12[h].at<float>(r, c); q.t12[r] = vt12[h].at<float>(r); }
+    q.s12 = vs12[h]; q.th2 = th2; q.fix_scale = bFixScale ? 1 : 0; q.jacobian = jacobian; q.keep = a.keep.data();
+  }
+  check(cms_sim3_optimize(opt, ctx, (int)nH, jobs.data()), "cms_sim3_optimize");
+  for (size_t h = 0; h < nH; ++h) {
+    const cms_sim3_opt_job& q = jobs[h];
+    for (int k = 0; k < q.N; ++k)
+      if (!arr[h].keep[(size_t)k]) vvpMatches1[h][arr[h].vnIndexEdge[(size_t)k]] = static_cast<MapPoint*>(NULL);      // :1046, :1080
+    for (int c = 0; c < 4; ++c) vS12[h].q[c] = q.q12[c];
+    for (int c = 0; c < 3; ++c) vS12[h].t[c] = q.t12_out[c];
+    vS12[h].s = q.s12_out;
+    vnInliers[h] = q.n_inliers;
+  }
+}
+
+int OptimizeSim3(cms_sim3_opt* opt, cms_ctx* ctx, KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, const cv::Mat& R12, const cv::Mat& t12, float s12,
+                 float th2, bool bFixScale, Sim3Estimate& S12, int jacobian) {
+  std::vector<std::vector<MapPoint*> > vv(1, vpMatches1);
+  std::vector<Sim3Estimate> vS;
+  std::vector<int> vn;
+  OptimizeSim3Candidates(opt, ctx, pKF1, std::vector<KeyFrame*>(1, pKF2), vv, std::vector<cv::Mat>(1, R12), std::vector<cv::Mat>(1, t12), std::vector<float>(1, s12), th2,
+                         bFixScale, vS, vn, jacobian);
+  vpMatches1 = vv[0];
+  S12 = vS[0];
+  return vn[0];
+}
+
 // ---- Initializer (src/Initializer.cpp)
 Initializer::Initializer(const Frame& ReferenceFrame, float sigma, int iterations) : mSigma(sigma), mMaxIterations(iterations) {
   const size_t n1 = ReferenceFrame.mvKeys.size();

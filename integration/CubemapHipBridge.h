@@ -130,10 +130,26 @@ void SearchByBoWLoopCandidates(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pCurr
 // does; vnFound[h] = what SearchBySim3 returns.  vbAlreadyMatched1 / 2 are built here with GetIndexInKeyFrame (:1390-1400); positions, the distance
 // getters' values and descriptors of the map points travel with the call.  zAsWritten = true is the reference's line :1507 (the default: the
 // contract is the reference's result).  Both key frames must be resident; nothing runs on the store's stream (cms_kfstore_search_by_sim3), and the
-// store's book is locked from the look-up to the end of the call.  The caller goes on with Optimizer::OptimizeSim3, which stays host code.
+// store's book is locked from the look-up to the end of the call.  The caller goes on with Hip::OptimizeSim3 / Hip::OptimizeSim3Candidates (below).
 void SearchBySim3(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pCurrentKF, const std::vector<KeyFrame*>& vpKFs, std::vector<std::vector<MapPoint*> >& vvpMatches12,
                   const std::vector<float>& vs12, const std::vector<cv::Mat>& vR12, const std::vector<cv::Mat>& vt12, float th, std::vector<int>& vnFound,
                   bool zAsWritten = true);
+// ---- Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cpp:888-1091) behind SearchBySim3 (LoopClosing.cpp:324-326), for
+// one hypothesis or for every accepted hypothesis of a pass as ONE cms_sim3_optimize call.  The start is what :324 hands g2o::Sim3: the solver's R
+// (3 x 3 CV_32F), t (3 x 1 CV_32F) and s, widened as Converter::toMatrix3d / toVector3d do.  The pointer work of :941-978 is done here
+// (!pMP1 || !pMP2, isBad, GetIndexInKeyFrame < 0, Rcw Xw + tcw with the reference's own cv::Mat arithmetic, mvInvLevelSigma2[octave]);
+// vpMatches1[idx] becomes NULL where the reference nulls it; the return value / vnInliers[h] is the reference's.  The optimised g2oS12 comes back
+// as a Sim3Estimate: g2o::Sim3(Eigen::Quaterniond(q[3], q[0], q[1], q[2]), Eigen::Vector3d(t[0], t[1], t[2]), s); it is the start when the call
+// returns 0 at :1061.  jacobian = CMS_SIM3_OPT_AS_WRITTEN (default) is the reference's numeric Jacobian, CMS_SIM3_OPT_ANALYTIC the derivative.
+// One stated difference: a key point in no face makes the call throw where the reference's computeError calls exit().  `ctx` supplies the face size
+// and the device only; no key frame needs to be resident.
+struct Sim3Estimate { double q[4], t[3], s; };      // q = x y z w
+cms_sim3_opt* CreateSim3Optimizer(int maxHypotheses, int maxCorrespondences);
+void OptimizeSim3Candidates(cms_sim3_opt* opt, cms_ctx* ctx, KeyFrame* pKF1, const std::vector<KeyFrame*>& vpKF2, std::vector<std::vector<MapPoint*> >& vvpMatches1,
+                            const std::vector<cv::Mat>& vR12, const std::vector<cv::Mat>& vt12, const std::vector<float>& vs12, float th2, bool bFixScale,
+                            std::vector<Sim3Estimate>& vS12, std::vector<int>& vnInliers, int jacobian = CMS_SIM3_OPT_AS_WRITTEN);
+int OptimizeSim3(cms_sim3_opt* opt, cms_ctx* ctx, KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, const cv::Mat& R12, const cv::Mat& t12, float s12,
+                 float th2, bool bFixScale, Sim3Estimate& S12, int jacobian = CMS_SIM3_OPT_AS_WRITTEN);
 // ---- Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cpp) with the reference's surface, for LoopClosing::ComputeSim3 (LoopClosing.cpp:273-345).  The
 // constructor filters and orders as :66-127 does (with the reference's own cv::Mat arithmetic for Rcw Xw + tcw and its TransformRaysToCubemap);
 // iterate() makes the call's draws with DUtils::Random::RandomInt -- three per iteration, for max(mRansacMaxIts - mnIterations, nIterations)
