@@ -228,6 +228,21 @@ def remap_tiles_host(cam, lut, tile_w, tile_h, lds_budget=RT_LDS_MAX):
     return out[:n_all.value].copy(), n_live.value, lds.value
 
 
+def fast_cells_host(cam, which, nfeatures=2000, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7):
+    """cms_fast_cells_host: the FAST work list `which` (0 every cell, 1 without the zero corners, 2 the remapped batch's) as (level, row, column)
+    int arrays in the kernel's order, built on the host (no device)"""
+    cam = make_camera(cam) if isinstance(cam, dict) else cam
+    orb = OrbParams(nfeatures, scale_factor, nlevels, ini_th, min_th)
+    f = lib().cms_fast_cells_host
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    n = C.c_int()
+    _chk(f(C.byref(cam), C.byref(orb), which, None, 0, C.byref(n)), "cms_fast_cells_host")
+    out = np.zeros(max(n.value, 1), np.int32)
+    _chk(f(C.byref(cam), C.byref(orb), which, _p(out), len(out), C.byref(n)), "cms_fast_cells_host")
+    out = out[:n.value]
+    return out & 15, (out >> 4) & 255, (out >> 12) & 255
+
+
 class Context(_Handle):
     """cms_ctx: remap LUT + extractor tables + device buffers for up to max_batch frames."""
     _entries = ("cms_ctx_create", "cms_ctx_destroy")

@@ -85,7 +85,7 @@ struct cms_ctx {
   uint32_t* d_cand = nullptr; uint16_t* d_node = nullptr; int* d_cand_cnt = nullptr; int* d_overflow = nullptr;
   uint32_t* d_qt_out = nullptr; int* d_qt_cnt = nullptr;
   uint32_t* d_cell_cand = nullptr; int* d_cell_cnt = nullptr;
-  int* d_cells_all = nullptr; int* d_cells_nz = nullptr; int n_cells_all = 0, n_cells_nz = 0;   // FAST work lists
+  int* d_cells_all = nullptr; int* d_cells_live = nullptr; int n_cells_all = 0, n_cells_live = 0;   // FAST work lists (cms_fast_cell_lists)
   // frame grid (Frame::AssignFeaturesToGrid), allocated on first use
   uint16_t* d_area_sorted = nullptr; int* d_area_cell_start = nullptr; int* d_area_nvalid = nullptr; int area_frames = 0;
   int* d_area_psum = nullptr; int area_psum_cap = 0;         // one sum of counts per workgroup of k_area_query
@@ -208,12 +208,194 @@ static void cms_resize_table(int sn, int dn, bool clamp_frac, CmsResizeTab* out)
 
 #include "cms_api_util.h"
 
+// Level geometry, resize tables and FAST work lists: plain host code, no device (cms_ctx_create and cms_fast_cells_host share it).
+struct CmsLevelSetup {
+  float scale[CMS_MAX_LEVELS], inv_scale[CMS_MAX_LEVELS], sigma2[CMS_MAX_LEVELS], inv_sigma2[CMS_MAX_LEVELS];
+  size_t tab_off = 0;
+  int maxq = 0, wCellMax = 0, hCellMax = 0;
+};
+static int cms_level_geometry(const cms_camera* cam, const cms_orb_params* orb, CmsGeom& g, CmsLevelSetup* x) {
+  if (orb->nlevels < 1 || orb->nlevels > CMS_MAX_LEVELS) return cms_fail(CMS_ERR_UNSUPPORTED, "nlevels must be 1..12");
+  if (cam->face < 32 || 3 * cam->face > 4095) return cms_fail(CMS_ERR_UNSUPPORTED, "face size must satisfy 32 <= F and 3F <= 4095");
+  memset(&g, 0, sizeof(g));
+  const int L = orb->nlevels, F = cam->face, W = 3 * F;
+  float *scale = x->scale, *inv_scale = x->inv_scale, *sigma2 = x->sigma2, *inv_sigma2 = x->inv_sigma2;
+  g.nlevels = L; g.W = W; g.F = F; g.ini_th = orb->ini_th_fast; g.min_th = orb->min_th_fast;
+  // ---- ORBextractor::ORBextractor tables (ORBExtractor.cpp:386-418)
+  const double scaleFactor = orb->scale_factor;
+  scale[0] = 1.0f; sigma2[0] = 1.0f;
+  for (int i = 1; i < L; ++i) { scale[i] = (float)(scale[i - 1] * scaleFactor); sigma2[i] = scale[i] * scale[i]; }
+  for (int i = 0; i < L; ++i) { inv_scale[i] = 1.0f / scale[i]; inv_sigma2[i] = 1.0f / sigma2[i]; }
+  {
+    const float factor = (float)(1.0f / scaleFactor);
+    float nDesired = orb->nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)L));
+    int sum = 0;
+    for (int l = 0; l < L - 1; ++l) { g.lv[l].quota = (int)lrint((double)nDesired); sum += g.lv[l].quota; nDesired *= factor; }
+    g.lv[L - 1].quota = orb->nfeatures - sum > 0 ? orb->nfeatures - sum : 0;
+  }
+  // ---- level geometry (ORBExtractor.cpp:928-934, 745-762)
+  size_t off = 0, cand_off = 0; size_t& tab_off = x->tab_off;
+  int cell0 = 0, kp_off = 0; int &maxq = x->maxq, &wCellMax = x->wCellMax, &hCellMax = x->hCellMax;
+  for (int l = 0; l < L; ++l) {
+    CmsLevel& lv = g.lv[l];
+    lv.w = (int)lrint((double)((float)W * inv_scale[l]));
+    lv.h = lv.w;
+    if (lv.w < 2 * CMS_MINB + 30) { return cms_fail(CMS_ERR_UNSUPPORTED, "pyramid level too small for the FAST cell grid"); }
+    lv.stride = (int)cms_align((size_t)lv.w + 8, 128);
+    lv.off = off;
+    off += cms_align((size_t)lv.stride * (lv.h + 1), 256);
+    const float width = (float)(lv.w - 2 * CMS_MINB), height = (float)(lv.h - 2 * CMS_MINB);
+    lv.nCols = (int)(width / 30.f); lv.nRows = (int)(height / 30.f);
+    lv.wCell = (int)ceilf(width / lv.nCols); lv.hCell = (int)ceilf(height / lv.nRows);
+    lv.cell0 = cell0; cell0 += lv.nCols * lv.nRows;
+    lv.cand_cap = (lv.w * lv.h) / 4 + 4096;
+    lv.cand_off = cand_off; cand_off += cms_align((size_t)lv.cand_cap, 64);
+    lv.kp_off = kp_off; kp_off += lv.quota + 3;
+    lv.scale = scale[l];
+    lv.patch_size = (float)(int)(31 * scale[l]);
+    lv.tab_off = tab_off; tab_off += (size_t)lv.w + lv.h;
+    if (lv.quota > maxq) maxq = lv.quota;
+    if (lv.wCell > wCellMax) wCellMax = lv.wCell;
+    if (lv.hCell > hCellMax) hCellMax = lv.hCell;
+    if (lv.nCols > 255 || lv.nRows > 255) { return cms_fail(CMS_ERR_UNSUPPORTED, "more than 255 FAST cells per row"); }
+  }
+  g.total_cells = cell0; g.kp_cap = kp_off; g.pyr_bytes = off; g.cand_total = cand_off;
+  return CMS_OK;
+}
+
+// Resize tables, zero-corner extents and the three FAST work lists of a geometry (g.lv[].zlo / zhi are filled in):
+//   all  = every cell the reference loop visits (ORBExtractor.cpp:764-781);
+//   nz   = those not wholly inside the zero corner blocks of a remapped cross (same tests as in k_fast_cells);
+//   live = those of nz whose ROI is not constant for every remapped frame either.
+// A remapped canvas has two kinds of pixels that do not depend on the picture: the corner blocks (0) and the face pixels the reference never
+// writes (LUT entry 0: the frame's pixel (0, 0), cms_remap_tiles.h).  A pixel of level l keeps such a class when all four taps of its
+// bilinear blend have it at level l - 1 AND the blend of four equal taps returns that value for its coefficients, which is evaluated here
+// for c = 0 .. 255 with k_resize's own integer formula and not assumed: otherwise the pixel is "varying" from that level on.  FAST finds
+// nothing in a constant ROI, so such a cell leaves cell_cnt at 0 whether it is listed or not.
+enum { CMS_CLS_VARYING = 0, CMS_CLS_ZERO = 1, CMS_CLS_PIX00 = 2 };
+static int cms_fast_cell_lists(CmsGeom& g, size_t tab_entries, const uint32_t* lut, int lut_stride, std::vector<CmsResizeTab>& tab,
+                               std::vector<int>& all, std::vector<int>& nz, std::vector<int>& live) {
+  const int L = g.nlevels, F = g.F;
+  tab.assign(tab_entries, CmsResizeTab());
+  for (int l = 1; l < L; ++l) {
+    cms_resize_table(g.lv[l - 1].w, g.lv[l].w, true, &tab[g.lv[l].tab_off]);
+    cms_resize_table(g.lv[l - 1].h, g.lv[l].h, false, &tab[g.lv[l].tab_off + g.lv[l].w]);
+  }
+  // extent of the exactly-zero corner regions per level (exact, from the very tables k_resize uses): a destination
+  // pixel is zero when both source taps sx, sx+1 lie inside the previous level's zero region (w == h, x and y tables agree
+  // on the index part)
+  g.lv[0].zlo = F; g.lv[0].zhi = F;
+  for (int l = 1; l < L; ++l) {
+    const CmsResizeTab* tx = &tab[g.lv[l].tab_off];
+    const int sw = g.lv[l - 1].w, dw = g.lv[l].w;
+    int lo = 0, hi = 0;
+    while (lo < dw && std::min((int)tx[lo].s + 1, sw - 1) < g.lv[l - 1].zlo) ++lo;
+    while (hi < dw && (int)tx[dw - 1 - hi].s >= sw - g.lv[l - 1].zhi) ++hi;
+    g.lv[l].zlo = lo; g.lv[l].zhi = hi;
+  }
+  all.clear(); nz.clear(); live.clear();
+  std::vector<uint8_t> cls, prev;           // class map of level l and of level l - 1, w x h bytes
+  for (int l = 0; l < L; ++l) {
+    if (g.lv[l].nRows > 255 || g.lv[l].nCols > 255) return cms_fail(CMS_ERR_UNSUPPORTED, "cms_ctx_create: more than 255 FAST cells per row");
+    const CmsLevel& lv = g.lv[l];
+    prev.swap(cls);
+    cls.assign((size_t)lv.w * lv.h, (uint8_t)CMS_CLS_VARYING);
+    if (l == 0) {
+      for (int y = 0; y < lv.h; ++y)
+        for (int x = 0; x < lv.w; ++x) {
+          const bool corner = !(y >= F && y < 2 * F) && (x < F || x >= 2 * F);
+          cls[(size_t)y * lv.w + x] = corner ? CMS_CLS_ZERO : lut[(size_t)y * lut_stride + x] == 0 ? CMS_CLS_PIX00 : CMS_CLS_VARYING;
+        }
+    } else {
+      const CmsLevel& sv = g.lv[l - 1];
+      const CmsResizeTab* tx = &tab[lv.tab_off];
+      const CmsResizeTab* ty = tx + lv.w;
+      // does the blend with this column's / row's coefficients map four equal taps c to c?  (k_resize: h = c a0 + c a1 per source row, then
+      // v = ((b0 (h0 >> 4) >> 16) + (b1 (h1 >> 4) >> 16) + 2) >> 2.)  Columns must give h = 2048 c exactly; rows are then tried with that h.
+      std::vector<uint8_t> okx(lv.w), oky(lv.h);
+      for (int x = 0; x < lv.w; ++x) okx[x] = (int)tx[x].a0 + (int)tx[x].a1 == 2048 && tx[x].a0 >= 0 && tx[x].a1 >= 0;
+      for (int y = 0; y < lv.h; ++y) {
+        const uint32_t b0 = (uint32_t)ty[y].a0 & 0xFFFu, b1 = (uint32_t)ty[y].a1 & 0xFFFu;
+        bool ok = ty[y].a0 >= 0 && ty[y].a1 >= 0;
+        for (uint32_t c = 0; c < 256 && ok; ++c) {
+          const uint32_t h = ((c * 2048u) >> 4) & 0xFFFFu;
+          ok = (int)(((b0 * h) >> 16) + ((b1 * h) >> 16) + 2) >> 2 == (int)c;
+        }
+        oky[y] = ok;
+      }
+      for (int y = 0; y < lv.h; ++y) {
+        const int r0 = std::min(std::max((int)ty[y].s, 0), sv.h - 1), r1 = std::min(std::max((int)ty[y].s + 1, 0), sv.h - 1);
+        for (int x = 0; x < lv.w; ++x) {
+          const int c0 = tx[x].s, c1 = std::min((int)tx[x].s + 1, sv.w - 1);
+          const uint8_t k = prev[(size_t)r0 * sv.w + c0];
+          if (k != CMS_CLS_VARYING && okx[x] && oky[y] && prev[(size_t)r0 * sv.w + c1] == k && prev[(size_t)r1 * sv.w + c0] == k && prev[(size_t)r1 * sv.w + c1] == k)
+            cls[(size_t)y * lv.w + x] = k;
+        }
+      }
+    }
+    const int maxBX = lv.w - CMS_MINB, maxBY = lv.h - CMS_MINB;
+    for (int ci = 0; ci < lv.nRows; ++ci)
+      for (int cj = 0; cj < lv.nCols; ++cj) {
+        const int iniY = CMS_MINB + ci * lv.hCell, iniX = CMS_MINB + cj * lv.wCell;
+        if (iniY >= maxBY - 3 || iniX >= maxBX - 6) continue;
+        const int maxY = std::min(iniY + lv.hCell + 6, maxBY), maxX = std::min(iniX + lv.wCell + 6, maxBX);
+        if (maxX - iniX - 6 <= 0 || maxY - iniY - 6 <= 0) continue;
+        // list entry: level (4 bits) | row (8) | column (8): the kernel needs no division to find its cell
+        const int id = l | (ci << 4) | (cj << 12);
+        all.push_back(id);
+        const bool zero = (maxX <= lv.zlo || iniX >= lv.w - lv.zhi) && (maxY <= lv.zlo || iniY >= lv.h - lv.zhi);
+        if (zero) continue;
+        nz.push_back(id);
+        const uint8_t k = cls[(size_t)iniY * lv.w + iniX];
+        bool constant = k != CMS_CLS_VARYING;
+        for (int y = iniY; y < maxY && constant; ++y)
+          for (int x = iniX; x < maxX; ++x) if (cls[(size_t)y * lv.w + x] != k) { constant = false; break; }
+        if (!constant) live.push_back(id);
+      }
+  }
+  // Workgroups are dealt round-robin to the 8 XCDs (each with its own L2).  Listing the cells so that every XCD walks ONE
+  // contiguous eighth of the row-major cell order keeps the 128-byte lines that horizontally adjacent cells share inside one
+  // L2 (PMC: FETCH_SIZE of k_fast_cells was 2.8x the bytes of the non-zero cells with the plain order).
+  auto xcd_stripe = [](std::vector<int>& v) {
+    if (getenv("CMS_FAST_NO_XCD_STRIPE")) return;
+    const size_t n = v.size(), per = (n + 7) / 8;
+    std::vector<int> out;
+    out.reserve(n);
+    for (size_t j = 0; j < per; ++j)
+      for (size_t x = 0; x < 8; ++x) if (x * per + j < n) out.push_back(v[x * per + j]);
+    v.swap(out);
+  };
+  xcd_stripe(all); xcd_stripe(nz); xcd_stripe(live);
+  return CMS_OK;
+}
+
+// The FAST work lists of a camera and extractor configuration, built on the host (no device): which = 0 every cell, 1 without the zero
+// corner blocks, 2 also without the cells that are constant in every remapped frame (the list cms_frames_process(.., from_fisheye = 1) uses).
+// Entries: level | row << 4 | column << 12, in the order the kernel walks them.  *n = the list's length, also when it exceeds cap.
+extern "C" int cms_fast_cells_host(const cms_camera* cam, const cms_orb_params* orb, int which, int* out, int cap, int* n) {
+  if (!cam || !orb || !n || which < 0 || which > 2 || cap < 0 || (cap > 0 && !out)) return cms_fail(CMS_ERR_ARG, "cms_fast_cells_host: bad argument");
+  if (cam->Iw < 2 || cam->Ih < 2 || cam->Iw > 2047 || cam->Ih > 2047) return cms_fail(CMS_ERR_UNSUPPORTED, "fisheye size must be <= 2047");
+  CmsGeom g;
+  CmsLevelSetup ls{};
+  { const int rc = cms_level_geometry(cam, orb, g, &ls); if (rc != CMS_OK) return rc; }
+  const int lut_stride = (int)cms_align((size_t)g.W, 4);
+  std::vector<uint32_t> lut;
+  cms_build_lut(*cam, lut_stride, lut);
+  std::vector<CmsResizeTab> tab;
+  std::vector<int> lists[3];
+  { const int rc = cms_fast_cell_lists(g, ls.tab_off, lut.data(), lut_stride, tab, lists[0], lists[1], lists[2]); if (rc != CMS_OK) return rc; }
+  *n = (int)lists[which].size();
+  if (*n > cap) return cap == 0 ? CMS_OK : cms_fail(CMS_ERR_OVERFLOW, "cms_fast_cells_host: caller capacity too small");
+  if (*n) memcpy(out, lists[which].data(), (size_t)*n * sizeof(int));
+  return CMS_OK;
+}
+
 static void cms_ctx_free(cms_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   void* ptrs[] = {c->d_fish, c->d_lut, c->d_pyr, c->d_mask, c->d_tab, c->d_pattern, c->d_cand, c->d_node, c->d_cand_cnt,
                   c->d_overflow, c->d_qt_out, c->d_qt_cnt, c->d_kps, c->d_aux, c->d_order, c->d_aux_sorted, c->d_desc, c->d_kp_cnt, c->d_cell_cand,
-                  c->d_cell_cnt, c->d_cells_all, c->d_cells_nz, c->d_area_sorted, c->d_area_cell_start, c->d_area_nvalid, c->d_area_psum, c->d_area_tmp, c->d_walk_cnt, c->d_rays, c->d_rtiles};
+                  c->d_cell_cnt, c->d_cells_all, c->d_cells_live, c->d_area_sorted, c->d_area_cell_start, c->d_area_nvalid, c->d_area_psum, c->d_area_tmp, c->d_walk_cnt, c->d_rays, c->d_rtiles};
   for (void* p : ptrs) if (p) hipFree(p);
   cms_ctx_bow_free(c->bow);
   if (c->h_fish_stage) (void)hipHostFree(c->h_fish_stage);
@@ -241,48 +423,13 @@ extern "C" int cms_ctx_create(cms_ctx** out, int device, const cms_camera* cam, 
   cms_ctx* c = new cms_ctx;
   c->device = device; c->cam = *cam; c->orb = *orb; c->max_batch = max_batch;
   CmsGeom& g = c->g;
-  memset(&g, 0, sizeof(g));
   const int L = orb->nlevels, F = cam->face, W = 3 * F;
-  g.nlevels = L; g.W = W; g.F = F; g.ini_th = orb->ini_th_fast; g.min_th = orb->min_th_fast;
-  // ---- ORBextractor::ORBextractor tables (ORBExtractor.cpp:386-418)
-  const double scaleFactor = orb->scale_factor;
-  c->scale[0] = 1.0f; c->sigma2[0] = 1.0f;
-  for (int i = 1; i < L; ++i) { c->scale[i] = (float)(c->scale[i - 1] * scaleFactor); c->sigma2[i] = c->scale[i] * c->scale[i]; }
-  for (int i = 0; i < L; ++i) { c->inv_scale[i] = 1.0f / c->scale[i]; c->inv_sigma2[i] = 1.0f / c->sigma2[i]; }
-  {
-    const float factor = (float)(1.0f / scaleFactor);
-    float nDesired = orb->nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)L));
-    int sum = 0;
-    for (int l = 0; l < L - 1; ++l) { g.lv[l].quota = (int)lrint((double)nDesired); sum += g.lv[l].quota; nDesired *= factor; }
-    g.lv[L - 1].quota = orb->nfeatures - sum > 0 ? orb->nfeatures - sum : 0;
-  }
-  // ---- level geometry (ORBExtractor.cpp:928-934, 745-762)
-  size_t off = 0, cand_off = 0, tab_off = 0;
-  int cell0 = 0, kp_off = 0, maxq = 0, wCellMax = 0, hCellMax = 0;
-  for (int l = 0; l < L; ++l) {
-    CmsLevel& lv = g.lv[l];
-    lv.w = (int)lrint((double)((float)W * c->inv_scale[l]));
-    lv.h = lv.w;
-    if (lv.w < 2 * CMS_MINB + 30) { delete c; return cms_fail(CMS_ERR_UNSUPPORTED, "pyramid level too small for the FAST cell grid"); }
-    lv.stride = (int)cms_align((size_t)lv.w + 8, 128);
-    lv.off = off;
-    off += cms_align((size_t)lv.stride * (lv.h + 1), 256);
-    const float width = (float)(lv.w - 2 * CMS_MINB), height = (float)(lv.h - 2 * CMS_MINB);
-    lv.nCols = (int)(width / 30.f); lv.nRows = (int)(height / 30.f);
-    lv.wCell = (int)ceilf(width / lv.nCols); lv.hCell = (int)ceilf(height / lv.nRows);
-    lv.cell0 = cell0; cell0 += lv.nCols * lv.nRows;
-    lv.cand_cap = (lv.w * lv.h) / 4 + 4096;
-    lv.cand_off = cand_off; cand_off += cms_align((size_t)lv.cand_cap, 64);
-    lv.kp_off = kp_off; kp_off += lv.quota + 3;
-    lv.scale = c->scale[l];
-    lv.patch_size = (float)(int)(31 * c->scale[l]);
-    lv.tab_off = tab_off; tab_off += (size_t)lv.w + lv.h;
-    if (lv.quota > maxq) maxq = lv.quota;
-    if (lv.wCell > wCellMax) wCellMax = lv.wCell;
-    if (lv.hCell > hCellMax) hCellMax = lv.hCell;
-    if (lv.nCols > 255 || lv.nRows > 255) { delete c; return cms_fail(CMS_ERR_UNSUPPORTED, "more than 255 FAST cells per row"); }
-  }
-  g.total_cells = cell0; g.kp_cap = kp_off; g.pyr_bytes = off; g.cand_total = cand_off;
+  CmsLevelSetup ls{};
+  { const int rc = cms_level_geometry(cam, orb, g, &ls); if (rc != CMS_OK) { delete c; return rc; } }
+  memcpy(c->scale, ls.scale, sizeof(c->scale)); memcpy(c->inv_scale, ls.inv_scale, sizeof(c->inv_scale));
+  memcpy(c->sigma2, ls.sigma2, sizeof(c->sigma2)); memcpy(c->inv_sigma2, ls.inv_sigma2, sizeof(c->inv_sigma2));
+  const size_t tab_off = ls.tab_off;
+  const int maxq = ls.maxq, wCellMax = ls.wCellMax, hCellMax = ls.hCellMax;
   g.qt_maxn = 8;
   while (g.qt_maxn < maxq + 3) g.qt_maxn <<= 1;
   if (g.qt_maxn > 2048) { delete c; return cms_fail(CMS_ERR_UNSUPPORTED, "per-level feature quota above 2045 is not supported"); }
@@ -376,64 +523,17 @@ extern "C" int cms_ctx_create(cms_ctx** out, int device, const cms_camera* cam, 
       if (hipMalloc((void**)&c->d_rtiles, tiles.size() * sizeof(cms_remap_tile)) != hipSuccess) { cms_ctx_free(c); return cms_fail(CMS_ERR_HIP, "hipMalloc tile table"); }
       hipMemcpy(c->d_rtiles, tiles.data(), tiles.size() * sizeof(cms_remap_tile), hipMemcpyHostToDevice);
     }
-    std::vector<CmsResizeTab> tab(tab_off);
-    for (int l = 1; l < L; ++l) {
-      cms_resize_table(g.lv[l - 1].w, g.lv[l].w, true, &tab[g.lv[l].tab_off]);
-      cms_resize_table(g.lv[l - 1].h, g.lv[l].h, false, &tab[g.lv[l].tab_off + g.lv[l].w]);
-    }
-    // extent of the exactly-zero corner regions per level (exact, from the very tables k_resize uses): a destination
-    // pixel is zero when both source taps sx, sx+1 lie inside the previous level's zero region (w == h, x and y tables agree
-    // on the index part)
-    g.lv[0].zlo = F; g.lv[0].zhi = F;
-    for (int l = 1; l < L; ++l) {
-      const CmsResizeTab* tx = &tab[g.lv[l].tab_off];
-      const int sw = g.lv[l - 1].w, dw = g.lv[l].w;
-      int lo = 0, hi = 0;
-      while (lo < dw && std::min((int)tx[lo].s + 1, sw - 1) < g.lv[l - 1].zlo) ++lo;
-      while (hi < dw && (int)tx[dw - 1 - hi].s >= sw - g.lv[l - 1].zhi) ++hi;
-      g.lv[l].zlo = lo; g.lv[l].zhi = hi;
-    }
+    std::vector<CmsResizeTab> tab;
+    std::vector<int> all, nz, live;
+    { const int rc = cms_fast_cell_lists(g, tab_off, lut.data(), c->lut_stride, tab, all, nz, live); if (rc != CMS_OK) { cms_ctx_free(c); return rc; } }
     hipMemcpy(c->d_tab, tab.data(), tab.size() * sizeof(CmsResizeTab), hipMemcpyHostToDevice);
-    // FAST work lists: every cell the reference loop visits (ORBExtractor.cpp:764-781), and the subset that does not lie
-    // wholly inside the zero corner regions of a remapped cross (same tests as in k_fast_cells)
-    std::vector<int> all, nz;
-    for (int l = 0; l < L; ++l) {
-      if (g.lv[l].nRows > 255 || g.lv[l].nCols > 255) { cms_ctx_free(c); return cms_fail(CMS_ERR_UNSUPPORTED, "cms_ctx_create: more than 255 FAST cells per row"); }
-      const CmsLevel& lv = g.lv[l];
-      const int maxBX = lv.w - CMS_MINB, maxBY = lv.h - CMS_MINB;
-      for (int ci = 0; ci < lv.nRows; ++ci)
-        for (int cj = 0; cj < lv.nCols; ++cj) {
-          const int iniY = CMS_MINB + ci * lv.hCell, iniX = CMS_MINB + cj * lv.wCell;
-          if (iniY >= maxBY - 3 || iniX >= maxBX - 6) continue;
-          const int maxY = std::min(iniY + lv.hCell + 6, maxBY), maxX = std::min(iniX + lv.wCell + 6, maxBX);
-          if (maxX - iniX - 6 <= 0 || maxY - iniY - 6 <= 0) continue;
-          // list entry: level (4 bits) | row (8) | column (8): the kernel needs no division to find its cell
-          const int id = l | (ci << 4) | (cj << 12);
-          all.push_back(id);
-          const bool zero = (maxX <= lv.zlo || iniX >= lv.w - lv.zhi) && (maxY <= lv.zlo || iniY >= lv.h - lv.zhi);
-          if (!zero) nz.push_back(id);
-        }
-    }
-    // Workgroups are dealt round-robin to the 8 XCDs (each with its own L2).  Listing the cells so that every XCD walks ONE
-    // contiguous eighth of the row-major cell order keeps the 128-byte lines that horizontally adjacent cells share inside one
-    // L2 (PMC: FETCH_SIZE of k_fast_cells was 2.8x the bytes of the non-zero cells with the plain order).
-    auto xcd_stripe = [](std::vector<int>& v) {
-      if (getenv("CMS_FAST_NO_XCD_STRIPE")) return;
-      const size_t n = v.size(), per = (n + 7) / 8;
-      std::vector<int> out;
-      out.reserve(n);
-      for (size_t j = 0; j < per; ++j)
-        for (size_t x = 0; x < 8; ++x) if (x * per + j < n) out.push_back(v[x * per + j]);
-      v.swap(out);
-    };
-    xcd_stripe(all); xcd_stripe(nz);
-    c->n_cells_all = (int)all.size(); c->n_cells_nz = (int)nz.size();
+    c->n_cells_all = (int)all.size(); c->n_cells_live = (int)live.size();
     if (hipMalloc((void**)&c->d_cells_all, std::max<size_t>(all.size(), 1) * 4) != hipSuccess ||
-        hipMalloc((void**)&c->d_cells_nz, std::max<size_t>(nz.size(), 1) * 4) != hipSuccess) {
+        hipMalloc((void**)&c->d_cells_live, std::max<size_t>(live.size(), 1) * 4) != hipSuccess) {
       cms_ctx_free(c); return cms_fail(CMS_ERR_HIP, "hipMalloc cell lists");
     }
     hipMemcpy(c->d_cells_all, all.data(), all.size() * 4, hipMemcpyHostToDevice);
-    hipMemcpy(c->d_cells_nz, nz.data(), nz.size() * 4, hipMemcpyHostToDevice);
+    hipMemcpy(c->d_cells_live, live.data(), live.size() * 4, hipMemcpyHostToDevice);
     float patf[1024];
     for (int i = 0; i < 1024; ++i) patf[i] = (float)kOrbPattern[i];
     hipMemcpy(c->d_pattern, patf, sizeof(patf), hipMemcpyHostToDevice);
@@ -645,18 +745,20 @@ static int cms_launch_frames(cms_ctx* c, int B, int from_fisheye, const uint8_t*
     }
     const CmsLevel& d = g.lv[l];
     dim3 grid((d.w + 255) / 256, (d.h + CMS_RZ_ROWS - 1) / CMS_RZ_ROWS, B);
-    const int ls = (int)cms_align((size_t)ceil(256 * ratio) + 34, 16);    // LDS row stride of the staged source rectangle (16-byte columns)
     const int lrows = (int)ceil(CMS_RZ_ROWS * ratio) + 7;               // the kernel's integer bounds can be one row wider on either side
-    hipLaunchKernelGGL(k_resize, grid, block, (size_t)ls * lrows, s, c->d_pyr, g.pyr_bytes, g.lv[l - 1], d,
-                       (const CmsResizeTab*)(c->d_tab + d.tab_off), (const CmsResizeTab*)(c->d_tab + d.tab_off + d.w), ls, clean,
+    // CMS_RZ_LS = the kernel's LDS row stride; 16 spare bytes: the right tap of the last column of the last row is addressed, with weight 0
+    hipLaunchKernelGGL(k_resize, grid, block, (size_t)CMS_RZ_LS * lrows + 16, s, c->d_pyr, g.pyr_bytes, g.lv[l - 1], d,
+                       (const CmsResizeTab*)(c->d_tab + d.tab_off), (const CmsResizeTab*)(c->d_tab + d.tab_off + d.w), clean,
                        (int)floor(ratio * 65536.0), (int)ceil(ratio * 65536.0));
   }
   if (c->prof) hipEventRecord(c->ev[2], s);
   HIPCHK(hipMemsetAsync(c->d_cell_cnt, 0, (size_t)B * g.total_cells * sizeof(int), s));
   {
 #if CMS_FAST_LIST
-    const int* list = from_fisheye ? c->d_cells_nz : c->d_cells_all;
-    const int nlist = from_fisheye ? c->n_cells_nz : c->n_cells_all;
+    // a remapped canvas: without the cells that hold the same value in every remapped frame (every level is recomputed from the remap's
+    // output in this very launch, whatever a caller-supplied canvas left there before); a caller-supplied canvas: every cell
+    const int* list = from_fisheye ? c->d_cells_live : c->d_cells_all;
+    const int nlist = from_fisheye ? c->n_cells_live : c->n_cells_all;
 #else
     const int* list = nullptr;
     const int nlist = g.total_cells;

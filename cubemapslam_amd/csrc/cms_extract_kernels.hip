@@ -245,16 +245,27 @@ CMS_REMAP_TILE_KERNEL(k_remap_t64d, 64, false)
 CMS_REMAP_TILE_KERNEL(k_remap_t128d, 128, false)
 
 // ------------------------------------------------------------------------------------------------ resize
-// One workgroup (64 x 4 threads) produces a 256 x CMS_RZ_ROWS destination tile.  The source rectangle it needs (about 310 x 12
+// One workgroup (64 x 4 threads) produces a 256 x CMS_RZ_ROWS destination tile.  The source rectangle it needs (about 310 x 23
 // pixels at scale 1.2) is staged in LDS with coalesced dword loads; the 2 x 2 taps of every destination pixel are then
 // byte reads from LDS (a byte gather straight from global memory is bound by the texture-address path, not by HBM).
-// `ls` = LDS row stride in bytes (multiple of 4, <= 512).
+// The kernel is bound by its per-pixel integer work and its LDS byte reads, so the staged rectangle is laid out for few instructions per pixel:
+//  - one compile-time row stride, CMS_RZ_LS bytes (the staged width is at most 512: 32 sixteen-byte columns), so that the second
+//    source row of a pixel is the first one's address plus an immediate offset;
+//  - the right tap's address is the left one's + 1 computed ONCE per pixel column and hidden from the compiler (an empty asm): written as
+//    left + 1 the compiler fuses the two byte reads of a row into one unaligned 16-bit LDS read, which runs 4x slower.
+//    (Packing both taps into one register with ds_read_u8_d16 / ds_read_u8_d16_hi for a one-instruction blend does not work on this chip:
+//    with SRAM ECC on, a d16 load clears the other half of its destination instead of keeping it.)
+//  - no per-pixel clamps.  x: the table is built with clamped fractions, at s = src.w - 1 the right weight is 0 and the byte at + 1 (the next
+//    staged column, or the first byte of the next LDS row, or of the 16 spare bytes behind the last one) only has to be addressable.  y: the
+//    table is NOT clamped in its weights, the reference clamps the row index: source rows -1 and src.h are staged as copies of rows 0 and
+//    src.h - 1, so that row s + 1 is always the next LDS row.
 #ifndef CMS_RZ_ROWS
 #define CMS_RZ_ROWS 16
 #endif
+#define CMS_RZ_LS 512
 extern "C" __global__ void __launch_bounds__(256)
 k_resize(uint8_t* __restrict__ pyr, size_t pyr_bytes, CmsLevel src, CmsLevel dst,
-         const CmsResizeTab* __restrict__ tabx, const CmsResizeTab* __restrict__ taby, int ls, int skip_zero, int scale_lo, int scale_hi) {
+         const CmsResizeTab* __restrict__ tabx, const CmsResizeTab* __restrict__ taby, int skip_zero, int scale_lo, int scale_hi) {
   extern __shared__ __align__(16) uint8_t rtile[];
   const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 64 + tx;
   const int xb = blockIdx.x * 256, yb = blockIdx.y * CMS_RZ_ROWS, b = blockIdx.z;
@@ -265,11 +276,12 @@ k_resize(uint8_t* __restrict__ pyr, size_t pyr_bytes, CmsLevel src, CmsLevel dst
   // lies in [floor(d scale) - 1, floor((d + 1) scale)]), so the pixel loads do not wait for the coefficient-table loads.
   // scale_lo / scale_hi = the ratio rounded down / up to 16 fractional bits: (d scale_lo) >> 16 <= floor(d scale) <=
   // (d scale_hi + 65535) >> 16, all of it wave-uniform integer arithmetic on the scalar unit (the double-precision floor this
-  // replaces ran on the vector unit at half rate, 16 instructions per wave)
+  // replaces ran on the vector unit at half rate, 16 instructions per wave).  Rows r0 = -1 and r1 = src.h are the copies of the
+  // first and last source row.
   const int c0 = max(((xb * scale_lo) >> 16) - 1, 0) & ~15;
   const int c1 = min((((xl + 1) * scale_hi + 65535) >> 16) + 1, src.w - 1);
-  const int r0 = min(max(((yb * scale_lo) >> 16) - 1, 0), src.h - 1);
-  const int r1 = min((((yl + 1) * scale_hi + 65535) >> 16) + 1, src.h - 1);
+  const int r0 = min(((yb * scale_lo) >> 16) - 1, src.h - 1);
+  const int r1 = min((((yl + 1) * scale_hi + 65535) >> 16) + 1, src.h);
   const int nq = ((c1 - c0) >> 4) + 1, nr = r1 - r0 + 1;          // 16-byte columns (<= 32), rows
   const uint8_t* simg = pyr + (size_t)b * pyr_bytes + src.off;
   const int x0 = xb + 4 * tx;
@@ -282,18 +294,19 @@ k_resize(uint8_t* __restrict__ pyr, size_t pyr_bytes, CmsLevel src, CmsLevel dst
   for (int rr = 0; rr < CMS_RZ_ROWS / 4; ++rr) tyr[rr] = taby[min(yb + ty + 4 * rr, dst.h - 1)];
   {
     const int c = tid & 31, rs = tid >> 5;
-    const uint8_t* gp = simg + (size_t)r0 * src.stride + c0 + 16 * c;
+    const uint8_t* gp = simg + c0 + 16 * c;
     constexpr int NLD = (CMS_RZ_ROWS * 2 + 5 + 7) / 8;               // rows staged <= 1.9 * CMS_RZ_ROWS + 5
     uint4 tmp[NLD];
 #pragma unroll
     for (int k = 0; k < NLD; ++k) {
       const int r = rs + 8 * k;
-      tmp[k] = (c < nq && r < nr) ? *reinterpret_cast<const uint4*>(gp + (uint32_t)__mul24(r, src.stride)) : make_uint4(0, 0, 0, 0);
+      const int sr = min(max(r0 + r, 0), src.h - 1);
+      tmp[k] = (c < nq && r < nr) ? *reinterpret_cast<const uint4*>(gp + (uint32_t)__mul24(sr, src.stride)) : make_uint4(0, 0, 0, 0);
     }
 #pragma unroll
     for (int k = 0; k < NLD; ++k) {
       const int r = rs + 8 * k;
-      if (c < nq && r < nr) reinterpret_cast<uint4*>(rtile + __mul24(r, ls))[c] = tmp[k];
+      if (c < nq && r < nr) reinterpret_cast<uint4*>(rtile + r * CMS_RZ_LS)[c] = tmp[k];
     }
   }
   __syncthreads();
@@ -303,7 +316,8 @@ k_resize(uint8_t* __restrict__ pyr, size_t pyr_bytes, CmsLevel src, CmsLevel dst
   for (int i = 0; i < 4; ++i) {
     const CmsResizeTab t = t4[i];
     ca[i] = (int)t.s - c0;
-    cb[i] = min((int)t.s + 1, src.w - 1) - c0;
+    cb[i] = ca[i] + 1;
+    asm("" : "+v"(cb[i]));             // (see above: keeps the two byte reads apart)
     a0[i] = t.a0; a1[i] = t.a1;
   }
 #pragma unroll
@@ -311,17 +325,15 @@ k_resize(uint8_t* __restrict__ pyr, size_t pyr_bytes, CmsLevel src, CmsLevel dst
     const int y = yb + ty + 4 * rr;
     if (y >= dst.h) break;
     const CmsResizeTab tyy = tyr[rr];
-    const uint8_t* S0 = rtile + __mul24(min(max((int)tyy.s, 0), src.h - 1) - r0, ls);
-    const uint8_t* S1 = rtile + __mul24(min(max((int)tyy.s + 1, 0), src.h - 1) - r0, ls);
+    const uint8_t* S0 = rtile + ((int)tyy.s - r0) * CMS_RZ_LS;      // wave-uniform; row s + 1 is S0 + CMS_RZ_LS
     const int b0 = tyy.a0, b1 = tyy.a1;
     uint32_t out = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       // 8-bit pixels x 11-bit weights: 24-bit multiplies (full rate; the 32-bit integer multiply is not)
-      // (the right tap keeps its own address: written as left + 1 the two byte reads are fused into one unaligned 16-bit LDS read,
-      // which runs 4x slower)
-      const int h0 = __mul24(S0[ca[i]], a0[i]) + __mul24(S0[cb[i]], a1[i]);
-      const int h1 = __mul24(S1[ca[i]], a0[i]) + __mul24(S1[cb[i]], a1[i]);
+      const uint8_t* L = S0 + ca[i]; const uint8_t* R = S0 + cb[i];
+      const int h0 = __mul24(L[0], a0[i]) + __mul24(R[0], a1[i]);
+      const int h1 = __mul24(L[CMS_RZ_LS], a0[i]) + __mul24(R[CMS_RZ_LS], a1[i]);
       // weights are in [0, 2048], h >> 4 < 2^16: the masks tell the compiler so and it picks the 24-bit multiply
       const int v = (int)((((uint32_t)b0 & 0xFFFu) * (((uint32_t)h0 >> 4) & 0xFFFFu) >> 16) +
                           (((uint32_t)b1 & 0xFFFu) * (((uint32_t)h1 >> 4) & 0xFFFFu) >> 16) + 2) >> 2;
@@ -569,7 +581,7 @@ k_fast_cells(const uint8_t* __restrict__ pyr, size_t pyr_bytes, CmsGeom g, const
   const int slot = blockIdx.x * CMS_FAST_WPB + wave;
 #if CMS_FAST_LIST
   if (slot >= n_list) return;
-  // host-built list of the cells that can hold a corner (see cms_ctx_create); an entry carries level | row | column
+  // host-built list of the cells that can hold a corner (cms_fast_cell_lists); an entry carries level | row | column
   const int entry = cell_list[slot];
   const int l = entry & 15, ci = (entry >> 4) & 255, cj = (entry >> 12) & 255;
   const CmsLevel& lv = g.lv[l];
@@ -970,12 +982,11 @@ k_cull(CmsGeom g, const uint32_t* __restrict__ qt_out, const int* __restrict__ q
 // ------------------------------------------------------------------------------------------------ orientation + rBRIEF
 // One wavefront per surviving key point.  A 43x43 raw patch (taps reach +-18, the 7-tap blur +-3 more) is staged in
 // LDS with REFLECT_101 at the level edges, IC_Angle runs on its centre, then a separable fixed-point 7x7 Gaussian
-// ([18,34,49,55,49,34,18], (sum+32768)>>16) produces the 37x37 blurred neighbourhood the 512 steered taps read.
+// ([18,34,49,55,49,34,18], (sum+32768)>>16): the row pass over the whole patch, the column pass only at the 512 positions (inside the
+// 37x37 neighbourhood of the centre) that the steered taps read.
 #define PR 21
 #define PW 43
 #define PS 48
-#define BW 37
-#define BS 40
 #define RW 40            /* row-sum stride (16-bit entries): 10 quads per row */
 typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int reflect101(int i, int n) {
@@ -1006,13 +1017,12 @@ __device__ __forceinline__ void describe_body(const uint8_t* __restrict__ pyr, s
   // CMS_DESC_WPB key points per workgroup, one per wavefront, no data shared between them (wave-level synchronisation only)
   __shared__ __align__(16) uint8_t raw4[CMS_DESC_WPB][PW * PS + 16];
   __shared__ __align__(16) uint32_t rowp4[CMS_DESC_WPB][((PW + 1) / 2) * RW];      // row sums of rows 2m (low half) and 2m + 1 (high half), column by column
-  __shared__ __align__(4) uint8_t blr4[CMS_DESC_WPB][BW * BS];
 #if CMS_DESC_WPB == 1
   const int wave = 0, lane = threadIdx.x;
 #else
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #endif
-  uint8_t* raw = raw4[wave]; uint32_t* rowp = rowp4[wave]; uint8_t* blr = blr4[wave];
+  uint8_t* raw = raw4[wave]; uint32_t* rowp = rowp4[wave];
   // walk != nullptr (1-D grid): workgroups go round-robin to the 8 XCDs; XCD x works through the x-th eighth of the batch's walk (k_cull) in
   // order, so that patch rows shared by neighbouring key points are fetched into that XCD's L2 once
   int b, k;
@@ -1116,53 +1126,44 @@ __device__ __forceinline__ void describe_body(const uint8_t* __restrict__ pyr, s
     }
   }
   WAVE_SYNC();
-  // Column pass, four neighbouring columns per lane and step.  Output row ro needs the row sums ro .. ro + 6: four row PAIRS starting at pair
-  // ro >> 1 -- for an even ro the taps (18 34)(49 55)(49 34)(18 -), for an odd one (- 18)(34 49)(55 49)(34 18) -- four dot products of
-  // 16-bit pairs per output instead of seven multiplies and as many unpacking operations.
-  for (int task = lane; task < BW * (RW / 4); task += 64) {
-    const int r = __mul24(task, 6554) >> 16, q = task - r * (RW / 4);             // task / 10, exact for task < 494
-    const uint4* p = reinterpret_cast<const uint4*>(rowp + (r >> 1) * RW) + q;
-    const uint4 e0 = p[0], e1 = p[RW / 4], e2 = p[2 * (RW / 4)], e3 = p[3 * (RW / 4)];
+  // Column pass, only where BRIEF samples: of the 37 x 37 blurred block the 512 steered taps read 8 bytes per lane, so each lane evaluates the
+  // column pass at its own 8 positions straight from the row sums.  Output row ro needs the row sums ro .. ro + 6: four row PAIRS starting at
+  // pair ro >> 1 -- for an even ro the taps (18 34)(49 55)(49 34)(18 -), for an odd one (- 18)(34 49)(55 49)(34 18) -- four dot products of
+  // 16-bit pairs per sample, the four dwords of a column at one address plus immediate offsets.
+  auto blur_at = [&](int ry, int rx) -> int {
+    const int r = 18 + ry, c = 18 + rx;
+    const uint32_t* p = rowp + (r >> 1) * RW + c;
+    const uint32_t e0 = p[0], e1 = p[RW], e2 = p[2 * RW], e3 = p[3 * RW];
     const bool odd = (r & 1) != 0;
     const uint32_t w0 = odd ? (18u << 16) : (18u | (34u << 16)), w1 = odd ? (34u | (49u << 16)) : (49u | (55u << 16)),
                    w2 = odd ? (55u | (49u << 16)) : (49u | (34u << 16)), w3 = odd ? (34u | (18u << 16)) : 18u;
-    auto col = [&](uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3) -> int {
-      uint32_t acc = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, a0), __builtin_bit_cast(us2_t, w0), 0u, false);
-      acc = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, a1), __builtin_bit_cast(us2_t, w1), acc, false);
-      acc = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, a2), __builtin_bit_cast(us2_t, w2), acc, false);
-      acc = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, a3), __builtin_bit_cast(us2_t, w3), acc, false);
-      return (int)acc;
-    };
-    const int sv[4] = {col(e0.x, e1.x, e2.x, e3.x), col(e0.y, e1.y, e2.y, e3.y), col(e0.z, e1.z, e2.z, e3.z), col(e0.w, e1.w, e2.w, e3.w)};
-    uint32_t out = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int v = min((sv[i] + 32768) >> 16, 255);
-      if (SSE2) {
-        // an x86 OpenCV <= 3.2 evaluates the column pass in float with round-half-to-EVEN for the columns its SSE2 loops cover
-        // (x < width & ~3): every product and partial sum is exact in binary32, so the result
-        // differs from the integer formula exactly on ties (sum mod 65536 == 32768) with an even quotient
-        const int x0 = cx - 18 + 4 * q + i, xvec = lv.w & ~3;
-        if (x0 < xvec && (sv[i] & 0xFFFF) == 0x8000 && ((sv[i] >> 16) & 1) == 0) v = min(sv[i] >> 16, 255);
-      }
-      out |= (uint32_t)v << (8 * i);
+    uint32_t acc = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, e0), __builtin_bit_cast(us2_t, w0), 0u, false);
+    acc = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, e1), __builtin_bit_cast(us2_t, w1), acc, false);
+    acc = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, e2), __builtin_bit_cast(us2_t, w2), acc, false);
+    acc = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, e3), __builtin_bit_cast(us2_t, w3), acc, false);
+    const int sv = (int)acc;
+    int v = min((sv + 32768) >> 16, 255);
+    if (SSE2) {
+      // an x86 OpenCV <= 3.2 evaluates the column pass in float with round-half-to-EVEN for the columns its SSE2 loops cover
+      // (x < width & ~3): every product and partial sum is exact in binary32, so the result
+      // differs from the integer formula exactly on ties (sum mod 65536 == 32768) with an even quotient
+      const int x0 = cx - 18 + c, xvec = lv.w & ~3;
+      if (x0 < xvec && (sv & 0xFFFF) == 0x8000 && ((sv >> 16) & 1) == 0) v = min(sv >> 16, 255);
     }
-    *reinterpret_cast<uint32_t*>(blr + r * BS + 4 * q) = out;
-  }
-  WAVE_SYNC();
+    return v;
+  };
   // ---- steered BRIEF: lane i evaluates tests 4i .. 4i+3
   const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
   float sb, ca;
   cms_sincosf(angle * factorPI, &sb, &ca);
   const float4* pt4 = reinterpret_cast<const float4*>(pattern) + 4 * lane;      // float table: no int8 -> float conversions (32 per lane)
-  const uint8_t* ctr = blr + 18 * BS + 18;
   int nib = 0;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const float4 pq = pt4[t];
     const float x0 = pq.x, y0 = pq.y, x1 = pq.z, y1 = pq.w;
-    const int v0 = ctr[cms_cv_round(x0 * sb + y0 * ca) * BS + cms_cv_round(x0 * ca - y0 * sb)];
-    const int v1 = ctr[cms_cv_round(x1 * sb + y1 * ca) * BS + cms_cv_round(x1 * ca - y1 * sb)];
+    const int v0 = blur_at(cms_cv_round(x0 * sb + y0 * ca), cms_cv_round(x0 * ca - y0 * sb));
+    const int v1 = blur_at(cms_cv_round(x1 * sb + y1 * ca), cms_cv_round(x1 * ca - y1 * sb));
     nib |= (v0 < v1 ? 1 : 0) << t;
   }
   const int other = __shfl_xor(nib, 1);

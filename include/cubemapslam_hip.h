@@ -141,6 +141,15 @@ int cms_remap_lut_host(const cms_camera* cam, uint32_t* lut, int lut_stride);
 int cms_remap_tiles_host(const cms_camera* cam, const uint32_t* lut, int lut_stride, int tile_w, int tile_h, int lds_budget,
                          cms_remap_tile* out, int cap, int* n_live, int* n_all, int* lds_bytes);
 
+/* ---- the FAST work lists, host code only (no device is touched; cms_ctx_create builds the same lists once per context).
+ * which = 0: every cell the reference loop visits (ORBExtractor.cpp:764-781): the list of a caller-supplied canvas (cms_extract);
+ *         1: without the cells that lie wholly in the zero corner blocks of a remapped cross;
+ *         2: also without the cells whose whole ROI holds one value in every remapped frame -- corner blocks, or face pixels the reference never
+ *            writes (LUT entry 0: the frame's pixel (0, 0)), followed down the pyramid through the resize tables: the list of a remapped batch.
+ * Entries are level | row << 4 | column << 12 in the order k_fast_cells walks them.  *n = the list's length; cap = 0 only asks for it,
+ * CMS_ERR_OVERFLOW if 0 < cap < *n. */
+int cms_fast_cells_host(const cms_camera* cam, const cms_orb_params* orb, int which, int* out, int cap, int* n);
+
 /* ---- stage-by-stage read-back for the parity tests */
 int cms_debug_lut(cms_ctx* ctx, uint32_t* out, int* stride);
 int cms_debug_cubemap(cms_ctx* ctx, int b, uint8_t* dst, int dstride);

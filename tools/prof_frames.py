@@ -1,4 +1,5 @@
-"""Frame path only (remap + extract), B frames per launch (32 streams x 8 frames like bench.py), for rocprofv3 runs and A/B timing."""
+"""Frame path only (remap + extract), B frames per launch (32 streams x 8 frames like bench.py), for rocprofv3 runs and A/B timing.
+    python tools/prof_frames.py [B=256] [F=550] [iterations=10] [camera=lafida|front]"""
 import sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
@@ -7,7 +8,7 @@ import bench
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 F = int(sys.argv[2]) if len(sys.argv) > 2 else 550
 iters = int(sys.argv[3]) if len(sys.argv) > 3 else 10
-camd = synth.camera("lafida", F)
+camd = synth.camera(sys.argv[4] if len(sys.argv) > 4 else "lafida", F)
 ctx = api.Context(camd, nfeatures=camd["nfeatures"], max_batch=B)
 ctx.set_mask(synth.cubemap_valid_mask(camd))
 fps = 8 if B % 8 == 0 else 1
