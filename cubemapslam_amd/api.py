@@ -659,6 +659,11 @@ class Sim3SearchJob(C.Structure):
                 ("off1", C.c_int), ("off2", C.c_int)]
 
 
+class Sim3ProjJob(C.Structure):
+    """cms_sim3_proj_job (include/cubemapslam_hip.h)"""
+    _fields_ = [("slot", C.c_int), ("n", C.c_int), ("Scw", C.c_float * 12), ("set", C.c_int)]
+
+
 class KfProjJob(C.Structure):
     """cms_kfproj_job (include/cubemapslam_hip.h)"""
     _fields_ = [("slot", C.c_int), ("b", C.c_int), ("n", C.c_int), ("pose12", C.c_float * 12), ("nmp", C.c_int), ("kf_feat", C.c_void_p), ("pos", C.c_void_p),
@@ -997,6 +1002,59 @@ class KeyframeStore(_Handle):
         _chk(L.cms_kfstore_search_by_sim3(self.h, src_ctx.h, nj, arr, at if n_mp is None else n_mp, *[_p(v) for v in a], float(th), int(bool(z_as_written)), _p(idx2), _p(nf)),
              "cms_kfstore_search_by_sim3")
         return [(idx2[off[k]:off[k + 1]].copy(), int(nf[k])) for k in range(nj)]
+
+    def _sim3_proj_args(self, sets, jobs):
+        """the shared arguments of the two Sim3 projection entries.  sets: list of dict(pos, normal, min_dist, max_dist, desc); jobs: list of
+        dict(slot, n, Scw (3 x 4 or 4 x 4), set, skip (None or per point of the set), taken (None or n bytes; SearchByProjection only))"""
+        soff = np.concatenate([[0], np.cumsum([len(q["pos"]) for q in sets])]).astype(np.int32)
+
+        def cat(k, dt, tail):
+            if not sets:
+                return np.zeros((0,) + tail, dt)
+            return np.ascontiguousarray(np.concatenate([np.asarray(q[k], dt).reshape((-1,) + tail) for q in sets]), dt)
+        a = [cat("pos", np.float32, (3,)), cat("normal", np.float32, (3,)), cat("min_dist", np.float32, ()), cat("max_dist", np.float32, ()), cat("desc", np.uint8, (32,))]
+        nj = len(jobs)
+        arr = (Sim3ProjJob * max(nj, 1))()
+        sizes = []
+        for q, j in zip(arr, jobs):
+            q.slot = j["slot"]; q.n = j["n"]; q.set = j["set"]
+            q.Scw[:] = [float(v) for v in np.asarray(j["Scw"], np.float32).reshape(-1)[:12]]
+            sizes.append(int(soff[j["set"] + 1] - soff[j["set"]]) if 0 <= j["set"] < len(sets) else 0)
+        eoff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        skip = None
+        if any(j.get("skip") is not None for j in jobs):
+            skip = np.ascontiguousarray(np.concatenate([np.zeros(sz, np.uint8) if j.get("skip") is None else np.asarray(j["skip"], np.uint8) for j, sz in zip(jobs, sizes)]
+                                                       + [np.zeros(1, np.uint8)]), np.uint8)
+        return soff, a, arr, eoff, skip
+
+    def search_by_projection_sim3(self, src_ctx, sets, jobs, th=10.0, out=None):
+        """cms_kfstore_search_by_projection_sim3: ORBMatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (LoopClosing::ComputeSim3's last step)
+        for many (resident key frame, Scw, set of map points) jobs in ONE call on src_ctx's stream.  sets / jobs: see _sim3_proj_args; a job's taken
+        flags say vpMatched[idx] != NULL on entry and are not written.  out: (match_kp, n_matches) arrays to receive the results (pinned ones, say).
+        Returns per job (match_kp int32[points of its set]: the key point the point takes or -1; n_matches)."""
+        soff, a, arr, eoff, skip = self._sim3_proj_args(sets, jobs)
+        nj = len(jobs)
+        taken = np.ascontiguousarray(np.concatenate([np.zeros(max(int(j["n"]), 0), np.uint8) if j.get("taken") is None else np.asarray(j["taken"], np.uint8) for j in jobs]
+                                                    + [np.zeros(1, np.uint8)]), np.uint8)
+        mk, nm = out if out is not None else (np.full(max(int(eoff[-1]), 1), -1, np.int32), np.zeros(max(nj, 1), np.int32))
+        L = lib()
+        L.cms_kfstore_search_by_projection_sim3.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_void_p, C.c_void_p]
+        _chk(L.cms_kfstore_search_by_projection_sim3(self.h, src_ctx.h, len(sets), _p(soff), *[_p(v) for v in a], nj, arr, None if skip is None else _p(skip), _p(taken), float(th),
+                                                     _p(mk), _p(nm)), "cms_kfstore_search_by_projection_sim3")
+        return [(mk[eoff[k]:eoff[k + 1]].copy(), int(nm[k])) for k in range(nj)]
+
+    def fuse_search_sim3(self, src_ctx, sets, jobs, th=4.0, out=None):
+        """cms_kfstore_fuse_search_sim3: the search half of ORBMatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (LoopClosing::SearchAndFuse) for many
+        (resident key frame, Scw, set of map points) jobs in ONE call on src_ctx's stream.  sets / jobs: see _sim3_proj_args.  out: (best_idx, best_dist)
+        arrays to receive the results.  Returns per job (best_idx int32[points of its set] or -1, best_dist (256 where -1))."""
+        soff, a, arr, eoff, skip = self._sim3_proj_args(sets, jobs)
+        nj = len(jobs)
+        bi, bd = out if out is not None else (np.full(max(int(eoff[-1]), 1), -1, np.int32), np.full(max(int(eoff[-1]), 1), 256, np.int32))
+        L = lib()
+        L.cms_kfstore_fuse_search_sim3.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 2 + [C.c_float, C.c_void_p, C.c_void_p]
+        _chk(L.cms_kfstore_fuse_search_sim3(self.h, src_ctx.h, len(sets), _p(soff), *[_p(v) for v in a], nj, arr, None if skip is None else _p(skip), float(th), _p(bi), _p(bd)),
+             "cms_kfstore_fuse_search_sim3")
+        return [(bi[eoff[k]:eoff[k + 1]].copy(), bd[eoff[k]:eoff[k + 1]].copy()) for k in range(nj)]
 
     def compute_bow(self, vocab, slots, levelsup=4):
         """cms_kfstore_compute_bow: KeyFrame::ComputeBoW on the resident descriptors of `slots`; the FeatureVector goes into the slots' layout, the

@@ -529,6 +529,98 @@ int ORBMatcher::SearchBySim3(const KeyFrameView& pKF1, const KeyFrameView& pKF2,
   return nFound;
 }
 
+namespace {
+// what the two Scw matchers share: the view in slot 0 of the shared context's small store, the points as ONE set, one job
+struct Sim3ProjCall {
+  std::vector<float> pos, nrm, dmin, dmax;
+  std::vector<uint8_t> desc, skip;
+  cms_sim3_proj_job q;
+  int set_off[2];
+  KfPack pack;
+  cms_keyframe k;
+  Sim3ProjCall(const char* who, const KeyFrameView& kf, const cv::Mat& Scw, const std::vector<MapPointView>& pts) {
+    const int N = (int)kf.mvKeys.size(), M = (int)pts.size();
+    if (Scw.type() != cv::CV_32F || Scw.cols != 4 || (Scw.rows != 4 && Scw.rows != 3)) throw std::runtime_error(std::string(who) + ": Scw must be 4x4 (or 3x4) CV_32F");
+    pos.resize(3 * (size_t)M + 3); nrm.resize(3 * (size_t)M + 3); dmin.resize(M + 1); dmax.resize(M + 1); desc.resize(32 * (size_t)M + 32); skip.assign(M + 1, 0);
+    for (int i = 0; i < M; ++i) {
+      for (int c = 0; c < 3; ++c) { pos[3 * (size_t)i + c] = pts[i].mWorldPos.at<float>(c, 0); nrm[3 * (size_t)i + c] = pts[i].mNormalVector.at<float>(c, 0); }
+      dmin[i] = pts[i].mfMinDistance; dmax[i] = pts[i].mfMaxDistance;
+      std::memcpy(&desc[32 * (size_t)i], pts[i].mDescriptor.ptr<uint8_t>(0), 32);
+    }
+    KeyFrameView v;
+    v.mvKeys = kf.mvKeys; v.mDescriptors = kf.mDescriptors; v.mvpMapPoints = kf.mvpMapPoints;
+    v.mvKeyRays.assign(N, cv::Vec3f());
+    float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};      // (the search does not read the slot's pose)
+    v.Tcw = cv::Mat(4, 4, cv::CV_32F, eye, 16);
+    k = pack_keyframe(v, pack);
+    q.slot = 0; q.n = N; q.set = 0;
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) q.Scw[4 * r + c] = Scw.at<float>(r, c);
+    set_off[0] = 0; set_off[1] = M;
+  }
+};
+}  // namespace
+
+int ORBMatcher::SearchByProjection(const KeyFrameView& pKF, const cv::Mat& Scw, const std::vector<MapPointView>& vpPoints, std::vector<long>& vpMatched, int th) {
+  const int N = (int)pKF.mvKeys.size(), M = (int)vpPoints.size();
+  if ((int)vpMatched.size() != N) throw std::runtime_error("SearchByProjection: vpMatched must have one entry per key point of pKF");
+  Sim3ProjCall call("SearchByProjection", pKF, Scw, vpPoints);
+  if (N == 0 || M == 0) return 0;
+  cms_ctx* ctx = SharedContext(g_ctx_orb.nfeatures, g_ctx_orb.scale_factor, g_ctx_orb.nlevels, g_ctx_orb.ini_th_fast, g_ctx_orb.min_th_fast);
+  std::set<long> spAlreadyFound(vpMatched.begin(), vpMatched.end());      // :806-807
+  spAlreadyFound.erase(-1);
+  std::vector<uint8_t> taken(N + 1, 0);
+  for (int i = 0; i < N; ++i) taken[i] = vpMatched[i] >= 0;
+  for (int i = 0; i < M; ++i) call.skip[i] = vpPoints[i].mbBad || spAlreadyFound.count(vpPoints[i].mnId);      // :817
+  std::vector<int> match(M, -1);
+  int nmatches = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!g_bow_kf_store && cms_kfstore_create(&g_bow_kf_store, ctx, 2, 4096, 4096) != CMS_OK)
+      throw std::runtime_error(std::string("cms_kfstore_create: ") + cms_last_error());
+    int rc = cms_kfstore_put(g_bow_kf_store, 0, &call.k);
+    if (rc == CMS_OK) rc = cms_kfstore_search_by_projection_sim3(g_bow_kf_store, ctx, 1, call.set_off, call.pos.data(), call.nrm.data(), call.dmin.data(), call.dmax.data(),
+                                                                 call.desc.data(), 1, &call.q, call.skip.data(), taken.data(), (float)th, match.data(), &nmatches);
+    if (rc != CMS_OK) throw std::runtime_error(std::string("cms_kfstore_search_by_projection_sim3: ") + cms_last_error());
+  }
+  for (int i = 0; i < M; ++i) if (match[i] >= 0) vpMatched[match[i]] = vpPoints[i].mnId;      // :896
+  return nmatches;
+}
+
+int ORBMatcher::Fuse(KeyFrameView& pKF, const cv::Mat& Scw, const std::vector<MapPointView>& vpPoints, float th, std::vector<long>& vpReplacePoint) {
+  const int N = (int)pKF.mvKeys.size(), M = (int)vpPoints.size();
+  if ((int)vpReplacePoint.size() != M) throw std::runtime_error("Fuse: vpReplacePoint must have one entry per point");
+  Sim3ProjCall call("Fuse", pKF, Scw, vpPoints);
+  if (N == 0 || M == 0) return 0;
+  cms_ctx* ctx = SharedContext(g_ctx_orb.nfeatures, g_ctx_orb.scale_factor, g_ctx_orb.nlevels, g_ctx_orb.ini_th_fast, g_ctx_orb.min_th_fast);
+  auto bad_at = [&](int i) { return i < (int)pKF.mvbMapPointBad.size() && pKF.mvbMapPointBad[i]; };
+  std::set<long> spAlreadyFound;                                            // pKF->GetMapPoints(): the key frame's points that are not bad (:1256)
+  for (int i = 0; i < N; ++i) if (pKF.mvpMapPoints[i] >= 0 && !bad_at(i)) spAlreadyFound.insert(pKF.mvpMapPoints[i]);
+  for (int i = 0; i < M; ++i) call.skip[i] = vpPoints[i].mbBad || spAlreadyFound.count(vpPoints[i].mnId);      // :1268
+  std::vector<int> bi(M, -1), bd(M, 256);
+  {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!g_bow_kf_store && cms_kfstore_create(&g_bow_kf_store, ctx, 2, 4096, 4096) != CMS_OK)
+      throw std::runtime_error(std::string("cms_kfstore_create: ") + cms_last_error());
+    int rc = cms_kfstore_put(g_bow_kf_store, 0, &call.k);
+    if (rc == CMS_OK) rc = cms_kfstore_fuse_search_sim3(g_bow_kf_store, ctx, 1, call.set_off, call.pos.data(), call.nrm.data(), call.dmin.data(), call.dmax.data(),
+                                                        call.desc.data(), 1, &call.q, call.skip.data(), th, bi.data(), bd.data());
+    if (rc != CMS_OK) throw std::runtime_error(std::string("cms_kfstore_fuse_search_sim3: ") + cms_last_error());
+  }
+  int nFused = 0;
+  for (int i = 0; i < M; ++i) {                                             // :1345-1359 in list order
+    if (bi[i] < 0) continue;
+    const long pMPinKF = pKF.mvpMapPoints[bi[i]];
+    if (pMPinKF >= 0) {
+      if (!bad_at(bi[i])) vpReplacePoint[i] = pMPinKF;
+    } else {
+      pKF.mvpMapPoints[bi[i]] = vpPoints[i].mnId;                           // pMP->AddObservation(pKF,bestIdx); pKF->AddMapPoint(pMP,bestIdx);
+      if (bi[i] < (int)pKF.mvbMapPointBad.size()) pKF.mvbMapPointBad[bi[i]] = 0;
+    }
+    ++nFused;
+  }
+  return nFused;
+}
+
 int ORBMatcher::SearchByProjection(FrameView& CurrentFrame, const KeyFrameView& pKF, const std::set<long>& sAlreadyFound, float th, int ORBdist) {
   const int N = (int)CurrentFrame.mvKeys.size(), NK = (int)pKF.mvKeys.size();
   if (N == 0) return 0;

@@ -210,6 +210,18 @@ class ORBMatcher {
   // (cms_kfstore_search_by_sim3: both views go into the small store of the shared context first; the device path only)
   int SearchBySim3(const KeyFrameView& pKF1, const KeyFrameView& pKF2, std::vector<long>& vpMatches12, float s12, const cv::Mat& R12, const cv::Mat& t12, float th,
                    bool zAsWritten = true);
+  // ORBMatcher.cpp:796-903, LoopClosing.cpp:374: vpPoints that are not bad (MapPointView::mbBad) and not among vpMatched on entry (:806-807, :817) are
+  // projected through the decomposed Scw (4x4 or 3x4 CV_32F; pKF.Tcw is not read) and matched inside windows th * scale[predicted level] over octaves
+  // level - 1 and level; key points with vpMatched[idx] >= 0 -- on entry or through an earlier point of the call -- are passed over; best Hamming
+  // <= TH_LOW.  vpMatched (ids, -1 = NULL, one per key point of pKF) receives the matched points; returns nmatches.
+  // (cms_kfstore_search_by_projection_sim3: the view goes into the small store of the shared context first; the device path only)
+  int SearchByProjection(const KeyFrameView& pKF, const cv::Mat& Scw, const std::vector<MapPointView>& vpPoints, std::vector<long>& vpMatched, int th);
+  // ORBMatcher.cpp:1246-1363, LoopClosing.cpp:586-612: vpPoints that are not bad and not among pKF's map points that are not bad (GetMapPoints, :1256,
+  // :1268) are projected through the decomposed Scw and matched as above without the vpMatched test.  In list order (:1345-1359): where the key point
+  // holds a map point that is not bad, vpReplacePoint[iMP] receives its id; where it holds a bad one nothing; a free key point receives the point
+  // (AddObservation / AddMapPoint: pKF.mvpMapPoints[bestIdx] = the id, which is why pKF is not const here).  vpReplacePoint must have one entry per
+  // point; returns nFused.  (cms_kfstore_fuse_search_sim3)
+  int Fuse(KeyFrameView& pKF, const cv::Mat& Scw, const std::vector<MapPointView>& vpPoints, float th, std::vector<long>& vpReplacePoint);
   static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 12;
 
  protected:
@@ -222,6 +234,7 @@ class ORBMatcher {
 // mbTrackInView / mTrackProj* / mnTrackScaleLevel / mTrackViewCos fields Tracking uses afterwards.
 struct MapPointView {
   long mnId = -1;
+  bool mbBad = false;                   // isBad(), where a function reads it from the point (the Scw matchers of loop closing)
   cv::Mat mWorldPos, mNormalVector;     // 3x1 CV_32F
   float mfMinDistance = 0, mfMaxDistance = 0;
   cv::Mat mDescriptor;                  // 1x32 CV_8U

@@ -363,6 +363,58 @@ extern "C" int hm_search_by_sim3(int n1, const cms_keypoint* k1, const uint8_t* 
     for (int i = 0; i < n1; ++i) matches12[i] = m[i];
     return nm;)
 }
+// The two Scw matchers of loop closing through the mirror.  The key frame: n key points with descriptors, map-point ids kf_mp (-1 = none; Fuse: in / out)
+// and their bad flags or NULL; Scw 12 floats (rows 0..2 of [sR | t]); M points (position, normal, distance members, descriptor, id, bad flag or NULL).
+// hm_search_by_projection_sim3: matched[n] = vpMatched as ids, in / out.  hm_fuse_sim3: replace[M] = vpReplacePoint as ids, in / out.
+namespace {
+void sim3p_views(KeyFrameView& kf, std::vector<MapPointView>& pts, int n, const cms_keypoint* k, const uint8_t* desc, const long* kf_mp, const uint8_t* kf_bad, int M,
+                 const float* pos, const float* normal, const float* mn, const float* mx, const uint8_t* mpd, const long* mp_id, const uint8_t* mp_bad) {
+  kf.mvKeys.resize(n);
+  kf.mDescriptors.create(n > 0 ? n : 1, 32, cv::CV_8U);
+  kf.mvpMapPoints.assign(kf_mp, kf_mp + n);
+  if (kf_bad) kf.mvbMapPointBad.assign(kf_bad, kf_bad + n);
+  for (int i = 0; i < n; ++i) {
+    kf.mvKeys[i].pt = cv::Point2f(k[i].x, k[i].y); kf.mvKeys[i].angle = k[i].angle; kf.mvKeys[i].octave = k[i].octave; kf.mvKeys[i].size = k[i].size;
+    kf.mvKeys[i].response = k[i].response;
+    std::memcpy(kf.mDescriptors.ptr<uint8_t>(i), desc + (size_t)i * 32, 32);
+  }
+  pts.resize(M);
+  for (int i = 0; i < M; ++i) {
+    MapPointView& v = pts[i];
+    v.mnId = mp_id[i]; v.mbBad = mp_bad && mp_bad[i]; v.mfMinDistance = mn[i]; v.mfMaxDistance = mx[i];
+    v.mWorldPos.create(3, 1, cv::CV_32F); v.mNormalVector.create(3, 1, cv::CV_32F);
+    for (int c = 0; c < 3; ++c) { v.mWorldPos.at<float>(c, 0) = pos[3 * (size_t)i + c]; v.mNormalVector.at<float>(c, 0) = normal[3 * (size_t)i + c]; }
+    v.mDescriptor.create(1, 32, cv::CV_8U);
+    std::memcpy(v.mDescriptor.ptr<uint8_t>(0), mpd + 32 * (size_t)i, 32);
+  }
+}
+}  // namespace
+extern "C" int hm_search_by_projection_sim3(int n, const cms_keypoint* k, const uint8_t* desc, float* Scw, int M, const float* pos, const float* normal, const float* mn,
+                                            const float* mx, const uint8_t* mpd, const long* mp_id, const uint8_t* mp_bad, int th, long* matched) {
+  HM_TRY(
+    KeyFrameView kf;
+    std::vector<MapPointView> pts;
+    std::vector<long> none(n > 0 ? n : 1, -1);
+    sim3p_views(kf, pts, n, k, desc, none.data(), nullptr, M, pos, normal, mn, mx, mpd, mp_id, mp_bad);
+    std::vector<long> m(matched, matched + n);
+    ORBMatcher matcher(0.75f, true);
+    const int nm = matcher.SearchByProjection(kf, cv::Mat(3, 4, cv::CV_32F, Scw, 16), pts, m, th);
+    for (int i = 0; i < n; ++i) matched[i] = m[i];
+    return nm;)
+}
+extern "C" int hm_fuse_sim3(int n, const cms_keypoint* k, const uint8_t* desc, long* kf_mp, const uint8_t* kf_bad, float* Scw, int M, const float* pos, const float* normal,
+                            const float* mn, const float* mx, const uint8_t* mpd, const long* mp_id, const uint8_t* mp_bad, float th, long* replace) {
+  HM_TRY(
+    KeyFrameView kf;
+    std::vector<MapPointView> pts;
+    sim3p_views(kf, pts, n, k, desc, kf_mp, kf_bad, M, pos, normal, mn, mx, mpd, mp_id, mp_bad);
+    std::vector<long> r(replace, replace + M);
+    ORBMatcher matcher(0.8f);
+    const int nf = matcher.Fuse(kf, cv::Mat(3, 4, cv::CV_32F, Scw, 16), pts, th, r);
+    for (int i = 0; i < M; ++i) replace[i] = r[i];
+    for (int i = 0; i < n; ++i) kf_mp[i] = kf.mvpMapPoints[i];
+    return nf;)
+}
 // LocalMapping::CreateNewMapPoints through the mirror: key frame 0 is the current one, 1..nkf-1 its neighbours.  Flat inputs:
 // feat_off[nkf+1]; per feature kps/desc/rays/mp; Tcw nkf x 16; FeatureVector per key frame as node_off2[nkf+1] into (node_id, node_cnt)
 // and the features of the nodes concatenated in node_feat; median_depth[nkf].  Outputs up to cap records.

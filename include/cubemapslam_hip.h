@@ -826,6 +826,46 @@ int cms_kfstore_search_by_sim3(cms_kfstore* st, cms_ctx* src, int njobs, const c
                                const uint8_t* skip, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* mp_desc,
                                float th, int z_as_written, int* idx2, int* n_found);
 
+/* ---- The two projection matchers of a loop closure that see a key frame through a similarity Scw instead of its stored pose, on resident key frames:
+ *   ORBMatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, vpPoints, vpMatched, th) (src/ORBMatcher.cpp:796-903), the last step of
+ *     LoopClosing::ComputeSim3 (src/LoopClosing.cpp:374, th = 10), whose count decides "loop accepted";
+ *   the search half of ORBMatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, vpPoints, th, vpReplacePoint) (:1246-1363), which LoopClosing::SearchAndFuse
+ *     (src/LoopClosing.cpp:586-612, th = 4) runs once per key frame of CorrectedPosesMap over the same loop map points.
+ * Sets of map points are shared between jobs as in cms_kfstore_fuse_search_sets: set s holds records [set_off[s], set_off[s + 1]) of pos (3 floats),
+ * normal (3), min_dist, max_dist (as src's cms_set_distance_bounds_mode says) and mp_desc (32 bytes).  A job searches its set in its slot's key frame
+ * under its own Scw; its ENTRIES are the set's points in order, job after job.  skip (per entry, may be NULL) != 0 <=> pMP->isBad() ||
+ * spAlreadyFound.count(pMP) (:817, :1268; the pointer work of :806-807 / :1256 is the caller's).
+ * Per job Scw is decomposed (:799-803; csrc/cms_sim3_proj_core.h states the arithmetic): scw = sqrt(row0 . row0), Rcw = sRcw / scw, tcw = t / scw,
+ * Ow = -Rcw.t() * tcw.  Per entry (:817-860 / :1268-1312): p3Dc = Rcw*p3Dw + tcw, dropped on z < 0, projected (TransformRaysToCubemap), dropped outside
+ * [0, 3F)^2, dist = norm(p3Dw - Ow) against the point's scale-invariance distances, PO.dot(Pn) < 0.5*dist dropped, PredictScale, window
+ * th * mvScaleFactors[level] (GetFeaturesInArea without level arguments, its order), candidates of octave level - 1 or level.  The slot's stored pose
+ * is not read.  One stated difference: a ray no face takes (UNKNOWN_FACE) makes the reference's assert abort; here u = v = -1 and the point is dropped.
+ *   SearchByProjection (:870-898): candidates with vpMatched[idx] != NULL are passed over -- those of `taken` (per job n bytes, job after job; read,
+ *     never written) and those an earlier entry of the same job took; first strict Hamming minimum from 256, accepted when <= TH_LOW (50).
+ *     match_kp[entry] = the key point taken or -1, n_matches[job] = nmatches.  The store's max_features must not exceed 4096 (CMS_ERR_ARG).
+ *   Fuse (:1323-1345): no taken test and, unlike cms_kfstore_fuse_search, no reprojection gate; first strict minimum, accepted when <= TH_LOW.
+ *     best_idx[entry] = bestIdx or -1, best_dist[entry] = bestDist or 256.  What is done with bestIdx (:1347-1358) is the caller's.
+ * Both run on src's stream with src's staging block -- the loop-closing thread's -- and enqueue nothing on the store's: src's stream waits on the
+ * device for the copies of cms_kfstore_put_from_frame(s) that filled the named slots.  One synchronisation; a call whose candidate lists did not fit
+ * is repeated once with room for them.  Synchronous; results may be pageable or pinned host memory; a repeated call gives identical bytes.  Checked
+ * before anything is enqueued or written, CMS_ERR_ARG with the reason in cms_last_error: a slot out of range or not filled, n that is not the slot's
+ * stored key-point count, a set out of range, set offsets that do not ascend, scw zero or not finite or a non-finite Scw entry, th negative or not
+ * finite, more than 16 levels, a context on another device than the store's, a null array where entries exist.  njobs == 0 is CMS_OK with no
+ * launch; an empty set or n == 0 gives no match.  Threading as cms_kfstore_search_by_sim3.
+ * cms_sim3_proj_last_rounds: the most rounds a job of the calling thread's last cms_kfstore_search_by_projection_sim3 needed (for profiles). */
+typedef struct {
+  int slot, n;        /* resident key frame and its stored key-point count */
+  float Scw[12];      /* rows 0..2 of the 4 x 4 [sR | t], row major, float (mScw / Converter::toCvMat(g2oScw)) */
+  int set;            /* which map-point set the job searches */
+} cms_sim3_proj_job;
+int cms_kfstore_search_by_projection_sim3(cms_kfstore* st, cms_ctx* src, int nsets, const int* set_off, const float* pos, const float* normal,
+                                          const float* min_dist, const float* max_dist, const uint8_t* mp_desc, int njobs, const cms_sim3_proj_job* jobs,
+                                          const uint8_t* skip, const uint8_t* taken, float th, int* match_kp, int* n_matches);
+int cms_kfstore_fuse_search_sim3(cms_kfstore* st, cms_ctx* src, int nsets, const int* set_off, const float* pos, const float* normal,
+                                 const float* min_dist, const float* max_dist, const uint8_t* mp_desc, int njobs, const cms_sim3_proj_job* jobs,
+                                 const uint8_t* skip, float th, int* best_idx, int* best_dist);
+int cms_sim3_proj_last_rounds(void);
+
 /* ---- Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cpp:888-1091), which LoopClosing::ComputeSim3 runs on
  * every hypothesis behind cms_kfstore_search_by_sim3 (src/LoopClosing.cpp:324-326; the candidate is kept on >= 20 inliers): every accepted hypothesis
  * of a pass as ONE launch, one workgroup per job with both optimize() rounds, the Levenberg accept / reject loop and the two classifications inside

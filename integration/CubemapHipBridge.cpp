@@ -695,6 +695,123 @@ void SearchBySim3(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pCurrentKF, const 
   }
 }
 
+// ------------------------------------------------------------------------------------------------ LoopClosing: the two projection matchers under a Sim3
+namespace {
+// a map point as the Scw matchers read it, or an empty record for a skipped one (never read by the device)
+void push_point_or_blank(MapPoint* p, bool skipped, std::vector<float>& pos, std::vector<float>& nrm, std::vector<float>& dmin, std::vector<float>& dmax,
+                         std::vector<uint8_t>& desc) {
+  if (!skipped) { push_point(p, pos, nrm, dmin, dmax, desc); return; }
+  pos.insert(pos.end(), 3, 0.0f); nrm.insert(nrm.end(), 3, 0.0f); dmin.push_back(0.0f); dmax.push_back(0.0f); desc.insert(desc.end(), 32, 0);
+}
+void scw_floats(const cv::Mat& Scw, float* out12) {
+  for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) out12[4 * r + c] = Scw.at<float>(r, c);
+}
+}  // namespace
+
+int SearchByProjection(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pKF, const cv::Mat& Scw, const std::vector<MapPoint*>& vpPoints, std::vector<MapPoint*>& vpMatched, int th) {
+  StoreBook& b = book(store);
+  std::set<MapPoint*> spAlreadyFound(vpMatched.begin(), vpMatched.end());      // ORBMatcher.cpp:806-807
+  spAlreadyFound.erase(static_cast<MapPoint*>(NULL));
+  const int M = (int)vpPoints.size(), N = (int)vpMatched.size();
+  std::vector<float> pos, nrm, dmin, dmax;
+  std::vector<uint8_t> desc, skip, taken;
+  for (MapPoint* p : vpPoints) {
+    const bool out = p->isBad() || spAlreadyFound.count(p);                     // :817
+    skip.push_back(out ? 1 : 0);
+    push_point_or_blank(p, out, pos, nrm, dmin, dmax, desc);
+  }
+  for (MapPoint* p : vpMatched) taken.push_back(p ? 1 : 0);                     // :875 on entry
+  skip.push_back(0); taken.push_back(0); pos.push_back(0.0f); nrm.push_back(0.0f); dmin.push_back(0.0f); dmax.push_back(0.0f); desc.push_back(0);      // (never empty)
+  std::vector<int> match((size_t)M + 1, -1);
+  int nmatches = 0;
+  {
+    std::lock_guard<std::mutex> lk(b.mu);                                       // from the look-up to the end of the device call, like SearchBySim3
+    const int slot = slot_locked(b, pKF);
+    if (slot < 0) {                                                             // not resident: the reference's own matcher
+      ORBMatcher matcher(0.75, true);
+      return matcher.SearchByProjection(pKF, Scw, vpPoints, vpMatched, th);
+    }
+    cms_sim3_proj_job q;
+    q.slot = slot; q.n = N; q.set = 0;
+    scw_floats(Scw, q.Scw);
+    const int set_off[2] = {0, M};
+    check(cms_kfstore_search_by_projection_sim3(store, ctx, 1, set_off, pos.data(), nrm.data(), dmin.data(), dmax.data(), desc.data(), 1, &q, skip.data(), taken.data(),
+                                                (float)th, match.data(), &nmatches),
+          "cms_kfstore_search_by_projection_sim3");
+  }
+  for (int i = 0; i < M; ++i) if (match[i] >= 0) vpMatched[match[i]] = vpPoints[i];      // :896
+  return nmatches;
+}
+
+void SearchAndFuse(cms_kfstore* store, cms_ctx* ctx, const std::vector<std::pair<KeyFrame*, cv::Mat> >& vCorrectedPoses, const std::vector<MapPoint*>& vpLoopMapPoints,
+                   Map* pMap) {
+  StoreBook& b = book(store);
+  const int nLP = (int)vpLoopMapPoints.size();
+  // ---- one search over every resident key frame of the map, one set.  Why this equals the reference's sequential loop (LoopClosing.cpp:590-611):
+  // the search result of an entry -- bestIdx -- depends only on the point's position, normal, distances and descriptor, on the key frame's key points
+  // and descriptors and on Scw; none of them is changed by SearchAndFuse.  Only the skip test (:1268) and what is done with bestIdx (:1347-1358) read
+  // pointer state, and both are evaluated below, live, at the key frame's turn.  A point skipped NOW is skipped then as well: isBad() never turns
+  // false again, and membership of a loop point in a key frame only grows during SearchAndFuse (AddMapPoint, Replace) -- so the flags sent along
+  // only spare work.
+  std::vector<float> pos, nrm, dmin, dmax;
+  std::vector<uint8_t> desc, skip;
+  for (MapPoint* p : vpLoopMapPoints) push_point_or_blank(p, p->isBad(), pos, nrm, dmin, dmax, desc);
+  pos.push_back(0.0f); nrm.push_back(0.0f); dmin.push_back(0.0f); dmax.push_back(0.0f); desc.push_back(0);      // (never empty)
+  std::vector<cms_sim3_proj_job> jobs;
+  std::vector<int> job_of(vCorrectedPoses.size(), -1);
+  std::vector<int> best_idx, best_dist;
+  {
+    std::lock_guard<std::mutex> lk(b.mu);
+    for (size_t k = 0; k < vCorrectedPoses.size(); ++k) {
+      KeyFrame* pKF = vCorrectedPoses[k].first;
+      const int slot = slot_locked(b, pKF);
+      if (slot < 0) continue;
+      const std::set<MapPoint*> in_kf = pKF->GetMapPoints();
+      for (MapPoint* p : vpLoopMapPoints) skip.push_back((p->isBad() || in_kf.count(p)) ? 1 : 0);
+      cms_sim3_proj_job q;
+      q.slot = slot; q.n = (int)pKF->GetMapPointMatches().size(); q.set = 0;
+      scw_floats(vCorrectedPoses[k].second, q.Scw);
+      job_of[k] = (int)jobs.size();
+      jobs.push_back(q);
+    }
+    skip.push_back(0);
+    best_idx.assign(jobs.size() * (size_t)nLP + 1, -1); best_dist.assign(jobs.size() * (size_t)nLP + 1, 256);
+    const int set_off[2] = {0, nLP};
+    if (!jobs.empty())
+      check(cms_kfstore_fuse_search_sim3(store, ctx, 1, set_off, pos.data(), nrm.data(), dmin.data(), dmax.data(), desc.data(), (int)jobs.size(), jobs.data(), skip.data(), 4.0f,
+                                         best_idx.data(), best_dist.data()),
+            "cms_kfstore_fuse_search_sim3");
+  }
+  // ---- the decisions, in the map's order and per key frame in list order, with the reference's own statements
+  ORBMatcher matcher(0.8);
+  for (size_t k = 0; k < vCorrectedPoses.size(); ++k) {
+    KeyFrame* pKF = vCorrectedPoses[k].first;
+    std::vector<MapPoint*> vpReplacePoints(vpLoopMapPoints.size(), static_cast<MapPoint*>(NULL));
+    if (job_of[k] < 0) {
+      matcher.Fuse(pKF, vCorrectedPoses[k].second, vpLoopMapPoints, 4, vpReplacePoints);      // not resident: the reference's own search
+    } else {
+      const std::set<MapPoint*> spAlreadyFound = pKF->GetMapPoints();           // ORBMatcher.cpp:1256, at this key frame's turn
+      const int* bi = best_idx.data() + (size_t)job_of[k] * nLP;
+      for (int i = 0; i < nLP; ++i) {
+        MapPoint* pMP = vpLoopMapPoints[i];
+        if (bi[i] < 0 || pMP->isBad() || spAlreadyFound.count(pMP)) continue;   // :1268
+        MapPoint* pMPinKF = pKF->GetMapPoint(bi[i]);                            // :1347-1358
+        if (pMPinKF) {
+          if (!pMPinKF->isBad()) vpReplacePoints[i] = pMPinKF;
+        } else {
+          pMP->AddObservation(pKF, bi[i]);
+          pKF->AddMapPoint(pMP, bi[i]);
+        }
+      }
+    }
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                  // LoopClosing.cpp:601-610
+    for (int i = 0; i < nLP; ++i) {
+      MapPoint* pRep = vpReplacePoints[i];
+      if (pRep) pRep->Replace(vpLoopMapPoints[i]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ Tracking::Relocalization: the guided search
 int SearchByProjection(cms_kfstore* store, cms_ctx* frameCtx, Frame& CurrentFrame, KeyFrame* pKF, const std::set<MapPoint*>& sAlreadyFound, float th, int ORBdist,
                        bool checkOri) {

@@ -134,6 +134,22 @@ void SearchByBoWLoopCandidates(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pCurr
 void SearchBySim3(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pCurrentKF, const std::vector<KeyFrame*>& vpKFs, std::vector<std::vector<MapPoint*> >& vvpMatches12,
                   const std::vector<float>& vs12, const std::vector<cv::Mat>& vR12, const std::vector<cv::Mat>& vt12, float th, std::vector<int>& vnFound,
                   bool zAsWritten = true);
+// ---- The last step of LoopClosing::ComputeSim3, matcher.SearchByProjection(mpCurrentKF, mScw, mvpLoopMapPoints, mvpCurrentMatchedPoints, 10)
+// (LoopClosing.cpp:374, ORBMatcher.cpp:796-903), on the LOOP-CLOSING thread's context: the body of that statement.  spAlreadyFound, the skip flags
+// (:806-807, :817) and the taken flags (vpMatched[idx] != NULL) are built here; vpMatched receives the matches as the reference's vector does; returns
+// nmatches.  A key frame that is not resident goes through the reference's own matcher.  Nothing runs on the store's stream.
+int SearchByProjection(cms_kfstore* store, cms_ctx* ctx, KeyFrame* pKF, const cv::Mat& Scw, const std::vector<MapPoint*>& vpPoints, std::vector<MapPoint*>& vpMatched, int th);
+// ---- LoopClosing::SearchAndFuse (LoopClosing.cpp:586-612): matcher.Fuse(pKF, cvScw, mvpLoopMapPoints, 4, vpReplacePoints) (ORBMatcher.cpp:1246-1363) for
+// every key frame of CorrectedPosesMap, as ONE cms_kfstore_fuse_search_sim3 call over the resident ones with the loop map points as one shared set,
+// then the reference's own statements in the map's order and per key frame in list order: the skip test re-evaluated live at the key frame's turn
+// (isBad(), GetMapPoints()), GetMapPoint(bestIdx), vpReplacePoints, AddObservation / AddMapPoint, and Replace under mMutexMapUpdate.  The search
+// result of an entry depends only on geometry and descriptors, which SearchAndFuse does not change; only the skip test and what is done with bestIdx
+// read pointer state, and membership of loop points in a key frame only grows meanwhile -- hence one search equals the sequential loop
+// (INTEGRATION.md item 24).  A key frame that is not resident goes through the reference's own matcher.Fuse at its turn.
+// vCorrectedPoses: CorrectedPosesMap in ITS order as (key frame, Converter::toCvMat(g2oScw)) -- the call site's two lines; LoopClosing.h itself is
+// not pulled into this header.
+void SearchAndFuse(cms_kfstore* store, cms_ctx* ctx, const std::vector<std::pair<KeyFrame*, cv::Mat> >& vCorrectedPoses, const std::vector<MapPoint*>& vpLoopMapPoints,
+                   Map* pMap);
 // ---- Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cpp:888-1091) behind SearchBySim3 (LoopClosing.cpp:324-326), for
 // one hypothesis or for every accepted hypothesis of a pass as ONE cms_sim3_optimize call.  The start is what :324 hands g2o::Sim3: the solver's R
 // (3 x 3 CV_32F), t (3 x 1 CV_32F) and s, widened as Converter::toMatrix3d / toVector3d do.  The pointer work of :941-978 is done here

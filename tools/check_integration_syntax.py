@@ -44,7 +44,8 @@ def main(ref_inc):
                                                ("CubemapHipBridge.cpp", "cms_kfdb_detect(store, frameCtx, 1, &job,", "cms_kfdb_detect(store, 1, &job,"),
                                                ("CubemapHipBridge.cpp", "cms_kfstore_search_by_bow_keyframes(store, ctx, (int)jobs.size(),",
                                                 "cms_kfstore_search_by_bow_keyframes(store, (int)jobs.size(),"),
-                                               ("CubemapHipBridge.cpp", "cms_kfstore_search_by_sim3(store, ctx, (int)jobs.size(),", "cms_kfstore_search_by_sim3(store, (int)jobs.size(),"))):
+                                               ("CubemapHipBridge.cpp", "cms_kfstore_search_by_sim3(store, ctx, (int)jobs.size(),", "cms_kfstore_search_by_sim3(store, (int)jobs.size(),"),
+                                               ("CubemapHipBridge.cpp", "cms_kfstore_fuse_search_sim3(store, ctx, 1, set_off,", "cms_kfstore_fuse_search_sim3(store, 1, set_off,"))):
             d = os.path.join(td, "broken_%d" % i)
             shutil.copytree(os.path.join(ROOT, "integration"), d)
             src = open(os.path.join(d, fname)).read()
