@@ -61,6 +61,28 @@ static void cms_area_queries(CmsAreaArgs& a, int nq, const void* q_frame, const 
   a.qx = (const float*)qx; a.qy = (const float*)qy; a.qr = (const float*)qr; a.qmin = (const int*)qmin; a.qmax = (const int*)qmax;
   a.cnt = (int*)cnt; a.off = (int*)off; a.idx = (int*)idx; a.cap = cap; a.idx_base = idx_base;
 }
+// The per-entry staging columns of the Fuse-shaped entries (cms_fuse_search, kfstore_fuse_core, cms_kfstore_search_by_sim3, sim3p_core): what the
+// projection kernel writes (window, predicted level, the slot or frame whose grid is searched, the map-point record) and the window query's
+// counts and offsets (one entry more).  take() lays them out in the entry's block, at() gives the pointers once the block's address is known;
+// the candidate lists start at `o_idx`, behind everything else the entry staged.
+struct CmsWindowCols {
+  size_t o0 = 0, stride = 0;
+  float *qx, *qy, *qr; int *qmin, *qmax, *level, *slot, *rec, *cnt, *off, *idx;
+  void take(CmsBlock& b, size_t E) {
+    o0 = b.size; stride = cms_align(E * 4);
+    for (int k = 0; k < 9; ++k) b.take(E * 4);
+    b.take(E * 4, 4);
+  }
+  void at(uint8_t* p, size_t o_idx) {
+    float* f = (float*)(p + o0); int* i = (int*)(p + o0);
+    const size_t n = stride / 4;
+    qx = f; qy = f + n; qr = f + 2 * n; qmin = i + 3 * n; qmax = i + 4 * n; level = i + 5 * n; slot = i + 6 * n; rec = i + 7 * n; cnt = i + 8 * n; off = i + 9 * n;
+    idx = (int*)(p + o_idx);
+  }
+};
+static void cms_area_queries(CmsAreaArgs& a, int nq, const CmsWindowCols& w, int cap) {
+  cms_area_queries(a, nq, w.slot, w.qx, w.qy, w.qr, w.qmin, w.qmax, w.cnt, w.off, w.idx, cap, 0);
+}
 // Two launches, ordered by the stream: the search (counts, first CMS_AREA_TMP hits of every query, one sum of counts per workgroup), then
 // offsets + *d_total + lists per tile of queries (copied first hits; only a query with more candidates than that is searched again).
 static int cms_area_launch(cms_ctx* c, hipStream_t s, CmsAreaArgs a, void* d_total) {

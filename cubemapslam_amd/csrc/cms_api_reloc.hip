@@ -62,7 +62,7 @@ int reloc_run(cms_ctx* c, cms_kfstore* st, int njobs, const cms_kfproj_job* jobs
     a.n = n; a.pt_job = (const int*)(p + o_ptjob); a.pose12 = (const float*)(p + o_pose); a.job_frame = (const int*)(p + o_jframe); a.job_kp0 = (const int*)(p + o_jkp0);
     a.kf_kp = st ? st->d_kp : nullptr; a.kf_feat = (const int*)(p + o_feat); a.kf_angle = (const float*)(p + o_feat);
     a.pos = (const float*)(p + o_pos); a.min_dist = (const float*)(p + o_min); a.max_dist = (const float*)(p + o_max);
-    a.th = th; a.cos_fov = cms_cos_fov(c); a.log_scale = std::log(c->g.nlevels > 1 ? c->scale[1] : 1.2f); a.nlevels = c->g.nlevels; a.F = c->g.F;
+    a.th = th; a.cos_fov = cms_cos_fov(c); a.log_scale = cms_log_scale(c); a.nlevels = c->g.nlevels; a.F = c->g.F;
     a.bounds_scaled = c->dist_bounds_scaled;
     cms_level_table(a.sf, c, c->scale, 0.0f);
     a.q_frame = (int*)(p + o_qf); a.qx = (float*)(p + o_qx); a.qy = (float*)(p + o_qy); a.qr = (float*)(p + o_qr); a.qmin = (int*)(p + o_qmin); a.qmax = (int*)(p + o_qmax);

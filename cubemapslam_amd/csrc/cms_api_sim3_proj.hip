@@ -1,7 +1,6 @@
 // cms_api_sim3_proj.hip -- host side of ORBMatcher::SearchByProjection(KeyFrame*, Scw, ...) and of the search half of ORBMatcher::Fuse(KeyFrame*, Scw, ...)
 // on resident key frames (cms_kfstore_search_by_projection_sim3, cms_kfstore_fuse_search_sim3); included by cms_lib.hip behind cms_api_tri.hip
-// (cms_kfstore, kfstore_wait_puts), cms_api_area.hip (the window query's launcher), cms_sim3_search_kernels.hip (sim3s_job_of) and
-// cms_sim3_proj_kernels.hip.  Both entries are one body, sim3p_core: all jobs of a call are ONE launch sequence on src's stream with src's staging
+// (cms_kfstore, kfstore_wait_puts, kfstore_window_query, cms_window_scan_args), cms_api_area.hip (CmsWindowCols) and cms_sim3_proj_kernels.hip.  Both entries are one body, sim3p_core: all jobs of a call are ONE launch sequence on src's stream with src's staging
 // block, as cms_kfstore_search_by_sim3 runs -- k_sim3p_project, the window query against the store's grids, then k_sim3p_greedy or k_sim3p_scan; the
 // candidate total is read together with the results (one synchronisation) and a call whose lists did not fit is repeated by cms_retry_capacity.
 // Everything that becomes a device index is checked before anything is enqueued or written (cms_sim3_proj_job_check.h).
@@ -11,13 +10,6 @@
 #include "cms_sim3_proj_job_check.h"
 
 static thread_local int g_sim3p_last_rounds = 0;      // most rounds a job of this thread's last SearchByProjection call needed
-
-static bool sim3p_is_pinned(const void* ptr) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, ptr) == hipSuccess) return at.type == hipMemoryTypeHost;
-  (void)hipGetLastError();                                         // (a pageable pointer: not an error, just the copy)
-  return false;
-}
 
 // greedy: SearchByProjection (out_a = match_kp, out_b = NULL, n_matches); else Fuse (out_a = best_idx, out_b = best_dist)
 static int sim3p_core(const char* who, bool greedy, cms_kfstore* st, cms_ctx* src, int nsets, const int* set_off, const float* pos, const float* normal, const float* min_dist,
@@ -56,19 +48,21 @@ static int sim3p_core(const char* who, bool greedy, cms_kfstore* st, cms_ctx* sr
   if (rc) return rc;
   const size_t e4 = (size_t)E * 4, j4 = (size_t)njobs * 4, m4 = (size_t)M * 4;
   CmsBlock blk;
+  CmsWindowCols w;      // (slot: the job's; rec: the set's record an entry stands for)
   const size_t o_job = blk.take(jd.size() * sizeof(CmsSim3pJobDev)), o_eoff = blk.take(j4, 4), o_skip = blk.take((size_t)E), o_pos = blk.take(3 * m4), o_nrm = blk.take(3 * m4),
-               o_min = blk.take(m4), o_max = blk.take(m4), o_desc = blk.take((size_t)M * 32), o_taken = blk.take((size_t)T), o_qx = blk.take(e4), o_qy = blk.take(e4),
-               o_qr = blk.take(e4), o_qmin = blk.take(e4), o_qmax = blk.take(e4), o_lvl = blk.take(e4), o_qslot = blk.take(e4), o_rec = blk.take(e4), o_why = blk.take(e4),
-               o_cnt = blk.take(e4), o_off = blk.take(e4, 4), o_a = blk.take(e4), o_b = blk.take(e4), o_tot = blk.take(4 + 2 * j4);      // the total, n_matches, rounds
+               o_min = blk.take(m4), o_max = blk.take(m4), o_desc = blk.take((size_t)M * 32), o_taken = blk.take((size_t)T), o_why = blk.take(e4), o_a = blk.take(e4),
+               o_b = blk.take(e4), o_tot = blk.take(4 + 2 * j4);      // the total, n_matches, rounds
+  w.take(blk, (size_t)E);
   const size_t o_idx = blk.size;
   // results in pinned (device-visible) host memory: the last kernel stores there itself
-  const bool direct = sim3p_is_pinned(out_a) && (greedy || sim3p_is_pinned(out_b));
+  const bool direct = cms_is_pinned(out_a) && (greedy || cms_is_pinned(out_b));
   std::vector<int> back(1 + 2 * (size_t)njobs);
   rc = cms_retry_capacity(64 * E + 1024, who, [&](int cap, int& tot) -> int {
     const size_t o_pd = o_idx + cms_align((size_t)cap * 4);
     int rr = src->stage.reserve(s, o_pd + cms_align((size_t)cap * 2), 0);
     if (rr) return rr;
     uint8_t* p = src->stage.d;
+    w.at(p, o_idx);
     HIPCHK(hipMemcpyAsync(p + o_job, jd.data(), jd.size() * sizeof(CmsSim3pJobDev), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_eoff, ent_off.data(), j4 + 4, hipMemcpyHostToDevice, s));
     if (skip) HIPCHK(hipMemcpyAsync(p + o_skip, skip, (size_t)E, hipMemcpyHostToDevice, s));
@@ -83,31 +77,25 @@ static int sim3p_core(const char* who, bool greedy, cms_kfstore* st, cms_ctx* sr
     CmsSim3pArgs a = {};
     a.n_ent = E; a.njobs = njobs; a.job = (const CmsSim3pJobDev*)(p + o_job); a.ent_off = (const int*)(p + o_eoff); a.skip = p + o_skip;
     a.pos = (const float*)(p + o_pos); a.normal = (const float*)(p + o_nrm); a.min_dist = (const float*)(p + o_min); a.max_dist = (const float*)(p + o_max);
-    a.th = th; a.log_scale = std::log(g->g.nlevels > 1 ? g->scale[1] : 1.2f); a.nlevels = g->g.nlevels; a.F = g->g.F; a.bounds_scaled = src->dist_bounds_scaled;
+    a.th = th; a.log_scale = cms_log_scale(g); a.nlevels = g->g.nlevels; a.F = g->g.F; a.bounds_scaled = src->dist_bounds_scaled;
     cms_level_table(a.sf, g, g->scale, 0.0f);
-    a.qx = (float*)(p + o_qx); a.qy = (float*)(p + o_qy); a.qr = (float*)(p + o_qr); a.qmin = (int*)(p + o_qmin); a.qmax = (int*)(p + o_qmax);
-    a.level = (int*)(p + o_lvl); a.qslot = (int*)(p + o_qslot); a.rec = (int*)(p + o_rec); a.why = (int*)(p + o_why);
+    a.qx = w.qx; a.qy = w.qy; a.qr = w.qr; a.qmin = w.qmin; a.qmax = w.qmax; a.level = w.level; a.qslot = w.slot; a.rec = w.rec; a.why = (int*)(p + o_why);
     hipLaunchKernelGGL(k_sim3p_project, dim3((E + 255) / 256), dim3(256), 0, s, a);
-    // window query against the grids of the store's slots, with the CALLING context's first-hits and partial-sum buffers
-    CmsAreaArgs w = cms_area_args(st->d_kp, st->d_sorted, st->d_cell_start, st->maxf, g->g.F, cms_grid_inv(g));
-    cms_area_queries(w, E, p + o_qslot, a.qx, a.qy, a.qr, a.qmin, a.qmax, p + o_cnt, p + o_off, p + o_idx, cap, 0);
-    rr = cms_area_launch(src, s, w, p + o_tot);
+    rr = kfstore_window_query(st, src, s, w, E, cap, p + o_tot);
     if (rr) return rr;
     // the scan is enqueued right behind the windows: the total is looked at together with the results (the list kernel never writes beyond `cap`,
     // the scans never read beyond it, and a call whose lists did not fit is simply repeated with room for them)
     if (greedy) {
       CmsSim3pGreedyArgs ga = {};
-      ga.job = a.job; ga.ent_off = a.ent_off; ga.level = a.level; ga.rec = a.rec; ga.mp_desc = (const uint4*)(p + o_desc); ga.cand_off = (const int*)(p + o_off);
-      ga.cand_idx = (const int*)(p + o_idx); ga.cap = cap; ga.total = (const int*)(p + o_tot); ga.kp = st->d_kp; ga.t_desc = (const uint4*)st->d_desc; ga.maxf = st->maxf;
+      ga.job = a.job; ga.ent_off = a.ent_off; ga.level = a.level; ga.rec = a.rec; ga.mp_desc = (const uint4*)(p + o_desc); ga.cand_off = w.off;
+      ga.cand_idx = w.idx; ga.cap = cap; ga.total = (const int*)(p + o_tot); ga.kp = st->d_kp; ga.t_desc = (const uint4*)st->d_desc; ga.maxf = st->maxf;
       ga.taken = p + o_taken; ga.pair_dist = (uint16_t*)(p + o_pd); ga.match = (int*)(p + o_a); ga.out = direct ? out_a : (int*)(p + o_a);
       ga.n_matches = (int*)(p + o_tot) + 1; ga.rounds = (int*)(p + o_tot) + 1 + njobs;
       hipLaunchKernelGGL(k_sim3p_greedy, dim3(njobs), dim3(1024), 0, s, ga);
     } else {
-      CmsSim3pScanArgs sa = {};
-      sa.n_ent = E; sa.level = a.level; sa.rec = a.rec; sa.qslot = a.qslot; sa.mp_desc = (const uint4*)(p + o_desc); sa.cand_off = (const int*)(p + o_off);
-      sa.cand_idx = (const int*)(p + o_idx); sa.cap = cap; sa.kp = st->d_kp; sa.t_desc = (const uint4*)st->d_desc; sa.maxf = st->maxf;
-      sa.best_idx = direct ? out_a : (int*)(p + o_a); sa.best_dist = direct ? out_b : (int*)(p + o_b);
-      hipLaunchKernelGGL(k_sim3p_scan, dim3((unsigned)(((size_t)E * 8 + 255) / 256)), dim3(256), 0, s, sa);
+      const CmsWindowScanArgs sa = cms_window_scan_args(g, E, w, cap, w.rec, p + o_desc, st->d_kp, st->d_desc, w.slot, st->maxf, direct ? out_a : (int*)(p + o_a),
+                                                        direct ? out_b : (int*)(p + o_b));
+      hipLaunchKernelGGL(k_sim3p_scan, dim3(cms_window_scan_grid(E)), dim3(256), 0, s, sa);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(back.data(), p + o_tot, 4 + 2 * j4, hipMemcpyDeviceToHost, s));

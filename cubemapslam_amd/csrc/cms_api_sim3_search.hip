@@ -47,22 +47,19 @@ extern "C" int cms_kfstore_search_by_sim3(cms_kfstore* st, cms_ctx* src, int njo
   if (rc) return rc;
   const size_t e4 = (size_t)E * 4, j4 = (size_t)njobs * 4, m4 = (size_t)n_mp * 4;
   CmsBlock blk;
+  CmsWindowCols w;      // (slot: the OTHER key frame's; rec: the entry's map-point record)
   const size_t o_job = blk.take(jd.size() * sizeof(CmsSim3sJobDev)), o_eoff = blk.take(j4, 4), o_noff = blk.take(j4, 4), o_skip = blk.take((size_t)n_mp), o_pos = blk.take(3 * m4),
-               o_min = blk.take(m4), o_max = blk.take(m4), o_desc = blk.take((size_t)n_mp * 32), o_qx = blk.take(e4), o_qy = blk.take(e4), o_qr = blk.take(e4),
-               o_qmin = blk.take(e4), o_qmax = blk.take(e4), o_lvl = blk.take(e4), o_qslot = blk.take(e4), o_rec = blk.take(e4), o_cnt = blk.take(e4),
-               o_off = blk.take(e4, 4), o_match = blk.take(e4), o_idx2 = blk.take((size_t)N1 * 4), o_tot = blk.take(4 + j4);      // the total, then n_found
+               o_min = blk.take(m4), o_max = blk.take(m4), o_desc = blk.take((size_t)n_mp * 32), o_match = blk.take(e4), o_idx2 = blk.take((size_t)N1 * 4),
+               o_tot = blk.take(4 + j4);      // the total, then n_found
+  w.take(blk, (size_t)E);
   const size_t o_idx = blk.size;
-  bool direct = false;                                             // idx2 in pinned (device-visible) host memory: k_sim3s_agree stores there itself
-  {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, idx2) == hipSuccess) direct = at.type == hipMemoryTypeHost;
-    else (void)hipGetLastError();                                  // (a pageable pointer: not an error, just the copy)
-  }
+  const bool direct = cms_is_pinned(idx2);      // k_sim3s_agree stores there itself
   std::vector<int> back((size_t)njobs + 1);
   rc = cms_retry_capacity(64 * E + 1024, who, [&](int cap, int& tot) -> int {
     int rr = src->stage.reserve(s, o_idx + cms_align((size_t)cap * 4), 0);
     if (rr) return rr;
     uint8_t* p = src->stage.d;
+    w.at(p, o_idx);
     HIPCHK(hipMemcpyAsync(p + o_job, jd.data(), jd.size() * sizeof(CmsSim3sJobDev), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_eoff, ent_off.data(), j4 + 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_noff, n1_off.data(), j4 + 4, hipMemcpyHostToDevice, s));
@@ -75,26 +72,19 @@ extern "C" int cms_kfstore_search_by_sim3(cms_kfstore* st, cms_ctx* src, int njo
     CmsSim3sArgs a = {};
     a.n_ent = E; a.njobs = njobs; a.job = (const CmsSim3sJobDev*)(p + o_job); a.ent_off = (const int*)(p + o_eoff);
     a.skip = p + o_skip; a.pos = (const float*)(p + o_pos); a.min_dist = (const float*)(p + o_min); a.max_dist = (const float*)(p + o_max);
-    a.th = th; a.log_scale = std::log(g->g.nlevels > 1 ? g->scale[1] : 1.2f); a.nlevels = g->g.nlevels; a.F = g->g.F;
+    a.th = th; a.log_scale = cms_log_scale(g); a.nlevels = g->g.nlevels; a.F = g->g.F;
     a.bounds_scaled = src->dist_bounds_scaled; a.z_as_written = z_as_written ? 1 : 0;
     cms_level_table(a.sf, g, g->scale, 0.0f);
-    a.qx = (float*)(p + o_qx); a.qy = (float*)(p + o_qy); a.qr = (float*)(p + o_qr); a.qmin = (int*)(p + o_qmin); a.qmax = (int*)(p + o_qmax);
-    a.level = (int*)(p + o_lvl); a.qslot = (int*)(p + o_qslot); a.rec = (int*)(p + o_rec);
+    a.qx = w.qx; a.qy = w.qy; a.qr = w.qr; a.qmin = w.qmin; a.qmax = w.qmax; a.level = w.level; a.qslot = w.slot; a.rec = w.rec;
     hipLaunchKernelGGL(k_sim3s_project, dim3((E + 255) / 256), dim3(256), 0, s, a);
-    // window query against the grids of the store's slots, with the CALLING context's first-hits and partial-sum buffers: they belong to the
-    // context whose stream the call runs on
-    CmsAreaArgs w = cms_area_args(st->d_kp, st->d_sorted, st->d_cell_start, st->maxf, g->g.F, cms_grid_inv(g));
-    cms_area_queries(w, E, p + o_qslot, a.qx, a.qy, a.qr, a.qmin, a.qmax, p + o_cnt, p + o_off, p + o_idx, cap, 0);
-    rr = cms_area_launch(src, s, w, p + o_tot);
+    rr = kfstore_window_query(st, src, s, w, E, cap, p + o_tot);
     if (rr) return rr;
     // the scan and the agreement are enqueued right behind the windows: the total is looked at together with the results (the list kernel never
     // writes beyond `cap`, the scan never reads beyond it, and a call whose lists did not fit is simply repeated with room for them)
-    CmsSim3sScanArgs sa = {};
-    sa.n_ent = E; sa.level = a.level; sa.rec = a.rec; sa.qslot = a.qslot; sa.mp_desc = (const uint4*)(p + o_desc); sa.cand_off = (const int*)(p + o_off);
-    sa.cand_idx = (const int*)(p + o_idx); sa.cap = cap; sa.kp = st->d_kp; sa.t_desc = (const uint4*)st->d_desc; sa.maxf = st->maxf; sa.match = (int*)(p + o_match);
-    hipLaunchKernelGGL(k_sim3s_scan, dim3((unsigned)(((size_t)E * 8 + 255) / 256)), dim3(256), 0, s, sa);
+    const CmsWindowScanArgs sa = cms_window_scan_args(g, E, w, cap, w.rec, p + o_desc, st->d_kp, st->d_desc, w.slot, st->maxf, (int*)(p + o_match), nullptr);
+    hipLaunchKernelGGL(k_sim3s_scan, dim3(cms_window_scan_grid(E)), dim3(256), 0, s, sa);
     CmsSim3sAgreeArgs ga = {};
-    ga.n1_total = N1; ga.njobs = njobs; ga.job = a.job; ga.ent_off = a.ent_off; ga.n1_off = (const int*)(p + o_noff); ga.match = sa.match;
+    ga.n1_total = N1; ga.njobs = njobs; ga.job = a.job; ga.ent_off = a.ent_off; ga.n1_off = (const int*)(p + o_noff); ga.match = sa.best_idx;
     ga.idx2 = direct ? idx2 : (int*)(p + o_idx2); ga.n_found = (int*)(p + o_tot) + 1;
     hipLaunchKernelGGL(k_sim3s_agree, dim3((N1 + 255) / 256), dim3(256), 0, s, ga);
     HIPCHK(hipGetLastError());

@@ -36,7 +36,7 @@ extern "C" int cms_is_in_frustum_device(cms_ctx* c, int nmp, const void* d_mp_fr
   a.pose15 = (const float*)d_pose15; a.mp_frame = (const int*)d_mp_frame; a.n = nmp;
   a.P = (const float*)d_pos; a.normal = (const float*)d_normal; a.min_dist = (const float*)d_min_dist; a.max_dist = (const float*)d_max_dist;
   a.viewing_cos_limit = viewing_cos_limit; a.th = th; a.bounds_scaled = c->dist_bounds_scaled;
-  a.log_scale = std::log(c->g.nlevels > 1 ? c->scale[1] : 1.2f);          // mfLogScaleFactor = log(mfScaleFactor), float (Frame.cpp:113)
+  a.log_scale = cms_log_scale(c);          // mfLogScaleFactor = log(mfScaleFactor), float (Frame.cpp:113)
   a.nlevels = c->g.nlevels; a.F = c->g.F;
   cms_level_table(a.sf, c, c->scale, 0.0f);
   a.in_view = (uint8_t*)d_in_view; a.proj_x = (float*)d_proj_x; a.proj_y = (float*)d_proj_y; a.level = (int*)d_level; a.view_cos = (float*)d_view_cos;

@@ -1,7 +1,7 @@
 // cms_api_tri.hip -- host side of LocalMapping::CreateNewMapPoints and of the search half of ORBMatcher::Fuse, included by
 // cms_lib.hip after cms_api_track.hip.  Scratch blocks live in the context's CmsStage and are laid out with CmsBlock (TriWork: the work area of a
-// CreateNewMapPoints call); the two Fuse entries fill their kernels' arguments with fuse_project_args / fuse_scan_args, query the windows through
-// cms_area_launch and repeat a call whose candidate lists did not fit through cms_retry_capacity.
+// CreateNewMapPoints call); the two Fuse entries lay out their window columns with CmsWindowCols, fill their kernels' arguments with
+// fuse_project_args / cms_window_scan_args (the Sim3 entries' scans too), query the windows through cms_area_launch / kfstore_window_query and repeat a call whose candidate lists did not fit through cms_retry_capacity.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -754,24 +754,35 @@ extern "C" int cms_kfstore_create_new_map_points(cms_kfstore* st, int njobs, con
 // ---- search half of ORBMatcher::Fuse: the arguments of its two kernels, for one key frame of the context and for jobs on the store alike
 // k_fuse_project: n entries; mp_frame (NULL: all in frame 0 of pose15) names an entry's pose, src (NULL: itself) the map point it stands for
 static CmsFuseArgs fuse_project_args(const cms_ctx* c, int n, float th, const void* pose15, const void* mp_frame, const void* skip, const void* src, const void* P,
-                                     const void* normal, const void* min_dist, const void* max_dist, void* qx, void* qy, void* qr, void* qmin, void* qmax, void* level) {
+                                     const void* normal, const void* min_dist, const void* max_dist, const CmsWindowCols& w) {
   CmsFuseArgs a = {};
   a.pose15 = (const float*)pose15; a.mp_frame = (const int*)mp_frame; a.n = n; a.skip = (const uint8_t*)skip; a.src = (const int*)src;
   a.P = (const float*)P; a.normal = (const float*)normal; a.min_dist = (const float*)min_dist; a.max_dist = (const float*)max_dist;
+  // (not cms_log_scale: a context of one level has scale[1] == 0 where that helper assumes 1.2f; every level is clamped to 0 either way, but
+  // the kernel's argument would change)
   a.th = th; a.log_scale = std::log(c->scale[1]); a.nlevels = c->g.nlevels; a.F = c->g.F; a.bounds_scaled = c->dist_bounds_scaled;
   cms_level_table(a.sf, c, c->scale, 0.0f);
-  a.qx = (float*)qx; a.qy = (float*)qy; a.qr = (float*)qr; a.qmin = (int*)qmin; a.qmax = (int*)qmax; a.level = (int*)level;
+  a.qx = w.qx; a.qy = w.qy; a.qr = w.qr; a.qmin = w.qmin; a.qmax = w.qmax; a.level = w.level;
   return a;
 }
-// k_fuse_scan over the windows of `fa`'s projections.  cap / row_slot / maxf: see CmsFuseScanArgs (0 / NULL / 0 for one key frame of the context)
-static CmsFuseScanArgs fuse_scan_args(const cms_ctx* c, const CmsFuseArgs& fa, const void* mp_desc, const void* cand_off, const void* cand_idx, const CmsKeyPoint* kp,
-                                      const void* t_desc, int* best_idx, int* best_dist, int cap, const void* row_slot, int maxf) {
-  CmsFuseScanArgs a = {};
-  a.n = fa.n; a.qx = fa.qx; a.qy = fa.qy; a.level = fa.level; a.src = fa.src; a.mp_desc = (const uint4*)mp_desc;
-  a.cand_off = (const int*)cand_off; a.cand_idx = (const int*)cand_idx; a.kp = kp; a.t_desc = (const uint4*)t_desc;
-  cms_level_table(a.inv_sigma2, c, c->inv_sigma2, 0.0f);
-  a.best_idx = best_idx; a.best_dist = best_dist; a.cap = cap; a.row_slot = (const int*)row_slot; a.maxf = maxf;
+// The window scan (k_fuse_scan / k_sim3s_scan / k_sim3p_scan) over the lists of `w`, `cap` entries of which exist.  g: the geometry of the grids.
+// src (NULL: itself): the map-point record of an entry; row_slot / maxf (NULL / 0: one key frame of the context): see CmsWindowScanArgs.
+static CmsWindowScanArgs cms_window_scan_args(const cms_ctx* g, int n, const CmsWindowCols& w, int cap, const int* src, const void* mp_desc, const CmsKeyPoint* kp,
+                                              const void* t_desc, const int* row_slot, int maxf, int* best_idx, int* best_dist) {
+  CmsWindowScanArgs a = {};
+  a.n = n; a.qx = w.qx; a.qy = w.qy; a.level = w.level; a.src = src; a.mp_desc = (const uint4*)mp_desc;
+  a.cand_off = w.off; a.cand_idx = w.idx; a.cap = cap; a.kp = kp; a.t_desc = (const uint4*)t_desc;
+  cms_level_table(a.inv_sigma2, g, g->inv_sigma2, 0.0f);
+  a.row_slot = row_slot; a.maxf = maxf; a.best_idx = best_idx; a.best_dist = best_dist;
   return a;
+}
+static unsigned cms_window_scan_grid(int n) { return (unsigned)(((size_t)n * 8 + 255) / 256); }
+// The window query of E entries against the grids of the store's slots (w.slot names each entry's), with the first-hits and partial-sum buffers
+// of `ctx`: they belong to the context whose stream the call runs on
+static int kfstore_window_query(const cms_kfstore* st, cms_ctx* ctx, hipStream_t s, const CmsWindowCols& w, int E, int cap, void* d_total) {
+  CmsAreaArgs a = cms_area_args(st->d_kp, st->d_sorted, st->d_cell_start, st->maxf, st->c->g.F, cms_grid_inv(st->c));
+  cms_area_queries(a, E, w, cap);
+  return cms_area_launch(ctx, s, a, d_total);
 }
 
 // search half of ORBMatcher::Fuse(pKF, vpMapPoints, th) for key frame slot b (cms_area_set_keypoints / _descriptors + cms_area_grid first)
@@ -786,14 +797,16 @@ extern "C" int cms_fuse_search(cms_ctx* c, int b, const float* pose15, int nmp, 
   hipStream_t s = c->stream;
   const size_t n4 = (size_t)nmp * 4;
   CmsBlock blk;
+  CmsWindowCols w;      // (slot: the frame row b of every query; rec is not used)
   const size_t o_pose = blk.take(64), o_skip = blk.take(nmp), o_pos = blk.take(3 * n4), o_nrm = blk.take(3 * n4), o_min = blk.take(n4), o_max = blk.take(n4),
-               o_desc = blk.take((size_t)nmp * 32), o_qx = blk.take(n4), o_qy = blk.take(n4), o_qr = blk.take(n4), o_qmin = blk.take(n4), o_qmax = blk.take(n4),
-               o_lvl = blk.take(n4), o_cnt = blk.take(n4), o_off = blk.take(n4, 4), o_tot = blk.take(16), o_qf = blk.take(n4), o_bi = blk.take(n4), o_bd = blk.take(n4);
+               o_desc = blk.take((size_t)nmp * 32), o_tot = blk.take(16), o_bi = blk.take(n4), o_bd = blk.take(n4);
+  w.take(blk, (size_t)nmp);
   const size_t o_idx = blk.size;
   return cms_retry_capacity(64 * nmp + 1024, "cms_fuse_search", [&](int cap, int& tot) -> int {
     int rc = c->stage.reserve(s, o_idx + cms_align((size_t)cap * 4), 0);
     if (rc) return rc;
     uint8_t* p = c->stage.d;
+    w.at(p, o_idx);
     HIPCHK(hipMemcpyAsync(p + o_pose, pose15, 60, hipMemcpyHostToDevice, s));
     if (skip) HIPCHK(hipMemcpyAsync(p + o_skip, skip, nmp, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_pos, pos, 3 * n4, hipMemcpyHostToDevice, s));
@@ -802,19 +815,17 @@ extern "C" int cms_fuse_search(cms_ctx* c, int b, const float* pose15, int nmp, 
     HIPCHK(hipMemcpyAsync(p + o_max, max_dist, n4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_desc, mp_desc, (size_t)nmp * 32, hipMemcpyHostToDevice, s));
     const std::vector<int> qf((size_t)nmp, b);
-    HIPCHK(hipMemcpyAsync(p + o_qf, qf.data(), n4, hipMemcpyHostToDevice, s));
-    const CmsFuseArgs fa = fuse_project_args(c, nmp, th, p + o_pose, nullptr, skip ? p + o_skip : nullptr, nullptr, p + o_pos, p + o_nrm, p + o_min, p + o_max,
-                                             p + o_qx, p + o_qy, p + o_qr, p + o_qmin, p + o_qmax, p + o_lvl);
+    HIPCHK(hipMemcpyAsync(w.slot, qf.data(), n4, hipMemcpyHostToDevice, s));
+    const CmsFuseArgs fa = fuse_project_args(c, nmp, th, p + o_pose, nullptr, skip ? p + o_skip : nullptr, nullptr, p + o_pos, p + o_nrm, p + o_min, p + o_max, w);
     hipLaunchKernelGGL(k_fuse_project, dim3((nmp + 255) / 256), dim3(256), 0, s, fa);
     HIPCHK(hipGetLastError());
-    rc = cms_features_in_area_batch_device(c, nmp, p + o_qf, p + o_qx, p + o_qy, p + o_qr, p + o_qmin, p + o_qmax, p + o_cnt, p + o_off, p + o_idx, cap,
-                                           p + o_tot);
+    rc = cms_features_in_area_batch_device(c, nmp, w.slot, w.qx, w.qy, w.qr, w.qmin, w.qmax, w.cnt, w.off, w.idx, cap, p + o_tot);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(&tot, p + o_tot, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (tot > cap) return CMS_OK;
-    const CmsFuseScanArgs sa = fuse_scan_args(c, fa, p + o_desc, p + o_off, p + o_idx, (const CmsKeyPoint*)c->d_kps, c->d_desc, (int*)(p + o_bi), (int*)(p + o_bd), 0, nullptr, 0);
-    hipLaunchKernelGGL(k_fuse_scan, dim3((nmp * 8 + 255) / 256), dim3(256), 0, s, sa);
+    const CmsWindowScanArgs sa = cms_window_scan_args(c, nmp, w, cap, nullptr, p + o_desc, (const CmsKeyPoint*)c->d_kps, c->d_desc, nullptr, 0, (int*)(p + o_bi), (int*)(p + o_bd));
+    hipLaunchKernelGGL(k_fuse_scan, dim3(cms_window_scan_grid(nmp)), dim3(256), 0, s, sa);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(best_idx, p + o_bi, n4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(best_dist, p + o_bd, n4, hipMemcpyDeviceToHost, s));
@@ -906,8 +917,7 @@ k_fuse_expand_jobs(int nmp, int njobs, const int* __restrict__ mp_off, const int
                    const int* __restrict__ job_set0, int* __restrict__ mp_src) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nmp) return;
-  int lo = 0, hi = njobs;                                          // last job whose first map point is <= i (empty jobs skipped by the search)
-  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (mp_off[mid] <= i) lo = mid; else hi = mid; }
+  const int lo = cms_job_of(mp_off, njobs, i);
   mp_job[i] = lo; mp_slot[i] = job_slot[lo];
   if (mp_src) mp_src[i] = job_set0[lo] + (i - mp_off[lo]);         // jobs over shared sets of map points: entry -> the set's map point
 }
@@ -939,22 +949,18 @@ static int kfstore_fuse_core(cms_kfstore* st, int njobs, const int* job_slot, co
   if (!job_set0) npts = nmp;
   const size_t n4 = (size_t)nmp * 4, j4 = (size_t)njobs * 4, p4 = (size_t)npts * 4;
   CmsBlock blk;
-  const size_t o_pose = blk.take(pose.size() * 4), o_joff = blk.take(j4, 4), o_jslot = blk.take(j4), o_jset = blk.take(j4), o_src = blk.take(n4), o_job = blk.take(n4),
-               o_slot = blk.take(n4), o_skip = blk.take(nmp), o_pos = blk.take(3 * p4), o_nrm = blk.take(3 * p4), o_min = blk.take(p4), o_max = blk.take(p4),
-               o_desc = blk.take((size_t)npts * 32), o_qx = blk.take(n4), o_qy = blk.take(n4), o_qr = blk.take(n4), o_qmin = blk.take(n4), o_qmax = blk.take(n4),
-               o_lvl = blk.take(n4), o_cnt = blk.take(n4), o_off = blk.take(n4, 4), o_tot = blk.take(16), o_bi = blk.take(n4), o_bd = blk.take(n4);
+  CmsWindowCols w;      // (slot: the job's; rec: the set's map point an entry stands for, when the jobs share sets)
+  const size_t o_pose = blk.take(pose.size() * 4), o_joff = blk.take(j4, 4), o_jslot = blk.take(j4), o_jset = blk.take(j4), o_job = blk.take(n4), o_skip = blk.take(nmp),
+               o_pos = blk.take(3 * p4), o_nrm = blk.take(3 * p4), o_min = blk.take(p4), o_max = blk.take(p4), o_desc = blk.take((size_t)npts * 32), o_tot = blk.take(16),
+               o_bi = blk.take(n4), o_bd = blk.take(n4);
+  w.take(blk, (size_t)nmp);
   const size_t o_idx = blk.size;
-  bool direct = false;
-  {
-    hipPointerAttribute_t a1, a2;
-    if (hipPointerGetAttributes(&a1, best_idx) == hipSuccess && hipPointerGetAttributes(&a2, best_dist) == hipSuccess)
-      direct = a1.type == hipMemoryTypeHost && a2.type == hipMemoryTypeHost;
-    else (void)hipGetLastError();                                  // (a pageable pointer: not an error, just the copies)
-  }
+  const bool direct = cms_is_pinned(best_idx) && cms_is_pinned(best_dist);
   return cms_retry_capacity(64 * nmp + 1024, "cms_kfstore_fuse_search", [&](int cap, int& tot) -> int {
     int rc = c->stage.reserve(s, o_idx + cms_align((size_t)cap * 4), 0);
     if (rc) return rc;
     uint8_t* p = c->stage.d;
+    w.at(p, o_idx);
     HIPCHK(hipMemcpyAsync(p + o_pose, pose.data(), pose.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_joff, mp_off, j4 + 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_jslot, job_slot, j4, hipMemcpyHostToDevice, s));
@@ -965,23 +971,20 @@ static int kfstore_fuse_core(cms_kfstore* st, int njobs, const int* job_slot, co
     HIPCHK(hipMemcpyAsync(p + o_min, min_dist, p4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_max, max_dist, p4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(p + o_desc, mp_desc, (size_t)npts * 32, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_fuse_expand_jobs, dim3((nmp + 255) / 256), dim3(256), 0, s, nmp, njobs, (const int*)(p + o_joff), (const int*)(p + o_jslot), (int*)(p + o_job), (int*)(p + o_slot),
-                       job_set0 ? (const int*)(p + o_jset) : nullptr, job_set0 ? (int*)(p + o_src) : nullptr);
-    const CmsFuseArgs fa = fuse_project_args(c, nmp, th, p + o_pose, p + o_job, skip ? p + o_skip : nullptr, job_set0 ? p + o_src : nullptr, p + o_pos, p + o_nrm, p + o_min,
-                                             p + o_max, p + o_qx, p + o_qy, p + o_qr, p + o_qmin, p + o_qmax, p + o_lvl);
+    int* src = job_set0 ? w.rec : nullptr;
+    hipLaunchKernelGGL(k_fuse_expand_jobs, dim3((nmp + 255) / 256), dim3(256), 0, s, nmp, njobs, (const int*)(p + o_joff), (const int*)(p + o_jslot), (int*)(p + o_job), w.slot,
+                       job_set0 ? (const int*)(p + o_jset) : nullptr, src);
+    const CmsFuseArgs fa = fuse_project_args(c, nmp, th, p + o_pose, p + o_job, skip ? p + o_skip : nullptr, src, p + o_pos, p + o_nrm, p + o_min, p + o_max, w);
     hipLaunchKernelGGL(k_fuse_project, dim3((nmp + 255) / 256), dim3(256), 0, s, fa);
-    // window query against the grids of the store's slots (the context's first-hits buffer: this call runs on the context's stream)
-    CmsAreaArgs a = cms_area_args(st->d_kp, st->d_sorted, st->d_cell_start, st->maxf, c->g.F, cms_grid_inv(c));
-    cms_area_queries(a, nmp, p + o_slot, fa.qx, fa.qy, fa.qr, fa.qmin, fa.qmax, p + o_cnt, p + o_off, p + o_idx, cap, 0);
-    rc = cms_area_launch(c, s, a, p + o_tot);
+    rc = kfstore_window_query(st, c, s, w, nmp, cap, p + o_tot);
     if (rc) return rc;
     // The scan is enqueued right behind the windows: the total is looked at together with the results (ONE synchronisation per call; the list kernel
-    // never writes beyond `cap`, and a call whose lists did not fit is simply repeated with room for them).
+    // never writes beyond `cap`, the scan never reads beyond it, and a call whose lists did not fit is simply repeated with room for them).
     // Result arrays in pinned (device-visible) host memory: the kernels store there themselves -- copies queued behind kernels of the same stream are
     // blit kernels of the runtime, two more dependent launches that wait for a slot on a busy chip
-    const CmsFuseScanArgs sa = fuse_scan_args(c, fa, p + o_desc, p + o_off, p + o_idx, st->d_kp, st->d_desc, direct ? best_idx : (int*)(p + o_bi),
-                                              direct ? best_dist : (int*)(p + o_bd), cap, p + o_slot, st->maxf);
-    hipLaunchKernelGGL(k_fuse_scan, dim3((nmp * 8 + 255) / 256), dim3(256), 0, s, sa);      // (stores the key-point index inside the job's key frame: row - slot x maxf)
+    const CmsWindowScanArgs sa = cms_window_scan_args(c, nmp, w, cap, src, p + o_desc, st->d_kp, st->d_desc, w.slot, st->maxf, direct ? best_idx : (int*)(p + o_bi),
+                                                      direct ? best_dist : (int*)(p + o_bd));
+    hipLaunchKernelGGL(k_fuse_scan, dim3(cms_window_scan_grid(nmp)), dim3(256), 0, s, sa);      // (stores the key-point index inside the job's key frame: row - slot x maxf)
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(&tot, p + o_tot, sizeof(int), hipMemcpyDeviceToHost, s));
     if (!direct) {

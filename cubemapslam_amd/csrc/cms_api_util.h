@@ -37,6 +37,16 @@ static inline float cms_cos_fov(const cms_ctx* c) {      // CamModelGeneral::Set
   const float pif = 3.1415926535897932384626f;
   return std::cos(fov / 2 * (pif / 180));
 }
+static inline float cms_log_scale(const cms_ctx* c) {      // mfLogScaleFactor = log(mfScaleFactor), float (Frame.cpp:113)
+  return std::log(c->g.nlevels > 1 ? c->scale[1] : 1.2f);
+}
+// a result array in pinned (device-visible) host memory: the last kernel of a call may store there itself
+static inline bool cms_is_pinned(const void* ptr) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, ptr) == hipSuccess) return at.type == hipMemoryTypeHost;
+  (void)hipGetLastError();                                         // (a pageable pointer: not an error, just the copy)
+  return false;
+}
 static inline float cms_grid_inv(const cms_ctx* c) { return (float)(3 * CMS_AREA_G) / (float)c->g.W; }      // mfGridElementLengthInv (Frame.cpp:149)
 
 // Raise a kernel's dynamic-LDS ceiling above the 64 KB default.  The attribute is per function AND per device: `done` is the kernel's own

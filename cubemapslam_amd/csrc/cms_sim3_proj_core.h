@@ -5,8 +5,8 @@
 // the gfx950 kernel (k_sim3p_project, cms_sim3_proj_kernels.hip); the host side of the two C-ABI entries decomposes each job's Scw through it as
 // well.  Compiles under g++ as it stands.  Plain IEEE operations in the order this source fixes; both builds use -ffp-contract=off.
 //
-// The chain calls the helpers k_fuse_project calls (tri_mat3_vec, tri_dnorm3, tri_ddot3, track_distance_bounds, track_rays_to_cubemap); in the
-// device build they ARE the kernels' helpers, for g++ cms_sim3_search_core.h carries their twins and this header adds tri_ddot3's.
+// The chain calls the helpers k_fuse_project calls (tri_mat3_vec, tri_dnorm3, tri_ddot3, track_distance_bounds, track_predict_scale,
+// track_rays_to_cubemap): one CMS_HD definition each for both builds (cms_project_helpers.h, cms_cubemap_project.h).
 //
 // Three expressions are new here; one stated choice each (DESIGN.md "SearchByProjection / Fuse under a Sim3"), on the row-major 3 x 4 [sR | t]:
 //   scw = sqrt(sRcw.row(0).dot(sRcw.row(0)))   the double sum of the double products, k upwards from 0.0; sqrt in double; narrowed to float once
@@ -18,21 +18,13 @@
 // assert (:836, :1287) aborts; here u = v = -1 and the point is dropped by the IsInImage test.
 #ifndef CMS_SIM3_PROJ_CORE_H
 #define CMS_SIM3_PROJ_CORE_H
-#include "cms_sim3_search_core.h"     // CMS_HD, track_rays_to_cubemap and, for g++, the twins of tri_mat3_vec / tri_dnorm3 / track_distance_bounds
+#include "cms_project_helpers.h"
 
 #define CMS_SIM3P_KEEP 0
 #define CMS_SIM3P_BEHIND 1      /* z < 0 (:827, :1278) */
 #define CMS_SIM3P_IMAGE 2       /* unknown face or !IsInImage (:839, :1290) */
 #define CMS_SIM3P_DIST 3        /* outside the scale-invariance distances (:848, :1299) */
 #define CMS_SIM3P_ANGLE 4       /* PO.dot(Pn) < 0.5 * dist (:854, :1305) */
-
-#if !defined(__HIPCC__)
-static inline double tri_ddot3(const float* a, const float* b) {
-  double s = (double)a[0] * (double)b[0];
-  s = s + (double)a[1] * (double)b[1];
-  return s + (double)a[2] * (double)b[2];
-}
-#endif
 
 struct CmsSim3pPose { float Rcw[9], tcw[3], Ow[3], scw; };
 
@@ -54,18 +46,10 @@ CMS_HD void cms_sim3p_decompose(const float* Scw, CmsSim3pPose* p) {
   }
 }
 
-// MapPoint::PredictScale as k_fuse_project has it: ceil((float)log((double)ratio) / log_scale), clamped to [0, nlevels)
-CMS_SIM3S_CHAIN int cms_sim3p_predict_level(float raw_max, float dist, float log_scale, int nlevels) {
-  const float ratio = raw_max / dist;
-  int ns = (int)ceilf((float)log((double)ratio) / log_scale);
-  if (ns < 0) ns = 0; else if (ns >= nlevels) ns = nlevels - 1;
-  return ns;
-}
-
 // One map point through the decomposed similarity.  u, v = -1 unless the point reaches the distance test; level = -1 and radius = -1 unless it is
 // kept; dist is always written.  sf: mvScaleFactors.
-CMS_SIM3S_CHAIN int cms_sim3p_project(int F, const CmsSim3pPose* ps, const float* Pw, const float* Pn, int bounds_scaled, float min_in, float max_in, float th,
-                                      float log_scale, int nlevels, const float* sf, float* u, float* v, float* dist, int* level, float* radius) {
+CMS_HD int cms_sim3p_project(int F, const CmsSim3pPose* ps, const float* Pw, const float* Pn, int bounds_scaled, float min_in, float max_in, float th,
+                             float log_scale, int nlevels, const float* sf, float* u, float* v, float* dist, int* level, float* radius) {
   float pc[3];
   tri_mat3_vec(ps->Rcw, Pw, ps->tcw, pc);                                        // p3Dc = Rcw*p3Dw+tcw
   const float PO[3] = {Pw[0] - ps->Ow[0], Pw[1] - ps->Ow[1], Pw[2] - ps->Ow[2]}; // PO = p3Dw-Ow
@@ -81,7 +65,7 @@ CMS_SIM3S_CHAIN int cms_sim3p_project(int F, const CmsSim3pPose* ps, const float
   track_distance_bounds(bounds_scaled, min_in, max_in, minDistance, maxDistance, maxd);
   if (d < minDistance || d > maxDistance) return CMS_SIM3P_DIST;
   if (tri_ddot3(PO, Pn) < 0.5 * (double)d) return CMS_SIM3P_ANGLE;
-  const int ns = cms_sim3p_predict_level(maxd, d, log_scale, nlevels);
+  const int ns = track_predict_scale(maxd, d, log_scale, nlevels);
   *level = ns; *radius = th * sf[ns];
   return CMS_SIM3P_KEEP;
 }

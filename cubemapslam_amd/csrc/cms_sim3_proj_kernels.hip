@@ -6,8 +6,7 @@
 //                     the window (qx, qy, qr; qr < 0 = dropped), the predicted level and the drop code.  The set is shared: the entry reads the
 //                     point's record through `rec`, as CmsFuseArgs::src does
 //   (window query)    cms_area_kernels.hip against the store's grids, no level filter: KeyFrame::GetFeaturesInArea(u, v, radius), its order
-//   k_sim3p_scan      Fuse's scan (:1323-1342), eight lanes per entry: octave in {level - 1, level}, Hamming distance, key = dist << 20 | position,
-//                     so the first strict minimum in list order wins; accepted when dist <= TH_LOW (50).  k_fuse_scan without its reprojection gate
+//   k_sim3p_scan      Fuse's scan (:1323-1342): cms_window_scan (cms_tri_kernels.hip) without the reprojection gate, accepted when dist <= TH_LOW (50)
 //   k_sim3p_greedy    SearchByProjection's scan (:870-898), one workgroup per job.  The reference's loop is sequential: `if(vpMatched[idx]) continue;`
 //                     skips key points taken on entry and key points an earlier iMP of the same call took.  Resolved in rounds the way
 //                     k_search_local does: an entry is decided in the round in which it is the lowest undecided claimant of every free candidate
@@ -42,7 +41,7 @@ struct CmsSim3pArgs {
 extern "C" __global__ void __launch_bounds__(256) k_sim3p_project(CmsSim3pArgs a) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= a.n_ent) return;
-  const int j = sim3s_job_of(a.ent_off, a.njobs, e);
+  const int j = cms_job_of(a.ent_off, a.njobs, e);
   const CmsSim3pJobDev* jb = a.job + j;
   const int r = jb->set0 + (e - a.ent_off[j]);
   float u = -1.0f, v = -1.0f, qr = -1.0f, dist; int lvl = -1, why = -1;
@@ -54,42 +53,6 @@ extern "C" __global__ void __launch_bounds__(256) k_sim3p_project(CmsSim3pArgs a
   if (jb->n == 0) qr = -1.0f;                      // a key frame without key points: no window
   a.qx[e] = u; a.qy[e] = v; a.qr[e] = qr; a.qmin[e] = -1; a.qmax[e] = -1; a.level[e] = lvl;
   a.qslot[e] = jb->slot; a.rec[e] = r; a.why[e] = why;
-}
-
-struct CmsSim3pScanArgs {
-  int n_ent; const int* level; const int* rec; const int* qslot; const uint4* mp_desc;
-  const int* cand_off; const int* cand_idx;      // the window query's lists: rows of the store (slot x maxf + key point)
-  int cap;                                       // entries of cand_idx that exist: the scan is enqueued before the host has seen the total
-  const CmsKeyPoint* kp; const uint4* t_desc; int maxf;
-  int* best_idx; int* best_dist;                 // per entry: key point of the job's key frame or -1, its distance or 256
-};
-extern "C" __global__ void __launch_bounds__(256) k_sim3p_scan(CmsSim3pScanArgs a) {
-  const int gl = threadIdx.x & 7;
-  const int e = (blockIdx.x * blockDim.x + threadIdx.x) >> 3;
-  const bool live = e < a.n_ent;
-  const int ee = live ? e : 0;
-  const int c0 = live ? min(a.cand_off[ee], a.cap) : 0, c1 = live ? min(a.cand_off[ee + 1], a.cap) : 0;
-  const int lvl = a.level[ee];
-  uint32_t key = 0xFFFFFFFFu;                        // dist << 20 | position: the first minimum in list order wins
-  if (c1 > c0) {
-    const size_t mi = (size_t)a.rec[ee];
-    const uint4 d0 = a.mp_desc[2 * mi], d1 = a.mp_desc[2 * mi + 1];
-    for (int c = c0 + gl; c < c1; c += 8) {
-      const size_t row = (size_t)a.cand_idx[c];
-      const int oct = a.kp[row].octave;
-      if (oct < lvl - 1 || oct > lvl) continue;
-      const uint32_t d = (uint32_t)tri_hamming256(d0, d1, a.t_desc[2 * row], a.t_desc[2 * row + 1]);
-      key = min(key, (d << 20) | (uint32_t)(c - c0));
-    }
-  }
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) key = min(key, (uint32_t)__shfl_xor((int)key, o, 8));
-  if (live && gl == 0) {
-    const int d = key == 0xFFFFFFFFu ? 256 : (int)(key >> 20);      // no surviving candidate: bestDist stays INT_MAX
-    const bool hit = d <= 50;                                        // TH_LOW
-    a.best_idx[e] = hit ? a.cand_idx[c0 + (int)(key & 0xFFFFFu)] - a.qslot[e] * a.maxf : -1;
-    a.best_dist[e] = hit ? d : 256;
-  }
 }
 
 struct CmsSim3pGreedyArgs {

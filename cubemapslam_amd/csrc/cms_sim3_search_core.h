@@ -9,8 +9,7 @@
 //   cv::norm     tri_dnorm3: sqrt of the double sum of double squares; narrowed by the caller
 //   distances    track_distance_bounds: Get{Min,Max}DistanceInvariance and mfMaxDistance from what cms_set_distance_bounds_mode says was handed over
 //   projection   track_rays_to_cubemap (cms_cubemap_project.h)
-// In the device build these ARE the kernels' helpers (cms_tri_kernels.hip, cms_track_kernels.hip, included before this header).  g++ cannot see
-// __device__ functions of a .hip file, so the host build gets twins below, operation for operation; tests/test_sim3_search_cpu.py holds them to
+// The first three live in cms_project_helpers.h, one CMS_HD definition each for both builds; tests/test_sim3_search_cpu.py holds the host build to
 // the numpy restatement bit for bit and tests/test_gpu_search_by_sim3.py holds the device to the same restatement.
 //
 // Three expressions are new here; one stated choice each (DESIGN.md "SearchBySim3 on the device"):
@@ -24,56 +23,12 @@
 // (vp == F) and is dropped this way.
 #ifndef CMS_SIM3_SEARCH_CORE_H
 #define CMS_SIM3_SEARCH_CORE_H
-#include <math.h>
-#include <string.h>
-#include "cms_cubemap_project.h"      // CMS_HD, track_rays_to_cubemap = CamModelGeneral::TransformRaysToCubemap
+#include "cms_project_helpers.h"      // CMS_HD, tri_*, track_distance_bounds, track_rays_to_cubemap = CamModelGeneral::TransformRaysToCubemap
 
 #define CMS_SIM3S_KEEP 0
 #define CMS_SIM3S_BEHIND 1      /* z < 0 (:1421, :1502) */
 #define CMS_SIM3S_IMAGE 2       /* unknown face or !IsInImage (:1433, :1514) */
 #define CMS_SIM3S_DIST 3        /* outside the scale-invariance distances (:1441, :1522) */
-
-#if defined(__HIPCC__)
-#define CMS_SIM3S_CHAIN __device__ __forceinline__
-#else
-#define CMS_SIM3S_CHAIN inline
-// host twins of the kernels' helpers (see above); the names are the kernels' so that the chain below is one text
-static inline float tri_gemm3(float a0, float a1, float a2, float b0, float b1, float b2) {
-  float t = a0 * b0;
-  t = t + a1 * b1;
-  return t + a2 * b2;
-}
-static inline double tri_dnorm3(const float* a) {
-  double s = (double)a[0] * (double)a[0];
-  s = s + (double)a[1] * (double)a[1];
-  return sqrt(s + (double)a[2] * (double)a[2]);
-}
-static inline void tri_mat3_vec(const float* A, const float* x, const float* c, float* out) {
-  for (int r = 0; r < 3; ++r) {
-    const float t = tri_gemm3(A[3 * r], A[3 * r + 1], A[3 * r + 2], x[0], x[1], x[2]);
-    out[r] = c ? (float)((double)t * 1.0 + (double)c[r] * 1.0) : t;
-  }
-}
-static inline float cms_sim3s_next_float(float r, int step) {
-  unsigned u;
-  memcpy(&u, &r, 4);
-  u += (unsigned)step;
-  memcpy(&r, &u, 4);
-  return r;
-}
-static inline void track_distance_bounds(int scaled, float min_in, float max_in, float& minDistance, float& maxDistance, float& raw_max) {
-  if (scaled) {
-    maxDistance = max_in; minDistance = min_in;
-    float r = (float)((double)max_in / (double)1.2f);
-    const float lo = cms_sim3s_next_float(r, -1), hi = cms_sim3s_next_float(r, 1);
-    if (r > 0.0f && 1.2f * lo == max_in) r = lo;
-    else if (1.2f * r != max_in && 1.2f * hi == max_in) r = hi;
-    raw_max = r;
-  } else {
-    raw_max = max_in; maxDistance = 1.2f * max_in; minDistance = 0.8f * min_in;
-  }
-}
-#endif
 
 // sR12 | t12 carry key frame 2's camera frame into key frame 1's, sR21 | t21 the other way (row major)
 struct CmsSim3sMotion { float sR12[9], t12[3], sR21[9], t21[3]; };
@@ -94,8 +49,8 @@ CMS_HD void cms_sim3s_compose(float s12, const float* R12, const float* t12, Cms
 // One direction for one map point: Pw through its own key frame's pose (Rw | tw), then through the similarity (sR | t) into the other camera.
 // second_as_depth != 0: the ray handed to the projection is (x, y, y), line :1507 as written; the depth test and dist3D use the true vector.
 // u, v = -1 unless the point reaches the distance test; dist3D and raw_max (mfMaxDistance, PredictScale's numerator) are always written.
-CMS_SIM3S_CHAIN int cms_sim3s_project(int F, const float* Rw, const float* tw, const float* sR, const float* t, const float* Pw, int second_as_depth,
-                                      int bounds_scaled, float min_in, float max_in, float* u, float* v, float* dist3D, float* raw_max) {
+CMS_HD int cms_sim3s_project(int F, const float* Rw, const float* tw, const float* sR, const float* t, const float* Pw, int second_as_depth,
+                             int bounds_scaled, float min_in, float max_in, float* u, float* v, float* dist3D, float* raw_max) {
   float pa[3], pb[3];
   tri_mat3_vec(Rw, Pw, tw, pa);                      // p3Dc1 = R1w*p3Dw + t1w   (p3Dc2 = R2w*p3Dw + t2w)
   tri_mat3_vec(sR, pa, t, pb);                       // p3Dc2 = sR21*p3Dc1 + t21 (p3Dc1 = sR12*p3Dc2 + t12)

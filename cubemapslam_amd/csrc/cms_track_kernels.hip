@@ -32,30 +32,12 @@ struct CmsFrustumArgs {
 };
 
 // [host-emulation begin: bounds helpers] -- tests/test_project_keyframe_emu_cpu.py compiles the text between the markers for the host
-// Scale-invariance bounds of a map point (MapPoint.cpp:375-385) and mfMaxDistance itself, from what the caller handed over
-// (cms_set_distance_bounds_mode): the raw members, or the public getters' values
-__device__ __forceinline__ void track_distance_bounds(int scaled, float min_in, float max_in, float& minDistance, float& maxDistance, float& raw_max) {
-  if (scaled) {
-    maxDistance = max_in; minDistance = min_in;
-    float r = (float)((double)max_in / (double)1.2f);
-    const float lo = __uint_as_float(__float_as_uint(r) - 1u), hi = __uint_as_float(__float_as_uint(r) + 1u);
-    if (r > 0.0f && __fmul_rn(1.2f, lo) == max_in) r = lo;
-    else if (__fmul_rn(1.2f, r) != max_in && __fmul_rn(1.2f, hi) == max_in) r = hi;
-    raw_max = r;
-  } else {
-    raw_max = max_in; maxDistance = __fmul_rn(1.2f, max_in); minDistance = __fmul_rn(0.8f, min_in);
-  }
-}
-
-// CamModelGeneral::TransformRaysToCubemap: track_rays_to_cubemap, shared with the PnP core
-#include "cms_cubemap_project.h"
+// tri_*, track_distance_bounds, track_predict_scale and (through cms_cubemap_project.h) track_rays_to_cubemap: one source for both builds
+#include "cms_project_helpers.h"
 
 // `dist3D = cv::norm(P - Ow)` against the point's invariance bounds, shared by Frame::isInFrustum (Frame.cpp:222-231) and the key-frame
 // SearchByProjection (ORBMatcher.cpp:292-300): float difference, double sum of double squares, sqrt narrowed to float.  Returns false when the
 // distance is outside [minDistance, maxDistance]; raw_max = mfMaxDistance itself for track_predict_scale.
-// mfMaxDistance and the two invariance bounds: handed the public getters' values, the bounds are used as they are and mfMaxDistance is recovered
-// as the float r with 1.2f * r == bound (the product rounds up to two neighbouring r onto one bound when it crosses a power of two; the smaller
-// one is taken -- PredictScale can then differ from the reference only where log(ratio) / log(scale factor) sits within an ulp of an integer)
 __device__ __forceinline__ bool track_distance_in_bounds(int scaled, float min_in, float max_in, const float* PO, float& dist, float& raw_max) {
   float maxDistance, minDistance;
   track_distance_bounds(scaled, min_in, max_in, minDistance, maxDistance, raw_max);
@@ -65,16 +47,6 @@ __device__ __forceinline__ bool track_distance_in_bounds(int scaled, float min_i
   dist = (float)sqrt(s);
   return !(dist < minDistance || dist > maxDistance);
 }
-// MapPoint::PredictScale (MapPoint.cpp:404-419): ceil(logf(ratio) / mfLogScaleFactor); the float log is taken as the rounded double log (glibc's
-// logf is within 0.82 ulp of it; the two can only part where the quotient sits within an ulp of an integer)
-__device__ __forceinline__ int track_predict_scale(float raw_max, float dist, float log_scale, int nlevels) {
-  const float ratio = raw_max / dist;
-  const float lg = (float)log((double)ratio);
-  int ns = (int)ceilf(lg / log_scale);
-  if (ns < 0) ns = 0; else if (ns >= nlevels) ns = nlevels - 1;
-  return ns;
-}
-
 // [host-emulation end: bounds helpers]
 extern "C" __global__ void __launch_bounds__(256) k_in_frustum(CmsFrustumArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

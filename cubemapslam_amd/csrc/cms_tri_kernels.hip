@@ -16,6 +16,7 @@
 // double dot products and float rotations.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "cms_project_helpers.h"
 
 #define CMS_TRI_MAXF 4096           /* features per key frame the workgroup can hold in LDS */
 
@@ -52,23 +53,12 @@ __device__ __forceinline__ int tri_face_in_cubemap(int F, float x, float y) {
   if (i >= 2 && i < 3 && j >= 1 && j < 2) return 2;
   return -1;
 }
-__device__ __forceinline__ float tri_gemm3(float a0, float a1, float a2, float b0, float b1, float b2) {   // cv::gemm small path: float, left to right
-  float t = __fmul_rn(a0, b0);
-  t = __fadd_rn(t, __fmul_rn(a1, b1));
-  return __fadd_rn(t, __fmul_rn(a2, b2));
-}
-__device__ __forceinline__ double tri_ddot3(const float* a, const float* b) {
-  double s = __dmul_rn((double)a[0], (double)b[0]);
-  s = __dadd_rn(s, __dmul_rn((double)a[1], (double)b[1]));
-  return __dadd_rn(s, __dmul_rn((double)a[2], (double)b[2]));
-}
-__device__ __forceinline__ double tri_dnorm3(const float* a) { return sqrt(tri_ddot3(a, a)); }
-__device__ __forceinline__ void tri_mat3_vec(const float* A, const float* x, const float* c, float* out) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const float t = tri_gemm3(A[3 * r], A[3 * r + 1], A[3 * r + 2], x[0], x[1], x[2]);
-    out[r] = c ? (float)((double)t * 1.0 + (double)c[r] * 1.0) : t;
-  }
+// tri_gemm3 / tri_ddot3 / tri_dnorm3 / tri_mat3_vec: cms_project_helpers.h (one source for the kernels and the host build)
+// the job of entry i in a list of jobs' first entries: the last one whose first is <= i (empty jobs are skipped by the search)
+__device__ __forceinline__ int cms_job_of(const int* __restrict__ first, int njobs, int i) {
+  int lo = 0, hi = njobs;
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (first[mid] <= i) lo = mid; else hi = mid; }
+  return lo;
 }
 
 // CamModelGeneral::GetVectorSigma(key, normalRig, 1.0f)
@@ -526,59 +516,66 @@ extern "C" __global__ void __launch_bounds__(256) k_fuse_project(CmsFuseArgs a) 
     const float dist3D = (float)tri_dnorm3(PO);
     if (dist3D < minDistance || dist3D > maxDistance) break;
     if (tri_ddot3(PO, a.normal + 3 * m) < __dmul_rn(0.5, (double)dist3D)) break;
-    const float ratio = maxd / dist3D;
-    int ns = (int)ceilf((float)log((double)ratio) / a.log_scale);
-    if (ns < 0) ns = 0; else if (ns >= a.nlevels) ns = a.nlevels - 1;
-    lvl = ns; r = __fmul_rn(a.th, a.sf[ns]);
+    lvl = track_predict_scale(maxd, dist3D, a.log_scale, a.nlevels); r = __fmul_rn(a.th, a.sf[lvl]);
   } while (false);
   a.qx[i] = u; a.qy[i] = v; a.qr[i] = r; a.qmin[i] = -1; a.qmax[i] = -1; a.level[i] = lvl;
 }
 
-// ---- Fuse: gated Hamming minimum over the window (ORBMatcher.cpp:1186-1214); eight lanes per map point
-struct CmsFuseScanArgs {
-  int n; const float* qx; const float* qy; const int* level; const uint4* mp_desc; const int* cand_off; const int* cand_idx;
-  const CmsKeyPoint* kp; const uint4* t_desc; float inv_sigma2[16]; int* best_idx; int* best_dist;
-  int cap;                      // entries of cand_idx that exist (0: all of them): a scan enqueued before the host has seen the total never reads beyond them
-  const int* src;               // NULL, or per entry the map point whose descriptor it scans with (see CmsFuseArgs::src)
-  const int* row_slot; int maxf; // NULL, or per entry the store slot its candidates' rows belong to: the result is then the key-point index inside that key frame (row - slot x maxf)
+// ---- the window scan of the three Fuse-shaped matchers: eight lanes per entry over its candidates, octave in {level - 1, level}, Hamming distance,
+// key = dist << 20 | position, so the first minimum in list order wins; accepted when dist <= LIMIT (no surviving candidate: bestDist stays
+// INT_MAX).  ONE body, three instantiations:
+//   k_fuse_scan    Fuse(pKF, vpMapPoints, th) (ORBMatcher.cpp:1186-1214): the chi-square reprojection gate, TH_LOW, index and distance
+//   k_sim3s_scan   SearchBySim3 (:1444-1470, :1525-1551): no gate, TH_HIGH, the index alone
+//   k_sim3p_scan   Fuse(pKF, Scw, ...) (:1323-1342): no gate, TH_LOW, index and distance
+struct CmsWindowScanArgs {
+  int n; const float* qx; const float* qy;      // entries; their projections (read by the gate only)
+  const int* level; const uint4* mp_desc;
+  const int* src;                               // NULL, or per entry the map-point record whose descriptor it scans with (see CmsFuseArgs::src)
+  const int* cand_off; const int* cand_idx;     // the window query's lists: rows of the key-point array
+  int cap;                                      // entries of cand_idx that exist: a scan enqueued before the host has seen the total never reads beyond them
+  const CmsKeyPoint* kp; const uint4* t_desc; float inv_sigma2[16];
+  const int* row_slot; int maxf;                // NULL, or per entry the store slot its candidates' rows belong to: the result is then the key-point index inside that key frame (row - slot x maxf)
+  int* best_idx; int* best_dist;                // per entry: key point or -1, its distance or 256 (best_dist: instantiations that store it)
 };
-extern "C" __global__ void __launch_bounds__(256) k_fuse_scan(CmsFuseScanArgs a) {
-  const int n = a.n;
-  const float* qx = a.qx; const float* qy = a.qy; const int* level = a.level; const uint4* mp_desc = a.mp_desc;
-  const int* cand_off = a.cand_off; const int* cand_idx = a.cand_idx; const CmsKeyPoint* kp = a.kp; const uint4* t_desc = a.t_desc;
-  int* best_idx = a.best_idx; int* best_dist = a.best_dist;
+template <bool CHI2_GATE, int LIMIT, bool STORE_DIST>
+__device__ __forceinline__ void cms_window_scan(const CmsWindowScanArgs& a) {
   const int gl = threadIdx.x & 7;
   const int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 3;
-  const bool live = i < n;
+  const bool live = i < a.n;
   const int ii = live ? i : 0;
-  const int c0 = live ? cand_off[ii] : 0, c1 = live ? (a.cap > 0 ? min(cand_off[ii + 1], a.cap) : cand_off[ii + 1]) : 0;
-  const int lvl = level[ii];
-  const float u = qx[ii], v = qy[ii];
+  const int c0 = live ? min(a.cand_off[ii], a.cap) : 0, c1 = live ? min(a.cand_off[ii + 1], a.cap) : 0;
+  const int lvl = a.level[ii];
+  const float u = CHI2_GATE ? a.qx[ii] : 0.0f, v = CHI2_GATE ? a.qy[ii] : 0.0f;
   uint32_t key = 0xFFFFFFFFu;                        // dist << 20 | position: the first minimum in list order wins
   if (c1 > c0) {
     const size_t mi = a.src ? (size_t)a.src[ii] : (size_t)ii;
-    const uint4 d0 = mp_desc[2 * mi], d1 = mp_desc[2 * mi + 1];
+    const uint4 d0 = a.mp_desc[2 * mi], d1 = a.mp_desc[2 * mi + 1];
     for (int c = c0 + gl; c < c1; c += 8) {
-      const size_t row = (size_t)cand_idx[c];
-      const CmsKeyPoint k = kp[row];
-      if (k.octave < lvl - 1 || k.octave > lvl) continue;
-      const float ex = __fsub_rn(u, k.x), ey = __fsub_rn(v, k.y);
-      const float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-      if ((double)__fmul_rn(e2, a.inv_sigma2[k.octave & 15]) > 5.99) continue;
-      const uint32_t d = (uint32_t)tri_hamming256(d0, d1, t_desc[2 * row], t_desc[2 * row + 1]);
-      const uint32_t kk = (d << 20) | (uint32_t)(c - c0);
-      key = min(key, kk);
+      const size_t row = (size_t)a.cand_idx[c];
+      const CmsKeyPoint k = a.kp[row];
+      const int oct = k.octave;
+      if (oct < lvl - 1 || oct > lvl) continue;
+      if (CHI2_GATE) {
+        const float ex = __fsub_rn(u, k.x), ey = __fsub_rn(v, k.y);
+        const float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+        if ((double)__fmul_rn(e2, a.inv_sigma2[oct & 15]) > 5.99) continue;
+      }
+      const uint32_t d = (uint32_t)tri_hamming256(d0, d1, a.t_desc[2 * row], a.t_desc[2 * row + 1]);
+      key = min(key, (d << 20) | (uint32_t)(c - c0));
     }
   }
 #pragma unroll
   for (int o = 1; o < 8; o <<= 1) key = min(key, (uint32_t)__shfl_xor((int)key, o, 8));
   if (live && gl == 0) {
     const int d = key == 0xFFFFFFFFu ? 256 : (int)(key >> 20);
-    const bool hit = d <= 50;                        // TH_LOW
-    best_idx[i] = hit ? cand_idx[c0 + (int)(key & 0xFFFFFu)] - (a.row_slot ? a.row_slot[i] * a.maxf : 0) : -1;
-    best_dist[i] = hit ? d : 256;
+    const bool hit = d <= LIMIT;
+    a.best_idx[i] = hit ? a.cand_idx[c0 + (int)(key & 0xFFFFFu)] - (a.row_slot ? a.row_slot[i] * a.maxf : 0) : -1;
+    if (STORE_DIST) a.best_dist[i] = hit ? d : 256;
   }
 }
+extern "C" __global__ void __launch_bounds__(256) k_fuse_scan(CmsWindowScanArgs a) { cms_window_scan<true, 50, true>(a); }       // TH_LOW
+extern "C" __global__ void __launch_bounds__(256) k_sim3s_scan(CmsWindowScanArgs a) { cms_window_scan<false, 100, false>(a); }   // TH_HIGH
+extern "C" __global__ void __launch_bounds__(256) k_sim3p_scan(CmsWindowScanArgs a) { cms_window_scan<false, 50, true>(a); }     // TH_LOW
 
 // ---- MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cpp:243-308), one wavefront per map point.  Lane i owns observation i:
 // the median of its row of the distance matrix is found by bisection on the value (distances are integers in [0, 256]; the smallest v

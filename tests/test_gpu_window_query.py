@@ -217,3 +217,36 @@ def test_store_fuse_with_small_and_large_windows():
     for j in range(3):
         assert np.array_equal(got_s[j][0], want[j][0]) and np.array_equal(got_s[j][1], want[j][1]), ("sets", j)
     store.close(); ctx.close()
+
+
+def test_store_fuse_limit_and_reprojection_gate_by_hand():
+    """cms_kfstore_fuse_search_sets on a scene small enough to state the answer: what separates Fuse's instantiation of the window scan from
+    its two Sim3 siblings -- TH_LOW = 50 (not 100) and the 5.99 chi-square gate on the reprojection error (the siblings have none).
+    Identity pose, F = 150 (f = 75, front face at +150): the points project onto dyadic pixels exactly; max_dist = dist3D puts every
+    point on level 0 (or 1 at worst: octave 0 passes either way), radius th >= 8 px around the projection.
+      point 0 -> (225, 225);       key point 0 there,         Hamming 50           -> key point 0, distance 50
+      point 1 -> (243.75, 225);    key point 1 there,         Hamming 51           -> -1, 256
+      point 2 -> (206.25, 243.75); key point 2 at (+5, +1),   Hamming 10, e2 = 26  -> -1, 256   (26 / sigma2[0] = 26 > 5.99)"""
+    F = 150
+    camd = synth.camera("lafida", F)
+    ctx = api.Context(camd, nfeatures=2000, max_batch=1)
+    store = api.KeyframeStore(ctx, max_keyframes=2, max_features=2048, max_nodes=16)
+    pos = np.array([[0.0, 0.0, 2.0], [0.5, 0.0, 2.0], [-0.5, 0.5, 2.0]], np.float32)
+    kx = np.array([225.0, 243.75, 206.25 + 5.0], np.float32)
+    ky = np.array([225.0, 225.0, 243.75 + 1.0], np.float32)
+    bits = lambda k: np.packbits(np.arange(256) < k).astype(np.uint8)
+    kd = np.stack([bits(50), bits(51), bits(10)])
+    dist = np.sqrt((pos.astype(np.float64) ** 2).sum(1)).astype(np.float32)
+    pose15 = np.concatenate([np.eye(3, dtype=np.float32).ravel(), np.zeros(6, np.float32)])
+    kf = dict(x=kx, y=ky, octave=np.zeros(3, np.int32), angle=np.zeros(3, np.float32), desc=kd, mp=np.full(3, -1, np.int32), R=pose15[:9], t=pose15[9:12],
+              Ow=pose15[12:], node_id=np.zeros(0, np.int32), node_off=np.zeros(1, np.int32), node_feat=np.zeros(0, np.int32), median_depth=1.0,
+              rays=np.zeros((3, 3), np.float32))
+    K, _keep = api.make_keyframe(kf)
+    store.put(1, K)
+    mset = dict(pos=pos, normal=(pos / dist[:, None]).astype(np.float32), min_dist=(np.float32(0.5) * dist).astype(np.float32), max_dist=dist,
+                desc=np.zeros((3, 32), np.uint8))
+    (best_idx, best_dist), = store.fuse_search_sets([mset], [(1, 0, np.zeros(3, np.uint8))], th=8.0)
+    print("best_idx", best_idx, "best_dist", best_dist)
+    assert best_idx.tolist() == [0, -1, -1]
+    assert best_dist.tolist() == [50, 256, 256]
+    store.close(); ctx.close()
