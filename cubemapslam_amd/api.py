@@ -1864,3 +1864,78 @@ class TwoViewInitializer(_Handle):
         arr = init_jobs(states)
         self.two_view(ctx, arr, frames=True)
         return init_results(arr, states)
+
+
+class EssGraphJob(C.Structure):
+    """cms_ess_graph_job (include/cubemapslam_hip.h)"""
+    _fields_ = [("N", C.c_int), ("Scw", C.c_void_p), ("Snc", C.c_void_p), ("fixed", C.c_int), ("E", C.c_int), ("edges", C.c_void_p), ("fix_scale", C.c_int),
+                ("iterations", C.c_int), ("lambda_init", C.c_double), ("S_out", C.c_void_p), ("Tiw_out", C.c_void_p), ("chi2_initial", C.c_double),
+                ("chi2_final", C.c_double), ("lambda_final", C.c_double), ("iterations_run", C.c_int), ("trials_run", C.c_int), ("flags", C.c_int)]
+
+
+def ess_graph_job_state(graph, fix_scale=None, iterations=20, lambda_init=1e-16):
+    """The arrays of one OptimizeEssentialGraph call as a dict an EssGraphJob points into: graph has Scw, Snc (N x 8: q(x y z w) | t | s), fixed, edges
+    (E x 3: v0, v1, kind) and optionally fix_scale.  The output arrays start from a pattern, so that an untouched record shows."""
+    Scw = np.ascontiguousarray(np.array(graph["Scw"], np.float64).reshape(-1, 8))
+    N = len(Scw)
+    edges = np.ascontiguousarray(np.array(graph["edges"], np.int32).reshape(-1, 3))
+    return dict(N=N, Scw=Scw, Snc=np.ascontiguousarray(np.array(graph["Snc"], np.float64).reshape(N, 8)), fixed=int(graph["fixed"]), E=len(edges), edges=edges,
+                fix_scale=int(graph.get("fix_scale", 0) if fix_scale is None else fix_scale), iterations=int(iterations), lambda_init=float(lambda_init),
+                S_out=np.full((N, 8), 7.0, np.float64), Tiw_out=np.full((N, 12), 7.0, np.float32))
+
+
+def ess_graph_jobs(states):
+    """(EssGraphJob * n) over ess_graph_job_state() dicts; the dicts own the memory.  The scalar outputs start from -7."""
+    arr = (EssGraphJob * max(len(states), 1))()
+    for q, s in zip(arr, states):
+        q.N = s["N"]; q.fixed = s["fixed"]; q.E = s["E"]; q.fix_scale = s["fix_scale"]; q.iterations = s["iterations"]; q.lambda_init = s["lambda_init"]
+        for k in ("Scw", "Snc", "edges", "S_out", "Tiw_out"):
+            setattr(q, k, _p(s[k]) if s[k] is not None and (k != "edges" or s["E"] > 0) else None)
+        q.chi2_initial = -7.0; q.chi2_final = -7.0; q.lambda_final = -7.0; q.iterations_run = -7; q.trials_run = -7; q.flags = -7
+    return arr
+
+
+def ess_graph_results(arr, states):
+    """What a call left in the job records, one dict per job (arrays copied)"""
+    out = []
+    for q, s in zip(arr, states):
+        out.append(dict(S=s["S_out"].copy(), Tiw=s["Tiw_out"].copy(), chi2_initial=np.array([q.chi2_initial]), chi2_final=np.array([q.chi2_final]),
+                        lambda_final=np.array([q.lambda_final]), iterations_run=q.iterations_run, trials_run=q.trials_run, flags=q.flags))
+    return out
+
+
+ess_graph_first_difference = pnp_first_difference      # result dicts compared bit for bit: None, or (job, key, wanted, got)
+
+
+class EssentialGraphOptimizer(_Handle):
+    """Optimizer::OptimizeEssentialGraph for many graphs in one launch (cms_ess_graph_*).  jobs: an (EssGraphJob * n) array, e.g. from ess_graph_jobs()."""
+    _entries = ("cms_ess_graph_create", "cms_ess_graph_destroy")
+
+    def __init__(self, max_jobs, max_vertices_total, max_edges_total, max_envelope_blocks_total, device=0):
+        L = lib()
+        L.cms_ess_graph_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.cms_ess_graph_destroy.argtypes = [C.c_void_p]
+        L.cms_essential_graph_optimize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        self._create(device, max_jobs, max_vertices_total, max_edges_total, max_envelope_blocks_total)
+
+    def optimize(self, ctx, jobs, njobs=None):
+        _chk(lib().cms_essential_graph_optimize(self.h, ctx.h, len(jobs) if njobs is None else njobs, jobs), "cms_essential_graph_optimize")
+        return jobs
+
+    def run(self, ctx, states):
+        """One call over ess_graph_job_state() dicts -> one result dict per job"""
+        arr = ess_graph_jobs(states)
+        self.optimize(ctx, arr, len(states))
+        return ess_graph_results(arr, states)
+
+
+def sim3_correct_points(ctx, pos, ref, S_old, S_new):
+    """cms_sim3_correct_points: pos (n x 3 float32), ref (n, < 0 = copied), S_old / S_new (K x 8) -> corrected positions (n x 3 float32)"""
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    ref = np.ascontiguousarray(ref, np.int32)
+    S_old = np.ascontiguousarray(S_old, np.float64).reshape(-1, 8); S_new = np.ascontiguousarray(S_new, np.float64).reshape(-1, 8)
+    out = np.full((max(len(pos), 1), 3), 7.0, np.float32)
+    f = lib().cms_sim3_correct_points
+    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    _chk(f(ctx.h, len(pos), _p(pos), _p(ref), len(S_old), _p(S_old), _p(S_new), _p(out)), "cms_sim3_correct_points")
+    return out[:len(pos)]

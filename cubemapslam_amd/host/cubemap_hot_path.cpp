@@ -12,6 +12,8 @@
 #include <map>
 #include "../csrc/cms_vocab_core.h"
 #include "../csrc/cms_kfdb_core.h"
+#include "../csrc/cms_ess_graph_core.h"      // CmsS3 and Sim3(R, t, s) for vScw
+#include "../csrc/cms_ess_graph_job_check.h" // the envelope count for the handle
 #include "../csrc/cms_sim3_core.h"      // the gemm rule (cms_sim3_row) and TransformRaysToCubemap for the constructor's filter
 
 namespace CubemapSLAM {
@@ -1175,6 +1177,142 @@ int Optimizer::OptimizeSim3(const Sim3OptKeyFrameView& pKF1, const Sim3OptKeyFra
     if (!keep[(size_t)k]) vpMatches1[g.vnIndexEdge[(size_t)k]] = -1;      // vpMatches1[idx] = NULL (:1046, :1080)
   std::memcpy(g2oS12.q, q.q12, sizeof(g2oS12.q)); std::memcpy(g2oS12.t, q.t12_out, sizeof(g2oS12.t)); g2oS12.s = q.s12_out;
   return q.n_inliers;
+}
+
+// ------------------------------------------------------------------------------------------------ Optimizer::OptimizeEssentialGraph (src/Optimizer.cpp:623-886)
+extern "C" int hm_essential_graph_optimize_host(int njobs, cms_ess_graph_job* jobs);      // ess_graph_host.cpp: the host build of csrc/cms_ess_graph_core.h
+extern "C" int hm_sim3_correct_points_host(int n, const float* pos_in, const int* ref, int K, const double* S_old, const double* S_new, float* pos_out);
+extern "C" const char* hm_ess_graph_last_reason();
+
+EssGraph Optimizer::CollectEssentialGraph(const EssentialGraphMap& pMap, int pLoopKF, int pCurKF, const KeyFrameAndPose& NonCorrectedSim3,
+                                          const KeyFrameAndPose& CorrectedSim3, const std::map<int, std::set<int>>& LoopConnections) {
+  const std::vector<EssGraphKeyFrameView>& vpKFs = pMap.mvpKeyFrames;
+  const int nKF = (int)vpKFs.size();
+  const int minFeat = 100;
+  EssGraph g;
+  // :650-686: the vertices.  g2o indexes them by mnId; here they are compacted in mnId order, bad key frames left out
+  for (int i = 0; i < nKF; i++)
+    if (!vpKFs[(size_t)i].mbBad) g.vertexKF.push_back(i);
+  std::sort(g.vertexKF.begin(), g.vertexKF.end(), [&](int a, int b) { return vpKFs[(size_t)a].mnId < vpKFs[(size_t)b].mnId; });
+  std::vector<int> vertexOf((size_t)nKF, -1);
+  for (size_t v = 0; v < g.vertexKF.size(); ++v) vertexOf[(size_t)g.vertexKF[v]] = (int)v;
+  auto put = [](std::vector<double>& dst, const Sim3Pose& S) { dst.insert(dst.end(), S.q, S.q + 4); dst.insert(dst.end(), S.t, S.t + 3); dst.push_back(S.s); };
+  for (int kf : g.vertexKF) {
+    const EssGraphKeyFrameView& pKF = vpKFs[(size_t)kf];
+    Sim3Pose Siw;
+    KeyFrameAndPose::const_iterator it = CorrectedSim3.find(kf);
+    if (it != CorrectedSim3.end()) {
+      Siw = it->second;
+    } else {      // g2o::Sim3 Siw(Rcw, tcw, 1.0) of the float pose widened (Converter::toMatrix3d / toVector3d)
+      double R[9], t[3];
+      for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) R[3 * r + c] = (double)pKF.Tcw[4 * r + c]; t[r] = (double)pKF.Tcw[4 * r + 3]; }
+      CmsS3 S;
+      cms_s3o_from_Rts(R, t, 1.0, &S);
+      std::memcpy(Siw.q, S.q, sizeof(Siw.q)); std::memcpy(Siw.t, S.t, sizeof(Siw.t)); Siw.s = S.s;
+    }
+    put(g.Scw, Siw);
+    KeyFrameAndPose::const_iterator itn = NonCorrectedSim3.find(kf);      // what :737-741, :755-760, :776-781 and :805-810 pick per edge end
+    put(g.Snc, itn != NonCorrectedSim3.end() ? itn->second : Siw);
+  }
+  g.fixed = pLoopKF >= 0 && pLoopKF < nKF ? vertexOf[(size_t)pLoopKF] : -1;
+  auto weight = [&](const EssGraphKeyFrameView& k, int other) {      // KeyFrame::GetWeight
+    for (size_t c = 0; c < k.mvpOrderedConnectedKeyFrames.size(); ++c)
+      if (k.mvpOrderedConnectedKeyFrames[c] == other) return k.mvOrderedWeights[c];
+    return 0;
+  };
+  auto add = [&](int kfi, int kfj, int kind) {
+    if (kfj < 0 || kfj >= nKF || vertexOf[(size_t)kfi] < 0 || vertexOf[(size_t)kfj] < 0) return false;
+    g.edges.push_back(vertexOf[(size_t)kfi]); g.edges.push_back(vertexOf[(size_t)kfj]); g.edges.push_back(kind);
+    return true;
+  };
+  std::set<std::pair<long unsigned int, long unsigned int>> sInsertedEdges;
+  // :693-722: loop-connection edges, measured from vScw
+  for (std::map<int, std::set<int>>::const_iterator mit = LoopConnections.begin(); mit != LoopConnections.end(); ++mit) {
+    if (mit->first < 0 || mit->first >= nKF) continue;
+    const EssGraphKeyFrameView& pKF = vpKFs[(size_t)mit->first];
+    const long unsigned int nIDi = pKF.mnId;
+    for (int other : mit->second) {
+      if (other < 0 || other >= nKF) continue;
+      const long unsigned int nIDj = vpKFs[(size_t)other].mnId;
+      if ((nIDi != vpKFs[(size_t)pCurKF].mnId || nIDj != vpKFs[(size_t)pLoopKF].mnId) && weight(pKF, other) < minFeat) continue;
+      if (add(mit->first, other, 0)) sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+    }
+  }
+  // :724-825: normal edges, measured from NonCorrectedSim3 where present
+  for (int i = 0; i < nKF; i++) {
+    const EssGraphKeyFrameView& pKF = vpKFs[(size_t)i];
+    if (pKF.mbBad) continue;
+    const int pParentKF = pKF.mpParent;
+    if (pParentKF >= 0) add(i, pParentKF, 1);                                             // spanning tree edge
+    for (int pLKF : pKF.mspLoopEdges)                                                     // loop edges
+      if (pLKF >= 0 && pLKF < nKF && vpKFs[(size_t)pLKF].mnId < pKF.mnId) add(i, pLKF, 1);
+    for (size_t c = 0; c < pKF.mvpOrderedConnectedKeyFrames.size(); ++c) {                 // covisibility graph edges: GetCovisiblesByWeight(minFeat)
+      if (pKF.mvOrderedWeights[c] < minFeat) break;
+      const int pKFn = pKF.mvpOrderedConnectedKeyFrames[c];
+      if (pKFn < 0 || pKFn >= nKF || pKFn == pParentKF || pKF.mspChildrens.count(pKFn) || pKF.mspLoopEdges.count(pKFn)) continue;
+      const EssGraphKeyFrameView& n = vpKFs[(size_t)pKFn];
+      if (n.mbBad || !(n.mnId < pKF.mnId)) continue;
+      if (sInsertedEdges.count(std::make_pair(std::min(pKF.mnId, n.mnId), std::max(pKF.mnId, n.mnId)))) continue;
+      add(i, pKFn, 1);
+    }
+  }
+  return g;
+}
+
+void Optimizer::OptimizeEssentialGraph(EssentialGraphMap& pMap, int pLoopKF, int pCurKF, const KeyFrameAndPose& NonCorrectedSim3, const KeyFrameAndPose& CorrectedSim3,
+                                       const std::map<int, std::set<int>>& LoopConnections, const bool& bFixScale, Engine engine) {
+  EssGraph g = CollectEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections);
+  const int N = (int)g.vertexKF.size(), E = (int)g.edges.size() / 3;
+  if (N == 0 || g.fixed < 0) throw std::runtime_error("Optimizer::OptimizeEssentialGraph: pLoopKF has no vertex");
+  std::vector<double> S_out(8 * (size_t)N);
+  std::vector<float> Tiw(12 * (size_t)N);
+  g.edges.push_back(0);      // (never empty: data() stays valid)
+  cms_ess_graph_job q = {};
+  q.N = N; q.Scw = g.Scw.data(); q.Snc = g.Snc.data(); q.fixed = g.fixed; q.E = E; q.edges = g.edges.data(); q.fix_scale = bFixScale ? 1 : 0;
+  q.iterations = 20; q.lambda_init = 1e-16; q.S_out = S_out.data(); q.Tiw_out = Tiw.data();
+  // :854-885: the reference key frame of every map point, as a vertex
+  std::vector<int> vertexOfId;
+  for (int v = 0; v < N; ++v) {
+    const size_t id = (size_t)pMap.mvpKeyFrames[(size_t)g.vertexKF[(size_t)v]].mnId;
+    if (vertexOfId.size() <= id) vertexOfId.resize(id + 1, -1);
+    vertexOfId[id] = v;
+  }
+  const size_t nMP = pMap.mvpMapPoints.size();
+  std::vector<float> pos(3 * nMP + 3), pos_out(3 * nMP + 3);
+  std::vector<int> ref(nMP + 1, -1);
+  const long unsigned int curId = pMap.mvpKeyFrames[(size_t)pCurKF].mnId;
+  for (size_t i = 0; i < nMP; ++i) {
+    const EssGraphMapPointView& pMP = pMap.mvpMapPoints[i];
+    std::memcpy(&pos[3 * i], pMP.mWorldPos, 12);
+    if (pMP.mbBad) continue;
+    size_t nIDr;
+    if (pMP.mnCorrectedByKF == curId) nIDr = (size_t)pMP.mnCorrectedReference;
+    else if (pMP.mpRefKF >= 0) nIDr = (size_t)pMap.mvpKeyFrames[(size_t)pMP.mpRefKF].mnId;
+    else continue;
+    ref[i] = nIDr < vertexOfId.size() ? vertexOfId[nIDr] : -1;
+  }
+  if (engine == HOST_CORE) {
+    if (hm_essential_graph_optimize_host(1, &q)) throw std::runtime_error(std::string("Optimizer::OptimizeEssentialGraph: the job was refused: ") + hm_ess_graph_last_reason());
+    if (hm_sim3_correct_points_host((int)nMP, pos.data(), ref.data(), N, g.Scw.data(), S_out.data(), pos_out.data()))
+      throw std::runtime_error(std::string("Optimizer::OptimizeEssentialGraph: the points were refused: ") + hm_ess_graph_last_reason());
+  } else {
+    cms_ctx* ctx = SharedContext(g_ctx_orb.nfeatures > 0 ? g_ctx_orb.nfeatures : 1000, g_ctx_orb.nfeatures > 0 ? g_ctx_orb.scale_factor : 1.2f,
+                                 g_ctx_orb.nfeatures > 0 ? g_ctx_orb.nlevels : 8, g_ctx_orb.nfeatures > 0 ? g_ctx_orb.ini_th_fast : 20,
+                                 g_ctx_orb.nfeatures > 0 ? g_ctx_orb.min_th_fast : 7);
+    std::vector<int> first;
+    const long long blocks = cms_eg_envelope(N, g.fixed, E, g.edges.data(), first);
+    if (blocks > 0x7fffffffLL) throw std::runtime_error("Optimizer::OptimizeEssentialGraph: the envelope is too large");
+    cms_ess_graph* h = nullptr;
+    if (cms_ess_graph_create(&h, 0, 1, N, std::max(E, 1), (int)std::max(blocks, 1LL))) throw std::runtime_error(std::string("cms_ess_graph_create: ") + cms_last_error());
+    const int rc = cms_essential_graph_optimize(h, ctx, 1, &q);
+    cms_ess_graph_destroy(h);
+    if (rc) throw std::runtime_error(std::string("cms_essential_graph_optimize: ") + cms_last_error());
+    if (cms_sim3_correct_points(ctx, (int)nMP, pos.data(), ref.data(), N, g.Scw.data(), S_out.data(), pos_out.data()))
+      throw std::runtime_error(std::string("cms_sim3_correct_points: ") + cms_last_error());
+  }
+  for (int v = 0; v < N; ++v) std::memcpy(pMap.mvpKeyFrames[(size_t)g.vertexKF[(size_t)v]].Tcw, &Tiw[12 * (size_t)v], 48);      // pKFi->SetPose(Tiw)
+  for (size_t i = 0; i < nMP; ++i)
+    if (ref[i] >= 0) std::memcpy(pMap.mvpMapPoints[i].mWorldPos, &pos_out[3 * i], 12);                                          // pMP->SetWorldPos
 }
 
 // ------------------------------------------------------------------------------------------------ Initializer (src/Initializer.cpp)

@@ -19,6 +19,7 @@
 #ifndef CMS_CUBEMAP_HOT_PATH_H
 #define CMS_CUBEMAP_HOT_PATH_H
 #include <functional>
+#include <map>
 #include <string>
 #include <set>
 #include <vector>
@@ -451,9 +452,52 @@ struct Sim3OptGraph {
   std::vector<size_t> vnIndexEdge;
 };
 
+// What Optimizer::OptimizeEssentialGraph (src/Optimizer.cpp:623-886) reads and writes of the map.  Key frames and map points are named by their index
+// in the map's vectors (the order of GetAllKeyFrames / GetAllMapPoints); -1 = none.  The reference's containers are ordered by pointer value, which
+// is the allocator's business; the mirror's LoopConnections, loop edges and pose maps iterate in ascending index -- the order of addEdge, and with it
+// the order of the sums, is the caller's to choose there too.
+struct EssGraphKeyFrameView {
+  long unsigned int mnId = 0;
+  bool mbBad = false;
+  float Tcw[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};      // [R | t] row major; SetPose writes it (:833-852)
+  int mpParent = -1;
+  std::set<int> mspChildrens, mspLoopEdges;
+  std::vector<int> mvpOrderedConnectedKeyFrames, mvOrderedWeights;      // covisibles by descending weight (GetCovisiblesByWeight, GetWeight)
+};
+struct EssGraphMapPointView {
+  bool mbBad = false;
+  float mWorldPos[3] = {0, 0, 0};                                  // SetWorldPos writes it (:854-885)
+  int mpRefKF = -1;
+  long unsigned int mnCorrectedByKF = 0, mnCorrectedReference = 0;
+};
+struct EssentialGraphMap {
+  std::vector<EssGraphKeyFrameView> mvpKeyFrames;
+  std::vector<EssGraphMapPointView> mvpMapPoints;
+};
+struct Sim3Pose { double q[4] = {0, 0, 0, 1}, t[3] = {0, 0, 0}, s = 1; };      // g2o::Sim3: q (x y z w) | t | s
+typedef std::map<int, Sim3Pose> KeyFrameAndPose;                                 // LoopClosing::KeyFrameAndPose by key-frame index
+// The graph of :650-825 as the arrays of one cms_ess_graph_job: vertex v is key frame vertexKF[v] (the key frames that are not bad, in mnId order)
+struct EssGraph {
+  std::vector<int> vertexKF, edges;      // edges: v0, v1, kind
+  std::vector<double> Scw, Snc;          // 8 per vertex
+  int fixed = -1;
+};
+
 class Optimizer {
  public:
   enum Engine { DEVICE = 0, HOST_CORE = 1 };
+  // Optimizer.cpp:623-886.  CollectEssentialGraph does the pointer work of :650-825: one vertex per key frame that is not bad, in mnId order, with vScw
+  // = the CorrectedSim3 value or Sim3(Rcw, tcw, 1); the loop-connection edges under the minFeat = 100 rule with the (pCurKF, pLoopKF) exemption and
+  // sInsertedEdges; per key frame the spanning-tree edge, the loop edges to lower mnId and the covisibility edges of weight >= minFeat that are neither
+  // parent, child nor loop edge, not bad, of lower mnId and not in sInsertedEdges, measured from NonCorrectedSim3 where present.  An edge to a key
+  // frame without a vertex (bad) is left out, where the reference would hand g2o a null vertex.  The optimisation is one
+  // cms_essential_graph_optimize call on the shared context's device (engine DEVICE, the default) or the host build of the same core (HOST_CORE: the
+  // definition of record, no GPU needed; an explicit choice, never a fall-back).  Poses (:833-852) and map points (:854-885, through
+  // cms_sim3_correct_points) are written back; UpdateNormalAndDepth stays the caller's.
+  static void OptimizeEssentialGraph(EssentialGraphMap& pMap, int pLoopKF, int pCurKF, const KeyFrameAndPose& NonCorrectedSim3, const KeyFrameAndPose& CorrectedSim3,
+                                     const std::map<int, std::set<int>>& LoopConnections, const bool& bFixScale, Engine engine = DEVICE);
+  static EssGraph CollectEssentialGraph(const EssentialGraphMap& pMap, int pLoopKF, int pCurKF, const KeyFrameAndPose& NonCorrectedSim3,
+                                        const KeyFrameAndPose& CorrectedSim3, const std::map<int, std::set<int>>& LoopConnections);
   // Optimizer.cpp:888-1091.  vpMatches1[i] = index into pKF2.mvMapPoints of the map point matched to key point i of pKF1, -1 = NULL; entries the
   // reference nulls (:1046, :1080) become -1.  The pointer work of :941-978 is CollectSim3Graph: !pMP1 || !pMP2, isBad, GetIndexInKeyFrame(pKF2) < 0,
   // P3D1c / P3D2c = Rcw Xw + tcw by the gemm rule of Sim3Solver's constructor, mvKeys[i].pt / mvKeys[i2].pt, mvInvLevelSigma2[octave].  The rest is

@@ -970,3 +970,50 @@ extern "C" int hm_kfdb_mirror(void* voc, int engine, int n_kf, int n_feat, const
     for (size_t i = 0; i < l.size(); ++i) loop[i] = index_of(l[i]);
     return 0;)
 }
+
+// Optimizer::OptimizeEssentialGraph of cubemap_hot_path.h over flat arrays.  Key frames: mnId, bad, Tcw (12 floats, in/out), parent, and three lists
+// in CSR form (children, loop edges, covisibles with weights by descending weight).  Map points: bad, pos (in/out), reference key frame,
+// mnCorrectedByKF, mnCorrectedReference.  The pose maps as (key frame, 8 doubles) rows, LoopConnections in CSR form.  Out: the graph
+// CollectEssentialGraph made (N, E, vertex_kf, edges, fixed) with capacities cap_v / cap_e
+extern "C" int hm_ess_graph_mirror(int engine, int nkf, const int* mnId, const uint8_t* bad, float* Tcw, const int* parent, const int* child_off, const int* child,
+                                   const int* loop_off, const int* loop, const int* cov_off, const int* cov, const int* cov_w, int nmp, const uint8_t* mp_bad, float* mp_pos,
+                                   const int* mp_ref, const int* mp_by, const int* mp_cref, int loopKF, int curKF, int n_nc, const int* nc_kf, const double* nc_S, int n_c,
+                                   const int* c_kf, const double* c_S, int n_lc, const int* lc_kf, const int* lc_off, const int* lc, int fix_scale, int cap_v, int cap_e,
+                                   int* N_out, int* E_out, int* vertex_kf, int* edges, int* fixed_out) {
+  HM_TRY(
+    EssentialGraphMap map;
+    map.mvpKeyFrames.resize((size_t)nkf);
+    for (int i = 0; i < nkf; ++i) {
+      EssGraphKeyFrameView& k = map.mvpKeyFrames[(size_t)i];
+      k.mnId = (long unsigned int)mnId[i]; k.mbBad = bad[i] != 0; k.mpParent = parent[i];
+      std::memcpy(k.Tcw, Tcw + 12 * (size_t)i, 48);
+      k.mspChildrens.insert(child + child_off[i], child + child_off[i + 1]);
+      k.mspLoopEdges.insert(loop + loop_off[i], loop + loop_off[i + 1]);
+      k.mvpOrderedConnectedKeyFrames.assign(cov + cov_off[i], cov + cov_off[i + 1]);
+      k.mvOrderedWeights.assign(cov_w + cov_off[i], cov_w + cov_off[i + 1]);
+    }
+    map.mvpMapPoints.resize((size_t)nmp);
+    for (int i = 0; i < nmp; ++i) {
+      EssGraphMapPointView& m = map.mvpMapPoints[(size_t)i];
+      m.mbBad = mp_bad[i] != 0; m.mpRefKF = mp_ref[i]; m.mnCorrectedByKF = (long unsigned int)mp_by[i]; m.mnCorrectedReference = (long unsigned int)mp_cref[i];
+      std::memcpy(m.mWorldPos, mp_pos + 3 * (size_t)i, 12);
+    }
+    auto poses = [](int n, const int* kf, const double* S) {
+      KeyFrameAndPose m;
+      for (int i = 0; i < n; ++i) { Sim3Pose p; std::memcpy(p.q, S + 8 * (size_t)i, 32); std::memcpy(p.t, S + 8 * (size_t)i + 4, 24); p.s = S[8 * (size_t)i + 7]; m[kf[i]] = p; }
+      return m;
+    };
+    const KeyFrameAndPose nc = poses(n_nc, nc_kf, nc_S), co = poses(n_c, c_kf, c_S);
+    std::map<int, std::set<int>> lcm;
+    for (int i = 0; i < n_lc; ++i) lcm[lc_kf[i]].insert(lc + lc_off[i], lc + lc_off[i + 1]);
+    const EssGraph g = Optimizer::CollectEssentialGraph(map, loopKF, curKF, nc, co, lcm);
+    const int N = (int)g.vertexKF.size(), E = (int)g.edges.size() / 3;
+    if (N > cap_v || E > cap_e) throw std::runtime_error("hm_ess_graph_mirror: the graph exceeds the caller's arrays");
+    *N_out = N; *E_out = E; *fixed_out = g.fixed;
+    std::memcpy(vertex_kf, g.vertexKF.data(), sizeof(int) * (size_t)N);
+    std::memcpy(edges, g.edges.data(), sizeof(int) * 3 * (size_t)E);
+    Optimizer::OptimizeEssentialGraph(map, loopKF, curKF, nc, co, lcm, fix_scale != 0, engine ? Optimizer::HOST_CORE : Optimizer::DEVICE);
+    for (int i = 0; i < nkf; ++i) std::memcpy(Tcw + 12 * (size_t)i, map.mvpKeyFrames[(size_t)i].Tcw, 48);
+    for (int i = 0; i < nmp; ++i) std::memcpy(mp_pos + 3 * (size_t)i, map.mvpMapPoints[(size_t)i].mWorldPos, 12);
+    return 0;)
+}

@@ -908,6 +908,50 @@ typedef struct {
 } cms_sim3_opt_job;
 int cms_sim3_optimize(cms_sim3_opt* p, cms_ctx* ctx /* F */, int njobs, cms_sim3_opt_job* jobs);
 
+/* ---- Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale)
+ * (src/Optimizer.cpp:623-886), the Sim3 pose graph LoopClosing::CorrectLoop runs once a loop is accepted and fused, and the per-point loop
+ * correctedSwr.map(Srw.map(P)) around it (:854-885, src/LoopClosing.cpp:470-500).  Every job of a call is one workgroup of ONE launch with the
+ * whole optimize(20) inside the kernel.  g2o is not in the tree and libm's log / acos / exp / sin / cos differ from the device's in ulps, so the
+ * definition of record is the project's own core, csrc/cms_ess_graph_core.h (DESIGN.md "OptimizeEssentialGraph"): one source, built for the host
+ * (libcubemapslam_host.so: hm_essential_graph_optimize_host) and for the device, which is held to the host build bit for bit.
+ *   The graph: N VertexSim3Expmap vertices with the estimates Scw (vScw: the CorrectedSim3 value where there is one, else Sim3(Rcw, tcw, 1)),
+ *   vertex `fixed` (pLoopKF) fixed; E EdgeSim3 edges (v0, v1, kind) in the reference's order of addEdge, information = I, no robust kernel.
+ *   The measurement of an edge is Sji = Sjw * Swi with i = v0, j = v1, from Scw for kind 0 (the loop-connection edges, :693-722) and from Snc
+ *   for kind 1 (spanning tree, loop and covisibility edges, :724-825; Snc = the NonCorrectedSim3 value where there is one, else the Scw entry).
+ *   The pointer work of :650-825 (vertex compaction, bad key frames, minFeat, sInsertedEdges) is the caller's.
+ *   The error is log(C * S_v0 * S_v1^-1) with Sim3::log as written (four branches, a 3 x 3 partial-pivot LU); EdgeSim3 has no linearizeOplus, so
+ *   both Jacobians are g2o's central differences with delta = 1e-9; under fix_scale their column 6 is exactly 0 and the scale rows of the system
+ *   are lambda alone.  Levenberg with setUserLambdaInit(lambda_init) (the reference: 1e-16) and optimize(iterations) (20).  The normal end is ten
+ *   rejected trials at the minimum (flags & 1).
+ *   The solve is a block LDL^T inside the row envelope of the unknowns in ascending vertex index, unpivoted -- the ONE stated difference from the
+ *   reference's SimplicialLDLT under an AMD ordering: the same factorisation in exact arithmetic, another rounding.  A zero or non-finite pivot
+ *   is a failed solve (flags & 8): the trial is rejected and lambda grows, as g2o does when its solver fails.
+ *   Out: S_out (N x 8, q(x y z w) | t | s; the fixed vertex gets its input back), Tiw_out (N x 12 floats, [R | t / s] row major, :833-852),
+ *   chi2_initial, chi2_final, lambda_final, iterations_run, trials_run, flags (1 ended on ten rejected trials, 2 on rho == 0, 4 on three
+ *   iterations without progress, 8 a failed solve).  iterations == 0 returns the input and chi2_initial; E == 0 with N == 1 returns the input.
+ *   Synchronous; one launch sequence per call on the handle's stream: one pinned block up, one launch, one block back.  ctx supplies the device;
+ *   nothing is enqueued on its stream.  Checked before anything is enqueued or written (CMS_ERR_ARG, the reason in cms_last_error, the records
+ *   untouched): a null array, N < 1, fixed out of range, an edge index out of range or v0 == v1, a kind outside {0, 1}, a non-finite entry or a
+ *   scale <= 0 in Scw / Snc, iterations < 0, lambda_init not positive and finite, a context on another device, more jobs / vertices / edges than
+ *   cms_ess_graph_create was given, a vertex with no path to `fixed` (stated difference: g2o would factor a singular matrix).  The jobs' envelopes
+ *   exceeding max_envelope_blocks_total is CMS_ERR_OVERFLOW with the needed block count in the message, before any launch.  njobs == 0 is CMS_OK
+ *   with no launch.  One caller at a time per handle.
+ * cms_sim3_correct_points: pos_out[k] = S_new[ref[k]]^-1.map(S_old[ref[k]].map(pos_in[k])) in double, narrowed once; ref[k] < 0 copies the point.
+ * S_old / S_new are K x 8.  Synchronous on ctx's stream.  CMS_ERR_ARG: a null array with n > 0, n < 0, K < 0, ref[k] >= K. */
+typedef struct cms_ess_graph cms_ess_graph;
+int cms_ess_graph_create(cms_ess_graph** out, int device, int max_jobs, int max_vertices_total, int max_edges_total, int max_envelope_blocks_total);
+void cms_ess_graph_destroy(cms_ess_graph* p);
+typedef struct {
+  int N; const double* Scw; const double* Snc;    /* N x 8: q(x y z w) | t | s */
+  int fixed;                                      /* vertex index of pLoopKF */
+  int E; const int* edges;                        /* E x 3: v0, v1, kind (0 = measurement from Scw, 1 = from Snc) */
+  int fix_scale, iterations; double lambda_init;  /* 20, 1e-16 */
+  double* S_out; float* Tiw_out;                  /* N x 8, N x 12 */
+  double chi2_initial, chi2_final, lambda_final; int iterations_run, trials_run, flags;   /* out */
+} cms_ess_graph_job;
+int cms_essential_graph_optimize(cms_ess_graph* h, cms_ctx* ctx, int njobs, cms_ess_graph_job* jobs);
+int cms_sim3_correct_points(cms_ctx* ctx, int n, const float* pos_in, const int* ref, int K, const double* S_old, const double* S_new, float* pos_out);
+
 /* ---- Initializer (include/Initializer.h, src/Initializer.cpp), the two-view essential-matrix RANSAC of Tracking::MonocularInitialization
  * (src/Tracking.cpp:443), behind cms_search_for_initialization.  ComputeE21 takes the last row of a FULL_UV SVD of an 8 x 9 matrix, which OpenCV
  * completes from a basis nobody can pin (DESIGN.md "Initializer"), so the definition of record is the project's own core, csrc/cms_init_core.h: one

@@ -1391,4 +1391,185 @@ std::vector<double> LoopScore(cms_kfstore* store, KeyFrame* pKF, const std::vect
   return score;
 }
 
+// ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cpp:623-886) and the point loop of CorrectLoop (LoopClosing.cpp:470-500)
+EssentialGraph::EssentialGraph(int device_, int max_vertices_, int max_edges_) : h(NULL), device(device_), max_vertices(0), max_edges(0), max_blocks(0) {
+  Reserve(max_vertices_, max_edges_, 4LL * max_vertices_);
+}
+EssentialGraph::~EssentialGraph() { cms_ess_graph_destroy(h); }
+void EssentialGraph::Reserve(int vertices, int edges, long long blocks) {
+  if (h && vertices <= max_vertices && edges <= max_edges && blocks <= max_blocks) return;
+  if (blocks > 0x7fffffffLL) throw std::runtime_error("Hip::EssentialGraph: the envelope is too large");
+  cms_ess_graph_destroy(h);
+  h = NULL;
+  max_vertices = std::max(max_vertices, std::max(vertices, 1)); max_edges = std::max(max_edges, std::max(edges, 1)); max_blocks = std::max(max_blocks, (int)std::max(blocks, 1LL));
+  check(cms_ess_graph_create(&h, device, 1, max_vertices, max_edges, max_blocks), "cms_ess_graph_create");
+}
+
+void OptimizeEssentialGraph(EssentialGraph& eg, cms_ctx* ctx, Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndEstimate& NonCorrectedSim3,
+                            const KeyFrameAndEstimate& CorrectedSim3, const std::map<KeyFrame*, std::set<KeyFrame*> >& LoopConnections, bool bFixScale) {
+  const std::vector<KeyFrame*> vpKFs = pMap->GetAllKeyFrames();
+  const std::vector<MapPoint*> vpMPs = pMap->GetAllMapPoints();
+  const int minFeat = 100;
+  // :650-686: the vertices, compacted in mnId order, bad key frames left out
+  std::map<long unsigned int, KeyFrame*> byId;
+  for (size_t i = 0; i < vpKFs.size(); i++)
+    if (!vpKFs[i]->isBad()) byId[vpKFs[i]->mnId] = vpKFs[i];
+  std::map<KeyFrame*, int> vertexOf;
+  std::map<long unsigned int, int> vertexOfId;
+  std::vector<KeyFrame*> vertexKF;
+  std::vector<double> Scw, Snc;
+  for (std::map<long unsigned int, KeyFrame*>::const_iterator it = byId.begin(); it != byId.end(); ++it) {
+    KeyFrame* pKF = it->second;
+    Sim3Estimate Siw;
+    KeyFrameAndEstimate::const_iterator itc = CorrectedSim3.find(pKF);
+    if (itc != CorrectedSim3.end()) {
+      Siw = itc->second;
+    } else {      // g2o::Sim3 Siw(Rcw, tcw, 1.0)
+      const Eigen::Quaterniond q(Converter::toMatrix3d(pKF->GetRotation()));
+      const Eigen::Matrix<double, 3, 1> t = Converter::toVector3d(pKF->GetTranslation());
+      Siw.q[0] = q.x(); Siw.q[1] = q.y(); Siw.q[2] = q.z(); Siw.q[3] = q.w();
+      for (int i = 0; i < 3; ++i) Siw.t[i] = t[i];
+      Siw.s = 1.0;
+    }
+    KeyFrameAndEstimate::const_iterator itn = NonCorrectedSim3.find(pKF);
+    const Sim3Estimate& Snw = itn != NonCorrectedSim3.end() ? itn->second : Siw;
+    vertexOf[pKF] = (int)vertexKF.size(); vertexOfId[pKF->mnId] = (int)vertexKF.size();
+    vertexKF.push_back(pKF);
+    Scw.insert(Scw.end(), Siw.q, Siw.q + 4); Scw.insert(Scw.end(), Siw.t, Siw.t + 3); Scw.push_back(Siw.s);
+    Snc.insert(Snc.end(), Snw.q, Snw.q + 4); Snc.insert(Snc.end(), Snw.t, Snw.t + 3); Snc.push_back(Snw.s);
+  }
+  if (!vertexOf.count(pLoopKF)) throw std::runtime_error("Hip::OptimizeEssentialGraph: pLoopKF has no vertex");
+  std::vector<int> edges;
+  std::set<std::pair<long unsigned int, long unsigned int> > sInsertedEdges;
+  // :693-722: loop-connection edges, measured from vScw
+  for (std::map<KeyFrame*, std::set<KeyFrame*> >::const_iterator mit = LoopConnections.begin(), mend = LoopConnections.end(); mit != mend; mit++) {
+    KeyFrame* pKF = mit->first;
+    const long unsigned int nIDi = pKF->mnId;
+    const std::set<KeyFrame*>& spConnections = mit->second;
+    for (std::set<KeyFrame*>::const_iterator sit = spConnections.begin(), send = spConnections.end(); sit != send; sit++) {
+      const long unsigned int nIDj = (*sit)->mnId;
+      if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(*sit) < minFeat) continue;
+      if (!vertexOf.count(pKF) || !vertexOf.count(*sit)) continue;
+      edges.push_back(vertexOf[pKF]); edges.push_back(vertexOf[*sit]); edges.push_back(0);
+      sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+    }
+  }
+  // :724-825: normal edges, measured from NonCorrectedSim3 where present
+  for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {
+    KeyFrame* pKF = vpKFs[i];
+    if (!vertexOf.count(pKF)) continue;
+    const int vi = vertexOf[pKF];
+    KeyFrame* pParentKF = pKF->GetParent();
+    if (pParentKF && vertexOf.count(pParentKF)) { edges.push_back(vi); edges.push_back(vertexOf[pParentKF]); edges.push_back(1); }      // spanning tree edge
+    const std::set<KeyFrame*> sLoopEdges = pKF->GetLoopEdges();
+    for (std::set<KeyFrame*>::const_iterator sit = sLoopEdges.begin(), send = sLoopEdges.end(); sit != send; sit++) {
+      KeyFrame* pLKF = *sit;
+      if (pLKF->mnId < pKF->mnId && vertexOf.count(pLKF)) { edges.push_back(vi); edges.push_back(vertexOf[pLKF]); edges.push_back(1); }
+    }
+    const std::vector<KeyFrame*> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+    for (std::vector<KeyFrame*>::const_iterator vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); vit++) {
+      KeyFrame* pKFn = *vit;
+      if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
+        if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+          if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+          if (!vertexOf.count(pKFn)) continue;
+          edges.push_back(vi); edges.push_back(vertexOf[pKFn]); edges.push_back(1);
+        }
+      }
+    }
+  }
+  const int N = (int)vertexKF.size(), E = (int)edges.size() / 3;
+  // the envelope of the unknowns (the non-fixed vertices in ascending vertex index): rows from the lowest free neighbour to the diagonal
+  const int fixed = vertexOf[pLoopKF];
+  std::vector<int> first((size_t)std::max(N - 1, 0));
+  for (int f = 0; f < N - 1; ++f) first[(size_t)f] = f;
+  for (int e = 0; e < E; ++e) {
+    const int v0 = edges[3 * (size_t)e], v1 = edges[3 * (size_t)e + 1];
+    if (v0 == fixed || v1 == fixed) continue;
+    const int a = v0 - (v0 > fixed ? 1 : 0), b = v1 - (v1 > fixed ? 1 : 0);
+    first[(size_t)std::max(a, b)] = std::min(first[(size_t)std::max(a, b)], std::min(a, b));
+  }
+  long long blocks = 0;
+  for (int f = 0; f < N - 1; ++f) blocks += f - first[(size_t)f] + 1;
+  eg.Reserve(N, E, blocks);
+  std::vector<double> S_out(8 * (size_t)N);
+  std::vector<float> Tiw(12 * (size_t)N);
+  edges.push_back(0);
+  cms_ess_graph_job q;
+  std::memset(&q, 0, sizeof(q));
+  q.N = N; q.Scw = Scw.data(); q.Snc = Snc.data(); q.fixed = fixed; q.E = E; q.edges = edges.data(); q.fix_scale = bFixScale ? 1 : 0;
+  q.iterations = 20; q.lambda_init = 1e-16; q.S_out = S_out.data(); q.Tiw_out = Tiw.data();
+  check(cms_essential_graph_optimize(eg.h, ctx, 1, &q), "cms_essential_graph_optimize");
+  // :854-885: the map points through their reference key frames
+  std::vector<float> pos(3 * vpMPs.size() + 3), pos_out(3 * vpMPs.size() + 3);
+  std::vector<int> ref(vpMPs.size() + 1, -1);
+  for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {
+    MapPoint* pMP = vpMPs[i];
+    if (pMP->isBad()) continue;
+    const long unsigned int nIDr = pMP->mnCorrectedByKF == pCurKF->mnId ? pMP->mnCorrectedReference : pMP->GetReferenceKeyFrame()->mnId;
+    std::map<long unsigned int, int>::const_iterator it = vertexOfId.find(nIDr);
+    if (it == vertexOfId.end()) continue;
+    const cv::Mat P3Dw = pMP->GetWorldPos();
+    for (int c = 0; c < 3; ++c) pos[3 * i + c] = P3Dw.at<float>(c);
+    ref[i] = it->second;
+  }
+  check(cms_sim3_correct_points(ctx, (int)vpMPs.size(), pos.data(), ref.data(), N, Scw.data(), S_out.data(), pos_out.data()), "cms_sim3_correct_points");
+  std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+  for (int v = 0; v < N; ++v) {      // :833-852
+    cv::Mat T = cv::Mat::eye(4, 4, CV_32F);
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 4; ++c) T.at<float>(r, c) = Tiw[12 * (size_t)v + 4 * r + c];
+    vertexKF[(size_t)v]->SetPose(T);
+  }
+  for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {
+    if (ref[i] < 0) continue;
+    cv::Mat P(3, 1, CV_32F);
+    for (int c = 0; c < 3; ++c) P.at<float>(c) = pos_out[3 * i + c];
+    vpMPs[i]->SetWorldPos(P);
+    vpMPs[i]->UpdateNormalAndDepth();
+  }
+}
+
+void CorrectLoopPoints(cms_ctx* ctx, const KeyFrameAndEstimate& CorrectedSim3, const KeyFrameAndEstimate& NonCorrectedSim3, KeyFrame* pCurKF) {
+  std::vector<double> S_old, S_new;
+  std::vector<MapPoint*> pts;
+  std::vector<KeyFrame*> owner;
+  std::vector<float> pos;
+  std::vector<int> ref;
+  std::set<MapPoint*> taken;      // a point seen from two key frames is corrected by the first, as mnCorrectedByKF makes the reference do
+  int k = 0;
+  for (KeyFrameAndEstimate::const_iterator mit = CorrectedSim3.begin(), mend = CorrectedSim3.end(); mit != mend; mit++, k++) {
+    KeyFrame* pKFi = mit->first;
+    const Sim3Estimate& corrected = mit->second;
+    KeyFrameAndEstimate::const_iterator itn = NonCorrectedSim3.find(pKFi);
+    if (itn == NonCorrectedSim3.end()) throw std::runtime_error("Hip::CorrectLoopPoints: a corrected key frame without its non-corrected pose");
+    const Sim3Estimate& plain = itn->second;
+    S_new.insert(S_new.end(), corrected.q, corrected.q + 4); S_new.insert(S_new.end(), corrected.t, corrected.t + 3); S_new.push_back(corrected.s);
+    S_old.insert(S_old.end(), plain.q, plain.q + 4); S_old.insert(S_old.end(), plain.t, plain.t + 3); S_old.push_back(plain.s);
+    const std::vector<MapPoint*> vpMPsi = pKFi->GetMapPointMatches();
+    for (size_t iMP = 0, endMPi = vpMPsi.size(); iMP < endMPi; iMP++) {
+      MapPoint* pMPi = vpMPsi[iMP];
+      if (!pMPi) continue;
+      if (pMPi->isBad()) continue;
+      if (pMPi->mnCorrectedByKF == pCurKF->mnId || taken.count(pMPi)) continue;
+      taken.insert(pMPi);
+      const cv::Mat P3Dw = pMPi->GetWorldPos();
+      for (int c = 0; c < 3; ++c) pos.push_back(P3Dw.at<float>(c));
+      ref.push_back(k); pts.push_back(pMPi); owner.push_back(pKFi);
+    }
+  }
+  const int n = (int)pts.size();
+  std::vector<float> out(3 * (size_t)n + 3);
+  pos.push_back(0.0f); ref.push_back(-1);
+  check(cms_sim3_correct_points(ctx, n, pos.data(), ref.data(), k, S_old.data(), S_new.data(), out.data()), "cms_sim3_correct_points");
+  for (int i = 0; i < n; ++i) {
+    cv::Mat P(3, 1, CV_32F);
+    for (int c = 0; c < 3; ++c) P.at<float>(c) = out[3 * (size_t)i + c];
+    pts[(size_t)i]->SetWorldPos(P);
+    pts[(size_t)i]->mnCorrectedByKF = pCurKF->mnId;
+    pts[(size_t)i]->mnCorrectedReference = owner[(size_t)i]->mnId;
+    pts[(size_t)i]->UpdateNormalAndDepth();
+  }
+}
+
 }  // namespace Hip

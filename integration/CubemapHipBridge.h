@@ -3,6 +3,7 @@
 // Not built in this repository (syntax-checked against the reference's headers by tests/test_integration_syntax.py), see integration/README.md.  Each function is the new body of the reference function it names.
 #ifndef CUBEMAP_HIP_BRIDGE_H
 #define CUBEMAP_HIP_BRIDGE_H
+#include <map>
 #include <set>
 #include <vector>
 #include <opencv2/opencv.hpp>
@@ -254,5 +255,42 @@ void ClearDatabase(cms_kfstore* store);
 std::vector<KeyFrame*> DetectRelocalizationCandidates(cms_kfstore* store, cms_ctx* frameCtx, Frame& F);
 std::vector<KeyFrame*> DetectLoopCandidates(cms_kfstore* store, cms_ctx* frameCtx, KeyFrame* pKF, float minScore);
 std::vector<double> LoopScore(cms_kfstore* store, KeyFrame* pKF, const std::vector<KeyFrame*>& vpOthers);
+// ---- Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale) (src/Optimizer.cpp:623-886, call
+// site LoopClosing.cpp:561) and the point loop of CorrectLoop in front of it (LoopClosing.cpp:470-500), on the device: cms_essential_graph_optimize and
+// cms_sim3_correct_points (DESIGN.md "OptimizeEssentialGraph").  The pose maps are LoopClosing::KeyFrameAndPose with the estimates as Sim3Estimate
+// (ToEstimates converts: this header names no g2o type).  OptimizeEssentialGraph does the pointer work of :650-825 -- one vertex per key frame that is
+// not bad, in mnId order; the loop-connection edges under the minFeat = 100 rule with the (pCurKF, pLoopKF) exemption and sInsertedEdges; spanning-tree,
+// loop and covisibility edges -- and writes SetPose / SetWorldPos / UpdateNormalAndDepth back under mMutexMapUpdate as :833-885 do.  The containers the
+// reference orders by pointer value are walked as they are: the order of addEdge is the reference's own on the same process.
+typedef std::map<KeyFrame*, Sim3Estimate> KeyFrameAndEstimate;
+template <class KeyFrameAndPose>
+KeyFrameAndEstimate ToEstimates(const KeyFrameAndPose& m) {
+  KeyFrameAndEstimate out;
+  for (typename KeyFrameAndPose::const_iterator it = m.begin(); it != m.end(); ++it) {
+    Sim3Estimate e;
+    e.q[0] = it->second.rotation().x(); e.q[1] = it->second.rotation().y(); e.q[2] = it->second.rotation().z(); e.q[3] = it->second.rotation().w();
+    for (int i = 0; i < 3; ++i) e.t[i] = it->second.translation()[i];
+    e.s = it->second.scale();
+    out[it->first] = e;
+  }
+  return out;
+}
+// the handle with its capacities; the envelope's capacity follows the largest graph seen (the handle is made again when a graph needs more)
+struct EssentialGraph {
+  cms_ess_graph* h;
+  int device, max_vertices, max_edges, max_blocks;
+  EssentialGraph(int device_, int max_vertices_, int max_edges_);
+  ~EssentialGraph();
+  void Reserve(int vertices, int edges, long long blocks);
+ private:
+  EssentialGraph(const EssentialGraph&);
+  EssentialGraph& operator=(const EssentialGraph&);
+};
+void OptimizeEssentialGraph(EssentialGraph& eg, cms_ctx* ctx, Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndEstimate& NonCorrectedSim3,
+                            const KeyFrameAndEstimate& CorrectedSim3, const std::map<KeyFrame*, std::set<KeyFrame*> >& LoopConnections, bool bFixScale);
+// LoopClosing.cpp:470-500 for every key frame of CorrectedSim3 in one launch: map points that are not bad and not yet corrected by pCurKF go through
+// CorrectedSwi.map(Siw.map(P)) and get mnCorrectedByKF / mnCorrectedReference; the key frames' SetPose of :502-512 stays in CorrectLoop
+void CorrectLoopPoints(cms_ctx* ctx, const KeyFrameAndEstimate& CorrectedSim3, const KeyFrameAndEstimate& NonCorrectedSim3, KeyFrame* pCurKF);
+
 }  // namespace Hip
 #endif
