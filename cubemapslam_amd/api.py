@@ -1443,6 +1443,57 @@ def ba_run(prob, its=(5, 10), stop=None, device=0):
     return dict(rc=rc, poses=poses, points=pts, outliers=flags, stats=st)
 
 
+def ba_optimize_global(bas, iterations, robust, stop=None, stop_array=None):
+    """cms_ba_optimize_global_many: Optimizer::BundleAdjustment's one optimize(iterations) (Optimizer.cpp:570-572) over windows that have not
+    been optimised since they were created or reset; Huber(sqrt(5.99)) on every edge if robust, no classification.  bas: one BundleAdjuster or
+    a list.  -> (rc, [BaStats]) in the caller's order (slot [0] used)."""
+    if isinstance(bas, BundleAdjuster):
+        bas = [bas]
+    n = len(bas)
+    handles = (C.c_void_p * n)(*[b.h for b in bas])
+    stats = (BaStats * n)()
+    stop_arr = stop_array if stop_array is not None else (np.array([1], np.uint8) if stop else None)
+    L = lib()
+    L.cms_ba_optimize_global_many.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    rc = _chk(L.cms_ba_optimize_global_many(handles, n, int(iterations), 1 if robust else 0, _p(stop_arr), stats), "cms_ba_optimize_global_many")
+    return rc, list(stats)
+
+
+def ba_run_global(prob, iterations=10, robust=False, stop=None, device=0):
+    """create, cms_ba_optimize_global, read, destroy -- ba_run's return shape (the outlier flags stay zero: global BA classifies nothing)"""
+    ba = BundleAdjuster(prob, device)
+    try:
+        rc, st = ba_optimize_global([ba], iterations, robust, stop)
+        poses, pts, flags = ba.read()
+    finally:
+        ba.close()
+    return dict(rc=rc, poses=poses, points=pts, outliers=flags, stats=st[0])
+
+
+def ba_solve_tiled(A, b, device=0):
+    """cms_ba_debug_solve_tiled: the tiled LDL^T solve of a dense symmetric system on its own (the lower triangle of A is read) -> (x, status)"""
+    A = np.ascontiguousarray(A, np.float64); b = np.ascontiguousarray(b, np.float64)
+    n = int(b.shape[0])
+    if A.shape != (n, n):
+        raise ValueError("ba_solve_tiled: A must be n x n")
+    x = np.zeros(n); status = np.zeros(1, np.int32)
+    L = lib()
+    L.cms_ba_debug_solve_tiled.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    _chk(L.cms_ba_debug_solve_tiled(int(device), n, _p(A), _p(b), _p(x), _p(status)), "cms_ba_debug_solve_tiled")
+    return x, int(status[0])
+
+
+def ba_solve_timed(A, b, which=0, reps=3, device=0):
+    """cms_ba_debug_solve_timed: (x, status, mean milliseconds per solve by HIP events); which: 0 the tiled solve, 1 k_ba_solve (n <= 1024)"""
+    A = np.ascontiguousarray(A, np.float64); b = np.ascontiguousarray(b, np.float64)
+    n = int(b.shape[0])
+    x = np.zeros(n); status = np.zeros(1, np.int32); ms = np.zeros(1)
+    L = lib()
+    L.cms_ba_debug_solve_timed.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    _chk(L.cms_ba_debug_solve_timed(int(device), int(which), n, _p(A), _p(b), _p(x), _p(status), int(reps), _p(ms)), "cms_ba_debug_solve_timed")
+    return x, int(status[0]), float(ms[0])
+
+
 def ba_linearize(prob, robust=True, delta=float(np.sqrt(5.991)), device=0):
     K, P, E = len(prob["poses"]), len(prob["points"]), len(prob["e_pose"])
     poses = np.ascontiguousarray(prob["poses"], np.float64); pts = np.ascontiguousarray(prob["points"], np.float64)

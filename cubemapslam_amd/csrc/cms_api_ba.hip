@@ -155,6 +155,11 @@ struct cms_ba {
   BaSe grp_se = {};          // the window's share of the current group's Schur launch (ba_upload_items)
   std::vector<BaBlock> slabs; size_t slab_off = 0;      // device memory of the window: carved from pooled slabs (ba_alloc)
   size_t grp_pin_bytes[3] = {0, 0, 0};                  // sizes of grp_items_host, grp_scal_host, grp_lm_host (pooled pinned blocks)
+  // global bundle adjustment (cms_ba_optimize_global*): defined for a window that has not been optimised since it was created or reset
+  bool fresh = true;
+  bool tiled = false;        // this call's trials solve the reduced system with cms_ba_solve_tiled.hip where k_ba_solve stands (set and cleared by the global entry)
+  double* d_tl_ws = nullptr; // its workspace, carved from the window's slabs by the first global call that needs it
+  BaTl tl = {};
 };
 
 // Dynamic-LDS ceilings of the BA kernels: hipFuncAttributeMaxDynamicSharedMemorySize is a per-function (per device) global, so it is
@@ -1654,6 +1659,7 @@ extern "C" int cms_ba_reset(cms_ba* b) {
   HIPCHK(hipGetLastError());
   b->async_pending = true;
   b->gsum_clean = true;
+  b->fresh = true;
   return CMS_OK;       // asynchronous on the window's stream: every consumer (optimize, read) orders itself behind it
 }
 

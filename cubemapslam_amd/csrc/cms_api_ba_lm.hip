@@ -84,7 +84,9 @@ static int ba_enqueue_trial(cms_ba* b, const BaLm& st) {
       hipLaunchKernelGGL(k_ba_schur_finish, dim3(b->npairs), dim3(64), 0, s, b->np, (const int*)b->d_pair_s1, (const int*)b->d_pair_s2,
                          (const int*)b->d_pair_chunk_off, (const double*)b->d_chunk_sum, b->d_Hs, b->d_bs);
     }
-    if (b->solve_in_lds)
+    if (b->tiled && !b->solve_in_lds)      // cms_ba_optimize_global*: many workgroups (cms_ba_solve_tiled.hip)
+      ba_tl_enqueue(b->tl, b->d_bs, s);
+    else if (b->solve_in_lds)
       hipLaunchKernelGGL(k_ba_solve_r192, dim3(1), dim3(512), b->solve_lds, s, n, (const double*)b->d_Hs, (const double*)b->d_bs, b->d_x, b->d_status);
     else
       hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(256), 0, s, n, b->d_Hs, b->d_bs, b->d_x, b->d_Dg, b->d_status);
@@ -646,7 +648,9 @@ static int ba_classify_batched(cms_ba** bas, int n, int set_level, std::vector<i
   return CMS_OK;
 }
 
-static int ba_optimize_group(cms_ba** bas, int n, int its_robust, int its_final, const volatile uint8_t* stop, cms_ba_stats* stats);
+// one stage, no classification (cms_ba_optimize_global*): iterations, kernel or not, the kernel's width
+struct BaOneStage { int iterations, robust; double delta; };
+static int ba_optimize_group(cms_ba** bas, int n, int its_robust, int its_final, const volatile uint8_t* stop, cms_ba_stats* stats, const BaOneStage* one = nullptr);
 // Slices the Schur launch of a deterministic window's group leaves for the window: its share is det_ranges workgroups whatever the group
 // (ba_group_ranges), split the way ba_upload_items splits it (the run-major body only where the group's windows -- all of one kind -- have runs and
 // full workgroups)
@@ -659,9 +663,7 @@ static int ba_det_slices(const cms_ba* b) {
 // Windows are independent problems; the grouped driver wants a group of one kind (one device; all with the edge-major work list, or none:
 // a window that has it carries no other list) of at most BA_MAX_GROUP windows.  A call that mixes kinds is run as several groups, one
 // after the other -- same results, the caller's order of `stats` kept.
-extern "C" int cms_ba_optimize_many(cms_ba** bas, int n, int its_robust, int its_final, const volatile uint8_t* stop, cms_ba_stats* stats) {
-  if (!bas || n < 1) return cms_fail(CMS_ERR_ARG, "cms_ba_optimize_many: bad argument");
-  for (int w = 0; w < n; ++w) if (!bas[w]) return cms_fail(CMS_ERR_ARG, "null ba");
+static int ba_optimize_many(cms_ba** bas, int n, int its_robust, int its_final, const volatile uint8_t* stop, cms_ba_stats* stats, const BaOneStage* one1) {
   // (device-planned windows among themselves: their groups always run the fused kernels, which is all they carry lists for)
   // (a deterministic window's sums must not depend on its company: windows that would change the group's kernels -- fewer wavefronts per workgroup,
   // no signature runs, the other slice-summing solve kernel, the slices summed by a launch of their own -- form groups of their own: ba_group_kind,
@@ -676,7 +678,7 @@ extern "C" int cms_ba_optimize_many(cms_ba** bas, int n, int its_robust, int its
   };
   bool one = n <= BA_MAX_GROUP;
   for (int w = 1; w < n && one; ++w) one = kind(w) == kind(0);
-  if (one) return ba_optimize_group(bas, n, its_robust, its_final, stop, stats);
+  if (one) return ba_optimize_group(bas, n, its_robust, its_final, stop, stats, one1);
   std::vector<char> done(n, 0);
   int rc_all = CMS_OK;
   for (int w0 = 0; w0 < n; ++w0) {
@@ -685,14 +687,19 @@ extern "C" int cms_ba_optimize_many(cms_ba** bas, int n, int its_robust, int its
     for (int w = w0; w < n && (int)grp.size() < BA_MAX_GROUP; ++w)
       if (!done[w] && kind(w) == kind(w0)) { grp.push_back(bas[w]); idx.push_back(w); done[w] = 1; }
     std::vector<cms_ba_stats> gs(grp.size());
-    const int rc = ba_optimize_group(grp.data(), (int)grp.size(), its_robust, its_final, stop, gs.data());
+    const int rc = ba_optimize_group(grp.data(), (int)grp.size(), its_robust, its_final, stop, gs.data(), one1);
     if (stats) for (size_t i = 0; i < idx.size(); ++i) stats[idx[i]] = gs[i];
     if (rc < 0) return rc;                 // an error ends the call; "stopped" (1) lets the remaining groups see the flag themselves
     if (rc != CMS_OK) rc_all = rc;
   }
   return rc_all;
 }
-static int ba_optimize_group(cms_ba** bas, int n, int its_robust, int its_final, const volatile uint8_t* stop, cms_ba_stats* stats) {
+extern "C" int cms_ba_optimize_many(cms_ba** bas, int n, int its_robust, int its_final, const volatile uint8_t* stop, cms_ba_stats* stats) {
+  if (!bas || n < 1) return cms_fail(CMS_ERR_ARG, "cms_ba_optimize_many: bad argument");
+  for (int w = 0; w < n; ++w) if (!bas[w]) return cms_fail(CMS_ERR_ARG, "null ba");
+  return ba_optimize_many(bas, n, its_robust, its_final, stop, stats, nullptr);
+}
+static int ba_optimize_group(cms_ba** bas, int n, int its_robust, int its_final, const volatile uint8_t* stop, cms_ba_stats* stats, const BaOneStage* one) {
   const bool batched = ba_can_batch(bas, n);
   static const bool call_timing = getenv("CMS_BA_CALL_TIMING") != nullptr;      // developer knob: where a call's host time goes (stderr, ms since entry)
   const auto t_in = std::chrono::steady_clock::now();
@@ -735,9 +742,10 @@ static int ba_optimize_group(cms_ba** bas, int n, int its_robust, int its_final,
     if (stats) memcpy(stats, local.data(), n * sizeof(cms_ba_stats));
     return 1;
   }
-  const double delta = std::sqrt(5.991);
+  const double delta = one ? one->delta : std::sqrt(5.991);
   std::vector<BaLm> st(n);
-  for (int w = 0; w < n; ++w) { st[w] = BaLm(); st[w].iterations = its_robust; st[w].robust = 1; st[w].delta = delta; }
+  for (int w = 0; w < n; ++w) { st[w] = BaLm(); st[w].iterations = one ? one->iterations : its_robust; st[w].robust = one ? one->robust : 1; st[w].delta = delta; }
+  for (int w = 0; w < n; ++w) bas[w]->fresh = false;
   const bool host_lm = ba_knobs().host_lm;
   for (int w = 0; w < n; ++w)      // (cannot happen while the knobs are read once: the lists were chosen by the same switches)
     if (bas[w]->se_only && (!batched || host_lm || !ba_use_se(bas, n)))
@@ -748,6 +756,12 @@ static int ba_optimize_group(cms_ba** bas, int n, int its_robust, int its_final,
   for (int w = 0; w < n; ++w) {
     local[w].iterations_done[0] = st[w].done; local[w].chi2_initial[0] = st[w].chi_ini; local[w].chi2_final[0] = st[w].chi_fin;
     local[w].lambda_final[0] = st[w].lam_fin;
+  }
+  if (one) {      // BundleAdjustment (Optimizer.cpp:570-572): optimize(nIterations) and nothing else -- no classification, no level, no flag
+    if (stats) memcpy(stats, local.data(), n * sizeof(cms_ba_stats));
+    if (batched)      // the stage driver synchronised the group's stream: nothing of the windows is in flight, every round's solve kernel left the global copy zero
+      for (int w = 0; w < n; ++w) { bas[w]->async_pending = false; bas[w]->grp_stream = nullptr; bas[w]->gsum_clean = bas[w]->grp_se.gsum != 0; }
+    return CMS_OK;
   }
   std::vector<std::vector<uint8_t>> flags(n);
   std::vector<int> counts(n, 0);
@@ -793,4 +807,96 @@ static int ba_optimize_group(cms_ba** bas, int n, int its_robust, int its_final,
 extern "C" int cms_ba_optimize(cms_ba* b, int its_robust, int its_final, const volatile uint8_t* stop, cms_ba_stats* st) {
   if (!b) return cms_fail(CMS_ERR_ARG, "null ba");
   return cms_ba_optimize_many(&b, 1, its_robust, its_final, stop, st);
+}
+
+// ---- Optimizer::GlobalBundleAdjustemnt / BundleAdjustment (Optimizer.cpp:453-621): ONE optimize(iterations) over the window, Huber(sqrt(5.99)) on
+// every edge or no kernel (:541-546; the local BA's text has 5.991, :303), no classification.  Windows beyond the LDS solves factor their reduced
+// system with the tiled solve; its workspace is carved from the window's slabs at the first such call.
+extern "C" int cms_ba_optimize_global_many(cms_ba** bas, int n, int iterations, int robust, const volatile uint8_t* stop, cms_ba_stats* stats) {
+  if (!bas || n < 1 || iterations < 0) return cms_fail(CMS_ERR_ARG, "cms_ba_optimize_global_many: bad argument");
+  for (int w = 0; w < n; ++w) if (!bas[w]) return cms_fail(CMS_ERR_ARG, "null ba");
+  for (int w = 0; w < n; ++w)
+    if (!bas[w]->fresh) return cms_fail(CMS_ERR_ARG, "cms_ba_optimize_global: the window was optimised since it was created or reset (cms_ba_reset first)");
+  for (int w = 0; w < n; ++w)
+    for (int v = 0; v < w; ++v)
+      if (bas[v] == bas[w]) return cms_fail(CMS_ERR_ARG, "cms_ba_optimize_global_many: a window named twice");
+  if (ba_stopped(stop)) {      // nothing is enqueued; the windows stay as they were
+    if (stats) memset(stats, 0, (size_t)n * sizeof(cms_ba_stats));
+    return 1;
+  }
+  for (int w = 0; w < n; ++w) {
+    cms_ba* b = bas[w];
+    const int nn = 6 * b->np;
+    if (b->solve_blk || b->solve_in_lds || nn <= 0) continue;
+    if (nn > BA_TL_MAX_N) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "cms_ba_optimize_global: reduced system of order %d, the tiled solve takes up to %d (%d free key frames)", nn, BA_TL_MAX_N, BA_TL_MAX_N / 6);
+      return cms_fail(CMS_ERR_UNSUPPORTED, msg);
+    }
+    if (!b->d_tl_ws) { HIPCHK(hipSetDevice(b->device)); const int rc = ba_alloc(b, &b->d_tl_ws, ba_tl_ws_doubles(nn)); if (rc) return rc; }
+    b->tl = ba_tl_bind(nn, b->d_Hs, b->d_x, b->d_tl_ws, b->d_status);
+    b->tiled = true;
+  }
+  const BaOneStage one{iterations, robust ? 1 : 0, std::sqrt(5.99)};
+  const int rc = ba_optimize_many(bas, n, 0, 0, stop, stats, &one);
+  for (int w = 0; w < n; ++w) bas[w]->tiled = false;
+  return rc;
+}
+extern "C" int cms_ba_optimize_global(cms_ba* b, int iterations, int robust, const volatile uint8_t* stop, cms_ba_stats* st) {
+  if (!b) return cms_fail(CMS_ERR_ARG, "null ba");
+  return cms_ba_optimize_global_many(&b, 1, iterations, robust, stop, st);
+}
+
+// developer entries: the tiled solve on its own (host arrays; the lower triangle of the row-major A is read), and the same with HIP-event timing over
+// `reps` repetitions (the matrix is restored from a device copy before each; *ms: mean milliseconds per solve).  which = 1 times k_ba_solve, the one
+// workgroup the two-stage entry keeps for its large windows -- up to order 1024 only: beyond that its run time is the reason the tiled solve exists.
+static int ba_tl_debug(int device, int which, int n, const double* A, const double* b, double* x, int* status, int reps, double* ms) {
+  if (n < 1 || !A || !b || !x || !status || reps < 1 || !ba_pool_device_ok(device)) return cms_fail(CMS_ERR_ARG, "cms_ba_debug_solve_tiled: bad argument");
+  if (n > BA_TL_MAX_N || (which == 1 && n > 1024)) {
+    char msg[128];
+    snprintf(msg, sizeof(msg), "cms_ba_debug_solve: order %d, the %s takes up to %d", n, which == 1 ? "timed k_ba_solve" : "tiled solve", which == 1 ? 1024 : BA_TL_MAX_N);
+    return cms_fail(CMS_ERR_UNSUPPORTED, msg);
+  }
+  HIPCHK(hipSetDevice(device));
+  const bool timed = ms != nullptr;
+  const size_t nA = (size_t)n * n, nws = ba_tl_ws_doubles(n), total = ((timed ? 2 : 1) * nA + 3 * (size_t)n + nws + 8) * sizeof(double);
+  void* blk = nullptr; size_t got = 0;
+  hipError_t e = ba_dev_take(device, total, &blk, &got);
+  if (e != hipSuccess) return cms_fail(CMS_ERR_HIP, "hipMalloc (cms_ba_debug_solve_tiled)", e);
+  double* dA = static_cast<double*>(blk);
+  double* db = dA + nA; double* dx = db + n; double* dDg = dx + n; double* ws = dDg + n; int* dst = reinterpret_cast<int*>(ws + nws);
+  double* dA0 = reinterpret_cast<double*>(dst + 16);      // (timed: the pristine copy)
+  hipStream_t s = nullptr;      // (the null stream: a developer entry)
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  e = hipMemcpy(timed ? dA0 : dA, A, nA * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(db, b, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess && timed) { e = hipEventCreate(&ev[0]); if (e == hipSuccess) e = hipEventCreate(&ev[1]); }
+  double sum_ms = 0;
+  for (int r = 0; r < reps && e == hipSuccess; ++r) {
+    if (timed) { e = hipMemcpyAsync(dA, dA0, nA * sizeof(double), hipMemcpyDeviceToDevice, s); if (e != hipSuccess) break; hipEventRecord(ev[0], s); }
+    if (which == 1) hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(256), 0, s, n, dA, db, dx, dDg, dst);
+    else ba_tl_enqueue(ba_tl_bind(n, dA, dx, ws, dst), db, s);
+    e = hipGetLastError();
+    if (timed && e == hipSuccess) {
+      hipEventRecord(ev[1], s);
+      e = hipEventSynchronize(ev[1]);
+      float t = 0;
+      if (e == hipSuccess) e = hipEventElapsedTime(&t, ev[0], ev[1]);
+      sum_ms += t;
+    }
+  }
+  if (e == hipSuccess) e = hipMemcpy(x, dx, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(status, dst, sizeof(int), hipMemcpyDeviceToHost);
+  for (hipEvent_t v : ev) if (v) hipEventDestroy(v);
+  ba_dev_give(device, blk, got);
+  if (e != hipSuccess) return cms_fail(CMS_ERR_HIP, "cms_ba_debug_solve_tiled", e);
+  if (ms) *ms = sum_ms / reps;
+  return CMS_OK;
+}
+extern "C" int cms_ba_debug_solve_tiled(int device, int n, const double* A, const double* b, double* x, int* status) {
+  return ba_tl_debug(device, 0, n, A, b, x, status, 1, nullptr);
+}
+extern "C" int cms_ba_debug_solve_timed(int device, int which, int n, const double* A, const double* b, double* x, int* status, int reps, double* ms) {
+  if (!ms || which < 0 || which > 1) return cms_fail(CMS_ERR_ARG, "cms_ba_debug_solve_timed: bad argument");
+  return ba_tl_debug(device, which, n, A, b, x, status, reps, ms);
 }

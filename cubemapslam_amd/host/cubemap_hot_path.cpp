@@ -945,6 +945,88 @@ void Optimizer::LocalBundleAdjustment(LocalBAWindow* win, bool* pbStopFlag) {
 }
 
 
+// ------------------------------------------------------------------------------------------------ Optimizer::GlobalBundleAdjustemnt (src/Optimizer.cpp:453-621)
+GlobalBAGraph Optimizer::CollectGlobalBA(const GlobalBAMap& pMap) {
+  CamModelGeneral* cam = CamModelGeneral::GetCamera();
+  GlobalBAGraph g;
+  const int nAll = (int)pMap.mvpKeyFrames.size(), nKF = pMap.nListedKeyFrames < 0 ? nAll : std::min(pMap.nListedKeyFrames, nAll), nMP = (int)pMap.mvpMapPoints.size();
+  g.vbNotIncludedMP.assign((size_t)nMP, 0);
+  std::vector<int> slot((size_t)nAll, -1);
+  long unsigned int maxKFid = 0;
+  for (int i = 0; i < nKF; ++i) {                                                  // :483-495
+    const GlobalBAKeyFrameView& kf = pMap.mvpKeyFrames[(size_t)i];
+    if (kf.mbBad) continue;
+    double R[9], pose[7];                                                          // Converter::toSE3Quat (Converter.cpp:41-51)
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) R[3 * r + c] = kf.Tcw.at<float>(r, c);
+    for (int r = 0; r < 3; ++r) pose[r] = kf.Tcw.at<float>(r, 3);
+    R_to_quat(R, pose + 3);
+    slot[(size_t)i] = (int)g.vertexKF.size();
+    g.vertexKF.push_back(i);
+    g.poses.insert(g.poses.end(), pose, pose + 7);
+    g.fixed.push_back(kf.mnId == 0 ? 1 : 0);                                       // :491
+    if (kf.mnId > maxKFid) maxKFid = kf.mnId;
+  }
+  for (int i = 0; i < nMP; ++i) {                                                  // :500-568
+    const GlobalBAMapPointView& mp = pMap.mvpMapPoints[(size_t)i];
+    if (mp.mbBad) continue;
+    const int p = (int)g.vertexMP.size();
+    const size_t e0 = g.e_pose.size();
+    for (const std::pair<int, int>& ob : mp.observations) {
+      const GlobalBAKeyFrameView& kf = pMap.mvpKeyFrames[(size_t)ob.first];
+      if (kf.mbBad || kf.mnId > maxKFid) continue;                                 // :520
+      if (slot[(size_t)ob.first] < 0) continue;                                    // no vertex of that id (the reference would pass g2o a null vertex)
+      const cv::KeyPoint& kp = kf.mvKeys[(size_t)ob.second];
+      if (kf.mvKeyRays[(size_t)ob.second](2) < cam->GetCosFovTh()) continue;       // :525
+      const int face = cam->FaceInCubemap(kp.pt);                                  // :537
+      if (face == CamModelGeneral::UNKNOWN_FACE) throw std::runtime_error("GlobalBundleAdjustemnt: key point on an unknown face");      // the reference exits
+      double u, v;
+      cam->GetPosInFace(u, v, (double)kp.pt.x, (double)kp.pt.y);                    // :538-540
+      g.e_pose.push_back(slot[(size_t)ob.first]); g.e_point.push_back(p);
+      g.e_obs.push_back(u); g.e_obs.push_back(v);
+      g.e_invsig2.push_back((double)kf.mvInvLevelSigma2[(size_t)kp.octave]);       // :541
+      g.e_face.push_back((int8_t)face);
+    }
+    if (g.e_pose.size() == e0) { g.vbNotIncludedMP[(size_t)i] = 1; continue; }     // :559-563
+    g.vertexMP.push_back(i);
+    for (int c = 0; c < 3; ++c) g.points.push_back((double)mp.Xw.at<float>(c, 0)); // Converter::toVector3d
+  }
+  return g;
+}
+
+void Optimizer::GlobalBundleAdjustemnt(GlobalBAMap& pMap, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF, const bool bRobust) {
+  CamModelGeneral* cam = CamModelGeneral::GetCamera();
+  GlobalBAGraph g = CollectGlobalBA(pMap);
+  const int K = (int)g.vertexKF.size(), P = (int)g.vertexMP.size(), E = (int)g.e_pose.size();
+  if (K > 0 && E > 0) {                                                            // (nothing to optimise: g2o's optimize() returns at once, the estimates are written back as they are)
+    const double f = cam->Get_fx();
+    cms_ba* ba = nullptr;
+    int rc = cms_ba_create(&ba, 0, K, g.poses.data(), g.fixed.data(), P, g.points.data(), E, g.e_pose.data(), g.e_point.data(), g.e_obs.data(), g.e_invsig2.data(),
+                           g.e_face.data(), f, f, f, f);
+    if (rc < 0) throw std::runtime_error(std::string("cms_ba_create: ") + cms_last_error());
+    rc = cms_ba_optimize_global(ba, nIterations, bRobust ? 1 : 0, reinterpret_cast<const volatile uint8_t*>(pbStopFlag), nullptr);      // :570-572
+    if (rc >= 0) { const int rr = cms_ba_read(ba, g.poses.data(), g.points.data(), nullptr); if (rr < 0) rc = rr; }
+    cms_ba_destroy(ba);
+    if (rc < 0) throw std::runtime_error(std::string("cms_ba_optimize_global: ") + cms_last_error());
+  }
+  for (int k = 0; k < K; ++k) {                                                    // :577-594, Converter::toCvMat(SE3Quat) -> float 4x4 (Converter.cpp:53-104)
+    GlobalBAKeyFrameView& kf = pMap.mvpKeyFrames[(size_t)g.vertexKF[(size_t)k]];
+    const double* q = &g.poses[7 * (size_t)k + 3];
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z),
+                         2 * (y * z - x * w), 2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+    if (nLoopKF != 0) { if (kf.mTcwGBA.empty()) kf.mTcwGBA = cv::Mat::zeros(4, 4, cv::CV_32F); kf.mnBAGlobalForKF = nLoopKF; }
+    cv::Mat& T = nLoopKF == 0 ? kf.Tcw : kf.mTcwGBA;
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) T.at<float>(r, c) = (float)R[3 * r + c]; T.at<float>(r, 3) = (float)g.poses[7 * (size_t)k + r]; }
+    for (int c = 0; c < 4; ++c) T.at<float>(3, c) = c == 3 ? 1.0f : 0.0f;
+  }
+  for (int p = 0; p < P; ++p) {                                                    // :597-619
+    GlobalBAMapPointView& mp = pMap.mvpMapPoints[(size_t)g.vertexMP[(size_t)p]];
+    if (nLoopKF != 0) { if (mp.mPosGBA.empty()) mp.mPosGBA = cv::Mat::zeros(3, 1, cv::CV_32F); mp.mnBAGlobalForKF = nLoopKF; }
+    cv::Mat& X = nLoopKF == 0 ? mp.Xw : mp.mPosGBA;
+    for (int c = 0; c < 3; ++c) X.at<float>(c, 0) = (float)g.points[3 * (size_t)p + c];
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ PnPsolver (src/PnPsolver.cpp)
 extern "C" int hm_pnp_iterate_host(int F, int njobs, cms_pnp_job* jobs);      // pnp_host.cpp: the host build of csrc/cms_pnp_core.h
 

@@ -10,6 +10,7 @@
 //   ORBMatcher(nnratio, checkOri) / DescriptorDistance / SearchByProjection(CurrentFrame, LastFrame, th, mono)
 //                                                                   include/ORBMatcher.h:46-84, src/ORBMatcher.cpp:130-251,951-967
 //   Optimizer::LocalBundleAdjustment(...)                           include/Optimizer.h:50, src/Optimizer.cpp:192-451
+//   Optimizer::GlobalBundleAdjustemnt(...)                          include/Optimizer.h, src/Optimizer.cpp:453-621
 //   ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>) loadFromTextFile / saveToTextFile / transform / score
 //                                                                   include/ORBVocabulary.h, Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h
 //
@@ -483,9 +484,57 @@ struct EssGraph {
   int fixed = -1;
 };
 
+// What Optimizer::GlobalBundleAdjustemnt / BundleAdjustment (src/Optimizer.cpp:453-621) reads and writes of the map.  Key frames and map points are
+// named by their index in the map's vectors (the order of GetAllKeyFrames / GetAllMapPoints).  An observation names a key frame by its index in
+// mvpKeyFrames; the first nListedKeyFrames of them are the call's vpKFs, any further ones stand for key frames the map received after the snapshot (the
+// reference skips their observations: mnId > maxKFid, :520).  The reference walks a point's observations in the order of a std::map keyed by pointer,
+// which is the allocator's business; the mirror walks them as the caller lists them.
+struct GlobalBAKeyFrameView {
+  long unsigned int mnId = 0;
+  bool mbBad = false;
+  cv::Mat Tcw;                                  // 4x4 CV_32F; SetPose writes it when nLoopKF == 0 (:586)
+  std::vector<cv::KeyPoint> mvKeys;
+  std::vector<cv::Vec3f> mvKeyRays;
+  std::vector<float> mvInvLevelSigma2;
+  cv::Mat mTcwGBA;                              // 4x4 CV_32F, created and written when nLoopKF != 0 (:590-592)
+  long unsigned int mnBAGlobalForKF = 0;
+};
+struct GlobalBAMapPointView {
+  long unsigned int mnId = 0;
+  bool mbBad = false;
+  cv::Mat Xw;                                   // 3x1 CV_32F; SetWorldPos writes it when nLoopKF == 0 (:610)
+  std::vector<std::pair<int, int>> observations;      // (key-frame index, key-point index)
+  cv::Mat mPosGBA;                              // 3x1 CV_32F, created and written when nLoopKF != 0 (:615-617)
+  long unsigned int mnBAGlobalForKF = 0;
+};
+struct GlobalBAMap {
+  std::vector<GlobalBAKeyFrameView> mvpKeyFrames;
+  std::vector<GlobalBAMapPointView> mvpMapPoints;
+  int nListedKeyFrames = -1;                    // -1: all of mvpKeyFrames
+};
+// The graph of :480-568 as the arrays of cms_ba_create: pose k is key frame vertexKF[k] (the listed key frames that are not bad, in list order), point p
+// is map point vertexMP[p] (not bad and left with at least one edge, in list order); edges per point in list order, per observation in the point's order
+struct GlobalBAGraph {
+  std::vector<int> vertexKF, vertexMP;
+  std::vector<double> poses, points, e_obs, e_invsig2;      // 7 per pose (t, q), 3 per point, 2 per edge, 1 per edge
+  std::vector<uint8_t> fixed;                                // mnId == 0
+  std::vector<int> e_pose, e_point;
+  std::vector<int8_t> e_face;
+  std::vector<uint8_t> vbNotIncludedMP;                      // per map point of the map: bad points are never looked at (0), points without an edge are 1
+};
+
 class Optimizer {
  public:
   enum Engine { DEVICE = 0, HOST_CORE = 1 };
+  // Optimizer.cpp:453-621, spelled as the reference spells it.  CollectGlobalBA does the pointer work of :480-568: bad key frames and bad map points are
+  // left out, fixed = mnId == 0, observations from a bad key frame or from one with mnId > maxKFid are skipped (so are those from a key frame that has no
+  // vertex although its mnId is below maxKFid, where the reference would hand g2o a null vertex), rays with z < cosFovTh are skipped, face and in-face
+  // measurement come from the key point, invSigma2 is that of the octave, a map point left with no edge is marked not included and never written.  The
+  // optimisation is one cms_ba_optimize_global call -- optimize(nIterations), Huber(sqrt(5.99)) if bRobust -- on the shared context's device.  Write-back
+  // as :577-619: nLoopKF == 0 into Tcw / Xw through float, otherwise into mTcwGBA / mPosGBA with mnBAGlobalForKF = nLoopKF.  UpdateNormalAndDepth (:611)
+  // stays the caller's.
+  static void GlobalBundleAdjustemnt(GlobalBAMap& pMap, int nIterations = 5, bool* pbStopFlag = NULL, const unsigned long nLoopKF = 0, const bool bRobust = true);
+  static GlobalBAGraph CollectGlobalBA(const GlobalBAMap& pMap);
   // Optimizer.cpp:623-886.  CollectEssentialGraph does the pointer work of :650-825: one vertex per key frame that is not bad, in mnId order, with vScw
   // = the CorrectedSim3 value or Sim3(Rcw, tcw, 1); the loop-connection edges under the minFeat = 100 rule with the (pCurKF, pLoopKF) exemption and
   // sInsertedEdges; per key frame the spanning-tree edge, the loop edges to lower mnId and the covisibility edges of weight >= minFeat that are neither

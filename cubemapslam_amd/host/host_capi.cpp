@@ -1017,3 +1017,72 @@ extern "C" int hm_ess_graph_mirror(int engine, int nkf, const int* mnId, const u
     for (int i = 0; i < nmp; ++i) std::memcpy(mp_pos + 3 * (size_t)i, map.mvpMapPoints[(size_t)i].mWorldPos, 12);
     return 0;)
 }
+
+// Optimizer::GlobalBundleAdjustemnt of cubemap_hot_path.h over flat arrays.  Key frames (nkf of them, the first n_list are the call's list): mnId, bad, Tcw
+// (16 floats, row-major 4x4, in/out), nkp key points each (x, y | octave | ray), one invSigma2 table.  Map points: mnId, bad, Xw (in/out), observations in CSR
+// form (key-frame index, key-point index).  hm_global_ba_collect returns what CollectGlobalBA made (capacities: nkf poses, nmp points, obs_off[nmp] edges);
+// hm_global_ba_mirror runs the call and hands back Tcw / Xw, and mTcwGBA / mPosGBA / mnBAGlobalForKF where the call created them (other rows untouched).
+static GlobalBAMap gba_map(int nkf, int n_list, const long* kf_id, const uint8_t* kf_bad, float* Tcw, int nkp, const float* keys, const int* octave, const float* rays,
+                           const float* inv_sigma2, int nlevels, int nmp, const long* mp_id, const uint8_t* mp_bad, float* Xw, const int* obs_off, const int* obs_kf,
+                           const int* obs_kp) {
+  GlobalBAMap map;
+  map.nListedKeyFrames = n_list;
+  map.mvpKeyFrames.resize((size_t)nkf);
+  for (int k = 0; k < nkf; ++k) {
+    GlobalBAKeyFrameView& v = map.mvpKeyFrames[(size_t)k];
+    v.mnId = (long unsigned int)kf_id[k]; v.mbBad = kf_bad[k] != 0;
+    v.Tcw = cv::Mat(4, 4, cv::CV_32F, Tcw + 16 * (size_t)k, 16);
+    v.mvInvLevelSigma2.assign(inv_sigma2, inv_sigma2 + nlevels);
+    v.mvKeys.resize((size_t)nkp); v.mvKeyRays.resize((size_t)nkp);
+    for (int i = 0; i < nkp; ++i) {
+      const size_t o = (size_t)k * nkp + i;
+      v.mvKeys[(size_t)i].pt = cv::Point2f(keys[2 * o], keys[2 * o + 1]); v.mvKeys[(size_t)i].octave = octave[o];
+      for (int c = 0; c < 3; ++c) v.mvKeyRays[(size_t)i].v[c] = rays[3 * o + c];
+    }
+  }
+  map.mvpMapPoints.resize((size_t)nmp);
+  for (int p = 0; p < nmp; ++p) {
+    GlobalBAMapPointView& m = map.mvpMapPoints[(size_t)p];
+    m.mnId = (long unsigned int)mp_id[p]; m.mbBad = mp_bad[p] != 0;
+    m.Xw = cv::Mat(3, 1, cv::CV_32F, Xw + 3 * (size_t)p, 4);
+    for (int o = obs_off[p]; o < obs_off[p + 1]; ++o) m.observations.push_back(std::make_pair(obs_kf[o], obs_kp[o]));
+  }
+  return map;
+}
+extern "C" int hm_global_ba_collect(int nkf, int n_list, const long* kf_id, const uint8_t* kf_bad, float* Tcw, int nkp, const float* keys, const int* octave,
+                                    const float* rays, const float* inv_sigma2, int nlevels, int nmp, const long* mp_id, const uint8_t* mp_bad, float* Xw,
+                                    const int* obs_off, const int* obs_kf, const int* obs_kp, int* KPE, int* vertex_kf, int* vertex_mp, double* poses, uint8_t* fixed,
+                                    double* points, int* e_pose, int* e_point, double* e_obs, double* e_invsig2, int8_t* e_face, uint8_t* not_included) {
+  HM_TRY(
+    const GlobalBAMap map = gba_map(nkf, n_list, kf_id, kf_bad, Tcw, nkp, keys, octave, rays, inv_sigma2, nlevels, nmp, mp_id, mp_bad, Xw, obs_off, obs_kf, obs_kp);
+    const GlobalBAGraph g = Optimizer::CollectGlobalBA(map);
+    const size_t K = g.vertexKF.size(), P = g.vertexMP.size(), E = g.e_pose.size();
+    KPE[0] = (int)K; KPE[1] = (int)P; KPE[2] = (int)E;
+    std::memcpy(vertex_kf, g.vertexKF.data(), sizeof(int) * K); std::memcpy(vertex_mp, g.vertexMP.data(), sizeof(int) * P);
+    std::memcpy(poses, g.poses.data(), sizeof(double) * 7 * K); std::memcpy(fixed, g.fixed.data(), K);
+    std::memcpy(points, g.points.data(), sizeof(double) * 3 * P);
+    std::memcpy(e_pose, g.e_pose.data(), sizeof(int) * E); std::memcpy(e_point, g.e_point.data(), sizeof(int) * E);
+    std::memcpy(e_obs, g.e_obs.data(), sizeof(double) * 2 * E); std::memcpy(e_invsig2, g.e_invsig2.data(), sizeof(double) * E);
+    std::memcpy(e_face, g.e_face.data(), E);
+    std::memcpy(not_included, g.vbNotIncludedMP.data(), (size_t)nmp);
+    return 0;)
+}
+extern "C" int hm_global_ba_mirror(int nkf, int n_list, const long* kf_id, const uint8_t* kf_bad, float* Tcw, int nkp, const float* keys, const int* octave,
+                                   const float* rays, const float* inv_sigma2, int nlevels, int nmp, const long* mp_id, const uint8_t* mp_bad, float* Xw,
+                                   const int* obs_off, const int* obs_kf, const int* obs_kp, int iterations, uint8_t* stop, long nLoopKF, int robust, float* TcwGBA,
+                                   long* kf_gba, float* PosGBA, long* mp_gba) {
+  HM_TRY(
+    GlobalBAMap map = gba_map(nkf, n_list, kf_id, kf_bad, Tcw, nkp, keys, octave, rays, inv_sigma2, nlevels, nmp, mp_id, mp_bad, Xw, obs_off, obs_kf, obs_kp);
+    Optimizer::GlobalBundleAdjustemnt(map, iterations, reinterpret_cast<bool*>(stop), (unsigned long)nLoopKF, robust != 0);
+    for (int k = 0; k < nkf; ++k) {
+      const GlobalBAKeyFrameView& v = map.mvpKeyFrames[(size_t)k];
+      kf_gba[k] = (long)v.mnBAGlobalForKF;
+      if (!v.mTcwGBA.empty()) for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) TcwGBA[16 * (size_t)k + 4 * r + c] = v.mTcwGBA.at<float>(r, c);
+    }
+    for (int p = 0; p < nmp; ++p) {
+      const GlobalBAMapPointView& m = map.mvpMapPoints[(size_t)p];
+      mp_gba[p] = (long)m.mnBAGlobalForKF;
+      if (!m.mPosGBA.empty()) for (int c = 0; c < 3; ++c) PosGBA[3 * (size_t)p + c] = m.mPosGBA.at<float>(c, 0);
+    }
+    return 0;)
+}

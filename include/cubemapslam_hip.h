@@ -228,6 +228,27 @@ int cms_ba_optimize(cms_ba* ba, int its_robust, int its_final, const volatile ui
 /* n independent windows (e.g. the LocalMapping threads of n camera streams) advanced in lock-step by ONE host thread, each on
  * its own stream: same results as n cms_ba_optimize calls, without n host threads competing for the HIP runtime. stats[n]. */
 int cms_ba_optimize_many(cms_ba** bas, int n, int its_robust, int its_final, const volatile uint8_t* stop, cms_ba_stats* stats);
+/* ---- global bundle adjustment: numeric core of Optimizer::GlobalBundleAdjustemnt / Optimizer::BundleAdjustment (include/Optimizer.h,
+ *      src/Optimizer.cpp:453-621) over the same window handle (the caller assembles the whole map as Optimizer.cpp:480-568 does).
+ *      ONE SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg, exactly as one stage of the local BA runs it
+ *      (lambda0 = 1e-5 max diag, the accept / reject rules, qmax == 10, rho == 0, nBad >= 3; *stop polled at the same places).
+ *      robust != 0: Huber(sqrt(5.99)) on every edge -- BundleAdjustment's own text (:497); LocalBundleAdjustment writes 5.991 (:300) and
+ *      cms_ba_optimize follows that.  robust == 0: no kernel.  No classification: no level is set, no outlier flag written; stats uses
+ *      slot [0], everything else is zero.  *stop set on entry: nothing is enqueued, returns 1.  Defined for a window that has not been
+ *      optimised since cms_ba_create / cms_ba_create_many / cms_ba_reset; any other window is CMS_ERR_ARG.  The _many form treats its
+ *      windows as independent problems (grouped as cms_ba_optimize_many groups them), stats[n] in the caller's order.
+ *      Windows whose reduced camera system (order 6 x free key frames) does not fit the LDS solves factor it with a tiled LDL^T over many
+ *      workgroups (cms_ba_solve_tiled.hip) -- a dense factorisation in natural order where the reference runs Eigen's SimplicialLDLT under a
+ *      fill-reducing ordering: the same factorisation in exact arithmetic, another rounding.  Up to order 16 384 (2 730 free key frames);
+ *      beyond that CMS_ERR_UNSUPPORTED.  cms_ba_read / cms_ba_read_many return the estimate as ever. */
+int cms_ba_optimize_global(cms_ba* ba, int iterations, int robust, const volatile uint8_t* stop, cms_ba_stats* stats);
+int cms_ba_optimize_global_many(cms_ba** bas, int n, int iterations, int robust, const volatile uint8_t* stop, cms_ba_stats* stats);
+/* developer entry: the tiled solve on its own.  A (n x n, row-major, host; only the lower triangle is read), b -> x, *status 1, or 0 with x = 0 after a
+ * zero or non-finite pivot (no error code for that). */
+int cms_ba_debug_solve_tiled(int device, int n, const double* A, const double* b, double* x, int* status);
+/* ... and timed with HIP events over `reps` repetitions (*ms: mean milliseconds per solve; the matrix is restored on the device before each).
+ * which: 0 the tiled solve, 1 k_ba_solve (the one-workgroup kernel of cms_ba_optimize's large windows; n <= 1024, beyond that CMS_ERR_UNSUPPORTED). */
+int cms_ba_debug_solve_timed(int device, int which, int n, const double* A, const double* b, double* x, int* status, int reps, double* ms);
 int cms_ba_read(cms_ba* ba, double* poses, double* points, uint8_t* outlier_flags);
 void* cms_ba_stream(cms_ba* ba);
 /* run this window on a stream the caller owns (shared by the windows of a group, or the mapping context's own stream): keeps the

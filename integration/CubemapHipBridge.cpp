@@ -264,6 +264,82 @@ void LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap) {
   }
 }
 
+void GlobalBundleAdjustemnt(Map* pMap, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF, const bool bRobust) {
+  CamModelGeneral* cam = CamModelGeneral::GetCamera();
+  const std::vector<KeyFrame*> vpKFs = pMap->GetAllKeyFrames();    // Optimizer.cpp:455-456
+  const std::vector<MapPoint*> vpMP = pMap->GetAllMapPoints();
+  // ---- flat problem (what :480-568 hands g2o): one pose per key frame that is not bad, fixed = mnId == 0; one point per map point that is not bad and keeps an edge
+  std::vector<KeyFrame*> kfs;
+  std::map<KeyFrame*, int> kf_index;
+  std::vector<double> poses, points, e_obs, e_inv;
+  std::vector<uint8_t> fixed;
+  std::vector<int> e_pose, e_point;
+  std::vector<int8_t> e_face;
+  long unsigned int maxKFid = 0;
+  for (KeyFrame* k : vpKFs) {
+    if (k->isBad()) continue;
+    double p[7];
+    pose7(k->GetPose(), p);
+    kf_index[k] = (int)kfs.size(); kfs.push_back(k);
+    poses.insert(poses.end(), p, p + 7);
+    fixed.push_back(k->mnId == 0 ? 1 : 0);                          // :491
+    if (k->mnId > maxKFid) maxKFid = k->mnId;
+  }
+  std::vector<MapPoint*> mps;                                       // the included points (vbNotIncludedMP[i] == false)
+  for (MapPoint* pMP : vpMP) {
+    if (pMP->isBad()) continue;
+    const int i = (int)mps.size();
+    const size_t e0 = e_pose.size();
+    for (const auto& ob : pMP->GetObservations()) {
+      KeyFrame* k = ob.first;
+      if (k->isBad() || k->mnId > maxKFid) continue;                // :520
+      const auto it = kf_index.find(k);
+      if (it == kf_index.end()) continue;                           // no vertex of that id (the reference would hand g2o a null vertex)
+      if (k->mvKeyRays[ob.second](2) < cam->GetCosFovTh()) continue;            // :525
+      const cv::KeyPoint& kp = k->mvKeys[ob.second];
+      double u, v;
+      cam->GetPosInFace(u, v, (double)kp.pt.x, (double)kp.pt.y);
+      e_pose.push_back(it->second); e_point.push_back(i); e_obs.push_back(u); e_obs.push_back(v);
+      e_inv.push_back(k->mvInvLevelSigma2[kp.octave]); e_face.push_back((int8_t)cam->FaceInCubemap(kp.pt));
+    }
+    if (e_pose.size() == e0) continue;                              // :559-563: removed from the graph, never written
+    mps.push_back(pMP);
+    const cv::Mat x = pMP->GetWorldPos();
+    for (int k = 0; k < 3; ++k) points.push_back(x.at<float>(k));
+  }
+  const int K = (int)kfs.size(), P = (int)mps.size(), E = (int)e_pose.size();
+  if (K > 0 && E > 0) {
+    cms_ba* ba = nullptr;
+    check(cms_ba_create(&ba, g_device, K, poses.data(), fixed.data(), P, points.data(), E, e_pose.data(), e_point.data(), e_obs.data(), e_inv.data(), e_face.data(),
+                        cam->Get_fx(), cam->Get_fy(), cam->Get_cx(), cam->Get_cy()), "cms_ba_create");
+    int rc = cms_ba_optimize_global(ba, nIterations, bRobust ? 1 : 0, reinterpret_cast<const volatile uint8_t*>(pbStopFlag), nullptr);      // :570-572
+    if (rc >= 0) { const int rr = cms_ba_read(ba, poses.data(), points.data(), nullptr); if (rr < 0) rc = rr; }
+    cms_ba_destroy(ba);
+    check(rc, "cms_ba_optimize_global");
+  }
+  // ---- :577-619
+  for (int j = 0; j < K; ++j) {
+    if (nLoopKF == 0) kfs[j]->SetPose(toMat(&poses[(size_t)j * 7]));
+    else {
+      kfs[j]->mTcwGBA.create(4, 4, CV_32F);
+      toMat(&poses[(size_t)j * 7]).copyTo(kfs[j]->mTcwGBA);
+      kfs[j]->mnBAGlobalForKF = nLoopKF;
+    }
+  }
+  for (int i = 0; i < P; ++i) {
+    if (nLoopKF == 0) {
+      cv::Mat x(3, 1, CV_32F);
+      for (int k = 0; k < 3; ++k) x.at<float>(k) = (float)points[(size_t)i * 3 + k];
+      mps[i]->SetWorldPos(x);
+      mps[i]->UpdateNormalAndDepth();
+    } else {
+      mps[i]->mPosGBA.create(3, 1, CV_32F);
+      for (int k = 0; k < 3; ++k) mps[i]->mPosGBA.at<float>(k) = (float)points[(size_t)i * 3 + k];
+      mps[i]->mnBAGlobalForKF = nLoopKF;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ LocalMapping on resident key frames
 namespace {
 // The book is read by the tracking thread (SearchByBoW) and written by the mapping thread.  `mu` guards the two containers, and it is also held

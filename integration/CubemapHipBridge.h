@@ -39,6 +39,11 @@ int SearchLocalPoints(cms_ctx* ctx, Frame& F, const std::vector<MapPoint*>& vpMa
 int PoseOptimization(Frame* pFrame);
 // Optimizer::LocalBundleAdjustment (Optimizer.cpp:192-451)
 void LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap);
+// Optimizer::GlobalBundleAdjustemnt / BundleAdjustment (Optimizer.cpp:453-621; Tracking.cpp:514 with 20 iterations, LoopClosing.cpp:649 with 10 and
+// bRobust = false): the whole map as one window, one cms_ba_optimize_global call -- optimize(nIterations), Huber(sqrt(5.99)) if bRobust, no classification;
+// maps beyond the LDS solves factor their reduced camera system with the tiled LDL^T (DESIGN.md "GlobalBundleAdjustemnt").  Write-back as :577-619:
+// nLoopKF == 0 through SetPose / SetWorldPos + UpdateNormalAndDepth, otherwise into mTcwGBA / mPosGBA with mnBAGlobalForKF = nLoopKF.
+void GlobalBundleAdjustemnt(Map* pMap, int nIterations = 5, bool* pbStopFlag = NULL, const unsigned long nLoopKF = 0, const bool bRobust = true);
 // The reference's g2o is single-threaded (ThirdParty/g2o/config.h:4): the same window gives the same bits every time.  SetDeterministic(true) makes every
 // LocalBundleAdjustment call from then on add in a fixed order on the device (cms_ba_set_deterministic: 0.84-0.87 of the default throughput); the default adds with
 // FP64 atomics and its last bits vary from run to run (DESIGN.md section 2 says what it guarantees).
