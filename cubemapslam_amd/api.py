@@ -872,6 +872,15 @@ class KeyframeStore(_Handle):
         o["header"] = hdr; o["nvalid"] = int(misc[0]); o["kp_cnt"] = int(misc[1])
         return o
 
+    def update_map_points(self, slot, feat, mp):
+        """cms_kfstore_update_map_points: (slot, feature, new id) triples into the slots' mp rows, one asynchronous call"""
+        a = [np.ascontiguousarray(v, np.int32).reshape(-1) for v in (slot, feat, mp)]
+        assert len(a[0]) == len(a[1]) == len(a[2])
+        L = lib()
+        L.cms_kfstore_update_map_points.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        pp = lambda v: _p(v) if len(v) else None
+        _chk(L.cms_kfstore_update_map_points(self.h, len(a[0]), pp(a[0]), pp(a[1]), pp(a[2])), "cms_kfstore_update_map_points")
+
     def update_poses(self, slots, R, t, Ow):
         """cms_kfstore_update_poses: poses of resident key frames after a local BA, one asynchronous call"""
         slots = np.ascontiguousarray(slots, np.int32)
@@ -1195,6 +1204,80 @@ class KeyframeStore(_Handle):
         _chk(L.cms_kfstore_search_by_projection(self.h, src_ctx.h, len(jobs), arr, float(th), int(orb_dist), int(check_orientation), _p(nm)),
              "cms_kfstore_search_by_projection")
         return [(k[1][:k[2]], int(nm[i])) for i, k in enumerate(keep)]
+
+
+def _csr(lists):
+    """offsets and the concatenation of a list of int lists (one spare entry: an empty array has no pointer worth passing)"""
+    off = np.zeros(len(lists) + 1, np.int32)
+    off[1:] = np.cumsum([len(x) for x in lists])
+    flat = np.zeros(int(off[-1]) + 1, np.int32)
+    if int(off[-1]):
+        wide = np.concatenate([np.asarray(x, np.int64).reshape(-1) for x in lists if len(x)])
+        if wide.min() < -(1 << 31) or wide.max() >= (1 << 31):
+            raise CmsError("an id or index outside the range of a 32-bit int: %d .. %d" % (int(wide.min()), int(wide.max())))
+        flat[:-1] = wide
+    return off, flat
+
+
+class Covisibility(_Handle):
+    """cms_covis: the observation index over member slots of a KeyframeStore (UpdateConnections, KeyFrameCulling, the local-map votes and points).
+    Members are named by their position in the list build() was given.  Calls on one object are serialised inside the library."""
+    _entries = ("cms_covis_create", "cms_covis_destroy")
+
+    def __init__(self, store, max_members):
+        L = lib()
+        L.cms_covis_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.cms_covis_destroy.argtypes = [C.c_void_p]; L.cms_covis_destroy.restype = None
+        L.cms_covis_build.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.cms_covis_votes.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.cms_covis_connections.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.cms_covis_culling.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3
+        L.cms_covis_local_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self.store = store
+        self.n_members = 0
+        self._create(store.h, int(max_members))
+
+    def build(self, member_slots):
+        """cms_covis_build: snapshot the members' rows as the store holds them now"""
+        s = np.ascontiguousarray(member_slots, np.int32).reshape(-1)
+        _chk(lib().cms_covis_build(self.h, len(s), _p(s) if len(s) else None), "cms_covis_build")
+        self.n_members = len(s)
+
+    def votes(self, src_ctx, id_lists):
+        """cms_covis_votes: per frame the ids of its map points -> votes[njobs, n_members]"""
+        off, ids = _csr(id_lists)
+        out = np.zeros((len(id_lists), self.n_members), np.int32)
+        _chk(lib().cms_covis_votes(self.h, src_ctx.h, len(id_lists), _p(off), _p(ids), _p(out) if out.size else None), "cms_covis_votes")
+        return out
+
+    def connections(self, members, th=15):
+        """cms_covis_connections -> (weights[njobs, M], order[njobs, M] padded with -1, n_connected[njobs])"""
+        m = np.ascontiguousarray(members, np.int32).reshape(-1)
+        shape = (len(m), max(self.n_members, 1))
+        w = np.zeros(shape, np.int32); order = np.full(shape, -1, np.int32); nc = np.zeros(max(len(m), 1), np.int32)
+        _chk(lib().cms_covis_connections(self.h, len(m), _p(m) if len(m) else None, int(th), _p(w), _p(order), _p(nc)), "cms_covis_connections")
+        return w[:, :self.n_members], order[:, :self.n_members], nc[:len(m)]
+
+    def culling(self, chains, erasable, th_obs=3):
+        """cms_covis_culling: chains of candidates (members), erasable flags of the same shape -> (n_mps, n_redundant, redundant) over all jobs"""
+        off, jobs = _csr(chains)
+        er = np.zeros(len(jobs), np.uint8)
+        er[:int(off[-1])] = [int(bool(v)) for x in erasable for v in x]
+        assert sum(len(x) for x in erasable) == int(off[-1])
+        n = max(int(off[-1]), 1)
+        nm = np.zeros(n, np.int32); nr = np.zeros(n, np.int32); red = np.zeros(n, np.uint8)
+        _chk(lib().cms_covis_culling(self.h, len(chains), _p(off), _p(jobs), _p(er), int(th_obs), _p(nm), _p(nr), _p(red)), "cms_covis_culling")
+        return nm[:int(off[-1])], nr[:int(off[-1])], red[:int(off[-1])]
+
+    def local_points(self, src_ctx, member_lists, cap):
+        """cms_covis_local_points -> (code, n_out[njobs], [ids written per job]); the code is 0 or CMS_ERR_OVERFLOW (-4), anything else raises"""
+        off, kfs = _csr(member_lists)
+        nj = len(member_lists)
+        ids = np.full((max(nj, 1), max(int(cap), 1)), -1, np.int32); n_out = np.zeros(max(nj, 1), np.int32)
+        rc = lib().cms_covis_local_points(self.h, src_ctx.h, nj, _p(off), _p(kfs), int(cap), _p(ids), _p(n_out))
+        if rc != -4:
+            _chk(rc, "cms_covis_local_points")
+        return rc, n_out[:nj], [[int(v) for v in ids[j, :min(int(n_out[j]), int(cap))]] for j in range(nj)]
 
 
 def distinctive_descriptors(ctx, obs_off, desc):

@@ -323,10 +323,13 @@ struct CmsStoreKfdb;     // the key-frame database over the slots (cms_api_kfdb.
 static CmsStoreKfdb* cms_store_kfdb_new(int max_keyframes);
 static void cms_store_kfdb_free(CmsStoreKfdb* d);
 static void cms_store_kfdb_refill(CmsStoreKfdb* d, int slot);      // a slot is refilled: the key frame it held leaves the database
+struct CmsStoreMpUpd;    // the pinned ring of cms_kfstore_update_map_points (cms_api_covis.hip), allocated on first use
+static void cms_store_mpupd_free(CmsStoreMpUpd* u);
 struct cms_kfstore {
   cms_ctx* c = nullptr;
   CmsStoreBow* bow = nullptr;
   CmsStoreKfdb* kfdb = nullptr;
+  CmsStoreMpUpd* mpupd = nullptr;
   int maxkf = 0, maxf = 0, maxn = 0;
   CmsTriKF* d_kf = nullptr; CmsKeyPoint* d_kp = nullptr; uint8_t* d_desc = nullptr; float* d_rays = nullptr; int* d_mp = nullptr; int* d_fn = nullptr;
   int* d_nid = nullptr; int* d_noff = nullptr; int* d_nfeat = nullptr;
@@ -372,6 +375,7 @@ extern "C" void cms_kfstore_destroy(cms_kfstore* st) {
   for (void* b : bufs) if (b) (void)hipFree(b);
   cms_store_bow_free(st->bow);
   cms_store_kfdb_free(st->kfdb);
+  cms_store_mpupd_free(st->mpupd);
   if (st->h_ff) (void)hipHostFree(st->h_ff);
   if (st->h_items) (void)hipHostFree(st->h_items);
   if (st->h_upd) (void)hipHostFree(st->h_upd);

@@ -12,6 +12,7 @@
 #include <map>
 #include "../csrc/cms_vocab_core.h"
 #include "../csrc/cms_kfdb_core.h"
+#include "../csrc/cms_covis_core.h"
 #include "../csrc/cms_ess_graph_core.h"      // CmsS3 and Sim3(R, t, s) for vScw
 #include "../csrc/cms_ess_graph_job_check.h" // the envelope count for the handle
 #include "../csrc/cms_sim3_core.h"      // the gemm rule (cms_sim3_row) and TransformRaysToCubemap for the constructor's filter
@@ -1703,6 +1704,154 @@ std::vector<KeyFrameView*> KeyFrameDatabase::DetectRelocalizationCandidates(Fram
 }
 std::vector<KeyFrameView*> KeyFrameDatabase::DetectLoopCandidates(KeyFrameView* pKF, float minScore, const std::vector<KeyFrameView*>& connected) {
   return impl_->detect(engine, CMS_KFDB_LOOP, pKF->mBowVec, minScore, connected);
+}
+
+// ---- Covisibility (src/KeyFrame.cpp:315-404, src/LocalMapping.cpp:561-619, src/Tracking.cpp:855-928)
+struct Covisibility::Impl {
+  Engine engine;
+  int max_keyframes, max_features;
+  CmsCovisHostStore host;                    // HOST_CORE
+  cms_kfstore* store = nullptr;              // DEVICE, made by the first Build
+  cms_covis* cv = nullptr;
+  std::vector<KeyFrameView*> members;
+  std::map<KeyFrameView*, int> pos_of;
+  Impl(Engine e, int K, int Fq) : engine(e), max_keyframes(K), max_features(Fq), host(K, Fq, K) {}
+  cms_ctx* ctx() const {
+    return g_ctx_orb.nfeatures > 0 ? SharedContext(g_ctx_orb.nfeatures, g_ctx_orb.scale_factor, g_ctx_orb.nlevels, g_ctx_orb.ini_th_fast, g_ctx_orb.min_th_fast)
+                                   : SharedContext(2000, 1.2f, 8, 20, 7);
+  }
+  int pos(KeyFrameView* k, const char* who) const {
+    auto it = pos_of.find(k);
+    if (it == pos_of.end()) throw std::runtime_error(std::string(who) + ": the key frame is not a member of the last Build");
+    return it->second;
+  }
+  static void fail(const char* who) { throw std::runtime_error(std::string(who) + " failed: " + cms_last_error()); }
+};
+Covisibility::Covisibility(Engine engine, int max_keyframes, int max_features) : impl_(new Impl(engine, max_keyframes, max_features)) {}
+Covisibility::~Covisibility() {
+  if (impl_->cv) cms_covis_destroy(impl_->cv);
+  if (impl_->store) cms_kfstore_destroy(impl_->store);
+  delete impl_;
+}
+void Covisibility::Build(const std::vector<KeyFrameView*>& members) {
+  Impl& m = *impl_;
+  if ((int)members.size() > m.max_keyframes) throw std::runtime_error("Covisibility::Build: more key frames than max_keyframes");
+  std::map<KeyFrameView*, int> pos_of;
+  std::vector<int> slots(members.size() + 1);
+  for (size_t i = 0; i < members.size(); ++i) {
+    if (!members[i] || pos_of.count(members[i])) throw std::runtime_error("Covisibility::Build: a null key frame, or one listed twice");
+    if ((int)members[i]->mvKeys.size() > m.max_features) throw std::runtime_error("Covisibility::Build: a key frame with more features than max_features");
+    pos_of[members[i]] = (int)i; slots[i] = (int)i;
+  }
+  std::vector<std::vector<int>> rows(members.size());
+  for (size_t i = 0; i < members.size(); ++i) {
+    const KeyFrameView& k = *members[i];
+    rows[i].resize(k.mvKeys.size() + 1);
+    for (size_t f = 0; f < k.mvKeys.size(); ++f) {
+      const bool bad = !k.mvbMapPointBad.empty() && k.mvbMapPointBad[f];
+      rows[i][f] = (k.mvpMapPoints[f] >= 0 && !bad) ? (int)(k.mvpMapPoints[f] & 0x3FFFFFFF) : -1;
+    }
+  }
+  if (m.engine == HOST_CORE) {
+    for (size_t i = 0; i < members.size(); ++i) {
+      std::vector<int> oct(members[i]->mvKeys.size() + 1);
+      for (size_t f = 0; f < members[i]->mvKeys.size(); ++f) oct[f] = members[i]->mvKeys[f].octave;
+      if (m.host.put((int)i, (int)members[i]->mvKeys.size(), rows[i].data(), oct.data())) throw std::runtime_error("Covisibility::Build: bad key frame");
+    }
+    if (m.host.build((int)members.size(), slots.data())) throw std::runtime_error("Covisibility::Build: a key frame names a map point twice");
+  } else {
+    cms_ctx* c = m.ctx();
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!m.store && cms_kfstore_create(&m.store, c, m.max_keyframes, m.max_features, m.max_features) != CMS_OK) Impl::fail("cms_kfstore_create");
+    if (!m.cv && cms_covis_create(&m.cv, m.store, m.max_keyframes) != CMS_OK) Impl::fail("cms_covis_create");
+    for (size_t i = 0; i < members.size(); ++i) {
+      KfPack pack;
+      cms_keyframe k = pack_keyframe(*members[i], pack);
+      k.mp = rows[i].data();
+      if (cms_kfstore_put(m.store, (int)i, &k) != CMS_OK) Impl::fail("cms_kfstore_put");
+    }
+    if (cms_covis_build(m.cv, (int)members.size(), slots.data()) != CMS_OK) Impl::fail("cms_covis_build");
+  }
+  m.members = members; m.pos_of.swap(pos_of);
+}
+Covisibility::Connections Covisibility::UpdateConnections(KeyFrameView* pKF, int th) {
+  Impl& m = *impl_;
+  const int job = m.pos(pKF, "Covisibility::UpdateConnections");
+  const size_t M = m.members.size();
+  std::vector<int> w(M), order(M);
+  int n = 0;
+  if (m.engine == HOST_CORE) {
+    if (m.host.index.connections(1, &job, th, w.data(), order.data(), &n)) throw std::runtime_error("Covisibility::UpdateConnections: bad argument");
+  } else {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (cms_covis_connections(m.cv, 1, &job, th, w.data(), order.data(), &n) != CMS_OK) Impl::fail("cms_covis_connections");
+  }
+  Connections out;
+  for (size_t i = 0; i < M; ++i) if (w[i] > 0) out.weights[m.members[i]] = w[i];
+  for (int i = 0; i < n; ++i) { out.ordered.push_back(m.members[(size_t)order[(size_t)i]]); out.orderedWeights.push_back(w[(size_t)order[(size_t)i]]); }
+  return out;
+}
+std::vector<Covisibility::Culled> Covisibility::KeyFrameCulling(const std::vector<KeyFrameView*>& candidates, const std::vector<bool>& notErase, int thObs) {
+  Impl& m = *impl_;
+  const size_t Q = candidates.size();
+  if (notErase.size() != Q) throw std::runtime_error("Covisibility::KeyFrameCulling: one mbNotErase per candidate");
+  std::vector<int> jobs(Q + 1), nm(Q + 1), nr(Q + 1);
+  std::vector<uint8_t> er(Q + 1), red(Q + 1);
+  for (size_t i = 0; i < Q; ++i) { jobs[i] = m.pos(candidates[i], "Covisibility::KeyFrameCulling"); er[i] = notErase[i] ? 0 : 1; }
+  const int off[2] = {0, (int)Q};
+  if (m.engine == HOST_CORE) {
+    if (m.host.index.culling(1, off, jobs.data(), er.data(), thObs, nm.data(), nr.data(), red.data())) throw std::runtime_error("Covisibility::KeyFrameCulling: a candidate listed twice");
+  } else {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (cms_covis_culling(m.cv, 1, off, jobs.data(), er.data(), thObs, nm.data(), nr.data(), red.data()) != CMS_OK) Impl::fail("cms_covis_culling");
+  }
+  std::vector<Culled> out;
+  for (size_t i = 0; i < Q; ++i) out.push_back(Culled{candidates[i], nm[i], nr[i], red[i] != 0});
+  return out;
+}
+std::vector<KeyFrameView*> Covisibility::UpdateLocalKeyFrames(const std::vector<long>& framePoints, KeyFrameView** pKFmax, std::vector<int>* votes) {
+  Impl& m = *impl_;
+  const size_t M = m.members.size();
+  std::vector<int> ids(framePoints.size() + 1), v(M + 1, 0);
+  for (size_t i = 0; i < framePoints.size(); ++i) {
+    if (framePoints[i] < 0) throw std::runtime_error("Covisibility::UpdateLocalKeyFrames: list the frame's map points, not its empty entries");
+    ids[i] = (int)(framePoints[i] & 0x3FFFFFFF);
+  }
+  const int off[2] = {0, (int)framePoints.size()};
+  if (m.engine == HOST_CORE) {
+    if (m.host.index.votes(1, off, ids.data(), v.data())) throw std::runtime_error("Covisibility::UpdateLocalKeyFrames: bad argument");
+  } else {
+    cms_ctx* c = m.ctx();
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (cms_covis_votes(m.cv, c, 1, off, ids.data(), v.data()) != CMS_OK) Impl::fail("cms_covis_votes");
+  }
+  std::vector<KeyFrameView*> local;
+  int max = 0;
+  if (pKFmax) *pKFmax = nullptr;
+  for (size_t i = 0; i < M; ++i) {      // Tracking.cpp:913-928: the map's order, a strict >
+    if (v[i] == 0) continue;
+    if (v[i] > max) { max = v[i]; if (pKFmax) *pKFmax = m.members[i]; }
+    local.push_back(m.members[i]);
+  }
+  if (votes) votes->assign(v.begin(), v.begin() + (long)M);
+  return local;
+}
+std::vector<long> Covisibility::UpdateLocalPoints(const std::vector<KeyFrameView*>& localKeyFrames) {
+  Impl& m = *impl_;
+  std::vector<int> kfs(localKeyFrames.size() + 1);
+  size_t cap = 1;
+  for (size_t i = 0; i < localKeyFrames.size(); ++i) { kfs[i] = m.pos(localKeyFrames[i], "Covisibility::UpdateLocalPoints"); cap += localKeyFrames[i]->mvKeys.size(); }
+  const int off[2] = {0, (int)localKeyFrames.size()};
+  std::vector<int> ids(cap);
+  int n = 0;
+  if (m.engine == HOST_CORE) {
+    if (m.host.index.local_points(1, off, kfs.data(), (int)cap, ids.data(), &n)) throw std::runtime_error("Covisibility::UpdateLocalPoints: a key frame listed twice");
+  } else {
+    cms_ctx* c = m.ctx();
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (cms_covis_local_points(m.cv, c, 1, off, kfs.data(), (int)cap, ids.data(), &n) != CMS_OK) Impl::fail("cms_covis_local_points");
+  }
+  return std::vector<long>(ids.begin(), ids.begin() + n);
 }
 
 }  // namespace CubemapSLAM

@@ -429,6 +429,42 @@ class KeyFrameDatabase {
   Impl* impl_;
 };
 
+// The covisibility bookkeeping under the reference's names on KeyFrameView handles: KeyFrame::UpdateConnections (KeyFrame.cpp:315-404),
+// LocalMapping::KeyFrameCulling (LocalMapping.cpp:561-619), Tracking::UpdateLocalKeyFrames' votes and max rule (Tracking.cpp:881-928) and
+// Tracking::UpdateLocalPoints (:855-878).  Two engines, an explicit choice and never a fall-back: DEVICE keeps the members in a cms_kfstore on the shared
+// context's device and answers with cms_covis_*; HOST_CORE is the host build of csrc/cms_covis_core.h, the definition of record, no GPU needed.
+// Build() hands over the map's key frames that are not bad, in the order that then decides ties (the reference's pointer order is the allocator's
+// business); a map point is mvpMapPoints[i] >= 0 with mvbMapPointBad[i] == 0, named by its id & 0x3FFFFFFF.  Every method answers from the last Build.
+// This is a parity mirror, not the intended usage: the DEVICE engine keeps a private store and puts EVERY member into it again on each Build (key
+// points, descriptors, rays and the grid build included).  A host that tracks keeps its key frames resident and sends only what changed
+// (cms_kfstore_update_map_points), as the bridge's Hip::BuildCovisibility does.
+class Covisibility {
+ public:
+  enum Engine { DEVICE = 0, HOST_CORE = 1 };
+  explicit Covisibility(Engine engine, int max_keyframes = 256, int max_features = 2048);
+  ~Covisibility();
+  Covisibility(const Covisibility&) = delete;
+  Covisibility& operator=(const Covisibility&) = delete;
+  void Build(const std::vector<KeyFrameView*>& members);
+  // mConnectedKeyFrameWeights (members with weight 0 left out), mvpOrderedConnectedKeyFrames and mvOrderedWeights of pKF; AddConnection on the others,
+  // the parent and the spanning tree stay with the caller
+  struct Connections { std::map<KeyFrameView*, int> weights; std::vector<KeyFrameView*> ordered; std::vector<int> orderedWeights; };
+  Connections UpdateConnections(KeyFrameView* pKF, int th = 15);
+  // one KeyFrameCulling call: the candidates are GetVectorCovisibleKeyFrames() minus mnId == 0 in that order, notErase their mbNotErase.  Per
+  // candidate nMPs, nRedundantObservations and the verdict; SetBadFlag on the redundant ones stays with the caller
+  struct Culled { KeyFrameView* pKF; int nMPs, nRedundantObservations; bool redundant; };
+  std::vector<Culled> KeyFrameCulling(const std::vector<KeyFrameView*>& candidates, const std::vector<bool>& notErase, int thObs = 3);
+  // the frame's non-NULL, non-bad map points as ids: the key frames with a vote in member order (mvpLocalKeyFrames before the neighbours are added),
+  // their votes, and pKFmax (NULL: keyframeCounter is empty)
+  std::vector<KeyFrameView*> UpdateLocalKeyFrames(const std::vector<long>& framePoints, KeyFrameView** pKFmax, std::vector<int>* votes = nullptr);
+  // mvpLocalMapPoints as ids
+  std::vector<long> UpdateLocalPoints(const std::vector<KeyFrameView*>& localKeyFrames);
+
+ private:
+  struct Impl;
+  Impl* impl_;
+};
+
 
 class LocalMapping {
  public:

@@ -6,6 +6,7 @@
 #include "io_formats.h"
 #include "../csrc/cms_vocab_core.h"
 #include "../csrc/cms_kfdb_core.h"
+#include "../csrc/cms_covis_core.h"
 using namespace CubemapSLAM;
 
 static thread_local std::string g_err;
@@ -917,6 +918,102 @@ extern "C" int hm_kfdb_bow_score(void* db, int npairs, const int* slot_a, const 
 extern "C" int hm_kfdb_score(int n1, const int* id1, const double* val1, int n2, const int* id2, const double* val2, double* out) {
   *out = cms_kfdb_score_host(CmsKfdbBow{n1, id1, val1}, CmsKfdbBow{n2, id2, val2});
   return 0;
+}
+
+// ---- Covisibility (tests/covis_hostlib.py): the host build of csrc/cms_covis_core.h, the definition of record of cms_covis_*.  The calls mirror the
+// C-ABI's on a handle of its own that also stands in for the store's rows (hm_covis_put: a slot's mp row and octaves); they return 0, -1
+// (CMS_ERR_ARG), -3 (CMS_ERR_UNSUPPORTED) or -4 (CMS_ERR_OVERFLOW).
+extern "C" int hm_covis_create(void** out, int max_keyframes, int max_features, int max_members) {
+  HM_TRY(
+    if (!out || max_keyframes < 1 || max_features < 1 || max_members < 1) throw std::runtime_error("hm_covis_create: bad argument");
+    *out = new CmsCovisHostStore(max_keyframes, max_features, max_members);
+    return 0;)
+}
+extern "C" void hm_covis_destroy(void* cv) { delete static_cast<CmsCovisHostStore*>(cv); }
+extern "C" int hm_covis_put(void* cv, int slot, int n, const int* mp, const int* octave) { HM_TRY(return static_cast<CmsCovisHostStore*>(cv)->put(slot, n, mp, octave);) }
+extern "C" int hm_covis_update_map_points(void* cv, int n, const int* slot, const int* feat, const int* mp) {
+  HM_TRY(return static_cast<CmsCovisHostStore*>(cv)->update_map_points(n, slot, feat, mp);)
+}
+extern "C" int hm_covis_fetch_mp(void* cv, int slot, int* mp) {
+  HM_TRY(
+    CmsCovisHostStore* d = static_cast<CmsCovisHostStore*>(cv);
+    if (!d->slot_ok(slot) || !d->slots[(size_t)slot].used) return -1;
+    std::copy(d->slots[(size_t)slot].mp.begin(), d->slots[(size_t)slot].mp.end(), mp);
+    return 0;)
+}
+extern "C" int hm_covis_build(void* cv, int n_members, const int* member_slots) { HM_TRY(return static_cast<CmsCovisHostStore*>(cv)->build(n_members, member_slots);) }
+extern "C" int hm_covis_votes(void* cv, int njobs, const int* id_off, const int* ids, int* votes) {
+  HM_TRY(return static_cast<CmsCovisHostStore*>(cv)->index.votes(njobs, id_off, ids, votes);)
+}
+extern "C" int hm_covis_connections(void* cv, int njobs, const int* job_member, int th, int* weights, int* order, int* n_connected) {
+  HM_TRY(return static_cast<CmsCovisHostStore*>(cv)->index.connections(njobs, job_member, th, weights, order, n_connected);)
+}
+extern "C" int hm_covis_culling(void* cv, int n_chains, const int* chain_off, const int* job_member, const uint8_t* erasable, int th_obs, int* n_mps, int* n_redundant,
+                                uint8_t* redundant) {
+  HM_TRY(return static_cast<CmsCovisHostStore*>(cv)->index.culling(n_chains, chain_off, job_member, erasable, th_obs, n_mps, n_redundant, redundant);)
+}
+extern "C" int hm_covis_local_points(void* cv, int njobs, const int* kf_off, const int* kf_members, int cap, int* ids_out, int* n_out) {
+  HM_TRY(return static_cast<CmsCovisHostStore*>(cv)->index.local_points(njobs, kf_off, kf_members, cap, ids_out, n_out);)
+}
+
+// CubemapSLAM::Covisibility of the mirror through the named engine (0 = device, 1 = host core): n_kf key frames of n_feat[k] features (mp and octave rows
+// concatenated) are the members; then UpdateConnections for conn_kf[0, n_conn) (the ordered key frames of all, concatenated, into `ordered` with
+// their weights; n_ordered[i] each), ONE KeyFrameCulling over cull_kf[0, n_cull) with not_erase (nMPs, nRedundantObservations, verdict),
+// UpdateLocalKeyFrames for the frame's ids (the local key frames into local_kf, n_local, pKFmax as an index or -1) and UpdateLocalPoints over
+// lp_kf[0, n_lp) (ids into lp_ids, cap lp_cap, n_lp_ids).
+extern "C" int hm_covis_mirror(int engine, int n_kf, const int* n_feat, const int* mp, const int* octave, int n_conn, const int* conn_kf, int* ordered, int* ordered_w,
+                               int* n_ordered, int n_cull, const int* cull_kf, const uint8_t* not_erase, int* cull_nmps, int* cull_nred, uint8_t* cull_red, int n_ids,
+                               const int* ids, int* local_kf, int* n_local, int* kf_max, int n_lp, const int* lp_kf, int lp_cap, int* lp_ids, int* n_lp_ids) {
+  HM_TRY(
+    std::vector<KeyFrameView> kfs((size_t)n_kf);
+    std::vector<KeyFrameView*> members;
+    int max_feat = 1;
+    size_t at = 0;
+    for (int k = 0; k < n_kf; ++k) {
+      KeyFrameView& v = kfs[(size_t)k];
+      const int n = n_feat[k];
+      max_feat = std::max(max_feat, n);
+      v.mnId = k + 1;
+      v.mDescriptors = cv::Mat::zeros(std::max(n, 1), 32, cv::CV_8U);
+      v.mvKeys.resize((size_t)n);
+      cv::Vec3f ray;
+      ray.v[0] = 0.f; ray.v[1] = 0.f; ray.v[2] = 1.f;
+      v.mvKeyRays.assign((size_t)n, ray);
+      v.mvpMapPoints.resize((size_t)n);
+      for (int f = 0; f < n; ++f) {
+        v.mvKeys[(size_t)f].pt.x = 10.f + (float)(f % 100); v.mvKeys[(size_t)f].pt.y = 10.f + (float)(f / 100); v.mvKeys[(size_t)f].octave = octave[at + (size_t)f];
+        v.mvpMapPoints[(size_t)f] = mp[at + (size_t)f];
+      }
+      at += (size_t)n;
+      v.Tcw = cv::Mat::zeros(4, 4, cv::CV_32F);
+      for (int r = 0; r < 4; ++r) v.Tcw.at<float>(r, r) = 1.f;
+      members.push_back(&v);
+    }
+    auto index_of = [&](KeyFrameView* k) { return (int)(k - kfs.data()); };
+    Covisibility cvs(engine ? Covisibility::HOST_CORE : Covisibility::DEVICE, n_kf + 1, max_feat);
+    cvs.Build(members);
+    size_t o = 0;
+    for (int i = 0; i < n_conn; ++i) {
+      const Covisibility::Connections c = cvs.UpdateConnections(&kfs[(size_t)conn_kf[i]]);
+      n_ordered[i] = (int)c.ordered.size();
+      for (size_t q = 0; q < c.ordered.size(); ++q, ++o) { ordered[o] = index_of(c.ordered[q]); ordered_w[o] = c.orderedWeights[q]; }
+    }
+    std::vector<KeyFrameView*> cand;
+    std::vector<bool> ne;
+    for (int i = 0; i < n_cull; ++i) { cand.push_back(&kfs[(size_t)cull_kf[i]]); ne.push_back(not_erase[i] != 0); }
+    const std::vector<Covisibility::Culled> cu = cvs.KeyFrameCulling(cand, ne);
+    for (size_t i = 0; i < cu.size(); ++i) { cull_nmps[i] = cu[i].nMPs; cull_nred[i] = cu[i].nRedundantObservations; cull_red[i] = cu[i].redundant ? 1 : 0; }
+    KeyFrameView* best = nullptr;
+    const std::vector<KeyFrameView*> local = cvs.UpdateLocalKeyFrames(std::vector<long>(ids, ids + n_ids), &best);
+    *n_local = (int)local.size();
+    for (size_t i = 0; i < local.size(); ++i) local_kf[i] = index_of(local[i]);
+    *kf_max = best ? index_of(best) : -1;
+    std::vector<KeyFrameView*> lp;
+    for (int i = 0; i < n_lp; ++i) lp.push_back(&kfs[(size_t)lp_kf[i]]);
+    const std::vector<long> pts = cvs.UpdateLocalPoints(lp);
+    *n_lp_ids = (int)pts.size();
+    for (size_t i = 0; i < pts.size() && (int)i < lp_cap; ++i) lp_ids[i] = (int)pts[i];
+    return 0;)
 }
 
 // ORB_SLAM2::KeyFrameDatabase of the mirror through the named engine (0 = device, 1 = host core): n_kf key frames of n_feat descriptors each enter in

@@ -1048,6 +1048,54 @@ int cms_pose_fetch(cms_pose* p, double* poses7, uint8_t* outlier, int* n_inliers
 int cms_pose_optimize(int device, int n, const double* Xw, const double* obs_uv, const double* inv_sigma2, const int8_t* face,
                       double fx, double fy, double cx, double cy, double* pose7, uint8_t* outlier, int* n_inliers, cms_pose_stats* stats);
 
+/* ---- Covisibility on resident key frames: KeyFrame::UpdateConnections (src/KeyFrame.cpp:315-404), LocalMapping::KeyFrameCulling
+ * (src/LocalMapping.cpp:561-619), the votes of Tracking::UpdateLocalKeyFrames (src/Tracking.cpp:881-928) and Tracking::UpdateLocalPoints (:855-878).
+ * The definition of record is csrc/cms_covis_core.h (DESIGN.md "Covisibility on the device"): one source, built for the host (hm_covis_* of
+ * libcubemapslam_host.so) and for the kernels.  Everything is integer work: the results equal the host core's exactly.
+ *
+ * A cms_covis is an OBSERVATION INDEX over a list of member slots of one store: the key frames of one map that are not bad, in the caller's order.
+ * An observation is (id, member position, feature, octave) for every feature of a member with mp >= 0 (ids in [0, 2^30)); Observations(id) is the
+ * number of members holding the id (MapPoint::nObs).  A member is named by its POSITION in the list in every query and result.
+ * Threading: calls on one cms_covis are serialised by a mutex in the handle; the store must outlive it.
+ *
+ * cms_covis_build snapshots the members' mp rows and octaves as the store holds them at that moment (on the store's stream, behind pending puts and
+ * updates) and builds the index from the snapshot.  Every query answers from the last successful build: a later cms_kfstore_update* is not seen until
+ * the next build.  CMS_ERR_ARG: an empty slot, a slot named twice, more members than max_members, or a row that names an id twice
+ * (MapPoint::AddObservation's invariant) -- then the previous index stays in place.  CMS_ERR_UNSUPPORTED: more than 16 384 members. */
+typedef struct cms_covis cms_covis;
+int cms_covis_create(cms_covis** out, cms_kfstore* st, int max_members);
+void cms_covis_destroy(cms_covis* cv);
+int cms_covis_build(cms_covis* cv, int n_members, const int* member_slots);
+/* keyframeCounter (Tracking.cpp:885-901) of njobs frames in one launch: job j lists the ids of its frame's non-NULL, non-bad map points in
+ * ids[id_off[j], id_off[j + 1]); votes[j * n_members + m] is the number of entries that member m observes.  An id listed twice counts twice (the
+ * reference loops over key points), an id the index does not know adds nothing, a negative id is CMS_ERR_ARG.  On src's stream (the frame thread's),
+ * which waits on the device for the last build. */
+int cms_covis_votes(cms_covis* cv, cms_ctx* src, int njobs, const int* id_off, const int* ids, int* votes);
+/* UpdateConnections up to the pointer work (KeyFrame.cpp:317-394) for the members job_member[j]: weights[j * n_members + m] is KFcounter (ids
+ * shared with member m, 0 for the member itself); order[j * n_members + i] lists the members with weight >= th (15 in the reference) in descending
+ * weight, ties to the EARLIER member position (the reference sorts pair<int, KeyFrame*>: the pointer decides there), -1 behind them.  Nobody reaches
+ * th: the single member of maximal weight, the earliest such (:374-378).  An empty KFcounter: n_connected[j] = 0 (:349).  The first N entries are
+ * GetBestCovisibilityKeyFrames(N).  AddConnection on the others, the parent and the spanning tree stay host code.  On the store's stream. */
+int cms_covis_connections(cms_covis* cv, int njobs, const int* job_member, int th, int* weights, int* order, int* n_connected);
+/* KeyFrameCulling's counters (LocalMapping.cpp:569-618).  Chain c lists the candidates of ONE KeyFrameCulling call in the reference's order
+ * (GetVectorCovisibleKeyFrames() minus mnId == 0) as job_member[chain_off[c], chain_off[c + 1]); chains are independent.  Per job: n_mps the
+ * features with a live id, n_redundant those with Observations(id) > th_obs (3) that at least th_obs OTHER live members observe at
+ * octave_i <= octave + 1 (:588-610), redundant = (double)n_redundant > 0.9 * (double)n_mps (:616).  The jobs of a chain are evaluated as if one
+ * after the other: a redundant job with erasable[j] != 0 (!mbNotErase) leaves before the next one, each of its ids loses an observation, and an id
+ * that falls to <= 2 becomes bad and vanishes from every member (MapPoint.cpp:115-136, KeyFrame.cpp:494-496).  All of that lives in scratch of the
+ * call: the index is unchanged afterwards; the caller applies SetBadFlag on the host and rebuilds.  A member twice in a chain is CMS_ERR_ARG.  On the
+ * store's stream. */
+int cms_covis_culling(cms_covis* cv, int n_chains, const int* chain_off, const int* job_member, const uint8_t* erasable, int th_obs, int* n_mps,
+                      int* n_redundant, uint8_t* redundant);
+/* UpdateLocalPoints (Tracking.cpp:857-877): job j lists its local key frames as members in kf_members[kf_off[j], kf_off[j + 1]) (each once);
+ * ids_out[j * cap + i] are the ids of their rows in member order, then feature order, each id once at its first occurrence; n_out[j] their number.
+ * More than cap: CMS_ERR_OVERFLOW with n_out delivered and the first cap ids written.  Stream rules of cms_covis_votes. */
+int cms_covis_local_points(cms_covis* cv, cms_ctx* src, int njobs, const int* kf_off, const int* kf_members, int cap, int* ids_out, int* n_out);
+/* n (slot, feature, new id) triples into the slots' mp rows (ORBMatcher::Fuse's Replace, MapPointCulling: a handful of entries in many key frames),
+ * id in [-1, 2^30): one kernel reading a pinned block, asynchronous on the store's stream like cms_kfstore_update_poses.  All triples are checked
+ * first (a (slot, feature) named twice is CMS_ERR_ARG): on an error nothing is written. */
+int cms_kfstore_update_map_points(cms_kfstore* st, int n, const int* slot, const int* feat, const int* mp);
+
 #ifdef __cplusplus
 }
 #endif

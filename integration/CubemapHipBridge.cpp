@@ -345,7 +345,9 @@ namespace {
 // The book is read by the tracking thread (SearchByBoW) and written by the mapping thread.  `mu` guards the two containers, and it is also held
 // across every host call that refills or updates a slot (cms_kfstore_put_from_frame, cms_kfstore_update) and across a whole search, so a slot a
 // search names is never released, refilled or updated while the search runs (the threading contract of cms_kfstore_search_by_bow).
-struct StoreBook { std::map<KeyFrame*, int> slot; std::vector<int> free_slots; int max_features = 0; std::mutex mu; };
+// dev_mp: the map-point row each slot holds on the device, as the bridge last sent it (every upload of a row goes through here), so that
+// Hip::BuildCovisibility sends only the entries that changed since
+struct StoreBook { std::map<KeyFrame*, int> slot; std::vector<int> free_slots; int max_features = 0; std::map<int, std::vector<int> > dev_mp; std::mutex mu; };
 std::map<cms_kfstore*, StoreBook> g_books;      // (std::map: a StoreBook never moves once created)
 std::mutex g_books_mutex;
 StoreBook& book(cms_kfstore* st) { std::lock_guard<std::mutex> lk(g_books_mutex); return g_books[st]; }
@@ -359,11 +361,23 @@ void pose_floats(KeyFrame* k, float* R9, float* t3, float* O3) {
   const cv::Mat R = k->GetRotation(), t = k->GetTranslation(), O = k->GetCameraCenter();
   for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) R9[3 * r + c] = R.at<float>(r, c); t3[r] = t.at<float>(r); O3[r] = O.at<float>(r); }
 }
-// the map-point slot per key point as the device holds it: >= 0 where the key point holds a point that is not bad (the id only has to be >= 0)
+// the map-point slot per key point as the device holds it: the point's id & 0x3FFFFFFF where the key point holds a point that is not bad.  A row names
+// an id once (the observation index refuses a row that repeats one): where two key points hold the same point, the one the point itself names
+// (GetIndexInKeyFrame) keeps it
 void mp_slots(KeyFrame* k, std::vector<int>& mp) {
   const std::vector<MapPoint*> v = k->GetMapPointMatches();
   mp.assign(v.size(), -1);
-  for (size_t i = 0; i < v.size(); ++i) if (v[i] && !v[i]->isBad()) mp[i] = (int)(v[i]->mnId & 0x3FFFFFFF);
+  std::map<MapPoint*, int> kept;      // the key point that holds the point's id so far
+  for (size_t i = 0; i < v.size(); ++i) {
+    if (!v[i] || v[i]->isBad()) continue;
+    const auto it = kept.find(v[i]);
+    if (it != kept.end()) {           // the row would repeat the id: the key point the point names keeps it, else the first one
+      if (v[i]->GetIndexInKeyFrame(k) != (int)i) continue;
+      mp[(size_t)it->second] = -1;
+    }
+    kept[v[i]] = (int)i;
+    mp[i] = (int)(v[i]->mnId & 0x3FFFFFFF);
+  }
 }
 // a map point as the Fuse search reads it (ORBMatcher.cpp:1140-1175)
 void push_point(MapPoint* p, std::vector<float>& pos, std::vector<float>& nrm, std::vector<float>& dmin, std::vector<float>& dmax, std::vector<uint8_t>& desc) {
@@ -404,6 +418,7 @@ int ProcessNewKeyFrame(cms_kfstore* store, cms_ctx* frameCtx, KeyFrame* pKF) {
   pose_floats(pKF, R, t, O);
   check(cms_kfstore_put_from_frame(store, slot, frameCtx, 0, pKF->N, R, t, O, pKF->ComputeSceneMedianDepth(2), mp.data(), (int)node_id.size(), node_id.data(),
                                    node_off.data(), node_feat.data()), "cms_kfstore_put_from_frame");
+  b.dev_mp[slot] = mp;
   return slot;
 }
 
@@ -417,6 +432,7 @@ void ReleaseKeyFrame(cms_kfstore* store, KeyFrame* pKF) {
     std::lock_guard<std::mutex> lk2(d.mu);
     if (d.in_db.erase(pKF)) check(cms_kfdb_erase(store, 1, &it->second), "cms_kfdb_erase");
   }
+  b.dev_mp.erase(it->second);
   b.free_slots.push_back(it->second);
   b.slot.erase(it);
 }
@@ -437,6 +453,7 @@ int CreateNewMapPoints(cms_kfstore* store, KeyFrame* pCurrentKF, Map* pMap, std:
     {
       std::lock_guard<std::mutex> lk(b.mu);
       check(cms_kfstore_update(store, s, R, t, O, &md, mp.data()), "cms_kfstore_update");
+      b.dev_mp[s] = mp;
     }
     neigh.push_back(k); neigh_slot.push_back(s);
   }
@@ -445,6 +462,7 @@ int CreateNewMapPoints(cms_kfstore* store, KeyFrame* pCurrentKF, Map* pMap, std:
     pose_floats(pCurrentKF, R, t, O); mp_slots(pCurrentKF, mp);
     std::lock_guard<std::mutex> lk(b.mu);
     check(cms_kfstore_update(store, cur, R, t, O, nullptr, mp.data()), "cms_kfstore_update");
+    b.dev_mp[cur] = mp;
   }
   if (neigh.empty()) return 0;
   const int cap = pCurrentKF->N;
@@ -471,7 +489,16 @@ int CreateNewMapPoints(cms_kfstore* store, KeyFrame* pCurrentKF, Map* pMap, std:
   return n_new;
 }
 
+namespace {
+void search_in_neighbors_fuse(cms_kfstore* store, KeyFrame* pCurrentKF);
+}
 void SearchInNeighbors(cms_kfstore* store, KeyFrame* pCurrentKF) {
+  search_in_neighbors_fuse(store, pCurrentKF);
+  pCurrentKF->UpdateConnections();
+}
+namespace {
+// LocalMapping.cpp:388-463: everything of SearchInNeighbors but the final UpdateConnections
+void search_in_neighbors_fuse(cms_kfstore* store, KeyFrame* pCurrentKF) {
   StoreBook& b = book(store);
   const int cur = slot_of(b, pCurrentKF);
   if (cur < 0) throw std::runtime_error("Hip::SearchInNeighbors: the current key frame is not resident");
@@ -540,7 +567,157 @@ void SearchInNeighbors(cms_kfstore* store, KeyFrame* pCurrentKF) {
   // ---- update points and connections (LocalMapping.cpp:449-465)
   for (MapPoint* p : pCurrentKF->GetMapPointMatches())
     if (p && !p->isBad()) { p->ComputeDistinctiveDescriptors(); p->UpdateNormalAndDepth(); }
-  pCurrentKF->UpdateConnections();
+}
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------ Covisibility on the device
+namespace {
+// the members of a cms_covis as of its last build, and the map points behind the ids of their rows
+struct CovisBook { std::vector<KeyFrame*> members; std::map<KeyFrame*, int> pos; std::map<int, MapPoint*> point; std::mutex mu; };
+std::map<cms_covis*, CovisBook> g_covis_books;
+std::mutex g_covis_books_mutex;
+CovisBook& covis_book(cms_covis* cv) { std::lock_guard<std::mutex> lk(g_covis_books_mutex); return g_covis_books[cv]; }
+int member_of(CovisBook& c, KeyFrame* k) { const auto it = c.pos.find(k); return it == c.pos.end() ? -1 : it->second; }      // c.mu held
+}  // namespace
+
+cms_covis* CreateCovisibility(cms_kfstore* store, int maxKeyFrames) {
+  cms_covis* cv = nullptr;
+  check(cms_covis_create(&cv, store, maxKeyFrames), "cms_covis_create");
+  return cv;
+}
+
+void BuildCovisibility(cms_kfstore* store, cms_covis* covis, const std::vector<KeyFrame*>& vpKFs) {
+  StoreBook& b = book(store);
+  CovisBook& c = covis_book(covis);
+  std::lock_guard<std::mutex> lkc(c.mu);
+  c.members.clear(); c.pos.clear(); c.point.clear();
+  std::vector<int> slots, up_slot, up_feat, up_mp;      // the members; the (slot, feature, id) entries that differ from what the device holds
+  std::lock_guard<std::mutex> lk(b.mu);
+  for (KeyFrame* k : vpKFs) {
+    if (!k || k->isBad() || c.pos.count(k)) continue;
+    const int s = slot_locked(b, k);
+    if (s < 0) continue;
+    std::vector<int> mp;
+    mp_slots(k, mp);
+    const std::vector<MapPoint*> v = k->GetMapPointMatches();
+    for (size_t i = 0; i < v.size(); ++i) if (mp[i] >= 0) c.point[mp[i]] = v[i];
+    std::vector<int>& have = b.dev_mp[s];
+    if (have.size() != mp.size()) {                     // a row the bridge has no record of: the whole row, once
+      check(cms_kfstore_update(store, s, nullptr, nullptr, nullptr, nullptr, mp.data()), "cms_kfstore_update");
+    } else {
+      for (size_t i = 0; i < mp.size(); ++i)
+        if (mp[i] != have[i]) { up_slot.push_back(s); up_feat.push_back((int)i); up_mp.push_back(mp[i]); }
+    }
+    have.swap(mp);
+    c.pos[k] = (int)c.members.size(); c.members.push_back(k); slots.push_back(s);
+  }
+  // Fuse's Replace, MapPointCulling, new points: a handful of entries in many key frames -- ONE asynchronous scatter, no copy and no wait per key frame
+  if (!up_slot.empty())
+    check(cms_kfstore_update_map_points(store, (int)up_slot.size(), up_slot.data(), up_feat.data(), up_mp.data()), "cms_kfstore_update_map_points");
+  check(cms_covis_build(covis, (int)slots.size(), slots.data()), "cms_covis_build");
+}
+
+Connections UpdateConnections(cms_kfstore* store, cms_covis* covis, KeyFrame* pKF) {
+  (void)store;
+  CovisBook& c = covis_book(covis);
+  std::lock_guard<std::mutex> lk(c.mu);
+  const int job = member_of(c, pKF);
+  if (job < 0) throw std::runtime_error("Hip::UpdateConnections: the key frame is not a member of the last Hip::BuildCovisibility");
+  const size_t M = c.members.size();
+  std::vector<int> w(M), order(M);
+  int n = 0;
+  check(cms_covis_connections(covis, 1, &job, 15, w.data(), order.data(), &n), "cms_covis_connections");
+  Connections out;
+  for (size_t m = 0; m < M; ++m) if (w[m] > 0) out.weights[c.members[m]] = w[m];      // KFcounter (:338-346)
+  for (int i = 0; i < n; ++i) {
+    KeyFrame* k = c.members[(size_t)order[(size_t)i]];
+    k->AddConnection(pKF, w[(size_t)order[(size_t)i]]);                               // :370, :377
+    out.ordered.push_back(k); out.orderedWeights.push_back(w[(size_t)order[(size_t)i]]);
+  }
+  return out;
+}
+
+Connections SearchInNeighbors(cms_kfstore* store, cms_covis* covis, KeyFrame* pCurrentKF) {
+  search_in_neighbors_fuse(store, pCurrentKF);
+  return UpdateConnections(store, covis, pCurrentKF);
+}
+
+std::vector<KeyFrame*> KeyFrameCulling(cms_kfstore* store, cms_covis* covis, KeyFrame* pCurrentKF, const std::vector<KeyFrame*>& vpNotErase) {
+  (void)store;
+  CovisBook& c = covis_book(covis);
+  std::vector<KeyFrame*> cand;
+  std::vector<int> jobs;
+  std::vector<uint8_t> erasable;
+  {
+    std::lock_guard<std::mutex> lk(c.mu);
+    const std::set<KeyFrame*> keep(vpNotErase.begin(), vpNotErase.end());
+    for (KeyFrame* k : pCurrentKF->GetVectorCovisibleKeyFrames()) {
+      if (k->mnId == 0) continue;                                                     // :572
+      const int m = member_of(c, k);
+      if (m < 0) continue;
+      cand.push_back(k); jobs.push_back(m); erasable.push_back(keep.count(k) ? 0 : 1);
+    }
+  }
+  std::vector<KeyFrame*> culled;
+  if (cand.empty()) return culled;
+  const int off[2] = {0, (int)jobs.size()};
+  std::vector<int> n_mps(jobs.size()), n_red(jobs.size());
+  std::vector<uint8_t> red(jobs.size());
+  check(cms_covis_culling(covis, 1, off, jobs.data(), erasable.data(), 3, n_mps.data(), n_red.data(), red.data()), "cms_covis_culling");
+  for (size_t i = 0; i < cand.size(); ++i)
+    if (red[i]) { cand[i]->SetBadFlag(); culled.push_back(cand[i]); }                 // :616-617 (SetBadFlag honours mbNotErase itself)
+  return culled;
+}
+
+void UpdateLocalMap(cms_covis* covis, cms_ctx* frameCtx, Frame& F, std::vector<KeyFrame*>& vpLocalKeyFrames, KeyFrame*& pKFmax, std::vector<MapPoint*>& vpLocalMapPoints) {
+  CovisBook& c = covis_book(covis);
+  std::lock_guard<std::mutex> lk(c.mu);
+  vpLocalKeyFrames.clear(); vpLocalMapPoints.clear(); pKFmax = NULL;
+  // ---- the votes (Tracking.cpp:885-901)
+  std::vector<int> ids;
+  for (int i = 0; i < F.N; ++i) {
+    MapPoint* p = F.mvpMapPoints[i];
+    if (!p) continue;
+    if (p->isBad()) { F.mvpMapPoints[i] = NULL; continue; }
+    ids.push_back((int)(p->mnId & 0x3FFFFFFF));
+  }
+  const size_t M = c.members.size();
+  std::vector<int> votes(M + 1, 0);
+  const int id_off[2] = {0, (int)ids.size()};
+  ids.push_back(0);
+  check(cms_covis_votes(covis, frameCtx, 1, id_off, ids.data(), votes.data()), "cms_covis_votes");
+  // ---- :903-928 in member order, then the neighbours of :930-981 on the pointer graph
+  int max = 0;
+  std::set<KeyFrame*> in;
+  for (size_t m = 0; m < M; ++m) {
+    if (votes[m] == 0 || c.members[m]->isBad()) continue;
+    if (votes[m] > max) { max = votes[m]; pKFmax = c.members[m]; }
+    vpLocalKeyFrames.push_back(c.members[m]); in.insert(c.members[m]);
+  }
+  if (vpLocalKeyFrames.empty()) return;                                               // keyframeCounter.empty() (:903)
+  for (size_t i = 0; i < vpLocalKeyFrames.size(); ++i) {
+    if (vpLocalKeyFrames.size() > 80) break;
+    KeyFrame* pKF = vpLocalKeyFrames[i];
+    for (KeyFrame* n : pKF->GetBestCovisibilityKeyFrames(10))
+      if (!n->isBad() && in.insert(n).second) { vpLocalKeyFrames.push_back(n); break; }
+    for (KeyFrame* ch : pKF->GetChilds())
+      if (!ch->isBad() && in.insert(ch).second) { vpLocalKeyFrames.push_back(ch); break; }
+    KeyFrame* pParent = pKF->GetParent();
+    if (pParent && in.insert(pParent).second) { vpLocalKeyFrames.push_back(pParent); break; }      // (:971-978: the reference's break leaves the loop)
+  }
+  // ---- UpdateLocalPoints (:857-877) over the local key frames that are members
+  std::vector<int> kfs;
+  size_t cap = 1;
+  for (KeyFrame* k : vpLocalKeyFrames) { const int m = member_of(c, k); if (m >= 0) { kfs.push_back(m); cap += (size_t)k->N; } }
+  const int kf_off[2] = {0, (int)kfs.size()};
+  kfs.push_back(0);
+  std::vector<int> out(cap);
+  int n = 0;
+  check(cms_covis_local_points(covis, frameCtx, 1, kf_off, kfs.data(), (int)cap, out.data(), &n), "cms_covis_local_points");
+  for (int i = 0; i < n; ++i) {
+    const auto it = c.point.find(out[(size_t)i]);
+    if (it != c.point.end() && !it->second->isBad()) vpLocalMapPoints.push_back(it->second);
+  }
 }
 
 void UpdateKeyFramePoses(cms_kfstore* store, const std::vector<KeyFrame*>& vpKFs) {

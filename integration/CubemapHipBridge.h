@@ -69,6 +69,28 @@ int CreateNewMapPoints(cms_kfstore* store, KeyFrame* pCurrentKF, Map* pMap, std:
 void SearchInNeighbors(cms_kfstore* store, KeyFrame* pCurrentKF);
 // after Optimizer::LocalBundleAdjustment's write-back (Optimizer.cpp:419-431): the resident copies of the local key frames get their new poses
 void UpdateKeyFramePoses(cms_kfstore* store, const std::vector<KeyFrame*>& vpKFs);
+// ---- Covisibility on the device (cms_covis_*): the observation index over the resident key frames of ONE map.  BuildCovisibility hands over the map's
+// key frames (mpMap->GetAllKeyFrames(); bad or non-resident ones are left out), sends the entries of their map-point rows that changed since the bridge last uploaded them (ONE cms_kfstore_update_map_points) and builds the index; the
+// order of vpKFs is the member order, which decides ties where the reference lets the pointer decide.  Every function below answers from the last
+// BuildCovisibility of `covis`: call it after the map-point bookkeeping of the step (ProcessNewKeyFrame's AddObservation loop, Fuse) and before them.
+cms_covis* CreateCovisibility(cms_kfstore* store, int maxKeyFrames);
+void BuildCovisibility(cms_kfstore* store, cms_covis* covis, const std::vector<KeyFrame*>& vpKFs);
+// KeyFrame::UpdateConnections (KeyFrame.cpp:315-404) for a member: KFcounter, the ordered key frames and weights from the device; AddConnection on the
+// key frames that reach th = 15 (or on the one of maximal weight, :370, :377) is done here.  What remains are the assignments under mMutexConnections
+// (:389-402), which touch protected members: the maintainer gives KeyFrame a three-line setter that takes this struct (integration/README.md).  The
+// overload of SearchInNeighbors ends in this function instead of pKF->UpdateConnections() and returns its result.
+struct Connections { std::map<KeyFrame*, int> weights; std::vector<KeyFrame*> ordered; std::vector<int> orderedWeights; };
+Connections UpdateConnections(cms_kfstore* store, cms_covis* covis, KeyFrame* pKF);
+Connections SearchInNeighbors(cms_kfstore* store, cms_covis* covis, KeyFrame* pCurrentKF);
+// LocalMapping::KeyFrameCulling (LocalMapping.cpp:561-619) for pCurrentKF->GetVectorCovisibleKeyFrames(): the counters of the whole chain in one device
+// call, cascade included, then pKF->SetBadFlag() on the redundant ones in the reference's order.  vpNotErase: the key frames whose mbNotErase is set
+// (LoopClosing::SetNotErase holds them; the flag itself is protected).  Returns the key frames SetBadFlag was called on.
+std::vector<KeyFrame*> KeyFrameCulling(cms_kfstore* store, cms_covis* covis, KeyFrame* pCurrentKF, const std::vector<KeyFrame*>& vpNotErase = std::vector<KeyFrame*>());
+// Tracking::UpdateLocalKeyFrames' votes and maximum (Tracking.cpp:884-928) and Tracking::UpdateLocalPoints (:855-878) for the frame `frameCtx` tracks:
+// vpLocalKeyFrames receives the voted key frames followed by the neighbours, children and parents of :930-981 (host pointer code, unchanged), pKFmax
+// the reference key frame (NULL: no votes), vpLocalMapPoints the points of the local key frames in the reference's order -- the list
+// Hip::SearchLocalPoints then gathers positions for.  Bad map points of F are set to NULL like :896-899.
+void UpdateLocalMap(cms_covis* covis, cms_ctx* frameCtx, Frame& F, std::vector<KeyFrame*>& vpLocalKeyFrames, KeyFrame*& pKFmax, std::vector<MapPoint*>& vpLocalMapPoints);
 // ---- Tracking's SearchByBoW(KeyFrame*, Frame&, ...) (ORBMatcher.cpp:409-539) against key frames resident in `store`, on the FRAME thread: F is the frame
 // `frameCtx` extracted last (slot 0 of its batch) after F.ComputeBoW().  The slot comes from the store's KeyFrame* -> slot book; a key-frame feature takes
 // part where the slot's map-point entry (as ProcessNewKeyFrame / CreateNewMapPoints last wrote it) is set and GetMapPointMatches() still holds a point

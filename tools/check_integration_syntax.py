@@ -45,7 +45,9 @@ def main(ref_inc):
                                                ("CubemapHipBridge.cpp", "cms_kfstore_search_by_bow_keyframes(store, ctx, (int)jobs.size(),",
                                                 "cms_kfstore_search_by_bow_keyframes(store, (int)jobs.size(),"),
                                                ("CubemapHipBridge.cpp", "cms_kfstore_search_by_sim3(store, ctx, (int)jobs.size(),", "cms_kfstore_search_by_sim3(store, (int)jobs.size(),"),
-                                               ("CubemapHipBridge.cpp", "cms_kfstore_fuse_search_sim3(store, ctx, 1, set_off,", "cms_kfstore_fuse_search_sim3(store, 1, set_off,"))):
+                                               ("CubemapHipBridge.cpp", "cms_kfstore_fuse_search_sim3(store, ctx, 1, set_off,", "cms_kfstore_fuse_search_sim3(store, 1, set_off,"),
+                                               ("CubemapHipBridge.cpp", "cms_covis_votes(covis, frameCtx, 1, id_off,", "cms_covis_votes(covis, 1, id_off,"),
+                                               ("CubemapHipBridge.cpp", "cms_kfstore_update_map_points(store, (int)up_slot.size(),", "cms_kfstore_update_map_points(store,"))):
             d = os.path.join(td, "broken_%d" % i)
             shutil.copytree(os.path.join(ROOT, "integration"), d)
             src = open(os.path.join(d, fname)).read()
