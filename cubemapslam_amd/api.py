@@ -113,6 +113,9 @@ def lib():
         L.cms_area_set_descriptors.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.cms_search_local_points.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_float] * 3 + [C.c_int, C.c_int] +
                                               [C.c_void_p] * 9)
+        L.cms_search_local_points_ids.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_float] * 3 + [C.c_int, C.c_int] +
+                                                  [C.c_void_p] * 9)
+        L.cms_kfstore_fuse_search_sets_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_void_p, C.c_void_p]
         L.cms_search_by_projection.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_int, C.c_int, C.c_int] +
                                                [C.c_void_p] * 3)
         L.cms_project_last_frame_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 5
@@ -472,6 +475,19 @@ class Context(_Handle):
         _chk(lib().cms_search_local_points(self.h, b, _p(pose15), n, _p(pos), _p(normal), _p(min_dist), _p(max_dist), _p(mp_desc),
                                            viewing_cos_limit, th, nnratio, th_high, len(kp_mp), _p(kp_mp), _p(vis), _p(px), _p(py), _p(lvl),
                                            _p(vc), _p(match), C.addressof(nm), C.addressof(rounds)), "cms_search_local_points")
+        return dict(in_view=vis, proj_x=px, proj_y=py, level=lvl, view_cos=vc, match=match, n_matches=nm.value, rounds=rounds.value)
+
+    def search_local_points_ids(self, b, pose15, mpstore, ids, kp_mp, viewing_cos_limit=0.5, th=1.0, nnratio=0.8, th_high=100):
+        """cms_search_local_points_ids: search_local_points with the map points named by id in a MapPointStore; same dict"""
+        pose15 = np.ascontiguousarray(pose15, np.float32).reshape(15)
+        ids = _ids32(ids)
+        n = len(ids)
+        assert kp_mp.dtype == np.int32 and kp_mp.flags.c_contiguous
+        vis = np.zeros(n, np.uint8); px = np.zeros(n, np.float32); py = np.zeros(n, np.float32); lvl = np.zeros(n, np.int32)
+        vc = np.zeros(n, np.float32); match = np.full(n, -1, np.int32)
+        nm = C.c_int(0); rounds = C.c_int(0)
+        _chk(lib().cms_search_local_points_ids(self.h, b, _p(pose15), mpstore.h, n, _p(ids) if n else None, viewing_cos_limit, th, nnratio, th_high, len(kp_mp), _p(kp_mp),
+                                               _p(vis), _p(px), _p(py), _p(lvl), _p(vc), _p(match), C.addressof(nm), C.addressof(rounds)), "cms_search_local_points_ids")
         return dict(in_view=vis, proj_x=px, proj_y=py, level=lvl, view_cos=vc, match=match, n_matches=nm.value, rounds=rounds.value)
 
     def search_by_projection(self, b, pose12, valid, Xw, octave, angle, mp_desc, kp_mp, th=15.0, check_ori=True, th_high=100):
@@ -915,6 +931,20 @@ class KeyframeStore(_Handle):
              "cms_kfstore_fuse_search_sets")
         return [(bi[eoff[j]:eoff[j + 1]].copy(), bd[eoff[j]:eoff[j + 1]].copy()) for j in range(len(jobs))]
 
+    def fuse_search_sets_ids(self, mpstore, sets, jobs, th=3.0):
+        """cms_kfstore_fuse_search_sets_ids.  sets: list of id lists (rows of a MapPointStore of this store); jobs as in fuse_search_sets
+        -> per job (best_idx, best_dist)"""
+        soff = np.concatenate([[0], np.cumsum([len(q) for q in sets])]).astype(np.int32)
+        ids = _ids32(np.concatenate([np.asarray(q, np.int64).reshape(-1) for q in sets]) if len(sets) else [])
+        slots = np.array([j[0] for j in jobs], np.int32); jset = np.array([j[1] for j in jobs], np.int32)
+        sizes = [int(soff[j[1] + 1] - soff[j[1]]) for j in jobs]
+        eoff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        skip = np.ascontiguousarray(np.concatenate([np.zeros(sz, np.uint8) if j[2] is None else np.asarray(j[2], np.uint8) for j, sz in zip(jobs, sizes)]), np.uint8)
+        bi = np.zeros(max(int(eoff[-1]), 1), np.int32); bd = np.zeros(max(int(eoff[-1]), 1), np.int32)
+        _chk(lib().cms_kfstore_fuse_search_sets_ids(self.h, mpstore.h, len(sets), _p(soff), _p(ids) if len(ids) else None, len(jobs), _p(slots), _p(jset), _p(skip), th,
+                                                    _p(bi), _p(bd)), "cms_kfstore_fuse_search_sets_ids")
+        return [(bi[eoff[j]:eoff[j + 1]].copy(), bd[eoff[j]:eoff[j + 1]].copy()) for j in range(len(jobs))]
+
     def create_new_map_points(self, jobs, check_orientation=False, cap=2048, copy=True):
         """jobs: list of (current slot, [neighbour slots in covisibility order]) -> per job (neigh, idx1, idx2, x3d).
         The job arrays and the output buffers are kept between calls with the same job list (a mapping thread calls this once per key frame,
@@ -1278,6 +1308,68 @@ class Covisibility(_Handle):
         if rc != -4:
             _chk(rc, "cms_covis_local_points")
         return rc, n_out[:nj], [[int(v) for v in ids[j, :min(int(n_out[j]), int(cap))]] for j in range(nj)]
+
+
+MP_DESCRIPTOR, MP_NORMAL_DEPTH = 1, 2
+
+
+def _ids32(ids):
+    """ids as a contiguous int32 array; one that does not fit is refused here, before it could wrap"""
+    wide = np.asarray(ids, np.int64).reshape(-1)
+    if len(wide) and (wide.min() < -(1 << 31) or wide.max() >= (1 << 31)):
+        raise CmsError("an id outside the range of a 32-bit int: %d .. %d" % (int(wide.min()), int(wide.max())))
+    return np.ascontiguousarray(wide, np.int32)
+
+
+class MapPointStore(_Handle):
+    """cms_mpstore: the map-point table next to a KeyframeStore, rows indexed by id (position, normal, distance bounds, descriptor, reference slot).
+    Calls on one object are serialised inside the library."""
+    _entries = ("cms_mpstore_create", "cms_mpstore_destroy")
+
+    def __init__(self, store, max_points):
+        L = lib()
+        L.cms_mpstore_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.cms_mpstore_destroy.argtypes = [C.c_void_p]; L.cms_mpstore_destroy.restype = None
+        L.cms_mpstore_set.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.cms_mpstore_erase.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.cms_mpstore_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.cms_mpstore_fetch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
+        self.store = store
+        self.max_points = int(max_points)
+        self._create(store.h, int(max_points))
+
+    def set(self, ids, pos=None, ref_slot=None):
+        """cms_mpstore_set: world positions (n x 3 or None) and reference slots (n or None) of the rows `ids`; asynchronous"""
+        ids = _ids32(ids)
+        pos = None if pos is None else np.ascontiguousarray(pos, np.float32).reshape(-1)
+        ref = None if ref_slot is None else np.ascontiguousarray(ref_slot, np.int32).reshape(-1)
+        assert (pos is None or len(pos) == 3 * len(ids)) and (ref is None or len(ref) == len(ids))
+        pp = lambda v: _p(v) if v is not None and len(v) else None
+        _chk(lib().cms_mpstore_set(self.h, len(ids), pp(ids), pp(pos), pp(ref)), "cms_mpstore_set")
+
+    def erase(self, ids):
+        """cms_mpstore_erase: the rows are empty again; asynchronous"""
+        ids = _ids32(ids)
+        _chk(lib().cms_mpstore_erase(self.h, len(ids), _p(ids) if len(ids) else None), "cms_mpstore_erase")
+
+    def refresh(self, covis, ids, what=MP_DESCRIPTOR | MP_NORMAL_DEPTH):
+        """cms_mpstore_refresh: descriptor and / or normal and depth of the rows `ids` from the index -> status per id (0 done, 1 no observation,
+        2 the reference slot does not observe the id)"""
+        ids = _ids32(ids)
+        status = np.zeros(max(len(ids), 1), np.uint8)
+        _chk(lib().cms_mpstore_refresh(self.h, covis.h, len(ids), _p(ids) if len(ids) else None, int(what), _p(status)), "cms_mpstore_refresh")
+        return status[:len(ids)]
+
+    def fetch(self, ids):
+        """cms_mpstore_fetch -> dict(pos, normal, min_dist, max_dist, desc, best_member, best_feature) of the rows `ids`"""
+        ids = _ids32(ids)
+        n = len(ids)
+        o = dict(pos=np.zeros((n, 3), np.float32), normal=np.zeros((n, 3), np.float32), min_dist=np.zeros(n, np.float32), max_dist=np.zeros(n, np.float32),
+                 desc=np.zeros((n, 32), np.uint8), best_member=np.zeros(n, np.int32), best_feature=np.zeros(n, np.int32))
+        if n:
+            _chk(lib().cms_mpstore_fetch(self.h, n, _p(ids), _p(o["pos"]), _p(o["normal"]), _p(o["min_dist"]), _p(o["max_dist"]), _p(o["desc"]), _p(o["best_member"]),
+                                         _p(o["best_feature"])), "cms_mpstore_fetch")
+        return o
 
 
 def distinctive_descriptors(ctx, obs_off, desc):

@@ -15,9 +15,9 @@ struct cms_covis {
   int M = 0, bits = 8;
   size_t sum_n = 0;                         // the members' features: the bound of observations and of ids
   // capacities: members, table entries, observations
-  size_t cap_m = 0, cap_rows = 0, cap_h = 0, cap_o = 0, cap_dec = 0;
+  size_t cap_m = 0, cap_rows = 0, cap_h = 0, cap_o = 0, cap_of = 0, cap_dec = 0;
   int* d_slot = nullptr; int* d_n = nullptr; int* d_snap_u = nullptr; int* d_snap_oct = nullptr;
-  int* d_key = nullptr; int* d_cnt = nullptr; int* d_off = nullptr; int* d_uix = nullptr; int* d_cur = nullptr; int2* d_obs = nullptr;
+  int* d_key = nullptr; int* d_cnt = nullptr; int* d_off = nullptr; int* d_uix = nullptr; int* d_cur = nullptr; int2* d_obs = nullptr; int* d_obs_feat = nullptr;
   int* d_counters = nullptr; int* d_dec = nullptr;
   hipEvent_t built_ev = nullptr;
   CmsStage stage;
@@ -27,7 +27,7 @@ static void covis_free(void* p) { if (p) (void)hipFree(p); }
 extern "C" void cms_covis_destroy(cms_covis* cv) {
   if (!cv) return;
   if (cv->st && cv->st->c) (void)hipSetDevice(cv->st->c->device);
-  void* bufs[] = {cv->d_slot, cv->d_n, cv->d_snap_u, cv->d_snap_oct, cv->d_key, cv->d_cnt, cv->d_off, cv->d_uix, cv->d_cur, cv->d_obs, cv->d_counters, cv->d_dec};
+  void* bufs[] = {cv->d_slot, cv->d_n, cv->d_snap_u, cv->d_snap_oct, cv->d_key, cv->d_cnt, cv->d_off, cv->d_uix, cv->d_cur, cv->d_obs, cv->d_obs_feat, cv->d_counters, cv->d_dec};
   for (void* b : bufs) covis_free(b);
   if (cv->built_ev) (void)hipEventDestroy(cv->built_ev);
   cv->stage.release();
@@ -60,7 +60,7 @@ static int covis_grow(std::initializer_list<void**> bufs, size_t& have, size_t n
 static CmsCovisDev covis_dev(const cms_covis* cv) {
   CmsCovisDev d;
   d.M = cv->M; d.maxf = cv->st->maxf; d.bits = cv->bits; d.n = cv->d_n; d.snap_u = cv->d_snap_u; d.snap_oct = cv->d_snap_oct;
-  d.key = cv->d_key; d.cnt = cv->d_cnt; d.off = cv->d_off; d.uix = cv->d_uix; d.obs = cv->d_obs;
+  d.key = cv->d_key; d.cnt = cv->d_cnt; d.off = cv->d_off; d.uix = cv->d_uix; d.obs = cv->d_obs; d.obs_feat = cv->d_obs_feat; d.slot = cv->d_slot;
   return d;
 }
 
@@ -119,6 +119,7 @@ extern "C" int cms_covis_build(cms_covis* cv, int n_members, const int* member_s
   if ((rc = covis_grow({(void**)&cv->d_snap_u, (void**)&cv->d_snap_oct}, cv->cap_rows, M * (size_t)st->maxf, 4))) return rc;
   if ((rc = covis_grow({(void**)&cv->d_key, (void**)&cv->d_cnt, (void**)&cv->d_off, (void**)&cv->d_uix, (void**)&cv->d_cur}, cv->cap_h, H, 4))) return rc;
   if ((rc = covis_grow({(void**)&cv->d_obs}, cv->cap_o, std::max(sum_n, (size_t)1), sizeof(int2)))) return rc;
+  if ((rc = covis_grow({(void**)&cv->d_obs_feat}, cv->cap_of, std::max(sum_n, (size_t)1), 4))) return rc;
   HIPCHK(hipMemcpyAsync(cv->d_slot, d + o_slot, 4 * M, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipMemcpyAsync(cv->d_n, d + o_n, 4 * M, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipMemsetAsync(cv->d_key, 0xFF, 4 * H, s));
@@ -127,7 +128,7 @@ extern "C" int cms_covis_build(cms_covis* cv, int n_members, const int* member_s
   HIPCHK(hipMemsetAsync(cv->d_counters, 0, 8, s));
   CmsCovisBuild a;
   a.M = n_members; a.maxf = st->maxf; a.bits = bits; a.st_maxf = st->maxf; a.slot = cv->d_slot; a.n = cv->d_n; a.st_mp = st->d_mp; a.st_kp = st->d_kp;
-  a.snap_u = cv->d_snap_u; a.snap_oct = cv->d_snap_oct; a.key = cv->d_key; a.cnt = cv->d_cnt; a.off = cv->d_off; a.uix = cv->d_uix; a.cur = cv->d_cur; a.obs = cv->d_obs;
+  a.snap_u = cv->d_snap_u; a.snap_oct = cv->d_snap_oct; a.key = cv->d_key; a.cnt = cv->d_cnt; a.off = cv->d_off; a.uix = cv->d_uix; a.cur = cv->d_cur; a.obs = cv->d_obs; a.obs_feat = cv->d_obs_feat;
   a.counters = cv->d_counters;
   if (max_n > 0) {
     const dim3 rows((unsigned)((max_n + 255) / 256), (unsigned)M);

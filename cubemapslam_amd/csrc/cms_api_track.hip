@@ -89,15 +89,17 @@ static int track_rows_to_frame(const cms_ctx* c, int b, int n, const int* rows, 
 // One frame, host buffers: isInFrustum for the n map points, window query against frame b's grid, greedy search.  kp_mp: one int per
 // key point of frame b, in/out (>= 0 on entry = key point already holds a map point with observations; matches are written as the
 // index of the map point in this list).
-extern "C" int cms_search_local_points(cms_ctx* c, int b, const float* pose15, int nmp, const float* pos, const float* normal,
-                                       const float* min_dist, const float* max_dist, const uint8_t* mp_desc, float viewing_cos_limit, float th,
-                                       float nnratio, int th_high, int nkp, int* kp_mp, uint8_t* in_view, float* proj_x, float* proj_y,
-                                       int* level, float* view_cos, int* mp_match, int* n_matches, int* rounds) {
-  if (!c || !pose15 || nmp < 0 || nkp < 0 || nkp > (c ? c->g.kp_cap : 0) || (nmp > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !mp_match)) ||
-      (nkp > 0 && !kp_mp))
-    return cms_fail(CMS_ERR_ARG, "cms_search_local_points: bad argument");
-  if (b < 0 || b >= c->area_frames) return cms_fail(CMS_ERR_ARG, "cms_search_local_points: no grid for this frame (cms_area_grid first)");
-  if (c->g.kp_cap > CMS_TRACK_KPMAX) return cms_fail(CMS_ERR_UNSUPPORTED, "cms_search_local_points: more than 4096 key points per frame");
+// gather (NULL: the five host arrays): the map points come from a table on the device (cms_search_local_points_ids).  who: the entry, for its errors
+static int track_search_local_one_frame(cms_ctx* c, const char* who, int b, const float* pose15, int nmp, const float* pos, const float* normal, const float* min_dist,
+                                        const float* max_dist, const uint8_t* mp_desc, const CmsPointGather* gather, float viewing_cos_limit, float th,
+                                        float nnratio, int th_high, int nkp, int* kp_mp, uint8_t* in_view, float* proj_x, float* proj_y,
+                                        int* level, float* view_cos, int* mp_match, int* n_matches, int* rounds) {
+  const std::string me(who);
+  if (!c || !pose15 || nmp < 0 || nkp < 0 || nkp > (c ? c->g.kp_cap : 0) ||
+      (nmp > 0 && ((!gather && (!pos || !normal || !min_dist || !max_dist || !mp_desc)) || !mp_match)) || (nkp > 0 && !kp_mp))
+    return cms_fail(CMS_ERR_ARG, (me + ": bad argument").c_str());
+  if (b < 0 || b >= c->area_frames) return cms_fail(CMS_ERR_ARG, (me + ": no grid for this frame (cms_area_grid first)").c_str());
+  if (c->g.kp_cap > CMS_TRACK_KPMAX) return cms_fail(CMS_ERR_UNSUPPORTED, (me + ": more than 4096 key points per frame").c_str());
   if (n_matches) *n_matches = 0;
   if (rounds) *rounds = 0;
   if (nmp == 0) return CMS_OK;
@@ -114,17 +116,25 @@ extern "C" int cms_search_local_points(cms_ctx* c, int b, const float* pose15, i
   const size_t out_begin = o_kpmp, out_end = blk.size;
   const size_t o_qr = blk.take(n4), o_qmin = blk.take(n4), o_qmax = blk.take(n4), o_cnt = blk.take(n4), o_off = blk.take(n4, 4);
   const size_t o_idx = blk.size;
-  return cms_retry_capacity(64 * nmp + 1024, "cms_search_local_points", [&](int cap, int& tot) -> int {
+  return cms_retry_capacity(64 * nmp + 1024, who, [&](int cap, int& tot) -> int {
     const size_t o_pd = o_idx + cms_align((size_t)cap * 4);
     int rc = c->stage.reserve(s, o_pd + cms_align((size_t)cap * 2), out_end);
     if (rc) return rc;
     uint8_t* p = c->stage.d;
     uint8_t* h = c->stage.h;
     memcpy(h + o_pose, pose15, 60);
-    memcpy(h + o_pos, pos, 3 * n4); memcpy(h + o_nrm, normal, 3 * n4); memcpy(h + o_min, min_dist, n4); memcpy(h + o_max, max_dist, n4);
-    memcpy(h + o_desc, mp_desc, (size_t)nmp * 32);
+    if (!gather) {
+      memcpy(h + o_pos, pos, 3 * n4); memcpy(h + o_nrm, normal, 3 * n4); memcpy(h + o_min, min_dist, n4); memcpy(h + o_max, max_dist, n4);
+      memcpy(h + o_desc, mp_desc, (size_t)nmp * 32);
+    }
     track_stage_one_frame(c, h, o_qf, o_mpoff, o_kpmp, b, nmp, nkp, kp_mp);
-    rc = c->stage.up(s, in_bytes, "cms_search_local_points");
+    if (gather) {      // the five places are filled on the device: the pose, and what lies behind them, travel; they do not
+      HIPCHK(hipMemcpyAsync(p + o_pose, h + o_pose, 64, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(p + o_qf, h + o_qf, in_bytes - o_qf, hipMemcpyHostToDevice, s));
+      rc = (*gather)(s, (float*)(p + o_pos), (float*)(p + o_nrm), (float*)(p + o_min), (float*)(p + o_max), p + o_desc);
+    } else {
+      rc = c->stage.up(s, in_bytes, who);
+    }
     if (rc) return rc;
     rc = cms_is_in_frustum_device(c, nmp, nullptr, p + o_pose, p + o_pos, p + o_nrm, p + o_min, p + o_max, viewing_cos_limit, th, p + o_vis,
                                   p + o_px, p + o_py, p + o_lvl, p + o_vc, p + o_qr, p + o_qmin, p + o_qmax);
@@ -137,7 +147,7 @@ extern "C" int cms_search_local_points(cms_ctx* c, int b, const float* pose15, i
                                                          p + o_rounds, nnratio, th_high, b, p + o_tot, cap);
     hipLaunchKernelGGL(k_search_local, dim3(1), dim3(1024), 0, s, a);
     HIPCHK(hipGetLastError());
-    rc = c->stage.back_and_wait(s, out_begin, out_end, "cms_search_local_points");
+    rc = c->stage.back_and_wait(s, out_begin, out_end, who);
     if (rc) return rc;
     tot = *reinterpret_cast<const int*>(h + o_tot);
     if (tot > cap) return CMS_OK;
@@ -152,6 +162,13 @@ extern "C" int cms_search_local_points(cms_ctx* c, int b, const float* pose15, i
     if (rounds) *rounds = *reinterpret_cast<const int*>(h + o_rounds);
     return CMS_OK;
   });
+}
+extern "C" int cms_search_local_points(cms_ctx* c, int b, const float* pose15, int nmp, const float* pos, const float* normal,
+                                       const float* min_dist, const float* max_dist, const uint8_t* mp_desc, float viewing_cos_limit, float th,
+                                       float nnratio, int th_high, int nkp, int* kp_mp, uint8_t* in_view, float* proj_x, float* proj_y,
+                                       int* level, float* view_cos, int* mp_match, int* n_matches, int* rounds) {
+  return track_search_local_one_frame(c, "cms_search_local_points", b, pose15, nmp, pos, normal, min_dist, max_dist, mp_desc, nullptr, viewing_cos_limit, th, nnratio, th_high, nkp, kp_mp,
+                                      in_view, proj_x, proj_y, level, view_cos, mp_match, n_matches, rounds);
 }
 
 // ---- ORBMatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono): device-pointer pieces (asynchronous on the ctx stream) ...

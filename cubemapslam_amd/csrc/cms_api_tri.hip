@@ -929,21 +929,23 @@ k_fuse_expand_jobs(int nmp, int njobs, const int* __restrict__ mp_off, const int
 // refer to SETS of map points uploaded once (job j's entries are the points job_set0[j] .. of the npts-long arrays): SearchInNeighbors sends one key
 // frame's map points to each of its ~20 neighbours, and 20 copies of the same positions / normals / descriptors were 15 of the 16 MB a call uploaded.
 static int kfstore_fuse_core(cms_kfstore* st, int njobs, const int* job_slot, const int* mp_off, const int* job_set0, int npts, const uint8_t* skip, const float* pos,
-                             const float* normal, const float* min_dist, const float* max_dist, const uint8_t* mp_desc, float th, int* best_idx, int* best_dist) {
-  if (!st || njobs < 0 || (njobs > 0 && (!job_slot || !mp_off))) return cms_fail(CMS_ERR_ARG, "cms_kfstore_fuse_search: bad argument");
+                             const float* normal, const float* min_dist, const float* max_dist, const uint8_t* mp_desc, const CmsPointGather* gather, float th, int* best_idx,
+                             int* best_dist) {
+  const std::string me(gather ? "cms_kfstore_fuse_search_sets_ids" : "cms_kfstore_fuse_search");      // (the one entry that gathers: its errors name it)
+  if (!st || njobs < 0 || (njobs > 0 && (!job_slot || !mp_off))) return cms_fail(CMS_ERR_ARG, (me + ": bad argument").c_str());
   if (njobs == 0) return CMS_OK;
   const int nmp = mp_off[njobs];
-  if (nmp < 0 || mp_off[0] != 0 || (nmp > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !best_idx || !best_dist)))
-    return cms_fail(CMS_ERR_ARG, "cms_kfstore_fuse_search: bad map-point arrays");
+  if (nmp < 0 || mp_off[0] != 0 || (nmp > 0 && ((!gather && (!pos || !normal || !min_dist || !max_dist || !mp_desc)) || !best_idx || !best_dist)))
+    return cms_fail(CMS_ERR_ARG, (me + ": bad map-point arrays").c_str());
   if (nmp == 0) return CMS_OK;
   cms_ctx* c = st->c;
-  if (c->g.nlevels > 16) return cms_fail(CMS_ERR_UNSUPPORTED, "cms_kfstore_fuse_search: more than 16 pyramid levels");
+  if (c->g.nlevels > 16) return cms_fail(CMS_ERR_UNSUPPORTED, (me + ": more than 16 pyramid levels").c_str());
   // per JOB on the host: the slot's pose; per MAP POINT everything happens on the device
   static thread_local std::vector<float> pose;
   pose.resize((size_t)njobs * 15);
   for (int j = 0; j < njobs; ++j) {
     const int sl = job_slot[j];
-    if (sl < 0 || sl >= st->maxkf || !st->used[(size_t)sl] || mp_off[j + 1] < mp_off[j]) return cms_fail(CMS_ERR_ARG, "cms_kfstore_fuse_search: bad job");
+    if (sl < 0 || sl >= st->maxkf || !st->used[(size_t)sl] || mp_off[j + 1] < mp_off[j]) return cms_fail(CMS_ERR_ARG, (me + ": bad job").c_str());
     const CmsTriKF& k = st->h_kf[(size_t)sl];
     memcpy(&pose[15 * (size_t)j], k.Rcw, 36); memcpy(&pose[15 * (size_t)j + 9], k.tcw, 12); memcpy(&pose[15 * (size_t)j + 12], k.Ow, 12);
   }
@@ -960,7 +962,7 @@ static int kfstore_fuse_core(cms_kfstore* st, int njobs, const int* job_slot, co
   w.take(blk, (size_t)nmp);
   const size_t o_idx = blk.size;
   const bool direct = cms_is_pinned(best_idx) && cms_is_pinned(best_dist);
-  return cms_retry_capacity(64 * nmp + 1024, "cms_kfstore_fuse_search", [&](int cap, int& tot) -> int {
+  return cms_retry_capacity(64 * nmp + 1024, me.c_str(), [&](int cap, int& tot) -> int {
     int rc = c->stage.reserve(s, o_idx + cms_align((size_t)cap * 4), 0);
     if (rc) return rc;
     uint8_t* p = c->stage.d;
@@ -970,11 +972,16 @@ static int kfstore_fuse_core(cms_kfstore* st, int njobs, const int* job_slot, co
     HIPCHK(hipMemcpyAsync(p + o_jslot, job_slot, j4, hipMemcpyHostToDevice, s));
     if (skip) HIPCHK(hipMemcpyAsync(p + o_skip, skip, nmp, hipMemcpyHostToDevice, s));
     if (job_set0) HIPCHK(hipMemcpyAsync(p + o_jset, job_set0, j4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(p + o_pos, pos, 3 * p4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(p + o_nrm, normal, 3 * p4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(p + o_min, min_dist, p4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(p + o_max, max_dist, p4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(p + o_desc, mp_desc, (size_t)npts * 32, hipMemcpyHostToDevice, s));
+    if (gather) {      // the sets' points come from a table on the device (cms_kfstore_fuse_search_sets_ids)
+      rc = (*gather)(s, (float*)(p + o_pos), (float*)(p + o_nrm), (float*)(p + o_min), (float*)(p + o_max), p + o_desc);
+      if (rc) return rc;
+    } else {
+      HIPCHK(hipMemcpyAsync(p + o_pos, pos, 3 * p4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(p + o_nrm, normal, 3 * p4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(p + o_min, min_dist, p4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(p + o_max, max_dist, p4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(p + o_desc, mp_desc, (size_t)npts * 32, hipMemcpyHostToDevice, s));
+    }
     int* src = job_set0 ? w.rec : nullptr;
     hipLaunchKernelGGL(k_fuse_expand_jobs, dim3((nmp + 255) / 256), dim3(256), 0, s, nmp, njobs, (const int*)(p + o_joff), (const int*)(p + o_jslot), (int*)(p + o_job), w.slot,
                        job_set0 ? (const int*)(p + o_jset) : nullptr, src);
@@ -1002,27 +1009,33 @@ static int kfstore_fuse_core(cms_kfstore* st, int njobs, const int* job_slot, co
 extern "C" int cms_kfstore_fuse_search(cms_kfstore* st, int njobs, const int* job_slot, const int* mp_off, const uint8_t* skip, const float* pos,
                                        const float* normal, const float* min_dist, const float* max_dist, const uint8_t* mp_desc, float th,
                                        int* best_idx, int* best_dist) {
-  return kfstore_fuse_core(st, njobs, job_slot, mp_off, nullptr, 0, skip, pos, normal, min_dist, max_dist, mp_desc, th, best_idx, best_dist);
+  return kfstore_fuse_core(st, njobs, job_slot, mp_off, nullptr, 0, skip, pos, normal, min_dist, max_dist, mp_desc, nullptr, th, best_idx, best_dist);
 }
 // SearchInNeighbors' shape (LocalMapping.cpp:388-466): nsets sets of map points (set s = points set_off[s] .. set_off[s + 1] of pos / normal / min_dist /
 // max_dist / mp_desc), njobs jobs (key frame slot job_slot[j], set job_set[j]); skip / best_idx / best_dist are per ENTRY: job after job, a job's entries
-// in the order of its set (skip may be NULL)
-extern "C" int cms_kfstore_fuse_search_sets(cms_kfstore* st, int nsets, const int* set_off, const float* pos, const float* normal, const float* min_dist,
-                                            const float* max_dist, const uint8_t* mp_desc, int njobs, const int* job_slot, const int* job_set, const uint8_t* skip,
-                                            float th, int* best_idx, int* best_dist) {
-  if (!st || nsets < 0 || njobs < 0 || (nsets > 0 && !set_off) || (njobs > 0 && (!job_slot || !job_set))) return cms_fail(CMS_ERR_ARG, "cms_kfstore_fuse_search_sets: bad argument");
+// in the order of its set (skip may be NULL).  gather (NULL: the five host arrays): see kfstore_fuse_core
+static int kfstore_fuse_sets(cms_kfstore* st, int nsets, const int* set_off, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                             const uint8_t* mp_desc, const CmsPointGather* gather, int njobs, const int* job_slot, const int* job_set, const uint8_t* skip, float th,
+                             int* best_idx, int* best_dist) {
+  const std::string me(gather ? "cms_kfstore_fuse_search_sets_ids" : "cms_kfstore_fuse_search_sets");
+  if (!st || nsets < 0 || njobs < 0 || (nsets > 0 && !set_off) || (njobs > 0 && (!job_slot || !job_set))) return cms_fail(CMS_ERR_ARG, (me + ": bad argument").c_str());
   if (njobs == 0) return CMS_OK;
-  if (nsets == 0 || set_off[0] != 0) return cms_fail(CMS_ERR_ARG, "cms_kfstore_fuse_search_sets: bad sets");
-  for (int s = 0; s < nsets; ++s) if (set_off[s + 1] < set_off[s]) return cms_fail(CMS_ERR_ARG, "cms_kfstore_fuse_search_sets: set offsets must ascend");
+  if (nsets == 0 || set_off[0] != 0) return cms_fail(CMS_ERR_ARG, (me + ": bad sets").c_str());
+  for (int s = 0; s < nsets; ++s) if (set_off[s + 1] < set_off[s]) return cms_fail(CMS_ERR_ARG, (me + ": set offsets must ascend").c_str());
   static thread_local std::vector<int> off, set0;
   off.resize((size_t)njobs + 1); set0.resize((size_t)njobs);
   off[0] = 0;
   for (int j = 0; j < njobs; ++j) {
-    if (job_set[j] < 0 || job_set[j] >= nsets) return cms_fail(CMS_ERR_ARG, "cms_kfstore_fuse_search_sets: bad set index");
+    if (job_set[j] < 0 || job_set[j] >= nsets) return cms_fail(CMS_ERR_ARG, (me + ": bad set index").c_str());
     set0[(size_t)j] = set_off[job_set[j]];
     const long long nx = (long long)off[(size_t)j] + (set_off[job_set[j] + 1] - set_off[job_set[j]]);
-    if (nx > 0x7FFFFFFF / 80) return cms_fail(CMS_ERR_ARG, "cms_kfstore_fuse_search_sets: too many entries for one call");
+    if (nx > 0x7FFFFFFF / 80) return cms_fail(CMS_ERR_ARG, (me + ": too many entries for one call").c_str());
     off[(size_t)j + 1] = (int)nx;
   }
-  return kfstore_fuse_core(st, njobs, job_slot, off.data(), set0.data(), set_off[nsets], skip, pos, normal, min_dist, max_dist, mp_desc, th, best_idx, best_dist);
+  return kfstore_fuse_core(st, njobs, job_slot, off.data(), set0.data(), set_off[nsets], skip, pos, normal, min_dist, max_dist, mp_desc, gather, th, best_idx, best_dist);
+}
+extern "C" int cms_kfstore_fuse_search_sets(cms_kfstore* st, int nsets, const int* set_off, const float* pos, const float* normal, const float* min_dist,
+                                            const float* max_dist, const uint8_t* mp_desc, int njobs, const int* job_slot, const int* job_set, const uint8_t* skip,
+                                            float th, int* best_idx, int* best_dist) {
+  return kfstore_fuse_sets(st, nsets, set_off, pos, normal, min_dist, max_dist, mp_desc, nullptr, njobs, job_slot, job_set, skip, th, best_idx, best_dist);
 }

@@ -1,6 +1,7 @@
 // cms_api_util.h -- host-side helpers shared by the cms_api_*.hip files; included by cms_api_frames.hip behind cms_ctx, cms_fail and HIPCHK.
 #pragma once
 #include <cmath>
+#include <functional>
 #include <mutex>
 #include <string>
 
@@ -57,6 +58,11 @@ static int cms_lds_ceiling_once(const void* kernel, int bytes, int device, bool 
   if (device >= 0 && device < 64 && !done[device]) { HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)); done[device] = true; }
   return CMS_OK;
 }
+
+// Where the map points of a search entry come from when not from the caller's host arrays: the hook fills pos | normal | min_dist | max_dist | desc
+// of the call's points on the device, in the order of stream s (cms_api_mappoints.hip: rows of a cms_mpstore named by id).  The launch chain behind
+// it is the host-array entry's.
+using CmsPointGather = std::function<int(hipStream_t s, float* pos, float* normal, float* min_dist, float* max_dist, uint8_t* desc)>;
 
 // The window-query entries guess a candidate capacity (64 per window) and repeat ONCE with the exact size when the device counted more.
 // attempt(cap, total) is one whole attempt: reserve (CmsStage::reserve may reallocate: block pointers are taken after that), stage the

@@ -2,7 +2,7 @@
 // cms_api_covis.hip).  gfx950, wave64.
 //
 // The index is an open-addressing table over the map-point ids (2^bits >= twice the members' features, integer CAS, linear probing) with one
-// segment of (member, octave) observations per id.  Where a segment lies and the order inside it depend on the order in which atomics land; no
+// segment of (member, octave) observations per id, the feature index in a parallel array (cms_mappoint_kernels.hip reads it).  Where a segment lies and the order inside it depend on the order in which atomics land; no
 // result does: the queries only COUNT over segments, and the rank in `order` is a function of (weight, member position).
 #include "cms_covis_core.h"
 
@@ -16,6 +16,8 @@ struct CmsCovisDev {
   const int* off;        // [2^bits] where the id's segment starts in obs
   const int* uix;        // [2^bits] a dense number per id (the culling scratch is indexed by it)
   const int2* obs;       // (member, octave)
+  const int* obs_feat;   // the observation's feature index in its member's row, parallel to obs
+  const int* slot;       // [M] the store slot of a member
 };
 
 // ---- build
@@ -49,7 +51,7 @@ struct CmsCovisBuild {
   int M, maxf, bits, st_maxf;
   const int* slot; const int* n;            // [M]
   const int* st_mp; const CmsKeyPoint* st_kp;
-  int* snap_u; int* snap_oct; int* key; int* cnt; int* off; int* uix; int* cur; int2* obs;
+  int* snap_u; int* snap_oct; int* key; int* cnt; int* off; int* uix; int* cur; int2* obs; int* obs_feat;
   int* counters;                            // [0]: observations placed, [1]: ids numbered
 };
 // the snapshot of the members' rows, every live id into the table.  blockIdx.y = member
@@ -88,6 +90,7 @@ extern "C" __global__ void __launch_bounds__(256) k_covis_fill(const CmsCovisBui
   if (u < 0) return;
   const int e = a.off[u] + atomicAdd(&a.cur[u], 1);      // (cur[u] stays below cnt[u]: one add per observation counted)
   a.obs[e] = make_int2(m, a.snap_oct[dst]);
+  a.obs_feat[e] = f;
 }
 
 // the table entry of an id, -1: the index does not know it

@@ -13,6 +13,7 @@
 #include "../csrc/cms_vocab_core.h"
 #include "../csrc/cms_kfdb_core.h"
 #include "../csrc/cms_covis_core.h"
+#include "../csrc/cms_mappoint_core.h"
 #include "../csrc/cms_ess_graph_core.h"      // CmsS3 and Sim3(R, t, s) for vScw
 #include "../csrc/cms_ess_graph_job_check.h" // the envelope count for the handle
 #include "../csrc/cms_sim3_core.h"      // the gemm rule (cms_sim3_row) and TransformRaysToCubemap for the constructor's filter
@@ -1852,6 +1853,164 @@ std::vector<long> Covisibility::UpdateLocalPoints(const std::vector<KeyFrameView
     if (cms_covis_local_points(m.cv, c, 1, off, kfs.data(), (int)cap, ids.data(), &n) != CMS_OK) Impl::fail("cms_covis_local_points");
   }
   return std::vector<long>(ids.begin(), ids.begin() + n);
+}
+
+// ---- MapPointStore (src/MapPoint.cpp:243-308, :332-373)
+struct MapPointStore::Impl {
+  Engine engine;
+  int max_keyframes, max_features, max_points;
+  CmsMpHostStore* host = nullptr;            // HOST_CORE, made by the first Build (it wants the level scale factors)
+  cms_kfstore* store = nullptr;              // DEVICE, made by the first Build
+  cms_covis* cv = nullptr;
+  cms_mpstore* mp = nullptr;
+  std::vector<KeyFrameView*> members;
+  std::map<KeyFrameView*, int> pos_of;
+  Impl(Engine e, int K, int Fq, int P) : engine(e), max_keyframes(K), max_features(Fq), max_points(P) {}
+  static cms_orb_params orb() {
+    if (g_ctx_orb.nfeatures > 0) return g_ctx_orb;
+    cms_orb_params o{};
+    o.nfeatures = 2000; o.scale_factor = 1.2f; o.nlevels = 8; o.ini_th_fast = 20; o.min_th_fast = 7;
+    return o;
+  }
+  static void fail(const char* who) { throw std::runtime_error(std::string(who) + " failed: " + cms_last_error()); }
+  std::vector<int> ids32(const std::vector<long>& ids, const char* who) const {
+    std::vector<int> out(ids.size() + 1);
+    for (size_t i = 0; i < ids.size(); ++i) {
+      if (ids[i] < 0 || ids[i] >= max_points) throw std::runtime_error(std::string(who) + ": an id outside the table");
+      out[i] = (int)ids[i];
+    }
+    return out;
+  }
+};
+MapPointStore::MapPointStore(Engine engine, int max_keyframes, int max_features, int max_points) : impl_(new Impl(engine, max_keyframes, max_features, max_points)) {}
+MapPointStore::~MapPointStore() {
+  if (impl_->mp) cms_mpstore_destroy(impl_->mp);
+  if (impl_->cv) cms_covis_destroy(impl_->cv);
+  if (impl_->store) cms_kfstore_destroy(impl_->store);
+  delete impl_->host;
+  delete impl_;
+}
+void MapPointStore::Build(const std::vector<KeyFrameView*>& members) {
+  Impl& m = *impl_;
+  if ((int)members.size() > m.max_keyframes) throw std::runtime_error("MapPointStore::Build: more key frames than max_keyframes");
+  std::map<KeyFrameView*, int> pos_of;
+  std::vector<int> slots(members.size() + 1);
+  std::vector<std::vector<int>> rows(members.size());
+  for (size_t i = 0; i < members.size(); ++i) {
+    if (!members[i] || pos_of.count(members[i])) throw std::runtime_error("MapPointStore::Build: a null key frame, or one listed twice");
+    const KeyFrameView& k = *members[i];
+    if ((int)k.mvKeys.size() > m.max_features) throw std::runtime_error("MapPointStore::Build: a key frame with more features than max_features");
+    pos_of[members[i]] = (int)i; slots[i] = (int)i;
+    rows[i].resize(k.mvKeys.size() + 1);
+    for (size_t f = 0; f < k.mvKeys.size(); ++f) {
+      const bool bad = !k.mvbMapPointBad.empty() && k.mvbMapPointBad[f];
+      rows[i][f] = (k.mvpMapPoints[f] >= 0 && k.mvpMapPoints[f] < m.max_points && !bad) ? (int)k.mvpMapPoints[f] : -1;
+    }
+  }
+  const cms_orb_params orb = Impl::orb();
+  if (m.engine == HOST_CORE) {
+    if (!m.host) {
+      float sf[16];      // ORBextractor's mvScaleFactor as cms_ctx_create forms it
+      sf[0] = 1.0f;
+      for (int l = 1; l < 16; ++l) sf[l] = (float)(sf[l - 1] * (double)orb.scale_factor);
+      m.host = new CmsMpHostStore(m.max_keyframes, m.max_features, m.max_keyframes, m.max_points, orb.nlevels, sf);
+    }
+    for (size_t i = 0; i < members.size(); ++i) {
+      const KeyFrameView& k = *members[i];
+      std::vector<int> oct(k.mvKeys.size() + 1);
+      std::vector<uint8_t> desc(32 * k.mvKeys.size() + 32);
+      for (size_t f = 0; f < k.mvKeys.size(); ++f) { oct[f] = k.mvKeys[f].octave; std::memcpy(&desc[32 * f], k.mDescriptors.ptr<uint8_t>((int)f), 32); }
+      float R[9], t[3], Ow[3];
+      pose15_from_Tcw(k.Tcw, R, t, Ow);
+      if (m.host->put((int)i, (int)k.mvKeys.size(), rows[i].data(), oct.data(), desc.data(), Ow)) throw std::runtime_error("MapPointStore::Build: bad key frame");
+    }
+    if (m.host->build((int)members.size(), slots.data())) throw std::runtime_error("MapPointStore::Build: a key frame names a map point twice");
+  } else {
+    cms_ctx* c = SharedContext(orb.nfeatures, orb.scale_factor, orb.nlevels, orb.ini_th_fast, orb.min_th_fast);
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!m.store && cms_kfstore_create(&m.store, c, m.max_keyframes, m.max_features, m.max_features) != CMS_OK) Impl::fail("cms_kfstore_create");
+    if (!m.cv && cms_covis_create(&m.cv, m.store, m.max_keyframes) != CMS_OK) Impl::fail("cms_covis_create");
+    if (!m.mp && cms_mpstore_create(&m.mp, m.store, m.max_points) != CMS_OK) Impl::fail("cms_mpstore_create");
+    for (size_t i = 0; i < members.size(); ++i) {
+      KfPack pack;
+      cms_keyframe k = pack_keyframe(*members[i], pack);
+      k.mp = rows[i].data();
+      if (cms_kfstore_put(m.store, (int)i, &k) != CMS_OK) Impl::fail("cms_kfstore_put");
+    }
+    if (cms_covis_build(m.cv, (int)members.size(), slots.data()) != CMS_OK) Impl::fail("cms_covis_build");
+  }
+  m.members = members; m.pos_of.swap(pos_of);
+}
+void MapPointStore::SetMapPoints(const std::vector<MapPointView>& points) {
+  Impl& m = *impl_;
+  if (points.empty()) return;
+  std::vector<long> ids(points.size());
+  std::vector<float> pos(3 * points.size());
+  std::vector<int> ref(points.size());
+  for (size_t i = 0; i < points.size(); ++i) {
+    ids[i] = points[i].id;
+    std::memcpy(&pos[3 * i], points[i].pos, 12);
+    auto it = m.pos_of.find(points[i].pRefKF);
+    if (it == m.pos_of.end()) throw std::runtime_error("MapPointStore::SetMapPoints: pRefKF is not a member of the last Build");
+    ref[i] = it->second;
+  }
+  const std::vector<int> id32 = m.ids32(ids, "MapPointStore::SetMapPoints");
+  if (m.engine == HOST_CORE) {
+    if (!m.host || m.host->set((int)points.size(), id32.data(), pos.data(), ref.data())) throw std::runtime_error("MapPointStore::SetMapPoints: an id twice (or no Build yet)");
+  } else {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!m.mp || cms_mpstore_set(m.mp, (int)points.size(), id32.data(), pos.data(), ref.data()) != CMS_OK) Impl::fail("cms_mpstore_set");
+  }
+}
+void MapPointStore::EraseMapPoints(const std::vector<long>& ids) {
+  Impl& m = *impl_;
+  if (ids.empty()) return;
+  const std::vector<int> id32 = m.ids32(ids, "MapPointStore::EraseMapPoints");
+  if (m.engine == HOST_CORE) {
+    if (!m.host || m.host->erase((int)ids.size(), id32.data())) throw std::runtime_error("MapPointStore::EraseMapPoints: an id twice (or no Build yet)");
+  } else {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!m.mp || cms_mpstore_erase(m.mp, (int)ids.size(), id32.data()) != CMS_OK) Impl::fail("cms_mpstore_erase");
+  }
+}
+std::vector<unsigned char> MapPointStore::Refresh(const std::vector<long>& ids, int what) {
+  Impl& m = *impl_;
+  std::vector<unsigned char> status(ids.size() + 1);
+  if (!ids.empty()) {
+    const std::vector<int> id32 = m.ids32(ids, "MapPointStore::Refresh");
+    if (m.engine == HOST_CORE) {
+      if (!m.host || m.host->refresh((int)ids.size(), id32.data(), what, status.data())) throw std::runtime_error("MapPointStore::Refresh: an id twice, or a point that was never set");
+    } else {
+      std::lock_guard<std::mutex> lock(g_ctx_mutex);
+      if (!m.mp || cms_mpstore_refresh(m.mp, m.cv, (int)ids.size(), id32.data(), what, status.data()) != CMS_OK) Impl::fail("cms_mpstore_refresh");
+    }
+  }
+  status.resize(ids.size());
+  return status;
+}
+std::vector<MapPointStore::Row> MapPointStore::Fetch(const std::vector<long>& ids) {
+  Impl& m = *impl_;
+  const size_t n = ids.size();
+  std::vector<Row> out(n);
+  if (n == 0) return out;
+  const std::vector<int> id32 = m.ids32(ids, "MapPointStore::Fetch");
+  std::vector<float> pos(3 * n), nrm(3 * n), mn(n), mx(n);
+  std::vector<uint8_t> desc(32 * n);
+  std::vector<int> bm(n), bf(n);
+  if (m.engine == HOST_CORE) {
+    if (!m.host || m.host->fetch((int)n, id32.data(), pos.data(), nrm.data(), mn.data(), mx.data(), desc.data(), bm.data(), bf.data())) throw std::runtime_error("MapPointStore::Fetch: no Build yet");
+  } else {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!m.mp || cms_mpstore_fetch(m.mp, (int)n, id32.data(), pos.data(), nrm.data(), mn.data(), mx.data(), desc.data(), bm.data(), bf.data()) != CMS_OK) Impl::fail("cms_mpstore_fetch");
+  }
+  for (size_t i = 0; i < n; ++i) {
+    Row& r = out[i];
+    std::memcpy(r.pos, &pos[3 * i], 12); std::memcpy(r.normal, &nrm[3 * i], 12); std::memcpy(r.descriptor, &desc[32 * i], 32);
+    r.minDistance = mn[i]; r.maxDistance = mx[i];
+    r.pBestKF = (bm[i] >= 0 && (size_t)bm[i] < m.members.size()) ? m.members[(size_t)bm[i]] : nullptr;
+    r.bestIdx = bf[i];
+  }
+  return out;
 }
 
 }  // namespace CubemapSLAM

@@ -465,6 +465,35 @@ class Covisibility {
   Impl* impl_;
 };
 
+// The map points' derived members under the reference's names: MapPoint::ComputeDistinctiveDescriptors (MapPoint.cpp:243-308) and
+// MapPoint::UpdateNormalAndDepth (:332-373) over the key frames of the last Build, a map point named by its id (the value in mvpMapPoints, below
+// max_points).  Two engines, an explicit choice and never a fall-back: DEVICE keeps the members in a cms_kfstore with a cms_covis and a cms_mpstore
+// on the shared context's device; HOST_CORE is the host build of csrc/cms_mappoint_core.h, the definition of record, no GPU needed.  Observations are
+// taken in the order of Build's list (the reference's std::map<KeyFrame*, size_t> iterates by pointer).  A parity mirror like Covisibility: the
+// DEVICE engine puts every member into a private store again on each Build.
+class MapPointStore {
+ public:
+  enum Engine { DEVICE = 0, HOST_CORE = 1 };
+  enum { DESCRIPTOR = 1, NORMAL_DEPTH = 2 };
+  explicit MapPointStore(Engine engine, int max_keyframes = 256, int max_features = 2048, int max_points = 65536);
+  ~MapPointStore();
+  MapPointStore(const MapPointStore&) = delete;
+  MapPointStore& operator=(const MapPointStore&) = delete;
+  void Build(const std::vector<KeyFrameView*>& members);
+  // SetWorldPos and mpRefKF of the named points (pRefKF: any key frame of the last Build)
+  struct MapPointView { long id; float pos[3]; KeyFrameView* pRefKF; };
+  void SetMapPoints(const std::vector<MapPointView>& points);
+  void EraseMapPoints(const std::vector<long>& ids);
+  // per id: 0 done, 1 no observation among the members (the reference's early return), 2 pRefKF does not observe the point; 1 and 2 leave the row as it was
+  std::vector<unsigned char> Refresh(const std::vector<long>& ids, int what = DESCRIPTOR | NORMAL_DEPTH);
+  // mDescriptor, mNormalVector, mfMinDistance, mfMaxDistance and the observation the descriptor came from (NULL, -1: none)
+  struct Row { float pos[3], normal[3], minDistance, maxDistance; unsigned char descriptor[32]; KeyFrameView* pBestKF; int bestIdx; };
+  std::vector<Row> Fetch(const std::vector<long>& ids);
+
+ private:
+  struct Impl;
+  Impl* impl_;
+};
 
 class LocalMapping {
  public:

@@ -7,6 +7,7 @@
 #include "../csrc/cms_vocab_core.h"
 #include "../csrc/cms_kfdb_core.h"
 #include "../csrc/cms_covis_core.h"
+#include "../csrc/cms_mappoint_core.h"
 using namespace CubemapSLAM;
 
 static thread_local std::string g_err;
@@ -954,6 +955,99 @@ extern "C" int hm_covis_culling(void* cv, int n_chains, const int* chain_off, co
 }
 extern "C" int hm_covis_local_points(void* cv, int njobs, const int* kf_off, const int* kf_members, int cap, int* ids_out, int* n_out) {
   HM_TRY(return static_cast<CmsCovisHostStore*>(cv)->index.local_points(njobs, kf_off, kf_members, cap, ids_out, n_out);)
+}
+
+// ---- Map points (tests/mappoint_hostlib.py): the host build of csrc/cms_mappoint_core.h, the definition of record of cms_mpstore_*.  One handle stands
+// in for the store (hm_mpstore_put: a slot's mp row, octaves, descriptors and camera centre), the index (hm_mpstore_build) and the table; the
+// level scale factors come with the create call.  0, -1 (CMS_ERR_ARG: nothing was written) or -3 (CMS_ERR_UNSUPPORTED).
+extern "C" int hm_mpstore_create(void** out, int max_keyframes, int max_features, int max_members, int max_points, int nlevels, const float* scale_factors) {
+  HM_TRY(
+    if (!out || max_keyframes < 1 || max_features < 1 || max_members < 1 || max_points < 1 || nlevels < 1 || nlevels > 16 || !scale_factors)
+      throw std::runtime_error("hm_mpstore_create: bad argument");
+    *out = new CmsMpHostStore(max_keyframes, max_features, max_members, max_points, nlevels, scale_factors);
+    return 0;)
+}
+extern "C" void hm_mpstore_destroy(void* mp) { delete static_cast<CmsMpHostStore*>(mp); }
+extern "C" int hm_mpstore_put(void* mp, int slot, int n, const int* ids, const int* octave, const uint8_t* desc, const float* Ow) {
+  HM_TRY(return static_cast<CmsMpHostStore*>(mp)->put(slot, n, ids, octave, desc, Ow);)
+}
+extern "C" int hm_mpstore_update_poses(void* mp, int n, const int* slots, const float* Ow) { HM_TRY(return static_cast<CmsMpHostStore*>(mp)->update_poses(n, slots, Ow);) }
+extern "C" int hm_mpstore_update_map_points(void* mp, int n, const int* slot, const int* feat, const int* ids) {
+  HM_TRY(return static_cast<CmsMpHostStore*>(mp)->cv.update_map_points(n, slot, feat, ids);)
+}
+extern "C" int hm_mpstore_build(void* mp, int n_members, const int* member_slots) { HM_TRY(return static_cast<CmsMpHostStore*>(mp)->build(n_members, member_slots);) }
+// the index's observations of an id in member order: up to cap (member, feature, octave) triples into out, their number into n_out
+extern "C" int hm_mpstore_observations(void* mp, int id, int cap, int* out, int* n_out) {
+  HM_TRY(
+    const CmsCovisHost& ix = static_cast<CmsMpHostStore*>(mp)->cv.index;
+    const int u = ix.find(id);
+    *n_out = u < 0 ? 0 : ix.seg[(size_t)u + 1] - ix.seg[(size_t)u];
+    for (int k = 0; k < *n_out && k < cap; ++k) {
+      const CmsCovisHost::Obs& o = ix.obs[(size_t)ix.seg[(size_t)u] + (size_t)k];
+      out[3 * k] = o.member; out[3 * k + 1] = o.feat; out[3 * k + 2] = o.octave;
+    }
+    return 0;)
+}
+extern "C" int hm_mpstore_set(void* mp, int n, const int* ids, const float* pos, const int* ref_slot) { HM_TRY(return static_cast<CmsMpHostStore*>(mp)->set(n, ids, pos, ref_slot);) }
+extern "C" int hm_mpstore_erase(void* mp, int n, const int* ids) { HM_TRY(return static_cast<CmsMpHostStore*>(mp)->erase(n, ids);) }
+extern "C" int hm_mpstore_refresh(void* mp, int n, const int* ids, int what, uint8_t* status) { HM_TRY(return static_cast<CmsMpHostStore*>(mp)->refresh(n, ids, what, status);) }
+extern "C" int hm_mpstore_fetch(void* mp, int n, const int* ids, float* pos, float* normal, float* min_dist, float* max_dist, uint8_t* desc, int* best_member,
+                                int* best_feature) {
+  HM_TRY(return static_cast<CmsMpHostStore*>(mp)->fetch(n, ids, pos, normal, min_dist, max_dist, desc, best_member, best_feature);)
+}
+
+// CubemapSLAM::MapPointStore of the mirror through the named engine (0 = device, 1 = host core): n_kf key frames of n_feat[k] features (mp, octave and
+// descriptor rows concatenated, Tcw 16 floats each) are the members; n_pts points (id, position, reference key frame as an index) are set, refreshed
+// with `what` and fetched: status, normal, distances, descriptor, the best observation's key frame (index or -1) and feature per point.
+extern "C" int hm_mpstore_mirror(int engine, int n_kf, const int* n_feat, const int* mp, const int* octave, const uint8_t* desc, const float* Tcw16, int max_points, int n_pts,
+                                 const int* ids, const float* pos, const int* ref_kf, int what, uint8_t* status, float* normal, float* min_dist, float* max_dist,
+                                 uint8_t* out_desc, int* best_kf, int* best_idx) {
+  HM_TRY(
+    std::vector<KeyFrameView> kfs((size_t)n_kf);
+    std::vector<KeyFrameView*> members;
+    int max_feat = 1;
+    size_t at = 0;
+    for (int k = 0; k < n_kf; ++k) {
+      KeyFrameView& v = kfs[(size_t)k];
+      const int n = n_feat[k];
+      max_feat = std::max(max_feat, n);
+      v.mnId = k + 1;
+      v.mDescriptors = cv::Mat::zeros(std::max(n, 1), 32, cv::CV_8U);
+      v.mvKeys.resize((size_t)n);
+      cv::Vec3f ray;
+      ray.v[0] = 0.f; ray.v[1] = 0.f; ray.v[2] = 1.f;
+      v.mvKeyRays.assign((size_t)n, ray);
+      v.mvpMapPoints.resize((size_t)n);
+      for (int f = 0; f < n; ++f) {
+        v.mvKeys[(size_t)f].pt.x = 10.f + (float)(f % 100); v.mvKeys[(size_t)f].pt.y = 10.f + (float)(f / 100); v.mvKeys[(size_t)f].octave = octave[at + (size_t)f];
+        v.mvpMapPoints[(size_t)f] = mp[at + (size_t)f];
+        std::memcpy(v.mDescriptors.ptr<uint8_t>(f), desc + 32 * (at + (size_t)f), 32);
+      }
+      at += (size_t)n;
+      v.Tcw = cv::Mat::zeros(4, 4, cv::CV_32F);
+      for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) v.Tcw.at<float>(r, c) = Tcw16[16 * (size_t)k + 4 * (size_t)r + (size_t)c];
+      members.push_back(&v);
+    }
+    MapPointStore mps(engine ? MapPointStore::HOST_CORE : MapPointStore::DEVICE, n_kf + 1, max_feat, max_points);
+    mps.Build(members);
+    std::vector<MapPointStore::MapPointView> pts((size_t)n_pts);
+    std::vector<long> lids((size_t)n_pts);
+    for (int i = 0; i < n_pts; ++i) {
+      pts[(size_t)i].id = ids[i]; lids[(size_t)i] = ids[i];
+      std::memcpy(pts[(size_t)i].pos, pos + 3 * (size_t)i, 12);
+      pts[(size_t)i].pRefKF = &kfs[(size_t)ref_kf[i]];
+    }
+    mps.SetMapPoints(pts);
+    const std::vector<unsigned char> st = mps.Refresh(lids, what);
+    const std::vector<MapPointStore::Row> rows = mps.Fetch(lids);
+    for (int i = 0; i < n_pts; ++i) {
+      const MapPointStore::Row& r = rows[(size_t)i];
+      status[i] = st[(size_t)i];
+      std::memcpy(normal + 3 * (size_t)i, r.normal, 12); min_dist[i] = r.minDistance; max_dist[i] = r.maxDistance;
+      std::memcpy(out_desc + 32 * (size_t)i, r.descriptor, 32);
+      best_kf[i] = r.pBestKF ? (int)(r.pBestKF - kfs.data()) : -1; best_idx[i] = r.bestIdx;
+    }
+    return 0;)
 }
 
 // CubemapSLAM::Covisibility of the mirror through the named engine (0 = device, 1 = host core): n_kf key frames of n_feat[k] features (mp and octave rows

@@ -1096,6 +1096,57 @@ int cms_covis_local_points(cms_covis* cv, cms_ctx* src, int njobs, const int* kf
  * first (a (slot, feature) named twice is CMS_ERR_ARG): on an error nothing is written. */
 int cms_kfstore_update_map_points(cms_kfstore* st, int n, const int* slot, const int* feat, const int* mp);
 
+/* ---- Map points on resident key frames: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cpp:243-308) and MapPoint::UpdateNormalAndDepth
+ * (:332-373) from the observation index, and the two per-key-frame consumers of map-point attributes taking ids.  The definition of record is
+ * csrc/cms_mappoint_core.h (DESIGN.md "Map points on the device"): one source, built for the host (hm_mpstore_* of libcubemapslam_host.so) and for
+ * the kernels.  Descriptors, indices and status equal the host core's exactly, normal and bounds bit for bit.
+ *
+ * A cms_mpstore is a TABLE OF ROWS next to one store, indexed directly by the map point's id: 0 <= id < max_points (otherwise CMS_ERR_ARG), the ids
+ * the store's mp rows and a cms_covis hold; a binding hands out rows the way it hands out key-frame slots.  A row holds the world position, the
+ * normal, mfMinDistance / mfMaxDistance, the 32-byte descriptor, mpRefKF as a store slot and the (member, feature) the descriptor came from.
+ *
+ * The observations of an id are the index's entries for it, taken in ASCENDING MEMBER POSITION (the reference iterates a std::map<KeyFrame*, size_t>:
+ * the pointer decides there).  cms_distinctive_descriptors / cms_update_normal_and_depth called with observations listed in member order give the
+ * same results.  The descriptor is the observation of least median Hamming distance, the earliest member on ties; the normal is summed in member
+ * order in k_update_normal_depth's float arithmetic; the bounds come from the observation whose member lives in the reference slot.  Camera centres
+ * are what the store holds when the refresh runs (behind pending cms_kfstore_update_poses); features and octaves are the index's snapshot: a
+ * cms_kfstore_update_map_points is not seen before the next cms_covis_build.
+ *
+ * Every entry checks all its arguments on the host before anything is enqueued (ids in range, an id named twice in set / erase / refresh, a consumer
+ * naming a row without descriptor or normal): on an error nothing is written and cms_last_error names the reason.
+ * Threading: calls on one cms_mpstore are serialised by a mutex in the handle; the store and any cms_covis passed in must outlive the call, and a
+ * refresh also holds the cms_covis's mutex.  set / erase / refresh / fetch and the Fuse entry run on the store's stream. */
+typedef struct cms_mpstore cms_mpstore;
+#define CMS_MP_DESCRIPTOR 1
+#define CMS_MP_NORMAL_DEPTH 2
+int cms_mpstore_create(cms_mpstore** out, cms_kfstore* st, int max_points);
+void cms_mpstore_destroy(cms_mpstore* mp);
+/* n rows named by id: world position (3 floats each, NULL = unchanged) and mpRefKF as a store slot (NULL = unchanged; any slot index of the store).
+ * A row is created by its first set, which wants both.  One kernel reading a pinned block, asynchronous on the store's stream. */
+int cms_mpstore_set(cms_mpstore* mp, int n, const int* ids, const float* pos, const int* ref_slot);
+/* SetBadFlag / Replace: the row is empty again.  Asynchronous like cms_mpstore_set. */
+int cms_mpstore_erase(cms_mpstore* mp, int n, const int* ids);
+/* Rows of n ids (each set, none twice) from the index cv of the same store, one wavefront per map point; what = CMS_MP_DESCRIPTOR, CMS_MP_NORMAL_DEPTH
+ * or both (the reference calls UpdateNormalAndDepth alone after a bundle adjustment).  status[i]: 0 done; 1 the index knows no observation of the id,
+ * the row is untouched (the reference's early return); 2 normal and depth were asked for and the reference slot is not a member that observes the id,
+ * the row is untouched (descriptor included).  Synchronous, one wait. */
+int cms_mpstore_refresh(cms_mpstore* mp, cms_covis* cv, int n, const int* ids, int what, uint8_t* status);
+/* The rows of n ids as the table holds them (MapPoint::mDescriptor, mNormalVector, mfMin/MaxDistance back on the host); any output may be NULL.
+ * An empty row reads zeros, best (-1, -1).  Synchronous. */
+int cms_mpstore_fetch(cms_mpstore* mp, int n, const int* ids, float* pos, float* normal, float* min_dist, float* max_dist, uint8_t* desc,
+                      int* best_member, int* best_feature);
+/* cms_search_local_points with the map points named by id: one gather kernel writes their rows into the staged block, then the unchanged launch
+ * chain.  Every row must hold a descriptor and a normal (CMS_ERR_ARG otherwise).  Table values are the raw mfMinDistance / mfMaxDistance:
+ * cms_set_distance_bounds_mode does not apply.  On ctx's stream, which waits on the device for the table's last write; ctx must be on the store's
+ * device (CMS_ERR_ARG). */
+int cms_search_local_points_ids(cms_ctx* ctx, int b, const float* pose15, cms_mpstore* mp, int nmp, const int* ids, float viewing_cos_limit, float th,
+                                float nnratio, int th_high, int nkp, int* kp_mp, uint8_t* in_view, float* proj_x, float* proj_y, int* level,
+                                float* view_cos, int* mp_match, int* n_matches, int* rounds);
+/* cms_kfstore_fuse_search_sets with the sets' map points named by id (ids: set_off[nsets] entries); mp must belong to st.  Rows and distance bounds
+ * as for cms_search_local_points_ids.  On the store's stream. */
+int cms_kfstore_fuse_search_sets_ids(cms_kfstore* st, cms_mpstore* mp, int nsets, const int* set_off, const int* ids, int njobs, const int* job_slot,
+                                     const int* job_set, const uint8_t* skip, float th, int* best_idx, int* best_dist);
+
 #ifdef __cplusplus
 }
 #endif

@@ -490,15 +490,18 @@ int CreateNewMapPoints(cms_kfstore* store, KeyFrame* pCurrentKF, Map* pMap, std:
 }
 
 namespace {
-void search_in_neighbors_fuse(cms_kfstore* store, KeyFrame* pCurrentKF);
+void search_in_neighbors_fuse(cms_kfstore* store, KeyFrame* pCurrentKF, cms_mpstore* mps, std::vector<MapPoint*>* replaced);
+bool row_ready(cms_mpstore* mps, MapPoint* p);
 }
 void SearchInNeighbors(cms_kfstore* store, KeyFrame* pCurrentKF) {
-  search_in_neighbors_fuse(store, pCurrentKF);
+  search_in_neighbors_fuse(store, pCurrentKF, nullptr, nullptr);
   pCurrentKF->UpdateConnections();
 }
 namespace {
-// LocalMapping.cpp:388-463: everything of SearchInNeighbors but the final UpdateConnections
-void search_in_neighbors_fuse(cms_kfstore* store, KeyFrame* pCurrentKF) {
+// LocalMapping.cpp:388-463: everything of SearchInNeighbors but the final UpdateConnections.  mps (NULL: the points' attributes travel as host arrays):
+// the search takes ids into the table, points without a refreshed row stay out of the sets, `replaced` receives the points Replace made bad, and the
+// update of the current key frame's points (:449-463) is left to the caller, which refreshes their rows
+void search_in_neighbors_fuse(cms_kfstore* store, KeyFrame* pCurrentKF, cms_mpstore* mps, std::vector<MapPoint*>* replaced) {
   StoreBook& b = book(store);
   const int cur = slot_of(b, pCurrentKF);
   if (cur < 0) throw std::runtime_error("Hip::SearchInNeighbors: the current key frame is not resident");
@@ -518,17 +521,24 @@ void search_in_neighbors_fuse(cms_kfstore* store, KeyFrame* pCurrentKF) {
   if (tk.empty()) return;
   // ---- set 0: the current key frame's map points (into every target); set 1: the targets' map points, first appearance (into the current key frame)
   std::vector<MapPoint*> set0, set1;
-  for (MapPoint* p : pCurrentKF->GetMapPointMatches()) if (p) set0.push_back(p);            // (ORBMatcher::Fuse skips null / bad points itself: the skip flags below)
+  for (MapPoint* p : pCurrentKF->GetMapPointMatches())
+    if (p && (!mps || row_ready(mps, p))) set0.push_back(p);                                // (ORBMatcher::Fuse skips null / bad points itself: the skip flags below)
   for (KeyFrame* k : tk)
     for (MapPoint* p : k->GetMapPointMatches()) {
       if (!p || p->isBad() || p->mnFuseCandidateForKF == pCurrentKF->mnId) continue;        // LocalMapping.cpp:432-447
       p->mnFuseCandidateForKF = pCurrentKF->mnId;
-      set1.push_back(p);
+      if (!mps || row_ready(mps, p)) set1.push_back(p);
     }
   std::vector<float> pos, nrm, dmin, dmax;
   std::vector<uint8_t> desc;
-  for (MapPoint* p : set0) push_point(p, pos, nrm, dmin, dmax, desc);
-  for (MapPoint* p : set1) push_point(p, pos, nrm, dmin, dmax, desc);
+  std::vector<int> ids;
+  if (mps) {
+    for (MapPoint* p : set0) ids.push_back((int)p->mnId);
+    for (MapPoint* p : set1) ids.push_back((int)p->mnId);
+  } else {
+    for (MapPoint* p : set0) push_point(p, pos, nrm, dmin, dmax, desc);
+    for (MapPoint* p : set1) push_point(p, pos, nrm, dmin, dmax, desc);
+  }
   const int set_off[3] = {0, (int)set0.size(), (int)(set0.size() + set1.size())};
   // ---- jobs: set 0 into every target, set 1 into the current key frame; an entry is skipped like ORBMatcher.cpp:1143-1147 skips it
   std::vector<int> job_slot, job_set;
@@ -541,8 +551,12 @@ void search_in_neighbors_fuse(cms_kfstore* store, KeyFrame* pCurrentKF) {
   for (MapPoint* p : set1) skip.push_back((p->isBad() || p->IsInKeyFrame(pCurrentKF)) ? 1 : 0);
   // the searched key frames' map-point slots as they are NOW (the search only needs the key points; the decisions below read the live objects)
   std::vector<int> best_idx(skip.size()), best_dist(skip.size());
-  check(cms_kfstore_fuse_search_sets(store, 2, set_off, pos.data(), nrm.data(), dmin.data(), dmax.data(), desc.data(), (int)job_slot.size(), job_slot.data(),
-                                     job_set.data(), skip.data(), 3.0f, best_idx.data(), best_dist.data()), "cms_kfstore_fuse_search_sets");
+  if (mps)
+    check(cms_kfstore_fuse_search_sets_ids(store, mps, 2, set_off, ids.data(), (int)job_slot.size(), job_slot.data(), job_set.data(), skip.data(), 3.0f,
+                                           best_idx.data(), best_dist.data()), "cms_kfstore_fuse_search_sets_ids");
+  else
+    check(cms_kfstore_fuse_search_sets(store, 2, set_off, pos.data(), nrm.data(), dmin.data(), dmax.data(), desc.data(), (int)job_slot.size(), job_slot.data(),
+                                       job_set.data(), skip.data(), 3.0f, best_idx.data(), best_dist.data()), "cms_kfstore_fuse_search_sets");
   // ---- the decisions, job after job and point after point in the reference's order (ORBMatcher.cpp:1213-1236).  A point that an earlier job of this
   // call added to / replaced in a later job's key frame is re-checked here exactly like the reference's sequential Fuse calls would see it
   size_t e = 0;
@@ -555,8 +569,9 @@ void search_in_neighbors_fuse(cms_kfstore* store, KeyFrame* pCurrentKF) {
       MapPoint* pMPinKF = pKF->GetMapPoint(best_idx[e]);
       if (pMPinKF) {
         if (!pMPinKF->isBad()) {
-          if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
-          else pMPinKF->Replace(pMP);
+          MapPoint* gone = pMPinKF->Observations() > pMP->Observations() ? pMP : pMPinKF;
+          gone->Replace(gone == pMP ? pMPinKF : pMP);
+          if (replaced) replaced->push_back(gone);
         }
       } else {
         pMP->AddObservation(pKF, best_idx[e]);
@@ -565,6 +580,7 @@ void search_in_neighbors_fuse(cms_kfstore* store, KeyFrame* pCurrentKF) {
     }
   }
   // ---- update points and connections (LocalMapping.cpp:449-465)
+  if (mps) return;                                                 // (the caller refreshes the rows once the index has seen the fusion)
   for (MapPoint* p : pCurrentKF->GetMapPointMatches())
     if (p && !p->isBad()) { p->ComputeDistinctiveDescriptors(); p->UpdateNormalAndDepth(); }
 }
@@ -638,7 +654,7 @@ Connections UpdateConnections(cms_kfstore* store, cms_covis* covis, KeyFrame* pK
 }
 
 Connections SearchInNeighbors(cms_kfstore* store, cms_covis* covis, KeyFrame* pCurrentKF) {
-  search_in_neighbors_fuse(store, pCurrentKF);
+  search_in_neighbors_fuse(store, pCurrentKF, nullptr, nullptr);
   return UpdateConnections(store, covis, pCurrentKF);
 }
 
@@ -718,6 +734,156 @@ void UpdateLocalMap(cms_covis* covis, cms_ctx* frameCtx, Frame& F, std::vector<K
     const auto it = c.point.find(out[(size_t)i]);
     if (it != c.point.end() && !it->second->isBad()) vpLocalMapPoints.push_back(it->second);
   }
+}
+
+// ------------------------------------------------------------------------------------------------ Map points on the device
+namespace {
+// a table's store and capacity, and which rows hold what: `set` by Hip::SetMapPoints, `ready` once a refresh has given the row a descriptor AND
+// normal and depth (what the two consumers ask for).  Erased rows leave both.
+struct MpBook { cms_kfstore* store = nullptr; int max_points = 0; std::set<int> set, has_desc, has_normal; std::mutex mu; };
+std::map<cms_mpstore*, MpBook> g_mp_books;
+std::mutex g_mp_books_mutex;
+MpBook& mp_book(cms_mpstore* mps) { std::lock_guard<std::mutex> lk(g_mp_books_mutex); return g_mp_books[mps]; }
+// the row of a map point, -1: its mnId does not fit the table
+int row_of(const MpBook& m, MapPoint* p) { return p->mnId < (long unsigned int)m.max_points ? (int)p->mnId : -1; }
+bool row_ready(cms_mpstore* mps, MapPoint* p) {
+  MpBook& m = mp_book(mps);
+  std::lock_guard<std::mutex> lk(m.mu);
+  const int r = row_of(m, p);
+  return r >= 0 && !p->isBad() && m.has_desc.count(r) && m.has_normal.count(r);
+}
+}  // namespace
+
+cms_mpstore* CreateMapPointStore(cms_kfstore* store, int maxPoints) {
+  cms_mpstore* mps = nullptr;
+  check(cms_mpstore_create(&mps, store, maxPoints), "cms_mpstore_create");
+  MpBook& m = mp_book(mps);
+  std::lock_guard<std::mutex> lk(m.mu);
+  m.store = store; m.max_points = maxPoints;
+  return mps;
+}
+
+int SetMapPoints(cms_mpstore* mps, const std::vector<MapPoint*>& vpMPs) {
+  MpBook& m = mp_book(mps);
+  std::lock_guard<std::mutex> lk(m.mu);
+  StoreBook& b = book(m.store);
+  std::vector<int> ids, ref;
+  std::vector<float> pos;
+  std::set<int> named;
+  for (MapPoint* p : vpMPs) {
+    if (!p || p->isBad()) continue;
+    const int r = row_of(m, p);
+    if (r < 0) throw std::runtime_error("Hip::SetMapPoints: a map point's mnId is beyond the table (Hip::CreateMapPointStore's maxPoints)");
+    KeyFrame* pRef = p->GetReferenceKeyFrame();
+    const int s = pRef ? slot_of(b, pRef) : -1;
+    if (s < 0 || !named.insert(r).second) continue;               // (the reference key frame is not resident; or the point is listed twice)
+    const cv::Mat x = p->GetWorldPos();
+    ids.push_back(r); ref.push_back(s);
+    for (int k = 0; k < 3; ++k) pos.push_back(x.at<float>(k));
+  }
+  if (ids.empty()) return 0;
+  check(cms_mpstore_set(mps, (int)ids.size(), ids.data(), pos.data(), ref.data()), "cms_mpstore_set");
+  m.set.insert(ids.begin(), ids.end());
+  return (int)ids.size();
+}
+
+void EraseMapPoints(cms_mpstore* mps, const std::vector<MapPoint*>& vpMPs) {
+  MpBook& m = mp_book(mps);
+  std::lock_guard<std::mutex> lk(m.mu);
+  std::vector<int> ids;
+  std::set<int> named;
+  for (MapPoint* p : vpMPs) {
+    if (!p) continue;
+    const int r = row_of(m, p);
+    if (r >= 0 && m.set.count(r) && named.insert(r).second) ids.push_back(r);
+  }
+  if (ids.empty()) return;
+  check(cms_mpstore_erase(mps, (int)ids.size(), ids.data()), "cms_mpstore_erase");
+  for (int r : ids) { m.set.erase(r); m.has_desc.erase(r); m.has_normal.erase(r); }
+}
+
+std::vector<MapPointAttributes> RefreshMapPoints(cms_mpstore* mps, cms_covis* covis, const std::vector<MapPoint*>& vpMPs, int what) {
+  MpBook& m = mp_book(mps);
+  std::lock_guard<std::mutex> lk(m.mu);
+  std::vector<MapPointAttributes> out;
+  std::vector<int> ids;
+  std::set<int> named;
+  for (MapPoint* p : vpMPs) {
+    if (!p || p->isBad()) continue;
+    const int r = row_of(m, p);
+    if (r < 0 || !m.set.count(r) || !named.insert(r).second) continue;
+    MapPointAttributes a;
+    a.pMP = p; a.status = 0; a.minDistance = 0.0f; a.maxDistance = 0.0f;
+    out.push_back(a); ids.push_back(r);
+  }
+  const size_t n = ids.size();
+  if (n == 0) return out;
+  std::vector<uint8_t> status(n), desc(32 * n);
+  std::vector<float> nrm(3 * n), dmin(n), dmax(n);
+  check(cms_mpstore_refresh(mps, covis, (int)n, ids.data(), what, status.data()), "cms_mpstore_refresh");
+  check(cms_mpstore_fetch(mps, (int)n, ids.data(), nullptr, nrm.data(), dmin.data(), dmax.data(), desc.data(), nullptr, nullptr), "cms_mpstore_fetch");
+  for (size_t i = 0; i < n; ++i) {
+    MapPointAttributes& a = out[i];
+    a.status = status[i];
+    a.descriptor = cv::Mat(1, 32, CV_8U);
+    std::memcpy(a.descriptor.data, &desc[32 * i], 32);
+    a.normal = cv::Mat(3, 1, CV_32F);
+    for (int k = 0; k < 3; ++k) a.normal.at<float>(k) = nrm[3 * i + k];
+    a.minDistance = dmin[i]; a.maxDistance = dmax[i];
+    if (status[i] == 0) {
+      if (what & CMS_MP_DESCRIPTOR) m.has_desc.insert(ids[i]);
+      if (what & CMS_MP_NORMAL_DEPTH) m.has_normal.insert(ids[i]);
+    }
+  }
+  return out;
+}
+
+int SearchLocalPoints(cms_ctx* ctx, cms_mpstore* mps, Frame& F, const std::vector<MapPoint*>& vpMapPoints, float th) {
+  // the caller (Tracking::SearchLocalPoints, Tracking.cpp:797-822) has removed the points already matched in the frame and the bad ones
+  const int n = (int)vpMapPoints.size();
+  std::vector<float> px(n), py(n), vc(n);
+  std::vector<uint8_t> inview(n);
+  std::vector<int> ids(n), level(n), match(n);
+  {
+    MpBook& m = mp_book(mps);
+    std::lock_guard<std::mutex> lk(m.mu);
+    for (int i = 0; i < n; ++i) {
+      ids[i] = row_of(m, vpMapPoints[i]);
+      if (ids[i] < 0) throw std::runtime_error("Hip::SearchLocalPoints: a map point's mnId is beyond the table");
+    }
+  }
+  float pose15[15];
+  for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) pose15[3 * r + c] = F.mTcw.at<float>(r, c); pose15[9 + r] = F.mTcw.at<float>(r, 3); }
+  const cv::Mat Ow = F.GetCameraCenter();
+  for (int k = 0; k < 3; ++k) pose15[12 + k] = Ow.at<float>(k);
+  std::vector<int> kp_mp(F.N);
+  for (int i = 0; i < F.N; ++i) { MapPoint* p = F.mvpMapPoints[i]; kp_mp[i] = (p && p->Observations() > 0) ? (1 << 30) : -1; }   // ORBMatcher.cpp:91-95
+  int nm = 0;
+  check(cms_search_local_points_ids(ctx, 0, pose15, mps, n, ids.data(), 0.5f, th, 0.8f, ORBMatcher::TH_HIGH, F.N, kp_mp.data(), inview.data(), px.data(), py.data(),
+                                    level.data(), vc.data(), match.data(), &nm, nullptr), "cms_search_local_points_ids");
+  for (int i = 0; i < n; ++i) {                                    // what Frame::isInFrustum leaves on the MapPoint (Frame.cpp:199-248) ...
+    MapPoint* p = vpMapPoints[i];
+    p->mbTrackInView = inview[i] != 0;
+    if (!inview[i]) continue;
+    p->mTrackProjX = px[i]; p->mTrackProjY = py[i]; p->mnTrackScaleLevel = level[i]; p->mTrackViewCos = vc[i];
+    p->IncreaseVisible();                                          // Tracking.cpp:829
+    if (match[i] >= 0) F.mvpMapPoints[match[i]] = p;               // ... and what the matcher leaves in the frame (ORBMatcher.cpp:121)
+  }
+  return nm;
+}
+
+Connections SearchInNeighbors(cms_kfstore* store, cms_covis* covis, cms_mpstore* mps, KeyFrame* pCurrentKF, std::vector<MapPointAttributes>& refreshed) {
+  std::vector<MapPoint*> replaced;
+  search_in_neighbors_fuse(store, pCurrentKF, mps, &replaced);
+  EraseMapPoints(mps, replaced);
+  std::vector<KeyFrame*> members;
+  { CovisBook& c = covis_book(covis); std::lock_guard<std::mutex> lk(c.mu); members = c.members; }
+  BuildCovisibility(store, covis, members);                        // the index sees the fusion: AddObservation, Replace
+  std::vector<MapPoint*> mine;
+  for (MapPoint* p : pCurrentKF->GetMapPointMatches()) if (p && !p->isBad()) mine.push_back(p);      // LocalMapping.cpp:452-463
+  SetMapPoints(mps, mine);                                         // (Replace may have moved mpRefKF)
+  refreshed = RefreshMapPoints(mps, covis, mine, CMS_MP_DESCRIPTOR | CMS_MP_NORMAL_DEPTH);
+  return UpdateConnections(store, covis, pCurrentKF);
 }
 
 void UpdateKeyFramePoses(cms_kfstore* store, const std::vector<KeyFrame*>& vpKFs) {

@@ -91,6 +91,33 @@ std::vector<KeyFrame*> KeyFrameCulling(cms_kfstore* store, cms_covis* covis, Key
 // the reference key frame (NULL: no votes), vpLocalMapPoints the points of the local key frames in the reference's order -- the list
 // Hip::SearchLocalPoints then gathers positions for.  Bad map points of F are set to NULL like :896-899.
 void UpdateLocalMap(cms_covis* covis, cms_ctx* frameCtx, Frame& F, std::vector<KeyFrame*>& vpLocalKeyFrames, KeyFrame*& pKFmax, std::vector<MapPoint*>& vpLocalMapPoints);
+// ---- Map points on the device (cms_mpstore_*): MapPoint::ComputeDistinctiveDescriptors (MapPoint.cpp:243-308) and MapPoint::UpdateNormalAndDepth
+// (:332-373) from the observation index, and the two per-key-frame consumers taking ids.  A map point's row is its mnId, which must be below maxPoints
+// (the ids the key frames' rows and the index hold: mnId & 0x3FFFFFFF).  Observations are taken in the member order of the last BuildCovisibility, where
+// the reference lets the pointer decide.
+cms_mpstore* CreateMapPointStore(cms_kfstore* store, int maxPoints);
+// pMP->SetWorldPos / mpRefKF as the table holds them: GetWorldPos() and GetReferenceKeyFrame() through the store's KeyFrame* -> slot book, ONE asynchronous
+// cms_mpstore_set.  Bad points and points whose reference key frame is not resident are left out; returns how many were set.  Call it for the points
+// CreateNewMapPoints made, and for the points a bundle adjustment moved.
+int SetMapPoints(cms_mpstore* mps, const std::vector<MapPoint*>& vpMPs);
+// MapPoint::SetBadFlag / Replace: the rows are empty again (one asynchronous cms_mpstore_erase)
+void EraseMapPoints(cms_mpstore* mps, const std::vector<MapPoint*>& vpMPs);
+// What a refresh leaves in a row: mDescriptor, mNormalVector, mfMinDistance, mfMaxDistance.  The members are protected, so MapPoint gains one setter
+// that takes this struct (integration/README.md).  status: 0 done, 1 no observation in the index, 2 the reference key frame does not observe the point
+// (1 and 2: the row, and the attributes here, are what they were).
+struct MapPointAttributes { MapPoint* pMP; int status; cv::Mat descriptor, normal; float minDistance, maxDistance; };
+// pMP->ComputeDistinctiveDescriptors() and / or pMP->UpdateNormalAndDepth() for every listed point that is set, in ONE cms_mpstore_refresh
+// (what = CMS_MP_DESCRIPTOR | CMS_MP_NORMAL_DEPTH, or one of them: the reference calls UpdateNormalAndDepth alone after a bundle adjustment) and one
+// cms_mpstore_fetch.  `covis`: the index after the step's BuildCovisibility.  Points that were never set are left out of the result.
+std::vector<MapPointAttributes> RefreshMapPoints(cms_mpstore* mps, cms_covis* covis, const std::vector<MapPoint*>& vpMPs, int what = CMS_MP_DESCRIPTOR | CMS_MP_NORMAL_DEPTH);
+// Tracking::SearchLocalPoints on rows of the table: only ids travel (cms_search_local_points_ids).  Every listed point must hold a refreshed row; the
+// table's raw mfMinDistance / mfMaxDistance are used, whatever cms_set_distance_bounds_mode says.
+int SearchLocalPoints(cms_ctx* ctx, cms_mpstore* mps, Frame& F, const std::vector<MapPoint*>& vpMapPoints, float th);
+// LocalMapping::SearchInNeighbors on rows of the table: the Fuse search takes ids (cms_kfstore_fuse_search_sets_ids); points without a refreshed row are
+// left out of the search.  Behind the reference's decisions the replaced points' rows are erased, the index is rebuilt over the members of the last
+// BuildCovisibility, and the current key frame's points are set and refreshed (LocalMapping.cpp:449-463) -- `refreshed` receives their attributes --
+// before UpdateConnections.
+Connections SearchInNeighbors(cms_kfstore* store, cms_covis* covis, cms_mpstore* mps, KeyFrame* pCurrentKF, std::vector<MapPointAttributes>& refreshed);
 // ---- Tracking's SearchByBoW(KeyFrame*, Frame&, ...) (ORBMatcher.cpp:409-539) against key frames resident in `store`, on the FRAME thread: F is the frame
 // `frameCtx` extracted last (slot 0 of its batch) after F.ComputeBoW().  The slot comes from the store's KeyFrame* -> slot book; a key-frame feature takes
 // part where the slot's map-point entry (as ProcessNewKeyFrame / CreateNewMapPoints last wrote it) is set and GetMapPointMatches() still holds a point

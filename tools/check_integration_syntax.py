@@ -47,7 +47,10 @@ def main(ref_inc):
                                                ("CubemapHipBridge.cpp", "cms_kfstore_search_by_sim3(store, ctx, (int)jobs.size(),", "cms_kfstore_search_by_sim3(store, (int)jobs.size(),"),
                                                ("CubemapHipBridge.cpp", "cms_kfstore_fuse_search_sim3(store, ctx, 1, set_off,", "cms_kfstore_fuse_search_sim3(store, 1, set_off,"),
                                                ("CubemapHipBridge.cpp", "cms_covis_votes(covis, frameCtx, 1, id_off,", "cms_covis_votes(covis, 1, id_off,"),
-                                               ("CubemapHipBridge.cpp", "cms_kfstore_update_map_points(store, (int)up_slot.size(),", "cms_kfstore_update_map_points(store,"))):
+                                               ("CubemapHipBridge.cpp", "cms_kfstore_update_map_points(store, (int)up_slot.size(),", "cms_kfstore_update_map_points(store,"),
+                                               ("CubemapHipBridge.cpp", "cms_mpstore_refresh(mps, covis, (int)n,", "cms_mpstore_refresh(mps, (int)n,"),
+                                               ("CubemapHipBridge.cpp", "cms_search_local_points_ids(ctx, 0, pose15, mps, n,", "cms_search_local_points_ids(ctx, 0, pose15, n,"),
+                                               ("CubemapHipBridge.cpp", "cms_kfstore_fuse_search_sets_ids(store, mps, 2, set_off,", "cms_kfstore_fuse_search_sets_ids(store, 2, set_off,"))):
             d = os.path.join(td, "broken_%d" % i)
             shutil.copytree(os.path.join(ROOT, "integration"), d)
             src = open(os.path.join(d, fname)).read()
