@@ -1309,6 +1309,73 @@ class Covisibility(_Handle):
             _chk(rc, "cms_covis_local_points")
         return rc, n_out[:nj], [[int(v) for v in ids[j, :min(int(n_out[j]), int(cap))]] for j in range(nj)]
 
+    def local_ba_windows(self, mps, jobs, cap_kf, cap_points, cap_edges, pinned=False, out=None):
+        """cms_covis_local_ba_windows: the local BA windows of `jobs` ((local members in the reference's order, first_member or -1) each) from this
+        index, its store and the MapPointStore mps.  -> one dict per job in synth.ba_problem's layout (poses, fixed, points, e_pose, e_point, e_obs,
+        e_invsig2, e_face, fx, fy, cx, cy: what BundleAdjuster and ba_run take) plus kf_member, point_id, e_feat and counts.  pinned: the arrays lie
+        in pinned memory the kernels store into, and the dicts carry _pinned (ba_window_array sets CMS_BA_INPUTS_PINNED).  out: arrays of
+        ba_window_arrays() to fill instead of fresh ones (a refused call must leave them as they are).  CMS_ERR_OVERFLOW raises CmsOverflow with the
+        counts of every job in .counts."""
+        L = lib()
+        L.cms_covis_local_ba_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 12
+        nj = len(jobs)
+        arr = (BaWindowJob * max(nj, 1))()
+        keep = []
+        for q, (members, first) in zip(arr, jobs):
+            m = np.ascontiguousarray(members, np.int32).reshape(-1)
+            keep.append(m)
+            q.n_local = len(m); q.local_members = m.ctypes.data if len(m) else None; q.first_member = int(first)
+        o = out if out is not None else ba_window_arrays(nj, cap_kf, cap_points, cap_edges, pinned)
+        rc = L.cms_covis_local_ba_windows(self.h, mps.h, nj, arr, int(cap_kf), int(cap_points), int(cap_edges),
+                                          *[_p(o[k]) for k in ("counts",) + BA_WINDOW_ARRAYS])
+        if rc == -4:
+            e = CmsOverflow(lib().cms_last_error().decode())
+            e.counts = o["counts"][:nj].copy()
+            raise e
+        _chk(rc, "cms_covis_local_ba_windows")
+        f = self.store.ctx.geom.F / 2.0
+        res = []
+        for j in range(nj):
+            K, _, P, E = (int(v) for v in o["counts"][j])
+            w = dict(poses=o["poses"][j, :K], fixed=o["fixed"][j, :K], points=o["points"][j, :P], e_pose=o["e_pose"][j, :E], e_point=o["e_point"][j, :E],
+                     e_obs=o["e_obs"][j, :E], e_invsig2=o["e_invsig2"][j, :E], e_face=o["e_face"][j, :E], fx=f, fy=f, cx=f, cy=f,
+                     kf_member=o["kf_member"][j, :K], point_id=o["point_id"][j, :P], e_feat=o["e_feat"][j, :E], counts=o["counts"][j].copy())
+            if pinned:
+                w["_pinned"] = o["_pinned"]
+            res.append(w)
+        return res
+
+
+class BaWindowJob(C.Structure):      # cms_ba_window_job (include/cubemapslam_hip.h)
+    _fields_ = [("n_local", C.c_int), ("local_members", C.c_void_p), ("first_member", C.c_int)]
+
+
+class CmsOverflow(Exception):
+    """CMS_ERR_OVERFLOW of an entry that still delivers its counts"""
+
+
+BA_WINDOW_ARRAYS = ("kf_member", "point_id", "poses", "fixed", "points", "e_pose", "e_point", "e_obs", "e_invsig2", "e_face", "e_feat")
+
+
+def ba_window_arrays(njobs, cap_kf, cap_points, cap_edges, pinned=False, fill=0):
+    """the output arrays of cms_covis_local_ba_windows for njobs jobs, every byte `fill`; pinned: views of PinnedArray blocks kept under _pinned"""
+    nj, ck, cp, ce = max(int(njobs), 1), int(cap_kf), int(cap_points), int(cap_edges)
+    spec = dict(counts=((nj, 4), np.int32), kf_member=((nj, ck), np.int32), point_id=((nj, cp), np.int32), poses=((nj, ck, 7), np.float64), fixed=((nj, ck), np.uint8),
+                points=((nj, cp, 3), np.float64), e_pose=((nj, ce), np.int32), e_point=((nj, ce), np.int32), e_obs=((nj, ce, 2), np.float64),
+                e_invsig2=((nj, ce), np.float64), e_face=((nj, ce), np.int8), e_feat=((nj, ce), np.int32))
+    o = dict(_pinned=[])
+    for k, (shape, dt) in spec.items():
+        nbytes = int(np.prod(shape)) * np.dtype(dt).itemsize
+        if pinned and k != "counts":
+            pa = PinnedArray((max(nbytes, 16),))
+            o["_pinned"].append(pa)
+            raw = pa.array[:nbytes]
+        else:
+            raw = np.empty(nbytes, np.uint8)
+        raw[...] = fill
+        o[k] = raw.view(dt).reshape(shape)
+    return o
+
 
 MP_DESCRIPTOR, MP_NORMAL_DEPTH = 1, 2
 

@@ -14,6 +14,7 @@ struct cms_covis {
   bool built = false;
   int M = 0, bits = 8;
   size_t sum_n = 0;                         // the members' features: the bound of observations and of ids
+  std::vector<int> h_n;                     // features per member at the last build (cms_covis_local_ba_windows sizes its point lists by them)
   // capacities: members, table entries, observations
   size_t cap_m = 0, cap_rows = 0, cap_h = 0, cap_o = 0, cap_of = 0, cap_dec = 0;
   int* d_slot = nullptr; int* d_n = nullptr; int* d_snap_u = nullptr; int* d_snap_oct = nullptr;
@@ -88,7 +89,7 @@ extern "C" int cms_covis_build(cms_covis* cv, int n_members, const int* member_s
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(kfstore_order_behind_puts(st));
   hipStream_t s = c->stream;
-  if (M == 0) { cv->M = 0; cv->sum_n = 0; cv->built = true; HIPCHK(hipEventRecord(cv->built_ev, s)); return CMS_OK; }
+  if (M == 0) { cv->M = 0; cv->sum_n = 0; cv->h_n.clear(); cv->built = true; HIPCHK(hipEventRecord(cv->built_ev, s)); return CMS_OK; }
   // ---- the rows first: a row that names an id twice refuses the build before anything of the index is touched
   CmsBlock blk;
   const size_t o_slot = blk.take(4 * M), o_n = blk.take(4 * M), o_flag = blk.take(4), in_bytes = blk.size;
@@ -141,6 +142,7 @@ extern "C" int cms_covis_build(cms_covis* cv, int n_members, const int* member_s
   }
   HIPCHK(hipEventRecord(cv->built_ev, s));
   cv->M = n_members; cv->bits = bits; cv->sum_n = sum_n; cv->built = true;
+  cv->h_n.assign(h_n, h_n + M);      // (the stage's pinned block still holds them: nothing has reserved it since)
   return CMS_OK;
 }
 

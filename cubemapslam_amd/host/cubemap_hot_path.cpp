@@ -14,6 +14,7 @@
 #include "../csrc/cms_kfdb_core.h"
 #include "../csrc/cms_covis_core.h"
 #include "../csrc/cms_mappoint_core.h"
+#include "../csrc/cms_ba_window_core.h"
 #include "../csrc/cms_ess_graph_core.h"      // CmsS3 and Sim3(R, t, s) for vScw
 #include "../csrc/cms_ess_graph_job_check.h" // the envelope count for the handle
 #include "../csrc/cms_sim3_core.h"      // the gemm rule (cms_sim3_row) and TransformRaysToCubemap for the constructor's filter
@@ -2011,6 +2012,124 @@ std::vector<MapPointStore::Row> MapPointStore::Fetch(const std::vector<long>& id
     r.bestIdx = bf[i];
   }
   return out;
+}
+
+// ---- the local BA window from the resident stores (src/Optimizer.cpp:194-357; csrc/cms_ba_window_core.h)
+MapPointStore::BAWindow MapPointStore::LocalBAWindow(const std::vector<KeyFrameView*>& lLocalKeyFrames) {
+  Impl& m = *impl_;
+  const size_t M = m.members.size();
+  std::vector<int> local(lLocalKeyFrames.size() + 1);
+  size_t cap_points = 1;
+  for (size_t i = 0; i < lLocalKeyFrames.size(); ++i) {
+    auto it = m.pos_of.find(lLocalKeyFrames[i]);
+    if (it == m.pos_of.end()) throw std::runtime_error("MapPointStore::LocalBAWindow: a key frame is not a member of the last Build");
+    local[i] = it->second;
+    cap_points += lLocalKeyFrames[i]->mvKeys.size();
+  }
+  int first = -1;
+  for (size_t i = 0; i < M; ++i) if (m.members[i]->mnId == 0) first = (int)i;
+  const int cap_kf = (int)std::max(M, (size_t)1);
+  size_t cap_edges = 8 * cap_points;
+  CmsBaWindowCounts n = {0, 0, 0, 0};
+  std::vector<int> kf_member((size_t)cap_kf), point_id(cap_points);
+  BAWindow w;
+  for (int attempt = 0; attempt < 2; ++attempt) {      // (the edges' number is not known before the first call: a second one with the counted size)
+    w.poses.assign(7 * (size_t)cap_kf, 0.0); w.fixed.assign((size_t)cap_kf, 0); w.points.assign(3 * cap_points, 0.0);
+    w.e_pose.assign(cap_edges, 0); w.e_point.assign(cap_edges, 0); w.e_obs.assign(2 * cap_edges, 0.0); w.e_invsig2.assign(cap_edges, 0.0); w.e_face.assign(cap_edges, 0);
+    w.e_feat.assign(cap_edges, 0);
+    int rc;
+    if (m.engine == HOST_CORE) {
+      if (!m.host) throw std::runtime_error("MapPointStore::LocalBAWindow: no Build yet");
+      const cms_orb_params orb = Impl::orb();
+      const CamModelGeneral* cam = CamModelGeneral::GetCamera();
+      CmsBaWindowHostData D;
+      D.F = cam->GetCubeFaceWidth(); D.cos_fov = cam->GetCosFovTh();
+      float sc = 1.0f;      // mvInvLevelSigma2 as cms_ctx_create forms it
+      for (int l = 0; l < 16; ++l) {
+        if (l > 0) sc = (float)(sc * (double)orb.scale_factor);
+        D.inv_sigma2[l] = l < orb.nlevels ? 1.0f / (l == 0 ? 1.0f : sc * sc) : 0.0f;
+      }
+      D.kx.resize(M); D.ky.resize(M); D.ray_z.resize(M); D.Rcw.resize(9 * M); D.tcw.resize(3 * M);
+      for (size_t i = 0; i < M; ++i) {
+        const KeyFrameView& k = *m.members[i];
+        for (size_t f = 0; f < k.mvKeys.size(); ++f) { D.kx[i].push_back(k.mvKeys[f].pt.x); D.ky[i].push_back(k.mvKeys[f].pt.y); D.ray_z[i].push_back(k.mvKeyRays[f](2)); }
+        float Ow[3];
+        pose15_from_Tcw(k.Tcw, &D.Rcw[9 * i], &D.tcw[3 * i], Ow);
+      }
+      D.has_pos.resize(m.host->rows.size()); D.pos.resize(3 * m.host->rows.size());
+      for (size_t i = 0; i < m.host->rows.size(); ++i) { D.has_pos[i] = m.host->rows[i].state & 1; std::memcpy(&D.pos[3 * i], m.host->rows[i].pos, 12); }
+      const CmsBaWindowHostJob job = {(int)lLocalKeyFrames.size(), local.data(), first};
+      const CmsBaWindowHostOut o = {cap_kf, (int)cap_points, (int)cap_edges, &n, kf_member.data(), point_id.data(), w.poses.data(), w.fixed.data(), w.points.data(),
+                                    w.e_pose.data(), w.e_point.data(), w.e_obs.data(), w.e_invsig2.data(), w.e_face.data(), w.e_feat.data()};
+      std::string why;
+      rc = cms_ba_window_host(m.host->cv.index, D, 1, &job, o, &why);
+      if (rc == -1) throw std::runtime_error("MapPointStore::LocalBAWindow: " + why);
+    } else {
+      std::lock_guard<std::mutex> lock(g_ctx_mutex);
+      if (!m.mp) throw std::runtime_error("MapPointStore::LocalBAWindow: no Build yet");
+      const cms_ba_window_job job = {(int)lLocalKeyFrames.size(), local.data(), first};
+      cms_ba_window_counts c = {0, 0, 0, 0};
+      rc = cms_covis_local_ba_windows(m.cv, m.mp, 1, &job, cap_kf, (int)cap_points, (int)cap_edges, &c, kf_member.data(), point_id.data(), w.poses.data(), w.fixed.data(),
+                                      w.points.data(), w.e_pose.data(), w.e_point.data(), w.e_obs.data(), w.e_invsig2.data(), w.e_face.data(), w.e_feat.data());
+      if (rc != CMS_OK && rc != CMS_ERR_OVERFLOW) Impl::fail("cms_covis_local_ba_windows");
+      n = CmsBaWindowCounts{c.K, c.n_local, c.P, c.E};
+    }
+    if (rc == 0) break;
+    if (attempt == 1 || n.K > cap_kf || (size_t)n.P > cap_points) throw std::runtime_error("MapPointStore::LocalBAWindow: the window does not fit its own bounds");
+    cap_edges = (size_t)n.E;
+  }
+  w.nLocal = n.n_local;
+  w.poses.resize(7 * (size_t)n.K); w.fixed.resize((size_t)n.K); w.points.resize(3 * (size_t)n.P);
+  w.e_pose.resize((size_t)n.E); w.e_point.resize((size_t)n.E); w.e_obs.resize(2 * (size_t)n.E); w.e_invsig2.resize((size_t)n.E); w.e_face.resize((size_t)n.E); w.e_feat.resize((size_t)n.E);
+  for (int k = 0; k < n.K; ++k) w.keyframes.push_back(m.members[(size_t)kf_member[(size_t)k]]);
+  w.point_id.assign(point_id.begin(), point_id.begin() + n.P);
+  return w;
+}
+
+void MapPointStore::WriteBack(const BAWindow& w) {
+  Impl& m = *impl_;
+  std::vector<int> slots, ids, ref;
+  std::vector<float> R, t, Ow, pos;
+  for (size_t k = 0; k < w.keyframes.size(); ++k) {   // Converter::toCvMat(SE3Quat) -> float 4x4 (Converter.cpp:53-104)
+    if (w.fixed[k]) continue;                          // the reference rewrites local key frames only (:432-438)
+    const double* q = &w.poses[7 * k + 3];
+    const double x = q[0], y = q[1], z = q[2], s = q[3];
+    const double Rd[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * s), 2 * (x * z + y * s), 2 * (x * y + z * s), 1 - 2 * (x * x + z * z),
+                          2 * (y * z - x * s), 2 * (x * z - y * s), 2 * (y * z + x * s), 1 - 2 * (x * x + y * y)};
+    cv::Mat& T = w.keyframes[k]->Tcw;
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) T.at<float>(r, c) = (float)Rd[3 * r + c]; T.at<float>(r, 3) = (float)w.poses[7 * k + r]; }
+    float Rf[9], tf[3], Of[3];
+    pose15_from_Tcw(T, Rf, tf, Of);
+    slots.push_back(m.pos_of.at(w.keyframes[k]));
+    R.insert(R.end(), Rf, Rf + 9); t.insert(t.end(), tf, tf + 3); Ow.insert(Ow.end(), Of, Of + 3);
+  }
+  for (size_t p = 0; p < w.point_id.size(); ++p) {
+    ids.push_back((int)w.point_id[p]);
+    for (int c = 0; c < 3; ++c) pos.push_back((float)w.points[3 * p + c]);
+  }
+  if (m.engine == HOST_CORE) {
+    if (!slots.empty() && m.host->update_poses((int)slots.size(), slots.data(), Ow.data())) throw std::runtime_error("MapPointStore::WriteBack: bad key frame");
+    if (!ids.empty() && m.host->set((int)ids.size(), ids.data(), pos.data(), nullptr)) throw std::runtime_error("MapPointStore::WriteBack: bad point");
+  } else {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!slots.empty() && cms_kfstore_update_poses(m.store, (int)slots.size(), slots.data(), R.data(), t.data(), Ow.data()) != CMS_OK) Impl::fail("cms_kfstore_update_poses");
+    if (!ids.empty() && cms_mpstore_set(m.mp, (int)ids.size(), ids.data(), pos.data(), nullptr) != CMS_OK) Impl::fail("cms_mpstore_set");
+  }
+}
+
+void Optimizer::LocalBundleAdjustment(MapPointStore& mps, MapPointStore::BAWindow* win, bool* pbStopFlag) {
+  const int K = (int)win->keyframes.size(), P = (int)win->point_id.size(), E = (int)win->e_pose.size();
+  win->toErase.clear();
+  if (K == 0 || P == 0 || E == 0) return;
+  if (pbStopFlag && *pbStopFlag) return;                                       // :359-361
+  std::vector<uint8_t> flags((size_t)E);
+  const double f = CamModelGeneral::GetCamera()->Get_fx();
+  const int rc = cms_ba_run(0, K, win->poses.data(), win->fixed.data(), P, win->points.data(), E, win->e_pose.data(), win->e_point.data(), win->e_obs.data(),
+                            win->e_invsig2.data(), win->e_face.data(), f, f, f, f, 5, 10, reinterpret_cast<const volatile uint8_t*>(pbStopFlag), flags.data(), nullptr);
+  if (rc < 0) throw std::runtime_error(std::string("cms_ba_run: ") + cms_last_error());
+  if (rc == 1) return;
+  for (int e = 0; e < E; ++e) if (flags[(size_t)e]) win->toErase.push_back(std::make_pair(win->keyframes[(size_t)win->e_pose[(size_t)e]], win->e_feat[(size_t)e]));  // :399-412
+  mps.WriteBack(*win);
 }
 
 }  // namespace CubemapSLAM

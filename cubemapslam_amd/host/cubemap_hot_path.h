@@ -489,6 +489,26 @@ class MapPointStore {
   // mDescriptor, mNormalVector, mfMinDistance, mfMaxDistance and the observation the descriptor came from (NULL, -1: none)
   struct Row { float pos[3], normal[3], minDistance, maxDistance; unsigned char descriptor[32]; KeyFrameView* pBestKF; int bestIdx; };
   std::vector<Row> Fetch(const std::vector<long>& ids);
+  // The window Optimizer::LocalBundleAdjustment collects (Optimizer.cpp:194-357) from the key frames of the last Build and the points that were set:
+  // lLocalKeyFrames is pKF followed by its GetVectorCovisibleKeyFrames(), the key frame of mnId 0 is looked up among the members.  DEVICE: one
+  // cms_covis_local_ba_windows call on the private store (key points, rays and poses as Build put them); HOST_CORE: the host build of
+  // csrc/cms_ba_window_core.h over the same views.  The arrays are cms_ba_create's arguments; keyframes[k] is the view behind pose k, and
+  // (keyframes[e_pose[e]], e_feat[e]) names the observation of edge e.  This class, not Covisibility, carries the method: it is the mirror that holds
+  // an index and a table of one store.
+  struct BAWindow {
+    std::vector<KeyFrameView*> keyframes;
+    int nLocal = 0;
+    std::vector<long> point_id;
+    std::vector<double> poses, points, e_obs, e_invsig2;      // 7 per pose (t, q), 3 per point, 2 per edge, 1 per edge
+    std::vector<uint8_t> fixed;
+    std::vector<int> e_pose, e_point, e_feat;
+    std::vector<int8_t> e_face;
+    std::vector<std::pair<KeyFrameView*, int>> toErase;      // out of Optimizer::LocalBundleAdjustment: (key frame, feature) observations to erase
+  };
+  BAWindow LocalBAWindow(const std::vector<KeyFrameView*>& lLocalKeyFrames);
+  // SetPose / SetWorldPos of an optimised window (Optimizer.cpp:432-450): the local key frames' Tcw and the points' positions through float
+  // (Converter.cpp:53-104), into the views and into the engine's store (cms_kfstore_update_poses, cms_mpstore_set)
+  void WriteBack(const BAWindow& window);
 
  private:
   struct Impl;
@@ -632,6 +652,9 @@ class Optimizer {
   // runs optimize(5) / classify / optimize(10) on the GPU, writes poses and points back through float (Converter.cpp:53-104)
   // and lists the observations to erase.  *pbStopFlag is polled like g2o's forceStopFlag.
   static void LocalBundleAdjustment(LocalBAWindow* window, bool* pbStopFlag);
+  // ... with the window assembled from resident data (MapPointStore::LocalBAWindow): cms_ba_run on its arrays as they lie, the outlier edges into
+  // window->toErase (:399-412), then MapPointStore::WriteBack.  Nothing is walked on the host.
+  static void LocalBundleAdjustment(MapPointStore& mps, MapPointStore::BAWindow* window, bool* pbStopFlag);
 };
 
 }  // namespace CubemapSLAM

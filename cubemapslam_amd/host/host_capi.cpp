@@ -1,6 +1,7 @@
 // host_capi.cpp -- flat C entry points around the C++ mirror classes (cubemap_hot_path.h) so the Python test-suite can
 // drive them exactly the way a C++ caller (Tracking / LocalMapping) would.  Test plumbing, not part of the boundary.
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include "cubemap_hot_path.h"
 #include "io_formats.h"
@@ -8,6 +9,7 @@
 #include "../csrc/cms_kfdb_core.h"
 #include "../csrc/cms_covis_core.h"
 #include "../csrc/cms_mappoint_core.h"
+#include "../csrc/cms_ba_window_core.h"
 using namespace CubemapSLAM;
 
 static thread_local std::string g_err;
@@ -994,6 +996,123 @@ extern "C" int hm_mpstore_refresh(void* mp, int n, const int* ids, int what, uin
 extern "C" int hm_mpstore_fetch(void* mp, int n, const int* ids, float* pos, float* normal, float* min_dist, float* max_dist, uint8_t* desc, int* best_member,
                                 int* best_feature) {
   HM_TRY(return static_cast<CmsMpHostStore*>(mp)->fetch(n, ids, pos, normal, min_dist, max_dist, desc, best_member, best_feature);)
+}
+
+// ---- Local BA window (tests/ba_window_hostlib.py): the host build of csrc/cms_ba_window_core.h, the definition of record of cms_covis_local_ba_windows.
+// One handle holds what the walk reads: the index over n_members rows (n_feat[m] features each; mp, octave, key-point x / y and the rays' z
+// concatenated), the members' Rcw (9 floats) and tcw (3), the table's rows that hold a position (n_pos ids with 3 floats each, ids below max_points),
+// mvInvLevelSigma2, and the camera of hm_set_camera (face width, cos_fov).  hm_ba_window_run assembles njobs windows (job j: the members
+// local_members[local_off[j], local_off[j + 1]) and first_member[j]) into row j of every output.  0, -1 (CMS_ERR_ARG: nothing was written, hm_last_error
+// says why) or -4 (CMS_ERR_OVERFLOW).
+struct HmBaWindow { CmsCovisHost ix; CmsBaWindowHostData D; };
+extern "C" int hm_ba_window_create(void** out, int n_members, const int* n_feat, const int* mp, const int* octave, const float* kp_x, const float* kp_y, const float* ray_z,
+                                   const float* Rcw, const float* tcw, int max_points, int n_pos, const int* pos_ids, const float* pos, int nlevels, const float* inv_sigma2) {
+  HM_TRY(
+    if (!out || n_members < 0 || max_points < 1 || n_pos < 0 || nlevels < 1 || nlevels > 16 || !inv_sigma2) throw std::runtime_error("hm_ba_window_create: bad argument");
+    std::unique_ptr<HmBaWindow> w(new HmBaWindow());
+    std::vector<const int*> rows((size_t)n_members), octs((size_t)n_members);
+    CmsBaWindowHostData& D = w->D;
+    D.kx.resize((size_t)n_members); D.ky.resize((size_t)n_members); D.ray_z.resize((size_t)n_members);
+    size_t at = 0;
+    for (int m = 0; m < n_members; ++m) {
+      const size_t n = (size_t)n_feat[m];
+      rows[(size_t)m] = mp + at; octs[(size_t)m] = octave + at;
+      for (size_t f = 0; f < n; ++f) if (octave[at + f] < 0 || octave[at + f] >= nlevels) throw std::runtime_error("hm_ba_window_create: an octave outside the pyramid");
+      D.kx[(size_t)m].assign(kp_x + at, kp_x + at + n); D.ky[(size_t)m].assign(kp_y + at, kp_y + at + n); D.ray_z[(size_t)m].assign(ray_z + at, ray_z + at + n);
+      at += n;
+    }
+    if (w->ix.build(n_members, n_feat, rows.data(), octs.data())) throw std::runtime_error("hm_ba_window_create: the index refuses the rows");
+    D.Rcw.assign(Rcw, Rcw + 9 * (size_t)n_members); D.tcw.assign(tcw, tcw + 3 * (size_t)n_members);
+    D.has_pos.assign((size_t)max_points, 0); D.pos.assign(3 * (size_t)max_points, 0.0f);
+    for (int i = 0; i < n_pos; ++i) {
+      if (pos_ids[i] < 0 || pos_ids[i] >= max_points) throw std::runtime_error("hm_ba_window_create: an id outside the table");
+      D.has_pos[(size_t)pos_ids[i]] = 1;
+      std::memcpy(&D.pos[3 * (size_t)pos_ids[i]], pos + 3 * (size_t)i, 12);
+    }
+    for (int l = 0; l < 16; ++l) D.inv_sigma2[l] = l < nlevels ? inv_sigma2[l] : 0.0f;
+    const CamModelGeneral* cam = CamModelGeneral::GetCamera();
+    D.F = cam->GetCubeFaceWidth(); D.cos_fov = cam->GetCosFovTh();
+    *out = w.release();
+    return 0;)
+}
+extern "C" void hm_ba_window_destroy(void* w) { delete static_cast<HmBaWindow*>(w); }
+extern "C" int hm_ba_window_run(void* handle, int njobs, const int* local_off, const int* local_members, const int* first_member, int cap_kf, int cap_points, int cap_edges,
+                                int* counts, int* kf_member, int* point_id, double* poses, uint8_t* fixed, double* points, int* e_pose, int* e_point, double* e_obs,
+                                double* e_invsig2, int8_t* e_face, int* e_feat) {
+  HM_TRY(
+    const HmBaWindow* w = static_cast<const HmBaWindow*>(handle);
+    if (!w || njobs < 0 || (njobs > 0 && (!local_off || !first_member))) throw std::runtime_error("hm_ba_window_run: bad argument");
+    std::vector<CmsBaWindowHostJob> jobs((size_t)njobs);
+    for (int j = 0; j < njobs; ++j) jobs[(size_t)j] = CmsBaWindowHostJob{local_off[j + 1] - local_off[j], local_members + local_off[j], first_member[j]};
+    const CmsBaWindowHostOut o = {cap_kf, cap_points, cap_edges, reinterpret_cast<CmsBaWindowCounts*>(counts), kf_member, point_id, poses, fixed, points,
+                                  e_pose, e_point, e_obs, e_invsig2, e_face, e_feat};
+    std::string why;
+    const int rc = cms_ba_window_host(w->ix, w->D, njobs, jobs.data(), o, &why);
+    if (rc == -1) g_err = "hm_ba_window_run: " + why;
+    return rc;)
+}
+
+// CubemapSLAM::MapPointStore::LocalBAWindow of the mirror through the named engine (0 = device, 1 = host core): n_kf key frames (features concatenated: mp,
+// octave, key-point x / y, rays 3 floats each; Tcw 16 floats and mnId each) are the members, n_pts points (id, position, reference key frame as an
+// index) are set, the window of local_kf[0, n_local) is assembled into the arrays (caps as given; -4 when it does not fit), key frames as member
+// indices.  run_ba: Optimizer::LocalBundleAdjustment(mps, &window) behind it -- poses and points are then the optimised ones, n_erase the
+// observations to erase, and the members' Tcw after the write-back come back in Tcw_out (16 floats each).
+extern "C" int hm_ba_window_mirror(int engine, int n_kf, const int* n_feat, const int* mp, const int* octave, const float* kp_x, const float* kp_y, const float* rays,
+                                   const float* Tcw16, const int* mn_id, int max_points, int n_pts, const int* ids, const float* pos, const int* ref_kf, int n_local,
+                                   const int* local_kf, int run_ba, int cap_kf, int cap_points, int cap_edges, int* counts, int* kf_member, int* point_id, double* poses,
+                                   uint8_t* fixed, double* points, int* e_pose, int* e_point, double* e_obs, double* e_invsig2, int8_t* e_face, int* e_feat, int* n_erase,
+                                   float* Tcw_out) {
+  HM_TRY(
+    std::vector<KeyFrameView> kfs((size_t)n_kf);
+    std::vector<KeyFrameView*> members;
+    int max_feat = 1;
+    size_t at = 0;
+    for (int k = 0; k < n_kf; ++k) {
+      KeyFrameView& v = kfs[(size_t)k];
+      const int n = n_feat[k];
+      max_feat = std::max(max_feat, n);
+      v.mnId = mn_id[k];
+      v.mDescriptors = cv::Mat::zeros(std::max(n, 1), 32, cv::CV_8U);
+      v.mvKeys.resize((size_t)n); v.mvKeyRays.resize((size_t)n); v.mvpMapPoints.resize((size_t)n);
+      for (int f = 0; f < n; ++f) {
+        const size_t i = at + (size_t)f;
+        v.mvKeys[(size_t)f].pt.x = kp_x[i]; v.mvKeys[(size_t)f].pt.y = kp_y[i]; v.mvKeys[(size_t)f].octave = octave[i];
+        for (int c = 0; c < 3; ++c) v.mvKeyRays[(size_t)f].v[c] = rays[3 * i + (size_t)c];
+        v.mvpMapPoints[(size_t)f] = mp[i];
+      }
+      at += (size_t)n;
+      v.Tcw = cv::Mat::zeros(4, 4, cv::CV_32F);
+      for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) v.Tcw.at<float>(r, c) = Tcw16[16 * (size_t)k + 4 * (size_t)r + (size_t)c];
+      members.push_back(&v);
+    }
+    MapPointStore mps(engine ? MapPointStore::HOST_CORE : MapPointStore::DEVICE, n_kf + 1, max_feat, max_points);
+    mps.Build(members);
+    std::vector<MapPointStore::MapPointView> pts((size_t)n_pts);
+    for (int i = 0; i < n_pts; ++i) {
+      pts[(size_t)i].id = ids[i];
+      std::memcpy(pts[(size_t)i].pos, pos + 3 * (size_t)i, 12);
+      pts[(size_t)i].pRefKF = &kfs[(size_t)ref_kf[i]];
+    }
+    mps.SetMapPoints(pts);
+    std::vector<KeyFrameView*> local;
+    for (int i = 0; i < n_local; ++i) local.push_back(&kfs[(size_t)local_kf[i]]);
+    MapPointStore::BAWindow w = mps.LocalBAWindow(local);
+    *n_erase = 0;
+    if (run_ba) {
+      Optimizer::LocalBundleAdjustment(mps, &w, nullptr);
+      *n_erase = (int)w.toErase.size();
+      for (int k = 0; k < n_kf; ++k)
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) Tcw_out[16 * (size_t)k + 4 * (size_t)r + (size_t)c] = kfs[(size_t)k].Tcw.at<float>(r, c);
+    }
+    const int K = (int)w.keyframes.size(), P = (int)w.point_id.size(), E = (int)w.e_pose.size();
+    counts[0] = K; counts[1] = w.nLocal; counts[2] = P; counts[3] = E;
+    if (K > cap_kf || P > cap_points || E > cap_edges) return -4;
+    for (int k = 0; k < K; ++k) kf_member[k] = (int)(w.keyframes[(size_t)k] - kfs.data());
+    for (int p = 0; p < P; ++p) point_id[p] = (int)w.point_id[(size_t)p];
+    std::copy(w.poses.begin(), w.poses.end(), poses); std::copy(w.fixed.begin(), w.fixed.end(), fixed); std::copy(w.points.begin(), w.points.end(), points);
+    std::copy(w.e_pose.begin(), w.e_pose.end(), e_pose); std::copy(w.e_point.begin(), w.e_point.end(), e_point); std::copy(w.e_obs.begin(), w.e_obs.end(), e_obs);
+    std::copy(w.e_invsig2.begin(), w.e_invsig2.end(), e_invsig2); std::copy(w.e_face.begin(), w.e_face.end(), e_face); std::copy(w.e_feat.begin(), w.e_feat.end(), e_feat);
+    return 0;)
 }
 
 // CubemapSLAM::MapPointStore of the mirror through the named engine (0 = device, 1 = host core): n_kf key frames of n_feat[k] features (mp, octave and

@@ -1147,6 +1147,46 @@ int cms_search_local_points_ids(cms_ctx* ctx, int b, const float* pose15, cms_mp
 int cms_kfstore_fuse_search_sets_ids(cms_kfstore* st, cms_mpstore* mp, int nsets, const int* set_off, const int* ids, int njobs, const int* job_slot,
                                      const int* job_set, const uint8_t* skip, float th, int* best_idx, int* best_dist);
 
+/* ---- Local BA window from the resident stores: what Optimizer::LocalBundleAdjustment collects before it optimises (src/Optimizer.cpp:194-357), built
+ * on the device from the observation index, the store's slots and the map-point table.  The definition of record is csrc/cms_ba_window_core.h
+ * (DESIGN.md "Local BA window from the resident stores"): one source, built for the host (hm_ba_window_* of libcubemapslam_host.so) and for the
+ * kernels.  Every output equals the host core's bit for bit.
+ *
+ * A job names lLocalKeyFrames as member POSITIONS of the index in the reference's order -- the current key frame first, then its
+ * GetVectorCovisibleKeyFrames() (`order` of cms_covis_connections) -- and first_member, the member whose mnId is 0, or -1.  Job j owns row j of every
+ * output, with strides cap_kf, cap_points and cap_edges (times 7, 3 or 2 for poses, points and e_obs):
+ *   counts[j]   {K, n_local, P, E}
+ *   point_id    the local points: the ids of the local members' rows in list order, then feature order, each once (cms_covis_local_points)
+ *   kf_member   the window's key frames as members: the locals in list order, then the fixed ones -- every other member that observes a local point --
+ *               in ascending (list position of the first local point it observes, member position), the order in which the reference meets them
+ *   fixed       k >= n_local || kf_member[k] == first_member
+ *   poses       (t, q) per key frame: Converter::toSE3Quat of the slot's float Rcw | tcw
+ *   points      the table's float positions, widened
+ *   e_*         one edge per observation of a local point whose key ray has z >= cos_fov and whose key point lies on a face: points in list order,
+ *               a point's observations in ascending member position.  e_pose indexes kf_member, e_point the point list; e_obs is the position in
+ *               the face, e_invsig2 mvInvLevelSigma2 of the octave; e_feat is the feature index inside the key frame, so (kf_member[e_pose], e_feat)
+ *               names the observation to erase.  A point that keeps no edge stays in the list.
+ * The arrays of a job are cms_ba_create's arguments as they lie.
+ *
+ * What the call sees: rows, features and octaves are the index's SNAPSHOT (a cms_kfstore_update_map_points is not seen before the next
+ * cms_covis_build); key points, rays and poses are what the slots hold when the call runs, positions what the table holds then.  It runs on the
+ * store's stream, behind the last cms_covis_build, cms_kfstore_update_poses and cms_mpstore_set.  A member slot must not be refilled between the build
+ * and the call (cms_mpstore_refresh's contract).
+ *
+ * All jobs of a call are one launch sequence with one wait.  Outputs may be plain host arrays (copied back through the index's staging block) or ALL
+ * lie in pinned memory (cms_host_alloc): then the kernels store into them and the window can go to cms_ba_create_many with CMS_BA_INPUTS_PINNED.
+ *
+ * CMS_ERR_ARG with nothing written, checked on the host before anything is enqueued: no index built, an index and a table of different stores,
+ * n_local < 1, a member out of range or named twice in a job, first_member outside [-1, M), a cap < 1.  A local point whose table row holds no
+ * position is found on the device: CMS_ERR_ARG after the wait, the message names the job (plain host outputs are untouched, pinned ones are not).
+ * CMS_ERR_OVERFLOW: a job has more key frames, points or edges than a cap; counts holds the true numbers of every job, jobs that fit are complete,
+ * and nothing is written at or beyond any cap.  Holds the mutexes of both handles. */
+typedef struct { int n_local; const int* local_members; int first_member; } cms_ba_window_job;
+typedef struct { int K, n_local, P, E; } cms_ba_window_counts;
+int cms_covis_local_ba_windows(cms_covis* cv, cms_mpstore* mp, int njobs, const cms_ba_window_job* jobs, int cap_kf, int cap_points, int cap_edges,
+                               cms_ba_window_counts* counts, int* kf_member, int* point_id, double* poses, uint8_t* fixed, double* points, int* e_pose,
+                               int* e_point, double* e_obs, double* e_invsig2, int8_t* e_face, int* e_feat);
+
 #ifdef __cplusplus
 }
 #endif

@@ -900,6 +900,85 @@ void UpdateKeyFramePoses(cms_kfstore* store, const std::vector<KeyFrame*>& vpKFs
   if (!slots.empty()) check(cms_kfstore_update_poses(store, (int)slots.size(), slots.data(), R.data(), t.data(), O.data()), "cms_kfstore_update_poses");
 }
 
+// Optimizer::LocalBundleAdjustment with the window assembled on the device (cms_covis_local_ba_windows): no walk over observations on the host
+void LocalBundleAdjustment(cms_kfstore* store, cms_covis* covis, cms_mpstore* mps, KeyFrame* pKF, bool* pbStopFlag, Map* pMap) {
+  CamModelGeneral* cam = CamModelGeneral::GetCamera();
+  CovisBook& c = covis_book(covis);
+  std::vector<KeyFrame*> members;
+  std::map<int, MapPoint*> point;
+  std::vector<int> local;
+  int first = -1;
+  size_t cap_points = 1;
+  {
+    std::lock_guard<std::mutex> lk(c.mu);
+    members = c.members; point = c.point;
+    const int m0 = member_of(c, pKF);
+    if (m0 < 0) throw std::runtime_error("Hip::LocalBundleAdjustment: the key frame is not a member of the last Hip::BuildCovisibility");
+    std::set<int> listed;
+    local.push_back(m0); listed.insert(m0);                        // lLocalKeyFrames (Optimizer.cpp:198-207): pKF, then its covisibles in their order
+    for (KeyFrame* k : pKF->GetVectorCovisibleKeyFrames()) {
+      const int m = member_of(c, k);
+      if (m >= 0 && listed.insert(m).second) local.push_back(m);   // (a covisible that is bad or not resident is no member)
+    }
+    for (size_t m = 0; m < members.size(); ++m) if (members[m]->mnId == 0) first = (int)m;
+    for (int m : local) cap_points += members[(size_t)m]->mvKeys.size();
+  }
+  const int cap_kf = (int)members.size();
+  size_t cap_edges = 8 * cap_points;
+  cms_ba_window_counts n = {0, 0, 0, 0};
+  std::vector<int> kf_member((size_t)cap_kf), point_id(cap_points), e_pose, e_point, e_feat;
+  std::vector<double> poses(7 * (size_t)cap_kf), points(3 * cap_points), e_obs, e_inv;
+  std::vector<uint8_t> fixed((size_t)cap_kf);
+  std::vector<int8_t> e_face;
+  const cms_ba_window_job job = {(int)local.size(), local.data(), first};
+  for (int attempt = 0; ; ++attempt) {                             // (the number of edges is known after the first call: at most one more)
+    e_pose.resize(cap_edges); e_point.resize(cap_edges); e_feat.resize(cap_edges); e_obs.resize(2 * cap_edges); e_inv.resize(cap_edges); e_face.resize(cap_edges);
+    const int rc = cms_covis_local_ba_windows(covis, mps, 1, &job, cap_kf, (int)cap_points, (int)cap_edges, &n, kf_member.data(), point_id.data(), poses.data(), fixed.data(),
+                                              points.data(), e_pose.data(), e_point.data(), e_obs.data(), e_inv.data(), e_face.data(), e_feat.data());
+    if (rc == CMS_OK) break;
+    if (rc != CMS_ERR_OVERFLOW || attempt > 0 || n.K > cap_kf || (size_t)n.P > cap_points) check(rc, "cms_covis_local_ba_windows");
+    cap_edges = (size_t)n.E;
+  }
+  const int K = n.K, P = n.P, E = n.E;
+  if (E == 0) return;
+  std::vector<uint8_t> erase((size_t)E, 0);
+  cms_ba_stats st;
+  const int rc = cms_ba_run(g_device, K, poses.data(), fixed.data(), P, points.data(), E, e_pose.data(), e_point.data(), e_obs.data(), e_inv.data(), e_face.data(),
+                            cam->Get_fx(), cam->Get_fy(), cam->Get_cx(), cam->Get_cy(), 5, 10, reinterpret_cast<const volatile uint8_t*>(pbStopFlag), erase.data(), &st);
+  check(rc, "cms_ba_run");
+  if (rc == 1) return;                                              // stop requested before the optimisation started (:359-361)
+  // ---- write-back under the map mutex (:419-450): the observation of edge e is (kf_member[e_pose[e]], e_feat[e]), nothing is searched
+  std::vector<KeyFrame*> moved;
+  std::vector<MapPoint*> pts;
+  {
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+    for (int e = 0; e < E; ++e) {
+      if (!erase[(size_t)e]) continue;
+      KeyFrame* k = members[(size_t)kf_member[(size_t)e_pose[(size_t)e]]];
+      MapPoint* p = k->GetMapPoint((size_t)e_feat[(size_t)e]);
+      if (!p || p->isBad()) continue;
+      k->EraseMapPointMatch((size_t)e_feat[(size_t)e]);
+      p->EraseObservation(k);
+    }
+    for (int j = 0; j < n.n_local; ++j) {
+      KeyFrame* k = members[(size_t)kf_member[(size_t)j]];
+      k->SetPose(toMat(&poses[(size_t)j * 7]));
+      moved.push_back(k);
+    }
+    for (int i = 0; i < P; ++i) {
+      const std::map<int, MapPoint*>::const_iterator it = point.find(point_id[(size_t)i]);
+      if (it == point.end() || !it->second || it->second->isBad()) continue;
+      cv::Mat x(3, 1, CV_32F);
+      for (int k = 0; k < 3; ++k) x.at<float>(k) = (float)points[(size_t)i * 3 + k];
+      it->second->SetWorldPos(x);
+      it->second->UpdateNormalAndDepth();
+      pts.push_back(it->second);
+    }
+  }
+  UpdateKeyFramePoses(store, moved);                                // the resident copies: ONE cms_kfstore_update_poses, ONE cms_mpstore_set
+  SetMapPoints(mps, pts);
+}
+
 // ------------------------------------------------------------------------------------------------ Tracking: SearchByBoW on resident key frames
 namespace {
 // the frame's FeatureVector (Frame::ComputeBoW) as CSR

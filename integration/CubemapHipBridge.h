@@ -118,6 +118,13 @@ int SearchLocalPoints(cms_ctx* ctx, cms_mpstore* mps, Frame& F, const std::vecto
 // BuildCovisibility, and the current key frame's points are set and refreshed (LocalMapping.cpp:449-463) -- `refreshed` receives their attributes --
 // before UpdateConnections.
 Connections SearchInNeighbors(cms_kfstore* store, cms_covis* covis, cms_mpstore* mps, KeyFrame* pCurrentKF, std::vector<MapPointAttributes>& refreshed);
+// Optimizer::LocalBundleAdjustment (Optimizer.cpp:192-451) on resident data: the window (:194-357) is ONE cms_covis_local_ba_windows call over the
+// index of the last BuildCovisibility and the table -- pKF and its GetVectorCovisibleKeyFrames() that are members, the key frame of mnId 0 -- then
+// cms_ba_run on the arrays as they come, then the write-back of :419-450: EraseMapPointMatch / EraseObservation over (kf_member[e_pose], e_feat)
+// without a search, SetPose, SetWorldPos and UpdateNormalAndDepth, and the resident copies through Hip::UpdateKeyFramePoses and Hip::SetMapPoints.
+// Every local point must have been set (Hip::SetMapPoints); the table's normals and bounds are refreshed by the caller behind its next
+// BuildCovisibility, which sees the erased observations.
+void LocalBundleAdjustment(cms_kfstore* store, cms_covis* covis, cms_mpstore* mps, KeyFrame* pKF, bool* pbStopFlag, Map* pMap);
 // ---- Tracking's SearchByBoW(KeyFrame*, Frame&, ...) (ORBMatcher.cpp:409-539) against key frames resident in `store`, on the FRAME thread: F is the frame
 // `frameCtx` extracted last (slot 0 of its batch) after F.ComputeBoW().  The slot comes from the store's KeyFrame* -> slot book; a key-frame feature takes
 // part where the slot's map-point entry (as ProcessNewKeyFrame / CreateNewMapPoints last wrote it) is set and GetMapPointMatches() still holds a point
