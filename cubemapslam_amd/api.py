@@ -904,6 +904,17 @@ class KeyframeStore(_Handle):
         assert len(a[0]) == 9 * len(slots) and len(a[1]) == 3 * len(slots) and len(a[2]) == 3 * len(slots)
         _chk(lib().cms_kfstore_update_poses(self.h, len(slots), _p(slots), _p(a[0]), _p(a[1]), _p(a[2])), "cms_kfstore_update_poses")
 
+    def scene_median_depth(self, mpstore, slots, q=2, store=False):
+        """cms_kfstore_scene_median_depth: KeyFrame::ComputeSceneMedianDepth(q) of the slots from their current mp rows and the table's positions
+        -> (depth[n], n_depths[n]); a slot without a depth reads (-1.0, 0).  store: the slots with a depth also keep it as their median_depth"""
+        L = lib()
+        L.cms_kfstore_scene_median_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        s = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        depth = np.zeros(max(len(s), 1), np.float32); nd = np.zeros(max(len(s), 1), np.int32)
+        _chk(L.cms_kfstore_scene_median_depth(self.h, mpstore.h, len(s), _p(s) if len(s) else None, int(q), int(bool(store)), _p(depth), _p(nd)),
+             "cms_kfstore_scene_median_depth")
+        return depth[:len(s)], nd[:len(s)]
+
     def fuse_search(self, jobs, th=3.0):
         """jobs: list of (slot, dict(skip, pos, normal, min_dist, max_dist, desc)) -> per job (best_idx, best_dist)"""
         nj = len(jobs)
@@ -1309,6 +1320,17 @@ class Covisibility(_Handle):
             _chk(rc, "cms_covis_local_points")
         return rc, n_out[:nj], [[int(v) for v in ids[j, :min(int(n_out[j]), int(cap))]] for j in range(nj)]
 
+    def tracked_map_points(self, src_ctx, members, min_obs):
+        """cms_covis_tracked_map_points: KeyFrame::TrackedMapPoints(min_obs[j]) of member members[j] on the index's snapshot -> count[njobs]"""
+        L = lib()
+        L.cms_covis_tracked_map_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        m = np.ascontiguousarray(members, np.int32).reshape(-1)
+        mo = np.ascontiguousarray(np.broadcast_to(np.asarray(min_obs, np.int32), m.shape))
+        count = np.zeros(max(len(m), 1), np.int32)
+        pp = lambda v: _p(v) if len(v) else None
+        _chk(L.cms_covis_tracked_map_points(self.h, src_ctx.h, len(m), pp(m), pp(mo), _p(count)), "cms_covis_tracked_map_points")
+        return count[:len(m)]
+
     def local_ba_windows(self, mps, jobs, cap_kf, cap_points, cap_edges, pinned=False, out=None):
         """cms_covis_local_ba_windows: the local BA windows of `jobs` ((local members in the reference's order, first_member or -1) each) from this
         index, its store and the MapPointStore mps.  -> one dict per job in synth.ba_problem's layout (poses, fixed, points, e_pose, e_point, e_obs,
@@ -1378,6 +1400,7 @@ def ba_window_arrays(njobs, cap_kf, cap_points, cap_edges, pinned=False, fill=0)
 
 
 MP_DESCRIPTOR, MP_NORMAL_DEPTH = 1, 2
+MP_VISIBLE, MP_FOUND = 1, 2      # the columns of MapPointStore.count
 
 
 def _ids32(ids):
@@ -1437,6 +1460,73 @@ class MapPointStore(_Handle):
             _chk(lib().cms_mpstore_fetch(self.h, n, _p(ids), _p(o["pos"]), _p(o["normal"]), _p(o["min_dist"]), _p(o["max_dist"]), _p(o["desc"]), _p(o["best_member"]),
                                          _p(o["best_feature"])), "cms_mpstore_fetch")
         return o
+
+    # ---- the statistics columns (mnVisible, mnFound, mnFirstKFid) and LocalMapping::MapPointCulling
+    @staticmethod
+    def _stats_lib():
+        L = lib()
+        L.cms_mpstore_set_stats.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        L.cms_mpstore_add_stats.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.cms_mpstore_fetch_stats.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        L.cms_mpstore_count.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int]
+        L.cms_mpstore_culling.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p]
+        return L
+
+    @staticmethod
+    def _column(v, n):
+        if v is None:
+            return None
+        v = np.ascontiguousarray(v, np.int32).reshape(-1)
+        assert len(v) == n
+        return v
+
+    def set_stats(self, ids, first_kf=None, visible=None, found=None):
+        """cms_mpstore_set_stats: absolute mnFirstKFid / mnVisible / mnFound of set rows (None = unchanged); asynchronous"""
+        ids = _ids32(ids)
+        a = [self._column(v, len(ids)) for v in (first_kf, visible, found)]
+        pp = lambda v: _p(v) if v is not None and len(v) else None
+        _chk(self._stats_lib().cms_mpstore_set_stats(self.h, len(ids), pp(ids), *[pp(v) for v in a]), "cms_mpstore_set_stats")
+
+    def add_stats(self, ids, d_visible=None, d_found=None):
+        """cms_mpstore_add_stats: IncreaseVisible(n) / IncreaseFound(n) of set rows (None = 0); asynchronous"""
+        ids = _ids32(ids)
+        a = [self._column(v, len(ids)) for v in (d_visible, d_found)]
+        pp = lambda v: _p(v) if v is not None and len(v) else None
+        _chk(self._stats_lib().cms_mpstore_add_stats(self.h, len(ids), pp(ids), *[pp(v) for v in a]), "cms_mpstore_add_stats")
+
+    def fetch_stats(self, ids):
+        """cms_mpstore_fetch_stats -> (visible, found, first_kf) of the rows `ids`; an empty row reads (1, 1, -1)"""
+        ids = _ids32(ids)
+        n = len(ids)
+        o = [np.zeros(n, np.int32) for _ in range(3)]
+        if n:
+            _chk(self._stats_lib().cms_mpstore_fetch_stats(self.h, n, _p(ids), _p(o[0]), _p(o[1]), _p(o[2])), "cms_mpstore_fetch_stats")
+        return tuple(o)
+
+    def count(self, src_ctx, which, id_lists, flags=None, count_if=1):
+        """cms_mpstore_count: per frame a list of ids (-1 = no point) and, or None for all frames, a list of flags of the same length; an entry adds 1
+        to column `which` (MP_VISIBLE / MP_FOUND) iff its id is >= 0 and (flags is None or (flag != 0) == (count_if != 0)).  Asynchronous on
+        src_ctx's stream"""
+        off, ids = _csr(id_lists)
+        fl = None
+        if flags is not None:
+            assert [len(f) for f in flags] == [len(x) for x in id_lists]
+            fl = np.zeros(len(ids), np.uint8)
+            if int(off[-1]):
+                fl[:-1] = np.concatenate([np.asarray(f, np.uint8).reshape(-1) for f in flags if len(f)])
+        _chk(self._stats_lib().cms_mpstore_count(self.h, src_ctx.h, int(which), len(id_lists), _p(off), _p(ids), _p(fl), int(count_if)), "cms_mpstore_count")
+
+    def culling(self, covis, id_lists, current_kf, th_obs=2, apply=False):
+        """cms_mpstore_culling: per MapPointCulling call the recent ids and the current key frame's mnId -> one array of verdicts per job (0 stays,
+        1 bad by found ratio, 2 bad by too few observations, 3 leaves the list, 4 empty row).  apply: SetBadFlag of verdicts 1 and 2 on the store's
+        mp rows and the table"""
+        off, ids = _csr(id_lists)
+        cur = np.zeros(len(id_lists) + 1, np.int32)
+        cur[:-1] = np.asarray(current_kf, np.int32).reshape(-1)
+        verdict = np.zeros(len(ids), np.uint8)
+        _chk(self._stats_lib().cms_mpstore_culling(self.h, covis.h, len(id_lists), _p(off), _p(ids), _p(cur), int(th_obs), int(bool(apply)), _p(verdict)),
+             "cms_mpstore_culling")
+        return [verdict[off[j]:off[j + 1]].copy() for j in range(len(id_lists))]
 
 
 def distinctive_descriptors(ctx, obs_off, desc):

@@ -23,14 +23,21 @@ struct cms_mpstore {
   hipEvent_t rec_ev[4] = {nullptr, nullptr, nullptr, nullptr}; bool rec_ev_set[4] = {false, false, false, false};
   unsigned rec_call = 0;
   hipEvent_t write_ev = nullptr; bool written = false;      // behind the table's last write on the store's stream
+  // cms_mpstore_count (cms_api_mpstats.hip): a pinned ring of four blocks of ids and flags, and per frame context the event behind its last call
+  uint8_t* h_cnt[4] = {nullptr, nullptr, nullptr, nullptr}; size_t cnt_cap[4] = {0, 0, 0, 0};
+  hipEvent_t cnt_ev[4] = {nullptr, nullptr, nullptr, nullptr}; bool cnt_ev_set[4] = {false, false, false, false};
+  unsigned cnt_call = 0;
+  std::vector<std::pair<cms_ctx*, hipEvent_t>> count_done;
   CmsStage stage;
 };
 
 extern "C" void cms_mpstore_destroy(cms_mpstore* mp) {
   if (!mp) return;
   if (mp->st && mp->st->c) (void)hipSetDevice(mp->st->c->device);
-  void* bufs[] = {mp->t.pos, mp->t.normal, mp->t.min_dist, mp->t.max_dist, mp->t.desc, mp->t.ref, mp->t.best};
+  void* bufs[] = {mp->t.pos, mp->t.normal, mp->t.min_dist, mp->t.max_dist, mp->t.desc, mp->t.ref, mp->t.best, mp->t.visible, mp->t.found, mp->t.first_kf};
   for (void* b : bufs) if (b) (void)hipFree(b);
+  for (int i = 0; i < 4; ++i) { if (mp->h_cnt[i]) (void)hipHostFree(mp->h_cnt[i]); if (mp->cnt_ev[i]) (void)hipEventDestroy(mp->cnt_ev[i]); }
+  for (auto& e : mp->count_done) (void)hipEventDestroy(e.second);
   for (int i = 0; i < 4; ++i) { if (mp->h_rec[i]) (void)hipHostFree(mp->h_rec[i]); if (mp->rec_ev[i]) (void)hipEventDestroy(mp->rec_ev[i]); }
   if (mp->write_ev) (void)hipEventDestroy(mp->write_ev);
   mp->stage.release();
@@ -50,11 +57,15 @@ extern "C" int cms_mpstore_create(cms_mpstore** out, cms_kfstore* st, int max_po
   ok = ok && hipMalloc((void**)&mp->t.min_dist, 4 * n) == hipSuccess && hipMalloc((void**)&mp->t.max_dist, 4 * n) == hipSuccess;
   ok = ok && hipMalloc((void**)&mp->t.desc, 32 * n) == hipSuccess && hipMalloc((void**)&mp->t.ref, 4 * n) == hipSuccess;
   ok = ok && hipMalloc((void**)&mp->t.best, 8 * n) == hipSuccess;
+  ok = ok && hipMalloc((void**)&mp->t.visible, 4 * n) == hipSuccess && hipMalloc((void**)&mp->t.found, 4 * n) == hipSuccess && hipMalloc((void**)&mp->t.first_kf, 4 * n) == hipSuccess;
   // an empty row: zeros, no reference slot, no best observation (what k_mp_set's erase leaves)
   ok = ok && hipMemsetAsync(mp->t.pos, 0, 12 * n, s) == hipSuccess && hipMemsetAsync(mp->t.normal, 0, 12 * n, s) == hipSuccess;
   ok = ok && hipMemsetAsync(mp->t.min_dist, 0, 4 * n, s) == hipSuccess && hipMemsetAsync(mp->t.max_dist, 0, 4 * n, s) == hipSuccess;
   ok = ok && hipMemsetAsync(mp->t.desc, 0, 32 * n, s) == hipSuccess && hipMemsetAsync(mp->t.ref, 0xFF, 4 * n, s) == hipSuccess;
-  ok = ok && hipMemsetAsync(mp->t.best, 0xFF, 8 * n, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  ok = ok && hipMemsetAsync(mp->t.best, 0xFF, 8 * n, s) == hipSuccess;
+  // (the counters of both MapPoint constructors: CMS_MP_EMPTY_*)
+  ok = ok && hipMemsetD32Async((hipDeviceptr_t)mp->t.visible, CMS_MP_EMPTY_VISIBLE, n, s) == hipSuccess && hipMemsetD32Async((hipDeviceptr_t)mp->t.found, CMS_MP_EMPTY_FOUND, n, s) == hipSuccess;
+  ok = ok && hipMemsetAsync(mp->t.first_kf, 0xFF, 4 * n, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
   if (!ok) { cms_mpstore_destroy(mp); return cms_fail(CMS_ERR_HIP, "cms_mpstore_create: out of device memory"); }
   mp->state.assign(n, 0); mp->seen.assign(n, 0);
   *out = mp;
@@ -75,12 +86,19 @@ static const char* mpstore_check_ids(cms_mpstore* mp, int n, const int* ids, boo
 }
 static int mpstore_fail(const char* who, const char* why) { return cms_fail(CMS_ERR_ARG, (std::string(who) + ": " + why).c_str()); }
 
+// the stream waits (on the device) for every cms_mpstore_count enqueued so far: in front of whatever reads or resets the counters
+static hipError_t mpstore_behind_counts(cms_mpstore* mp, hipStream_t s) {
+  for (auto& e : mp->count_done) { const hipError_t rc = hipStreamWaitEvent(s, e.second, 0); if (rc != hipSuccess) return rc; }
+  return hipSuccess;
+}
+
 // n records through the next ring block, one k_mp_set behind them; fill(rec) writes the 6 n words
 template <class Fill>
 static int mpstore_records(cms_mpstore* mp, int n, Fill&& fill) {
   cms_ctx* c = mp->st->c;
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(kfstore_order_behind_puts(mp->st));
+  HIPCHK(mpstore_behind_counts(mp, c->stream));
   const unsigned ring = mp->rec_call++ & 3;
   if (!mp->rec_ev[ring]) HIPCHK(hipEventCreateWithFlags(&mp->rec_ev[ring], hipEventDisableTiming));
   if (mp->rec_ev_set[ring]) HIPCHK(hipEventSynchronize(mp->rec_ev[ring]));      // the kernel that last read this block: four calls ago

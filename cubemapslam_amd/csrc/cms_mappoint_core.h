@@ -71,17 +71,20 @@ struct CmsMpHostStore {
     float pos[3] = {0, 0, 0}, normal[3] = {0, 0, 0}, min_dist = 0, max_dist = 0;
     uint8_t desc[32] = {0};
     int ref = -1, best_member = -1, best_feature = -1;
+    int visible = 1, found = 1, first_kf = -1;      // cms_mpstats_core.h: what both MapPoint constructors leave
   };
   CmsCovisHostStore cv;
   std::vector<std::vector<uint8_t>> desc;      // per slot: n x 32
   std::vector<float> Ow;                       // per slot: 3
+  std::vector<float> Rcw, tcw, median;         // per slot: 9, 3, 1 (hm_mpstats_*: the scene median depth).  put() leaves Rcw = I, tcw = -Ow
   std::vector<int> member_slot;                // of the last successful build
   std::vector<Row> rows;
   float sf[16];
   int nlevels;
 
   CmsMpHostStore(int max_keyframes, int max_feat, int max_mem, int max_points, int nlev, const float* scale)
-      : cv(max_keyframes, max_feat, max_mem), desc((size_t)max_keyframes), Ow((size_t)max_keyframes * 3, 0.0f), rows((size_t)max_points), nlevels(nlev) {
+      : cv(max_keyframes, max_feat, max_mem), desc((size_t)max_keyframes), Ow((size_t)max_keyframes * 3, 0.0f), Rcw((size_t)max_keyframes * 9, 0.0f),
+        tcw((size_t)max_keyframes * 3, 0.0f), median((size_t)max_keyframes, 1.0f), rows((size_t)max_points), nlevels(nlev) {
     for (int l = 0; l < 16; ++l) sf[l] = l < nlev ? scale[l] : 1.0f;
   }
   int put(int s, int n, const int* mp, const int* oct, const uint8_t* d, const float* ow) {
@@ -90,6 +93,8 @@ struct CmsMpHostStore {
     if (cv.put(s, n, mp, oct)) return -1;
     desc[(size_t)s].assign(d, d + (size_t)n * 32);
     memcpy(&Ow[(size_t)s * 3], ow, 12);
+    for (int k = 0; k < 9; ++k) Rcw[(size_t)s * 9 + k] = (k % 4 == 0) ? 1.0f : 0.0f;
+    for (int k = 0; k < 3; ++k) tcw[(size_t)s * 3 + k] = -ow[k];
     return 0;
   }
   int update_poses(int n, const int* slot, const float* ow) {

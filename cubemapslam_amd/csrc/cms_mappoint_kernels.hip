@@ -8,6 +8,7 @@
 // Resources of k_mp_refresh (hipcc's kernel-resource-usage): 76 VGPRs, six waves per SIMD, no LDS, no scratch (no per-thread array has a runtime
 // index); the kernel waits on dependent loads (segment -> member's slot -> descriptor row), so waves per SIMD are what hides them.
 #include "cms_mappoint_core.h"
+#include "cms_mpstats_core.h"
 
 struct CmsMpTable {
   int max_points;
@@ -16,23 +17,40 @@ struct CmsMpTable {
   uint4* desc;                    // [max_points x 2]
   int* ref;                       // mpRefKF as a store slot, -1: an empty row
   int2* best;                     // (member, feature) the descriptor was taken from, (-1, -1): none
+  int* visible; int* found;       // mnVisible, mnFound (cms_mpstats_core.h); an empty row: 1, 1
+  int* first_kf;                  // mnFirstKFid, -1: an empty row
 };
 
-// ---- cms_mpstore_set / cms_mpstore_erase: six words per record read from a pinned block: id, flags, pos[3], ref
+// ---- cms_mpstore_set / cms_mpstore_erase: six words per record read from a pinned block: id, flags, pos[3], ref.  A statistics record
+// (cms_mpstore_set_stats / add_stats) carries first_kf, visible, found in the three position words: absolute values, or with CMS_MP_REC_ADD the
+// amounts to add (nothing else adds to the row meanwhile: the store's stream is behind every counting call)
 #define CMS_MP_REC_POS 1
 #define CMS_MP_REC_REF 2
 #define CMS_MP_REC_ERASE 4
+#define CMS_MP_REC_FIRST_KF 8
+#define CMS_MP_REC_VISIBLE 16
+#define CMS_MP_REC_FOUND 32
+#define CMS_MP_REC_ADD 64
+// the erase state of a row (cms_mpstore_create fills the table with it)
+__device__ __forceinline__ void mp_row_clear(const CmsMpTable& t, int id) {
+  for (int k = 0; k < 3; ++k) { t.pos[3 * (size_t)id + k] = 0.0f; t.normal[3 * (size_t)id + k] = 0.0f; }
+  t.min_dist[id] = 0.0f; t.max_dist[id] = 0.0f;
+  t.desc[2 * (size_t)id] = make_uint4(0, 0, 0, 0); t.desc[2 * (size_t)id + 1] = make_uint4(0, 0, 0, 0);
+  t.ref[id] = -1; t.best[id] = make_int2(-1, -1);
+  t.visible[id] = CMS_MP_EMPTY_VISIBLE; t.found[id] = CMS_MP_EMPTY_FOUND; t.first_kf[id] = CMS_MP_EMPTY_FIRST_KF;
+}
 extern "C" __global__ void __launch_bounds__(256) k_mp_set(const CmsMpTable t, const int* __restrict__ rec, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int* r = rec + 6 * (size_t)i;
   const int id = r[0], flags = r[1];
   if (id < 0 || id >= t.max_points) return;      // (the host has checked; a row outside the table is never written)
-  if (flags & CMS_MP_REC_ERASE) {
-    for (int k = 0; k < 3; ++k) { t.pos[3 * (size_t)id + k] = 0.0f; t.normal[3 * (size_t)id + k] = 0.0f; }
-    t.min_dist[id] = 0.0f; t.max_dist[id] = 0.0f;
-    t.desc[2 * (size_t)id] = make_uint4(0, 0, 0, 0); t.desc[2 * (size_t)id + 1] = make_uint4(0, 0, 0, 0);
-    t.ref[id] = -1; t.best[id] = make_int2(-1, -1);
+  if (flags & CMS_MP_REC_ERASE) { mp_row_clear(t, id); return; }
+  if (flags & (CMS_MP_REC_FIRST_KF | CMS_MP_REC_VISIBLE | CMS_MP_REC_FOUND)) {
+    const int add = flags & CMS_MP_REC_ADD;
+    if (flags & CMS_MP_REC_FIRST_KF) t.first_kf[id] = r[2];
+    if (flags & CMS_MP_REC_VISIBLE) t.visible[id] = add ? t.visible[id] + r[3] : r[3];
+    if (flags & CMS_MP_REC_FOUND) t.found[id] = add ? t.found[id] + r[4] : r[4];
     return;
   }
   if (flags & CMS_MP_REC_POS) for (int k = 0; k < 3; ++k) t.pos[3 * (size_t)id + k] = __int_as_float(r[2 + k]);

@@ -14,6 +14,7 @@
 #include "../csrc/cms_kfdb_core.h"
 #include "../csrc/cms_covis_core.h"
 #include "../csrc/cms_mappoint_core.h"
+#include "../csrc/cms_mpstats_core.h"
 #include "../csrc/cms_ba_window_core.h"
 #include "../csrc/cms_ess_graph_core.h"      // CmsS3 and Sim3(R, t, s) for vScw
 #include "../csrc/cms_ess_graph_job_check.h" // the envelope count for the handle
@@ -1924,6 +1925,7 @@ void MapPointStore::Build(const std::vector<KeyFrameView*>& members) {
       float R[9], t[3], Ow[3];
       pose15_from_Tcw(k.Tcw, R, t, Ow);
       if (m.host->put((int)i, (int)k.mvKeys.size(), rows[i].data(), oct.data(), desc.data(), Ow)) throw std::runtime_error("MapPointStore::Build: bad key frame");
+      std::memcpy(&m.host->Rcw[9 * i], R, 36); std::memcpy(&m.host->tcw[3 * i], t, 12);      // (the scene median depth reads the whole pose)
     }
     if (m.host->build((int)members.size(), slots.data())) throw std::runtime_error("MapPointStore::Build: a key frame names a map point twice");
   } else {
@@ -2109,12 +2111,148 @@ void MapPointStore::WriteBack(const BAWindow& w) {
   }
   if (m.engine == HOST_CORE) {
     if (!slots.empty() && m.host->update_poses((int)slots.size(), slots.data(), Ow.data())) throw std::runtime_error("MapPointStore::WriteBack: bad key frame");
+    for (size_t i = 0; i < slots.size(); ++i) { std::memcpy(&m.host->Rcw[9 * (size_t)slots[i]], &R[9 * i], 36); std::memcpy(&m.host->tcw[3 * (size_t)slots[i]], &t[3 * i], 12); }
     if (!ids.empty() && m.host->set((int)ids.size(), ids.data(), pos.data(), nullptr)) throw std::runtime_error("MapPointStore::WriteBack: bad point");
   } else {
     std::lock_guard<std::mutex> lock(g_ctx_mutex);
     if (!slots.empty() && cms_kfstore_update_poses(m.store, (int)slots.size(), slots.data(), R.data(), t.data(), Ow.data()) != CMS_OK) Impl::fail("cms_kfstore_update_poses");
     if (!ids.empty() && cms_mpstore_set(m.mp, (int)ids.size(), ids.data(), pos.data(), nullptr) != CMS_OK) Impl::fail("cms_mpstore_set");
   }
+}
+
+// ---- the points' counters, MapPointCulling, TrackedMapPoints and ComputeSceneMedianDepth (csrc/cms_mpstats_core.h).  HOST_CORE goes through the
+// host build's entries on the same table (host_capi.cpp)
+extern "C" {
+int hm_mpstats_set_stats(void* mp, int n, const int* ids, const int* first_kf, const int* visible, const int* found);
+int hm_mpstats_fetch_stats(void* mp, int n, const int* ids, int* visible, int* found, int* first_kf);
+int hm_mpstats_count(void* mp, int which, int njobs, const int* off, const int* ids, const uint8_t* flag, int count_if);
+int hm_mpstats_culling(void* mp, int njobs, const int* off, const int* ids, const int* current_kf, int th_obs, int apply, uint8_t* verdict);
+int hm_mpstats_tracked_map_points(void* mp, int njobs, const int* job_member, const int* min_obs, int* count);
+int hm_mpstats_scene_median_depth(void* mp, int n, const int* slots, int q, int store, float* depth, int* n_depths);
+}
+void MapPointStore::SetStatistics(const std::vector<MapPointStats>& stats) {
+  Impl& m = *impl_;
+  // one call per combination of columns: a point names the counters it sets
+  for (int mask = 1; mask < 8; ++mask) {
+    std::vector<long> ids;
+    std::vector<int> first, vis, found;
+    for (const MapPointStats& s : stats) {
+      const int has = (s.nFirstKFid >= -1 ? 1 : 0) | (s.nVisible >= 0 ? 2 : 0) | (s.nFound >= 0 ? 4 : 0);
+      if (has != mask) continue;
+      ids.push_back(s.id); first.push_back(s.nFirstKFid); vis.push_back(s.nVisible); found.push_back(s.nFound);
+    }
+    if (ids.empty()) continue;
+    const std::vector<int> id32 = m.ids32(ids, "MapPointStore::SetStatistics");
+    const int n = (int)ids.size();
+    const int* pf = (mask & 1) ? first.data() : nullptr;
+    const int* pv = (mask & 2) ? vis.data() : nullptr;
+    const int* pn = (mask & 4) ? found.data() : nullptr;
+    if (m.engine == HOST_CORE) {
+      if (!m.host || hm_mpstats_set_stats(m.host, n, id32.data(), pf, pv, pn)) throw std::runtime_error("MapPointStore::SetStatistics: a point that was never set, an id twice or a counter out of range");
+    } else {
+      std::lock_guard<std::mutex> lock(g_ctx_mutex);
+      if (!m.mp || cms_mpstore_set_stats(m.mp, n, id32.data(), pf, pv, pn) != CMS_OK) Impl::fail("cms_mpstore_set_stats");
+    }
+  }
+}
+std::vector<MapPointStore::MapPointStats> MapPointStore::FetchStatistics(const std::vector<long>& ids) {
+  Impl& m = *impl_;
+  const int n = (int)ids.size();
+  std::vector<MapPointStats> out(ids.size());
+  if (n == 0) return out;
+  const std::vector<int> id32 = m.ids32(ids, "MapPointStore::FetchStatistics");
+  std::vector<int> vis(ids.size()), found(ids.size()), first(ids.size());
+  if (m.engine == HOST_CORE) {
+    if (!m.host || hm_mpstats_fetch_stats(m.host, n, id32.data(), vis.data(), found.data(), first.data())) throw std::runtime_error("MapPointStore::FetchStatistics: no Build yet");
+  } else {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!m.mp || cms_mpstore_fetch_stats(m.mp, n, id32.data(), vis.data(), found.data(), first.data()) != CMS_OK) Impl::fail("cms_mpstore_fetch_stats");
+  }
+  for (size_t i = 0; i < ids.size(); ++i) out[i] = MapPointStats{ids[i], first[i], vis[i], found[i]};
+  return out;
+}
+void MapPointStore::UpdateTrackStatistics(const std::vector<long>& localIds, const std::vector<unsigned char>& inView, const std::vector<long>& frameIds,
+                                          const std::vector<unsigned char>& outlier) {
+  Impl& m = *impl_;
+  if (localIds.size() != inView.size() || frameIds.size() != outlier.size()) throw std::runtime_error("MapPointStore::UpdateTrackStatistics: a flag per id");
+  struct Pass { const std::vector<long>* ids; const std::vector<unsigned char>* flag; int which, count_if; };
+  const Pass passes[2] = {{&localIds, &inView, CMS_MP_VISIBLE, 1}, {&frameIds, &outlier, CMS_MP_FOUND, 0}};
+  for (const Pass& p : passes) {
+    if (p.ids->empty()) continue;
+    std::vector<int> id32(p.ids->size());
+    for (size_t i = 0; i < p.ids->size(); ++i) {
+      const long id = (*p.ids)[i];
+      if (id < -1 || id >= m.max_points) throw std::runtime_error("MapPointStore::UpdateTrackStatistics: an id outside the table");
+      id32[i] = (int)id;
+    }
+    const int off[2] = {0, (int)id32.size()};
+    if (m.engine == HOST_CORE) {
+      if (!m.host || hm_mpstats_count(m.host, p.which, 1, off, id32.data(), p.flag->data(), p.count_if)) throw std::runtime_error("MapPointStore::UpdateTrackStatistics: a counted point that was never set");
+    } else {
+      const cms_orb_params orb = Impl::orb();
+      cms_ctx* c = SharedContext(orb.nfeatures, orb.scale_factor, orb.nlevels, orb.ini_th_fast, orb.min_th_fast);
+      std::lock_guard<std::mutex> lock(g_ctx_mutex);
+      if (!m.mp || cms_mpstore_count(m.mp, c, p.which, 1, off, id32.data(), p.flag->data(), p.count_if) != CMS_OK) Impl::fail("cms_mpstore_count");
+    }
+  }
+}
+std::vector<unsigned char> MapPointStore::MapPointCulling(std::list<long>& recentIds, int currentKFid, int thObs) {
+  Impl& m = *impl_;
+  const std::vector<long> ids(recentIds.begin(), recentIds.end());
+  std::vector<unsigned char> verdict(ids.size() + 1);
+  if (!ids.empty()) {
+    const std::vector<int> id32 = m.ids32(ids, "MapPointStore::MapPointCulling");
+    const int off[2] = {0, (int)ids.size()};
+    if (m.engine == HOST_CORE) {
+      if (!m.host || hm_mpstats_culling(m.host, 1, off, id32.data(), &currentKFid, thObs, 1, verdict.data())) throw std::runtime_error("MapPointStore::MapPointCulling: an id twice (or no Build yet)");
+    } else {
+      std::lock_guard<std::mutex> lock(g_ctx_mutex);
+      if (!m.mp || cms_mpstore_culling(m.mp, m.cv, 1, off, id32.data(), &currentKFid, thObs, 1, verdict.data()) != CMS_OK) Impl::fail("cms_mpstore_culling");
+    }
+  }
+  verdict.resize(ids.size());
+  // SetBadFlag on the views (MapPoint.cpp:115-136), then the list (LocalMapping.cpp:184-205): only a point of verdict 0 stays
+  std::set<long> bad;
+  size_t i = 0;
+  for (auto it = recentIds.begin(); it != recentIds.end(); ++i) {
+    if (verdict[i] == CMS_MP_BAD_RATIO || verdict[i] == CMS_MP_BAD_FEW_OBS) bad.insert(*it);
+    if (verdict[i] != CMS_MP_STAYS) it = recentIds.erase(it); else ++it;
+  }
+  if (!bad.empty())
+    for (KeyFrameView* k : m.members)
+      for (long& id : k->mvpMapPoints) if (id >= 0 && bad.count(id)) id = -1;
+  return verdict;
+}
+int MapPointStore::TrackedMapPoints(KeyFrameView* pKF, int minObs) {
+  Impl& m = *impl_;
+  auto it = m.pos_of.find(pKF);
+  if (it == m.pos_of.end()) throw std::runtime_error("MapPointStore::TrackedMapPoints: not a key frame of the last Build");
+  const int member = it->second;
+  int count = 0;
+  if (m.engine == HOST_CORE) {
+    if (!m.host || hm_mpstats_tracked_map_points(m.host, 1, &member, &minObs, &count)) throw std::runtime_error("MapPointStore::TrackedMapPoints: no Build yet");
+  } else {
+    const cms_orb_params orb = Impl::orb();
+    cms_ctx* c = SharedContext(orb.nfeatures, orb.scale_factor, orb.nlevels, orb.ini_th_fast, orb.min_th_fast);
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!m.cv || cms_covis_tracked_map_points(m.cv, c, 1, &member, &minObs, &count) != CMS_OK) Impl::fail("cms_covis_tracked_map_points");
+  }
+  return count;
+}
+float MapPointStore::ComputeSceneMedianDepth(KeyFrameView* pKF, int q) {
+  Impl& m = *impl_;
+  auto it = m.pos_of.find(pKF);
+  if (it == m.pos_of.end()) throw std::runtime_error("MapPointStore::ComputeSceneMedianDepth: not a key frame of the last Build");
+  const int slot = it->second;      // (Build puts member i into slot i)
+  float depth = -1.0f;
+  int n = 0;
+  if (m.engine == HOST_CORE) {
+    if (!m.host || hm_mpstats_scene_median_depth(m.host, 1, &slot, q, 0, &depth, &n)) throw std::runtime_error("MapPointStore::ComputeSceneMedianDepth: q < 1 (or no Build yet)");
+  } else {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    if (!m.mp || cms_kfstore_scene_median_depth(m.store, m.mp, 1, &slot, q, 0, &depth, &n) != CMS_OK) Impl::fail("cms_kfstore_scene_median_depth");
+  }
+  return depth;
 }
 
 void Optimizer::LocalBundleAdjustment(MapPointStore& mps, MapPointStore::BAWindow* win, bool* pbStopFlag) {

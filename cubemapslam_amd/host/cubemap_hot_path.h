@@ -20,6 +20,7 @@
 #ifndef CMS_CUBEMAP_HOT_PATH_H
 #define CMS_CUBEMAP_HOT_PATH_H
 #include <functional>
+#include <list>
 #include <map>
 #include <string>
 #include <set>
@@ -509,6 +510,26 @@ class MapPointStore {
   // SetPose / SetWorldPos of an optimised window (Optimizer.cpp:432-450): the local key frames' Tcw and the points' positions through float
   // (Converter.cpp:53-104), into the views and into the engine's store (cms_kfstore_update_poses, cms_mpstore_set)
   void WriteBack(const BAWindow& window);
+
+  // ---- the points' counters and what reads them (csrc/cms_mpstats_core.h; DEVICE: cms_mpstore_set_stats / count / culling,
+  // cms_covis_tracked_map_points, cms_kfstore_scene_median_depth; HOST_CORE: hm_mpstats_* on the same table)
+  // mnFirstKFid, mnVisible and mnFound of points that were set (a negative nVisible / nFound leaves the counter; nFirstKFid < -1 leaves it)
+  struct MapPointStats { long id; int nFirstKFid, nVisible, nFound; };
+  void SetStatistics(const std::vector<MapPointStats>& stats);
+  std::vector<MapPointStats> FetchStatistics(const std::vector<long>& ids);
+  // The statistics loop of Tracking::TrackLocalMap and SearchLocalPoints for one frame: IncreaseVisible() for the local points with inView[i] != 0
+  // (Tracking.cpp:808, :829), IncreaseFound() for the frame's points (-1: none) with outlier[i] == 0 (:698).  Either list may be empty
+  void UpdateTrackStatistics(const std::vector<long>& localIds, const std::vector<unsigned char>& inView, const std::vector<long>& frameIds,
+                             const std::vector<unsigned char>& outlier);
+  // LocalMapping::MapPointCulling (LocalMapping.cpp:175-206) on mlpRecentAddedMapPoints as ids: one culling call with apply, then the list handling
+  // of :184-205 (a point that is bad, became bad or is three key frames old leaves the list).  SetBadFlag reaches the engine's store and the views
+  // of the last Build (mvpMapPoints -> -1).  Returns the verdicts in the list's order before the call
+  std::vector<unsigned char> MapPointCulling(std::list<long>& recentIds, int currentKFid, int thObs = 2);
+  // KeyFrame::TrackedMapPoints(minObs) (KeyFrame.cpp:276-301) of a key frame of the last Build, on the rows as they were then
+  int TrackedMapPoints(KeyFrameView* pKF, int minObs);
+  // KeyFrame::ComputeSceneMedianDepth(q) (KeyFrame.cpp:1064-1094) from the key frame's current row in the store and the points that were set;
+  // -1 when it sees none
+  float ComputeSceneMedianDepth(KeyFrameView* pKF, int q = 2);
 
  private:
   struct Impl;

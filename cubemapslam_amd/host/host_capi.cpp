@@ -9,6 +9,7 @@
 #include "../csrc/cms_kfdb_core.h"
 #include "../csrc/cms_covis_core.h"
 #include "../csrc/cms_mappoint_core.h"
+#include "../csrc/cms_mpstats_core.h"
 #include "../csrc/cms_ba_window_core.h"
 using namespace CubemapSLAM;
 
@@ -998,6 +999,175 @@ extern "C" int hm_mpstore_fetch(void* mp, int n, const int* ids, float* pos, flo
   HM_TRY(return static_cast<CmsMpHostStore*>(mp)->fetch(n, ids, pos, normal, min_dist, max_dist, desc, best_member, best_feature);)
 }
 
+// ---- Map-point statistics (tests/mpstats_hostlib.py): the host build of csrc/cms_mpstats_core.h on the same handle, the definition of record of
+// cms_mpstore_set_stats / add_stats / fetch_stats / count / culling, cms_covis_tracked_map_points and cms_kfstore_scene_median_depth.  0 or -1
+// (CMS_ERR_ARG: nothing was written).
+static bool hm_mpstats_off_ok(int njobs, const int* off) {
+  if (njobs < 0 || (njobs > 0 && (!off || off[0] != 0))) return false;
+  for (int j = 0; j < njobs; ++j) if (off[j + 1] < off[j]) return false;
+  return true;
+}
+// has hm_mpstore_build succeeded yet?  (the device entries refuse a query without an index)
+static bool hm_mpstats_built(const CmsMpHostStore& s) { return !s.cv.index.seg.empty(); }
+// the full pose of slots (hm_mpstore_put leaves Rcw = I, tcw = -Ow; hm_mpstore_update_poses moves only Ow)
+extern "C" int hm_mpstats_update_poses(void* mp, int n, const int* slots, const float* Rcw, const float* tcw, const float* Ow) {
+  HM_TRY(
+    CmsMpHostStore& s = *static_cast<CmsMpHostStore*>(mp);
+    if (s.update_poses(n, slots, Ow)) return -1;
+    for (int i = 0; i < n; ++i) { memcpy(&s.Rcw[(size_t)slots[i] * 9], Rcw + 9 * (size_t)i, 36); memcpy(&s.tcw[(size_t)slots[i] * 3], tcw + 3 * (size_t)i, 12); }
+    return 0;)
+}
+extern "C" int hm_mpstats_set_stats(void* mp, int n, const int* ids, const int* first_kf, const int* visible, const int* found) {
+  HM_TRY(
+    CmsMpHostStore& s = *static_cast<CmsMpHostStore*>(mp);
+    if (n < 0 || (n > 0 && !ids) || !s.ids_ok(n, ids)) return -1;
+    for (int i = 0; i < n; ++i) {
+      if (!(s.rows[(size_t)ids[i]].state & 1)) return -1;
+      if ((first_kf && first_kf[i] < -1) || (visible && visible[i] < 1) || (found && found[i] < 0)) return -1;
+    }
+    for (int i = 0; i < n; ++i) {
+      CmsMpHostStore::Row& r = s.rows[(size_t)ids[i]];
+      if (first_kf) r.first_kf = first_kf[i];
+      if (visible) r.visible = visible[i];
+      if (found) r.found = found[i];
+    }
+    return 0;)
+}
+extern "C" int hm_mpstats_add_stats(void* mp, int n, const int* ids, const int* d_visible, const int* d_found) {
+  HM_TRY(
+    CmsMpHostStore& s = *static_cast<CmsMpHostStore*>(mp);
+    if (n < 0 || (n > 0 && !ids) || !s.ids_ok(n, ids)) return -1;
+    for (int i = 0; i < n; ++i)
+      if (!(s.rows[(size_t)ids[i]].state & 1) || (d_visible && d_visible[i] < 0) || (d_found && d_found[i] < 0)) return -1;
+    for (int i = 0; i < n; ++i) {
+      CmsMpHostStore::Row& r = s.rows[(size_t)ids[i]];
+      if (d_visible) r.visible += d_visible[i];
+      if (d_found) r.found += d_found[i];
+    }
+    return 0;)
+}
+extern "C" int hm_mpstats_fetch_stats(void* mp, int n, const int* ids, int* visible, int* found, int* first_kf) {
+  HM_TRY(
+    const CmsMpHostStore& s = *static_cast<CmsMpHostStore*>(mp);
+    if (n < 0 || (n > 0 && !ids)) return -1;
+    for (int i = 0; i < n; ++i) if (!s.id_ok(ids[i])) return -1;
+    for (int i = 0; i < n; ++i) {
+      const CmsMpHostStore::Row& r = s.rows[(size_t)ids[i]];
+      if (visible) visible[i] = r.visible;
+      if (found) found[i] = r.found;
+      if (first_kf) first_kf[i] = r.first_kf;
+    }
+    return 0;)
+}
+extern "C" int hm_mpstats_count(void* mp, int which, int njobs, const int* off, const int* ids, const uint8_t* flag, int count_if) {
+  HM_TRY(
+    CmsMpHostStore& s = *static_cast<CmsMpHostStore*>(mp);
+    if ((which != CMS_MP_VISIBLE && which != CMS_MP_FOUND) || !hm_mpstats_off_ok(njobs, off)) return -1;
+    const int T = njobs > 0 ? off[njobs] : 0;
+    if (T > 0 && !ids) return -1;
+    auto counted = [&](int i) { return ids[i] >= 0 && (!flag || (flag[i] != 0) == (count_if != 0)); };
+    for (int i = 0; i < T; ++i) {
+      if (ids[i] < -1 || ids[i] >= (int)s.rows.size()) return -1;
+      if (counted(i) && !(s.rows[(size_t)ids[i]].state & 1)) return -1;
+    }
+    for (int i = 0; i < T; ++i)
+      if (counted(i)) ++(which == CMS_MP_VISIBLE ? s.rows[(size_t)ids[i]].visible : s.rows[(size_t)ids[i]].found);
+    return 0;)
+}
+extern "C" int hm_mpstats_culling(void* mp, int njobs, const int* off, const int* ids, const int* current_kf, int th_obs, int apply, uint8_t* verdict) {
+  HM_TRY(
+    CmsMpHostStore& s = *static_cast<CmsMpHostStore*>(mp);
+    if (th_obs < 0 || !hm_mpstats_off_ok(njobs, off) || !hm_mpstats_built(s)) return -1;
+    const int n = njobs > 0 ? off[njobs] : 0;
+    if ((njobs > 0 && !current_kf) || (n > 0 && (!ids || !verdict)) || !s.ids_ok(n, ids)) return -1;
+    const CmsCovisHost& ix = s.cv.index;
+    for (int j = 0; j < njobs; ++j)
+      for (int i = off[j]; i < off[j + 1]; ++i) {
+        const CmsMpHostStore::Row& r = s.rows[(size_t)ids[i]];
+        const int u = ix.find(ids[i]);
+        const int n_obs = u < 0 ? 0 : ix.seg[(size_t)u + 1] - ix.seg[(size_t)u];
+        verdict[i] = (uint8_t)((r.state & 1) ? cms_mpstats_verdict(r.found, r.visible, r.first_kf, n_obs, current_kf[j], th_obs) : CMS_MP_ALREADY_BAD);
+      }
+    if (!apply) return 0;
+    for (int i = 0; i < n; ++i) {      // MapPoint::SetBadFlag (MapPoint.cpp:115-136)
+      if (verdict[i] != CMS_MP_BAD_RATIO && verdict[i] != CMS_MP_BAD_FEW_OBS) continue;
+      const int u = ix.find(ids[i]);
+      if (u >= 0)
+        for (int e = ix.seg[(size_t)u]; e < ix.seg[(size_t)u + 1]; ++e) {
+          std::vector<int>& row = s.cv.slots[(size_t)s.member_slot[(size_t)ix.obs[(size_t)e].member]].mp;
+          const size_t f = (size_t)ix.obs[(size_t)e].feat;
+          if (f < row.size() && row[f] == ids[i]) row[f] = -1;      // (an entry changed since the build is left alone)
+        }
+      s.rows[(size_t)ids[i]] = CmsMpHostStore::Row();
+    }
+    return 0;)
+}
+extern "C" int hm_mpstats_tracked_map_points(void* mp, int njobs, const int* job_member, const int* min_obs, int* count) {
+  HM_TRY(
+    const CmsMpHostStore& s = *static_cast<CmsMpHostStore*>(mp);
+    const CmsCovisHost& ix = s.cv.index;
+    if (njobs < 0 || (njobs > 0 && (!job_member || !min_obs || !count)) || !hm_mpstats_built(s)) return -1;
+    for (int j = 0; j < njobs; ++j) if (job_member[j] < 0 || job_member[j] >= ix.n_members) return -1;
+    for (int j = 0; j < njobs; ++j) {
+      int c = 0;
+      for (int id : ix.mp[(size_t)job_member[j]]) {
+        if (id < 0) continue;
+        const int u = ix.find(id);      // (an id of the snapshot is in the index; the test keeps the function on its own feet)
+        const int n_obs = u < 0 ? 0 : ix.seg[(size_t)u + 1] - ix.seg[(size_t)u];
+        if (min_obs[j] <= 0 || n_obs >= min_obs[j]) ++c;
+      }
+      count[j] = c;
+    }
+    return 0;)
+}
+extern "C" int hm_mpstats_scene_median_depth(void* mp, int n, const int* slots, int q, int store, float* depth, int* n_depths) {
+  HM_TRY(
+    CmsMpHostStore& s = *static_cast<CmsMpHostStore*>(mp);
+    if (n < 0 || q < 1 || (n > 0 && (!slots || !depth || !n_depths))) return -1;
+    std::vector<uint8_t> seen(s.cv.slots.size(), 0);
+    for (int i = 0; i < n; ++i) {
+      if (!s.cv.slot_ok(slots[i]) || !s.cv.slots[(size_t)slots[i]].used || seen[(size_t)slots[i]]) return -1;
+      seen[(size_t)slots[i]] = 1;
+    }
+    for (int i = 0; i < n; ++i) {
+      const size_t sl = (size_t)slots[i];
+      std::vector<uint32_t> key;
+      for (int id : s.cv.slots[sl].mp)
+        if (s.id_ok(id) && (s.rows[(size_t)id].state & 1)) key.push_back(cms_mpstats_depth_key(cms_mpstats_depth(&s.Rcw[sl * 9], &s.tcw[sl * 3], s.rows[(size_t)id].pos)));
+      n_depths[i] = (int)key.size();
+      if (key.empty()) { depth[i] = -1.0f; continue; }
+      // the smallest key v with #(key <= v) > idx, by bisection on the 32 bits: the rule as cms_mpstats_core.h words it
+      const int idx = cms_mpstats_depth_index((int)key.size(), q);
+      uint32_t lo = 0u, hi = 0xFFFFFFFFu;
+      while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        int c = 0;
+        for (uint32_t k : key) c += k <= mid;
+        if (c > idx) hi = mid; else lo = mid + 1u;
+      }
+      depth[i] = cms_mpstats_depth_from_key(lo);
+      if (store) s.median[sl] = depth[i];
+    }
+    return 0;)
+}
+// a slot's mp row as the stand-in of the store holds it now (n entries: what hm_mpstore_put gave)
+extern "C" int hm_mpstats_fetch_mp(void* mp, int slot, int cap, int* out, int* n_out) {
+  HM_TRY(
+    const CmsMpHostStore& s = *static_cast<CmsMpHostStore*>(mp);
+    if (!s.cv.slot_ok(slot) || !s.cv.slots[(size_t)slot].used) return -1;
+    const std::vector<int>& row = s.cv.slots[(size_t)slot].mp;
+    *n_out = (int)row.size();
+    for (size_t f = 0; f < row.size() && f < (size_t)cap; ++f) out[f] = row[f];
+    return 0;)
+}
+extern "C" int hm_mpstats_fetch_median(void* mp, int slot, float* median) {
+  HM_TRY(
+    const CmsMpHostStore& s = *static_cast<CmsMpHostStore*>(mp);
+    if (!s.cv.slot_ok(slot)) return -1;
+    *median = s.median[(size_t)slot];
+    return 0;)
+}
+
 // ---- Local BA window (tests/ba_window_hostlib.py): the host build of csrc/cms_ba_window_core.h, the definition of record of cms_covis_local_ba_windows.
 // One handle holds what the walk reads: the index over n_members rows (n_feat[m] features each; mp, octave, key-point x / y and the rays' z
 // concatenated), the members' Rcw (9 floats) and tcw (3), the table's rows that hold a position (n_pos ids with 3 floats each, ids below max_points),
@@ -1115,6 +1285,38 @@ extern "C" int hm_ba_window_mirror(int engine, int n_kf, const int* n_feat, cons
     return 0;)
 }
 
+// the key-frame views of the two MapPointStore mirrors below: n_kf key frames of n_feat[k] features (mp, octave and descriptor rows concatenated -- desc
+// may be NULL: zeros --, Tcw 16 floats each); returns the longest row
+static int hm_mirror_views(int n_kf, const int* n_feat, const int* mp, const int* octave, const uint8_t* desc, const float* Tcw16, std::vector<KeyFrameView>& kfs,
+                           std::vector<KeyFrameView*>& members) {
+  kfs.assign((size_t)n_kf, KeyFrameView());
+  members.clear();
+  int max_feat = 1;
+  size_t at = 0;
+  for (int k = 0; k < n_kf; ++k) {
+    KeyFrameView& v = kfs[(size_t)k];
+    const int n = n_feat[k];
+    max_feat = std::max(max_feat, n);
+    v.mnId = k + 1;
+    v.mDescriptors = cv::Mat::zeros(std::max(n, 1), 32, cv::CV_8U);
+    v.mvKeys.resize((size_t)n);
+    cv::Vec3f ray;
+    ray.v[0] = 0.f; ray.v[1] = 0.f; ray.v[2] = 1.f;
+    v.mvKeyRays.assign((size_t)n, ray);
+    v.mvpMapPoints.resize((size_t)n);
+    for (int f = 0; f < n; ++f) {
+      v.mvKeys[(size_t)f].pt.x = 10.f + (float)(f % 100); v.mvKeys[(size_t)f].pt.y = 10.f + (float)(f / 100); v.mvKeys[(size_t)f].octave = octave[at + (size_t)f];
+      v.mvpMapPoints[(size_t)f] = mp[at + (size_t)f];
+      if (desc) std::memcpy(v.mDescriptors.ptr<uint8_t>(f), desc + 32 * (at + (size_t)f), 32);
+    }
+    at += (size_t)n;
+    v.Tcw = cv::Mat::zeros(4, 4, cv::CV_32F);
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) v.Tcw.at<float>(r, c) = Tcw16[16 * (size_t)k + 4 * (size_t)r + (size_t)c];
+    members.push_back(&v);
+  }
+  return max_feat;
+}
+
 // CubemapSLAM::MapPointStore of the mirror through the named engine (0 = device, 1 = host core): n_kf key frames of n_feat[k] features (mp, octave and
 // descriptor rows concatenated, Tcw 16 floats each) are the members; n_pts points (id, position, reference key frame as an index) are set, refreshed
 // with `what` and fetched: status, normal, distances, descriptor, the best observation's key frame (index or -1) and feature per point.
@@ -1122,31 +1324,9 @@ extern "C" int hm_mpstore_mirror(int engine, int n_kf, const int* n_feat, const 
                                  const int* ids, const float* pos, const int* ref_kf, int what, uint8_t* status, float* normal, float* min_dist, float* max_dist,
                                  uint8_t* out_desc, int* best_kf, int* best_idx) {
   HM_TRY(
-    std::vector<KeyFrameView> kfs((size_t)n_kf);
+    std::vector<KeyFrameView> kfs;
     std::vector<KeyFrameView*> members;
-    int max_feat = 1;
-    size_t at = 0;
-    for (int k = 0; k < n_kf; ++k) {
-      KeyFrameView& v = kfs[(size_t)k];
-      const int n = n_feat[k];
-      max_feat = std::max(max_feat, n);
-      v.mnId = k + 1;
-      v.mDescriptors = cv::Mat::zeros(std::max(n, 1), 32, cv::CV_8U);
-      v.mvKeys.resize((size_t)n);
-      cv::Vec3f ray;
-      ray.v[0] = 0.f; ray.v[1] = 0.f; ray.v[2] = 1.f;
-      v.mvKeyRays.assign((size_t)n, ray);
-      v.mvpMapPoints.resize((size_t)n);
-      for (int f = 0; f < n; ++f) {
-        v.mvKeys[(size_t)f].pt.x = 10.f + (float)(f % 100); v.mvKeys[(size_t)f].pt.y = 10.f + (float)(f / 100); v.mvKeys[(size_t)f].octave = octave[at + (size_t)f];
-        v.mvpMapPoints[(size_t)f] = mp[at + (size_t)f];
-        std::memcpy(v.mDescriptors.ptr<uint8_t>(f), desc + 32 * (at + (size_t)f), 32);
-      }
-      at += (size_t)n;
-      v.Tcw = cv::Mat::zeros(4, 4, cv::CV_32F);
-      for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) v.Tcw.at<float>(r, c) = Tcw16[16 * (size_t)k + 4 * (size_t)r + (size_t)c];
-      members.push_back(&v);
-    }
+    const int max_feat = hm_mirror_views(n_kf, n_feat, mp, octave, desc, Tcw16, kfs, members);
     MapPointStore mps(engine ? MapPointStore::HOST_CORE : MapPointStore::DEVICE, n_kf + 1, max_feat, max_points);
     mps.Build(members);
     std::vector<MapPointStore::MapPointView> pts((size_t)n_pts);
@@ -1166,6 +1346,51 @@ extern "C" int hm_mpstore_mirror(int engine, int n_kf, const int* n_feat, const 
       std::memcpy(out_desc + 32 * (size_t)i, r.descriptor, 32);
       best_kf[i] = r.pBestKF ? (int)(r.pBestKF - kfs.data()) : -1; best_idx[i] = r.bestIdx;
     }
+    return 0;)
+}
+
+// The statistics methods of the mirror's MapPointStore through the named engine, one mapping step: Build over the key frames, SetMapPoints (every point
+// refers to key frame 0), SetStatistics(first_kf), UpdateTrackStatistics per frame (frame f: the ids [frame_off[f], frame_off[f + 1]) with their
+// in_view and outlier flags, used both as the local and as the frame's list), MapPointCulling of all points in id order with current_kf, a second
+// Build over the views as the culling left them, then TrackedMapPoints(min_obs) and ComputeSceneMedianDepth(q) of every key frame.
+// verdict / stats (first_kf, visible, found per point, after the culling) / n_left (the list's length) / mp_out (the views' rows) / tracked / depth
+extern "C" int hm_mpstats_mirror(int engine, int n_kf, const int* n_feat, const int* mp, const int* octave, const float* Tcw16, int max_points, int n_pts, const int* ids,
+                                 const float* pos, const int* first_kf, int n_frames, const int* frame_off, const int* frame_ids, const uint8_t* in_view,
+                                 const uint8_t* outlier, int current_kf, int min_obs, int q, uint8_t* verdict, int* stats, int* n_left, int* mp_out, int* tracked,
+                                 float* depth) {
+  HM_TRY(
+    std::vector<KeyFrameView> kfs;
+    std::vector<KeyFrameView*> members;
+    const int max_feat = hm_mirror_views(n_kf, n_feat, mp, octave, nullptr, Tcw16, kfs, members);
+    MapPointStore mps(engine ? MapPointStore::HOST_CORE : MapPointStore::DEVICE, n_kf + 1, max_feat, max_points);
+    mps.Build(members);
+    std::vector<MapPointStore::MapPointView> pts((size_t)n_pts);
+    std::vector<MapPointStore::MapPointStats> st((size_t)n_pts);
+    std::list<long> recent;
+    std::vector<long> lids((size_t)n_pts);
+    for (int i = 0; i < n_pts; ++i) {
+      pts[(size_t)i].id = ids[i]; lids[(size_t)i] = ids[i];
+      std::memcpy(pts[(size_t)i].pos, pos + 3 * (size_t)i, 12);
+      pts[(size_t)i].pRefKF = &kfs[0];
+      st[(size_t)i] = MapPointStore::MapPointStats{ids[i], first_kf[i], -1, -1};
+      recent.push_back(ids[i]);
+    }
+    mps.SetMapPoints(pts);
+    mps.SetStatistics(st);
+    for (int f = 0; f < n_frames; ++f) {
+      const int a = frame_off[f], b = frame_off[f + 1];
+      const std::vector<long> fid(frame_ids + a, frame_ids + b);
+      mps.UpdateTrackStatistics(fid, std::vector<unsigned char>(in_view + a, in_view + b), fid, std::vector<unsigned char>(outlier + a, outlier + b));
+    }
+    const std::vector<unsigned char> v = mps.MapPointCulling(recent, current_kf);
+    std::copy(v.begin(), v.end(), verdict);
+    *n_left = (int)recent.size();
+    const std::vector<MapPointStore::MapPointStats> after = mps.FetchStatistics(lids);
+    for (int i = 0; i < n_pts; ++i) { stats[3 * i] = after[(size_t)i].nFirstKFid; stats[3 * i + 1] = after[(size_t)i].nVisible; stats[3 * i + 2] = after[(size_t)i].nFound; }
+    size_t at = 0;
+    for (int k = 0; k < n_kf; ++k) for (long id : kfs[(size_t)k].mvpMapPoints) mp_out[at++] = (int)id;
+    mps.Build(members);
+    for (int k = 0; k < n_kf; ++k) { tracked[k] = mps.TrackedMapPoints(&kfs[(size_t)k], min_obs); depth[k] = mps.ComputeSceneMedianDepth(&kfs[(size_t)k], q); }
     return 0;)
 }
 

@@ -1187,6 +1187,57 @@ int cms_covis_local_ba_windows(cms_covis* cv, cms_mpstore* mp, int njobs, const 
                                cms_ba_window_counts* counts, int* kf_member, int* point_id, double* poses, uint8_t* fixed, double* points, int* e_pose,
                                int* e_point, double* e_obs, double* e_invsig2, int8_t* e_face, int* e_feat);
 
+/* ---- Map-point statistics on the resident stores: LocalMapping::MapPointCulling (src/LocalMapping.cpp:175-206), KeyFrame::TrackedMapPoints
+ * (src/KeyFrame.cpp:276-301), KeyFrame::ComputeSceneMedianDepth (:1064-1094) and the mnVisible / mnFound counting of Tracking (src/Tracking.cpp:698,
+ * :808, :829).  The definition of record is csrc/cms_mpstats_core.h (DESIGN.md "Map-point statistics on the device"): one source, built for the host
+ * (hm_mpstats_* of libcubemapslam_host.so) and for the kernels.  Counts and verdicts equal the host core's by value, depths bit for bit.
+ *
+ * A table row carries three more columns: mnVisible, mnFound and mnFirstKFid.  An empty row holds (1, 1, -1), what both MapPoint constructors leave;
+ * cms_mpstore_erase restores it.  Every entry checks all its arguments on the host before anything is enqueued: a refused call writes nothing. */
+#define CMS_MP_VISIBLE 1      /* Tracking.cpp:808 and :829: IncreaseVisible() */
+#define CMS_MP_FOUND 2        /* Tracking.cpp:698 (and :264): IncreaseFound() */
+/* Absolute values for n set rows (none named twice); any array may be NULL = unchanged.  visible >= 1, found >= 0, first_kf >= -1, otherwise
+ * CMS_ERR_ARG.  mnFirstKFid at creation; the counters when a map is loaded.  One kernel reading the pinned record ring of cms_mpstore_set,
+ * asynchronous on the store's stream. */
+int cms_mpstore_set_stats(cms_mpstore* mp, int n, const int* ids, const int* first_kf, const int* visible, const int* found);
+/* MapPoint::Replace's transfer (MapPoint.cpp:209-210) and any host-side IncreaseVisible(n) / IncreaseFound(n): adds; d_* >= 0, NULL = 0.
+ * Asynchronous like cms_mpstore_set_stats. */
+int cms_mpstore_add_stats(cms_mpstore* mp, int n, const int* ids, const int* d_visible, const int* d_found);
+/* The three columns as the table holds them (any output may be NULL); synchronous; an empty row reads (1, 1, -1). */
+int cms_mpstore_fetch_stats(cms_mpstore* mp, int n, const int* ids, int* visible, int* found, int* first_kf);
+/* The per-frame counting of all frames of a tick.  Job j owns the entries [off[j], off[j + 1]) of ids and of flag; entry i adds 1 to column `which`
+ * of row ids[i] iff ids[i] >= 0 and (flag == NULL or (flag[i] != 0) == (count_if != 0)).  A frame's kp_mp row can be passed as it lies (-1 = no
+ * point): for CMS_MP_VISIBLE the local ids given to cms_search_local_points_ids with its in_view and count_if = 1, for CMS_MP_FOUND the frame's ids
+ * with the pose optimiser's outlier flags and count_if = 0.  An id listed twice counts twice.  CMS_ERR_ARG with nothing written: an id >=
+ * max_points or < -1, a counted id whose row was never set.  One launch for all jobs (global atomicAdd), ids and flags read from a pinned ring of
+ * four blocks; asynchronous on src's stream (src on the store's device), which waits on the device for the table's last write.  Every later entry
+ * on the store's stream that reads or resets the counters (culling, fetch_stats, set_stats, add_stats, set, erase) waits on the device for the
+ * call's event: a culling issued after a count returns sees that count completely.  Calls from two frame contexts may overlap. */
+int cms_mpstore_count(cms_mpstore* mp, cms_ctx* src, int which, int njobs, const int* off, const int* ids, const uint8_t* flag, int count_if);
+/* Job j is one MapPointCulling call: mlpRecentAddedMapPoints as ids in [off[j], off[j + 1]) and mpCurrentKeyFrame->mnId in current_kf[j]; no id
+ * twice in the call.  verdict[i] is cms_mpstats_verdict on the row's counters and Observations(id) of the index's snapshot (0 for an id the index
+ * does not know): 1 bad by the found ratio, 2 bad by too few observations two key frames on (th_obs: 2 in the reference), 3 leaves the list alive,
+ * 0 stays; 4 for an empty row (already bad).  Verdicts of one call do not influence one another.  With apply != 0 the call performs
+ * MapPoint::SetBadFlag (MapPoint.cpp:115-136) for verdicts 1 and 2: -1 into the mp row of every observing slot at the recorded feature, only where
+ * the row still holds the id, then the table row is emptied (counters included) and refused by later consumers like an erased one.  The index is
+ * unchanged and stale until the next cms_covis_build (cms_covis_culling's contract).  One launch, one wavefront per id.  Synchronous with one wait
+ * on the store's stream, behind the last build and the last count; holds both handles' mutexes.  CMS_ERR_ARG with nothing written: no index
+ * built, an index of another store, an id out of range or named twice, th_obs < 0. */
+int cms_mpstore_culling(cms_mpstore* mp, cms_covis* cv, int njobs, const int* off, const int* ids, const int* current_kf, int th_obs, int apply,
+                        uint8_t* verdict);
+/* count[j] = KeyFrame::TrackedMapPoints(min_obs[j]) of member job_member[j]: the features of the member's snapshot row with an id >= 0 and, when
+ * min_obs[j] > 0, Observations(id) >= min_obs[j].  A bad point is one that has left the rows.  One wavefront per job.  Stream rules of
+ * cms_covis_votes. */
+int cms_covis_tracked_map_points(cms_covis* cv, cms_ctx* src, int njobs, const int* job_member, const int* min_obs, int* count);
+/* KeyFrame::ComputeSceneMedianDepth(q) of n slots (each once, none empty): the depths (cms_mpstats_depth of the slot's Rcw, tcw and the row's position) of every feature whose
+ * CURRENT mp row entry names an id with a position in the table (an id whose table row is empty takes no part: the reference does not test isBad()
+ * here), the element at index (n_depths - 1) / q in ascending order, selected by bisection on the depth key (-0.0f before +0.0f).  A slot without a
+ * depth returns -1.0f and n_depths 0.  q >= 1.  With store != 0 every slot with a depth gets the value as its median_depth, as by
+ * cms_kfstore_update(..., &median, NULL): the next cms_kfstore_create_new_map_points reads it.  One workgroup per slot, the keys in LDS.
+ * Synchronous with one wait on the store's stream, behind pending cms_kfstore_update_poses, cms_kfstore_update_map_points and cms_mpstore_set;
+ * holds the table's mutex. */
+int cms_kfstore_scene_median_depth(cms_kfstore* st, cms_mpstore* mp, int n, const int* slots, int q, int store, float* depth, int* n_depths);
+
 #ifdef __cplusplus
 }
 #endif

@@ -437,7 +437,10 @@ void ReleaseKeyFrame(cms_kfstore* store, KeyFrame* pKF) {
   b.slot.erase(it);
 }
 
-int CreateNewMapPoints(cms_kfstore* store, KeyFrame* pCurrentKF, Map* pMap, std::vector<MapPoint*>& newPoints) {
+namespace {
+// mps == NULL: every neighbour's median depth is computed on the host and handed over; otherwise ONE cms_kfstore_scene_median_depth call with
+// store = 1 for the current key frame and its neighbours, from the rows just sent and the table's positions
+int create_new_map_points(cms_kfstore* store, cms_mpstore* mps, KeyFrame* pCurrentKF, Map* pMap, std::vector<MapPoint*>& newPoints) {
   StoreBook& b = book(store);
   const int cur = slot_of(b, pCurrentKF);
   if (cur < 0) throw std::runtime_error("Hip::CreateNewMapPoints: the current key frame is not resident (Hip::ProcessNewKeyFrame first)");
@@ -449,10 +452,10 @@ int CreateNewMapPoints(cms_kfstore* store, KeyFrame* pCurrentKF, Map* pMap, std:
     // poses, median depths and map-point slots may have changed since the key frame entered the store (local BA, Fuse, culling)
     float R[9], t[3], O[3]; std::vector<int> mp;
     pose_floats(k, R, t, O); mp_slots(k, mp);
-    const float md = k->ComputeSceneMedianDepth(2);
+    const float md = mps ? 0.0f : k->ComputeSceneMedianDepth(2);
     {
       std::lock_guard<std::mutex> lk(b.mu);
-      check(cms_kfstore_update(store, s, R, t, O, &md, mp.data()), "cms_kfstore_update");
+      check(cms_kfstore_update(store, s, R, t, O, mps ? nullptr : &md, mp.data()), "cms_kfstore_update");
       b.dev_mp[s] = mp;
     }
     neigh.push_back(k); neigh_slot.push_back(s);
@@ -465,6 +468,13 @@ int CreateNewMapPoints(cms_kfstore* store, KeyFrame* pCurrentKF, Map* pMap, std:
     b.dev_mp[cur] = mp;
   }
   if (neigh.empty()) return 0;
+  if (mps) {
+    std::vector<int> slots(1, cur);
+    slots.insert(slots.end(), neigh_slot.begin(), neigh_slot.end());
+    std::vector<float> depth(slots.size());
+    std::vector<int> n_depths(slots.size());
+    check(cms_kfstore_scene_median_depth(store, mps, (int)slots.size(), slots.data(), 2, 1, depth.data(), n_depths.data()), "cms_kfstore_scene_median_depth");
+  }
   const int cap = pCurrentKF->N;
   const int neigh_off[2] = {0, (int)neigh.size()};
   int n_new = 0;
@@ -487,6 +497,13 @@ int CreateNewMapPoints(cms_kfstore* store, KeyFrame* pCurrentKF, Map* pMap, std:
     newPoints.push_back(pMP);
   }
   return n_new;
+}
+}  // namespace
+int CreateNewMapPoints(cms_kfstore* store, KeyFrame* pCurrentKF, Map* pMap, std::vector<MapPoint*>& newPoints) {
+  return create_new_map_points(store, nullptr, pCurrentKF, pMap, newPoints);
+}
+int CreateNewMapPoints(cms_kfstore* store, cms_mpstore* mps, KeyFrame* pCurrentKF, Map* pMap, std::vector<MapPoint*>& newPoints) {
+  return create_new_map_points(store, mps, pCurrentKF, pMap, newPoints);
 }
 
 namespace {
@@ -977,6 +994,118 @@ void LocalBundleAdjustment(cms_kfstore* store, cms_covis* covis, cms_mpstore* mp
   }
   UpdateKeyFramePoses(store, moved);                                // the resident copies: ONE cms_kfstore_update_poses, ONE cms_mpstore_set
   SetMapPoints(mps, pts);
+}
+
+// ------------------------------------------------------------------------------------------------ Map-point statistics on the device
+void SetMapPointStatistics(cms_mpstore* mps, const std::vector<MapPoint*>& vpMPs) {
+  MpBook& m = mp_book(mps);
+  std::lock_guard<std::mutex> lk(m.mu);
+  std::vector<int> ids, first;
+  std::set<int> named;
+  for (MapPoint* p : vpMPs) {
+    if (!p || p->isBad()) continue;
+    const int r = row_of(m, p);
+    if (r < 0 || !m.set.count(r) || !named.insert(r).second) continue;
+    ids.push_back(r); first.push_back((int)p->mnFirstKFid);
+  }
+  if (ids.empty()) return;
+  check(cms_mpstore_set_stats(mps, (int)ids.size(), ids.data(), first.data(), nullptr, nullptr), "cms_mpstore_set_stats");
+}
+
+void UpdateTrackStatistics(cms_ctx* frameCtx, cms_mpstore* mps, Frame& F, const std::vector<MapPoint*>& vpLocalMapPoints, const std::vector<uint8_t>& inView) {
+  if (vpLocalMapPoints.size() != inView.size()) throw std::runtime_error("Hip::UpdateTrackStatistics: a flag per local point");
+  MpBook& m = mp_book(mps);
+  std::lock_guard<std::mutex> lk(m.mu);
+  // IncreaseVisible() of the local points that were in view (Tracking.cpp:829) and of the frame's own points (:808: they are in view by construction)
+  std::vector<int> ids;
+  std::vector<uint8_t> flag;
+  for (size_t i = 0; i < vpLocalMapPoints.size(); ++i) {
+    MapPoint* p = vpLocalMapPoints[i];
+    const int r = (p && !p->isBad()) ? row_of(m, p) : -1;
+    ids.push_back(r >= 0 && m.set.count(r) ? r : -1); flag.push_back(inView[i]);
+    if (ids.back() >= 0 && inView[i]) p->IncreaseVisible();
+  }
+  // IncreaseFound() of the frame's points the pose optimisation kept (:698)
+  std::vector<int> fids((size_t)F.N, -1);
+  std::vector<uint8_t> outlier((size_t)F.N, 1);
+  for (int i = 0; i < F.N; ++i) {
+    MapPoint* p = F.mvpMapPoints[i];
+    if (!p) continue;
+    const int r = row_of(m, p);
+    if (r < 0 || !m.set.count(r)) continue;
+    fids[(size_t)i] = r; outlier[(size_t)i] = F.mvbOutlier[i] ? 1 : 0;
+    if (!F.mvbOutlier[i]) p->IncreaseFound();
+  }
+  const int off_l[2] = {0, (int)ids.size()}, off_f[2] = {0, F.N};
+  if (!ids.empty()) check(cms_mpstore_count(mps, frameCtx, CMS_MP_VISIBLE, 1, off_l, ids.data(), flag.data(), 1), "cms_mpstore_count");
+  if (F.N > 0) check(cms_mpstore_count(mps, frameCtx, CMS_MP_FOUND, 1, off_f, fids.data(), outlier.data(), 0), "cms_mpstore_count");
+}
+
+std::vector<uint8_t> MapPointCulling(cms_kfstore* store, cms_covis* covis, cms_mpstore* mps, std::list<MapPoint*>& lpRecentAddedMapPoints, KeyFrame* pCurrentKF) {
+  MpBook& m = mp_book(mps);
+  // held to the end: the frame thread's Hip::UpdateTrackStatistics reads m.set, and a row the device has emptied must have left it before that
+  // thread can name the row again
+  std::lock_guard<std::mutex> lk(m.mu);
+  typedef std::list<MapPoint*>::iterator It;
+  std::vector<It> at;            // the list entries that go to the device, in list order
+  std::vector<int> ids, place;   // their rows, and their positions in the list
+  std::set<int> named;
+  int n_list = 0;
+  for (It it = lpRecentAddedMapPoints.begin(); it != lpRecentAddedMapPoints.end();) {
+    if ((*it)->isBad()) { it = lpRecentAddedMapPoints.erase(it); continue; }      // :187-190
+    const int r = row_of(m, *it);
+    // a point the table does not hold (mnId beyond it, or never set) cannot be judged here: it stays in the list, as the reference keeps every point
+    // that is not bad, and gets verdict 0
+    if (r >= 0 && m.set.count(r) && named.insert(r).second) { at.push_back(it); ids.push_back(r); place.push_back(n_list); }
+    ++n_list; ++it;
+  }
+  std::vector<uint8_t> verdict((size_t)n_list, 0);
+  if (ids.empty()) return verdict;
+  std::vector<uint8_t> v(ids.size());
+  const int off[2] = {0, (int)ids.size()};
+  const int current = (int)pCurrentKF->mnId;
+  check(cms_mpstore_culling(mps, covis, 1, off, ids.data(), &current, 2, 1, v.data()), "cms_mpstore_culling");
+  // the pointer graph follows: SetBadFlag on the host objects of verdicts 1 and 2, the list as LocalMapping.cpp:191-205 leaves it
+  StoreBook& b = book(store);
+  for (size_t i = 0; i < ids.size(); ++i) {
+    MapPoint* p = *at[i];
+    verdict[(size_t)place[i]] = v[i];
+    if (v[i] == 1 || v[i] == 2) {
+      {      // the device has already written -1 where the rows named the point: the bridge's copy of the rows follows
+        std::lock_guard<std::mutex> lkb(b.mu);
+        const std::map<KeyFrame*, size_t> obs = p->GetObservations();
+        for (std::map<KeyFrame*, size_t>::const_iterator o = obs.begin(); o != obs.end(); ++o) {
+          const int s = slot_locked(b, o->first);
+          if (s < 0) continue;
+          std::vector<int>& row = b.dev_mp[s];
+          if (o->second < row.size() && row[o->second] == ids[i]) row[o->second] = -1;
+        }
+      }
+      p->SetBadFlag();
+      m.set.erase(ids[i]); m.has_desc.erase(ids[i]); m.has_normal.erase(ids[i]);
+    }
+    if (v[i] == 1 || v[i] == 2 || v[i] == 3) lpRecentAddedMapPoints.erase(at[i]);      // (4, an empty row behind a live point, cannot come: m.set says the row is set)
+  }
+  return verdict;
+}
+
+int TrackedMapPoints(cms_covis* covis, cms_ctx* frameCtx, KeyFrame* pKF, int minObs) {
+  CovisBook& c = covis_book(covis);
+  int member;
+  { std::lock_guard<std::mutex> lk(c.mu); member = member_of(c, pKF); }
+  if (member < 0) throw std::runtime_error("Hip::TrackedMapPoints: the key frame is not a member of the last Hip::BuildCovisibility");
+  int count = 0;
+  check(cms_covis_tracked_map_points(covis, frameCtx, 1, &member, &minObs, &count), "cms_covis_tracked_map_points");
+  return count;
+}
+
+float ComputeSceneMedianDepth(cms_kfstore* store, cms_mpstore* mps, KeyFrame* pKF, int q) {
+  const int slot = slot_of(book(store), pKF);
+  if (slot < 0) throw std::runtime_error("Hip::ComputeSceneMedianDepth: the key frame is not resident");
+  float depth = -1.0f;
+  int n = 0;
+  check(cms_kfstore_scene_median_depth(store, mps, 1, &slot, q, 0, &depth, &n), "cms_kfstore_scene_median_depth");
+  return depth;
 }
 
 // ------------------------------------------------------------------------------------------------ Tracking: SearchByBoW on resident key frames

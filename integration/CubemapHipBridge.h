@@ -3,6 +3,7 @@
 // Not built in this repository (syntax-checked against the reference's headers by tests/test_integration_syntax.py), see integration/README.md.  Each function is the new body of the reference function it names.
 #ifndef CUBEMAP_HIP_BRIDGE_H
 #define CUBEMAP_HIP_BRIDGE_H
+#include <list>
 #include <map>
 #include <set>
 #include <vector>
@@ -125,6 +126,31 @@ Connections SearchInNeighbors(cms_kfstore* store, cms_covis* covis, cms_mpstore*
 // Every local point must have been set (Hip::SetMapPoints); the table's normals and bounds are refreshed by the caller behind its next
 // BuildCovisibility, which sees the erased observations.
 void LocalBundleAdjustment(cms_kfstore* store, cms_covis* covis, cms_mpstore* mps, KeyFrame* pKF, bool* pbStopFlag, Map* pMap);
+// ---- Map-point statistics on the device (cms_mpstore_set_stats / count / culling, cms_covis_tracked_map_points, cms_kfstore_scene_median_depth): the
+// table carries mnVisible, mnFound and mnFirstKFid next to the points' rows.
+// mnFirstKFid of points that are set (one asynchronous cms_mpstore_set_stats): behind Hip::SetMapPoints for the points CreateNewMapPoints made.  The
+// counters need no call: a fresh row holds mnVisible = mnFound = 1 like a fresh MapPoint, and both follow through Hip::UpdateTrackStatistics.
+void SetMapPointStatistics(cms_mpstore* mps, const std::vector<MapPoint*>& vpMPs);
+// The statistics of one tracked frame, two asynchronous cms_mpstore_count calls on the frame context's stream: IncreaseVisible() for the local points
+// Hip::SearchLocalPoints projected, inView[i] = mbTrackInView of vpLocalMapPoints[i] (Tracking.cpp:808, :829: list the frame's own points with a 1),
+// and IncreaseFound() for mCurrentFrame's points that are no outliers (:698).  The host objects are counted too, so that GetFoundRatio() stays in step.
+void UpdateTrackStatistics(cms_ctx* frameCtx, cms_mpstore* mps, Frame& F, const std::vector<MapPoint*>& vpLocalMapPoints, const std::vector<uint8_t>& inView);
+// LocalMapping::MapPointCulling (LocalMapping.cpp:175-206): ONE cms_mpstore_culling call with apply for mlpRecentAddedMapPoints and mpCurrentKeyFrame,
+// then SetBadFlag on the host objects of verdicts 1 and 2 -- the pointer graph stays in step with the rows the device has already cleared -- and the list
+// handling of :184-205.  `covis`: the index of the step's BuildCovisibility (Observations() is its snapshot).  Bad points leave the list first (:187-190);
+// a point the table does not hold (its mnId is beyond maxPoints, or Hip::SetMapPoints never named it) cannot be judged on the device and STAYS in the
+// list with verdict 0.  Returns one verdict per point of the list as it stood after the bad ones left.  The table's book is locked for the whole
+// call, so Hip::UpdateTrackStatistics on the frame thread never names a row this call has just emptied.
+std::vector<uint8_t> MapPointCulling(cms_kfstore* store, cms_covis* covis, cms_mpstore* mps, std::list<MapPoint*>& lpRecentAddedMapPoints, KeyFrame* pCurrentKF);
+// KeyFrame::TrackedMapPoints(minObs) (KeyFrame.cpp:276-301) of a member of the last BuildCovisibility: Tracking::NeedNewKeyFrame's nRefMatches, on the
+// frame thread's stream
+int TrackedMapPoints(cms_covis* covis, cms_ctx* frameCtx, KeyFrame* pKF, int minObs);
+// KeyFrame::ComputeSceneMedianDepth(q) (KeyFrame.cpp:1064-1094) of a resident key frame from its row on the device and the table's positions; -1 when
+// no point of the row has a position (Tracking.cpp:520 tests medianDepth < 0)
+float ComputeSceneMedianDepth(cms_kfstore* store, cms_mpstore* mps, KeyFrame* pKF, int q);
+// Hip::CreateNewMapPoints with the median depths of the current key frame and its neighbours taken on the device, in ONE
+// cms_kfstore_scene_median_depth call with store = 1 in front of the triangulation, instead of pKF2->ComputeSceneMedianDepth(2) per neighbour
+int CreateNewMapPoints(cms_kfstore* store, cms_mpstore* mps, KeyFrame* pCurrentKF, Map* pMap, std::vector<MapPoint*>& newPoints);
 // ---- Tracking's SearchByBoW(KeyFrame*, Frame&, ...) (ORBMatcher.cpp:409-539) against key frames resident in `store`, on the FRAME thread: F is the frame
 // `frameCtx` extracted last (slot 0 of its batch) after F.ComputeBoW().  The slot comes from the store's KeyFrame* -> slot book; a key-frame feature takes
 // part where the slot's map-point entry (as ProcessNewKeyFrame / CreateNewMapPoints last wrote it) is set and GetMapPointMatches() still holds a point

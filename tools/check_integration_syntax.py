@@ -50,7 +50,9 @@ def main(ref_inc):
                                                ("CubemapHipBridge.cpp", "cms_kfstore_update_map_points(store, (int)up_slot.size(),", "cms_kfstore_update_map_points(store,"),
                                                ("CubemapHipBridge.cpp", "cms_mpstore_refresh(mps, covis, (int)n,", "cms_mpstore_refresh(mps, (int)n,"),
                                                ("CubemapHipBridge.cpp", "cms_search_local_points_ids(ctx, 0, pose15, mps, n,", "cms_search_local_points_ids(ctx, 0, pose15, n,"),
-                                               ("CubemapHipBridge.cpp", "cms_kfstore_fuse_search_sets_ids(store, mps, 2, set_off,", "cms_kfstore_fuse_search_sets_ids(store, 2, set_off,"))):
+                                               ("CubemapHipBridge.cpp", "cms_kfstore_fuse_search_sets_ids(store, mps, 2, set_off,", "cms_kfstore_fuse_search_sets_ids(store, 2, set_off,"),
+                                               ("CubemapHipBridge.cpp", "cms_mpstore_culling(mps, covis, 1, off,", "cms_mpstore_culling(mps, 1, off,"),
+                                               ("CubemapHipBridge.cpp", "cms_kfstore_scene_median_depth(store, mps, 1, &slot,", "cms_kfstore_scene_median_depth(store, 1, &slot,"))):
             d = os.path.join(td, "broken_%d" % i)
             shutil.copytree(os.path.join(ROOT, "integration"), d)
             src = open(os.path.join(d, fname)).read()
